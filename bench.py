@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py - env-steps/sec of the batched step()/reset() hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N --steps K --warmup W] [--workload C2|C3|C4|C5] [--mode step|rollout]
+    python bench.py [--gpus N --steps K --warmup W] [--workload C2|C3|C4|C5] [--mode step|rollout] [--full] [--dump-outputs DIR]
 
 A "step" is ONE batched env step over the whole resident batch: the step kernel advances every env, resets the ones
 whose episode ended (done, or horizon H = 100) and writes the new observation batch.  Inputs (state + int32 actions)
@@ -16,8 +16,16 @@ else it reads RANK / LOCAL_RANK / WORLD_SIZE from the environment.
 Timed region: barrier + torch.cuda.synchronize(), clock, K steps, torch.cuda.synchronize(), clock, barrier; `value` uses the MAX
 over ranks of that span (= until the slowest rank had finished its K steps).
 
-The JSON line carries, besides the contract's fields,
-  roofline        algorithmic bytes per env-step (2*S*S + 12*K + 45) * envs per launch / the step kernel's
+A plain run sets up, warms up (a short device-clock warm-up on a scratch handle, W steps, one untimed replay of the timed region's
+hipGraph where there is one), times exactly K steps once, and
+prints the line: `value` / `ms_per_step` are that one region.  --dump-outputs DIR then writes what the timed path left for its caller
+after its last step (the observation batch, reward / done / info; the lidar rows with --lidar) as DIR/<name>.npy, float32 for 8- and
+16-bit data and float64 for 32-bit data, rank 0 only, at most 64 MB (a fixed, seeded sample of envs where the batch is larger).
+
+--full adds everything else, each measured after the dump: `value` becomes the median of the contract region and R repeats of it, and
+the JSON line carries, besides the contract's fields,
+  roofline        (in a plain run too, from its one region, without `floor`)
+                  algorithmic bytes per env-step (2*S*S + 12*K + 45) * envs per launch / the step kernel's
                   average launch duration, measured with a HIP event pair on the kernel's own stream, vs 8 TB/s HBM peak
                   (`frac`), and the same on the wall-clock ms_per_step the driver can check (`frac_wall`)
   repeats         the K-step region run R = 5 more times after the contract's one: median / min / max (device and wall)
@@ -141,6 +149,35 @@ def c1_single_env(budget_s=2.0):
     return out
 
 
+DUMP_MAX_BYTES = 64 * 10 ** 6          # the whole dump, .npy headers included
+
+
+def dump_outputs(v, out_dir):
+    """What the timed path left for its caller after its last step - the device-resident arrays device_observation(),
+    device_outputs() and, with the fused lidar on, lidar_observation(device=True) hand out - as float32 (8- / 16-bit data) or
+    float64 (32-bit data) .npy files.  A batch larger than DUMP_MAX_BYTES is cut to the same seeded, sorted sample of envs in
+    every array.  Only device pointers are read: the handle's host mirrors are not created, so later measurements are unchanged."""
+    import numpy as np
+    v.sync()
+    arrays = dict(v.device_observation(), **v.device_outputs())
+    if v.lidar is not None:
+        rows = v.lidar_observation(device=True)
+        if v.lidar_packed:
+            arrays['lidar_beams'], arrays['lidar_inventory'] = rows
+        else:
+            arrays['lidar'] = rows
+    arrays = {k: t.cpu().numpy() for k, t in arrays.items()}
+    wide = lambda a: np.float64 if a.dtype.itemsize > 2 else np.float32
+    n = v.num_envs
+    per_env = sum(a[:1].size * np.dtype(wide(a)).itemsize for a in arrays.values())
+    keep = min(n, (DUMP_MAX_BYTES - 4096 * len(arrays)) // per_env)
+    idx = np.sort(np.random.RandomState(20240607).choice(n, keep, replace=False)) if keep < n else slice(None)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a[idx], dtype=wide(a)))
+    return {'dir': out_dir, 'arrays': sorted(arrays), 'envs': int(keep), 'of_envs': n}
+
+
 def self_launch(args):
     """`python bench.py --gpus N` outside torchrun: start the N ranks as CHILD processes (this process has not touched the
     GPU and never will), relay their output, exit with their code."""
@@ -173,7 +210,7 @@ def main():
                          'low power state, and 5 warm-up steps are 25 us); 0 = off')
     ap.add_argument('--lidar', default='', choices=['', 'int32', 'int16', 'packed'],
                     help='run the MAIN timed region with the fused LidarInFront observation in this row format (profiling runs; the default line reports it in `lidar`)')
-    ap.add_argument('--repeats', type=int, default=5, help='run the K-step region this many more times after the contract region (median / spread in `repeats`)')
+    ap.add_argument('--repeats', type=int, default=5, help='--full: run the K-step region this many more times after the contract region (median / spread in `repeats`)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-stagger', action='store_true', help='skip the staggered-episode-ends side measurement')
     ap.add_argument('--no-side', action='store_true', help='skip every side measurement (fused rollout, API mode, C1, stagger): tuning runs')
@@ -181,6 +218,10 @@ def main():
     ap.add_argument('--dist-backend', default='nccl', choices=['nccl', 'gloo'],
                     help='gloo + --single-device: rehearse the N > 1 code path on a one-GPU box (every rank on cuda:0)')
     ap.add_argument('--single-device', action='store_true')
+    ap.add_argument('--full', action='store_true',
+                    help='also run the repeats, the cold region, the launch floor, every side measurement and the CPU baseline (a plain run times K steps once)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default='',
+                    help="write what the timed path's last step left for its caller as DIR/<name>.npy (float32 / float64, at most 64 MB)")
     args = ap.parse_args()
 
     world = int(os.environ.get('WORLD_SIZE', 1))
@@ -222,7 +263,7 @@ def main():
         """reset(), then start every episode so that the timed region holds auto-reset work whatever K is: with K < H the
         horizon falls in the middle of the timed launches (synchronized over the batch: BASELINE's loop resets all envs together)."""
         v.reset()
-        hit = warmup + max(1, steps // 2)                  # 1-based batched step at which step_count reaches H
+        hit = warmup + g_steps + max(1, steps // 2)        # 1-based batched step at which step_count reaches H (g_steps: the primed graph)
         s0 = (HORIZON - hit) % HORIZON if steps < HORIZON else 0
         if s0:
             v.set_state(0, step_count=np.full(n, s0, np.int32))
@@ -237,7 +278,7 @@ def main():
         # the time is up.  The measured handle `v` is not touched by either: its W warm-up steps and K timed steps follow as the contract says.
         from gym_novel_gridworlds_amd import VecNovelGridworld
         scratch = VecNovelGridworld(spec=spec, num_envs=n, seed=99, autoreset=True, horizon=HORIZON, device=local_rank)
-        if args.mode == 'step' and not args.no_side:
+        if args.full and args.mode == 'step' and not args.no_side:
             g0 = torch.Generator(device='cuda')
             g0.manual_seed(ACTION_SEED + 31 + rank)
             kc = min(steps, 200)
@@ -274,7 +315,6 @@ def main():
             v.step_device_many(acts0.data_ptr(), n, 100)
             v.sync()                                       # (the host reads the refills' reports between calls)
         del acts0
-    start_episodes()
     GRAPH_MAX = 2048                      # kernel nodes per graph; longer runs replay it (its action rows repeat)
     # ONE graph launch enqueues the whole region (15 us of host time for 20 launches; an eager launch costs ~3.3 us of host time),
     # but the FIRST launch of an instantiated graph costs ~70 us more than a later one (20 steps fence to fence: 187 us against
@@ -289,8 +329,9 @@ def main():
     # ran at 3.5 - 5.5 us per step on the device's own clock (the device waiting for launches), twelve replays at 3.86 (+ the regions that hold the
     # all-env reset: 5.4): `repeats.regions_in_order`.  `value` is the median of the contract region and the repeats either way.
     use_graph = args.mode == 'step' and args.launch == 'graph' and steps >= 16
+    side = args.full and world == 1 and not args.no_side
     ptrs = []
-    if args.mode == 'step' or not args.no_side:
+    if args.mode == 'step' or side:
         # i.i.d. uniform int32 actions over len(actions_id), seed 1234 (+rank), resident in HBM before the timed region
         g = torch.Generator(device='cuda')
         g.manual_seed(ACTION_SEED + rank)
@@ -301,6 +342,8 @@ def main():
     g_steps = 0
     if use_graph:
         g_steps = min(steps, GRAPH_MAX) & ~1
+    start_episodes()
+    if use_graph:
         v.graph_build(ptrs[warmup], n, g_steps)
 
     def run_eager(k, row0):
@@ -346,6 +389,8 @@ def main():
             v.rollout(warmup, ACTION_SEED, 0)
     else:
         run_eager(warmup, -1)
+        if use_graph:
+            v.graph_launch(1)             # the first replay of an instantiated graph costs ~70 us more than later ones: not in the timed region
     fence()
     ep_before = episode0()
     fence()
@@ -369,11 +414,12 @@ def main():
         t[rank] = dt_rank
         dist.all_reduce(t, op=dist.ReduceOp.SUM)
         per_rank = [round(n * steps / float(x), 1) for x in t.tolist()]
+    dumped = dump_outputs(v, args.dump_outputs) if args.dump_outputs and rank == 0 else None
 
     # the same K-step region R more times (device already in the state the contract region left it in: episodes keep ending
     # every H steps): one 100-us sample says little about a 4-us step
     repeats = None
-    if args.repeats > 0 and args.mode == 'step':
+    if args.full and args.repeats > 0 and args.mode == 'step':
         wall, dev = [], []
         for _ in range(args.repeats):
             fence()
@@ -453,30 +499,31 @@ def main():
             roofline['traffic'], roofline['traffic_source'] = tr, src
             roofline['traffic_provenance'] = pmc.get('_provenance', 'constant of the kernel measured in an earlier profiling run (profiles/pmc_traffic.json)')
             roofline['traffic_frac'] = round(tr / (ms_step * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-        try:
-            import ctypes as C
-            from gym_novel_gridworlds_amd import _cabi
-            fl = _cabi.lib().ngw_debug_launch_floor
-            fl.argtypes, fl.restype = [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_double)], C.c_int
-            us_g, us_e = C.c_double(0), C.c_double(0)
-            kfl = g_steps if use_graph else max(steps, 64)
-            _cabi.check(fl(v._h, int(kfl), 1, C.byref(us_g)))            # replayed from a graph: the device-side boundary between dependent launches
-            _cabi.check(fl(v._h, int(kfl), 0, C.byref(us_e)))            # issued eagerly: what the HOST can sustain (a region below 100 steps is launched this way)
-            wl = pmc.get('%s_wave_life' % args.workload, pmc.get('C2_wave_life', {}))
-            life_us = wl.get('median_us_net_of_stamps', wl.get('median_us'))   # (net of what the eight clock stamps themselves cost a wave)
-            # the device needs the boundary + a wave's life per launch; an eager loop cannot go faster than the host issues launches
-            floor_us = max(us_g.value + (life_us or 0.0), 0.0 if use_graph else us_e.value)
-            roofline['floor'] = {'empty_kernel_launch_period_us': {'hipGraph replay': round(us_g.value, 4), 'eager': round(us_e.value, 4)},
-                                 'launch_form_of_this_region': 'hipGraph replay' if use_graph else 'eager',
-                                 'launches': int(kfl), 'stamped_wave_life_us': life_us, 'stamped_wave_life_us_with_stamp_cost': wl.get('median_us'), 'wave_life_source': wl.get('source'),
-                                 'floor_us': round(floor_us, 4),
-                                 'what': 'floor = max(empty-kernel launch period replayed from a graph (the shortest of a few regions of the same length as the timed one) + the median life of a wave of the step kernel (in-kernel clock '
-                                         'stamps, profiles/), and - for an eagerly launched region - the empty-kernel launch period of the host loop): EMPTY kernels '
-                                         'in the step kernel\'s launch shape, issued back to back on this handle in this run (HIP event pair).  What one launch per '
-                                         'step() costs when nothing but latency is left'}
-            roofline['frac_of_floor'] = round(floor_us / (dev_step * 1e3), 4)
-        except Exception as ex:       # noqa: BLE001 - a diagnostics entry point: its absence must not cost the line
-            roofline['floor'] = {'error': repr(ex)}
+        if args.full:                 # a launch-floor probe of its own
+            try:
+                import ctypes as C
+                from gym_novel_gridworlds_amd import _cabi
+                fl = _cabi.lib().ngw_debug_launch_floor
+                fl.argtypes, fl.restype = [C.c_void_p, C.c_int32, C.c_int, C.POINTER(C.c_double)], C.c_int
+                us_g, us_e = C.c_double(0), C.c_double(0)
+                kfl = g_steps if use_graph else max(steps, 64)
+                _cabi.check(fl(v._h, int(kfl), 1, C.byref(us_g)))            # replayed from a graph: the device-side boundary between dependent launches
+                _cabi.check(fl(v._h, int(kfl), 0, C.byref(us_e)))            # issued eagerly: what the HOST can sustain (a region below 100 steps is launched this way)
+                wl = pmc.get('%s_wave_life' % args.workload, pmc.get('C2_wave_life', {}))
+                life_us = wl.get('median_us_net_of_stamps', wl.get('median_us'))   # (net of what the eight clock stamps themselves cost a wave)
+                # the device needs the boundary + a wave's life per launch; an eager loop cannot go faster than the host issues launches
+                floor_us = max(us_g.value + (life_us or 0.0), 0.0 if use_graph else us_e.value)
+                roofline['floor'] = {'empty_kernel_launch_period_us': {'hipGraph replay': round(us_g.value, 4), 'eager': round(us_e.value, 4)},
+                                     'launch_form_of_this_region': 'hipGraph replay' if use_graph else 'eager',
+                                     'launches': int(kfl), 'stamped_wave_life_us': life_us, 'stamped_wave_life_us_with_stamp_cost': wl.get('median_us'), 'wave_life_source': wl.get('source'),
+                                     'floor_us': round(floor_us, 4),
+                                     'what': 'floor = max(empty-kernel launch period replayed from a graph (the shortest of a few regions of the same length as the timed one) + the median life of a wave of the step kernel (in-kernel clock '
+                                             'stamps, profiles/), and - for an eagerly launched region - the empty-kernel launch period of the host loop): EMPTY kernels '
+                                             'in the step kernel\'s launch shape, issued back to back on this handle in this run (HIP event pair).  What one launch per '
+                                             'step() costs when nothing but latency is left'}
+                roofline['frac_of_floor'] = round(floor_us / (dev_step * 1e3), 4)
+            except Exception as ex:       # noqa: BLE001 - a diagnostics entry point: its absence must not cost the line
+                roofline['floor'] = {'error': repr(ex)}
     else:
         # T steps per launch keep the state on chip: HBM sees a few bytes per env-step, the kernel is bound by instruction issue
         roofline = {'bound': 'issue', 'achieved': None, 'peak': None, 'unit': None, 'frac': None, 'traffic': None, 'kernel': 'ngw_rollout_lean',
@@ -485,7 +532,6 @@ def main():
         if tr:
             roofline['traffic'], roofline['traffic_source'] = tr, src
 
-    side = world == 1 and not args.no_side
     # the other mode of the same workload, reported beside the headline (fused T-step rollout: SURVEY.md §8(d))
     fused = None
     if args.mode == 'step' and side:
@@ -635,7 +681,7 @@ def main():
 
     # the one collective of the path, timed on its own: pack launch per rank + gather to rank 0 + unpack launch there
     gather = None
-    if world > 1 or not args.no_side:
+    if args.full and (world > 1 or not args.no_side):
         offs = sv.payload_layout()
         sv.gather_observation(dst=0)                          # allocates the payload / receive / global buffers
         fence()
@@ -694,7 +740,9 @@ def main():
             line['api_mode'] = api
         if c1:
             line['c1_single_env'] = c1
-        if world == 1 and not args.no_cpu_baseline:
+        if dumped:
+            line['dumped_outputs'] = dumped
+        if args.full and world == 1 and not args.no_cpu_baseline:
             cb = cpu_baseline(spec)
             line['cpu_baseline'] = {'value': round(cb['allcores']['value'], 1), 'unit': 'env-steps/s',
                                     'cores': cb['allcores']['cores'], 'kind': 'port', 'sample': cb['allcores']['sample'],

@@ -202,9 +202,9 @@ def test_dist_module_has_no_device_wide_synchronisation():
 
 def test_bench_starts_its_own_ranks():
     """`python bench.py --gpus 2` outside torchrun: the parent spawns the ranks before it touches a GPU; rank 0's line
-    reports both ranks, resets inside the timed region and the gather leg."""
+    reports both ranks, resets inside the timed region and the gather leg (--full)."""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--dist-backend', 'gloo', '--single-device', '--workload', 'C4',
-           '--steps', '40', '--warmup', '5', '--no-cpu-baseline', '--no-side']
+           '--steps', '40', '--warmup', '5', '--no-cpu-baseline', '--no-side', '--full']
     env = dict(os.environ)
     env.pop('RANK', None)
     env.pop('WORLD_SIZE', None)

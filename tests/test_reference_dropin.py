@@ -1,9 +1,9 @@
-"""The drop-in boundary against the LIVE reference (CPU; skipped where /root/reference is absent, like the fixture-integrity test).
+"""The drop-in boundary against the reference (CPU), replayed from tapes of the reference side (tests/golden/dropin_*.json.gz, written
+by `tests/dropin_driver.py ... --record`, which runs the live reference beside this package and checks every step as it records).
 
-Two differential checks the golden fixtures cannot make (tests/dropin_driver.py has the details; it runs in a subprocess because the
-reference needs the stand-in `gym` package on the path, which then also becomes this package's adapter base class):
-  * the reference's OWN wrapper classes (inject_novelty, LimitActions, LidarInFront, AgentMap) stacked unchanged on this package's
-    single-env adapter, against the same stack on the reference env - 15 stacks x 600 steps;
+Two differential checks the golden fixtures cannot make (tests/dropin_driver.py has the details; it runs in a subprocess):
+  * this package's wrapper classes (inject_novelty, LimitActions, LidarInFront, AgentMap) stacked on its single-env adapter, against
+    the same stack of the reference's classes on the reference env - 15 stacks x 600 steps;
   * randomised configurations without a fixture (env id x map size x one or two novelties per case), this package's inject_novelty
     against the reference's; argument errors must match text for text."""
 import os
@@ -13,9 +13,6 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REFERENCE = '/root/reference'
-pytestmark = pytest.mark.skipif(not os.path.isdir(os.path.join(REFERENCE, 'gym_novel_gridworlds')),
-                                reason='the reference is only present in the build container')
 
 
 JOBS = {'wrappers': ('wrappers', 2024, 600), 'random2024': ('random', 2024, 24, 300), 'random77': ('random', 77, 24, 300)}
@@ -25,8 +22,9 @@ JOBS = {'wrappers': ('wrappers', 2024, 600), 'random2024': ('random', 2024, 24, 
 def runs():
     """The three driver runs side by side (each a single-threaded Python loop of ~1 minute): started together, collected as needed."""
     env = dict(os.environ, PYTHONDONTWRITEBYTECODE='1', MPLBACKEND='Agg', OMP_NUM_THREADS='1',
-               PYTHONPATH=os.pathsep.join([os.path.join(ROOT, 'oracle', 'gym_shim'), REFERENCE, ROOT, os.path.join(ROOT, 'tests')]))
-    procs = {k: subprocess.Popen([sys.executable, os.path.join(ROOT, 'tests', 'dropin_driver.py')] + [str(a) for a in args], env=env, cwd=ROOT,
+               PYTHONPATH=os.pathsep.join([ROOT, os.path.join(ROOT, 'tests')]))
+    procs = {k: subprocess.Popen([sys.executable, os.path.join(ROOT, 'tests', 'dropin_driver.py')] + [str(a) for a in args] +
+                                 ['--replay', os.path.join(ROOT, 'tests', 'golden', 'dropin_%s.json.gz' % k)], env=env, cwd=ROOT,
                                  stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True) for k, args in JOBS.items()}
     done = {}
 
@@ -43,7 +41,7 @@ def runs():
             p.kill()
 
 
-def test_reference_wrapper_classes_run_unchanged_on_the_adapter(runs):
+def test_wrapper_stacks_on_the_adapter_match_the_reference(runs):
     out = runs('wrappers')
     last = out.strip().splitlines()[-1].split()
     assert last[0] == 'WRAPPERS_OK' and int(last[1]) >= 8 and int(last[3]) >= 4800, out[-600:]     # >= 8 novelties x 600 steps

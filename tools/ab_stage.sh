@@ -6,7 +6,7 @@ for W in C2 C4 C2@16384 C2@4096 C2@64; do
   WL=${W%@*}
   for NS in 0 100; do
     export NGW_NOSTAGE=$NS      # 0: staged at every size the LDS takes; 100: in place from 10 x 10 up
-    timeout -k 10 200 python bench.py --workload $WL $ENVS --steps 1000 --warmup 100 --no-side --no-cpu-baseline --repeats 3 > $OUT/ab_stage_${W}_$NS.json 2> $OUT/ab_stage_${W}_$NS.err
+    timeout -k 10 200 python bench.py --full --workload $WL $ENVS --steps 1000 --warmup 100 --no-side --no-cpu-baseline --repeats 3 > $OUT/ab_stage_${W}_$NS.json 2> $OUT/ab_stage_${W}_$NS.err
     python - <<PY
 import json
 d = json.load(open('$OUT/ab_stage_${W}_$NS.json'))

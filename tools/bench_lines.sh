@@ -1,8 +1,8 @@
 #!/bin/bash
 # The bench lines of a round: the driver's form (20 eager steps after 5) and the default (1000 replayed steps), both with every side measurement.
 OUT=gpurun_out/${ROUND:-r04}; mkdir -p $OUT
-timeout -k 10 400 python bench.py --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { tail -5 $OUT/bench_driver.err; exit 1; }
-timeout -k 10 400 python bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full --steps 20 --warmup 5 > $OUT/bench_driver.json 2> $OUT/bench_driver.err || { tail -5 $OUT/bench_driver.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -5 $OUT/bench_default.err; exit 1; }
 python - <<PY
 import json
 for f in ('bench_driver', 'bench_default'):

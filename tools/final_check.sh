@@ -6,9 +6,9 @@ ROUND=${1:-r04}; OUT=gpurun_out/$ROUND; mkdir -p $OUT
 timeout -k 10 700 python -m pytest tests -x -q -m gpu > $OUT/gpu_suite_final.log 2>&1 || { tail -20 $OUT/gpu_suite_final.log; exit 1; }
 tail -2 $OUT/gpu_suite_final.log
 timeout -k 10 120 python -c "import __graft_entry__ as g; g.smoke()" || exit 1
-timeout -k 10 300 python bench.py > $OUT/bench_final.log 2>&1 || { tail -5 $OUT/bench_final.log; exit 1; }
+timeout -k 10 300 python bench.py --full > $OUT/bench_final.log 2>&1 || { tail -5 $OUT/bench_final.log; exit 1; }
 grep "^{" $OUT/bench_final.log | tail -1 > $OUT/bench_final.json
-timeout -k 10 200 python bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_final.log 2>&1 || { tail -5 $OUT/bench_driver_final.log; exit 1; }
+timeout -k 10 200 python bench.py --full --gpus 1 --steps 20 --warmup 5 > $OUT/bench_driver_final.log 2>&1 || { tail -5 $OUT/bench_driver_final.log; exit 1; }
 grep "^{" $OUT/bench_driver_final.log | tail -1 > $OUT/bench_driver_final.json
 python - "$OUT" <<'PY'
 import json, sys

@@ -7,15 +7,15 @@ ROUND=${1:-r04}
 OUT=gpurun_out/matrix_$ROUND; rm -rf $OUT; mkdir -p $OUT
 make -C gym_novel_gridworlds_amd/csrc stamps > $OUT/stamps_build.log 2>&1 || { echo "stamps build failed"; tail -5 $OUT/stamps_build.log; }
 for W in C2 C3 C4 C5; do
-  timeout -k 10 300 python bench.py --workload $W > $OUT/bench_$W.log 2>&1 || echo "bench $W failed"
+  timeout -k 10 300 python bench.py --full --workload $W > $OUT/bench_$W.log 2>&1 || echo "bench $W failed"
   grep '^{' $OUT/bench_$W.log | tail -1 > $OUT/bench_$W.json
 done
-timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_C2_driver_style.log 2>&1; grep '^{' $OUT/bench_C2_driver_style.log | tail -1 > $OUT/bench_C2_driver_style.json
+timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline > $OUT/bench_C2_driver_style.log 2>&1; grep '^{' $OUT/bench_C2_driver_style.log | tail -1 > $OUT/bench_C2_driver_style.json
 for W in C4 C5; do
-  timeout -k 10 300 python bench.py --gpus 2 --dist-backend gloo --single-device --workload $W --no-cpu-baseline --steps 400 > $OUT/bench_2rank_$W.log 2>&1; grep '^{' $OUT/bench_2rank_$W.log | tail -1 > $OUT/bench_2rank_$W.json
+  timeout -k 10 300 python bench.py --full --gpus 2 --dist-backend gloo --single-device --workload $W --no-cpu-baseline --steps 400 > $OUT/bench_2rank_$W.log 2>&1; grep '^{' $OUT/bench_2rank_$W.log | tail -1 > $OUT/bench_2rank_$W.json
 done
 for W in X1 X2 X3; do   # wrapper predicates (FireWall, FenceRestriction, Crate): high episode churn, adaptive prepared episodes
-  timeout -k 10 300 python bench.py --workload $W --no-cpu-baseline > $OUT/bench_$W.log 2>&1; grep '^{' $OUT/bench_$W.log | tail -1 > $OUT/bench_$W.json
+  timeout -k 10 300 python bench.py --full --workload $W --no-cpu-baseline > $OUT/bench_$W.log 2>&1; grep '^{' $OUT/bench_$W.log | tail -1 > $OUT/bench_$W.json
 done
 NGW_HOST_DELTA=0 timeout -k 10 200 python tools/api_mode_rate.py > $OUT/api_full_copy.log 2>&1
 timeout -k 10 200 python tools/api_mode_rate.py > $OUT/api_delta.log 2>&1
