@@ -25,7 +25,8 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_pack_layout', 'ngw_pack_obs', 'ngw_unpack_obs', 'ngw_rollout_outputs', 'ngw_episode_stats', 'ngw_host_step_layout', 'ngw_step_device_many',
            'ngw_set_reset_prefetch_depth', 'ngw_get_reset_prefetch_depth', 'ngw_stream_order', 'ngw_host_mirror_invalidate', 'ngw_reset_host',
            'ngw_lidar_row_layout', 'ngw_step_kernel_info', 'ngw_set_terminal_capture', 'ngw_get_terminal_obs', 'ngw_terminal_device_ptrs',
-           'ngw_host_step_layout_packed', 'ngw_step_host_packed', 'ngw_lidar_host_rows']
+           'ngw_host_step_layout_packed', 'ngw_step_host_packed', 'ngw_lidar_host_rows',
+           'ngw_set_action_mask', 'ngw_action_mask', 'ngw_get_action_mask', 'ngw_action_mask_device_ptr']
 
 _lib = None
 
@@ -147,6 +148,11 @@ def lib():
         L.ngw_episode_stats.argtypes = [vp, vp, vp, vp, vp, C.c_int]
     if hasattr(L, 'ngw_host_step_layout'):
         L.ngw_host_step_layout.argtypes = [vp, C.POINTER(u64)]
+    if hasattr(L, 'ngw_set_action_mask'):
+        L.ngw_set_action_mask.argtypes = [vp, C.c_int]
+        L.ngw_action_mask.argtypes = [vp]
+        L.ngw_get_action_mask.argtypes = [vp, vp]
+        L.ngw_action_mask_device_ptr.argtypes = [vp, C.POINTER(vp)]
     L.ngw_host_alloc.argtypes = [u64]
     L.ngw_host_alloc.restype = vp
     L.ngw_host_free.argtypes = [vp]

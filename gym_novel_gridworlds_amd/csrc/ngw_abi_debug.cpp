@@ -51,6 +51,9 @@ int ngw_debug_set_stamps(ngw_handle* h, void* stamps_dev) {
  * setting it adapts between 2 and 32 steps to how fast episodes end. */
 int ngw_debug_refill_cadence(ngw_handle* h) { return h ? (h->prefetch_every > 0 ? h->cadence : 0) : -1; }
 
+/* Diagnostics: how many times the one-env handle's resident step loop (ngw_solo.inc) has been launched since the handle was created. */
+long long ngw_debug_solo_starts(ngw_handle* h) { return h ? h->solo_starts : -1; }
+
 /* Diagnostics: resets that found no prepared episode (stale row) and ran the placement loop inside a step or rollout launch
  * since prepared episodes were switched on; -1 = off.  Waits for the stream. */
 long long ngw_debug_slow_resets(ngw_handle* h) {

@@ -707,6 +707,7 @@ int ngw_set_state(ngw_handle* h, int64_t first, int64_t count, const int8_t* map
     if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     h->solo_mirror_valid = false;
     h->mirror_valid = false;
+    h->act_mask_fresh = false;
     if (map) h->brd_dirty = true;                    // (boards mode: the bit rows are rebuilt before the next step launch)
     H2D(h->b.map + f * S2, map, n * S2);
     H2D(h->b.loc + f * 2, loc, n * 2 * sizeof(int32_t));

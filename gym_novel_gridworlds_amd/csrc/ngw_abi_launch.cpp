@@ -147,6 +147,7 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
     if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     h->solo_mirror_valid = false;                     // (a per-launch step / reset refreshes the WHOLE mirror itself; the loop's host side starts from a copy)
     h->mirror_valid = false;                          // (ngw_step_host's delta path sets it again after its own launch)
+    h->act_mask_fresh = false;                        // (every launch here changes the state; a step with masks on recomputes them below)
     NgwLaunch a = h->proto;
     a.b = h->b;
     a.mode = mode;
@@ -170,12 +171,16 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
         h->brd_dirty = false;
     }
     bool fast_took = false;
+    // action masks of the post-step state: fused into the plain step kernels (both forms), the standalone kernel behind the others
+    const bool want_mask = mode == NGW_MODE_STEP && h->act_mask_on && !h->act_mask_defer && h->act_mask;
+    bool fused_mask = false;
     if (mode == NGW_MODE_RESET) { if (int rc = launch_reset_fast(h, NGW_MODE_RESET, mask_dev, &taken)) return rc; fast_took = taken; }
     if (!taken && mode == NGW_MODE_STEP && h->nostage && (!h->lidar_fused || boards)) {   // maps read in place: no-stage step kernel
         NgwLaunch q = h->ns_proto;
         q.b = h->b; q.mode = mode; q.n_steps = 1; q.actions = actions_dev; q.autoreset = h->autoreset; q.horizon = h->horizon; q.stamps = h->proto.stamps;
         q.seq = h->launch_wire ? h->wt_seq : h->launch_seq; q.action0 = h->launch_action0; q.use_action0 = h->launch_use_action0 ? 1 : (h->launch_act_u8 ? 2 : 0);
-        HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, 8 | (h->ext ? 2 : 0) | (boards ? 1 : 0) | (h->launch_wire ? 16 : 0), grid, h->ns_lds, h->stream));
+        fused_mask = want_mask && h->act_mask_fused && !boards && !h->launch_wire;
+        HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, 8 | (h->ext ? 2 : 0) | (boards ? 1 : 0) | (h->launch_wire ? 16 : 0) | (fused_mask ? 32 : 0), grid, h->ns_lds, h->stream));
         taken = true;
     }
     if (!taken) {
@@ -184,7 +189,8 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
                                            "and they need more than 160 KiB; per-launch steps and resets are available", h->proto.S);
         const bool march = h->lidar_fused && !(boards && mode == NGW_MODE_RESET);
         if (!boards) a.b.brd = nullptr;                                // (the general kernel writes bit rows only while somebody reads them)
-        HIP_TRY(ngw_launch(h->dspec, &a, h->map_mode, (march ? 1 : 0) | (h->ext ? 2 : 0), grid, h->lds_bytes, h->stream));
+        fused_mask = want_mask && h->act_mask_fused && !march;
+        HIP_TRY(ngw_launch(h->dspec, &a, h->map_mode, (march ? 1 : 0) | (h->ext ? 2 : 0) | (fused_mask ? 32 : 0), grid, h->lds_bytes, h->stream));
     }
     if (boards && mode == NGW_MODE_RESET) {
         // (the dedicated new-episode kernel wrote the bit rows of the maps it made or copied; a masked reset leaves the others as they were,
@@ -195,6 +201,8 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
         if (int rc = launch_lidar_boards(h)) return rc;
     }
     if (boards && (mode == NGW_MODE_ROLLOUT || mode == NGW_MODE_ROLLOUT_ACT)) h->brd_dirty = true;
+    if (fused_mask) h->act_mask_fresh = true;
+    else if (want_mask) { if (int rc = launch_act_mask(h)) return rc; }   // (same stream: right behind the step)
     if (h->prefetch_every > 0 && (mode == NGW_MODE_STEP || mode == NGW_MODE_RESET || mode == NGW_MODE_ROLLOUT || mode == NGW_MODE_ROLLOUT_ACT)) {
         // Prepared next episodes: every `prefetch_every` batched steps (and right after an explicit reset) one more launch
         // refills the shadow rows that resets have consumed since.  Same stream, so it is ordered between the steps.
@@ -211,6 +219,7 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
 int launch_step_slice(ngw_handle* h, const uint8_t* actions_u8_dev, int64_t first, int64_t count) {
     if (first == 0) {
         h->mirror_valid = false;
+        h->act_mask_fresh = false;
         if (h->boards_on && h->brd_dirty) {
             if (int rc = rebuild_boards(h, h->b.map, h->b.brd, h->n_pad)) return rc;
             h->brd_dirty = false;
@@ -286,6 +295,7 @@ int solo_start(ngw_handle* h, int32_t commit0, uint32_t k0) {
     __atomic_thread_fence(__ATOMIC_SEQ_CST);
     HIP_TRY(ngw_solo_launch(h->dspec, &p, h->ext, h->solo_lds, h->stream));
     h->solo_running = true;
+    h->solo_starts++;
     return NGW_OK;
 }
 inline void cpu_pause() {
@@ -354,6 +364,7 @@ int solo_step(ngw_handle* h, int32_t action) {
     // ---- post the command: the loop commits it and speculates from the new state
     h->solo_last_action = action;
     h->solo_seq++;
+    h->act_mask_fresh = false;                                       // (the masks of this state come from the loop's records: ngw_get_action_mask)
     if (out[1]) {                                                    // (the loop has ended meanwhile: start the next one with the commit)
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->solo_running = false;
@@ -366,6 +377,7 @@ int solo_step(ngw_handle* h, int32_t action) {
 }
 
 int step_slices_done(ngw_handle* h) {
+    if (h->act_mask_on && h->act_mask) { if (int rc = launch_act_mask(h)) return rc; }
     if (h->prefetch_every > 0) {
         h->since_refill += 1;
         if (h->since_refill >= h->cadence) return launch_refill(h);
@@ -476,11 +488,16 @@ int capture_graph(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride
     // the refill between replays, eagerly, whenever the next replay would overrun the cadence.
     const bool open = h->prefetch_every > 0 && n_steps * 2 <= h->cadence;
     const int since0 = h->since_refill;
+    const bool mask_fresh0 = h->act_mask_fresh;       // (capturing runs nothing: whether the masks describe the state stays as it was)
     h->since_refill = 0;                              // the captured refill cadence starts from a known phase
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     h->capturing = true;                              // (the depth and cadence the handle has adapted to so far are the ones captured)
     int rc = NGW_OK;
-    for (int i = 0; i < n_steps && !rc; i++) rc = launch(h, NGW_MODE_STEP, 1, actions_dev + (int64_t)i * step_stride, nullptr, 0, 0);
+    for (int i = 0; i < n_steps && !rc; i++) {
+        h->act_mask_defer = i < n_steps - 1;                                    // (one replay leaves the masks of the state it ends in)
+        rc = launch(h, NGW_MODE_STEP, 1, actions_dev + (int64_t)i * step_stride, nullptr, 0, 0);
+    }
+    h->act_mask_defer = false;
     // every replay must leave the refill cadence where it found it: a graph shorter than (or not a multiple of) the cadence
     // ends with one more refill, otherwise a replayed graph would never re-prepare the episodes its steps consume
     if (!rc && h->prefetch_every > 0 && h->since_refill > 0 && !open) {
@@ -489,6 +506,8 @@ int capture_graph(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride
     }
     if (open) h->since_refill = since0;               // (nothing ran: the steps since the last refill are what they were)
     h->capturing = false;
+    h->act_mask_fresh = mask_fresh0;
+    h->graph_act_mask = h->act_mask_on;
     hipError_t e = hipStreamEndCapture(h->stream, &h->graph);
     if (rc) { drop_graph(h); return rc; }
     if (e != hipSuccess) { drop_graph(h); return fail(NGW_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e)); }
@@ -687,8 +706,12 @@ int ngw_step_device_many(ngw_handle* h, const int32_t* actions_dev, int64_t step
     if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "n_steps must be >= 1");
     HIP_TRY(hipSetDevice(h->device));
-    for (int32_t i = 0; i < n_steps; i++)
-        if (int rc = launch(h, NGW_MODE_STEP, 1, actions_dev + (int64_t)i * step_stride, nullptr, 0, 0)) return rc;
+    for (int32_t i = 0; i < n_steps; i++) {
+        h->act_mask_defer = i < n_steps - 1;                                    // (masks only for the state the call ends in)
+        const int rc = launch(h, NGW_MODE_STEP, 1, actions_dev + (int64_t)i * step_stride, nullptr, 0, 0);
+        h->act_mask_defer = false;
+        if (rc) return rc;
+    }
     return NGW_OK;
 }
 
@@ -807,6 +830,7 @@ int ngw_graph_launch(ngw_handle* h, int32_t reps) {
             if (int rc = launch_refill(h)) return rc;                               // (an open graph: the cadence is kept between its replays)
         }
         HIP_TRY(hipGraphLaunch(h->graph_exec, h->stream));
+        h->act_mask_fresh = h->graph_act_mask;
         if (h->graph_open) h->since_refill += h->graph_steps;
     }
     return NGW_OK;

@@ -221,6 +221,7 @@ struct NgwDevSpec {
     NgwTerm term;
     NgwWT wt;
     double pctq[NGW_MAX_PASSES][64];   /* per reset pass: pct / 100.0 for pct in [pct_lo, pct_hi) as the host's IEEE double */
+    uint64_t* amask;             /* [n_pad] action masks (ngw_mask.inc): the fused form of the step kernel stores the post-step masks here; nullptr until allocated */
 };
 
 #ifdef __cplusplus
@@ -390,5 +391,11 @@ struct NgwSolo {
 extern "C"
 #endif
 hipError_t ngw_solo_launch(const NgwDevSpec* dspec, const struct NgwSolo* p, int ext, size_t lds_bytes, hipStream_t stream);
+/* Action masks of the state in HBM (ngw_mask.inc): out[e] bit a = step(a) from env e's state would report result == True; [n_pad] words,
+ * padding rows 0.  ext: the spec has wrapper predicates (NgwExtU). */
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_mask_launch(const NgwDevSpec* dspec, const NgwBufs* b, int64_t n, int S, int K, int ext, uint64_t* out, unsigned grid, hipStream_t stream);
 
 #endif

@@ -4,6 +4,7 @@
 //   ngw_abi_host.cpp     the host API's wire formats (ngw_step_host, ngw_step_host_packed), state in / out, the multi-GPU payload
 //   ngw_abi_obs.cpp      observation wrappers on the device: LidarInFront (marches and the bit-row form), AgentMap
 //   ngw_abi_debug.cpp    timing pair and diagnostics entry points (not in include/ngw.h)
+//   ngw_abi_mask.cpp     action masks: the standalone mask kernel, staleness, the one-env loop's speculated records
 #ifndef NGW_HOST_H
 #define NGW_HOST_H
 #include <hip/hip_runtime.h>
@@ -154,6 +155,14 @@ struct ngw_handle {
     int8_t* view_out = nullptr;           // AgentMap windows
     int view_size = 0;
     size_t view_cap = 0;
+    // Action masks (ngw_abi_mask.cpp, ngw_mask.inc): [n_pad] uint64 words in HBM.  act_mask_fresh: they describe the current state (every
+    // launch that changes the state clears it; a step with act_mask_on leaves the post-step masks behind it on the stream and sets it)
+    uint64_t* act_mask = nullptr;
+    bool act_mask_on = false, act_mask_fresh = false;
+    bool graph_act_mask = false;          // the captured graph leaves the masks of the state it ends in
+    bool act_mask_defer = false;          // a step of a multi-step call that is not its last: its masks could never be read, none are computed
+    int act_mask_fused = 1;               // NGW_MASK_FUSED=0: the standalone kernel behind every plain step instead of the fused form (A/B)
+    long long solo_starts = 0;            // launches of the one-env resident loop (ngw_debug_solo_starts)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int graph_steps = 0;
@@ -194,6 +203,9 @@ int alloc_nx(ngw_handle* h, int depth, bool on);
 void adapt_cadence(ngw_handle* h);
 int rebuild_boards(ngw_handle* h, const int8_t* map, uint32_t* brd, int64_t rows);
 void drop_graph(ngw_handle* h);
+// ngw_abi_mask.cpp
+int launch_act_mask(ngw_handle* h);                 // the masks of the state in HBM, on the handle's stream (allocates the buffer on first use)
+int alloc_act_mask(ngw_handle* h);                  // the mask buffer, published to NgwDevSpec::amask (no-op once allocated)
 // ngw_abi_host.cpp
 void host_step_layout(const ngw_handle* h, uint64_t off[11]);
 

@@ -32,6 +32,8 @@
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
 //   8: the bit-row (boards) lidar: in-place step kernels with the O(1) observation, ngw_boards_kernel, ngw_lidar_boards_kernel
+//   9 / 10: the host write-through step kernels, plain / with the bit-row lidar (9 also holds the standalone mask kernel and the in-place step
+//   with fused masks; 1 / 6 / 7 hold the staged ones)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -664,7 +666,8 @@ extern "C" hipError_t ngw_reset_fast_launch(const NgwDevSpec* dspec, const NgwRe
 }
 #endif  // NGW_HAS(5)
 
-// feat: 1 = fused LidarInFront epilogue, 2 = wrapper predicates (EXT), 8 = no-stage step (maps read in place), 16 = host write-through (with 8)
+// feat: 1 = fused LidarInFront epilogue, 2 = wrapper predicates (EXT), 8 = no-stage step (maps read in place), 16 = host write-through (with 8),
+// 32 = fused action masks (plain steps only: ngw_step_lean<..., MASK>)
 extern "C" hipError_t ngw_part_step(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat, unsigned grid, size_t lds_bytes,
                                     hipStream_t stream);
 extern "C" hipError_t ngw_part_rollout_straight(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
@@ -675,6 +678,9 @@ extern "C" hipError_t ngw_part_rollout_byte(const NgwDevSpec* dspec, const NgwLa
 #define NGW_STEP_PART(NAME, MM)                                                                                                         \
     extern "C" hipError_t NAME(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) { \
         const bool lidar = (feat & 1) != 0, ext = (feat & 2) != 0;                                                                      \
+        if ((feat & 32) && !lidar)                                         /* fused action masks */                                    \
+            return ext ? launch_lean<MM, true, true, false, 0, false, true>(dspec, a, grid, lds_bytes, stream)                           \
+                       : launch_lean<MM, true, false, false, 0, false, true>(dspec, a, grid, lds_bytes, stream);                         \
         return lidar ? (ext ? launch_lean<MM, true, true, true>(dspec, a, grid, lds_bytes, stream)                                      \
                             : launch_lean<MM, true, false, true>(dspec, a, grid, lds_bytes, stream))                                    \
                      : (ext ? launch_lean<MM, true, true, false>(dspec, a, grid, lds_bytes, stream)                                     \
@@ -686,12 +692,27 @@ extern "C" hipError_t ngw_part_step_byte(const NgwDevSpec* dspec, const NgwLaunc
 extern "C" hipError_t ngw_part_step_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
 extern "C" hipError_t ngw_part_step_wire(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
 extern "C" hipError_t ngw_part_step_wire_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
+extern "C" hipError_t ngw_part_step_mask_ns(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
 #if NGW_HAS(9)
+// in-place step with the fused action masks
+extern "C" hipError_t ngw_part_step_mask_ns(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+    return (feat & 2) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false, 0, false, true>(dspec, a, grid, lds_bytes, stream)
+                      : launch_lean<NGW_MAP_STRAIGHT, false, false, false, 0, false, true>(dspec, a, grid, lds_bytes, stream);
+}
 // in-place step with the host write-through (NgwWT: ngw_step_host_packed's steady state)
 extern "C" hipError_t ngw_part_step_wire(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
     if (feat & 1) return ngw_part_step_wire_boards(dspec, a, feat, grid, lds_bytes, stream);
     return (feat & 2) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false, 0, true>(dspec, a, grid, lds_bytes, stream)
                       : launch_lean<NGW_MAP_STRAIGHT, false, false, false, 0, true>(dspec, a, grid, lds_bytes, stream);
+}
+#endif  // NGW_HAS(9)
+#if NGW_HAS(9)
+// the action masks of the state in HBM (ngw_mask.inc): [n_pad] uint64 words at `out`
+extern "C" hipError_t ngw_mask_launch(const NgwDevSpec* dspec, const NgwBufs* b, int64_t n, int S, int K, int ext, uint64_t* out, unsigned grid, hipStream_t stream) {
+    if (n <= 0 || n > 0xFFFFFFFFll || S < 3 || S > NGW_MAX_MAP_SIZE || K < 1 || K > NGW_MAX_ITEMS) return hipErrorInvalidValue;
+    if (ext) hipLaunchKernelGGL(ngw_mask_kernel<true>, dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, out);
+    else hipLaunchKernelGGL(ngw_mask_kernel<false>, dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, out);
+    return hipGetLastError();
 }
 #endif  // NGW_HAS(9)
 #if NGW_HAS(10)
@@ -743,6 +764,7 @@ extern "C" hipError_t ngw_part_step(const NgwDevSpec* dspec, const NgwLaunch* a,
     if (feat & 8) {                                                     // no-stage: with the lidar observation, the one on the occupancy bit rows
         if (feat & 16) return ngw_part_step_wire(dspec, a, feat, grid, lds_bytes, stream);   // ... with the host write-through
         if (feat & 1) return ngw_part_step_boards(dspec, a, feat, grid, lds_bytes, stream);
+        if (feat & 32) return ngw_part_step_mask_ns(dspec, a, feat, grid, lds_bytes, stream);
         return (feat & 2) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false>(dspec, a, grid, lds_bytes, stream)
                           : launch_lean<NGW_MAP_STRAIGHT, false, false, false>(dspec, a, grid, lds_bytes, stream);
     }

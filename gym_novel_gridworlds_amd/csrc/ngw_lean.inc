@@ -15,10 +15,11 @@
 //     function that reads its arguments from the HBM blob, so none of its address arithmetic is hoisted into the hot path.
 // Semantics and citations are those of ngw_kernel (pogostick_v1_env.py:230-367 etc.); results are bit-identical.
 //
-// The pieces (each included here, in this order): ngw_lean_cold.inc (helpers, prepared-episode copies, cold paths), ngw_lean_body.inc (the step),
+// The pieces (each included here, in this order): ngw_lean_cold.inc (helpers, prepared-episode copies, cold paths), ngw_lean_body.inc (the step), ngw_mask.inc (action masks),
 // ngw_lean_step.inc (the per-launch kernel + the host write-through form), ngw_lean_rollout.inc (fused rollouts).
 
 #include "ngw_lean_cold.inc"
 #include "ngw_lean_body.inc"
+#include "ngw_mask.inc"
 #include "ngw_lean_step.inc"
 #include "ngw_lean_rollout.inc"

@@ -4,6 +4,90 @@
 // Bit k of `x` as a lane mask-free 0 / 1 value with a per-lane k.
 __device__ __forceinline__ uint32_t bit_of(uint32_t x, uint32_t k) { return (x >> k) & 1u; }
 
+// ---- THE success predicate, shared by lean_body (every step kernel, the fused rollouts, the one-env loop) and the action-mask kernel
+//      (ngw_mask.inc): whatever decides info['result'] lives here and nowhere else, so the mask cannot drift from the step.
+// Condition bits NGW_CB_* of one lane for one action entry: most bits depend on the state only (the block in front, its 4-neighbourhood,
+// the cell two ahead, the uniform inventory slots); MISSING, NEED_TABLE and NO_ARG_ITEM depend on the entry (recipe inputs in e1 / e2 -
+// the caller read their slots iv0..iv3 -, the table flag and argument of e0).  axe_ok / missing: what lean_body needs of them besides.
+template <class UT>
+__device__ __forceinline__ uint32_t lean_cond_bits(const UT& U, uint32_t e0, uint32_t e2, int front, int front2, bool ok2, bool okN, bool okS, bool okW,
+                                                   bool okE, int nbN, int nbS, int nbW, int nbE, int inv_place, int inv_axe, int inv_arg,
+                                                   int iv0, int iv1, int iv2, int iv3, int sel, bool& axe_ok, uint32_t& missing) {
+    const int axe_item = U.axe_item;
+    axe_ok = axe_item && inv_axe >= 1 && sel == axe_item;                          // novelty_wrappers.py:155
+    const int nearP = U.place_near, nearE = U.ext_near;
+    const bool near_place = (okN && nbN == nearP) || (okS && nbS == nearP) || (okW && nbW == nearP) || (okE && nbE == nearP);
+    bool near_ext = near_place;                                                    // Pogostick: both rules look for a tree_log
+    // (scalar parameters: a uniform skip where both rules look for the same item; parameters pinned in VGPRs - the fused rollout - : no branch)
+    if (!__is_same(UT, NgwStepU) || nearE != nearP) {
+        const bool ne = !nearE || (okN && nbN == nearE) || (okS && nbS == nearE) || (okW && nbW == nearE) || (okE && nbE == nearE);
+        near_ext = nearE != nearP ? ne : near_place;
+    }
+    missing = (iv0 < (int)(e2 & 255u) ? 1u : 0u) | (iv1 < (int)((e2 >> 8) & 255u) ? 2u : 0u) |
+              (iv2 < (int)((e2 >> 16) & 255u) ? 4u : 0u) | (iv3 < (int)(e2 >> 24) ? 8u : 0u);   // :422-427
+    const uint32_t fbit = 1u << front;
+    uint32_t cb = 1u << NGW_CB_TRUE;
+    cb |= front != 0 ? 1u << NGW_CB_FRONT_NZ : 0u;
+    cb |= (ok2 && front2 == 0) ? 0u : 1u << NGW_CB_JUMP_BLOCKED;
+    cb |= (U.brk_mask & fbit) ? 0u : 1u << NGW_CB_NOT_BRK;
+    cb |= inv_place >= 1 ? 0u : 1u << NGW_CB_NO_PLACE_ITEM;
+    cb |= front == U.ext_src ? 0u : 1u << NGW_CB_NOT_SRC;
+    cb |= near_ext ? 0u : 1u << NGW_CB_NOT_NEAR;
+    cb |= missing ? 1u << NGW_CB_MISSING : 0u;
+    cb |= (((e0 >> 7) & 1u) && front != U.table_item) ? 1u << NGW_CB_NEED_TABLE : 0u;
+    cb |= inv_arg >= 1 ? 0u : 1u << NGW_CB_NO_ARG_ITEM;
+    cb |= (!axe_ok && U.axe_required) ? 1u << NGW_CB_NEED_AXE : 0u;
+    cb |= near_place ? 1u << NGW_CB_NEAR_PLACE : 0u;
+    cb |= (axe_ok || (!axe_item && (U.rew_mask & fbit))) ? 1u << NGW_CB_BRK_REWARD : 0u;
+    return cb;
+}
+
+// outcome of an entry: s = 1 if its condition A holds, else 2 if B holds, else 0 (success)
+__device__ __forceinline__ uint32_t lean_outcome(uint32_t cb, uint32_t e4) {
+    const uint32_t cA = bit_of(cb, e4 & 15u), cB = bit_of(cb, (e4 >> 4) & 15u);
+    return cA ? 1u : (cB << 1);
+}
+
+// The wrappers' predicates around Break (EXT), the only ones that are not table entries.  brk_act: this lane's action is a valid Break.
+//   restricted:  FenceRestriction.step :924-946 refuses the Break (the step fails, whatever the table said)
+//   fence_twice: FenceRestriction let it through - the wrapper runs env.step() AND its own epilogue, which reports success (:949-972)
+//   crate_now:   Crate.step :1086-1089 hands out the crate's ingredients first - unless the Crate wrapper sits BELOW FenceRestriction
+//                (NGW_XF_CRATE_IN_FENCE): then a restricted Break never reaches it
+// The cells the fence rule reads are fetched only when some lane of the wave breaks a breakable block (a wave-uniform skip).
+struct LeanBreakX { bool restricted, fence_twice, crate_now; };
+template <class UT, class CELL>
+__device__ __forceinline__ LeanBreakX lean_break_ext(const UT& U, const NgwExtU& X, bool brk_act, int front, int S, int r, int c, int f, int fr, int fc,
+                                                     int fcell, const CELL& cell_at) {
+    LeanBreakX xb = {false, false, false};
+    const uint32_t fbit = 1u << front;
+    xb.crate_now = brk_act && X.crate_item && front == X.crate_item;
+    if (X.fence_mode && __any(brk_act && (U.brk_mask & fbit))) {                    // FenceRestriction.step :924-946
+        const int ac0 = r * S + c, fence = X.fence_item;
+        bool restricted;
+        if (X.fence_mode == 1) {                                                   // medium: fence beside the AGENT, across its facing
+            const int side = f <= 1 ? 1 : S;
+            restricted = cell_at(ac0 - side) == fence || cell_at(ac0 + side) == fence;
+        } else {                                                                   // hard: any fence in the 3x3 around the block in front
+            restricted = false;
+            const bool in3 = fr > 0 && fr < S - 1 && fc > 0 && fc < S - 1;         // (a breakable block is never on the border)
+            const int base = in3 ? fcell : ac0;
+#pragma unroll
+            for (int k = 0; k < 9; k++) restricted |= cell_at(base + (k / 3 - 1) * S + (k % 3 - 1)) == fence;
+            restricted &= in3;
+        }
+        if (brk_act && (U.brk_mask & fbit)) {
+            if (restricted && front != fence) {
+                xb.restricted = true;
+                if (X.nest & NGW_XF_CRATE_IN_FENCE) xb.crate_now = false;
+            } else xb.fence_twice = true;
+        }
+    }
+    return xb;
+}
+
+// result of one entry: the table's outcome, then the wrappers' Break predicates (lean_body reaches the same value through `succ`)
+__device__ __forceinline__ bool lean_result(uint32_t s, const LeanBreakX& xb) { return xb.fence_twice || (s == 0 && !xb.restricted); }
+
 // What one step computes, shared by the per-launch kernel and the fused rollout.  STAGE: the lane's map is in LDS (`mp`), else its
 // cells are read from HBM (`bmap` + `mapoff`).  WT: write every change through to the observation buffers in HBM (per-launch
 // kernel); the fused rollout keeps the state in LDS / registers and stores it once, when the launch ends.
@@ -69,35 +153,13 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
     PIN_V(inv_slot);
 
     // ---- condition bits NGW_CB_* of this lane
-    const bool axe_ok = axe_item && inv_axe >= 1 && sel == axe_item;               // novelty_wrappers.py:155
-    const int nearP = U.place_near, nearE = U.ext_near;
-    const bool near_place = (okN && nbN == nearP) || (okS && nbS == nearP) || (okW && nbW == nearP) || (okE && nbE == nearP);
-    bool near_ext = near_place;                                                    // Pogostick: both rules look for a tree_log
-    // (scalar parameters: a uniform skip where both rules look for the same item; parameters pinned in VGPRs - the fused rollout - : no branch)
-    if (!__is_same(UT, NgwStepU) || nearE != nearP) {
-        const bool ne = !nearE || (okN && nbN == nearE) || (okS && nbS == nearE) || (okW && nbW == nearE) || (okE && nbE == nearE);
-        near_ext = nearE != nearP ? ne : near_place;
-    }
-    const uint32_t missing = (iv0 < (int)(e2 & 255u) ? 1u : 0u) | (iv1 < (int)((e2 >> 8) & 255u) ? 2u : 0u) |
-                             (iv2 < (int)((e2 >> 16) & 255u) ? 4u : 0u) | (iv3 < (int)(e2 >> 24) ? 8u : 0u);   // :422-427
-    const uint32_t fbit = 1u << front;
-    uint32_t cb = 1u << NGW_CB_TRUE;
-    cb |= front != 0 ? 1u << NGW_CB_FRONT_NZ : 0u;
-    cb |= (ok2 && front2 == 0) ? 0u : 1u << NGW_CB_JUMP_BLOCKED;
-    cb |= (U.brk_mask & fbit) ? 0u : 1u << NGW_CB_NOT_BRK;
-    cb |= inv_place >= 1 ? 0u : 1u << NGW_CB_NO_PLACE_ITEM;
-    cb |= front == U.ext_src ? 0u : 1u << NGW_CB_NOT_SRC;
-    cb |= near_ext ? 0u : 1u << NGW_CB_NOT_NEAR;
-    cb |= missing ? 1u << NGW_CB_MISSING : 0u;
-    cb |= (((e0 >> 7) & 1u) && front != U.table_item) ? 1u << NGW_CB_NEED_TABLE : 0u;
-    cb |= inv_arg >= 1 ? 0u : 1u << NGW_CB_NO_ARG_ITEM;
-    cb |= (!axe_ok && U.axe_required) ? 1u << NGW_CB_NEED_AXE : 0u;
-    cb |= near_place ? 1u << NGW_CB_NEAR_PLACE : 0u;
-    cb |= (axe_ok || (!axe_item && (U.rew_mask & fbit))) ? 1u << NGW_CB_BRK_REWARD : 0u;
+    bool axe_ok;
+    uint32_t missing;
+    const uint32_t cb = lean_cond_bits(U, e0, e2, front, front2, ok2, okN, okS, okW, okE, nbN, nbS, nbW, nbE, inv_place, inv_axe, inv_arg,
+                                       iv0, iv1, iv2, iv3, sel, axe_ok, missing);
 
     // ---- outcome: s = 1 if condition A holds, else 2 if B holds, else 0 (success)
-    const uint32_t cA = bit_of(cb, e4 & 15u), cB = bit_of(cb, (e4 >> 4) & 15u);
-    const uint32_t s = cA ? 1u : (cB << 1);
+    const uint32_t s = lean_outcome(cb, e4);
     bool succ = s == 0;                                                            // (a no-op entry "succeeds" at doing nothing)
     int msg = (int)((e4 >> (8u + 4u * s)) & 15u);
     const uint32_t asel = (e4 >> (20u + 2u * s)) & 3u;
@@ -108,31 +170,9 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
     // ---- wrappers around Break (FenceRestriction, Crate): the only predicates that are not table entries
     bool fence_twice = false, crate_now = false;
     if (EXT) {
-        const bool brk_act = is_break && valid;
-        // Crate.step :1086-1089: the ingredients come first - unless the Crate wrapper sits BELOW FenceRestriction
-        // (NGW_XF_CRATE_IN_FENCE): then a restricted Break never reaches it
-        crate_now = brk_act && X.crate_item && front == X.crate_item;
-        if (X.fence_mode && __any(brk_act && (U.brk_mask & fbit))) {                // FenceRestriction.step :924-946
-            const int ac0 = r * S + c, fence = X.fence_item;
-            bool restricted;
-            if (X.fence_mode == 1) {                                               // medium: fence beside the AGENT, across its facing
-                const int side = f <= 1 ? 1 : S;
-                restricted = cell_at(ac0 - side) == fence || cell_at(ac0 + side) == fence;
-            } else {                                                               // hard: any fence in the 3x3 around the block in front
-                restricted = false;
-                const bool in3 = fr > 0 && fr < S - 1 && fc > 0 && fc < S - 1;     // (a breakable block is never on the border)
-                const int base = in3 ? fcell : ac0;
-#pragma unroll
-                for (int k = 0; k < 9; k++) restricted |= cell_at(base + (k / 3 - 1) * S + (k % 3 - 1)) == fence;
-                restricted &= in3;
-            }
-            if (brk_act && (U.brk_mask & fbit)) {
-                if (restricted && front != fence) {
-                    succ = false; msg = NGW_MSG_FENCE_RESTRICTION; arg = 0; cost = (int)((e5 >> 14) & 63u);
-                    if (X.nest & NGW_XF_CRATE_IN_FENCE) crate_now = false;
-                } else fence_twice = true;                                         // the wrapper runs env.step() AND its own epilogue
-            }
-        }
+        const LeanBreakX xb = lean_break_ext(U, X, is_break && valid, front, S, r, c, f, fr, fc, fcell, cell_at);
+        crate_now = xb.crate_now; fence_twice = xb.fence_twice;
+        if (xb.restricted) { succ = false; msg = NGW_MSG_FENCE_RESTRICTION; arg = 0; cost = (int)((e5 >> 14) & 63u); }
     }
     // reward of a success: the entry's const, or the axe / break-reward rule of Break
     const int rew_val = is_break ? (axe_ok ? (int)U.axe_reward : U.break_reward) : (int)(int8_t)(e5 & 255u);

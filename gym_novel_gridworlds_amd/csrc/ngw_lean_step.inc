@@ -65,12 +65,16 @@ __device__ __forceinline__ void wire_done(const NgwWT& W, const uint32_t* dev_fl
     }
 }
 
-template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false>
+// MASK: the fused action masks - after the step, every lane evaluates the mask of the state it leaves (the post-step pose and cells, or the
+// new episode's first state where the launch started one) with lane_mask (ngw_mask.inc) and stores it to NgwDevSpec::amask.  Plain steps
+// only (no lidar epilogue, no host write-through): with those the library runs the standalone mask kernel behind the step.
+template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false>
 __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int32_t* actions, uint32_t n32, uint32_t o_brd, const NgwDevSpec* __restrict__ dspec,
                                                          uint32_t o_inv, uint32_t o_loc, uint32_t o_fac, uint32_t o_sel, uint32_t o_stp, uint32_t s2k,
                                                          const NgwLaunch a) {
     static_assert(!LIDAR || STAGE || NR > 0, "the fused LidarInFront epilogue marches over the map in LDS, or reads NR bit rows");
     static_assert(!HW || !STAGE, "the host write-through form is the in-place kernel's");
+    static_assert(!MASK || (!LIDAR && !HW), "the fused masks are the plain step's");
     constexpr bool BRD = LIDAR && !STAGE;
     constexpr int NRR = NR > 0 ? NR : 4;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -289,6 +293,13 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
             wave_lds_sync();                                                       // (the tile was zeroed, the item tables written, by other lanes)
             lidar_boards_rows<NRR>(a, lds, (int)tid, R, Rd, Ra, roww | ring, pt, Sb, S2, nr, nc, o.f, bmap, tid * (uint32_t)S2, inv, lid0, lid1, bid, HW ? W.rows : nullptr);
         }
+        if (MASK) {                                                                // the post-step state: pose in registers, map in LDS (staged) or
+            const uint32_t mo = tid * (uint32_t)S2;                                //   HBM (this lane's own writes), inventory row in LDS
+            auto cell = [&](int q) -> int { return STAGE ? (int)mp[q] : (int)ldg<int8_t>(bmap, mo + (uint32_t)q); };
+            const uint64_t m = lane_mask<EXT>(dspec, a.S, K, live ? o.r : 1, live ? o.c : 1, live ? o.f : 0, o.sel, inv, cell);
+            uint64_t* const am = dspec->amask;
+            if (am) stg<uint64_t>(reinterpret_cast<char*>(am) + (uint64_t)bid * (EPB * 8), tid * 8u, live ? m : 0ull);
+        }
         if (HW) {
             step_signals(dspec, flags, 0u);
             wire_done(W, a.b.flags, a.seq, gridDim.x, tid);
@@ -358,6 +369,21 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
             wave_lds_sync();
             lidar_boards_rows<NRR>(c, lds, (int)tid, R2, Rd2, Ra2, rw | 1u | (1u << (cS - 1)), BoardPatch{0u, 0u, 0u, 0u}, cS, cS2, nr, nc, fo, cmap, tid * (uint32_t)cS2, inv, lid0, lid1, gbid, HW ? Wc.rows : nullptr);
         }
+        if (MASK) {
+            // the wave has rewritten the rows of its resetting envs in HBM (prepared-episode copies, inline placement, the staged chunk's
+            // store-back): every lane reads its map and inventory row back from there (program order inside the wave = a workgroup-scope
+            // fence, as in terminal_capture) and evaluates the state it leaves - the new episode's first state where it started one
+            __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+            const int cS = c.S, cS2 = c.S2, cK = c.K;
+            char* const cmap = reinterpret_cast<char*>(c.b.map) + (uint64_t)gbid * (uint32_t)(EPB * cS2);
+            char* const cinv = reinterpret_cast<char*>(c.b.inv) + (uint64_t)gbid * (uint32_t)(EPB * 4 * cK);
+            for (int k = 0; k < cK; k++) inv[k] = ldgg<int>(cinv, tid * 4u * (uint32_t)cK + 4u * (uint32_t)k);
+            const uint32_t mo = tid * (uint32_t)cS2;
+            auto cell = [&](int q) -> int { return (int)ldgg<int8_t>(cmap, mo + (uint32_t)q); };
+            const uint64_t m = lane_mask<EXT>(dspec, cS, cK, live ? ro : 1, live ? co : 1, live ? fo : 0, so, inv, cell);
+            uint64_t* const am = dspec->amask;
+            if (am) stgg<uint64_t>(reinterpret_cast<char*>(am) + (uint64_t)gbid * (EPB * 8), tid * 8u, live ? m : 0ull);
+        }
         if (HW) {
             step_signals(dspec, flags, 0u);
             wire_done(Wc, c.b.flags, seq, gridDim.x, tid);
@@ -372,14 +398,14 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
 }
 
 
-template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false>
+template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false>
 hipError_t launch_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned grid, size_t lds_bytes, hipStream_t stream) {
     static size_t lds_opt_in[64] = {0};
     int dev = 0;
     hipError_t e = hipGetDevice(&dev);
     if (e != hipSuccess) return e;
     if (lds_bytes > 64 * 1024 && dev < 64 && lds_bytes > lds_opt_in[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
         if (e != hipSuccess) return e;
         lds_opt_in[dev] = lds_bytes;
     }
@@ -401,7 +427,7 @@ hipError_t launch_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned gri
     } else if (NR > 0) return hipErrorInvalidValue;
     if (NR > 0 && (a->BS > NR || a->BS < 4)) return hipErrorInvalidValue;
     const uint32_t s2k = (uint32_t)a->S2 | ((uint32_t)a->K << 16) | ((uint32_t)a->S << 24);
-    hipLaunchKernelGGL((ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW>), dim3(grid), dim3(NGW_EPB), lds_bytes, stream, base, a->actions, (uint32_t)a->n, o_brd, dspec,
+    hipLaunchKernelGGL((ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK>), dim3(grid), dim3(NGW_EPB), lds_bytes, stream, base, a->actions, (uint32_t)a->n, o_brd, dspec,
                        off[0], off[1], off[2], off[3], off[4], s2k, *a);
     return hipGetLastError();
 }

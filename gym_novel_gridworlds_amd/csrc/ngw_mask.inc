@@ -1,0 +1,96 @@
+// ngw_mask.inc - action masks (included by ngw_lean.inc between the step body and the step kernel): lane_mask, which the fused form of the step
+// kernel (ngw_step_lean<..., MASK = true>) calls at its end, and the standalone mask kernel.
+//
+// The mask of env i is a 64-bit word: bit a is 1 exactly when step(a) taken from env i's current state would report info['result'] == True
+// under the handle's spec, with every novelty and wrapper on it; bits >= n_actions are 0.  Nothing here restates a game rule: every bit comes
+// from the predicate lean_body uses (lean_cond_bits, lean_outcome, lean_break_ext, lean_result in ngw_lean_body.inc).
+//
+// One lane per env, 64 envs per wave, like the step kernels.  The lane reads its pose, the block in front, its 4-neighbourhood and (Jump) the
+// cell two ahead ONCE, lands its inventory row in a private LDS row, then walks the n_actions micro-op entries.  The entries are wave-uniform:
+// lane l holds entry l (the step kernels' table fetch) and the loop reads entry a out of lane a with v_readlane, so every entry field is a
+// scalar.  The only per-action memory reads are the recipe-input and argument slots of the LDS row (and, with FenceRestriction, the fence
+// cells of a Break - fetched once per wave that breaks anything breakable).
+
+// The mask of one lane's env from its pose and selected item, its inventory row (a lane-private LDS row) and its map (cell_at: a cell
+// index -> the item there).  Fetches the table (lane l holds entry l), the uniform parameters and the wrapper predicates itself, so that a
+// caller has nothing of them live across its own work.  All lanes of the wave must be active (the loop is wave-uniform).
+template <bool EXT, class CELL>
+__device__ __forceinline__ uint64_t lane_mask(const NgwDevSpec* __restrict__ dspec, int S, int K, int r, int c, int f, int sel, const int32_t* inv,
+                                              const CELL& cell_at) {
+    const uint32_t tid = threadIdx.x;
+    uint32_t t0, t1, t2, t4;
+    {
+        const uint2* ld = reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(dspec->act_lean) + min(tid, (uint32_t)(NGW_MAX_ACTIONS - 1)) * (4u * NGW_LEAN_DW));
+        const uint2 x0 = ld[0], x1 = ld[1], x2 = ld[2];
+        t0 = x0.x; t1 = x0.y; t2 = x1.x; t4 = x2.x;
+    }
+    NgwStepU U;                                                                    // uniform: scalar loads
+    {
+        const uint32_t* up = reinterpret_cast<const uint32_t*>(&dspec->u);
+        uint32_t uw[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) uw[i] = up[i];
+        __builtin_memcpy(&U, uw, sizeof(U));
+    }
+    NgwExtU X = {};
+    if (EXT) {
+        const uint32_t* xp = reinterpret_cast<const uint32_t*>(&dspec->x);
+        uint32_t xw[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) xw[i] = xp[i];
+        __builtin_memcpy(&X, xw, sizeof(X));
+    }
+    // ---- the cells every entry looks at (lean_body's L0 reads)
+    const int dr = (f == 0) ? -1 : (f == 1 ? 1 : 0), dc = (f == 2) ? -1 : (f == 3 ? 1 : 0);
+    const int fr = r + dr, fc = c + dc, dcell = dr * S + dc, fcell = r * S + c + dcell;
+    const int front = cell_at(fcell);
+    const bool okN = fr > 0, okS = fr < S - 1, okW = fc > 0, okE = fc < S - 1;
+    const int nbN = cell_at(okN ? fcell - S : fcell), nbS = cell_at(okS ? fcell + S : fcell);
+    const int nbW = cell_at(okW ? fcell - 1 : fcell), nbE = cell_at(okE ? fcell + 1 : fcell);
+    const int fr2 = fr + dr, fc2 = fc + dc;
+    const bool ok2 = fr2 >= 0 && fr2 <= S - 1 && fc2 >= 0 && fc2 <= S - 1;
+    int front2 = 1;
+    if (U.feat & NGW_FEAT_JUMP) front2 = cell_at(ok2 ? fcell + dcell : fcell);
+    const int inv_place = inv[U.place_item], inv_axe = inv[U.axe_item];
+    uint64_t mask = 0;
+    const int A = min(U.n_actions, NGW_MAX_ACTIONS);
+    for (int a = 0; a < A; a++) {
+        const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)t0, a), e1 = (uint32_t)__builtin_amdgcn_readlane((int)t1, a);
+        const uint32_t e2 = (uint32_t)__builtin_amdgcn_readlane((int)t2, a), e4 = (uint32_t)__builtin_amdgcn_readlane((int)t4, a);
+        const int aarg = (e0 >> 8) & 255;
+        const int inv_arg = inv[min(aarg, K - 1)];
+        const int iv0 = inv[e1 & 255], iv1 = inv[(e1 >> 8) & 255], iv2 = inv[(e1 >> 16) & 255], iv3 = inv[e1 >> 24];
+        bool axe_ok;
+        uint32_t missing;
+        const uint32_t cb = lean_cond_bits(U, e0, e2, front, front2, ok2, okN, okS, okW, okE, nbN, nbS, nbW, nbE, inv_place, inv_axe, inv_arg,
+                                           iv0, iv1, iv2, iv3, sel, axe_ok, missing);
+        const uint32_t s = lean_outcome(cb, e4);
+        LeanBreakX xb = {false, false, false};
+        if (EXT) xb = lean_break_ext(U, X, ((e0 >> 24) & 1u) != 0, front, S, r, c, f, fr, fc, fcell, cell_at);
+        mask |= (uint64_t)(lean_result(s, xb) ? 1u : 0u) << a;
+    }
+    return mask;
+}
+
+// The standalone form: the masks of the state held in HBM, [n_pad] words at `out` (padding rows 0).
+template <bool EXT>
+__global__ void __launch_bounds__(NGW_EPB) ngw_mask_kernel(const NgwDevSpec* __restrict__ dspec, const NgwBufs b, uint32_t n32, int S, int K,
+                                                           uint64_t* __restrict__ out) {
+    __shared__ int32_t inv_lds[NGW_EPB * (NGW_MAX_ITEMS | 1)];
+    const uint32_t bid = blockIdx.x, tid = threadIdx.x;
+    const int S2 = S * S, KP = K | 1;
+    const int nlive = (int)min((int64_t)EPB, (int64_t)n32 - (int64_t)bid * EPB);
+    const bool live = (int)tid < nlive;                                            // (every state array is n_pad long: lanes beyond n read padding rows)
+    const char* const bmap = reinterpret_cast<const char*>(b.map) + (uint64_t)bid * (uint32_t)(EPB * S2);
+    const char* const binv = reinterpret_cast<const char*>(b.inv) + (uint64_t)bid * (uint32_t)(EPB * 4 * K);
+    const int2 rc = ldg<int2>(reinterpret_cast<const char*>(b.loc) + (uint64_t)bid * (EPB * 8), tid * 8u);
+    const int f0 = ldg<int>(reinterpret_cast<const char*>(b.facing) + (uint64_t)bid * (EPB * 4), tid * 4u);
+    const int sel = ldg<uint8_t>(reinterpret_cast<const char*>(b.selected) + (uint64_t)bid * EPB, tid);
+    int32_t* inv = inv_lds + tid * KP;
+    for (int k = 0; k < K; k++) inv[k] = ldg<int>(binv, tid * 4u * (uint32_t)K + 4u * (uint32_t)k);
+    // a padding lane evaluates a pose inside the map (its rows are zeros) and stores 0
+    const uint32_t mapoff = tid * (uint32_t)S2;
+    auto cell_at = [&](int cell) -> int { return (int)ldg<int8_t>(bmap, mapoff + (uint32_t)cell); };
+    const uint64_t mask = lane_mask<EXT>(dspec, S, K, live ? rc.x : 1, live ? rc.y : 1, live ? (f0 & 3) : 0, sel, inv, cell_at);
+    stg<uint64_t>(reinterpret_cast<char*>(out) + (uint64_t)bid * (EPB * 8), tid * 8u, live ? mask : 0ull);
+}

@@ -100,6 +100,16 @@ class ShardedVecNovelGridworld:
     def sync(self):
         return self.local.sync()
 
+    def set_action_masks(self, on=True):
+        return self.local.set_action_masks(on)
+
+    def action_masks(self, device=False, copy=False):
+        """The action masks of this rank's shard (VecNovelGridworld.action_masks)."""
+        return self.local.action_masks(device, copy)
+
+    def action_mask_words(self, device=False, copy=False):
+        return self.local.action_mask_words(device, copy)
+
     def close(self):
         return self.local.close()
 

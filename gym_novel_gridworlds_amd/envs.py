@@ -299,6 +299,13 @@ class _NovelGridworldEnv(_EnvBase):
         self.last_done = done
         return obs, reward, done, out_info
 
+    def action_masks(self):
+        """bool [n_actions] (len(actions_id)): True where step(a) from the current state would report info['result'] == True.  While the
+        device's resident step loop runs, the answer is read from the outcomes it has already speculated for every action (no relaunch)."""
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        return vec.action_masks()[0]
+
     def get_observation(self):
         assert not self.max_items < len(self.items), "Cannot have more than " + str(self.max_items) + " items"
         return {'map': self.map, 'agent_location': self.agent_location, 'agent_facing_id': self.agent_facing_id,

@@ -43,6 +43,9 @@ class NoveltyWrapper(object):
     def reset(self, **kwargs):
         return self.env.reset(**kwargs)
 
+    def action_masks(self):
+        return self.env.action_masks()
+
     def render(self, mode='human', **kwargs):
         return self.env.render(mode, **kwargs)
 

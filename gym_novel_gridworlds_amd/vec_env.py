@@ -24,6 +24,13 @@ class _DevArray:
                                          'version': 2, 'strides': None}
 
 
+def unpack_action_masks(words, n_actions):
+    """[N] packed action-mask words (bit a of word i: step(a) from env i's state would report result == True) -> bool [N, n_actions]."""
+    w = np.ascontiguousarray(words, np.uint64).reshape(-1)
+    bits = w.view(np.uint8).reshape(-1, 8)                  # little-endian: byte j holds actions 8j .. 8j+7
+    return np.unpackbits(bits, axis=1, bitorder='little')[:, :n_actions].astype(bool)
+
+
 class StepInfo(dict):
     """info of a batched step: 'result' bool[N], 'step_cost_code', 'message_code', 'message_arg' - and 'step_cost' f64[N].  Fields
     that are not there yet are made when they are first asked for: 'step_cost' is looked up from the codes (a 65 536-element
@@ -185,6 +192,8 @@ class VecNovelGridworld:
             self.set_terminal_capture(True)
         if self.lidar is not None:                            # the observation setup travels with the env (rebuild)
             self.lidar_configure(self.lidar, fused=self.lidar_fused, dtype='packed' if self.lidar_packed else self.lidar_dtype)
+        if self.__dict__.get('_act_masks_on'):
+            self.set_action_masks(True)
 
     def rebuild(self, spec):
         """The same batched env - same object, same shard of the global env index space (`env_index_base`), same autoreset /
@@ -622,6 +631,47 @@ class VecNovelGridworld:
         return {'reward': torch.as_tensor(_DevArray(p[0].value, (N,), '<i4'), device=dev),
                 'done': torch.as_tensor(_DevArray(p[1].value, (N,), '|u1'), device=dev),
                 'info': torch.as_tensor(_DevArray(p[2].value, (N,), '<i4'), device=dev)}
+
+    # ------------------------------------------------------------------ action masks (include/ngw.h ngw_set_action_mask)
+    @property
+    def n_actions(self):
+        """Actions of the handle's spec: the width of action_masks() (a novelty may add actions beyond action_space.n)."""
+        return len(self.actions_id)
+
+    def set_action_masks(self, on=True):
+        """on: every step leaves the action masks of the state it produced behind it on the device (one more kernel launch per
+        step); off: action_masks() computes them when asked.  Either way action_masks() describes the current state."""
+        self._act_masks_on = bool(on)
+        _cabi.check(_cabi.lib().ngw_set_action_mask(self._h, int(self._act_masks_on)))
+
+    def action_mask_words(self, device=False, copy=False):
+        """The packed masks of the current state: uint64 [N], bit a = step(a) would report info['result'] == True.  On the host this is the
+        handle's ONE page-locked array, overwritten by the next call (copy=True: a fresh array); device=True: a torch int64 tensor over the
+        handle's device buffer (zero copy, valid until the next call that changes the state)."""
+        L = _cabi.lib()
+        if device:
+            import torch
+            _cabi.check(L.ngw_action_mask(self._h))
+            p = C.c_void_p()
+            _cabi.check(L.ngw_action_mask_device_ptr(self._h, C.byref(p)))
+            self.sync()
+            return torch.as_tensor(_DevArray(p.value, (self.num_envs,), '<i8'), device='cuda:%d' % self.device)
+        w = self.__dict__.get('_mask_words')
+        if w is None:
+            w = self._mask_words = _cabi.pinned_array((self.num_envs,), np.uint64)
+        _cabi.check(L.ngw_get_action_mask(self._h, _cabi._ptr(w, np.uint64)))
+        return w.copy() if copy else w
+
+    def action_masks(self, device=False, copy=False):
+        """Invalid-action masks of the current state (the state the next step() acts on): bool [N, n_actions], True where step(a) would
+        report info['result'] == True.  device=True: a torch bool tensor on the handle's device, expanded from the packed words with torch
+        ops.  The host array is a new array either way; `copy` is accepted for symmetry with the other observation calls."""
+        if device:
+            import torch
+            w = self.action_mask_words(device=True)
+            bits = torch.arange(self.n_actions, device=w.device, dtype=torch.int64)
+            return ((w[:, None] >> bits) & 1).bool()
+        return unpack_action_masks(self.action_mask_words(), self.n_actions)
 
     # ------------------------------------------------------------------ multi-GPU observation stack (dist.py)
     def pack_layout(self):

@@ -11,6 +11,7 @@ import os
 import pickle
 import datetime as _datetime
 
+import numpy as np
 
 from . import spaces
 from .novelty_wrappers import NoveltyWrapper
@@ -84,6 +85,24 @@ class LimitActions(NoveltyWrapper):
         env_actions = self.actions_id
         assert name in env_actions, _NOT_AN_ACTION.format(name=name, env_id=self.env_id)
         return self.env.step(env_actions[name])
+
+    def action_masks(self):
+        """bool [len(limited_actions)]: column i is the env's column of the action limited id i steps (the same two look-ups as step);
+        a limited id step() would refuse is False."""
+        return limit_mask_columns(self.env.action_masks(), self.limited_actions_id, self.actions_id, len(self.limited_actions))
+
+
+def limit_mask_columns(inner, limited_actions_id, actions_id, n):
+    """The env's mask row(s) `inner` ([..., n_env_actions]) in LimitActions' id space: column i <- the env's column of the FIRST name
+    that holds limited id i in `limited_actions_id` (table order), looked up in `actions_id`."""
+    inner = np.asarray(inner, bool)
+    out = np.zeros(inner.shape[:-1] + (n,), bool)
+    for i in range(n):
+        name = next((candidate for candidate, limited in limited_actions_id.items() if limited == i), None)
+        if name is None or name not in actions_id or actions_id[name] >= inner.shape[-1]:
+            continue
+        out[..., i] = inner[..., actions_id[name]]
+    return out
 
 
 def limit_actions_vec(venv, limited_actions):

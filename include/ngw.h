@@ -431,6 +431,23 @@ int ngw_agent_view(ngw_handle* h, int view_size);
 int ngw_get_agent_view(ngw_handle* h, int8_t* out_host);
 int ngw_agent_view_device_ptr(ngw_handle* h, void** out);
 
+/* Action masks (invalid-action masking, the action_masks() convention of MaskablePPO): the mask of env i is a uint64 word, bit a = 1
+ * exactly when step(a) taken from env i's CURRENT state (the state the next step acts on; after an autoreset, the new episode's first
+ * state) would report result = 1 under the handle's spec, every novelty and wrapper predicate included; bits >= n_actions are 0.
+ * The handle tracks whether its mask buffer describes the current state: reset, set_state, a rollout and steps taken with masks off
+ * make it stale, and ngw_action_mask / ngw_get_action_mask recompute it (one kernel launch).
+ * enable = 1: every following step (ngw_step*, the host steps, graphs built while it is on) also leaves the post-step masks, computed
+ * inside the step kernel (with the fused lidar or the host write-through form: by the mask kernel right behind the step on the handle's
+ * stream); ngw_step_device_many and a graph's replay compute them for their last step only.  0 = computed on demand only. */
+int ngw_set_action_mask(ngw_handle* h, int enable);
+/* makes the device buffer current (enqueued on the handle's stream; no launch when it is current already) */
+int ngw_action_mask(ngw_handle* h);
+/* [n_envs] words to host memory, made current first; waits for the stream.  A one-env handle whose resident step loop is running
+ * answers from the outcomes the loop has speculated for every action of the current state: no launch, the loop keeps running. */
+int ngw_get_action_mask(ngw_handle* h, uint64_t* out_host);
+/* the device buffer: [n_envs] uint64 in HBM (call ngw_action_mask before reading it) */
+int ngw_action_mask_device_ptr(ngw_handle* h, void** out);
+
 #ifdef __cplusplus
 }
 #endif
