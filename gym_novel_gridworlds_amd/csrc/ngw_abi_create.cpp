@@ -618,6 +618,7 @@ int ngw_destroy(ngw_handle* h) {
 int ngw_set_stream(ngw_handle* h, void* hip_stream) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);
     if (h->own_stream) { HIP_TRY(hipStreamDestroy(h->stream)); h->own_stream = false; }
@@ -633,6 +634,7 @@ int ngw_set_stream(ngw_handle* h, void* hip_stream) {
 int ngw_stream_order(ngw_handle* h, void* other_stream, int handle_waits) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     hipStream_t other = static_cast<hipStream_t>(other_stream);
     if (other == h->stream) return NGW_OK;                          // one stream: already in order
     if (!h->order_ev) HIP_TRY(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));

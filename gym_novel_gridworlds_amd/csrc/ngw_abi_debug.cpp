@@ -9,6 +9,7 @@ extern "C" {
 int ngw_timing_begin(ngw_handle* h) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     if (!h->ev0) { HIP_TRY(hipEventCreate(&h->ev0)); HIP_TRY(hipEventCreate(&h->ev1)); }
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     h->ev_marked = false;
@@ -19,6 +20,7 @@ int ngw_timing_mark(ngw_handle* h) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (!h->ev0) return fail(NGW_E_INVALID_ARG, "ngw_timing_mark without ngw_timing_begin");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     h->ev_marked = true;
     return NGW_OK;
@@ -28,6 +30,7 @@ int ngw_timing_end(ngw_handle* h, double* elapsed_ms) {
     if (!h || !elapsed_ms) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (!h->ev0) return fail(NGW_E_INVALID_ARG, "ngw_timing_end without ngw_timing_begin");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     if (!h->ev_marked) HIP_TRY(hipEventRecord(h->ev1, h->stream));
     h->ev_marked = false;
     HIP_TRY(hipEventSynchronize(h->ev1));
@@ -41,6 +44,7 @@ int ngw_timing_end(ngw_handle* h, double* elapsed_ms) {
 int ngw_debug_set_stamps(ngw_handle* h, void* stamps_dev) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);
     h->proto.stamps = static_cast<uint64_t*>(stamps_dev);
@@ -58,7 +62,9 @@ long long ngw_debug_solo_starts(ngw_handle* h) { return h ? h->solo_starts : -1;
  * since prepared episodes were switched on; -1 = off.  Waits for the stream. */
 long long ngw_debug_slow_resets(ngw_handle* h) {
     if (!h || !h->nx.slow || h->prefetch_every <= 0) return -1;
-    if (hipSetDevice(h->device) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) return -2;
+    if (hipSetDevice(h->device) != hipSuccess) return -2;
+    if (h->solo_running && solo_stop(h)) return -2;
+    if (hipStreamSynchronize(h->stream) != hipSuccess) return -2;
     uint32_t v = 0;
     if (hipMemcpy(&v, h->nx.slow, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -2;
     return (long long)v;
@@ -80,6 +86,7 @@ int ngw_debug_launch(ngw_handle* h, int mode, int32_t n_launches) {
 int ngw_debug_launch_floor(ngw_handle* h, int32_t n_launches, int graph, double* us_per_launch) {
     if (!h || !us_per_launch || n_launches < 1) return fail(NGW_E_INVALID_ARG, "bad argument");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     NgwLaunch a = h->nostage ? h->ns_proto : h->proto;
     a.b = h->b; a.mode = 13; a.actions = h->actions_dev;

@@ -363,6 +363,7 @@ int ngw_step_host_packed(ngw_handle* h, const int32_t* actions_host, void* block
     const size_t n = (size_t)h->n, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
     if (h->proto.S > 255) return fail(NGW_E_INVALID_ARG, "map_size beyond the pose bytes");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     // ---- actions: validated and narrowed to one byte per env in ONE pass, into a page-locked, GPU-addressable buffer (two halves, an
     //      event per half as in ngw_step) that the step kernel reads in place: no copy call for 64 KB.  (The buffer is 4 n bytes long:
     //      the kernel's int32 load of the same lanes must stay in bounds.)
@@ -615,6 +616,7 @@ int ngw_pack_obs(ngw_handle* h, void* payload_dev) {
     if (!h || !payload_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if ((uintptr_t)payload_dev & 15u) return fail(NGW_E_INVALID_ARG, "payload must be 16-byte aligned");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     PackSection sec[7]; uint64_t offs[8];
     pack_sections(h, sec, offs);
     NgwPack p = {};
@@ -631,6 +633,7 @@ int ngw_unpack_obs(ngw_handle* h, const void* payloads_dev, int32_t world, int8_
     if (!h || !payloads_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (world < 1) return fail(NGW_E_INVALID_ARG, "world %d must be >= 1", world);
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     PackSection sec[7]; uint64_t offs[8];
     pack_sections(h, sec, offs);
     uint8_t* const dsts[7] = {reinterpret_cast<uint8_t*>(map), reinterpret_cast<uint8_t*>(loc), reinterpret_cast<uint8_t*>(facing),

@@ -552,6 +552,7 @@ int ngw_set_reset_prefetch(ngw_handle* h, int32_t every_n_steps) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (every_n_steps < 0) return fail(NGW_E_INVALID_ARG, "every_n_steps must be >= 0");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);                                   // captured launches bake the cadence in
     if (every_n_steps > 0 && !h->nx.episode) { if (int rc = alloc_nx(h, h->depth, true)) return rc; }
@@ -568,6 +569,7 @@ int ngw_set_reset_prefetch_depth(ngw_handle* h, int32_t depth) {
     static_assert(NGW_MAX_DEPTH == 8, "the depths accepted below");
     if (depth != 0 && depth != 1 && depth != 2 && depth != 4 && depth != 8) return fail(NGW_E_INVALID_ARG, "depth must be 0 (automatic), 1, 2, 4 or 8");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);                                   // captured launches bake the shadow pointers in
     h->depth_user = depth != 0;
@@ -678,6 +680,7 @@ int ngw_step(ngw_handle* h, const int32_t* actions_host) {
         if (actions_host[i] < 0 || actions_host[i] >= A)
             return fail(NGW_E_INVALID_ACTION, "%d is not in list", (int)actions_host[i]);   // pogostick_v1_env.py:236
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     // The caller's array may be pageable and is his again when this call returns: it goes (host to host) into one half of a
     // page-locked buffer and from there to the device by an asynchronous copy - no stream synchronisation (which would also wait
     // for a refill still running).  A half is rewritten only after the copy that read it last has finished (an event per half).
@@ -733,6 +736,7 @@ int ngw_rollout_actions(ngw_handle* h, const int32_t* actions_dev, int64_t step_
 int ngw_set_terminal_capture(ngw_handle* h, int enable) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (enable && !h->term.map) {
         const size_t np = (size_t)h->n_pad, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
@@ -759,6 +763,7 @@ int ngw_get_terminal_obs(ngw_handle* h, int8_t* map, int32_t* loc, int32_t* faci
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (!h->term.map) return fail(NGW_E_INVALID_ARG, "ngw_get_terminal_obs before ngw_set_terminal_capture(h, 1)");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     const size_t n = (size_t)h->n, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
     D2H(map, h->term.map, n * S2);
     D2H(loc, h->term.loc, n * 2 * sizeof(int32_t));
@@ -782,6 +787,7 @@ int ngw_rollout_outputs(ngw_handle* h, int32_t* reward_rows_dev, uint8_t* done_r
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if ((reward_rows_dev || done_rows_dev) && row_stride < h->n) return fail(NGW_E_INVALID_ARG, "row_stride %lld is smaller than n_envs", (long long)row_stride);
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->row_reward = reward_rows_dev; h->row_done = done_rows_dev; h->row_stride = row_stride;
     if (accumulate && !h->acc) { if (int rc = dev_alloc(h, &h->acc, (size_t)h->n_pad * 4)) return rc; }
@@ -794,6 +800,7 @@ int ngw_episode_stats(ngw_handle* h, int32_t* run_return, int32_t* run_length, i
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (!h->acc) return fail(NGW_E_INVALID_ARG, "ngw_episode_stats before ngw_rollout_outputs(..., accumulate = 1)");
     HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
     int32_t* const dst[4] = {run_return, run_length, sum_return, n_episodes};
     for (int i = 0; i < 4; i++)
         if (dst[i]) HIP_TRY(hipMemcpyAsync(dst[i], h->acc + (size_t)i * h->n_pad, (size_t)h->n * sizeof(int32_t), hipMemcpyDefault, h->stream));

@@ -819,6 +819,7 @@ class VecNovelGridworld:
             import torch
             p = C.c_void_p()
             _cabi.check(_cabi.lib().ngw_agent_view_device_ptr(self._h, C.byref(p)))
+            self.sync()                                           # (the gather ran on the handle's stream, torch reads on its own)
             return torch.as_tensor(_DevArray(p.value, (self.num_envs, W, W), '|i1'), device='cuda:%d' % self.device)
         host = getattr(self, '_view_host', None)
         if host is None or host.shape[1] != W:
