@@ -595,6 +595,7 @@ int ngw_destroy(ngw_handle* h) {
     if (h->solo_running) (void)solo_stop(h);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void* p : h->allocs) (void)hipFree(p);
+    for (ngw_snapshot* s : h->snaps) delete s;                       // (their slabs were in `allocs`)
     for (void* p : h->host_allocs) (void)hipHostFree(p);
     drop_graph(h);
     if (h->info_host) (void)hipHostFree(h->info_host);

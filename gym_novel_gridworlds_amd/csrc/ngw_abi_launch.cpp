@@ -8,7 +8,6 @@ int capture_graph(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride
 
 namespace {
 int launch_reset_fast(ngw_handle* h, int mode, const uint8_t* mask_dev, bool* taken);
-int launch_lidar_boards(ngw_handle* h);
 int refill_launches(ngw_handle* h, bool* fast);
 int rollout_chunks(ngw_handle* h, int mode, int32_t n_steps, const int32_t* actions_dev, uint64_t action_seed, int64_t t0, int64_t step_stride);
 }
@@ -134,6 +133,14 @@ void adapt_cadence(ngw_handle* h) {
 int rebuild_boards(ngw_handle* h, const int8_t* map, uint32_t* brd, int64_t rows) {
     if (!map || !brd || rows <= 0) return NGW_OK;
     HIP_TRY(ngw_boards_launch(&h->brd_proto, h->map_mode, map, brd, rows, h->brd_lds, h->stream));
+    return NGW_OK;
+}
+
+// ... and the LidarInFront observation of the current state from them, as its own launch (what follows an explicit reset in the boards mode)
+int launch_lidar_boards(ngw_handle* h) {
+    NgwLaunch a = h->lb_proto;
+    a.b = h->b;
+    HIP_TRY(ngw_lidar_boards_launch(&a, (unsigned)(h->n_pad / NGW_EPB), h->lb_lds, h->stream));
     return NGW_OK;
 }
 
@@ -411,13 +418,6 @@ int launch_reset_fast(ngw_handle* h, int mode, const uint8_t* mask_dev, bool* ta
     return NGW_OK;
 }
 
-// ... and the LidarInFront observation of the current state from them, as its own launch (what follows an explicit reset in the boards mode)
-int launch_lidar_boards(ngw_handle* h) {
-    NgwLaunch a = h->lb_proto;
-    a.b = h->b;
-    HIP_TRY(ngw_lidar_boards_launch(&a, (unsigned)(h->n_pad / NGW_EPB), h->lb_lds, h->stream));
-    return NGW_OK;
-}
 
 int refill_launches(ngw_handle* h, bool* fast) {
     *fast = false;

@@ -1,0 +1,168 @@
+// ngw_abi_snapshot.cpp - device-side snapshots (see ngw_host.h): buffers of saved env states and the one kernel (ngw_snapshot.inc) that moves
+// rows between them and the state slab through index lists.  A restore changes the state behind the library's back-ups, so it does what
+// ngw_set_state does - ends the one-env loop, drops the host mirrors and the action masks, marks the occupancy bit rows stale - and then
+// refreshes a fused lidar observation and schedules a refill of the prepared next episodes, as ngw_reset does.
+#include "ngw_host.h"
+
+using namespace ngwh;
+
+namespace {
+
+NgwSnapRows state_rows(const ngw_handle* h) {
+    NgwSnapRows r;
+    r.map = h->b.map; r.loc = h->b.loc; r.facing = h->b.facing; r.inv = h->b.inv;
+    r.selected = h->b.selected; r.step_count = h->b.step_count; r.episode = h->b.episode;
+    return r;
+}
+
+// is `s` an open snapshot of `h`?  (looked up by address, never dereferenced first: a closed one, or another handle's, is simply not found)
+bool owns(const ngw_handle* h, const ngw_snapshot* s) {
+    for (const ngw_snapshot* q : h->snaps)
+        if (q == s) return true;
+    return false;
+}
+
+// `count` rows src -> dst on the handle's stream.  Without index lists the rows are contiguous: still the same kernel (one launch), or
+// seven device-to-device copies when the snapshot was created under NGW_SNAP_MEMCPY=1 (the comparison: DESIGN.md 4.4).
+int move_rows(ngw_handle* h, bool copies, const NgwSnapRows& src, int64_t src_rows, const int32_t* si, const NgwSnapRows& dst, int64_t dst_rows, const int32_t* di,
+              int64_t count, bool keep_episode) {
+    if (count == 0) return NGW_OK;
+    const size_t S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K, n = (size_t)count;
+    if (copies && !si && !di) {
+        HIP_TRY(hipMemcpyAsync(dst.map, src.map, n * S2, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dst.loc, src.loc, n * 8, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dst.facing, src.facing, n * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dst.inv, src.inv, n * K * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dst.selected, src.selected, n, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipMemcpyAsync(dst.step_count, src.step_count, n * 4, hipMemcpyDeviceToDevice, h->stream));
+        if (!keep_episode) HIP_TRY(hipMemcpyAsync(dst.episode, src.episode, n * 4, hipMemcpyDeviceToDevice, h->stream));
+        return NGW_OK;
+    }
+    NgwSnap a{};
+    a.src = src; a.dst = dst; a.si = si; a.di = di; a.flags = h->b.flags;
+    a.count = (int32_t)count; a.src_rows = (int32_t)src_rows; a.dst_rows = (int32_t)dst_rows;
+    a.S2 = h->proto.S2; a.K = h->proto.K; a.keep_episode = keep_episode ? 1 : 0;
+    HIP_TRY(ngw_snapshot_launch(&a, h->stream));
+    return NGW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ngw_snapshot_create(ngw_handle* h, int64_t capacity, ngw_snapshot** out) {
+    if (!h || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    if (capacity < 1 || capacity > 0x7FFFFFFFll) return fail(NGW_E_INVALID_ARG, "snapshot capacity %lld outside [1, 2^31)", (long long)capacity);
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    // one allocation, laid out like the state slab: every array 256-byte aligned, so a row is as aligned as its size allows
+    const size_t cap = (size_t)capacity, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
+    auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t o_map = 0, o_inv = up(cap * S2), o_loc = o_inv + up(cap * K * 4), o_fac = o_loc + up(cap * 8), o_sel = o_fac + up(cap * 4),
+                 o_stp = o_sel + up(cap), o_epi = o_stp + up(cap * 4), total = o_epi + up(cap * 4);
+    uint8_t* slab = nullptr;
+    if (int rc = dev_alloc(h, &slab, total)) return rc;               // (zero-filled on the handle's stream)
+    ngw_snapshot* s = new ngw_snapshot;
+    s->cap = capacity; s->slab = slab;
+    if (const char* v = getenv("NGW_SNAP_MEMCPY")) s->memcpy_path = atoi(v) != 0;
+    s->r.map = reinterpret_cast<int8_t*>(slab + o_map); s->r.inv = reinterpret_cast<int32_t*>(slab + o_inv);
+    s->r.loc = reinterpret_cast<int32_t*>(slab + o_loc); s->r.facing = reinterpret_cast<int32_t*>(slab + o_fac);
+    s->r.selected = slab + o_sel; s->r.step_count = reinterpret_cast<int32_t*>(slab + o_stp);
+    s->r.episode = reinterpret_cast<uint32_t*>(slab + o_epi);
+    // a never-saved slot is a legal state: an empty map with the agent at (1, 1)
+    const hipError_t e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->r.loc), 1, cap * 2, h->stream);
+    if (e != hipSuccess) {
+        dev_free(h, slab);
+        delete s;
+        return fail(NGW_E_HIP, "hipMemsetD32Async failed: %s", hipGetErrorString(e));
+    }
+    h->snaps.push_back(s);
+    *out = s;
+    return NGW_OK;
+}
+
+int ngw_snapshot_destroy(ngw_handle* h, ngw_snapshot* s) {
+    if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    HIP_TRY(hipStreamSynchronize(h->stream));                         // (queued saves / restores may still use the buffer)
+    for (size_t i = 0; i < h->snaps.size(); i++)
+        if (h->snaps[i] == s) { h->snaps.erase(h->snaps.begin() + (long)i); break; }
+    dev_free(h, s->slab);
+    delete s;
+    return NGW_OK;
+}
+
+int ngw_snapshot_save(ngw_handle* h, ngw_snapshot* s, const int32_t* envs_dev, const int32_t* slots_dev, int64_t count) {
+    if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (count < 0 || count > s->cap) return fail(NGW_E_INVALID_ARG, "save of %lld states into a snapshot of %lld slots", (long long)count, (long long)s->cap);
+    if (!envs_dev && count > h->n) return fail(NGW_E_INVALID_ARG, "save of %lld states from %lld envs", (long long)count, (long long)h->n);
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }    // (the one-env loop: HBM holds the state once it has ended)
+    return move_rows(h, s->memcpy_path != 0, state_rows(h), h->n, envs_dev, s->r, s->cap, slots_dev, count, false);
+}
+
+int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, const int32_t* envs_dev, int64_t count, int flags) {
+    if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (count < 0 || count > h->n) return fail(NGW_E_INVALID_ARG, "restore of %lld states into %lld envs", (long long)count, (long long)h->n);
+    if (!slots_dev && count > s->cap) return fail(NGW_E_INVALID_ARG, "restore of %lld states from a snapshot of %lld slots", (long long)count, (long long)s->cap);
+    if (flags & ~NGW_SNAP_KEEP_EPISODE) return fail(NGW_E_INVALID_ARG, "unknown restore flags 0x%x", (unsigned)flags);
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (count == 0) return NGW_OK;
+    const bool keep = (flags & NGW_SNAP_KEEP_EPISODE) != 0;
+    h->solo_mirror_valid = false;
+    h->mirror_valid = false;
+    h->act_mask_fresh = false;
+    if (int rc = move_rows(h, s->memcpy_path != 0, s->r, s->cap, slots_dev, state_rows(h), h->n, envs_dev, count, keep)) return rc;
+    if (h->boards_on) {
+        // the bit rows of the restored maps, and the fused observation of the restored state (what an explicit reset does as well): two
+        // whole-batch launches however few envs were restored - the price of an observation that is current right after the call
+        if (int rc = rebuild_boards(h, h->b.map, h->b.brd, h->n_pad)) return rc;
+        h->brd_dirty = false;
+        if (int rc = launch_lidar_boards(h)) return rc;
+    } else if (h->lidar_fused && h->lidar_len && h->lidar_lds) {
+        NgwLaunch a = h->lidar_proto;
+        a.b = h->b;
+        HIP_TRY(ngw_lidar_launch(&a, h->map_mode, (unsigned)(h->n_pad / NGW_EPB), h->lidar_lds, h->stream));
+    }
+    // Prepared next episodes: a row is valid iff its tag is the episode it was prepared for, so rows of envs whose counter moved are
+    // merely stale (their next reset runs the placement loop: same result).  A refill behind the restore prepares fresh ones, like the
+    // one behind an explicit reset; with the counters kept every tag still matches and nothing is scheduled.
+    if (h->prefetch_every > 0 && !keep) {
+        h->since_refill += h->prefetch_every;
+        if (h->since_refill >= h->cadence) return launch_refill(h);
+    }
+    return NGW_OK;
+}
+
+int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t count, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv,
+                     int32_t* selected, int32_t* step_count, uint32_t* episode) {
+    if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (first < 0 || count < 0 || first + count > s->cap) return fail(NGW_E_INVALID_ARG, "slot range [%lld, +%lld) out of bounds", (long long)first, (long long)count);
+    HIP_TRY(hipSetDevice(h->device));
+    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    const size_t n = (size_t)count, f = (size_t)first, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
+    D2H(map, s->r.map + f * S2, n * S2);
+    D2H(loc, s->r.loc + f * 2, n * 2 * sizeof(int32_t));
+    D2H(facing, s->r.facing + f, n * sizeof(int32_t));
+    D2H(inv, s->r.inv + f * K, n * K * sizeof(int32_t));
+    D2H(step_count, s->r.step_count + f, n * sizeof(int32_t));
+    D2H(episode, s->r.episode + f, n * sizeof(uint32_t));
+    std::vector<uint8_t> sel;
+    if (selected) {
+        sel.resize(n);
+        HIP_TRY(hipMemcpyAsync(sel.data(), s->r.selected + f, n, hipMemcpyDefault, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (selected)
+        for (size_t i = 0; i < n; i++) selected[i] = sel[i];
+    return NGW_OK;
+}
+
+}  // extern "C"

@@ -398,4 +398,33 @@ extern "C"
 #endif
 hipError_t ngw_mask_launch(const NgwDevSpec* dspec, const NgwBufs* b, int64_t n, int S, int K, int ext, uint64_t* out, unsigned grid, hipStream_t stream);
 
+/* Device-side snapshots (ngw_snapshot.inc, ngw_abi_snapshot.cpp): the seven state arrays of `rows` envs, laid out like the state slab
+ * itself (one array per field, row i of every array = one env).  The state slab is the set {map, loc, facing, inv, selected, step_count,
+ * episode} of NgwBufs, a snapshot is a second such set of `capacity` rows. */
+struct NgwSnapRows {
+    int8_t* map;          /* [rows][S*S] */
+    int32_t* loc;         /* [rows][2]   */
+    int32_t* facing;      /* [rows]      */
+    int32_t* inv;         /* [rows][K]   */
+    uint8_t* selected;    /* [rows]      */
+    int32_t* step_count;  /* [rows]      */
+    uint32_t* episode;    /* [rows]      */
+};
+/* One launch moves `count` rows: dst row di[j] := src row si[j] (a NULL list = j itself).  A row index outside its set makes that one copy
+ * a no-op and raises NGW_F_BAD_INDEX in *flags.  keep_episode: dst.episode is left as it is. */
+struct NgwSnap {
+    NgwSnapRows src, dst;
+    const int32_t* si;
+    const int32_t* di;
+    uint32_t* flags;
+    int32_t count, src_rows, dst_rows;
+    int32_t S2, K, keep_episode;
+};
+#define NGW_SNAP_GROUP 16        /* lanes that share one row */
+#define NGW_SNAP_BLOCK 256       /* threads per workgroup: 16 rows */
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_snapshot_launch(const struct NgwSnap* p, hipStream_t stream);
+
 #endif

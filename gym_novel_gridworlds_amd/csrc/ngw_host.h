@@ -5,6 +5,7 @@
 //   ngw_abi_obs.cpp      observation wrappers on the device: LidarInFront (marches and the bit-row form), AgentMap
 //   ngw_abi_debug.cpp    timing pair and diagnostics entry points (not in include/ngw.h)
 //   ngw_abi_mask.cpp     action masks: the standalone mask kernel, staleness, the one-env loop's speculated records
+//   ngw_abi_snapshot.cpp device-side snapshots: save / restore / fork env states by index (ngw_snapshot.inc)
 #ifndef NGW_HOST_H
 #define NGW_HOST_H
 #include <hip/hip_runtime.h>
@@ -37,6 +38,14 @@ const char* last_error();
     do {                                                                                                 \
         if (src) HIP_TRY(hipMemcpyAsync((dst), (src), (bytes), hipMemcpyDefault, h->stream));        \
     } while (0)
+
+// A device-side snapshot (ngw_abi_snapshot.cpp): `cap` rows of the seven state arrays in ONE allocation of its handle.
+struct ngw_snapshot {
+    int64_t cap = 0;
+    void* slab = nullptr;
+    int memcpy_path = 0;                  // NGW_SNAP_MEMCPY=1 when it was created: a save / restore without index lists runs as seven device-to-device copies instead of the kernel (A/B)
+    NgwSnapRows r{};
+};
 
 struct ngw_handle {
     ngw_spec spec;
@@ -162,6 +171,7 @@ struct ngw_handle {
     bool graph_act_mask = false;          // the captured graph leaves the masks of the state it ends in
     bool act_mask_defer = false;          // a step of a multi-step call that is not its last: its masks could never be read, none are computed
     int act_mask_fused = 1;               // NGW_MASK_FUSED=0: the standalone kernel behind every plain step instead of the fused form (A/B)
+    std::vector<ngw_snapshot*> snaps;     // open snapshots (ngw_snapshot_create); their slabs are in `allocs`, ngw_destroy deletes what is left
     long long solo_starts = 0;            // launches of the one-env resident loop (ngw_debug_solo_starts)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
@@ -202,6 +212,7 @@ int publish_nx(ngw_handle* h, bool on);
 int alloc_nx(ngw_handle* h, int depth, bool on);
 void adapt_cadence(ngw_handle* h);
 int rebuild_boards(ngw_handle* h, const int8_t* map, uint32_t* brd, int64_t rows);
+int launch_lidar_boards(ngw_handle* h);            // boards mode: the LidarInFront observation of the current state from the bit rows, as its own launch
 void drop_graph(ngw_handle* h);
 // ngw_abi_mask.cpp
 int launch_act_mask(ngw_handle* h);                 // the masks of the state in HBM, on the handle's stream (allocates the buffer on first use)

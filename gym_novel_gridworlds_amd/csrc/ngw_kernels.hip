@@ -27,13 +27,14 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file ELEVEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file TWELVE times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
 //   8: the bit-row (boards) lidar: in-place step kernels with the O(1) observation, ngw_boards_kernel, ngw_lidar_boards_kernel
 //   9 / 10: the host write-through step kernels, plain / with the bit-row lidar (9 also holds the standalone mask kernel and the in-place step
 //   with fused masks; 1 / 6 / 7 hold the staged ones)
+//   11: device-side snapshots (ngw_snapshot.inc)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -836,3 +837,20 @@ extern "C" hipError_t ngw_launch(const NgwDevSpec* dspec, const NgwLaunch* a, in
     }
 }
 #endif  // NGW_HAS(0)
+#if NGW_HAS(11)
+namespace {
+#include "ngw_snapshot.inc"
+}  // namespace
+// device-side snapshots (ngw_snapshot.inc): p->count rows from p->src to p->dst through the index lists
+extern "C" hipError_t ngw_snapshot_launch(const NgwSnap* p, hipStream_t stream) {
+    if (p->count <= 0 || p->S2 < 9 || p->S2 > NGW_MAX_MAP_SIZE * NGW_MAX_MAP_SIZE || p->K < 1 || p->K > NGW_MAX_ITEMS || p->src_rows < 1 ||
+        p->dst_rows < 1 || !p->flags)
+        return hipErrorInvalidValue;
+    constexpr int rows = NGW_SNAP_BLOCK / NGW_SNAP_GROUP;
+    const dim3 grid((unsigned)((p->count + rows - 1) / rows)), block(NGW_SNAP_BLOCK);
+    if (p->S2 % 16 == 0) hipLaunchKernelGGL(ngw_snapshot_kernel<16>, grid, block, 0, stream, *p);
+    else if (p->S2 % 4 == 0) hipLaunchKernelGGL(ngw_snapshot_kernel<4>, grid, block, 0, stream, *p);
+    else hipLaunchKernelGGL(ngw_snapshot_kernel<1>, grid, block, 0, stream, *p);
+    return hipGetLastError();
+}
+#endif  // NGW_HAS(11)

@@ -110,6 +110,14 @@ class ShardedVecNovelGridworld:
     def action_mask_words(self, device=False, copy=False):
         return self.local.action_mask_words(device, copy)
 
+    def snapshot(self, capacity=None):
+        """A device-side snapshot of this rank's shard (VecNovelGridworld.snapshot): rank-local, env indices are the shard's own."""
+        return self.local.snapshot(capacity)
+
+    def fork(self, src, keep_episode=False):
+        """Every LOCAL env e becomes a copy of local env src[e] (VecNovelGridworld.fork)."""
+        return self.local.fork(src, keep_episode)
+
     def close(self):
         return self.local.close()
 

@@ -215,7 +215,8 @@ class VecNovelGridworld:
             self.__dict__.update(old_attrs)                   # the old handle, spec and host mirrors: nothing happened
             raise
         if old_h:
-            _cabi.lib().ngw_destroy(old_h)
+            _cabi.lib().ngw_destroy(old_h)                    # (waits for the old handle's stream)
+        self._drop_snapshots(sync=False)                      # they held states in the old handle's map size and item count, and went with it
         return self
 
     _HOST_ATTRS = ('_obs', '_reward', '_done', '_act_pinned', '_sel_host', '_steps_host', '_result', '_cost', '_msg', '_arg', '_flags_np', '_info_words')
@@ -277,6 +278,7 @@ class VecNovelGridworld:
     # ------------------------------------------------------------------ lifecycle
     def close(self):
         if getattr(self, '_h', None) is not None and self._h:
+            self._drop_snapshots()                            # (ngw_destroy frees their buffers)
             _cabi.lib().ngw_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -787,6 +789,37 @@ class VecNovelGridworld:
         if conv[0] is not None:
             conv[0] = conv[0].reshape(count, -1)
         _cabi.check(_cabi.lib().ngw_set_state(self._h, first, count, *[_cabi._ptr(a, dt) for a, (_, dt) in zip(conv, arrs)]))
+
+    # ------------------------------------------------------------------ device-side snapshots (snapshot.py, include/ngw.h ngw_snapshot_*)
+    def snapshot(self, capacity=None):
+        """A buffer of `capacity` saved env states on the device (default: one slot per env): Snapshot.save / restore / state / close.
+        It belongs to this env and is closed with it, and by an in-place rebuild() (inject_novelty)."""
+        from .snapshot import Snapshot
+        s = Snapshot(self, self.num_envs if capacity is None else capacity)
+        self.__dict__.setdefault('_snapshots', []).append(s)
+        return s
+
+    def fork(self, src, keep_episode=False):
+        """Every env e becomes a copy of env src[e] (src: num_envs indices - a list / numpy array, checked, or a torch int32 tensor on the
+        env's device), through an internal scratch snapshot: all states are saved first, so src may name any env, itself included.  The
+        copies share the rest of the current episode and differ from their next reset on (each env draws from its own stream)."""
+        if len(src) != self.num_envs:
+            raise ValueError("fork: src names %d envs, the batch has %d" % (len(src), self.num_envs))
+        s = self.__dict__.get('_fork_snap')
+        if s is None or s.closed:
+            s = self._fork_snap = self.snapshot()
+        s.save()
+        s.restore(slots=src, keep_episode=keep_episode)
+
+    def _drop_snapshots(self, sync=True):
+        """The handle is going: its snapshots' buffers go with it (ngw_destroy), the Python objects raise from now on."""
+        snaps = self.__dict__.get('_snapshots', ())
+        if sync and self._h and any(s._keep for s in snaps):
+            self.sync()                                       # (a queued save / restore may still be reading its uploaded index lists)
+        for s in snaps:
+            s._invalidate()
+        self.__dict__['_snapshots'] = []
+        self.__dict__.pop('_fork_snap', None)
 
     # ------------------------------------------------------------------ timing (bench roofline leg) / hipGraph stepping
     def timing_begin(self):

@@ -45,6 +45,7 @@ extern "C" {
 /* device-side sticky error flags (ngw_error_flags) */
 #define NGW_F_INVALID_ACTION 1u
 #define NGW_F_PLACEMENT 2u
+#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore: an env or slot index outside its range (that copy was skipped) */
 
 /* action kinds (act_kind[]); act_arg[] = recipe index (CRAFT) or item id (SELECT) */
 enum { NGW_ACT_FORWARD = 0, NGW_ACT_LEFT = 1, NGW_ACT_RIGHT = 2, NGW_ACT_BREAK = 3, NGW_ACT_PLACE = 4,
@@ -447,6 +448,36 @@ int ngw_action_mask(ngw_handle* h);
 int ngw_get_action_mask(ngw_handle* h, uint64_t* out_host);
 /* the device buffer: [n_envs] uint64 in HBM (call ngw_action_mask before reading it) */
 int ngw_action_mask_device_ptr(ngw_handle* h, void** out);
+
+/* Device-side snapshots: save, restore and fork env states by index, without leaving the device.
+ * A snapshot is a device buffer of `capacity` slots that belongs to the handle that created it; a slot holds the full state of one env in
+ * that handle's map size and item count - the seven arrays of ngw_get_state: map, agent_location, agent_facing_id, inventory, selected
+ * item, step_count and the episode counter.  That is everything: `done` is a function of the inventory, and the reset stream is a
+ * function of (seed, global env index, episode counter).  reward / done / info of the last step are NOT part of it: ngw_get_step_out
+ * after a restore still reports the last step.  A slot that was never saved holds an all-zero row with agent_location (1, 1), a legal state.
+ *   save     slot[slots[j]] := state[envs[j]]  for j < count.  The slots of one call must be distinct.
+ *   restore  state[envs[j]] := slot[slots[j]]  for j < count.  Slots may repeat - that is the fork; the envs of one call must be
+ *            distinct.  Envs not named keep every byte of their state.  flags: NGW_SNAP_KEEP_EPISODE leaves the destination env's
+ *            episode counter as it is; without it the counter is restored with the rest.
+ * Index lists are int32 arrays in DEVICE memory; NULL means 0 .. count-1.  An index outside [0, n_envs) / [0, capacity) makes that one
+ * copy a no-op and raises the sticky NGW_F_BAD_INDEX (ngw_error_flags).  count above n_envs (restore) or capacity (save), a NULL handle or
+ * snapshot, and a snapshot that is not an open snapshot of this handle return NGW_E_INVALID_ARG.
+ * The future of a restored env: env e, when it next resets, draws from env e's OWN stream at its (restored or kept) episode counter.  Two
+ * forks of one slot therefore share the rest of the current episode - same map, same actions, same outcomes - and differ from their next
+ * reset on; restoring the same env from the same slot twice replays the same future, resets included.
+ * Save and restore are enqueued on the handle's stream, like ngw_step_device, and do not wait.  A restore makes the action masks, the host
+ * mirrors and the occupancy bit rows stale like ngw_set_state does, refreshes a fused lidar observation, and - unless the episode counters
+ * were kept - is followed by a refill of the prepared next episodes, as ngw_reset is.  A captured graph stays valid.
+ * ngw_snapshot_get copies `count` slots from `first` to host arrays shaped as for ngw_get_state (any may be NULL) and waits.
+ * ngw_snapshot_destroy waits for the stream (queued copies may still read the buffer) and frees it; ngw_destroy frees what is still open. */
+typedef struct ngw_snapshot ngw_snapshot;
+#define NGW_SNAP_KEEP_EPISODE 1
+int ngw_snapshot_create(ngw_handle* h, int64_t capacity, ngw_snapshot** out);
+int ngw_snapshot_destroy(ngw_handle* h, ngw_snapshot* s);
+int ngw_snapshot_save(ngw_handle* h, ngw_snapshot* s, const int32_t* envs_dev, const int32_t* slots_dev, int64_t count);
+int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, const int32_t* envs_dev, int64_t count, int flags);
+int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t count, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv,
+                     int32_t* selected, int32_t* step_count, uint32_t* episode);
 
 #ifdef __cplusplus
 }
