@@ -618,8 +618,7 @@ int ngw_destroy(ngw_handle* h) {
 
 int ngw_set_stream(ngw_handle* h, void* hip_stream) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);
     if (h->own_stream) { HIP_TRY(hipStreamDestroy(h->stream)); h->own_stream = false; }
@@ -634,8 +633,7 @@ int ngw_set_stream(ngw_handle* h, void* hip_stream) {
 
 int ngw_stream_order(ngw_handle* h, void* other_stream, int handle_waits) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     hipStream_t other = static_cast<hipStream_t>(other_stream);
     if (other == h->stream) return NGW_OK;                          // one stream: already in order
     if (!h->order_ev) HIP_TRY(hipEventCreateWithFlags(&h->order_ev, hipEventDisableTiming));
@@ -646,8 +644,7 @@ int ngw_stream_order(ngw_handle* h, void* other_stream, int handle_waits) {
 
 int ngw_sync(ngw_handle* h) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     return NGW_OK;
 }
@@ -683,8 +680,7 @@ int ngw_out_device_ptrs(ngw_handle* h, void** reward, void** done, void** info) 
 
 int ngw_error_flags(ngw_handle* h, uint32_t* flags) {
     if (!h || !flags) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipMemcpyAsync(flags, h->b.flags, sizeof(uint32_t), hipMemcpyDefault, h->stream));
     HIP_TRY(hipMemsetAsync(h->b.flags, 0, sizeof(uint32_t), h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));

@@ -8,8 +8,7 @@ extern "C" {
 
 int ngw_timing_begin(ngw_handle* h) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     if (!h->ev0) { HIP_TRY(hipEventCreate(&h->ev0)); HIP_TRY(hipEventCreate(&h->ev1)); }
     HIP_TRY(hipEventRecord(h->ev0, h->stream));
     h->ev_marked = false;
@@ -19,8 +18,7 @@ int ngw_timing_begin(ngw_handle* h) {
 int ngw_timing_mark(ngw_handle* h) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (!h->ev0) return fail(NGW_E_INVALID_ARG, "ngw_timing_mark without ngw_timing_begin");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipEventRecord(h->ev1, h->stream));
     h->ev_marked = true;
     return NGW_OK;
@@ -29,8 +27,7 @@ int ngw_timing_mark(ngw_handle* h) {
 int ngw_timing_end(ngw_handle* h, double* elapsed_ms) {
     if (!h || !elapsed_ms) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (!h->ev0) return fail(NGW_E_INVALID_ARG, "ngw_timing_end without ngw_timing_begin");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     if (!h->ev_marked) HIP_TRY(hipEventRecord(h->ev1, h->stream));
     h->ev_marked = false;
     HIP_TRY(hipEventSynchronize(h->ev1));
@@ -43,8 +40,7 @@ int ngw_timing_end(ngw_handle* h, double* elapsed_ms) {
 /* Diagnostics builds (-DNGW_STAMPS): device buffer [grid][16] uint64 the kernels write their clock stamps to; NULL = off. */
 int ngw_debug_set_stamps(ngw_handle* h, void* stamps_dev) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);
     h->proto.stamps = static_cast<uint64_t*>(stamps_dev);
@@ -62,8 +58,7 @@ long long ngw_debug_solo_starts(ngw_handle* h) { return h ? h->solo_starts : -1;
  * since prepared episodes were switched on; -1 = off.  Waits for the stream. */
 long long ngw_debug_slow_resets(ngw_handle* h) {
     if (!h || !h->nx.slow || h->prefetch_every <= 0) return -1;
-    if (hipSetDevice(h->device) != hipSuccess) return -2;
-    if (h->solo_running && solo_stop(h)) return -2;
+    if (enter(h)) return -2;
     if (hipStreamSynchronize(h->stream) != hipSuccess) return -2;
     uint32_t v = 0;
     if (hipMemcpy(&v, h->nx.slow, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -2;
@@ -73,7 +68,7 @@ long long ngw_debug_slow_resets(ngw_handle* h) {
 /* Diagnostic launches (profiling only, not part of include/ngw.h): mode 8 = empty kernel, 9 = stage in/out only. */
 int ngw_debug_launch(ngw_handle* h, int mode, int32_t n_launches) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = enter(h)) return rc;
     for (int i = 0; i < n_launches; i++)
         if (int rc = launch(h, mode, 1, h->actions_dev, nullptr, 0, 0)) return rc;
     return NGW_OK;
@@ -85,8 +80,7 @@ int ngw_debug_launch(ngw_handle* h, int mode, int32_t n_launches) {
  * timed - measured with a HIP event pair.  What one launch per step() costs before a single instruction of the step runs. */
 int ngw_debug_launch_floor(ngw_handle* h, int32_t n_launches, int graph, double* us_per_launch) {
     if (!h || !us_per_launch || n_launches < 1) return fail(NGW_E_INVALID_ARG, "bad argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     NgwLaunch a = h->nostage ? h->ns_proto : h->proto;
     a.b = h->b; a.mode = 13; a.actions = h->actions_dev;

@@ -25,6 +25,13 @@ void host_step_layout(const ngw_handle* h, uint64_t off[11]) {
     off[10] = o;
 }
 
+// The reference raises for a bad id before it touches any state (pogostick_v1_env.py:236).
+int check_actions(const int32_t* actions, size_t n, int A) {
+    for (size_t i = 0; i < n; i++)
+        if (actions[i] < 0 || actions[i] >= A) return fail(NGW_E_INVALID_ACTION, "%d is not in list", (int)actions[i]);
+    return NGW_OK;
+}
+
 }  // namespace ngwh
 
 namespace {
@@ -87,6 +94,21 @@ uint32_t narrow_actions(const int32_t* a, uint8_t* o, size_t n, int A) {
     return bad;
 }
 
+// (Re-)seeds the delta shadows of the first `regions` sparse sections from the state: `block` mirrors the state from here on.  A block that
+// is not mapped into the GPU's address space, or shadows that cannot be allocated, leave the handle without a mirror: full copies.
+int seed_shadows(ngw_handle* h, void* block, int regions, const void* const* src, const uint64_t* nbytes) {
+    void* dev = nullptr;
+    bool ok = hipHostGetDevicePointer(&dev, block, 0) == hipSuccess && dev;
+    if (!ok) (void)hipGetLastError();
+    for (int k = 0; k < regions && ok; k++) {
+        if (!h->shadow[k]) ok = dev_alloc(h, &h->shadow[k], (size_t)((nbytes[k] + 255) & ~(uint64_t)255)) == NGW_OK;
+        if (ok) HIP_TRY(hipMemcpyAsync(h->shadow[k], src[k], (size_t)nbytes[k], hipMemcpyDeviceToDevice, h->stream));
+    }
+    h->mirror_block = ok ? block : nullptr; h->mirror_dev = static_cast<uint8_t*>(dev);
+    h->shadow_stale = false;
+    return NGW_OK;
+}
+
 /* Payload of the multi-GPU observation gather: the seven SoA arrays back to back, each section padded to 16 bytes. */
 struct PackSection { const void* dev; uint64_t bytes; };
 int pack_sections(const ngw_handle* h, PackSection sec[7], uint64_t offs[8]) {
@@ -105,8 +127,7 @@ extern "C" {
 
 int ngw_get_obs(ngw_handle* h, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     const size_t n = (size_t)h->n, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
     D2H(map, h->b.map, n * S2);
     D2H(loc, h->b.loc, n * 2 * sizeof(int32_t));
@@ -118,8 +139,7 @@ int ngw_get_obs(ngw_handle* h, int8_t* map, int32_t* loc, int32_t* facing, int32
 
 int ngw_get_step_out(ngw_handle* h, int32_t* reward, uint8_t* done, uint8_t* result, uint8_t* cost_code, uint16_t* msg_code, uint16_t* msg_arg) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     const size_t n = (size_t)h->n;
     D2H(reward, h->b.reward, n * sizeof(int32_t));
     D2H(done, h->b.done, n);
@@ -157,12 +177,9 @@ int ngw_step_host(ngw_handle* h, const int32_t* actions_host, int8_t* map, int32
                   uint8_t* done, uint8_t* result, uint8_t* cost_code, uint16_t* msg_code, uint16_t* msg_arg, uint32_t* error_flags,
                   uint8_t* selected, int32_t* step_count) {
     if (!h || !actions_host) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    const int A = h->spec.n_actions;
     const size_t n = (size_t)h->n, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
-    for (size_t i = 0; i < n; i++)
-        if (actions_host[i] < 0 || actions_host[i] >= A)
-            return fail(NGW_E_INVALID_ACTION, "%d is not in list", (int)actions_host[i]);   // pogostick_v1_env.py:236
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = check_actions(actions_host, n, h->spec.n_actions)) return rc;
+    HIP_TRY(hipSetDevice(h->device));                                   // (not enter(): on a one-env handle the resident loop IS the path, below; every other branch reaches launch())
     const bool want_info = result || cost_code || msg_code || msg_arg;
     const uint32_t* info_words = nullptr;
     // what the caller wants back: (host pointer, device source, bytes)
@@ -200,32 +217,17 @@ int ngw_step_host(ngw_handle* h, const int32_t* actions_host, int8_t* map, int32
         const double t0 = now();
 #endif
         memcpy(h->zc_host, actions_host, n * sizeof(int32_t));
-        // The kernel writes this launch's sequence number to host memory once its stores are out: polling that word costs a
-        // PCIe write's latency, a stream synchronisation several microseconds (and would also wait for a refill launch that
-        // follows the step on the stream).  Bounded: after ~20 ms without the word the stream is synchronised the usual way.
+        // The kernel writes this launch's sequence number to host memory once its stores are out, and that word is polled (wait_seq:
+        // after ~20 ms without it the stream is synchronised the usual way).
         h->step_seq = h->step_seq + 1u ? h->step_seq + 1u : 1u;
-        h->launch_seq = h->step_seq;
-        h->launch_use_action0 = n == 1; h->launch_action0 = actions_host[0];
-        const int lrc = launch(h, NGW_MODE_STEP, 1, n == 1 ? h->actions_dev : reinterpret_cast<const int32_t*>(h->zc_dev), nullptr, 0, 0);
-        h->launch_seq = 0; h->launch_use_action0 = false;
-        if (lrc) return lrc;
+        LaunchOpts o;
+        o.seq = h->step_seq;
+        if (n == 1) { o.actions = LaunchOpts::ACT_ARG; o.action0 = actions_host[0]; }
+        if (int rc = launch(h, NGW_MODE_STEP, 1, n == 1 ? h->actions_dev : reinterpret_cast<const int32_t*>(h->zc_dev), nullptr, 0, 0, o)) return rc;
 #ifdef NGW_HOSTTRACE
         const double t1 = now();
 #endif
-        {
-            volatile uint32_t* sp = h->b.flags_host + NGW_SEQ_WORD;
-            bool seen = false;
-            for (uint32_t spin = 0; spin < (1u << 21); spin++) {
-                if (*sp == h->step_seq) { seen = true; break; }
-#if defined(__x86_64__) || defined(__i386__)
-                __builtin_ia32_pause();
-#else
-                __asm__ __volatile__("" ::: "memory");
-#endif
-            }
-            if (!seen) HIP_TRY(hipStreamSynchronize(h->stream));
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);                                // the state reads below stay behind the poll
-        }
+        if (int rc = wait_seq(h, h->b.flags_host + NGW_SEQ_WORD, h->step_seq, 1u << 21)) return rc;
 #ifdef NGW_HOSTTRACE
         const double t2 = now();
 #endif
@@ -280,17 +282,10 @@ int ngw_step_host(ngw_handle* h, const int32_t* actions_host, int8_t* map, int32
         } else {
             HIP_TRY(ngw_pack_launch(&p, h->stream));
             HIP_TRY(hipMemcpyAsync(map, h->step_stage, (size_t)off[10], hipMemcpyDefault, h->stream));
-            if (h->host_delta) {                                      // (re-)seed the shadows: the block mirrors the state from here on
-                void* dev = nullptr;
-                bool ok = hipHostGetDevicePointer(&dev, map, 0) == hipSuccess && dev;
-                if (!ok) (void)hipGetLastError();                     // (a block that is not mapped into the GPU's address space: full copies)
-                for (int k = 0; k < 3 && ok; k++) {
-                    const int r = SPARSE[k];
-                    if (!h->shadow[k]) ok = dev_alloc(h, &h->shadow[k], (size_t)((nb[r] + 255) & ~(uint64_t)255)) == NGW_OK;
-                    if (ok) HIP_TRY(hipMemcpyAsync(h->shadow[k], srcs[r], (size_t)nb[r], hipMemcpyDeviceToDevice, h->stream));
-                }
-                h->mirror_block = ok ? map : nullptr; h->mirror_dev = static_cast<uint8_t*>(dev);
-                h->shadow_stale = false;
+            if (h->host_delta) {
+                const void* const ssrc[3] = {srcs[SPARSE[0]], srcs[SPARSE[1]], srcs[SPARSE[2]]};
+                const uint64_t snb[3] = {nb[SPARSE[0]], nb[SPARSE[1]], nb[SPARSE[2]]};
+                if (int rc = seed_shadows(h, map, 3, ssrc, snb)) return rc;
             }
         }
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -362,8 +357,7 @@ int ngw_step_host_packed(ngw_handle* h, const int32_t* actions_host, void* block
     const ngw_spec& sp = h->spec;
     const size_t n = (size_t)h->n, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
     if (h->proto.S > 255) return fail(NGW_E_INVALID_ARG, "map_size beyond the pose bytes");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     // ---- actions: validated and narrowed to one byte per env in ONE pass, into a page-locked, GPU-addressable buffer (two halves, an
     //      event per half as in ngw_step) that the step kernel reads in place: no copy call for 64 KB.  (The buffer is 4 n bytes long:
     //      the kernel's int32 load of the same lanes must stay in bounds.)
@@ -401,12 +395,11 @@ int ngw_step_host_packed(ngw_handle* h, const int32_t* actions_host, void* block
     // the envs that start an episode, pose / reward / done / info of every env - and its last block publishes the error flags and this call's
     // sequence number behind section 6's flags word, which is polled here: no delta kernel, no stream synchronisation (a refill launch that
     // follows the step on the stream runs while the caller already works on the results).  The delta kernel's shadows go stale meanwhile.
-    if (mirrored && h->wt_enabled && h->api_slices <= 1 && h->nostage && (!h->lidar_fused || h->boards_on) && !h->hostres && !h->capturing && !h->proto.stamps) {
+    if (mirrored && h->wt_enabled && h->api_slices <= 1 && step_in_place(h) && !h->hostres && !h->capturing && !h->proto.stamps) {
         const uint32_t bad = narrow_actions(actions_host, a8, n, A);
         if (bad) {
             h->act_next ^= 1;
-            for (size_t i = 0; i < n; i++)
-                if (actions_host[i] < 0 || actions_host[i] >= A) return fail(NGW_E_INVALID_ACTION, "%d is not in list", (int)actions_host[i]);   // pogostick_v1_env.py:236
+            if (int rc = check_actions(actions_host, n, A)) return rc;
         }
 #ifdef NGW_HOSTTRACE
         static double wA = 0, wB = 0, wC = 0; static int wn = 0;
@@ -437,10 +430,9 @@ int ngw_step_host_packed(ngw_handle* h, const int32_t* actions_host, void* block
         h->wt_seq = h->wt_seq + 1u ? h->wt_seq + 1u : 1u;
         volatile uint32_t* const sw = reinterpret_cast<volatile uint32_t*>(blk + off[6]) + 1;
         *sw = 0u;                                                       // (whatever the block held there)
-        h->launch_use_action0 = false; h->launch_act_u8 = true; h->launch_wire = true;
-        const int lrc = launch(h, NGW_MODE_STEP, 1, reinterpret_cast<const int32_t*>(h->act_pin_dev + (size_t)slot * cap), nullptr, 0, 0);
-        h->launch_act_u8 = false; h->launch_wire = false;
-        if (lrc) return lrc;
+        LaunchOpts o;
+        o.actions = LaunchOpts::ACT_U8; o.wire = true;
+        if (int rc = launch(h, NGW_MODE_STEP, 1, reinterpret_cast<const int32_t*>(h->act_pin_dev + (size_t)slot * cap), nullptr, 0, 0, o)) return rc;
         // (no event for the action buffer's slot: this call returns only after the kernel has published its sequence number)
 #ifdef NGW_HOSTTRACE
         const double w2 = pnow();                                      // the launch is enqueued
@@ -448,19 +440,8 @@ int ngw_step_host_packed(ngw_handle* h, const int32_t* actions_host, void* block
         if (lrows && !h->wt_rows) {
             HIP_TRY(hipMemcpyAsync(h->lidar_host_rows, h->lidar_out, n * lrb, hipMemcpyDefault, h->stream));
             HIP_TRY(hipStreamSynchronize(h->stream));
-        } else {
-            bool seen = false;
-            for (uint32_t spin = 0; spin < (1u << 22); spin++) {          // (bounded: ~100 ms, then the stream is synchronised the usual way)
-                if (*sw == h->wt_seq) { seen = true; break; }
-#if defined(__x86_64__) || defined(__i386__)
-                __builtin_ia32_pause();
-#else
-                __asm__ __volatile__("" ::: "memory");
-#endif
-            }
-            if (!seen) HIP_TRY(hipStreamSynchronize(h->stream));
-        }
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);                       // the block's reads stay behind the poll
+        } else if (int rc = wait_seq(h, sw, h->wt_seq, 1u << 22)) return rc;   // (bounded: ~100 ms)
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);                       // the block's reads stay behind either wait
 #ifdef NGW_HOSTTRACE
         {
             const double w3 = pnow();                                  // the sequence word has arrived: the block is written
@@ -481,7 +462,7 @@ int ngw_step_host_packed(ngw_handle* h, const int32_t* actions_host, void* block
     // slice's actions are still being narrowed on the host and its step kernel runs.  The reference raises for a bad action id BEFORE it
     // touches any state (pogostick_v1_env.py:236), so every id is checked first (read-only pass); narrowing then goes slice by slice.
     int nsl = 1;
-    if (delta && h->nostage && (!h->lidar_fused || h->boards_on) && !h->hostres && !h->capturing) {
+    if (delta && step_in_place(h) && !h->hostres && !h->capturing) {
         // MEASURED AND NOT THE DEFAULT (profiles/r05_ab.md): at 65 536 envs one slice 64.8 us per call, two 84.4, four 100.0 - every slice costs
         // two launches, an event record and a cross-stream wait (~10 us), more than the overlap returns.  NGW_API_SLICES=<n> still selects it.
         nsl = h->api_slices > 0 ? h->api_slices : 1;
@@ -493,8 +474,7 @@ int ngw_step_host_packed(ngw_handle* h, const int32_t* actions_host, void* block
         for (size_t i = 0; i < n; i++) bad |= (uint32_t)actions_host[i] >= (uint32_t)A ? 1u : 0u;     // (branch-free: vectorises)
         if (bad) {
             h->act_next ^= 1;
-            for (size_t i = 0; i < n; i++)
-                if (actions_host[i] < 0 || actions_host[i] >= A) return fail(NGW_E_INVALID_ACTION, "%d is not in list", (int)actions_host[i]);   // pogostick_v1_env.py:236
+            if (int rc = check_actions(actions_host, n, A)) return rc;
         }
         if (!h->stream2) {
             HIP_TRY(hipStreamCreateWithFlags(&h->stream2, hipStreamNonBlocking));
@@ -535,16 +515,14 @@ int ngw_step_host_packed(ngw_handle* h, const int32_t* actions_host, void* block
     const uint32_t bad = narrow_actions(actions_host, a8, n, A);
     if (bad) {
         h->act_next ^= 1;
-        for (size_t i = 0; i < n; i++)
-            if (actions_host[i] < 0 || actions_host[i] >= A) return fail(NGW_E_INVALID_ACTION, "%d is not in list", (int)actions_host[i]);   // pogostick_v1_env.py:236
+        if (int rc = check_actions(actions_host, n, A)) return rc;
     }
 #ifdef NGW_HOSTTRACE
     const double p1 = pnow();                                          // actions validated and narrowed
 #endif
-    h->launch_use_action0 = false; h->launch_act_u8 = true;
-    const int lrc = launch(h, NGW_MODE_STEP, 1, reinterpret_cast<const int32_t*>(h->act_pin_dev + (size_t)slot * cap), nullptr, 0, 0);
-    h->launch_act_u8 = false;
-    if (lrc) return lrc;
+    LaunchOpts o;
+    o.actions = LaunchOpts::ACT_U8;
+    if (int rc = launch(h, NGW_MODE_STEP, 1, reinterpret_cast<const int32_t*>(h->act_pin_dev + (size_t)slot * cap), nullptr, 0, 0, o)) return rc;
     HIP_TRY(hipEventRecord(h->act_ev[slot], h->stream));
     uint8_t* const blk = static_cast<uint8_t*>(block);
     const void* const srcs[2] = {h->b.map, h->b.inv};
@@ -560,17 +538,7 @@ int ngw_step_host_packed(ngw_handle* h, const int32_t* actions_host, void* block
         if (!merged) HIP_TRY(ngw_diff_launch(&d, h->stream));
     } else {
         for (int r = 0; r < 2; r++) HIP_TRY(hipMemcpyAsync(blk + off[r], srcs[r], (size_t)nb[r], hipMemcpyDefault, h->stream));
-        if (h->host_delta) {                                          // (re-)seed the shadows: the block mirrors the state from here on
-            void* dev = nullptr;
-            bool ok = hipHostGetDevicePointer(&dev, block, 0) == hipSuccess && dev;
-            if (!ok) (void)hipGetLastError();                         // (a block that is not mapped into the GPU's address space: full copies)
-            for (int r = 0; r < 2 && ok; r++) {
-                if (!h->shadow[r]) ok = dev_alloc(h, &h->shadow[r], (size_t)((nb[r] + 255) & ~(uint64_t)255)) == NGW_OK;
-                if (ok) HIP_TRY(hipMemcpyAsync(h->shadow[r], srcs[r], (size_t)nb[r], hipMemcpyDeviceToDevice, h->stream));
-            }
-            h->mirror_block = ok ? block : nullptr; h->mirror_dev = static_cast<uint8_t*>(dev);
-            h->shadow_stale = false;
-        }
+        if (h->host_delta) { if (int rc = seed_shadows(h, block, 2, srcs, nb)) return rc; }
     }
     NgwWire w = {};
     w.loc = h->b.loc; w.facing = h->b.facing; w.selected = h->b.selected; w.reward = h->b.reward; w.done = h->b.done; w.info = h->b.info; w.flags = h->b.flags;
@@ -615,8 +583,7 @@ int ngw_pack_layout(ngw_handle* h, uint64_t* offsets8) {
 int ngw_pack_obs(ngw_handle* h, void* payload_dev) {
     if (!h || !payload_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if ((uintptr_t)payload_dev & 15u) return fail(NGW_E_INVALID_ARG, "payload must be 16-byte aligned");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     PackSection sec[7]; uint64_t offs[8];
     pack_sections(h, sec, offs);
     NgwPack p = {};
@@ -632,8 +599,7 @@ int ngw_unpack_obs(ngw_handle* h, const void* payloads_dev, int32_t world, int8_
                    int32_t* reward, uint8_t* done, uint32_t* info) {
     if (!h || !payloads_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (world < 1) return fail(NGW_E_INVALID_ARG, "world %d must be >= 1", world);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     PackSection sec[7]; uint64_t offs[8];
     pack_sections(h, sec, offs);
     uint8_t* const dsts[7] = {reinterpret_cast<uint8_t*>(map), reinterpret_cast<uint8_t*>(loc), reinterpret_cast<uint8_t*>(facing),
@@ -658,8 +624,7 @@ int ngw_get_state(ngw_handle* h, int64_t first, int64_t count, int8_t* map, int3
                   int32_t* selected, int32_t* step_count, uint32_t* episode) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (first < 0 || count < 0 || first + count > h->n) return fail(NGW_E_INVALID_ARG, "env range [%lld, +%lld) out of bounds", (long long)first, (long long)count);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     const size_t n = (size_t)count, f = (size_t)first, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
     D2H(map, h->b.map + f * S2, n * S2);
     D2H(loc, h->b.loc + f * 2, n * 2 * sizeof(int32_t));
@@ -706,12 +671,8 @@ int ngw_set_state(ngw_handle* h, int64_t first, int64_t count, const int8_t* map
             sel[i] = (uint8_t)selected[i];
         }
     }
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
-    h->solo_mirror_valid = false;
-    h->mirror_valid = false;
-    h->act_mask_fresh = false;
-    if (map) h->brd_dirty = true;                    // (boards mode: the bit rows are rebuilt before the next step launch)
+    if (int rc = enter(h)) return rc;
+    state_written(h, map ? WROTE_MAPS : 0);          // (boards mode: the bit rows are rebuilt before the next step launch)
     H2D(h->b.map + f * S2, map, n * S2);
     H2D(h->b.loc + f * 2, loc, n * 2 * sizeof(int32_t));
     H2D(h->b.facing + f, facing, n * sizeof(int32_t));

@@ -7,7 +7,7 @@ using namespace ngwh;
 int capture_graph(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride, int32_t n_steps);
 
 namespace {
-int launch_reset_fast(ngw_handle* h, int mode, const uint8_t* mask_dev, bool* taken);
+int launch_reset_fast(ngw_handle* h, int mode, const uint8_t* mask_dev, uint32_t seq, bool* taken);
 int refill_launches(ngw_handle* h, bool* fast);
 int rollout_chunks(ngw_handle* h, int mode, int32_t n_steps, const int32_t* actions_dev, uint64_t action_seed, int64_t t0, int64_t step_stride);
 }
@@ -150,11 +150,68 @@ int launch_refill(ngw_handle* h) {
     return refill_launches(h, &fast);
 }
 
-int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, const uint8_t* mask_dev, uint64_t action_seed, int64_t t0) {
+int enter(ngw_handle* h) {
+    HIP_TRY(hipSetDevice(h->device));
+    return h->solo_running ? solo_stop(h) : NGW_OK;
+}
+
+// The state in HBM was (or is about to be, on the handle's stream) written by something other than the path that keeps a derived copy
+// current.  The ONE place that knows what the handle derives from the state:
+//   solo_mirror_valid  the one-env loop's host mirror (h->mir) holds the state: the next loop start copies it from the device again
+//   mirror_valid       the caller's page-locked block (ngw_step_host / _packed) mirrors the state: the next host step copies everything
+//                      and re-seeds the delta shadows, which also ends shadow_stale - that flag only means something under mirror_valid
+//   act_mask_fresh     the mask words describe the state: ngw_action_mask runs the kernel again
+//   brd_dirty          the main set's bit rows do not describe its maps: ensure_boards rebuilds them before the next reader
+// Writers differ in two ways that matter, and `how` names them:
+//   WROTE_MAPS          maps changed without their bit rows (ngw_set_state with a map, a snapshot restore, a fused rollout - it steps the
+//                       maps in LDS).  Step and reset kernels keep the rows themselves; ngw_set_state without a map touches none.
+//   WROTE_BY_SOLO_LOOP  the one-env loop committed a step: solo_step applies the same step to the host mirror, which stays valid.
+// Everything else the call sites used to differ in was accidental and is gone: a slice of a batched step did not clear
+// solo_mirror_valid and solo_step did not clear mirror_valid (neither flag is read on a handle that takes the other path; clearing is the
+// safe side), the bit rows were marked only in boards mode (brd_dirty is read only in boards mode, and switching it on marks them anyway).
+// A path that has just made one of these valid again assigns it itself, AFTER its own launch() (the host steps, launch_act_mask,
+// solo_start, ngw_reset_host).  since_refill is not a fact about the state but a count of consumed prepared rows: steps_since_refill.
+void state_written(ngw_handle* h, unsigned how) {
+    if (!(how & WROTE_BY_SOLO_LOOP)) h->solo_mirror_valid = false;
+    h->mirror_valid = false;
+    h->act_mask_fresh = false;
+    if (how & WROTE_MAPS) h->brd_dirty = true;
+}
+
+int ensure_boards(ngw_handle* h) {
+    if (!h->boards_on || !h->brd_dirty) return NGW_OK;
+    if (int rc = rebuild_boards(h, h->b.map, h->b.brd, h->n_pad)) return rc;
+    h->brd_dirty = false;
+    return NGW_OK;
+}
+
+// The observation that must be current right after a wholesale rewrite of the state (an explicit reset, a snapshot restore): two
+// whole-batch launches in boards mode - stale bit rows rebuilt, then the O(1) lidar on them - or the marched lidar launch.
+int refresh_fused_obs(ngw_handle* h) {
+    if (h->boards_on) {
+        if (int rc = ensure_boards(h)) return rc;
+        return launch_lidar_boards(h);
+    }
+    if (h->lidar_fused && h->lidar_len && h->lidar_lds) {
+        NgwLaunch a = h->lidar_proto;
+        a.b = h->b;
+        HIP_TRY(ngw_lidar_launch(&a, h->map_mode, (unsigned)(h->n_pad / NGW_EPB), h->lidar_lds, h->stream));
+    }
+    return NGW_OK;
+}
+
+// Prepared next episodes: every `cadence` batched steps (and right after a wholesale rewrite, which counts as a whole cadence) one more
+// launch refills the shadow rows that resets have consumed since.  Same stream, so it is ordered between the steps.
+int steps_since_refill(ngw_handle* h, int k) {
+    if (h->prefetch_every <= 0) return NGW_OK;
+    h->since_refill += k;
+    return h->since_refill >= h->cadence ? launch_refill(h) : NGW_OK;
+}
+
+int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, const uint8_t* mask_dev, uint64_t action_seed, int64_t t0, const LaunchOpts& o) {
     if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
-    h->solo_mirror_valid = false;                     // (a per-launch step / reset refreshes the WHOLE mirror itself; the loop's host side starts from a copy)
-    h->mirror_valid = false;                          // (ngw_step_host's delta path sets it again after its own launch)
-    h->act_mask_fresh = false;                        // (every launch here changes the state; a step with masks on recomputes them below)
+    const bool rollout = mode == NGW_MODE_ROLLOUT || mode == NGW_MODE_ROLLOUT_ACT;
+    state_written(h, rollout ? WROTE_MAPS : 0);       // (every launch here changes the state; a step with masks on recomputes them below)
     NgwLaunch a = h->proto;
     a.b = h->b;
     a.mode = mode;
@@ -165,29 +222,28 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
     a.horizon = h->horizon;
     a.action_seed = action_seed;
     a.t0 = t0;
-    a.seq = h->launch_seq;
-    a.action0 = h->launch_action0; a.use_action0 = h->launch_use_action0 ? 1 : (h->launch_act_u8 ? 2 : 0);
+    a.seq = o.seq;
+    a.action0 = o.action0; a.use_action0 = o.actions;
+    a.row_reward = o.row_reward; a.row_done = o.row_done; a.row_stride = o.row_stride; a.acc = o.acc;
     const unsigned grid = (unsigned)(h->n_pad / NGW_EPB);
     bool taken = false;
     // Boards mode (fused lidar on the occupancy bit rows): steps run the in-place kernel with the bit-row epilogue; an explicit reset runs
     // the plain new-episode kernels and is followed by the rebuild of the bit rows and the observation launch; a fused rollout still ends in
     // the staged march (its maps are in LDS anyway) and leaves the bit rows stale until the next step launch wants them.
     const bool boards = h->boards_on;
-    if (boards && h->brd_dirty && mode == NGW_MODE_STEP) {
-        if (int rc = rebuild_boards(h, h->b.map, h->b.brd, h->n_pad)) return rc;
-        h->brd_dirty = false;
-    }
-    bool fast_took = false;
+    const int ext = h->ext ? NGW_FEAT_EXT : 0;
+    if (mode == NGW_MODE_STEP) { if (int rc = ensure_boards(h)) return rc; }
     // action masks of the post-step state: fused into the plain step kernels (both forms), the standalone kernel behind the others
-    const bool want_mask = mode == NGW_MODE_STEP && h->act_mask_on && !h->act_mask_defer && h->act_mask;
+    const bool want_mask = mode == NGW_MODE_STEP && h->act_mask_on && o.masks && h->act_mask;
     bool fused_mask = false;
-    if (mode == NGW_MODE_RESET) { if (int rc = launch_reset_fast(h, NGW_MODE_RESET, mask_dev, &taken)) return rc; fast_took = taken; }
-    if (!taken && mode == NGW_MODE_STEP && h->nostage && (!h->lidar_fused || boards)) {   // maps read in place: no-stage step kernel
+    if (mode == NGW_MODE_RESET) { if (int rc = launch_reset_fast(h, NGW_MODE_RESET, mask_dev, o.seq, &taken)) return rc; }
+    if (!taken && mode == NGW_MODE_STEP && step_in_place(h)) {
         NgwLaunch q = h->ns_proto;
         q.b = h->b; q.mode = mode; q.n_steps = 1; q.actions = actions_dev; q.autoreset = h->autoreset; q.horizon = h->horizon; q.stamps = h->proto.stamps;
-        q.seq = h->launch_wire ? h->wt_seq : h->launch_seq; q.action0 = h->launch_action0; q.use_action0 = h->launch_use_action0 ? 1 : (h->launch_act_u8 ? 2 : 0);
-        fused_mask = want_mask && h->act_mask_fused && !boards && !h->launch_wire;
-        HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, 8 | (h->ext ? 2 : 0) | (boards ? 1 : 0) | (h->launch_wire ? 16 : 0) | (fused_mask ? 32 : 0), grid, h->ns_lds, h->stream));
+        q.seq = o.wire ? h->wt_seq : o.seq; q.action0 = o.action0; q.use_action0 = o.actions;
+        fused_mask = want_mask && h->act_mask_fused && !boards && !o.wire;
+        HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, NGW_FEAT_NOSTAGE | ext | (boards ? NGW_FEAT_LIDAR : 0) | (o.wire ? NGW_FEAT_WIRE : 0) | (fused_mask ? NGW_FEAT_MASK : 0),
+                           grid, h->ns_lds, h->stream));
         taken = true;
     }
     if (!taken) {
@@ -197,26 +253,16 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
         const bool march = h->lidar_fused && !(boards && mode == NGW_MODE_RESET);
         if (!boards) a.b.brd = nullptr;                                // (the general kernel writes bit rows only while somebody reads them)
         fused_mask = want_mask && h->act_mask_fused && !march;
-        HIP_TRY(ngw_launch(h->dspec, &a, h->map_mode, (march ? 1 : 0) | (h->ext ? 2 : 0) | (fused_mask ? 32 : 0), grid, h->lds_bytes, h->stream));
+        HIP_TRY(ngw_launch(h->dspec, &a, h->map_mode, (march ? NGW_FEAT_LIDAR : 0) | ext | (fused_mask ? NGW_FEAT_MASK : 0), grid, h->lds_bytes, h->stream));
     }
-    if (boards && mode == NGW_MODE_RESET) {
-        // (the dedicated new-episode kernel wrote the bit rows of the maps it made or copied; a masked reset leaves the others as they were,
-        //  which is only right if they were right before: a stale set is rebuilt whole)
-        (void)fast_took;
-        if (h->brd_dirty) { if (int rc = rebuild_boards(h, h->b.map, h->b.brd, h->n_pad)) return rc; }
-        h->brd_dirty = false;
-        if (int rc = launch_lidar_boards(h)) return rc;
-    }
-    if (boards && (mode == NGW_MODE_ROLLOUT || mode == NGW_MODE_ROLLOUT_ACT)) h->brd_dirty = true;
+    // (boards mode: the new-episode kernels wrote the bit rows of the maps they made or copied; a masked reset leaves the others as they
+    //  were, which is only right if they were right before: a stale set is rebuilt whole.  Without the bit rows the reset kernel marched.)
+    if (boards && mode == NGW_MODE_RESET) { if (int rc = refresh_fused_obs(h)) return rc; }
     if (fused_mask) h->act_mask_fresh = true;
     else if (want_mask) { if (int rc = launch_act_mask(h)) return rc; }   // (same stream: right behind the step)
-    if (h->prefetch_every > 0 && (mode == NGW_MODE_STEP || mode == NGW_MODE_RESET || mode == NGW_MODE_ROLLOUT || mode == NGW_MODE_ROLLOUT_ACT)) {
-        // Prepared next episodes: every `prefetch_every` batched steps (and right after an explicit reset) one more launch
-        // refills the shadow rows that resets have consumed since.  Same stream, so it is ordered between the steps.
-        h->since_refill += mode == NGW_MODE_RESET ? h->prefetch_every : n_steps;
-        if (h->since_refill >= h->cadence) return launch_refill(h);
-    }
-    return NGW_OK;
+    if (mode == NGW_MODE_RESET) return steps_since_refill(h, h->prefetch_every);
+    if (mode == NGW_MODE_STEP || rollout) return steps_since_refill(h, n_steps);
+    return NGW_OK;                                     // (the diagnostic modes)
 }
 
 // One SLICE [first, first + count) of a batched step through the in-place step kernel (first a multiple of 64): every array pointer of
@@ -225,12 +271,8 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
 // slices of ONE step back to back and then calls step_slices_done.
 int launch_step_slice(ngw_handle* h, const uint8_t* actions_u8_dev, int64_t first, int64_t count) {
     if (first == 0) {
-        h->mirror_valid = false;
-        h->act_mask_fresh = false;
-        if (h->boards_on && h->brd_dirty) {
-            if (int rc = rebuild_boards(h, h->b.map, h->b.brd, h->n_pad)) return rc;
-            h->brd_dirty = false;
-        }
+        state_written(h);
+        if (int rc = ensure_boards(h)) return rc;
     }
     const int64_t S2 = h->proto.S2, K = h->proto.K, BS = h->proto.BS;
     NgwLaunch q = h->ns_proto;
@@ -243,7 +285,7 @@ int launch_step_slice(ngw_handle* h, const uint8_t* actions_u8_dev, int64_t firs
     q.mode = NGW_MODE_STEP; q.n_steps = 1; q.actions = reinterpret_cast<const int32_t*>(actions_u8_dev); q.autoreset = h->autoreset; q.horizon = h->horizon;
     q.stamps = nullptr; q.seq = 0; q.action0 = 0; q.use_action0 = 2;
     const unsigned grid = (unsigned)((count + NGW_EPB - 1) / NGW_EPB);
-    HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, 8 | (h->ext ? 2 : 0) | (h->boards_on ? 1 : 0), grid, h->ns_lds, h->stream));
+    HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, NGW_FEAT_NOSTAGE | (h->ext ? NGW_FEAT_EXT : 0) | (h->boards_on ? NGW_FEAT_LIDAR : 0), grid, h->ns_lds, h->stream));
     return NGW_OK;
 }
 
@@ -305,13 +347,6 @@ int solo_start(ngw_handle* h, int32_t commit0, uint32_t k0) {
     h->solo_starts++;
     return NGW_OK;
 }
-inline void cpu_pause() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#else
-    __asm__ __volatile__("" ::: "memory");
-#endif
-}
 }  // namespace
 
 int solo_stop(ngw_handle* h) {
@@ -371,7 +406,7 @@ int solo_step(ngw_handle* h, int32_t action) {
     // ---- post the command: the loop commits it and speculates from the new state
     h->solo_last_action = action;
     h->solo_seq++;
-    h->act_mask_fresh = false;                                       // (the masks of this state come from the loop's records: ngw_get_action_mask)
+    state_written(h, WROTE_BY_SOLO_LOOP);                            // (the masks of this state come from the loop's records: ngw_get_action_mask)
     if (out[1]) {                                                    // (the loop has ended meanwhile: start the next one with the commit)
         HIP_TRY(hipStreamSynchronize(h->stream));
         h->solo_running = false;
@@ -385,11 +420,7 @@ int solo_step(ngw_handle* h, int32_t action) {
 
 int step_slices_done(ngw_handle* h) {
     if (h->act_mask_on && h->act_mask) { if (int rc = launch_act_mask(h)) return rc; }
-    if (h->prefetch_every > 0) {
-        h->since_refill += 1;
-        if (h->since_refill >= h->cadence) return launch_refill(h);
-    }
-    return NGW_OK;
+    return steps_since_refill(h, 1);
 }
 
 void drop_graph(ngw_handle* h) {
@@ -406,12 +437,12 @@ void drop_graph(ngw_handle* h) {
 namespace {
 
 // mode = NGW_MODE_RESET (mask_dev or nullptr) / NGW_MODE_REFILL; returns 1 if the dedicated kernel took the launch
-int launch_reset_fast(ngw_handle* h, int mode, const uint8_t* mask_dev, bool* taken) {
+int launch_reset_fast(ngw_handle* h, int mode, const uint8_t* mask_dev, uint32_t seq, bool* taken) {
     *taken = false;
     if (h->rf_nw < 0 || (h->lidar_fused && !h->boards_on)) return NGW_OK;   // (the march rides on the general kernel; the bit-row lidar is its own launch)
     NgwResetFast a = h->rf;
     a.main = h->b; a.nx = h->prefetch_every > 0 ? h->nx : NgwNx{}; a.mode = mode; a.reset_mask = mask_dev; a.stamps = h->proto.stamps;
-    a.seq = mode == NGW_MODE_RESET ? h->launch_seq : 0u;
+    a.seq = seq;
     a.boards = h->boards_on ? 1 : 0; a.BS = h->proto.BS;                            // (boards mode: the kernel writes the bit rows of its maps itself)
     HIP_TRY(ngw_reset_fast_launch(h->dspec, &a, h->rf_nw, h->rf_additem, (unsigned)(h->n_pad / NGW_EPB), h->rf_lds, h->stream));
     *taken = true;
@@ -429,7 +460,7 @@ int refill_launches(ngw_handle* h, bool* fast) {
     }
     h->refill_count++;
     bool taken = false;
-    if (int rc = launch_reset_fast(h, NGW_MODE_REFILL, nullptr, &taken)) return rc;
+    if (int rc = launch_reset_fast(h, NGW_MODE_REFILL, nullptr, 0u, &taken)) return rc;
     if (taken) { *fast = true; return NGW_OK; }
     // the general kernel prepares one slot per launch (its shadow set is the launch's buffer set)
     const size_t np = (size_t)h->n_pad, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
@@ -463,12 +494,12 @@ int rollout_chunks(ngw_handle* h, int mode, int32_t n_steps, const int32_t* acti
     }
     for (int32_t done = 0; done < n_steps; done += chunk) {
         const int32_t k = n_steps - done < chunk ? n_steps - done : chunk;
-        h->proto.row_reward = h->row_reward ? h->row_reward + (int64_t)done * h->row_stride : nullptr;
-        h->proto.row_done = h->row_done ? h->row_done + (int64_t)done * h->row_stride : nullptr;
-        h->proto.row_stride = h->row_stride; h->proto.acc = h->acc;
-        const int rc = mode == NGW_MODE_ROLLOUT ? launch(h, mode, k, nullptr, nullptr, action_seed, t0 + done)
-                                                : launch(h, mode, k, actions_dev + (int64_t)done * step_stride, nullptr, 0, step_stride);
-        h->proto.row_reward = nullptr; h->proto.row_done = nullptr; h->proto.acc = nullptr;
+        LaunchOpts o;
+        o.row_reward = h->row_reward ? h->row_reward + (int64_t)done * h->row_stride : nullptr;
+        o.row_done = h->row_done ? h->row_done + (int64_t)done * h->row_stride : nullptr;
+        o.row_stride = h->row_stride; o.acc = h->acc;
+        const int rc = mode == NGW_MODE_ROLLOUT ? launch(h, mode, k, nullptr, nullptr, action_seed, t0 + done, o)
+                                                : launch(h, mode, k, actions_dev + (int64_t)done * step_stride, nullptr, 0, step_stride, o);
         if (rc) return rc;
     }
     return NGW_OK;
@@ -479,34 +510,32 @@ int rollout_chunks(ngw_handle* h, int mode, int32_t n_steps, const int32_t* acti
 int capture_graph(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride, int32_t n_steps) {
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);
-    if (h->boards_on && h->brd_dirty) {               // (a rebuild captured into the graph would run with every replay)
-        if (int rc = rebuild_boards(h, h->b.map, h->b.brd, h->n_pad)) return rc;
-        h->brd_dirty = false;
-    }
+    if (int rc = ensure_boards(h)) return rc;         // (a rebuild captured into the graph would run with every replay)
     // A graph much shorter than the refill cadence is captured WITHOUT a refill: closing every replay of a 20-step graph with one (below) would
     // run the ~21 us launch four times as often as the cadence asks for.  Such a graph is "open": ngw_graph_launch counts its steps and issues
     // the refill between replays, eagerly, whenever the next replay would overrun the cadence.
     const bool open = h->prefetch_every > 0 && n_steps * 2 <= h->cadence;
-    const int since0 = h->since_refill;
-    const bool mask_fresh0 = h->act_mask_fresh;       // (capturing runs nothing: whether the masks describe the state stays as it was)
+    // Capturing runs nothing: what its launch() calls book as done is put back to `before` when the capture ends - whether the masks
+    // describe the state, and, for an open graph, the steps since the last refill.
+    const struct { int since_refill; bool act_mask_fresh; } before = {h->since_refill, h->act_mask_fresh};
     h->since_refill = 0;                              // the captured refill cadence starts from a known phase
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     h->capturing = true;                              // (the depth and cadence the handle has adapted to so far are the ones captured)
     int rc = NGW_OK;
     for (int i = 0; i < n_steps && !rc; i++) {
-        h->act_mask_defer = i < n_steps - 1;                                    // (one replay leaves the masks of the state it ends in)
-        rc = launch(h, NGW_MODE_STEP, 1, actions_dev + (int64_t)i * step_stride, nullptr, 0, 0);
+        LaunchOpts o;
+        o.masks = i == n_steps - 1;                                             // (one replay leaves the masks of the state it ends in)
+        rc = launch(h, NGW_MODE_STEP, 1, actions_dev + (int64_t)i * step_stride, nullptr, 0, 0, o);
     }
-    h->act_mask_defer = false;
     // every replay must leave the refill cadence where it found it: a graph shorter than (or not a multiple of) the cadence
     // ends with one more refill, otherwise a replayed graph would never re-prepare the episodes its steps consume
     if (!rc && h->prefetch_every > 0 && h->since_refill > 0 && !open) {
         h->since_refill = h->prefetch_every;
         rc = launch_refill(h);
     }
-    if (open) h->since_refill = since0;               // (nothing ran: the steps since the last refill are what they were)
     h->capturing = false;
-    h->act_mask_fresh = mask_fresh0;
+    h->act_mask_fresh = before.act_mask_fresh;
+    if (open) h->since_refill = before.since_refill;
     h->graph_act_mask = h->act_mask_on;
     hipError_t e = hipStreamEndCapture(h->stream, &h->graph);
     if (rc) { drop_graph(h); return rc; }
@@ -551,8 +580,7 @@ int ngw_get_reset_prefetch(ngw_handle* h, int32_t* every_n_steps) {
 int ngw_set_reset_prefetch(ngw_handle* h, int32_t every_n_steps) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (every_n_steps < 0) return fail(NGW_E_INVALID_ARG, "every_n_steps must be >= 0");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);                                   // captured launches bake the cadence in
     if (every_n_steps > 0 && !h->nx.episode) { if (int rc = alloc_nx(h, h->depth, true)) return rc; }
@@ -568,8 +596,7 @@ int ngw_set_reset_prefetch_depth(ngw_handle* h, int32_t depth) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     static_assert(NGW_MAX_DEPTH == 8, "the depths accepted below");
     if (depth != 0 && depth != 1 && depth != 2 && depth != 4 && depth != 8) return fail(NGW_E_INVALID_ARG, "depth must be 0 (automatic), 1, 2, 4 or 8");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);                                   // captured launches bake the shadow pointers in
     h->depth_user = depth != 0;
@@ -591,13 +618,13 @@ int ngw_get_reset_prefetch_depth(ngw_handle* h, int32_t* depth) {
 
 int ngw_step_kernel_info(ngw_handle* h, int32_t* map_in_place) {
     if (!h || !map_in_place) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    *map_in_place = (h->nostage && (!h->lidar_fused || h->boards_on)) ? 1 : 0;     // (the rule launch() applies to NGW_MODE_STEP)
+    *map_in_place = step_in_place(h) ? 1 : 0;
     return NGW_OK;
 }
 
 int ngw_reset(ngw_handle* h, const uint8_t* mask_host) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = enter(h)) return rc;
     const uint8_t* m = nullptr;
     int slot = -1;
     if (mask_host) {
@@ -626,29 +653,17 @@ int ngw_reset(ngw_handle* h, const uint8_t* mask_host) {
 int ngw_reset_host(ngw_handle* h, const uint8_t* mask_host, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv, uint8_t* selected,
                    int32_t* step_count, uint32_t* error_flags) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = enter(h)) return rc;
     const size_t n = (size_t)h->n, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
     if (h->hostres && !mask_host) {
         // Single-wavefront handle: ONE launch that ends by copying the wave's rows into the host mirror; completion polled on the
         // word the reset kernel writes when its stores are out (the refill that re-prepares the consumed episode follows on the
         // stream and is NOT waited for), results read from the mirror.
         h->step_seq = h->step_seq + 1u ? h->step_seq + 1u : 1u;
-        h->launch_seq = h->step_seq;
-        const int lrc = launch(h, NGW_MODE_RESET, 1, nullptr, nullptr, 0, 0);
-        h->launch_seq = 0;
-        if (lrc) return lrc;
-        volatile uint32_t* sp = h->b.flags_host + NGW_SEQ_WORD;
-        bool seen = false;
-        for (uint32_t spin = 0; spin < (1u << 21); spin++) {
-            if (*sp == h->step_seq) { seen = true; break; }
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#else
-            __asm__ __volatile__("" ::: "memory");
-#endif
-        }
-        if (!seen) HIP_TRY(hipStreamSynchronize(h->stream));
-        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        LaunchOpts o;
+        o.seq = h->step_seq;
+        if (int rc = launch(h, NGW_MODE_RESET, 1, nullptr, nullptr, 0, 0, o)) return rc;
+        if (int rc = wait_seq(h, h->b.flags_host + NGW_SEQ_WORD, h->step_seq, 1u << 21)) return rc;
         h->solo_mirror_valid = true;                                    // (the reset kernel has just written every row of the mirror: a one-env step loop starts from it without a copy)
         const NgwMirror& m = h->mir;
         if (map) memcpy(map, m.map, n * S2);
@@ -675,12 +690,8 @@ int ngw_reset_host(ngw_handle* h, const uint8_t* mask_host, int8_t* map, int32_t
 
 int ngw_step(ngw_handle* h, const int32_t* actions_host) {
     if (!h || !actions_host) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    const int A = h->spec.n_actions;
-    for (int64_t i = 0; i < h->n; i++)
-        if (actions_host[i] < 0 || actions_host[i] >= A)
-            return fail(NGW_E_INVALID_ACTION, "%d is not in list", (int)actions_host[i]);   // pogostick_v1_env.py:236
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = check_actions(actions_host, (size_t)h->n, h->spec.n_actions)) return rc;
+    if (int rc = enter(h)) return rc;
     // The caller's array may be pageable and is his again when this call returns: it goes (host to host) into one half of a
     // page-locked buffer and from there to the device by an asynchronous copy - no stream synchronisation (which would also wait
     // for a refill still running).  A half is rewritten only after the copy that read it last has finished (an event per half).
@@ -701,19 +712,18 @@ int ngw_step(ngw_handle* h, const int32_t* actions_host) {
 
 int ngw_step_device(ngw_handle* h, const int32_t* actions_dev) {
     if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = enter(h)) return rc;
     return launch(h, NGW_MODE_STEP, 1, actions_dev, nullptr, 0, 0);
 }
 
 int ngw_step_device_many(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride, int32_t n_steps) {
     if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "n_steps must be >= 1");
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = enter(h)) return rc;
     for (int32_t i = 0; i < n_steps; i++) {
-        h->act_mask_defer = i < n_steps - 1;                                    // (masks only for the state the call ends in)
-        const int rc = launch(h, NGW_MODE_STEP, 1, actions_dev + (int64_t)i * step_stride, nullptr, 0, 0);
-        h->act_mask_defer = false;
-        if (rc) return rc;
+        LaunchOpts o;
+        o.masks = i == n_steps - 1;                                             // (masks only for the state the call ends in)
+        if (int rc = launch(h, NGW_MODE_STEP, 1, actions_dev + (int64_t)i * step_stride, nullptr, 0, 0, o)) return rc;
     }
     return NGW_OK;
 }
@@ -721,7 +731,7 @@ int ngw_step_device_many(ngw_handle* h, const int32_t* actions_dev, int64_t step
 int ngw_rollout(ngw_handle* h, int32_t n_steps, uint64_t action_seed, int64_t t0) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "n_steps must be >= 1");
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = enter(h)) return rc;
     return rollout_chunks(h, NGW_MODE_ROLLOUT, n_steps, nullptr, action_seed, t0, 0);
 }
 
@@ -729,14 +739,13 @@ int ngw_rollout_actions(ngw_handle* h, const int32_t* actions_dev, int64_t step_
     if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "n_steps must be >= 1");
     if (step_stride < h->n) return fail(NGW_E_INVALID_ARG, "step_stride %lld is smaller than n_envs", (long long)step_stride);
-    HIP_TRY(hipSetDevice(h->device));
+    if (int rc = enter(h)) return rc;
     return rollout_chunks(h, NGW_MODE_ROLLOUT_ACT, n_steps, actions_dev, 0, 0, step_stride);
 }
 
 int ngw_set_terminal_capture(ngw_handle* h, int enable) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (enable && !h->term.map) {
         const size_t np = (size_t)h->n_pad, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
@@ -762,8 +771,7 @@ int ngw_set_terminal_capture(ngw_handle* h, int enable) {
 int ngw_get_terminal_obs(ngw_handle* h, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (!h->term.map) return fail(NGW_E_INVALID_ARG, "ngw_get_terminal_obs before ngw_set_terminal_capture(h, 1)");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     const size_t n = (size_t)h->n, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
     D2H(map, h->term.map, n * S2);
     D2H(loc, h->term.loc, n * 2 * sizeof(int32_t));
@@ -786,8 +794,7 @@ int ngw_terminal_device_ptrs(ngw_handle* h, void** map, void** loc, void** facin
 int ngw_rollout_outputs(ngw_handle* h, int32_t* reward_rows_dev, uint8_t* done_rows_dev, int64_t row_stride, int accumulate) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if ((reward_rows_dev || done_rows_dev) && row_stride < h->n) return fail(NGW_E_INVALID_ARG, "row_stride %lld is smaller than n_envs", (long long)row_stride);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->row_reward = reward_rows_dev; h->row_done = done_rows_dev; h->row_stride = row_stride;
     if (accumulate && !h->acc) { if (int rc = dev_alloc(h, &h->acc, (size_t)h->n_pad * 4)) return rc; }
@@ -799,8 +806,7 @@ int ngw_rollout_outputs(ngw_handle* h, int32_t* reward_rows_dev, uint8_t* done_r
 int ngw_episode_stats(ngw_handle* h, int32_t* run_return, int32_t* run_length, int32_t* sum_return, int32_t* n_episodes, int clear) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (!h->acc) return fail(NGW_E_INVALID_ARG, "ngw_episode_stats before ngw_rollout_outputs(..., accumulate = 1)");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     int32_t* const dst[4] = {run_return, run_length, sum_return, n_episodes};
     for (int i = 0; i < 4; i++)
         if (dst[i]) HIP_TRY(hipMemcpyAsync(dst[i], h->acc + (size_t)i * h->n_pad, (size_t)h->n * sizeof(int32_t), hipMemcpyDefault, h->stream));
@@ -812,17 +818,14 @@ int ngw_episode_stats(ngw_handle* h, int32_t* run_return, int32_t* run_length, i
 int ngw_graph_build(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride, int32_t n_steps) {
     if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "n_steps must be >= 1");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }    // (a one-env handle's resident loop: its stream is busy until it ends)
+    if (int rc = enter(h)) return rc;
     return capture_graph(h, actions_dev, step_stride, n_steps);
 }
 
 int ngw_graph_launch(ngw_handle* h, int32_t reps) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (!h->graph_exec) return fail(NGW_E_INVALID_ARG, "no graph: call ngw_graph_build first");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
-    h->solo_mirror_valid = false;
+    if (int rc = enter(h)) return rc;
     for (int i = 0; i < reps; i++) {
         // A captured graph holds the prepared-episode depth and the refill cadence it was captured with.  The refills inside it
         // keep reporting, so the host keeps adapting between replays (default setting only); when that changed something the
@@ -832,12 +835,12 @@ int ngw_graph_launch(ngw_handle* h, int32_t reps) {
             const int32_t* acts = h->graph_actions; const int64_t stride = h->graph_stride; const int32_t k = h->graph_steps;
             if (int rc = capture_graph(h, acts, stride, k)) return rc;
         }
-        h->mirror_valid = false;
+        state_written(h);
         if (h->graph_open && h->prefetch_every > 0 && h->since_refill + h->graph_steps > h->cadence) {
             if (int rc = launch_refill(h)) return rc;                               // (an open graph: the cadence is kept between its replays)
         }
         HIP_TRY(hipGraphLaunch(h->graph_exec, h->stream));
-        h->act_mask_fresh = h->graph_act_mask;
+        if (h->graph_act_mask) h->act_mask_fresh = true;
         if (h->graph_open) h->since_refill += h->graph_steps;
     }
     return NGW_OK;

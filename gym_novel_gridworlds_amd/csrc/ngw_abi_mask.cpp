@@ -27,14 +27,6 @@ int launch_act_mask(ngw_handle* h) {
 
 namespace {
 
-inline void cpu_pause() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#else
-    __asm__ __volatile__("" ::: "memory");
-#endif
-}
-
 // The one-env loop speculates every action from the committed state: bit 0 of record a's info word is exactly `result` of step(a).  Returns
 // false when the records do not belong to the host's state (the loop ended before it took the last command): the caller stops the loop and
 // runs the kernel instead.  Waits for the records like solo_step does, never stops the loop.
@@ -64,8 +56,7 @@ extern "C" {
 
 int ngw_set_action_mask(ngw_handle* h, int enable) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     if (enable) { if (int rc = alloc_act_mask(h)) return rc; }
     h->act_mask_on = enable != 0;
     return NGW_OK;
@@ -73,8 +64,7 @@ int ngw_set_action_mask(ngw_handle* h, int enable) {
 
 int ngw_action_mask(ngw_handle* h) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     if (!h->act_mask_fresh) { if (int rc = launch_act_mask(h)) return rc; }
     return NGW_OK;
 }

@@ -67,8 +67,7 @@ int ngw_lidar_configure(ngw_handle* h, const ngw_lidar_cfg* cfg) {
                 if (cfg->dr[f][b][k] > cfg->max_range || cfg->dr[f][b][k] < -cfg->max_range || cfg->dc[f][b][k] > cfg->max_range ||
                     cfg->dc[f][b][k] < -cfg->max_range)
                     return fail(NGW_E_INVALID_ARG, "lidar ray offset (%d, %d) beyond max_range %d", cfg->dr[f][b][k], cfg->dc[f][b][k], cfg->max_range);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);
     const int L = cfg->num_beams * cfg->n_chan + cfg->n_inv;
@@ -157,8 +156,7 @@ int ngw_lidar_configure(ngw_handle* h, const ngw_lidar_cfg* cfg) {
 int ngw_lidar_set_output(ngw_handle* h, int bits) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (bits != 8 && bits != 16 && bits != 32) return fail(NGW_E_INVALID_ARG, "lidar output format must be 32 (int32), 16 (int16) or 8 (packed: uint8 beams + int16 inventory)");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);                                   // captured launches bake the format in
     h->lidar_bits = bits;
@@ -189,8 +187,7 @@ int ngw_lidar_row_layout(ngw_handle* h, int32_t* row_bytes, int32_t* beam_bytes,
 int ngw_lidar_fuse(ngw_handle* h, int enable) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (enable && !h->lidar_len) return fail(NGW_E_INVALID_ARG, "ngw_lidar_fuse before ngw_lidar_configure");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     drop_graph(h);                                   // captured launches bake the LDS layout in
     if (enable && !h->general_ok) return fail(NGW_E_INVALID_ARG, "map_size %d: the fused lidar epilogue keeps a wavefront's 64 maps in LDS (> 160 KiB)", h->proto.S);
@@ -208,8 +205,7 @@ int ngw_lidar(ngw_handle* h) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (!h->lidar_len) return fail(NGW_E_INVALID_ARG, "ngw_lidar before ngw_lidar_configure");
     if (!h->lidar_lds) return fail(NGW_E_INVALID_ARG, "map_size %d: the lidar observation keeps a wavefront's 64 maps in LDS (> 160 KiB)", h->proto.S);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     NgwLaunch a = h->lidar_proto;
     a.b = h->b;
     HIP_TRY(ngw_lidar_launch(&a, h->map_mode, (unsigned)(h->n_pad / NGW_EPB), h->lidar_lds, h->stream));
@@ -219,8 +215,7 @@ int ngw_lidar(ngw_handle* h) {
 int ngw_get_lidar(ngw_handle* h, void* out_host) {
     if (!h || !out_host) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (!h->lidar_len) return fail(NGW_E_INVALID_ARG, "ngw_get_lidar before ngw_lidar_configure");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     NgwLaunch q{};
     lidar_format(h, q);
     HIP_TRY(hipMemcpyAsync(out_host, h->lidar_out, (size_t)h->n * (size_t)q.l_rb, hipMemcpyDefault, h->stream));
@@ -231,8 +226,7 @@ int ngw_get_lidar(ngw_handle* h, void* out_host) {
 int ngw_lidar_host_rows(ngw_handle* h, void* rows_host) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (rows_host && !h->lidar_len) return fail(NGW_E_INVALID_ARG, "ngw_lidar_host_rows before ngw_lidar_configure");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->lidar_host_rows = static_cast<uint8_t*>(rows_host);
     h->wt_block = nullptr;                           // (the step kernel's write-through targets are set up again)
@@ -250,8 +244,7 @@ int ngw_agent_view(ngw_handle* h, int view_size) {
     if (view_size < 1 || view_size > 127) return fail(NGW_E_INVALID_ARG, "view_size must be in 1..127");   // :99 'Increase the agent_view_size'
     const size_t W = 2 * (size_t)view_size + 1, bytes = (size_t)h->n * W * W;
     if (bytes + 4 > 0xffffffffull) return fail(NGW_E_INVALID_ARG, "agent view of %zu B exceeds the 4 GiB index range", bytes);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     if (view_size != h->view_size) {
         h->view_size = 0;
         if (bytes > h->view_cap) {
@@ -270,8 +263,7 @@ int ngw_agent_view(ngw_handle* h, int view_size) {
 int ngw_get_agent_view(ngw_handle* h, int8_t* out_host) {
     if (!h || !out_host) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (!h->view_size) return fail(NGW_E_INVALID_ARG, "ngw_get_agent_view before ngw_agent_view");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     const size_t W = 2 * (size_t)h->view_size + 1;
     HIP_TRY(hipMemcpyAsync(out_host, h->view_out, (size_t)h->n * W * W, hipMemcpyDefault, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));

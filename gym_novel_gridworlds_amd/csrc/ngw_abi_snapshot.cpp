@@ -1,7 +1,7 @@
 // ngw_abi_snapshot.cpp - device-side snapshots (see ngw_host.h): buffers of saved env states and the one kernel (ngw_snapshot.inc) that moves
-// rows between them and the state slab through index lists.  A restore changes the state behind the library's back-ups, so it does what
-// ngw_set_state does - ends the one-env loop, drops the host mirrors and the action masks, marks the occupancy bit rows stale - and then
-// refreshes a fused lidar observation and schedules a refill of the prepared next episodes, as ngw_reset does.
+// rows between them and the state slab through index lists.  A restore changes the state behind the library's back-ups, so it reports it
+// as ngw_set_state does (state_written), and then refreshes a fused lidar observation and schedules a refill of the prepared next
+// episodes, as ngw_reset does.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -54,8 +54,7 @@ int ngw_snapshot_create(ngw_handle* h, int64_t capacity, ngw_snapshot** out) {
     if (!h || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
     *out = nullptr;
     if (capacity < 1 || capacity > 0x7FFFFFFFll) return fail(NGW_E_INVALID_ARG, "snapshot capacity %lld outside [1, 2^31)", (long long)capacity);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     // one allocation, laid out like the state slab: every array 256-byte aligned, so a row is as aligned as its size allows
     const size_t cap = (size_t)capacity, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
     auto up = [](size_t b) { return (b + 255) & ~(size_t)255; };
@@ -85,8 +84,7 @@ int ngw_snapshot_create(ngw_handle* h, int64_t capacity, ngw_snapshot** out) {
 int ngw_snapshot_destroy(ngw_handle* h, ngw_snapshot* s) {
     if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));                         // (queued saves / restores may still use the buffer)
     for (size_t i = 0; i < h->snaps.size(); i++)
         if (h->snaps[i] == s) { h->snaps.erase(h->snaps.begin() + (long)i); break; }
@@ -100,8 +98,7 @@ int ngw_snapshot_save(ngw_handle* h, ngw_snapshot* s, const int32_t* envs_dev, c
     if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (count < 0 || count > s->cap) return fail(NGW_E_INVALID_ARG, "save of %lld states into a snapshot of %lld slots", (long long)count, (long long)s->cap);
     if (!envs_dev && count > h->n) return fail(NGW_E_INVALID_ARG, "save of %lld states from %lld envs", (long long)count, (long long)h->n);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }    // (the one-env loop: HBM holds the state once it has ended)
+    if (int rc = enter(h)) return rc;
     return move_rows(h, s->memcpy_path != 0, state_rows(h), h->n, envs_dev, s->r, s->cap, slots_dev, count, false);
 }
 
@@ -111,33 +108,18 @@ int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_de
     if (count < 0 || count > h->n) return fail(NGW_E_INVALID_ARG, "restore of %lld states into %lld envs", (long long)count, (long long)h->n);
     if (!slots_dev && count > s->cap) return fail(NGW_E_INVALID_ARG, "restore of %lld states from a snapshot of %lld slots", (long long)count, (long long)s->cap);
     if (flags & ~NGW_SNAP_KEEP_EPISODE) return fail(NGW_E_INVALID_ARG, "unknown restore flags 0x%x", (unsigned)flags);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     if (count == 0) return NGW_OK;
     const bool keep = (flags & NGW_SNAP_KEEP_EPISODE) != 0;
-    h->solo_mirror_valid = false;
-    h->mirror_valid = false;
-    h->act_mask_fresh = false;
+    state_written(h, WROTE_MAPS);
     if (int rc = move_rows(h, s->memcpy_path != 0, s->r, s->cap, slots_dev, state_rows(h), h->n, envs_dev, count, keep)) return rc;
-    if (h->boards_on) {
-        // the bit rows of the restored maps, and the fused observation of the restored state (what an explicit reset does as well): two
-        // whole-batch launches however few envs were restored - the price of an observation that is current right after the call
-        if (int rc = rebuild_boards(h, h->b.map, h->b.brd, h->n_pad)) return rc;
-        h->brd_dirty = false;
-        if (int rc = launch_lidar_boards(h)) return rc;
-    } else if (h->lidar_fused && h->lidar_len && h->lidar_lds) {
-        NgwLaunch a = h->lidar_proto;
-        a.b = h->b;
-        HIP_TRY(ngw_lidar_launch(&a, h->map_mode, (unsigned)(h->n_pad / NGW_EPB), h->lidar_lds, h->stream));
-    }
+    // the fused observation of the restored state (what an explicit reset does as well): whole-batch launches however few envs were
+    // restored - the price of an observation that is current right after the call
+    if (int rc = refresh_fused_obs(h)) return rc;
     // Prepared next episodes: a row is valid iff its tag is the episode it was prepared for, so rows of envs whose counter moved are
     // merely stale (their next reset runs the placement loop: same result).  A refill behind the restore prepares fresh ones, like the
     // one behind an explicit reset; with the counters kept every tag still matches and nothing is scheduled.
-    if (h->prefetch_every > 0 && !keep) {
-        h->since_refill += h->prefetch_every;
-        if (h->since_refill >= h->cadence) return launch_refill(h);
-    }
-    return NGW_OK;
+    return keep ? NGW_OK : steps_since_refill(h, h->prefetch_every);
 }
 
 int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t count, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv,
@@ -145,8 +127,7 @@ int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t coun
     if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (first < 0 || count < 0 || first + count > s->cap) return fail(NGW_E_INVALID_ARG, "slot range [%lld, +%lld) out of bounds", (long long)first, (long long)count);
-    HIP_TRY(hipSetDevice(h->device));
-    if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }
+    if (int rc = enter(h)) return rc;
     const size_t n = (size_t)count, f = (size_t)first, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;
     D2H(map, s->r.map + f * S2, n * S2);
     D2H(loc, s->r.loc + f * 2, n * 2 * sizeof(int32_t));

@@ -224,10 +224,16 @@ struct NgwDevSpec {
     uint64_t* amask;             /* [n_pad] action masks (ngw_mask.inc): the fused form of the step kernel stores the post-step masks here; nullptr until allocated */
 };
 
+/* ngw_launch's `feat`: which instantiation of the kernel that `mode` names the host dispatch (end of ngw_kernels.hip) picks. */
+enum { NGW_FEAT_LIDAR = 1,    /* fused LidarInFront epilogue (with NGW_FEAT_NOSTAGE: the one on the occupancy bit rows) */
+       NGW_FEAT_EXT = 2,      /* wrapper predicates (FireWall / FenceRestriction / Crate) */
+       NGW_FEAT_NOSTAGE = 8,  /* NGW_MODE_STEP: the in-place step kernel (maps read where they lie, no staging through LDS) */
+       NGW_FEAT_WIRE = 16,    /* ... its host write-through form (NgwWT) */
+       NGW_FEAT_MASK = 32 };  /* fused action masks (plain steps only: ngw_step_lean<..., MASK>) */
 #ifdef __cplusplus
 extern "C"
 #endif
-hipError_t ngw_launch(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat /* 1 = fused lidar, 2 = EXT, 8 = no-stage step */, unsigned grid, size_t lds_bytes,
+hipError_t ngw_launch(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat /* NGW_FEAT_* */, unsigned grid, size_t lds_bytes,
                       hipStream_t stream);
 /* Arguments of the dedicated new-episode kernel (ngw_reset.inc: explicit resets and prepared next episodes of the plain
  * configurations and of those with ONE subset pass over the air of the interior (AddItem / Crate) or the wall ring (ReplaceItem /

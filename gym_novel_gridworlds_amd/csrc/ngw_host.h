@@ -6,6 +6,17 @@
 //   ngw_abi_debug.cpp    timing pair and diagnostics entry points (not in include/ngw.h)
 //   ngw_abi_mask.cpp     action masks: the standalone mask kernel, staleness, the one-env loop's speculated records
 //   ngw_abi_snapshot.cpp device-side snapshots: save / restore / fork env states by index (ngw_snapshot.inc)
+//
+// Three rules hold in all of them:
+//   1. Guard first.  An entry point that uses the handle's stream or its device state starts with `if (int rc = enter(h)) return rc;`
+//      (current device, then the one-env handle's resident loop ended: HBM holds the state only once it has, and its stream is busy until
+//      then), or reaches a helper that does (launch, rollout_chunks).  The entry points that deliberately do something else say why where
+//      they do it (ngw_get_action_mask, ngw_action_mask_device_ptr, ngw_step_host, ngw_create); tests/test_solo_stop_audit.py checks it.
+//   2. Whoever writes the state in HBM says so through state_written().  The handle carries facts DERIVED from that state - the host
+//      mirrors, the delta shadows, the action masks, the occupancy bit rows - and state_written() is the one place that knows which of them
+//      a write leaves behind.  A path assigns one of those flags itself only where it has just made the thing valid again.
+//   3. Nothing is passed to launch() through the handle.  What one launch needs beyond its positional arguments travels in a LaunchOpts;
+//      the handle holds what outlives the call.
 #ifndef NGW_HOST_H
 #define NGW_HOST_H
 #include <hip/hip_runtime.h>
@@ -87,15 +98,12 @@ struct ngw_handle {
     hipEvent_t mask_ev[2] = {nullptr, nullptr};
     int mask_next = 0;
     uint8_t* act_pin_dev = nullptr;            // ... the same buffer as the GPU addresses it (ngw_step_host_packed: the kernel reads the actions in place)
-    bool launch_wire = false;                  // the launch being issued is the host write-through form (feat 16), its sequence number wt_seq
-    bool launch_act_u8 = false;                // the launch being issued reads one byte per env from `actions`
     uint8_t* wire_stage = nullptr;             // ngw_step_host_packed: device staging of the dense sections
     uint8_t* act_pin = nullptr;                // ngw_step's actions: two page-locked halves feeding the asynchronous copy
     hipEvent_t act_ev[2] = {nullptr, nullptr};
     int act_next = 0;
     int hostres = 0;                         // single-wavefront handle with a host mirror (NgwMirror)
-    uint32_t step_seq = 0, launch_seq = 0;   // hostres: sequence number the next step launch reports (launch_seq: only while ngw_step_host issues it)
-    int32_t launch_action0 = 0; bool launch_use_action0 = false;   // one-env handles: the action of the launch ngw_step_host is issuing
+    uint32_t step_seq = 0;                   // hostres: sequence number of the last launch that reported one (LaunchOpts::seq)
     // ngw_step_host_packed, pipelined: the batch steps in slices on the handle's stream while a second stream brings the finished slices'
     // results across PCIe (api_slices: 0 / 1 = off - the default: measured slower, profiles/r05_ab.md -, NGW_API_SLICES=<n> selects n slices)
     hipStream_t stream2 = nullptr;
@@ -164,12 +172,11 @@ struct ngw_handle {
     int8_t* view_out = nullptr;           // AgentMap windows
     int view_size = 0;
     size_t view_cap = 0;
-    // Action masks (ngw_abi_mask.cpp, ngw_mask.inc): [n_pad] uint64 words in HBM.  act_mask_fresh: they describe the current state (every
-    // launch that changes the state clears it; a step with act_mask_on leaves the post-step masks behind it on the stream and sets it)
+    // Action masks (ngw_abi_mask.cpp, ngw_mask.inc): [n_pad] uint64 words in HBM.  act_mask_fresh: they describe the current state
+    // (state_written clears it; a step with act_mask_on leaves the post-step masks behind it on the stream and sets it)
     uint64_t* act_mask = nullptr;
     bool act_mask_on = false, act_mask_fresh = false;
     bool graph_act_mask = false;          // the captured graph leaves the masks of the state it ends in
-    bool act_mask_defer = false;          // a step of a multi-step call that is not its last: its masks could never be read, none are computed
     int act_mask_fused = 1;               // NGW_MASK_FUSED=0: the standalone kernel behind every plain step instead of the fused form (A/B)
     std::vector<ngw_snapshot*> snaps;     // open snapshots (ngw_snapshot_create); their slabs are in `allocs`, ngw_destroy deletes what is left
     long long solo_starts = 0;            // launches of the one-env resident loop (ngw_debug_solo_starts)
@@ -201,9 +208,29 @@ int layout_lds(ngw_handle* h);
 int upload_reset_u(ngw_handle* h);
 void layout_reset_fast(ngw_handle* h);
 // ngw_abi_launch.cpp
-int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, const uint8_t* mask_dev, uint64_t action_seed, int64_t t0);
+// What ONE launch() needs beyond its positional arguments; most calls pass the defaults.
+struct LaunchOpts {
+    enum Actions { ACT_I32 = 0, ACT_ARG = 1, ACT_U8 = 2 };   // (NgwLaunch::use_action0's values)
+    Actions actions = ACT_I32;            // `actions_dev` holds int32 ids / is not read, the one env's action is `action0` / holds one byte per env
+    int32_t action0 = 0;
+    uint32_t seq = 0;                     // single-wavefront handles: the number the kernel reports to flags_host[NGW_SEQ_WORD] once the host mirror is written (0: neither)
+    bool wire = false;                    // the step kernel's host write-through form (NgwWT); it reports h->wt_seq
+    bool masks = true;                    // false: a step of a multi-step call that is not its last - its masks could never be read, none are computed
+    int32_t* row_reward = nullptr;        // fused rollouts: this launch's first output rows (ngw_rollout_outputs) and the episode accumulators
+    uint8_t* row_done = nullptr;
+    int64_t row_stride = 0;
+    int32_t* acc = nullptr;
+};
+int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, const uint8_t* mask_dev, uint64_t action_seed, int64_t t0,
+           const LaunchOpts& o = LaunchOpts());
 int launch_refill(ngw_handle* h);
-int solo_stop(ngw_handle* h);                       // ends the one-env handle's resident step loop (no-op when it is not running); every other entry point calls it first
+int enter(ngw_handle* h);                           // rule 1: the handle's device made current, its one-env loop ended
+enum : unsigned { WROTE_MAPS = 1u, WROTE_BY_SOLO_LOOP = 2u };
+void state_written(ngw_handle* h, unsigned how = 0);   // rule 2
+int ensure_boards(ngw_handle* h);                   // boards mode: the main set's bit rows rebuilt from its maps if they are stale
+int refresh_fused_obs(ngw_handle* h);               // the fused LidarInFront observation of the state in HBM, as launches of its own
+int steps_since_refill(ngw_handle* h, int k);       // prepared next episodes: k more steps' worth consumed; the refill launch when the cadence is reached
+int solo_stop(ngw_handle* h);                       // ends the one-env handle's resident step loop (no-op when it is not running): what enter() does for every entry point
 int solo_step(ngw_handle* h, int32_t action);      // one step() through the loop: the host mirror (h->mir) holds the new state afterwards
 bool solo_ok(const ngw_handle* h);
 int launch_step_slice(ngw_handle* h, const uint8_t* actions_u8_dev, int64_t first, int64_t count);   // one slice of a batched step (byte actions), on the handle's stream
@@ -219,6 +246,32 @@ int launch_act_mask(ngw_handle* h);                 // the masks of the state in
 int alloc_act_mask(ngw_handle* h);                  // the mask buffer, published to NgwDevSpec::amask (no-op once allocated)
 // ngw_abi_host.cpp
 void host_step_layout(const ngw_handle* h, uint64_t off[11]);
+int check_actions(const int32_t* actions, size_t n, int A);   // NGW_E_INVALID_ACTION naming the first id outside [0, A)
+
+// Which kernel an NGW_MODE_STEP launch runs: the in-place step kernel (no map staging) unless the fused lidar needs the maps in LDS for its march.
+inline bool step_in_place(const ngw_handle* h) { return h->nostage && (!h->lidar_fused || h->boards_on); }
+
+inline void cpu_pause() {
+#if defined(__x86_64__) || defined(__i386__)
+    __builtin_ia32_pause();
+#else
+    __asm__ __volatile__("" ::: "memory");
+#endif
+}
+
+// Waits for a kernel's sequence number in host memory: polling the word costs a PCIe write's latency where a stream synchronisation costs
+// several microseconds (and would also wait for a refill launch that follows on the stream).  Bounded: after `spins` polls without it the
+// stream is synchronised the usual way.  The caller's reads of what the kernel wrote stay behind the wait.
+inline int wait_seq(ngw_handle* h, volatile uint32_t* word, uint32_t seq, uint32_t spins) {
+    bool seen = false;
+    for (uint32_t spin = 0; spin < spins; spin++) {
+        if (*word == seq) { seen = true; break; }
+        cpu_pause();
+    }
+    if (!seen) HIP_TRY(hipStreamSynchronize(h->stream));
+    __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return NGW_OK;
+}
 
 }  // namespace ngwh
 #endif

@@ -667,8 +667,7 @@ extern "C" hipError_t ngw_reset_fast_launch(const NgwDevSpec* dspec, const NgwRe
 }
 #endif  // NGW_HAS(5)
 
-// feat: 1 = fused LidarInFront epilogue, 2 = wrapper predicates (EXT), 8 = no-stage step (maps read in place), 16 = host write-through (with 8),
-// 32 = fused action masks (plain steps only: ngw_step_lean<..., MASK>)
+// feat: the NGW_FEAT_* bits (ngw_device.h)
 extern "C" hipError_t ngw_part_step(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat, unsigned grid, size_t lds_bytes,
                                     hipStream_t stream);
 extern "C" hipError_t ngw_part_rollout_straight(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
@@ -678,8 +677,8 @@ extern "C" hipError_t ngw_part_rollout_byte(const NgwDevSpec* dspec, const NgwLa
 // ONE batched step(): ngw_step_lean.  The staged kernels of one map addressing mode (four each) are a unit of their own.
 #define NGW_STEP_PART(NAME, MM)                                                                                                         \
     extern "C" hipError_t NAME(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) { \
-        const bool lidar = (feat & 1) != 0, ext = (feat & 2) != 0;                                                                      \
-        if ((feat & 32) && !lidar)                                         /* fused action masks */                                    \
+        const bool lidar = (feat & NGW_FEAT_LIDAR) != 0, ext = (feat & NGW_FEAT_EXT) != 0;                                               \
+        if ((feat & NGW_FEAT_MASK) && !lidar)   /* fused action masks */                                                                 \
             return ext ? launch_lean<MM, true, true, false, 0, false, true>(dspec, a, grid, lds_bytes, stream)                           \
                        : launch_lean<MM, true, false, false, 0, false, true>(dspec, a, grid, lds_bytes, stream);                         \
         return lidar ? (ext ? launch_lean<MM, true, true, true>(dspec, a, grid, lds_bytes, stream)                                      \
@@ -697,13 +696,13 @@ extern "C" hipError_t ngw_part_step_mask_ns(const NgwDevSpec* dspec, const NgwLa
 #if NGW_HAS(9)
 // in-place step with the fused action masks
 extern "C" hipError_t ngw_part_step_mask_ns(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    return (feat & 2) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false, 0, false, true>(dspec, a, grid, lds_bytes, stream)
+    return (feat & NGW_FEAT_EXT) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false, 0, false, true>(dspec, a, grid, lds_bytes, stream)
                       : launch_lean<NGW_MAP_STRAIGHT, false, false, false, 0, false, true>(dspec, a, grid, lds_bytes, stream);
 }
 // in-place step with the host write-through (NgwWT: ngw_step_host_packed's steady state)
 extern "C" hipError_t ngw_part_step_wire(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    if (feat & 1) return ngw_part_step_wire_boards(dspec, a, feat, grid, lds_bytes, stream);
-    return (feat & 2) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false, 0, true>(dspec, a, grid, lds_bytes, stream)
+    if (feat & NGW_FEAT_LIDAR) return ngw_part_step_wire_boards(dspec, a, feat, grid, lds_bytes, stream);
+    return (feat & NGW_FEAT_EXT) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false, 0, true>(dspec, a, grid, lds_bytes, stream)
                       : launch_lean<NGW_MAP_STRAIGHT, false, false, false, 0, true>(dspec, a, grid, lds_bytes, stream);
 }
 #endif  // NGW_HAS(9)
@@ -718,7 +717,7 @@ extern "C" hipError_t ngw_mask_launch(const NgwDevSpec* dspec, const NgwBufs* b,
 #endif  // NGW_HAS(9)
 #if NGW_HAS(10)
 extern "C" hipError_t ngw_part_step_wire_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    const bool ext = (feat & 2) != 0;
+    const bool ext = (feat & NGW_FEAT_EXT) != 0;
     if (!a->l_boards || a->BS < 4 || a->BS > 32) return hipErrorInvalidValue;
     if (a->BS <= 12) return ext ? launch_lean<NGW_MAP_STRAIGHT, false, true, true, 12, true>(dspec, a, grid, lds_bytes, stream)
                                 : launch_lean<NGW_MAP_STRAIGHT, false, false, true, 12, true>(dspec, a, grid, lds_bytes, stream);
@@ -731,7 +730,7 @@ extern "C" hipError_t ngw_part_step_wire_boards(const NgwDevSpec* dspec, const N
 #if NGW_HAS(8)
 // in-place step + the LidarInFront observation from the occupancy bit rows (ngw_boards.inc): NR = 12 / 20 / 32 register rows
 extern "C" hipError_t ngw_part_step_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    const bool ext = (feat & 2) != 0;
+    const bool ext = (feat & NGW_FEAT_EXT) != 0;
     if (!a->l_boards || a->BS < 4 || a->BS > 32) return hipErrorInvalidValue;
     if (a->BS <= 12) return ext ? launch_lean<NGW_MAP_STRAIGHT, false, true, true, 12>(dspec, a, grid, lds_bytes, stream)
                                 : launch_lean<NGW_MAP_STRAIGHT, false, false, true, 12>(dspec, a, grid, lds_bytes, stream);
@@ -762,11 +761,11 @@ extern "C" hipError_t ngw_lidar_boards_launch(const NgwLaunch* a, unsigned grid,
 NGW_STEP_PART(ngw_part_step_straight, NGW_MAP_STRAIGHT)
 extern "C" hipError_t ngw_part_step(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat, unsigned grid, size_t lds_bytes,
                                     hipStream_t stream) {
-    if (feat & 8) {                                                     // no-stage: with the lidar observation, the one on the occupancy bit rows
-        if (feat & 16) return ngw_part_step_wire(dspec, a, feat, grid, lds_bytes, stream);   // ... with the host write-through
-        if (feat & 1) return ngw_part_step_boards(dspec, a, feat, grid, lds_bytes, stream);
-        if (feat & 32) return ngw_part_step_mask_ns(dspec, a, feat, grid, lds_bytes, stream);
-        return (feat & 2) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false>(dspec, a, grid, lds_bytes, stream)
+    if (feat & NGW_FEAT_NOSTAGE) {   // no-stage: with the lidar observation, the one on the occupancy bit rows
+        if (feat & NGW_FEAT_WIRE) return ngw_part_step_wire(dspec, a, feat, grid, lds_bytes, stream);   // ... with the host write-through
+        if (feat & NGW_FEAT_LIDAR) return ngw_part_step_boards(dspec, a, feat, grid, lds_bytes, stream);
+        if (feat & NGW_FEAT_MASK) return ngw_part_step_mask_ns(dspec, a, feat, grid, lds_bytes, stream);
+        return (feat & NGW_FEAT_EXT) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false>(dspec, a, grid, lds_bytes, stream)
                           : launch_lean<NGW_MAP_STRAIGHT, false, false, false>(dspec, a, grid, lds_bytes, stream);
     }
     switch (map_mode) {
@@ -787,7 +786,7 @@ NGW_STEP_PART(ngw_part_step_byte, NGW_MAP_BYTE)
 // fused rollout: ngw_rollout_lean, one part per map addressing mode (eight kernels each: the heaviest to compile)
 #define NGW_ROLLOUT_PART(NAME, MM)                                                                                                     \
     extern "C" hipError_t NAME(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) { \
-        const bool lidar = (feat & 1) != 0, ext = (feat & 2) != 0;                                                                     \
+        const bool lidar = (feat & NGW_FEAT_LIDAR) != 0, ext = (feat & NGW_FEAT_EXT) != 0;                                             \
         if (a->mode == NGW_MODE_ROLLOUT_ACT)                                                                                           \
             return lidar ? (ext ? launch_rollout_lean<MM, true, true, true>(dspec, a, grid, lds_bytes, stream)                         \
                                 : launch_rollout_lean<MM, true, false, true>(dspec, a, grid, lds_bytes, stream))                       \
@@ -829,7 +828,7 @@ extern "C" hipError_t ngw_launch(const NgwDevSpec* dspec, const NgwLaunch* a, in
         default: return ngw_part_rollout_byte(dspec, a, feat, grid, lds_bytes, stream);
         }
     }
-    const bool lidar = (feat & 1) != 0;
+    const bool lidar = (feat & NGW_FEAT_LIDAR) != 0;
     switch (map_mode) {
     case NGW_MAP_STRAIGHT: return launch_general<NGW_MAP_STRAIGHT>(dspec, a, lidar, grid, lds_bytes, stream);
     case NGW_MAP_DWORD: return launch_general<NGW_MAP_DWORD>(dspec, a, lidar, grid, lds_bytes, stream);
