@@ -161,6 +161,7 @@ int enter(ngw_handle* h) {
 //   mirror_valid       the caller's page-locked block (ngw_step_host / _packed) mirrors the state: the next host step copies everything
 //                      and re-seeds the delta shadows, which also ends shadow_stale - that flag only means something under mirror_valid
 //   act_mask_fresh     the mask words describe the state: ngw_action_mask runs the kernel again
+//   look_fresh         the lookahead table describes the state: ngw_lookahead runs the kernel again
 //   brd_dirty          the main set's bit rows do not describe its maps: ensure_boards rebuilds them before the next reader
 // Writers differ in two ways that matter, and `how` names them:
 //   WROTE_MAPS          maps changed without their bit rows (ngw_set_state with a map, a snapshot restore, a fused rollout - it steps the
@@ -175,6 +176,7 @@ void state_written(ngw_handle* h, unsigned how) {
     if (!(how & WROTE_BY_SOLO_LOOP)) h->solo_mirror_valid = false;
     h->mirror_valid = false;
     h->act_mask_fresh = false;
+    h->look_fresh = false;
     if (how & WROTE_MAPS) h->brd_dirty = true;
 }
 
@@ -517,7 +519,7 @@ int capture_graph(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride
     const bool open = h->prefetch_every > 0 && n_steps * 2 <= h->cadence;
     // Capturing runs nothing: what its launch() calls book as done is put back to `before` when the capture ends - whether the masks
     // describe the state, and, for an open graph, the steps since the last refill.
-    const struct { int since_refill; bool act_mask_fresh; } before = {h->since_refill, h->act_mask_fresh};
+    const struct { int since_refill; bool act_mask_fresh, look_fresh; } before = {h->since_refill, h->act_mask_fresh, h->look_fresh};
     h->since_refill = 0;                              // the captured refill cadence starts from a known phase
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     h->capturing = true;                              // (the depth and cadence the handle has adapted to so far are the ones captured)
@@ -535,6 +537,7 @@ int capture_graph(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride
     }
     h->capturing = false;
     h->act_mask_fresh = before.act_mask_fresh;
+    h->look_fresh = before.look_fresh;
     if (open) h->since_refill = before.since_refill;
     h->graph_act_mask = h->act_mask_on;
     hipError_t e = hipStreamEndCapture(h->stream, &h->graph);

@@ -23,14 +23,10 @@ int launch_act_mask(ngw_handle* h) {
     return NGW_OK;
 }
 
-}  // namespace ngwh
-
-namespace {
-
-// The one-env loop speculates every action from the committed state: bit 0 of record a's info word is exactly `result` of step(a).  Returns
-// false when the records do not belong to the host's state (the loop ended before it took the last command): the caller stops the loop and
-// runs the kernel instead.  Waits for the records like solo_step does, never stops the loop.
-bool solo_mask(ngw_handle* h, uint64_t* out) {
+// The one-env loop speculates every action from the committed state into records.  Returns false when the records do not belong to the
+// host's state (the loop ended before it took the last command): the caller stops the loop and runs a kernel instead.  Waits for the
+// records like solo_step does, never stops the loop.
+bool solo_records_ready(ngw_handle* h) {
     volatile uint32_t* o = h->solo_out;
     for (uint64_t spin = 0;; spin++) {
         if (o[0] == h->solo_seq) break;
@@ -43,6 +39,16 @@ bool solo_mask(ngw_handle* h, uint64_t* out) {
         cpu_pause();
     }
     __atomic_thread_fence(__ATOMIC_ACQUIRE);
+    return true;
+}
+
+}  // namespace ngwh
+
+namespace {
+
+// bit 0 of record a's info word is exactly `result` of step(a)
+bool solo_mask(ngw_handle* h, uint64_t* out) {
+    if (!solo_records_ready(h)) return false;
     const NgwSolo& p = h->solo_proto;
     uint64_t m = 0;
     for (int a = 0; a < p.A; a++) m |= (uint64_t)(h->solo_out[NGW_SOLO_REC0 + (size_t)a * (size_t)p.rec_dw + 1] & 1u) << a;

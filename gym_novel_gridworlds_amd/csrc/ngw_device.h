@@ -404,6 +404,15 @@ extern "C"
 #endif
 hipError_t ngw_mask_launch(const NgwDevSpec* dspec, const NgwBufs* b, int64_t n, int S, int K, int ext, uint64_t* out, unsigned grid, hipStream_t stream);
 
+/* One-step lookahead table of the state in HBM (ngw_lookahead.inc): entry (e, a) = reward / done / packed info word that a step of env e with
+ * action a would report under the spec and the autoreset setting given; nothing but the table is written.  Action-major: element (e, a) of
+ * each array at [a * n_pad + e], padding rows 0; grid = n_pad / NGW_EPB.  ext: the spec has wrapper predicates (NgwExtU). */
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_lookahead_launch(const NgwDevSpec* dspec, const NgwBufs* b, int64_t n, int64_t n_pad, int S, int K, int ext, int autoreset, int horizon,
+                                int32_t* reward, uint8_t* done, uint32_t* info, unsigned grid, hipStream_t stream);
+
 /* Device-side snapshots (ngw_snapshot.inc, ngw_abi_snapshot.cpp): the seven state arrays of `rows` envs, laid out like the state slab
  * itself (one array per field, row i of every array = one env).  The state slab is the set {map, loc, facing, inv, selected, step_count,
  * episode} of NgwBufs, a snapshot is a second such set of `capacity` rows. */

@@ -5,6 +5,7 @@
 //   ngw_abi_obs.cpp      observation wrappers on the device: LidarInFront (marches and the bit-row form), AgentMap
 //   ngw_abi_debug.cpp    timing pair and diagnostics entry points (not in include/ngw.h)
 //   ngw_abi_mask.cpp     action masks: the standalone mask kernel, staleness, the one-env loop's speculated records
+//   ngw_abi_lookahead.cpp one-step lookahead tables: the lookahead kernel (ngw_lookahead.inc), staleness, the one-env loop's speculated records
 //   ngw_abi_snapshot.cpp device-side snapshots: save / restore / fork env states by index (ngw_snapshot.inc)
 //
 // Three rules hold in all of them:
@@ -14,7 +15,7 @@
 //      they do it (ngw_get_action_mask, ngw_action_mask_device_ptr, ngw_step_host, ngw_create); tests/test_solo_stop_audit.py checks it.
 //   2. Whoever writes the state in HBM says so through state_written().  The handle carries facts DERIVED from that state - the host
 //      mirrors, the delta shadows, the action masks, the occupancy bit rows - and state_written() is the one place that knows which of them
-//      a write leaves behind.  A path assigns one of those flags itself only where it has just made the thing valid again.
+//      a write leaves behind (the lookahead table is one more of them).  A path assigns one of those flags itself only where it has just made the thing valid again.
 //   3. Nothing is passed to launch() through the handle.  What one launch needs beyond its positional arguments travels in a LaunchOpts;
 //      the handle holds what outlives the call.
 #ifndef NGW_HOST_H
@@ -178,6 +179,14 @@ struct ngw_handle {
     bool act_mask_on = false, act_mask_fresh = false;
     bool graph_act_mask = false;          // the captured graph leaves the masks of the state it ends in
     int act_mask_fused = 1;               // NGW_MASK_FUSED=0: the standalone kernel behind every plain step instead of the fused form (A/B)
+    // One-step lookahead table (ngw_abi_lookahead.cpp, ngw_lookahead.inc): action-major [n_actions][n_pad] reward / done / info in HBM, allocated on
+    // first use.  look_fresh: nothing has written the state since it was computed (state_written ends that), under the autoreset setting
+    // look_autoreset / look_horizon (a table computed under another setting than the handle's is recomputed too)
+    int32_t* look_reward = nullptr;
+    uint8_t* look_done = nullptr;
+    uint32_t* look_info = nullptr;
+    bool look_fresh = false;
+    int look_autoreset = 0, look_horizon = 0;
     std::vector<ngw_snapshot*> snaps;     // open snapshots (ngw_snapshot_create); their slabs are in `allocs`, ngw_destroy deletes what is left
     long long solo_starts = 0;            // launches of the one-env resident loop (ngw_debug_solo_starts)
     hipGraph_t graph = nullptr;
@@ -244,6 +253,7 @@ void drop_graph(ngw_handle* h);
 // ngw_abi_mask.cpp
 int launch_act_mask(ngw_handle* h);                 // the masks of the state in HBM, on the handle's stream (allocates the buffer on first use)
 int alloc_act_mask(ngw_handle* h);                  // the mask buffer, published to NgwDevSpec::amask (no-op once allocated)
+bool solo_records_ready(ngw_handle* h);             // the one-env loop's speculated records belong to the host's state (waits for them like solo_step, never stops the loop)
 // ngw_abi_host.cpp
 void host_step_layout(const ngw_handle* h, uint64_t off[11]);
 int check_actions(const int32_t* actions, size_t n, int A);   // NGW_E_INVALID_ACTION naming the first id outside [0, A)

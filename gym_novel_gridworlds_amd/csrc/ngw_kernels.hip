@@ -27,14 +27,14 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file TWELVE times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file THIRTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
 //   8: the bit-row (boards) lidar: in-place step kernels with the O(1) observation, ngw_boards_kernel, ngw_lidar_boards_kernel
 //   9 / 10: the host write-through step kernels, plain / with the bit-row lidar (9 also holds the standalone mask kernel and the in-place step
 //   with fused masks; 1 / 6 / 7 hold the staged ones)
-//   11: device-side snapshots (ngw_snapshot.inc)
+//   11: device-side snapshots (ngw_snapshot.inc)   12: one-step lookahead tables (ngw_lookahead.inc)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -379,6 +379,9 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #include "ngw_lean.inc"
 #include "ngw_solo.inc"
 #include "ngw_reset.inc"
+#if NGW_HAS(12)
+#include "ngw_lookahead.inc"
+#endif
 
 // ---------------------------------------------------------------- LidarInFront observation kernel (stand-alone launch)
 // observation_wrappers.py:32-80 of the CURRENT state.  Same wave = 64 envs decomposition and the same coalesced staging of the
@@ -853,3 +856,15 @@ extern "C" hipError_t ngw_snapshot_launch(const NgwSnap* p, hipStream_t stream) 
     return hipGetLastError();
 }
 #endif  // NGW_HAS(11)
+#if NGW_HAS(12)
+// the one-step lookahead table of the state in HBM (ngw_lookahead.inc): action-major [n_actions][n_pad] reward / done / info
+extern "C" hipError_t ngw_lookahead_launch(const NgwDevSpec* dspec, const NgwBufs* b, int64_t n, int64_t n_pad, int S, int K, int ext, int autoreset, int horizon,
+                                           int32_t* reward, uint8_t* done, uint32_t* info, unsigned grid, hipStream_t stream) {
+    if (n <= 0 || n > 0xFFFFFFFFll || n_pad < n || (int64_t)grid * NGW_EPB != n_pad || S < 3 || S > NGW_MAX_MAP_SIZE || K < 1 || K > NGW_MAX_ITEMS ||
+        !reward || !done || !info)
+        return hipErrorInvalidValue;
+    if (ext) hipLaunchKernelGGL(ngw_lookahead_kernel<true>, dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, autoreset, horizon, (uint64_t)n_pad, reward, done, info);
+    else hipLaunchKernelGGL(ngw_lookahead_kernel<false>, dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, autoreset, horizon, (uint64_t)n_pad, reward, done, info);
+    return hipGetLastError();
+}
+#endif  // NGW_HAS(12)

@@ -88,11 +88,103 @@ __device__ __forceinline__ LeanBreakX lean_break_ext(const UT& U, const NgwExtU&
 // result of one entry: the table's outcome, then the wrappers' Break predicates (lean_body reaches the same value through `succ`)
 __device__ __forceinline__ bool lean_result(uint32_t s, const LeanBreakX& xb) { return xb.fence_twice || (s == 0 && !xb.restricted); }
 
+// ---- what follows the predicate, shared by lean_body and the lookahead kernel (ngw_lookahead.inc): how an outcome is reported, the reward
+//      rule, what a success changes, what the goal test counts, the FireWall check at the new position and the goal / horizon epilogue.
+//      lean_body applies the effects to the state; the lookahead kernel keeps them in registers.  Neither restates a rule.
+__device__ __forceinline__ bool lean_is_break(uint32_t e0) { return (e0 >> 24) & 1u; }
+// how outcome s of an entry is reported: result, message code and argument, cost code (a Break with the selected axe costs axe_cost :155-165)
+struct LeanRep { bool succ; int msg, arg, cost; };
+template <class UT>
+__device__ __forceinline__ LeanRep lean_report(const UT& U, uint32_t e0, uint32_t e4, uint32_t e5, uint32_t s, int front, uint32_t missing, bool axe_ok) {
+    LeanRep p;
+    const int aarg = (e0 >> 8) & 255;
+    p.succ = s == 0;                                                               // (a no-op entry "succeeds" at doing nothing)
+    p.msg = (int)((e4 >> (8u + 4u * s)) & 15u);
+    const uint32_t asel = (e4 >> (20u + 2u * s)) & 3u;
+    p.arg = (asel == 1 ? front : 0) | (asel == 2 ? (int)((e0 >> 16) & 255u) : 0) | (asel == 3 ? (int)(((uint32_t)aarg << 8) | missing) : 0);
+    p.cost = (int)((e5 >> (14u + 6u * s)) & 63u);
+    if (p.succ && lean_is_break(e0) && axe_ok) p.cost = U.axe_cost;                 // novelty_wrappers.py:155-165
+    return p;
+}
+// FenceRestriction refused the Break (:924-946) / let it through and reports success itself (:949-972)
+__device__ __forceinline__ void lean_report_restricted(LeanRep& p, uint32_t e5) { p.succ = false; p.msg = NGW_MSG_FENCE_RESTRICTION; p.arg = 0; p.cost = (int)((e5 >> 14) & 63u); }
+__device__ __forceinline__ void lean_report_fence_twice(LeanRep& p, uint32_t e5) { p.succ = true; p.cost = (int)((e5 >> 14) & 63u); p.msg = NGW_MSG_NONE; p.arg = 0; }
+// reward of a step before the goal test: the entry's const, or the axe / break-reward rule of Break, when it succeeds under its reward condition
+template <class UT>
+__device__ __forceinline__ int lean_reward(const UT& U, uint32_t e0, uint32_t e5, uint32_t cb, bool succ, bool axe_ok) {
+    const int rew_val = lean_is_break(e0) ? (axe_ok ? (int)U.axe_reward : U.break_reward) : (int)(int8_t)(e5 & 255u);
+    return (succ && bit_of(cb, (e5 >> 8) & 15u)) ? rew_val : U.reward_step;
+}
+// effects of a success: the move (0 stay, 1 the cell in front, 2 two ahead), the front-cell write, the slot it changes and by how much
+__device__ __forceinline__ uint32_t lean_move(uint32_t e4, bool succ) { return succ ? (e4 >> 26) & 3u : 0u; }
+__device__ __forceinline__ bool lean_writes_cell(uint32_t e4, bool succ) { return succ && ((e4 >> 30) & 1u); }
+__device__ __forceinline__ int lean_cell_value(uint32_t e3) { return (int)((e3 >> 8) & 255u); }
+__device__ __forceinline__ int lean_slot(uint32_t e3, uint32_t e5, int front) { return ((e5 >> 12) & 3) == 1 ? front : (int)(e3 & 255u); }
+__device__ __forceinline__ bool lean_updates_slot(uint32_t e5, bool succ) { return succ && ((e5 >> 12) & 3) != 0; }
+template <class UT>
+__device__ __forceinline__ int lean_delta(const UT& U, uint32_t e0, uint32_t e3, int front, bool axe_ok) {
+    return lean_is_break(e0) ? (axe_ok ? (int)U.axe_qty : 1 + (int)((U.brk2_mask >> front) & 1u)) : ((int)e3 >> 16);
+}
+__device__ __forceinline__ bool lean_crafts(uint32_t e0, bool succ) { return succ && (e0 & 0x70u) != 0; }   // n_inputs > 0: a recipe
+// how many goal items the inventory holds after the step (:354-357), piece by piece: the slot a success changes ...
+__device__ __forceinline__ int lean_goal_slot(bool upd, int slot, int goal_item, int inv_slot, int delta, int inv_goal) {
+    return (upd && slot == goal_item) ? inv_slot + delta : inv_goal;
+}
+// ... what a crate holds of item i (Crate.step :1086-1089; the crate's own slot 0 holds no ingredient), and of the goal item
+__device__ __forceinline__ int lean_crate_qty(const NgwExtU& X, int i) {
+    const uint32_t w0 = X.crate_add[0], w1 = X.crate_add[1], w2 = X.crate_add[2];   // (by value: a select between the three ADDRESSES would keep X in memory)
+    const uint32_t w = i < 8 ? w0 : (i < 16 ? w1 : w2);
+    return (int)((w >> (4 * (i & 7))) & 15u);
+}
+__device__ __forceinline__ int lean_crate_goal(const NgwExtU& X, int goal_item, int K) { return (goal_item >= 1 && goal_item < K) ? lean_crate_qty(X, goal_item) : 0; }
+// ... what a recipe consumes of it (:455-474; ids of a recipe are distinct)
+__device__ __forceinline__ int lean_craft_goal_used(uint32_t e0, uint32_t e1, uint32_t e2, int goal_item) {
+    const int nin = (e0 >> 4) & 7;
+    const int in0 = e1 & 255, in1 = (e1 >> 8) & 255, in2 = (e1 >> 16) & 255, in3 = e1 >> 24;
+    const int nd0 = e2 & 255, nd1 = (e2 >> 8) & 255, nd2 = (e2 >> 16) & 255, nd3 = e2 >> 24;
+    return (nin > 0 && in0 == goal_item ? nd0 : 0) + (nin > 1 && in1 == goal_item ? nd1 : 0) +
+           (nin > 2 && in2 == goal_item ? nd2 : 0) + (nin > 3 && in3 == goal_item ? nd3 : 0);
+}
+// ... and the pick-up (grab_entities :538-554): a cell of the 3 x 3 around the new position that holds an entity is taken
+template <class UT>
+__device__ __forceinline__ bool lean_grabs(const UT& U, int id) { return id != 0 && ((U.ent_mask >> id) & 1u); }
+// the goal test: done while the inventory holds a goal item, with the forced reward (:354-357)
+template <class UT>
+__device__ __forceinline__ int lean_goal_done(const UT& U, int goal_cnt, int& rew) {
+    const int done = goal_cnt >= 1;
+    if (done) rew = U.reward_done;
+    return done;
+}
+// FireWall.step :1168-1189, after the wrapped step: does the check run for this entry (wrapper nesting), is a 4-neighbour of the new cell on fire
+__device__ __forceinline__ bool lean_fire_on(const NgwExtU& X, bool valid, uint32_t e0) {
+    const uint32_t kind = e0 & 15u, aarg = (e0 >> 8) & 255u;
+    return X.fire_item && valid && !((X.nest & NGW_XF_FIRE_SKIP_BREAK) && kind == NGW_ACT_BREAK) &&
+           !((X.nest >> 8) && kind == NGW_ACT_CRAFT && aarg + 1u == (X.nest >> 8));
+}
+__device__ __forceinline__ bool lean_burning(const NgwExtU& X, int n, int s, int w, int e) {
+    const int fire = X.fire_item;
+    return n == fire || s == fire || w == fire || e == fire;
+}
+__device__ __forceinline__ void lean_report_fire(const NgwExtU& X, LeanRep& p, int& rew, int& done) { rew = X.fire_reward; done = 1; p.msg = NGW_MSG_FIRE_WALL; p.arg = 0; }
+
 // What one step computes, shared by the per-launch kernel and the fused rollout.  STAGE: the lane's map is in LDS (`mp`), else its
 // cells are read from HBM (`bmap` + `mapoff`).  WT: write every change through to the observation buffers in HBM (per-launch
 // kernel); the fused rollout keeps the state in LDS / registers and stores it once, when the launch ends.
 struct LeanOut { int r, c, f, sel, steps, reward, ended; uint32_t info, flags; bool do_reset;
                  bool wcell; int cellv; uint32_t grab; };   // the cell writes of this step, for whoever keeps the occupancy bit rows: front cell := cellv; bit k of grab: cell k of the 3 x 3 around the NEW position was picked up
+
+// the step's outputs: step count (:362; FenceRestriction's own epilogue counts a second time :966), reward, the packed info word, and
+// whether the episode ends - done, or the horizon under the same-step autoreset (done = 1 for both, info bit 1 only for goal-done)
+__device__ __forceinline__ void lean_epilogue(LeanOut& o, bool live, bool valid, int steps0, int twice, int rew, int done, const LeanRep& p,
+                                              int autoreset, int horizon) {
+    o.flags = 0; o.reward = 0; o.ended = 0; o.steps = steps0; o.info = 0; o.do_reset = false;
+    if (valid) {
+        o.steps = steps0 + 1 + twice;                                              // :362
+        o.reward = rew; o.ended = done;
+        o.info = (p.succ ? 1u : 0u) | ((uint32_t)done << 1) | ((uint32_t)p.cost << 2) | ((uint32_t)p.msg << 8) | ((uint32_t)p.arg << 16);
+        if (autoreset && (done || (horizon > 0 && o.steps >= horizon))) { o.do_reset = true; o.ended = 1; }   // same-step autoreset
+    } else if (live) o.flags = NGW_F_INVALID_ACTION;
+}
 
 // The uniform step parameters as lean_body reads them, unpacked.  The per-launch kernel hands NgwStepU itself (scalars: used once);
 // the fused rollout hands this struct with the fields that only ever feed vector instructions PINNED IN VGPRS (every lane holds the
@@ -147,8 +239,7 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
     PIN_V(front); PIN_V(nbN); PIN_V(nbS); PIN_V(nbW); PIN_V(nbE); PIN_V(front2);
     PIN_V(inv_place); PIN_V(inv_axe); PIN_V(inv_arg); PIN_V(inv_goal); PIN_V(iv0); PIN_V(iv1); PIN_V(iv2); PIN_V(iv3);
     // ---- L1: the slot a success changes (the block in front, or the entry's const slot)
-    const int slotsel = (e5 >> 12) & 3;
-    const int slot = slotsel == 1 ? front : (int)(e3 & 255u);
+    const int slot = lean_slot(e3, e5, front);
     int inv_slot = inv[slot];
     PIN_V(inv_slot);
 
@@ -160,48 +251,42 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
 
     // ---- outcome: s = 1 if condition A holds, else 2 if B holds, else 0 (success)
     const uint32_t s = lean_outcome(cb, e4);
-    bool succ = s == 0;                                                            // (a no-op entry "succeeds" at doing nothing)
-    int msg = (int)((e4 >> (8u + 4u * s)) & 15u);
-    const uint32_t asel = (e4 >> (20u + 2u * s)) & 3u;
-    int arg = (asel == 1 ? front : 0) | (asel == 2 ? (int)((e0 >> 16) & 255u) : 0) | (asel == 3 ? (int)(((uint32_t)aarg << 8) | missing) : 0);
-    int cost = (int)((e5 >> (14u + 6u * s)) & 63u);
-    const bool is_break = (e0 >> 24) & 1u;
-    if (succ && is_break && axe_ok) cost = U.axe_cost;                              // novelty_wrappers.py:155-165
+    LeanRep p = lean_report(U, e0, e4, e5, s, front, missing, axe_ok);
+    const bool is_break = lean_is_break(e0);
     // ---- wrappers around Break (FenceRestriction, Crate): the only predicates that are not table entries
     bool fence_twice = false, crate_now = false;
     if (EXT) {
         const LeanBreakX xb = lean_break_ext(U, X, is_break && valid, front, S, r, c, f, fr, fc, fcell, cell_at);
         crate_now = xb.crate_now; fence_twice = xb.fence_twice;
-        if (xb.restricted) { succ = false; msg = NGW_MSG_FENCE_RESTRICTION; arg = 0; cost = (int)((e5 >> 14) & 63u); }
+        if (xb.restricted) lean_report_restricted(p, e5);
     }
     // reward of a success: the entry's const, or the axe / break-reward rule of Break
-    const int rew_val = is_break ? (axe_ok ? (int)U.axe_reward : U.break_reward) : (int)(int8_t)(e5 & 255u);
-    int rew = (succ && bit_of(cb, (e5 >> 8) & 15u)) ? rew_val : U.reward_step;
+    const bool succ = p.succ;                                                      // (what the wrappers report beyond this point changes no effect)
+    int rew = lean_reward(U, e0, e5, cb, succ, axe_ok);
     // ---- effects of a success
-    const uint32_t mv = succ ? (e4 >> 26) & 3u : 0u;
+    const uint32_t mv = lean_move(e4, succ);
     const int nr = mv == 1 ? fr : (mv == 2 ? fr2 : r), nc = mv == 1 ? fc : (mv == 2 ? fc2 : c);
     // turn LUT: 2 bits per (turn, facing): none {0,1,2,3}, left {2,3,1,0} (:258-268), right {3,2,0,1} (:269-279)
     const int nf = (int)((0x4B1EE4u >> (((e4 >> 25) & 0x18u) + 2u * (uint32_t)f)) & 3u);
     const int nsel = (succ && (e4 >> 31)) ? aarg : sel;
-    const bool wcell = succ && ((e4 >> 30) & 1u);
-    const int cellv = (int)((e3 >> 8) & 255u);
-    const int delta = is_break ? (axe_ok ? (int)U.axe_qty : 1 + (int)((U.brk2_mask >> front) & 1u)) : ((int)e3 >> 16);
-    const bool upd = succ && slotsel != 0;
-    const bool crafted = succ && (e0 & 0x70u) != 0;                               // n_inputs > 0: a recipe
+    const bool wcell = lean_writes_cell(e4, succ);
+    const int cellv = lean_cell_value(e3);
+    const int delta = lean_delta(U, e0, e3, front, axe_ok);
+    const bool upd = lean_updates_slot(e5, succ);
+    const bool crafted = lean_crafts(e0, succ);
 
     // ---- apply: LDS (the reset path reads it) and write-through to HBM
     // how many goal items the inventory holds after this step (:354-357), from registers
-    int goal_cnt = (upd && slot == goal_item) ? inv_slot + delta : inv_goal;
+    int goal_cnt = lean_goal_slot(upd, slot, goal_item, inv_slot, delta, inv_goal);
     if (EXT && __any(crate_now)) {                                                 // Crate.step :1086-1089 (the crate's own slot holds no ingredient)
         for (int i = 1; i < K; i++) {
-            const uint32_t w = i < 8 ? X.crate_add[0] : (i < 16 ? X.crate_add[1] : X.crate_add[2]);
-            const int q = (int)((w >> (4 * (i & 7))) & 15u);
+            const int q = lean_crate_qty(X, i);
             if (q && crate_now) {
                 const int nv = inv[i] + q;
                 inv[i] = nv; if (WT) stg<int>(binv, rowoff + 4u * (uint32_t)i, nv); if (HW) stgs<int>(hinv, rowoff + 4u * (uint32_t)i, nv);
-                goal_cnt += i == goal_item ? q : 0;
             }
         }
+        if (crate_now) goal_cnt += lean_crate_goal(X, goal_item, K);
     }
     if (wcell) { if (STAGE) mp[fcell] = (int8_t)cellv; if (WT) stg<int8_t>(bmap, mapoff + (uint32_t)fcell, (int8_t)cellv); if (HW) stgs<int8_t>(hmap, mapoff + (uint32_t)fcell, (int8_t)cellv); }
     if (__any(crafted)) {                                                          // :455-474 (ids of a recipe are distinct)
@@ -213,8 +298,7 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
             if (nin > 1) { inv[in1] = iv1 - nd1; if (WT) stg<int>(binv, rowoff + 4u * (uint32_t)in1, iv1 - nd1); if (HW) stgs<int>(hinv, rowoff + 4u * (uint32_t)in1, iv1 - nd1); }
             if (nin > 2) { inv[in2] = iv2 - nd2; if (WT) stg<int>(binv, rowoff + 4u * (uint32_t)in2, iv2 - nd2); if (HW) stgs<int>(hinv, rowoff + 4u * (uint32_t)in2, iv2 - nd2); }
             if (nin > 3) { inv[in3] = iv3 - nd3; if (WT) stg<int>(binv, rowoff + 4u * (uint32_t)in3, iv3 - nd3); if (HW) stgs<int>(hinv, rowoff + 4u * (uint32_t)in3, iv3 - nd3); }
-            goal_cnt -= (nin > 0 && in0 == goal_item ? nd0 : 0) + (nin > 1 && in1 == goal_item ? nd1 : 0) +
-                        (nin > 2 && in2 == goal_item ? nd2 : 0) + (nin > 3 && in3 == goal_item ? nd3 : 0);
+            goal_cnt -= lean_craft_goal_used(e0, e1, e2, goal_item);
         }
     }
     if (upd) { inv[slot] = inv_slot + delta; if (WT) stg<int>(binv, rowoff + 4u * (uint32_t)slot, inv_slot + delta); if (HW) stgs<int>(hinv, rowoff + 4u * (uint32_t)slot, inv_slot + delta); }
@@ -226,14 +310,14 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
 #pragma unroll
         for (int k = 0; k < 9; k++) {
             ev[k] = cell_at(ac + (k / 3 - 1) * S + (k % 3 - 1));
-            found |= ev[k] != 0 && ((U.ent_mask >> ev[k]) & 1u);
+            found |= lean_grabs(U, ev[k]);
         }
         found &= valid;
         if (__any(found)) {
 #pragma unroll
             for (int k = 0; k < 9; k++) {
                 const int id = ev[k];
-                if (found && id != 0 && ((U.ent_mask >> id) & 1u)) {
+                if (found && lean_grabs(U, id)) {
                     const int qc = ac + (k / 3 - 1) * S + (k % 3 - 1);
                     if (STAGE) mp[qc] = 0;
                     if (WT) stg<int8_t>(bmap, mapoff + (uint32_t)qc, (int8_t)0); if (HW) stgs<int8_t>(hmap, mapoff + (uint32_t)qc, (int8_t)0);
@@ -245,31 +329,19 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
             }
         }
     }
-    int done = goal_cnt >= 1;                                                      // :354-357
-    if (done) rew = U.reward_done;
+    int done = lean_goal_done(U, goal_cnt, rew);                                   // :354-357
     int twice = 0;
     if (EXT) {
-        if (fence_twice) {                                                         // FenceRestriction.step :949-972: its own info + a
-            succ = true; cost = (int)((e5 >> 14) & 63u); msg = NGW_MSG_NONE; arg = 0;   // second step_count += 1 (:966)
-            twice = 1;
-        }
-        const uint32_t kind = e0 & 15u;
-        const bool fire_on = X.fire_item && valid && !((X.nest & NGW_XF_FIRE_SKIP_BREAK) && kind == NGW_ACT_BREAK) &&
-                             !((X.nest >> 8) && kind == NGW_ACT_CRAFT && (uint32_t)aarg + 1u == (X.nest >> 8));
+        if (fence_twice) { lean_report_fence_twice(p, e5); twice = 1; }            // FenceRestriction.step :949-972: its own info + a second step_count += 1 (:966)
+        const bool fire_on = lean_fire_on(X, valid, e0);
         if (__any(fire_on)) {                                                      // FireWall.step :1168-1189, after the wrapped step
-            const int ac = nr * S + nc, fire = X.fire_item;
-            const bool burning = cell_at(ac - S) == fire || cell_at(ac + S) == fire || cell_at(ac - 1) == fire || cell_at(ac + 1) == fire;
-            if (fire_on && burning) { rew = X.fire_reward; done = 1; msg = NGW_MSG_FIRE_WALL; arg = 0; }
+            const int ac = nr * S + nc;
+            const bool burning = lean_burning(X, cell_at(ac - S), cell_at(ac + S), cell_at(ac - 1), cell_at(ac + 1));
+            if (fire_on && burning) lean_report_fire(X, p, rew, done);
         }
     }
     LeanOut o;
-    o.flags = 0; o.reward = 0; o.ended = 0; o.steps = steps0; o.info = 0; o.do_reset = false;
-    if (valid) {
-        o.steps = steps0 + 1 + twice;                                              // :362
-        o.reward = rew; o.ended = done;
-        o.info = (succ ? 1u : 0u) | ((uint32_t)done << 1) | ((uint32_t)cost << 2) | ((uint32_t)msg << 8) | ((uint32_t)arg << 16);
-        if (autoreset && (done || (horizon > 0 && o.steps >= horizon))) { o.do_reset = true; o.ended = 1; }   // same-step autoreset
-    } else if (live) o.flags = NGW_F_INVALID_ACTION;
+    lean_epilogue(o, live, valid, steps0, twice, rew, done, p, autoreset, horizon);
     o.r = nr; o.c = nc; o.f = nf; o.sel = nsel;
     o.wcell = wcell; o.cellv = cellv; o.grab = grab;
     return o;

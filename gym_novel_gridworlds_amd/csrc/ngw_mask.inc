@@ -11,20 +11,19 @@
 // scalar.  The only per-action memory reads are the recipe-input and argument slots of the LDS row (and, with FenceRestriction, the fence
 // cells of a Break - fetched once per wave that breaks anything breakable).
 
-// The mask of one lane's env from its pose and selected item, its inventory row (a lane-private LDS row) and its map (cell_at: a cell
-// index -> the item there).  Fetches the table (lane l holds entry l), the uniform parameters and the wrapper predicates itself, so that a
-// caller has nothing of them live across its own work.  All lanes of the wave must be active (the loop is wave-uniform).
-template <bool EXT, class CELL>
-__device__ __forceinline__ uint64_t lane_mask(const NgwDevSpec* __restrict__ dspec, int S, int K, int r, int c, int f, int sel, const int32_t* inv,
-                                              const CELL& cell_at) {
-    const uint32_t tid = threadIdx.x;
-    uint32_t t0, t1, t2, t4;
-    {
-        const uint2* ld = reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(dspec->act_lean) + min(tid, (uint32_t)(NGW_MAX_ACTIONS - 1)) * (4u * NGW_LEAN_DW));
-        const uint2 x0 = ld[0], x1 = ld[1], x2 = ld[2];
-        t0 = x0.x; t1 = x0.y; t2 = x1.x; t4 = x2.x;
-    }
-    NgwStepU U;                                                                    // uniform: scalar loads
+// ---- what the mask walk and the lookahead walk (ngw_lookahead.inc) share before their loops over the entries
+
+// The micro-op table as the step kernels fetch it: lane l holds the six words of entry l (a walk reads entry a out of lane a).
+struct LeanTable { uint32_t t0, t1, t2, t3, t4, t5; };
+__device__ __forceinline__ LeanTable lean_fetch_table(const NgwDevSpec* __restrict__ dspec) {
+    const uint2* ld = reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(dspec->act_lean) + min(threadIdx.x, (uint32_t)(NGW_MAX_ACTIONS - 1)) * (4u * NGW_LEAN_DW));
+    const uint2 x0 = ld[0], x1 = ld[1], x2 = ld[2];
+    return {x0.x, x0.y, x1.x, x1.y, x2.x, x2.y};
+}
+
+// The uniform parameters and (EXT) the wrapper predicates: scalar loads.
+template <bool EXT>
+__device__ __forceinline__ void lean_fetch_uniforms(const NgwDevSpec* __restrict__ dspec, NgwStepU& U, NgwExtU& X) {
     {
         const uint32_t* up = reinterpret_cast<const uint32_t*>(&dspec->u);
         uint32_t uw[16];
@@ -32,7 +31,7 @@ __device__ __forceinline__ uint64_t lane_mask(const NgwDevSpec* __restrict__ dsp
         for (int i = 0; i < 16; i++) uw[i] = up[i];
         __builtin_memcpy(&U, uw, sizeof(U));
     }
-    NgwExtU X = {};
+    X = {};
     if (EXT) {
         const uint32_t* xp = reinterpret_cast<const uint32_t*>(&dspec->x);
         uint32_t xw[9];
@@ -40,33 +39,87 @@ __device__ __forceinline__ uint64_t lane_mask(const NgwDevSpec* __restrict__ dsp
         for (int i = 0; i < 9; i++) xw[i] = xp[i];
         __builtin_memcpy(&X, xw, sizeof(X));
     }
-    // ---- the cells every entry looks at (lean_body's L0 reads)
+}
+
+// The cells every entry looks at (lean_body's L0 reads): the block in front, its 4-neighbourhood and (Jump) the cell two ahead.
+struct LeanFront {
+    int dcell, fr, fc, fcell, front;
+    bool okN, okS, okW, okE;
+    int nbN, nbS, nbW, nbE;
+    int fr2, fc2;
+    bool ok2;
+    int front2;
+};
+template <class CELL>
+__device__ __forceinline__ LeanFront lean_front_cells(const NgwStepU& U, int S, int r, int c, int f, const CELL& cell_at) {
+    LeanFront q;
     const int dr = (f == 0) ? -1 : (f == 1 ? 1 : 0), dc = (f == 2) ? -1 : (f == 3 ? 1 : 0);
-    const int fr = r + dr, fc = c + dc, dcell = dr * S + dc, fcell = r * S + c + dcell;
-    const int front = cell_at(fcell);
-    const bool okN = fr > 0, okS = fr < S - 1, okW = fc > 0, okE = fc < S - 1;
-    const int nbN = cell_at(okN ? fcell - S : fcell), nbS = cell_at(okS ? fcell + S : fcell);
-    const int nbW = cell_at(okW ? fcell - 1 : fcell), nbE = cell_at(okE ? fcell + 1 : fcell);
-    const int fr2 = fr + dr, fc2 = fc + dc;
-    const bool ok2 = fr2 >= 0 && fr2 <= S - 1 && fc2 >= 0 && fc2 <= S - 1;
-    int front2 = 1;
-    if (U.feat & NGW_FEAT_JUMP) front2 = cell_at(ok2 ? fcell + dcell : fcell);
+    q.fr = r + dr; q.fc = c + dc; q.dcell = dr * S + dc; q.fcell = r * S + c + q.dcell;
+    q.front = cell_at(q.fcell);
+    q.okN = q.fr > 0; q.okS = q.fr < S - 1; q.okW = q.fc > 0; q.okE = q.fc < S - 1;
+    q.nbN = cell_at(q.okN ? q.fcell - S : q.fcell); q.nbS = cell_at(q.okS ? q.fcell + S : q.fcell);
+    q.nbW = cell_at(q.okW ? q.fcell - 1 : q.fcell); q.nbE = cell_at(q.okE ? q.fcell + 1 : q.fcell);
+    q.fr2 = q.fr + dr; q.fc2 = q.fc + dc;
+    q.ok2 = q.fr2 >= 0 && q.fr2 <= S - 1 && q.fc2 >= 0 && q.fc2 <= S - 1;
+    q.front2 = 1;
+    if (U.feat & NGW_FEAT_JUMP) q.front2 = cell_at(q.ok2 ? q.fcell + q.dcell : q.fcell);
+    return q;
+}
+
+// One lane's env as the standalone kernels read it from HBM: the pose (a padding lane gets a pose inside the map - its rows are zeros),
+// the selected item, where its map starts, and its inventory row landed in the lane's private LDS row.
+struct LeanLane {
+    bool live;                                                                     // (every state array is n_pad long: lanes beyond n read padding rows)
+    int r, c, f, sel;
+    const char* bmap;
+    uint32_t mapoff;
+    int32_t* inv;
+};
+__device__ __forceinline__ LeanLane lean_load_lane(const NgwBufs& b, uint32_t n32, int S, int K, int32_t* inv_lds) {
+    const uint32_t bid = blockIdx.x, tid = threadIdx.x;
+    const int S2 = S * S, KP = K | 1;
+    const int nlive = (int)min((int64_t)EPB, (int64_t)n32 - (int64_t)bid * EPB);
+    LeanLane l;
+    l.live = (int)tid < nlive;
+    l.bmap = reinterpret_cast<const char*>(b.map) + (uint64_t)bid * (uint32_t)(EPB * S2);
+    const char* const binv = reinterpret_cast<const char*>(b.inv) + (uint64_t)bid * (uint32_t)(EPB * 4 * K);
+    const int2 rc = ldg<int2>(reinterpret_cast<const char*>(b.loc) + (uint64_t)bid * (EPB * 8), tid * 8u);
+    const int f0 = ldg<int>(reinterpret_cast<const char*>(b.facing) + (uint64_t)bid * (EPB * 4), tid * 4u);
+    l.sel = ldg<uint8_t>(reinterpret_cast<const char*>(b.selected) + (uint64_t)bid * EPB, tid);
+    l.inv = inv_lds + tid * KP;
+    for (int k = 0; k < K; k++) l.inv[k] = ldg<int>(binv, tid * 4u * (uint32_t)K + 4u * (uint32_t)k);
+    l.r = l.live ? rc.x : 1; l.c = l.live ? rc.y : 1; l.f = l.live ? (f0 & 3) : 0;
+    l.mapoff = tid * (uint32_t)S2;
+    return l;
+}
+
+// The mask of one lane's env from its pose and selected item, its inventory row (a lane-private LDS row) and its map (cell_at: a cell
+// index -> the item there).  Fetches the table (lane l holds entry l), the uniform parameters and the wrapper predicates itself, so that a
+// caller has nothing of them live across its own work.  All lanes of the wave must be active (the loop is wave-uniform).
+template <bool EXT, class CELL>
+__device__ __forceinline__ uint64_t lane_mask(const NgwDevSpec* __restrict__ dspec, int S, int K, int r, int c, int f, int sel, const int32_t* inv,
+                                              const CELL& cell_at) {
+    const LeanTable t = lean_fetch_table(dspec);
+    NgwStepU U;
+    NgwExtU X;
+    lean_fetch_uniforms<EXT>(dspec, U, X);
+    const LeanFront q = lean_front_cells(U, S, r, c, f, cell_at);
     const int inv_place = inv[U.place_item], inv_axe = inv[U.axe_item];
     uint64_t mask = 0;
     const int A = min(U.n_actions, NGW_MAX_ACTIONS);
     for (int a = 0; a < A; a++) {
-        const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)t0, a), e1 = (uint32_t)__builtin_amdgcn_readlane((int)t1, a);
-        const uint32_t e2 = (uint32_t)__builtin_amdgcn_readlane((int)t2, a), e4 = (uint32_t)__builtin_amdgcn_readlane((int)t4, a);
+        const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)t.t0, a), e1 = (uint32_t)__builtin_amdgcn_readlane((int)t.t1, a);
+        const uint32_t e2 = (uint32_t)__builtin_amdgcn_readlane((int)t.t2, a), e4 = (uint32_t)__builtin_amdgcn_readlane((int)t.t4, a);
         const int aarg = (e0 >> 8) & 255;
         const int inv_arg = inv[min(aarg, K - 1)];
         const int iv0 = inv[e1 & 255], iv1 = inv[(e1 >> 8) & 255], iv2 = inv[(e1 >> 16) & 255], iv3 = inv[e1 >> 24];
         bool axe_ok;
         uint32_t missing;
-        const uint32_t cb = lean_cond_bits(U, e0, e2, front, front2, ok2, okN, okS, okW, okE, nbN, nbS, nbW, nbE, inv_place, inv_axe, inv_arg,
-                                           iv0, iv1, iv2, iv3, sel, axe_ok, missing);
+        const uint32_t cb = lean_cond_bits(U, e0, e2, q.front, q.front2, q.ok2, q.okN, q.okS, q.okW, q.okE, q.nbN, q.nbS, q.nbW, q.nbE, inv_place,
+                                           inv_axe, inv_arg, iv0, iv1, iv2, iv3, sel, axe_ok, missing);
         const uint32_t s = lean_outcome(cb, e4);
         LeanBreakX xb = {false, false, false};
-        if (EXT) xb = lean_break_ext(U, X, ((e0 >> 24) & 1u) != 0, front, S, r, c, f, fr, fc, fcell, cell_at);
+        if (EXT) xb = lean_break_ext(U, X, lean_is_break(e0), q.front, S, r, c, f, q.fr, q.fc, q.fcell, cell_at);
         mask |= (uint64_t)(lean_result(s, xb) ? 1u : 0u) << a;
     }
     return mask;
@@ -78,19 +131,8 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_mask_kernel(const NgwDevSpec* __r
                                                            uint64_t* __restrict__ out) {
     __shared__ int32_t inv_lds[NGW_EPB * (NGW_MAX_ITEMS | 1)];
     const uint32_t bid = blockIdx.x, tid = threadIdx.x;
-    const int S2 = S * S, KP = K | 1;
-    const int nlive = (int)min((int64_t)EPB, (int64_t)n32 - (int64_t)bid * EPB);
-    const bool live = (int)tid < nlive;                                            // (every state array is n_pad long: lanes beyond n read padding rows)
-    const char* const bmap = reinterpret_cast<const char*>(b.map) + (uint64_t)bid * (uint32_t)(EPB * S2);
-    const char* const binv = reinterpret_cast<const char*>(b.inv) + (uint64_t)bid * (uint32_t)(EPB * 4 * K);
-    const int2 rc = ldg<int2>(reinterpret_cast<const char*>(b.loc) + (uint64_t)bid * (EPB * 8), tid * 8u);
-    const int f0 = ldg<int>(reinterpret_cast<const char*>(b.facing) + (uint64_t)bid * (EPB * 4), tid * 4u);
-    const int sel = ldg<uint8_t>(reinterpret_cast<const char*>(b.selected) + (uint64_t)bid * EPB, tid);
-    int32_t* inv = inv_lds + tid * KP;
-    for (int k = 0; k < K; k++) inv[k] = ldg<int>(binv, tid * 4u * (uint32_t)K + 4u * (uint32_t)k);
-    // a padding lane evaluates a pose inside the map (its rows are zeros) and stores 0
-    const uint32_t mapoff = tid * (uint32_t)S2;
-    auto cell_at = [&](int cell) -> int { return (int)ldg<int8_t>(bmap, mapoff + (uint32_t)cell); };
-    const uint64_t mask = lane_mask<EXT>(dspec, S, K, live ? rc.x : 1, live ? rc.y : 1, live ? (f0 & 3) : 0, sel, inv, cell_at);
-    stg<uint64_t>(reinterpret_cast<char*>(out) + (uint64_t)bid * (EPB * 8), tid * 8u, live ? mask : 0ull);
+    const LeanLane l = lean_load_lane(b, n32, S, K, inv_lds);
+    auto cell_at = [&](int cell) -> int { return (int)ldg<int8_t>(l.bmap, l.mapoff + (uint32_t)cell); };
+    const uint64_t mask = lane_mask<EXT>(dspec, S, K, l.r, l.c, l.f, l.sel, l.inv, cell_at);
+    stg<uint64_t>(reinterpret_cast<char*>(out) + (uint64_t)bid * (EPB * 8), tid * 8u, l.live ? mask : 0ull);
 }

@@ -110,6 +110,10 @@ class ShardedVecNovelGridworld:
     def action_mask_words(self, device=False, copy=False):
         return self.local.action_mask_words(device, copy)
 
+    def lookahead(self, device=False, copy=False):
+        """The one-step lookahead table of this rank's shard (VecNovelGridworld.lookahead): rank-local, no collective."""
+        return self.local.lookahead(device=device, copy=copy)
+
     def snapshot(self, capacity=None):
         """A device-side snapshot of this rank's shard (VecNovelGridworld.snapshot): rank-local, env indices are the shard's own."""
         return self.local.snapshot(capacity)

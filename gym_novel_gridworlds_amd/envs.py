@@ -306,6 +306,14 @@ class _NovelGridworldEnv(_EnvBase):
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
         return vec.action_masks()[0]
 
+    def lookahead(self, device=False, copy=False):
+        """Every action's outcome from the current state, without taking a step: 'reward' int32 [A], 'done' bool [A], 'result' bool [A]
+        and 'info' uint32 [A] words (A = len(actions_id)); see VecNovelGridworld.lookahead.  While the device's resident step loop runs,
+        the answer is read from the outcomes it has already speculated for every action (no relaunch, the loop keeps running)."""
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        return vec.lookahead(device=device, copy=copy).row(0)
+
     def get_observation(self):
         assert not self.max_items < len(self.items), "Cannot have more than " + str(self.max_items) + " items"
         return {'map': self.map, 'agent_location': self.agent_location, 'agent_facing_id': self.agent_facing_id,

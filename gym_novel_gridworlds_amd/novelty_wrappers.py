@@ -46,6 +46,9 @@ class NoveltyWrapper(object):
     def action_masks(self):
         return self.env.action_masks()
 
+    def lookahead(self, device=False, copy=False):
+        return self.env.lookahead(device=device, copy=copy)
+
     def render(self, mode='human', **kwargs):
         return self.env.render(mode, **kwargs)
 

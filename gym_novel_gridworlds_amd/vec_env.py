@@ -4,6 +4,7 @@ Batched mirror of the reference `gym.Env` surface (gym_novel_gridworlds/envs/pog
 `reset()` :86, `step(action_id)` :230 -> `(obs, reward, done, info)`, `get_observation()` :214 with the Dict
 observation of map / agent_location / agent_facing_id / inventory_items_quantity, plus `inject_novelty`
 semantics through `novelty=`.  All computation happens in the HIP kernels behind the C-ABI (`_cabi.py`)."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -29,6 +30,26 @@ def unpack_action_masks(words, n_actions):
     w = np.ascontiguousarray(words, np.uint64).reshape(-1)
     bits = w.view(np.uint8).reshape(-1, 8)                  # little-endian: byte j holds actions 8j .. 8j+7
     return np.unpackbits(bits, axis=1, bitorder='little')[:, :n_actions].astype(bool)
+
+
+def decode_info_words(words):
+    """Packed info words (include/ngw.h NGW_INFO_*) of any shape -> a StepInfo that decodes 'result', 'step_cost_code', 'message_code',
+    'message_arg' and 'step_cost' when they are read: what VecNovelGridworld.step_costs / .messages take.  For a lookahead table hand in
+    one column (`info[:, a]`, with actions = a) or one row (`info[i]`, with actions = range(A))."""
+    return StepInfo({'_words': np.asarray(words, np.uint32)})
+
+
+class Lookahead(collections.namedtuple('Lookahead', 'reward done result info')):
+    """What lookahead() returns: reward int32, done bool, result bool, info uint32 words, each [N, A] ([A] on the single-env adapter).
+    A named tuple (it unpacks in that order) whose fields can also be read by name: t['reward']."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    def row(self, i):
+        """Env i's rows (the single-env adapter's view)."""
+        return Lookahead(*[x[i] for x in self])
 
 
 class StepInfo(dict):
@@ -674,6 +695,36 @@ class VecNovelGridworld:
             bits = torch.arange(self.n_actions, device=w.device, dtype=torch.int64)
             return ((w[:, None] >> bits) & 1).bool()
         return unpack_action_masks(self.action_mask_words(), self.n_actions)
+
+    # ------------------------------------------------------------------ one-step lookahead tables (include/ngw.h ngw_lookahead)
+    def lookahead(self, device=False, copy=False):
+        """Every action's outcome for every env, from the current state, without taking a step: a Lookahead of 'reward' int32 [N, A],
+        'done' bool [N, A], 'result' bool [N, A] and 'info' uint32 [N, A] (the packed words: decode_info_words(info[:, a]) gives what
+        step_costs() / messages() take).  Entry (i, a) is what step() would report for env i with action a, under every novelty and the
+        autoreset setting; nothing is committed (no state byte changes, no reset runs, no prepared episode is consumed), and a second call
+        without a change of state launches nothing.  On the host these are the handle's own arrays, overwritten by the next call
+        (copy=True: fresh arrays).  device=True: zero-copy torch tensors shaped [N, A] over the device table - strided views of its
+        action-major layout, valid until the next call that changes the state; 'info' is int32 there (the same bits), 'result' is
+        computed from it."""
+        L, N, A = _cabi.lib(), self.num_envs, self.n_actions
+        if device:
+            import torch
+            _cabi.check(L.ngw_lookahead(self._h))
+            p = [C.c_void_p() for _ in range(3)]
+            es, as_ = C.c_int64(), C.c_int64()
+            _cabi.check(L.ngw_lookahead_device_ptrs(self._h, C.byref(p[0]), C.byref(p[1]), C.byref(p[2]), C.byref(es), C.byref(as_)))
+            assert es.value == 1, "the device table is action-major"
+            self.sync()
+            dev = 'cuda:%d' % self.device
+            view = lambda ptr, ts: torch.as_tensor(_DevArray(ptr.value, (A, as_.value), ts), device=dev)[:, :N].t()   # noqa: E731
+            info = view(p[2], '<i4')
+            return Lookahead(view(p[0], '<i4'), view(p[1], '|u1').view(torch.bool), (info & 1).bool(), info)
+        h = self.__dict__.get('_look_host')
+        if h is None or h[0].shape != (N, A):
+            h = self._look_host = (np.zeros((N, A), np.int32), np.zeros((N, A), np.uint8), np.zeros((N, A), np.uint32))
+        _cabi.check(L.ngw_get_lookahead(self._h, _cabi._ptr(h[0], np.int32), _cabi._ptr(h[1], np.uint8), _cabi._ptr(h[2], np.uint32)))
+        reward, done, info = (x.copy() for x in h) if copy else h
+        return Lookahead(reward, done.view(np.bool_), (info & 1).astype(np.bool_), info)
 
     # ------------------------------------------------------------------ multi-GPU observation stack (dist.py)
     def pack_layout(self):

@@ -91,17 +91,49 @@ class LimitActions(NoveltyWrapper):
         a limited id step() would refuse is False."""
         return limit_mask_columns(self.env.action_masks(), self.limited_actions_id, self.actions_id, len(self.limited_actions))
 
+    def lookahead(self, device=False, copy=False):
+        """The env's lookahead table in the limited id space: column i of 'reward' / 'done' / 'result' / 'info' is the env's column of the
+        action limited id i steps (the same two look-ups as step); a limited id step() would refuse is a column of zeros.  device=True:
+        torch tensors on the env's device, gathered from its zero-copy views (new tensors, not views)."""
+        from .vec_env import Lookahead
+        n = len(self.limited_actions)
+        if device:
+            import torch
+            t = self.env.lookahead(device=True)
+            ids = limit_column_ids(self.limited_actions_id, self.actions_id, n, t['reward'].shape[-1])
 
-def limit_mask_columns(inner, limited_actions_id, actions_id, n):
-    """The env's mask row(s) `inner` ([..., n_env_actions]) in LimitActions' id space: column i <- the env's column of the FIRST name
-    that holds limited id i in `limited_actions_id` (table order), looked up in `actions_id`."""
-    inner = np.asarray(inner, bool)
-    out = np.zeros(inner.shape[:-1] + (n,), bool)
+            def cols(x):
+                out = torch.zeros(tuple(x.shape[:-1]) + (n,), dtype=x.dtype, device=x.device)
+                for i, j in enumerate(ids):
+                    if j is not None:
+                        out[..., i] = x[..., j]
+                return out
+            return Lookahead(cols(t['reward']), cols(t['done']), cols(t['result']), cols(t['info']))
+        t = self.env.lookahead(copy=copy)
+        cols = lambda x, dt: limit_mask_columns(x, self.limited_actions_id, self.actions_id, n, dt)   # noqa: E731
+        return Lookahead(cols(t['reward'], np.int32), cols(t['done'], bool), cols(t['result'], bool), cols(t['info'], np.uint32))
+
+
+def limit_column_ids(limited_actions_id, actions_id, n, width):
+    """For each limited id i < n, the env's column it steps: the env's id (in `actions_id`) of the FIRST name that holds limited id i in
+    `limited_actions_id` (table order); None where step() would refuse the id or the env has no such column (< width)."""
+    ids = []
     for i in range(n):
         name = next((candidate for candidate, limited in limited_actions_id.items() if limited == i), None)
-        if name is None or name not in actions_id or actions_id[name] >= inner.shape[-1]:
-            continue
-        out[..., i] = inner[..., actions_id[name]]
+        ok = name is not None and name in actions_id and actions_id[name] < width
+        ids.append(actions_id[name] if ok else None)
+    return ids
+
+
+def limit_mask_columns(inner, limited_actions_id, actions_id, n, dtype=bool):
+    """The env's mask row(s) `inner` ([..., n_env_actions]) in LimitActions' id space: column i <- the env's column limited id i steps
+    (limit_column_ids).  dtype: the columns of a lookahead table map the same way (a limited id step() would refuse is a column of
+    zeros)."""
+    inner = np.asarray(inner, dtype)
+    out = np.zeros(inner.shape[:-1] + (n,), dtype)
+    for i, j in enumerate(limit_column_ids(limited_actions_id, actions_id, n, inner.shape[-1])):
+        if j is not None:
+            out[..., i] = inner[..., j]
     return out
 
 

@@ -479,6 +479,31 @@ int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_de
 int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t count, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv,
                      int32_t* selected, int32_t* step_count, uint32_t* episode);
 
+/* One-step lookahead tables: every action's outcome for every env, without taking a step.
+ * For a handle with A = n_actions the table of the CURRENT state is three arrays - reward int32, done uint8, info uint32 (the NGW_INFO_* packing).
+ * Entry (i, a) holds exactly what ngw_get_step_out would report for env i if ngw_step_device were called now with action a for that env, under
+ * the handle's spec - every novelty, the wrapper predicates (FireWall death, FenceRestriction, Crate), the axe rules, Jump, Chop, the sticky
+ * `done` with its forced reward - and under its autoreset setting: a step that reaches the horizon reports done = 1, and info bit 1 is set only
+ * for goal-done.  Bit 0 of info[i][a] equals bit a of env i's action mask, by construction (one predicate).  Columns a >= n_actions do not exist.
+ * Nothing is committed: after the call every byte of the state is what it was - map, pose, inventory, selected item, step_count, episode -, and so
+ * are the last step's reward / done / info, the prepared next episodes, the mask buffer, the lidar rows, the bit rows and the host mirrors; no
+ * reset is performed and no prepared row is consumed, even for entries that end an episode.
+ * The handle tracks whether its table describes the current state exactly as it does for the mask buffer: every launch that changes the state
+ * (step, host step, reset, ngw_set_state, snapshot restore, rollout, graph launch) makes it stale, as does a change of the autoreset setting, and
+ * the next query recomputes it (one kernel launch); a query on a current table launches nothing.  The buffers are allocated on first use and freed
+ * by ngw_destroy.
+ *   ngw_lookahead              makes the device table current (enqueued on the handle's stream; does not wait).
+ *   ngw_get_lookahead          the table to host arrays [n_envs][A], env-major, made current first; any pointer may be NULL; waits for the stream.
+ *                              A one-env handle whose resident step loop is running answers from the outcomes the loop has speculated for every
+ *                              action of the current state: no launch, the loop keeps running.
+ *   ngw_lookahead_device_ptrs  the device buffers in place (call ngw_lookahead before reading them; any pointer may be NULL).  The device layout
+ *                              is ACTION-MAJOR, [A][n_pad] with n_pad = n_envs rounded up to a multiple of 64: entry (i, a) of each array is element
+ *                              i * env_stride + a * action_stride (strides in ELEMENTS of the array's type; env_stride = 1, action_stride = n_pad),
+ *                              so that one lane per env stores consecutive addresses.  Columns of padding envs are 0. */
+int ngw_lookahead(ngw_handle* h);
+int ngw_get_lookahead(ngw_handle* h, int32_t* reward, uint8_t* done, uint32_t* info);
+int ngw_lookahead_device_ptrs(ngw_handle* h, void** reward, void** done, void** info, int64_t* env_stride, int64_t* action_stride);
+
 #ifdef __cplusplus
 }
 #endif
