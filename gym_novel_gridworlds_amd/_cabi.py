@@ -28,7 +28,8 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_host_step_layout_packed', 'ngw_step_host_packed', 'ngw_lidar_host_rows',
            'ngw_set_action_mask', 'ngw_action_mask', 'ngw_get_action_mask', 'ngw_action_mask_device_ptr',
            'ngw_snapshot_create', 'ngw_snapshot_destroy', 'ngw_snapshot_save', 'ngw_snapshot_restore', 'ngw_snapshot_get',
-           'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs']
+           'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
+           'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
 _lib = None
 
@@ -165,6 +166,10 @@ def lib():
         L.ngw_lookahead.argtypes = [vp]
         L.ngw_get_lookahead.argtypes = [vp, vp, vp, vp]
         L.ngw_lookahead_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
+    if hasattr(L, 'ngw_plan_eval'):
+        L.ngw_plan_eval.argtypes = [vp, vp, i64, i32, i32]
+        L.ngw_get_plan_eval.argtypes = [vp, vp, vp, vp, vp]
+        L.ngw_plan_eval_device_ptrs.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(i64), C.POINTER(i64)]
     L.ngw_host_alloc.argtypes = [u64]
     L.ngw_host_alloc.restype = vp
     L.ngw_host_free.argtypes = [vp]

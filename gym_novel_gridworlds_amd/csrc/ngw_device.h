@@ -413,6 +413,23 @@ extern "C"
 hipError_t ngw_lookahead_launch(const NgwDevSpec* dspec, const NgwBufs* b, int64_t n, int64_t n_pad, int S, int K, int ext, int autoreset, int horizon,
                                 int32_t* reward, uint8_t* done, uint32_t* info, unsigned grid, hipStream_t stream);
 
+/* Plan evaluation (ngw_plans.inc, ngw_abi_plans.cpp): n_plans candidate action sequences per env, stepped from the state in HBM on a private
+ * copy; nothing but the four result arrays is written.  Results are PLAN-MAJOR: element (e, p) of each array at [p * n_pad + e], padding rows 0.
+ * The launch block is the handle's rollout layout with actions = the plans (int32, action of env e, plan p, step t at
+ * [(t * n_plans + p) * t0 + e]), t0 = their env stride, n_steps, autoreset, horizon. */
+struct NgwPlan {
+    int32_t* ret;         /* [n_plans][n_pad] sum of the executed steps' rewards */
+    int32_t* length;      /* [n_plans][n_pad] steps executed */
+    uint8_t* ended;       /* [n_plans][n_pad] 1: the plan stopped at an episode end */
+    uint32_t* info;       /* [n_plans][n_pad] packed info word of the last executed step */
+    int32_t n_plans;
+    int32_t plan_major;   /* block order: 0 = env-block-major (bid = env_block * n_plans + p), 1 = plan-major (bid = p * env_blocks + env_block) */
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_plans_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwPlan* pa, int map_mode, int ext, size_t lds_bytes, hipStream_t stream);
+
 /* Device-side snapshots (ngw_snapshot.inc, ngw_abi_snapshot.cpp): the seven state arrays of `rows` envs, laid out like the state slab
  * itself (one array per field, row i of every array = one env).  The state slab is the set {map, loc, facing, inv, selected, step_count,
  * episode} of NgwBufs, a snapshot is a second such set of `capacity` rows. */

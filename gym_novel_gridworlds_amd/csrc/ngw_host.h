@@ -6,6 +6,7 @@
 //   ngw_abi_debug.cpp    timing pair and diagnostics entry points (not in include/ngw.h)
 //   ngw_abi_mask.cpp     action masks: the standalone mask kernel, staleness, the one-env loop's speculated records
 //   ngw_abi_lookahead.cpp one-step lookahead tables: the lookahead kernel (ngw_lookahead.inc), staleness, the one-env loop's speculated records
+//   ngw_abi_plans.cpp    plan evaluation: candidate action sequences scored from the current state without committing a step (ngw_plans.inc)
 //   ngw_abi_snapshot.cpp device-side snapshots: save / restore / fork env states by index (ngw_snapshot.inc)
 //
 // Three rules hold in all of them:
@@ -187,6 +188,15 @@ struct ngw_handle {
     uint32_t* look_info = nullptr;
     bool look_fresh = false;
     int look_autoreset = 0, look_horizon = 0;
+    // Plan evaluation (ngw_abi_plans.cpp, ngw_plans.inc): plan-major [plan_cap][n_pad] return / length / ended / info in HBM, allocated on first use and
+    // regrown when a call brings more plans.  plan_n: plans of the last evaluation (0 = none yet).  Not a fact derived from the state that anything
+    // keeps current: every ngw_plan_eval runs the kernel.
+    int32_t* plan_ret = nullptr;
+    int32_t* plan_len = nullptr;
+    uint8_t* plan_ended = nullptr;
+    uint32_t* plan_info = nullptr;
+    int32_t plan_cap = 0, plan_n = 0;
+    int plan_major = 0;                   // NGW_PLAN_ORDER=plan when the buffers were first allocated: the plan-major block order (A/B, tools/plan_cost.py)
     std::vector<ngw_snapshot*> snaps;     // open snapshots (ngw_snapshot_create); their slabs are in `allocs`, ngw_destroy deletes what is left
     long long solo_starts = 0;            // launches of the one-env resident loop (ngw_debug_solo_starts)
     hipGraph_t graph = nullptr;

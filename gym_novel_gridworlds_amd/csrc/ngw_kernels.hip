@@ -27,14 +27,14 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file THIRTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file FOURTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
 //   8: the bit-row (boards) lidar: in-place step kernels with the O(1) observation, ngw_boards_kernel, ngw_lidar_boards_kernel
 //   9 / 10: the host write-through step kernels, plain / with the bit-row lidar (9 also holds the standalone mask kernel and the in-place step
 //   with fused masks; 1 / 6 / 7 hold the staged ones)
-//   11: device-side snapshots (ngw_snapshot.inc)   12: one-step lookahead tables (ngw_lookahead.inc)
+//   11: device-side snapshots (ngw_snapshot.inc)   12: one-step lookahead tables (ngw_lookahead.inc)   13: plan evaluation (ngw_plans.inc)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -381,6 +381,9 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #include "ngw_reset.inc"
 #if NGW_HAS(12)
 #include "ngw_lookahead.inc"
+#endif
+#if NGW_HAS(13)
+#include "ngw_plans.inc"
 #endif
 
 // ---------------------------------------------------------------- LidarInFront observation kernel (stand-alone launch)
@@ -868,3 +871,21 @@ extern "C" hipError_t ngw_lookahead_launch(const NgwDevSpec* dspec, const NgwBuf
     return hipGetLastError();
 }
 #endif  // NGW_HAS(12)
+#if NGW_HAS(13)
+// plan evaluation (ngw_plans.inc): a = the handle's rollout layout with a.actions = the plans, a.t0 = their env stride, a.n_steps, a.autoreset,
+// a.horizon; grid = n_plans * n_pad / NGW_EPB work-groups
+extern "C" hipError_t ngw_plans_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwPlan* pa, int map_mode, int ext, size_t lds_bytes, hipStream_t stream) {
+    const uint64_t grid = (uint64_t)pa->n_plans * (uint64_t)(a->n_pad / NGW_EPB);
+    if (a->n <= 0 || a->n_pad < a->n || a->n_pad % NGW_EPB || pa->n_plans < 1 || a->n_steps < 1 || a->t0 < a->n || grid * NGW_EPB > 0xFFFFFFFFull ||
+        a->S < 3 || a->S > NGW_MAX_MAP_SIZE || a->K < 1 || a->K > NGW_MAX_ITEMS || !a->actions || !pa->ret || !pa->length || !pa->ended || !pa->info)
+        return hipErrorInvalidValue;
+    switch (map_mode) {
+    case NGW_MAP_STRAIGHT: return ext ? launch_plans_lean<NGW_MAP_STRAIGHT, true>(dspec, a, pa, (unsigned)grid, lds_bytes, stream)
+                                      : launch_plans_lean<NGW_MAP_STRAIGHT, false>(dspec, a, pa, (unsigned)grid, lds_bytes, stream);
+    case NGW_MAP_DWORD: return ext ? launch_plans_lean<NGW_MAP_DWORD, true>(dspec, a, pa, (unsigned)grid, lds_bytes, stream)
+                                   : launch_plans_lean<NGW_MAP_DWORD, false>(dspec, a, pa, (unsigned)grid, lds_bytes, stream);
+    default: return ext ? launch_plans_lean<NGW_MAP_BYTE, true>(dspec, a, pa, (unsigned)grid, lds_bytes, stream)
+                        : launch_plans_lean<NGW_MAP_BYTE, false>(dspec, a, pa, (unsigned)grid, lds_bytes, stream);
+    }
+}
+#endif  // NGW_HAS(13)

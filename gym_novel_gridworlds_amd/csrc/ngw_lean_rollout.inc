@@ -1,5 +1,70 @@
 // ngw_lean_rollout.inc - the fused rollout kernel (included by ngw_lean.inc) and its launcher.
 
+// ---------------------------------------------------------------- stage-in of a wave's 64 envs (fused rollouts, plan evaluation)
+// What a kernel that keeps the state on chip for several steps reads before its first step, as ONE memory round trip: pose, selected item and
+// step count into registers, the inventory rows and the map chunk (coalesced 16-B pieces, `buf` is the caller's piece registers) into the
+// handle's LDS layout (off_map / off_inv, MS, KP), lane l's micro-op entry, and the uniform step parameters U (and X when EXT).  The caller
+// puts the barrier behind it.  bmap .. bstp: the wave's first row of each state array.
+struct RolloutLane { int r, c, f, sel, steps; uint32_t rowoff, t0, t1, t2, t3, t4, t5; uint32_t* lds_map; int8_t* mp; int32_t* inv; };
+template <int MAPMODE, bool EXT>
+__device__ __forceinline__ RolloutLane rollout_stage_in(const NgwDevSpec* __restrict__ dspec, const NgwLaunch& a, uint32_t* lds, uint32_t tid, int K, int npieces,
+                                                        const char* bmap, const char* binv, const char* bloc, const char* bfac, const char* bsel,
+                                                        const char* bstp, u32x4 (&buf)[PB], NgwStepU& U, NgwExtU& X) {
+    const int2 rc = ldg<int2>(bloc, tid * 8u);
+    int r = rc.x, c = rc.y;
+    int f = ldg<int>(bfac, tid * 4u);
+    int sel = ldg<uint8_t>(bsel, tid);
+    int steps = ldg<int>(bstp, tid * 4u);
+    const uint32_t rowoff = tid * 4u * (uint32_t)K;
+    u32x4 q[IQ];
+#pragma unroll
+    for (int j = 0; j < IQ; j++)
+        q[j] = (4 * j < K) ? ldg<u32x4>(binv, rowoff + 4u * (uint32_t)min(4 * j, K - 4)) : u32x4{0u, 0u, 0u, 0u};
+    uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0;
+    if (tid < NGW_MAX_ACTIONS) {
+        const uint2* ld = reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(dspec->act_lean) + tid * (4u * NGW_LEAN_DW));
+        const uint2 x0 = ld[0], x1 = ld[1], x2 = ld[2];
+        t0 = x0.x; t1 = x0.y; t2 = x1.x; t3 = x1.y; t4 = x2.x; t5 = x2.y;
+    }
+#pragma unroll
+    for (int j = 0; j < PB; j++) buf[j] = ldg<u32x4>(bmap, 16u * (uint32_t)min((int)tid + EPB * j, npieces - 1));
+    {
+        const uint32_t* up = reinterpret_cast<const uint32_t*>(&dspec->u);
+        uint32_t uw[16];
+#pragma unroll
+        for (int i = 0; i < 16; i++) uw[i] = up[i];
+        __builtin_memcpy(&U, uw, sizeof(U));
+    }
+    X = NgwExtU{};                                                                // wrapper predicates (FireWall, FenceRestriction, Crate): 9 more dwords
+    if (EXT) {
+        const uint32_t* xp = reinterpret_cast<const uint32_t*>(&dspec->x);
+        uint32_t xw[9];
+#pragma unroll
+        for (int i = 0; i < 9; i++) xw[i] = xp[i];
+        __builtin_memcpy(&X, xw, sizeof(X));
+    }
+    uint32_t* lds_map = lds + a.off_map;
+    int8_t* mp = reinterpret_cast<int8_t*>(lds_map) + tid * a.MS;
+    int32_t* inv = reinterpret_cast<int32_t*>(lds + a.off_inv) + tid * a.KP;
+#pragma unroll
+    for (int j = 0; j < IQ; j++)
+        if (4 * j < K) {
+            const int o = min(4 * j, K - 4);
+            inv[o] = (int)q[j].x; inv[o + 1] = (int)q[j].y; inv[o + 2] = (int)q[j].z; inv[o + 3] = (int)q[j].w;
+        }
+    pieces_lds<true, MAPMODE>(buf, a, lds_map, 0, npieces, tid);
+    for (int base = EPB * PB; base < npieces; base += EPB * PB) {
+#pragma unroll
+        for (int j = 0; j < PB; j++) buf[j] = ldg<u32x4>(bmap, 16u * (uint32_t)min(base + (int)tid + EPB * j, npieces - 1));
+        pieces_lds<true, MAPMODE>(buf, a, lds_map, base, npieces, tid);
+    }
+    RolloutLane L;
+    L.r = r; L.c = c; L.f = f; L.sel = sel; L.steps = steps; L.rowoff = rowoff;
+    L.t0 = t0; L.t1 = t1; L.t2 = t2; L.t3 = t3; L.t4 = t4; L.t5 = t5;
+    L.lds_map = lds_map; L.mp = mp; L.inv = inv;
+    return L;
+}
+
 // ---------------------------------------------------------------- fused rollout of the plain configurations
 // T steps in one launch on the SAME branch-free step (lean_body).  The state lives in LDS (maps, inventory rows) and registers
 // (pose, selected item, step count) for the whole launch and goes back to HBM ONCE, when the launch ends, as the wave's coalesced
@@ -24,57 +89,17 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_rollout_lean(const NgwDevSpec* __
     char* const bfac = reinterpret_cast<char*>(a.b.facing) + (uint64_t)bid * (EPB * 4);
     char* const bsel = reinterpret_cast<char*>(a.b.selected) + (uint64_t)bid * EPB;
     char* const bstp = reinterpret_cast<char*>(a.b.step_count) + (uint64_t)bid * (EPB * 4);
-    // ---- stage in: pose, inventory rows, micro-op entries, map chunk
-    const int2 rc = ldg<int2>(bloc, tid * 8u);
-    int r = rc.x, c = rc.y;
-    int f = ldg<int>(bfac, tid * 4u);
-    int sel = ldg<uint8_t>(bsel, tid);
-    int steps = ldg<int>(bstp, tid * 4u);
-    const uint32_t rowoff = tid * 4u * (uint32_t)K;
-    u32x4 q[IQ];
-#pragma unroll
-    for (int j = 0; j < IQ; j++)
-        q[j] = (4 * j < K) ? ldg<u32x4>(binv, rowoff + 4u * (uint32_t)min(4 * j, K - 4)) : u32x4{0u, 0u, 0u, 0u};
-    uint32_t t0 = 0, t1 = 0, t2 = 0, t3 = 0, t4 = 0, t5 = 0;
-    if (tid < NGW_MAX_ACTIONS) {
-        const uint2* ld = reinterpret_cast<const uint2*>(reinterpret_cast<const char*>(dspec->act_lean) + tid * (4u * NGW_LEAN_DW));
-        const uint2 x0 = ld[0], x1 = ld[1], x2 = ld[2];
-        t0 = x0.x; t1 = x0.y; t2 = x1.x; t3 = x1.y; t4 = x2.x; t5 = x2.y;
-    }
+    // ---- stage in: pose, inventory rows, micro-op entries, map chunk (rollout_stage_in, shared with the plan evaluator)
     u32x4 buf[PB];
-#pragma unroll
-    for (int j = 0; j < PB; j++) buf[j] = ldg<u32x4>(bmap, 16u * (uint32_t)min((int)tid + EPB * j, npieces - 1));
     NgwStepU U;
-    {
-        const uint32_t* up = reinterpret_cast<const uint32_t*>(&dspec->u);
-        uint32_t uw[16];
-#pragma unroll
-        for (int i = 0; i < 16; i++) uw[i] = up[i];
-        __builtin_memcpy(&U, uw, sizeof(U));
-    }
-    NgwExtU X = {};                                                                // wrapper predicates (FireWall, FenceRestriction, Crate): 9 more dwords
-    if (EXT) {
-        const uint32_t* xp = reinterpret_cast<const uint32_t*>(&dspec->x);
-        uint32_t xw[9];
-#pragma unroll
-        for (int i = 0; i < 9; i++) xw[i] = xp[i];
-        __builtin_memcpy(&X, xw, sizeof(X));
-    }
-    uint32_t* lds_map = lds + a.off_map;
-    int8_t* mp = reinterpret_cast<int8_t*>(lds_map) + tid * a.MS;
-    int32_t* inv = reinterpret_cast<int32_t*>(lds + a.off_inv) + tid * a.KP;
-#pragma unroll
-    for (int j = 0; j < IQ; j++)
-        if (4 * j < K) {
-            const int o = min(4 * j, K - 4);
-            inv[o] = (int)q[j].x; inv[o + 1] = (int)q[j].y; inv[o + 2] = (int)q[j].z; inv[o + 3] = (int)q[j].w;
-        }
-    pieces_lds<true, MAPMODE>(buf, a, lds_map, 0, npieces, tid);
-    for (int base = EPB * PB; base < npieces; base += EPB * PB) {
-#pragma unroll
-        for (int j = 0; j < PB; j++) buf[j] = ldg<u32x4>(bmap, 16u * (uint32_t)min(base + (int)tid + EPB * j, npieces - 1));
-        pieces_lds<true, MAPMODE>(buf, a, lds_map, base, npieces, tid);
-    }
+    NgwExtU X;
+    const RolloutLane L = rollout_stage_in<MAPMODE, EXT>(dspec, a, lds, tid, K, npieces, bmap, binv, bloc, bfac, bsel, bstp, buf, U, X);
+    int r = L.r, c = L.c, f = L.f, sel = L.sel, steps = L.steps;
+    const uint32_t rowoff = L.rowoff;
+    const uint32_t t0 = L.t0, t1 = L.t1, t2 = L.t2, t3 = L.t3, t4 = L.t4, t5 = L.t5;
+    uint32_t* const lds_map = L.lds_map;
+    int8_t* const mp = L.mp;
+    int32_t* const inv = L.inv;
     // the cold path's placement sequence: staged once for the whole launch
     if (tid < NGW_MAX_PLACE / 4) lds[a.off_act + tid] = reinterpret_cast<const uint32_t*>(dspec->place_seq)[tid];
     __syncthreads();

@@ -114,6 +114,16 @@ class ShardedVecNovelGridworld:
         """The one-step lookahead table of this rank's shard (VecNovelGridworld.lookahead): rank-local, no collective."""
         return self.local.lookahead(device=device, copy=copy)
 
+    def evaluate_plans(self, plans, device=False, copy=False):
+        """Plan evaluation of this rank's shard (VecNovelGridworld.evaluate_plans): `plans` is the GLOBAL [global_num_envs, P, T] host array,
+        of which this rank evaluates rows [first, first + num_envs); rank-local, no collective.  A device tensor is the shard's own [T, P, n]."""
+        if not hasattr(plans, 'data_ptr'):
+            import numpy as np
+            plans = np.asarray(plans)
+            assert plans.ndim == 3 and plans.shape[0] == self.global_num_envs, "plans cover every env of the group: [global_num_envs, P, T]"
+            plans = plans[self.first:self.first + self.num_envs]
+        return self.local.evaluate_plans(plans, device=device, copy=copy)
+
     def snapshot(self, capacity=None):
         """A device-side snapshot of this rank's shard (VecNovelGridworld.snapshot): rank-local, env indices are the shard's own."""
         return self.local.snapshot(capacity)

@@ -314,6 +314,16 @@ class _NovelGridworldEnv(_EnvBase):
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
         return vec.lookahead(device=device, copy=copy).row(0)
 
+    def evaluate_plans(self, plans, device=False, copy=False):
+        """What each of P candidate action sequences ([P, T] integer ids) would return from the current state, without taking a step: a
+        PlanEval of 'ret' int32 [P], 'length' int32 [P], 'ended' bool [P] and 'info' uint32 [P]; see VecNovelGridworld.evaluate_plans.  An id
+        outside the action list raises the ValueError step() raises."""
+        a = np.asarray(plans)
+        assert a.ndim == 2, "plans are shaped [P, T]"
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        return vec.evaluate_plans(a[None], device=device, copy=copy).row(0)
+
     def get_observation(self):
         assert not self.max_items < len(self.items), "Cannot have more than " + str(self.max_items) + " items"
         return {'map': self.map, 'agent_location': self.agent_location, 'agent_facing_id': self.agent_facing_id,

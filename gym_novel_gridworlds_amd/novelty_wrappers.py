@@ -49,6 +49,9 @@ class NoveltyWrapper(object):
     def lookahead(self, device=False, copy=False):
         return self.env.lookahead(device=device, copy=copy)
 
+    def evaluate_plans(self, plans, device=False, copy=False):
+        return self.env.evaluate_plans(plans, device=device, copy=copy)
+
     def render(self, mode='human', **kwargs):
         return self.env.render(mode, **kwargs)
 

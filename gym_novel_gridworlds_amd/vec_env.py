@@ -52,6 +52,30 @@ class Lookahead(collections.namedtuple('Lookahead', 'reward done result info')):
         return Lookahead(*[x[i] for x in self])
 
 
+class PlanEval(collections.namedtuple('PlanEval', 'ret length ended info')):
+    """What evaluate_plans() returns: ret int32 (sum of the executed steps' rewards), length int32 (steps executed, 1 .. T), ended bool (the
+    plan stopped at an episode end) and info uint32 (the packed word of the last executed step), each [N, P] ([P] on the single-env adapter).
+    A named tuple (it unpacks in that order) whose fields can also be read by name: e['ret'].  numpy arrays or torch tensors."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    @property
+    def goal(self):
+        """The plan ended by reaching the goal (info bit 1; clear for a horizon cut)."""
+        return self.ended & (((self.info >> 1) & 1) != 0)
+
+    @property
+    def died(self):
+        """The plan ended in a FireWall death (message code 14)."""
+        return self.ended & (((self.info >> 8) & 255) == 14)
+
+    def row(self, i):
+        """Env i's rows (the single-env adapter's view)."""
+        return PlanEval(*[x[i] for x in self])
+
+
 class StepInfo(dict):
     """info of a batched step: 'result' bool[N], 'step_cost_code', 'message_code', 'message_arg' - and 'step_cost' f64[N].  Fields
     that are not there yet are made when they are first asked for: 'step_cost' is looked up from the codes (a 65 536-element
@@ -224,7 +248,7 @@ class VecNovelGridworld:
         and leaves the env as it was - the reference, too, asserts before it changes anything.  The state is undefined until the
         next reset(), as after construction."""
         old_h, old_attrs = self._h, dict(self.__dict__)
-        for name in VecNovelGridworld._HOST_ATTRS + ('_host', '_step_args', '_step1_args', '_step1_fn', '_step1_mv', '_state1_mv', '_reset1_args', '_last_state_views', '_lidar_host', '_view_host', '_last_actions', '_packed_block', '_packed_call', '_steps_stale'):
+        for name in VecNovelGridworld._HOST_ATTRS + ('_host', '_step_args', '_step1_args', '_step1_fn', '_step1_mv', '_state1_mv', '_reset1_args', '_last_state_views', '_lidar_host', '_view_host', '_plan_stage', '_plan_host', '_last_actions', '_packed_block', '_packed_call', '_steps_stale'):
             self.__dict__.pop(name, None)
         self._h = C.c_void_p()
         try:
@@ -725,6 +749,69 @@ class VecNovelGridworld:
         _cabi.check(L.ngw_get_lookahead(self._h, _cabi._ptr(h[0], np.int32), _cabi._ptr(h[1], np.uint8), _cabi._ptr(h[2], np.uint32)))
         reward, done, info = (x.copy() for x in h) if copy else h
         return Lookahead(reward, done.view(np.bool_), (info & 1).astype(np.bool_), info)
+
+    # ------------------------------------------------------------------ plan evaluation (include/ngw.h ngw_plan_eval)
+    def evaluate_plans(self, plans, device=False, copy=False):
+        """What P candidate action sequences of T steps would return from the CURRENT state of every env, without committing a step: a
+        PlanEval of 'ret' int32, 'length' int32, 'ended' bool and 'info' uint32, each [N, P].  Plan p of env i is stepped on a private copy
+        by the rules step() applies (every novelty, the autoreset setting and horizon) and stops at the first step that ends the episode -
+        that step counts; nothing is committed (no state byte changes, no reset runs, no prepared episode is consumed, masks and the
+        lookahead table stay current).
+        plans: an integer array [N, P, T], env-major, in host memory - validated here (an id outside the action list raises the ValueError
+        step() raises and nothing launches) and transposed into a device staging buffer the env keeps; or a contiguous torch int32 tensor
+        [T, P, N] on the env's device, used in place and unvalidated (an id outside the list is a no-op step of reward 0 that counts in
+        'length' and raises the sticky NGW_F_INVALID_ACTION, see error_flags()).
+        On the host the results are the env's own arrays, overwritten by the next call (copy=True: fresh arrays).  device=True: zero-copy
+        torch tensors [N, P] over the plan-major device buffers, valid until the next evaluate_plans; 'info' is int32 there (the same bits)."""
+        N = self.num_envs
+        if hasattr(plans, 'data_ptr'):                          # a torch tensor on the device, [T, P, N]
+            import torch
+            assert plans.dtype == torch.int32 and plans.is_cuda and plans.is_contiguous(), "device plans: a contiguous torch int32 tensor on the GPU"
+            assert plans.dim() == 3 and plans.shape[2] == N, "device plans are shaped [T, P, N]"
+            assert plans.device.index == self.device, "device plans live on the env's device"
+            T_, P = int(plans.shape[0]), int(plans.shape[1])
+            self.evaluate_plans_ptr(plans.data_ptr(), N, P, T_)
+        else:
+            import torch
+            a = np.asarray(plans)
+            assert a.dtype.kind in 'iu', "plans are integer action ids"
+            assert a.ndim == 3 and a.shape[0] == N, "host plans are shaped [N, P, T]"
+            P, T_ = int(a.shape[1]), int(a.shape[2])
+            A = len(self.actions_id)
+            bad = (a < 0) | (a >= A)
+            if bad.any():
+                raise ValueError("%d is not in list" % int(a[bad][0]))
+            tpn = np.ascontiguousarray(a.transpose(2, 1, 0), np.int32)
+            stage = self.__dict__.get('_plan_stage')
+            if stage is None or stage.numel() < tpn.size:
+                stage = self._plan_stage = torch.empty(tpn.size, dtype=torch.int32, device='cuda:%d' % self.device)
+            stage[:tpn.size].copy_(torch.from_numpy(tpn).reshape(-1))       # (from pageable memory: complete when it returns)
+            torch.cuda.current_stream(self.device).synchronize()
+            self.evaluate_plans_ptr(stage.data_ptr(), N, P, T_)
+        L = _cabi.lib()
+        if device:
+            import torch
+            p = [C.c_void_p() for _ in range(4)]
+            es, ps = C.c_int64(), C.c_int64()
+            _cabi.check(L.ngw_plan_eval_device_ptrs(self._h, *[C.byref(x) for x in p], C.byref(es), C.byref(ps)))
+            assert es.value == 1, "the device results are plan-major"
+            self.sync()
+            dev = 'cuda:%d' % self.device
+            view = lambda ptr, ts: torch.as_tensor(_DevArray(ptr.value, (P, ps.value), ts), device=dev)[:, :N].t()   # noqa: E731
+            return PlanEval(view(p[0], '<i4'), view(p[1], '<i4'), view(p[2], '|u1').view(torch.bool), view(p[3], '<i4'))
+        h = self.__dict__.get('_plan_host')
+        if h is None or h[0].shape != (N, P):
+            h = self._plan_host = (np.zeros((N, P), np.int32), np.zeros((N, P), np.int32), np.zeros((N, P), np.uint8), np.zeros((N, P), np.uint32))
+        _cabi.check(L.ngw_get_plan_eval(self._h, _cabi._ptr(h[0], np.int32), _cabi._ptr(h[1], np.int32), _cabi._ptr(h[2], np.uint8),
+                                        _cabi._ptr(h[3], np.uint32)))
+        ret, length, ended, info = (x.copy() for x in h) if copy else h
+        return PlanEval(ret, length, ended.view(np.bool_), info)
+
+    def evaluate_plans_ptr(self, plans_ptr, env_stride, n_plans, n_steps):
+        """The launch alone, for callers with their own memory (in the style of rollout_actions): the action of env i, plan p, step t is the
+        int32 at device address plans_ptr + 4 * ((t * n_plans + p) * env_stride + i).  Enqueued on the env's stream; the results are read
+        with ngw_get_plan_eval / ngw_plan_eval_device_ptrs (include/ngw.h)."""
+        _cabi.check(_cabi.lib().ngw_plan_eval(self._h, C.c_void_p(int(plans_ptr)) if plans_ptr else None, int(env_stride), int(n_plans), int(n_steps)))
 
     # ------------------------------------------------------------------ multi-GPU observation stack (dist.py)
     def pack_layout(self):

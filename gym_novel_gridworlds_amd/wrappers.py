@@ -113,6 +113,30 @@ class LimitActions(NoveltyWrapper):
         cols = lambda x, dt: limit_mask_columns(x, self.limited_actions_id, self.actions_id, n, dt)   # noqa: E731
         return Lookahead(cols(t['reward'], np.int32), cols(t['done'], bool), cols(t['result'], bool), cols(t['info'], np.uint32))
 
+    def evaluate_plans(self, plans, device=False, copy=False):
+        """The env's evaluate_plans for plans written in the limited id space ([P, T] integer ids): every id goes through the same two
+        look-ups as step() - as lookahead() maps columns - and an id step() would refuse raises step()'s AssertionError before anything
+        runs."""
+        return self.env.evaluate_plans(limit_plan_ids(plans, self.limited_actions_id, self.actions_id, len(self.limited_actions), self.env_id),
+                                       device=device, copy=copy)
+
+
+def limit_plan_ids(plans, limited_actions_id, actions_id, n, env_id=''):
+    """Plans written in LimitActions' id space -> the env's ids: every id through the two look-ups of step() (limit_column_ids, as the
+    columns of a lookahead table map).  An id step() would refuse - no name holds it, or the env does not know the name, e.g. an action
+    a wrapper below removed - raises step()'s AssertionError for it."""
+    plans = np.asarray(plans)
+    assert plans.dtype.kind in 'iu', "plans are integer action ids"
+    used = [int(i) for i in np.unique(plans)]
+    ids = limit_column_ids(limited_actions_id, actions_id, max(used + [n - 1]) + 1, max(list(actions_id.values()) + [0]) + 1)
+    out = np.zeros(plans.shape, np.int32)
+    for i in used:
+        name = next((candidate for candidate, limited in limited_actions_id.items() if limited == i), None)
+        assert name is not None, _BAD_LIMITED_ID.format(id=i, top=len(limited_actions_id) - 1)
+        assert ids[i] is not None, _NOT_AN_ACTION.format(name=name, env_id=env_id)
+        out[plans == i] = ids[i]
+    return out
+
 
 def limit_column_ids(limited_actions_id, actions_id, n, width):
     """For each limited id i < n, the env's column it steps: the env's id (in `actions_id`) of the FIRST name that holds limited id i in

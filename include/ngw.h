@@ -504,6 +504,39 @@ int ngw_lookahead(ngw_handle* h);
 int ngw_get_lookahead(ngw_handle* h, int32_t* reward, uint8_t* done, uint32_t* info);
 int ngw_lookahead_device_ptrs(ngw_handle* h, void** reward, void** done, void** info, int64_t* env_stride, int64_t* action_stride);
 
+/* Plan evaluation: what P candidate action sequences of T steps would return from the CURRENT state, without committing a step (the inner loop
+ * of random-shooting / CEM planning, beam search, tree-search rollouts, scoring macro-actions).
+ * Input: plans_dev, int32 in device memory; the action of env i, plan p, step t is plans_dev[(t * n_plans + p) * env_stride + i], env_stride >=
+ * n_envs - the [T, N] row form of ngw_rollout_actions with a plan axis in the middle.
+ * Plan p of env i is stepped from env i's current state on a private copy, by exactly the rules ngw_step_device applies: the handle's spec, every
+ * novelty and wrapper predicate, its autoreset setting and horizon.  It STOPS at the first step that ends the episode, i.e. the first step whose
+ * `done` (ngw_get_step_out) would be 1: the goal (including the sticky done of an env that already holds the goal item, autoreset off), a FireWall
+ * death, the horizon under autoreset.  That step counts and its reward is included; later steps of the plan are not executed and add nothing.  No
+ * reset runs.  Per (i, p):
+ *   ret     int32   sum of the executed steps' rewards
+ *   length  int32   number of steps executed, 1 .. n_steps
+ *   ended   uint8   1 if the plan stopped at an episode end
+ *   info    uint32  the NGW_INFO_* word of the last executed step (bit 1: goal-done, clear for a horizon cut; message code 14: FireWall death)
+ * An action id outside [0, n_actions) behaves as in ngw_rollout_actions: that step leaves the private state untouched, contributes reward 0, counts
+ * in `length`, its info word is 0, and the sticky NGW_F_INVALID_ACTION is raised.  With n_steps = 1, column p equals column a of the one-step
+ * lookahead table for plans[0][p][i] = a.
+ * Nothing is committed (the lookahead's list holds here too): every byte of the state, the last step's reward / done / info, the prepared next
+ * episodes, the mask buffer and the lookahead table and whether they are current, the lidar rows, the bit rows, the host mirrors, the rollout
+ * output rows and episode accumulators of ngw_rollout_outputs and the terminal-capture side set are what they were.  Because no reset runs, the call
+ * is allowed while terminal capture is on.  A handle whose maps do not fit LDS (the fused rollouts' limit) refuses it.
+ *   ngw_plan_eval              one kernel launch, enqueued on the handle's stream; does not wait.  Every call evaluates (there is no cached result).
+ *   ngw_get_plan_eval          the results of the last evaluation to host arrays [n_envs][n_plans], env-major; any pointer may be NULL; waits.
+ *   ngw_plan_eval_device_ptrs  the device buffers in place (any pointer may be NULL).  The device layout is PLAN-MAJOR, [n_plans][n_pad]: result
+ *                              (i, p) of each array is element i * env_stride + p * plan_stride (strides in ELEMENTS; env_stride = 1, plan_stride
+ *                              = n_pad), so that one lane per env stores consecutive addresses.  Columns of padding envs are 0.  The buffers (17 B per
+ *                              pair) are allocated on first use, regrown - the pointers change - when a call brings more plans than any before, and
+ *                              freed by ngw_destroy.
+ * NGW_E_INVALID_ARG: NULL handle or plans, n_plans < 1, n_steps < 1, env_stride < n_envs, n_plans * n_pad beyond 32 bits, the two getters before any
+ * evaluation, maps that do not fit LDS. */
+int ngw_plan_eval(ngw_handle* h, const int32_t* plans_dev, int64_t env_stride, int32_t n_plans, int32_t n_steps);
+int ngw_get_plan_eval(ngw_handle* h, int32_t* ret, int32_t* length, uint8_t* ended, uint32_t* info);
+int ngw_plan_eval_device_ptrs(ngw_handle* h, void** ret, void** length, void** ended, void** info, int64_t* env_stride, int64_t* plan_stride);
+
 #ifdef __cplusplus
 }
 #endif
