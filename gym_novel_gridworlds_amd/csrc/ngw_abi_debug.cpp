@@ -83,7 +83,7 @@ int ngw_debug_launch_floor(ngw_handle* h, int32_t n_launches, int graph, double*
     if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));
     NgwLaunch a = h->nostage ? h->ns_proto : h->proto;
-    a.b = h->b; a.mode = 13; a.actions = h->actions_dev;
+    a.b = h->b; a.mode = NGW_MODE_DBG_FLOOR; a.actions = h->actions_dev;
     const size_t lds = h->nostage ? h->ns_lds : h->lds_bytes;
     const unsigned grid = (unsigned)(h->n_pad / NGW_EPB);
     hipEvent_t e0 = nullptr, e1 = nullptr;

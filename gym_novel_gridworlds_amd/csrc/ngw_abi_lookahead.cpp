@@ -42,15 +42,6 @@ bool solo_table(ngw_handle* h, int32_t* reward, uint8_t* done, uint32_t* info) {
     return true;
 }
 
-// [A][n] rows as they arrive from the device -> the caller's env-major [n][A]
-template <typename T>
-void to_env_major(const std::vector<T>& rows, T* out, int64_t n, int A) {
-    for (int a = 0; a < A; a++) {
-        const T* src = rows.data() + (size_t)a * (size_t)n;
-        for (int64_t i = 0; i < n; i++) out[(size_t)i * (size_t)A + (size_t)a] = src[i];
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -66,29 +57,13 @@ int ngw_get_lookahead(ngw_handle* h, int32_t* reward, uint8_t* done, uint32_t* i
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (h->solo_running && solo_table(h, reward, done, info)) return NGW_OK;    // (the one-env loop keeps running: no relaunch per query)
     if (int rc = ngw_lookahead(h)) return rc;
-    const int A = h->spec.n_actions;
-    const size_t n = (size_t)h->n, cells = n * (size_t)A;
-    std::vector<int32_t> r(reward ? cells : 0);
-    std::vector<uint8_t> d(done ? cells : 0);
-    std::vector<uint32_t> w(info ? cells : 0);
-    // row a of the device table is n_pad long: one strided copy per array brings the n live columns of every row across
-    if (reward) HIP_TRY(hipMemcpy2DAsync(r.data(), n * 4, h->look_reward, (size_t)h->n_pad * 4, n * 4, (size_t)A, hipMemcpyDefault, h->stream));
-    if (done) HIP_TRY(hipMemcpy2DAsync(d.data(), n, h->look_done, (size_t)h->n_pad, n, (size_t)A, hipMemcpyDefault, h->stream));
-    if (info) HIP_TRY(hipMemcpy2DAsync(w.data(), n * 4, h->look_info, (size_t)h->n_pad * 4, n * 4, (size_t)A, hipMemcpyDefault, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (reward) to_env_major(r, reward, h->n, A);
-    if (done) to_env_major(d, done, h->n, A);
-    if (info) to_env_major(w, info, h->n, A);
-    return NGW_OK;
+    return fetch_env_major(h, h->spec.n_actions, {{h->look_reward, reward, 4}, {h->look_done, done, 1}, {h->look_info, info, 4}});
 }
 
 int ngw_lookahead_device_ptrs(ngw_handle* h, void** reward, void** done, void** info, int64_t* env_stride, int64_t* action_stride) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->look_info) {
-        if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }   // (the allocation zero-fills on the handle's stream)
-        if (int rc = alloc_table(h)) return rc;
-    }
+    if (int rc = enter_to_allocate(h, h->look_info != nullptr)) return rc;
+    if (int rc = alloc_table(h)) return rc;
     if (reward) *reward = h->look_reward;
     if (done) *done = h->look_done;
     if (info) *info = h->look_info;

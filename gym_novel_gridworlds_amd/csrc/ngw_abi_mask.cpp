@@ -86,11 +86,8 @@ int ngw_get_action_mask(ngw_handle* h, uint64_t* out_host) {
 
 int ngw_action_mask_device_ptr(ngw_handle* h, void** out) {
     if (!h || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    HIP_TRY(hipSetDevice(h->device));
-    if (!h->act_mask) {
-        if (h->solo_running) { if (int rc = solo_stop(h)) return rc; }   // (the allocation zero-fills on the handle's stream)
-        if (int rc = alloc_act_mask(h)) return rc;
-    }
+    if (int rc = enter_to_allocate(h, h->act_mask != nullptr)) return rc;
+    if (int rc = alloc_act_mask(h)) return rc;
     *out = h->act_mask;
     return NGW_OK;
 }

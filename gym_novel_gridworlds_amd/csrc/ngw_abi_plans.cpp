@@ -28,15 +28,6 @@ int alloc_results(ngw_handle* h, int32_t n_plans) {
     return NGW_OK;
 }
 
-// [P][n] rows as they arrive from the device -> the caller's env-major [n][P]
-template <typename T>
-void to_env_major(const std::vector<T>& rows, T* out, int64_t n, int P) {
-    for (int p = 0; p < P; p++) {
-        const T* src = rows.data() + (size_t)p * (size_t)n;
-        for (int64_t i = 0; i < n; i++) out[(size_t)i * (size_t)P + (size_t)p] = src[i];
-    }
-}
-
 }  // namespace
 
 extern "C" {
@@ -73,22 +64,7 @@ int ngw_get_plan_eval(ngw_handle* h, int32_t* ret, int32_t* length, uint8_t* end
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (!h->plan_n) return fail(NGW_E_INVALID_ARG, "ngw_get_plan_eval before ngw_plan_eval");
     if (int rc = enter(h)) return rc;
-    const int P = h->plan_n;
-    const size_t n = (size_t)h->n, cells = n * (size_t)P;
-    std::vector<int32_t> r(ret ? cells : 0), l(length ? cells : 0);
-    std::vector<uint8_t> d(ended ? cells : 0);
-    std::vector<uint32_t> w(info ? cells : 0);
-    // row p of a device array is n_pad long: one strided copy per array brings the n live columns of every row across
-    if (ret) HIP_TRY(hipMemcpy2DAsync(r.data(), n * 4, h->plan_ret, (size_t)h->n_pad * 4, n * 4, (size_t)P, hipMemcpyDefault, h->stream));
-    if (length) HIP_TRY(hipMemcpy2DAsync(l.data(), n * 4, h->plan_len, (size_t)h->n_pad * 4, n * 4, (size_t)P, hipMemcpyDefault, h->stream));
-    if (ended) HIP_TRY(hipMemcpy2DAsync(d.data(), n, h->plan_ended, (size_t)h->n_pad, n, (size_t)P, hipMemcpyDefault, h->stream));
-    if (info) HIP_TRY(hipMemcpy2DAsync(w.data(), n * 4, h->plan_info, (size_t)h->n_pad * 4, n * 4, (size_t)P, hipMemcpyDefault, h->stream));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (ret) to_env_major(r, ret, h->n, P);
-    if (length) to_env_major(l, length, h->n, P);
-    if (ended) to_env_major(d, ended, h->n, P);
-    if (info) to_env_major(w, info, h->n, P);
-    return NGW_OK;
+    return fetch_env_major(h, h->plan_n, {{h->plan_ret, ret, 4}, {h->plan_len, length, 4}, {h->plan_ended, ended, 1}, {h->plan_info, info, 4}});
 }
 
 int ngw_plan_eval_device_ptrs(ngw_handle* h, void** ret, void** length, void** ended, void** info, int64_t* env_stride, int64_t* plan_stride) {

@@ -10,7 +10,10 @@
 enum { NGW_MODE_STEP = 0, NGW_MODE_RESET = 1, NGW_MODE_ROLLOUT = 2,
        NGW_MODE_REFILL = 3 /* prepare next episodes in the shadow buffers: a.b = shadow set, a.actions = the main episode[] */,
        NGW_MODE_ROLLOUT_ACT = 4 /* fused rollout with the caller's actions: step t of env e takes a.actions[t * a.t0 + e] */,
-       NGW_MODE_DBG_NOP = 8 /* exit at once: launch floor */, NGW_MODE_DBG_COPY = 9 /* stage in/out, no step logic */ };
+       NGW_MODE_DBG_NOP = 8 /* exit at once: launch floor */, NGW_MODE_DBG_COPY = 9 /* stage in/out, no step logic */,
+       /* diagnostics: an EMPTY kernel over the same lanes in workgroups of 256 / 1024 / 128 threads (the last with twice the LDS request) ... */
+       NGW_MODE_DBG_WG256 = 10, NGW_MODE_DBG_WG1024 = 11, NGW_MODE_DBG_WG128_LDS2 = 12,
+       NGW_MODE_DBG_FLOOR = 13 /* ... and in the step kernel's own launch shape (ngw_debug_launch_floor) */ };
 /* how a wave's map chunk is laid out in LDS: same image as HBM / odd-dword-padded rows / byte-granular (odd S) */
 enum { NGW_MAP_STRAIGHT = 0, NGW_MAP_DWORD = 1, NGW_MAP_BYTE = 2 };
 

@@ -28,6 +28,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/ngw.h"
@@ -221,6 +222,32 @@ int dev_alloc(ngw_handle* h, T** p, size_t count) {
 }
 void dev_free(ngw_handle* h, void* p);
 
+// Device tables of `rows` rows, n_pad elements apart (action-major, plan-major), to the caller's env-major out[n][rows] arrays: one strided copy
+// per table brings the n live columns of every row across, ONE synchronisation waits for all of them, then the rows are transposed.  A table
+// whose `out` is NULL is left alone.
+struct RowTable { const void* dev; void* out; size_t elem; };   // elem: bytes per element, 1 or 4
+inline int fetch_env_major(ngw_handle* h, int rows, std::initializer_list<RowTable> tables) {
+    const size_t n = (size_t)h->n;
+    std::vector<std::vector<uint8_t>> stage;
+    for (const RowTable& t : tables) {
+        stage.emplace_back(t.out ? n * (size_t)rows * t.elem : 0);
+        if (t.out) HIP_TRY(hipMemcpy2DAsync(stage.back().data(), n * t.elem, t.dev, (size_t)h->n_pad * t.elem, n * t.elem, (size_t)rows, hipMemcpyDefault, h->stream));
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    auto transpose = [&](auto* out, const auto* src) {
+        for (int r = 0; r < rows; r++)
+            for (size_t i = 0; i < n; i++) out[i * (size_t)rows + (size_t)r] = src[(size_t)r * n + i];
+    };
+    size_t k = 0;
+    for (const RowTable& t : tables) {
+        const uint8_t* src = stage[k++].data();
+        if (!t.out) continue;
+        if (t.elem == 4) transpose(static_cast<uint32_t*>(t.out), reinterpret_cast<const uint32_t*>(src));
+        else transpose(static_cast<uint8_t*>(t.out), src);
+    }
+    return NGW_OK;
+}
+
 // ngw_abi_create.cpp
 void lidar_format(const ngw_handle* h, NgwLaunch& p);
 int layout_lds(ngw_handle* h);
@@ -270,6 +297,14 @@ int check_actions(const int32_t* actions, size_t n, int A);   // NGW_E_INVALID_A
 
 // Which kernel an NGW_MODE_STEP launch runs: the in-place step kernel (no map staging) unless the fused lidar needs the maps in LDS for its march.
 inline bool step_in_place(const ngw_handle* h) { return h->nostage && (!h->lidar_fused || h->boards_on); }
+
+// The *_device_ptr(s) getters of buffers that are allocated on first use (action masks, the lookahead table): exempt from rule 1 - they end the
+// one-env loop only if they have to allocate (the allocation zero-fills on the handle's stream); once the buffer exists they hand it out while the loop runs.
+inline int enter_to_allocate(ngw_handle* h, bool allocated) {
+    HIP_TRY(hipSetDevice(h->device));
+    if (!allocated && h->solo_running) return solo_stop(h);
+    return NGW_OK;
+}
 
 inline void cpu_pause() {
 #if defined(__x86_64__) || defined(__i386__)

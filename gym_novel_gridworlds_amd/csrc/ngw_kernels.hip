@@ -24,6 +24,9 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <atomic>
+#include <type_traits>
+
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
@@ -73,6 +76,7 @@ constexpr int EPB = NGW_EPB;   // envs per block = wavefront width
 #define STAMP_SUBV(a, i)
 #endif
 
+#include "ngw_launch.inc"
 #include "ngw_newepisode.inc"
 
 // ---------------------------------------------------------------- map staging HBM <-> LDS (coalesced 16-B pieces)
@@ -542,7 +546,123 @@ __global__ __launch_bounds__(256) void ngw_agent_view_kernel(const int8_t* __res
 }
 #endif  // NGW_HAS(5)
 
+#if NGW_HAS(0)
+__global__ void ngw_nop_kernel(const NgwDevSpec* dspec, const NgwLaunch a) {}
+
+// the general new-episode kernel: explicit resets (with or without the fused lidar observation), refills, diagnostics
+template <int MAPMODE>
+hipError_t launch_general(const NgwDevSpec* dspec, const NgwLaunch* a, bool lidar, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+    const dim3 g(grid), b(NGW_EPB);
+    switch (a->mode) {
+    case NGW_MODE_RESET:
+        return with_flag(lidar, [&](auto L) { return launch_kernel<ngw_kernel<MAPMODE, NGW_MODE_RESET, decltype(L)::value>>(g, b, lds_bytes, stream, dspec, *a); });
+    case NGW_MODE_REFILL: return launch_kernel<ngw_kernel<MAPMODE, NGW_MODE_REFILL, false>>(g, b, lds_bytes, stream, dspec, *a);
+    case NGW_MODE_DBG_COPY: return launch_kernel<ngw_kernel<MAPMODE, NGW_MODE_DBG_COPY, false>>(g, b, lds_bytes, stream, dspec, *a);
+    case NGW_MODE_DBG_NOP: return launch_kernel<ngw_kernel<MAPMODE, NGW_MODE_DBG_NOP, false>>(g, b, lds_bytes, stream, dspec, *a);
+    default: return hipErrorInvalidValue;
+    }
+}
+#endif  // NGW_HAS(0)
+
+// ONE batched step(): ngw_step_lean.  The staged kernels of one map addressing mode (six each: plain and fused lidar, the plain ones also with
+// fused action masks, all with and without the wrapper predicates) are a unit of their own.
+template <int MM>
+hipError_t step_staged(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+    const bool lidar = (feat & NGW_FEAT_LIDAR) != 0, ext = (feat & NGW_FEAT_EXT) != 0;
+    if ((feat & NGW_FEAT_MASK) && !lidar)   // fused action masks
+        return with_flag(ext, [&](auto E) { return launch_lean<MM, true, decltype(E)::value, false, 0, false, true>(dspec, a, grid, lds_bytes, stream); });
+    return with_flag(lidar, [&](auto L) {
+        return with_flag(ext, [&](auto E) { return launch_lean<MM, true, decltype(E)::value, decltype(L)::value>(dspec, a, grid, lds_bytes, stream); });
+    });
+}
+
+// in-place step + the LidarInFront observation from the occupancy bit rows (ngw_boards.inc): NR = 12 / 20 / 32 register rows; HW: with the host write-through
+template <bool HW>
+hipError_t step_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+    if (!a->l_boards) return hipErrorInvalidValue;
+    return with_board_rows(a->BS, [&](auto R) {
+        return with_flag((feat & NGW_FEAT_EXT) != 0, [&](auto E) {
+            return launch_lean<NGW_MAP_STRAIGHT, false, decltype(E)::value, true, decltype(R)::value, HW>(dspec, a, grid, lds_bytes, stream);
+        });
+    });
+}
+
+// fused rollout: ngw_rollout_lean, one part per map addressing mode (eight kernels each: the heaviest to compile)
+template <int MM>
+hipError_t rollout(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+    return with_flag(a->mode == NGW_MODE_ROLLOUT_ACT, [&](auto SUP) {
+        return with_flag((feat & NGW_FEAT_LIDAR) != 0, [&](auto L) {
+            return with_flag((feat & NGW_FEAT_EXT) != 0, [&](auto E) {
+                return launch_kernel<ngw_rollout_lean<MM, decltype(SUP)::value, decltype(E)::value, decltype(L)::value>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, dspec, *a);
+            });
+        });
+    });
+}
+
 }  // namespace
+
+// The parts call each other through these (feat: the NGW_FEAT_* bits, ngw_device.h).
+#define NGW_PART_FN(NAME) extern "C" hipError_t NAME(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream)
+extern "C" hipError_t ngw_part_step(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
+NGW_PART_FN(ngw_part_step_straight);
+NGW_PART_FN(ngw_part_step_dword);
+NGW_PART_FN(ngw_part_step_byte);
+NGW_PART_FN(ngw_part_step_boards);
+NGW_PART_FN(ngw_part_step_wire);
+NGW_PART_FN(ngw_part_step_wire_boards);
+NGW_PART_FN(ngw_part_step_mask_ns);
+NGW_PART_FN(ngw_part_rollout_straight);
+NGW_PART_FN(ngw_part_rollout_dword);
+NGW_PART_FN(ngw_part_rollout_byte);
+
+#if NGW_HAS(0)
+extern "C" hipError_t ngw_launch(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat, unsigned grid,
+                                 size_t lds_bytes, hipStream_t stream) {
+    if (a->mode >= NGW_MODE_DBG_WG256 && a->mode <= NGW_MODE_DBG_WG128_LDS2) {   // diagnostics: empty kernels with other workgroup shapes over the same lanes
+        const unsigned tpb = a->mode == NGW_MODE_DBG_WG256 ? 256 : (a->mode == NGW_MODE_DBG_WG1024 ? 1024 : 128);
+        return launch_kernel<ngw_nop_kernel>(dim3(grid * NGW_EPB / tpb), dim3(tpb), a->mode == NGW_MODE_DBG_WG128_LDS2 ? lds_bytes * 2 : 0, stream, dspec, *a);
+    }
+    if (a->mode == NGW_MODE_DBG_FLOOR)          // the launch floor: an empty kernel in the STEP kernel's launch shape (ngw_debug_launch_floor)
+        return launch_kernel<ngw_nop_kernel>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, dspec, *a);
+    if (a->mode == NGW_MODE_STEP) return ngw_part_step(dspec, a, map_mode, feat, grid, lds_bytes, stream);
+    if (a->mode == NGW_MODE_ROLLOUT || a->mode == NGW_MODE_ROLLOUT_ACT) {
+        switch (map_mode) {
+        case NGW_MAP_STRAIGHT: return ngw_part_rollout_straight(dspec, a, feat, grid, lds_bytes, stream);
+        case NGW_MAP_DWORD: return ngw_part_rollout_dword(dspec, a, feat, grid, lds_bytes, stream);
+        default: return ngw_part_rollout_byte(dspec, a, feat, grid, lds_bytes, stream);
+        }
+    }
+    return with_map_mode(map_mode, [&](auto MM) { return launch_general<decltype(MM)::value>(dspec, a, (feat & NGW_FEAT_LIDAR) != 0, grid, lds_bytes, stream); });
+}
+#endif  // NGW_HAS(0)
+
+#if NGW_HAS(1)
+NGW_PART_FN(ngw_part_step_straight) { return step_staged<NGW_MAP_STRAIGHT>(dspec, a, feat, grid, lds_bytes, stream); }
+extern "C" hipError_t ngw_part_step(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat, unsigned grid, size_t lds_bytes,
+                                    hipStream_t stream) {
+    if (feat & NGW_FEAT_NOSTAGE) {   // no-stage: with the lidar observation, the one on the occupancy bit rows
+        if (feat & NGW_FEAT_WIRE) return ngw_part_step_wire(dspec, a, feat, grid, lds_bytes, stream);   // ... with the host write-through
+        if (feat & NGW_FEAT_LIDAR) return ngw_part_step_boards(dspec, a, feat, grid, lds_bytes, stream);
+        if (feat & NGW_FEAT_MASK) return ngw_part_step_mask_ns(dspec, a, feat, grid, lds_bytes, stream);
+        return with_flag((feat & NGW_FEAT_EXT) != 0, [&](auto E) { return launch_lean<NGW_MAP_STRAIGHT, false, decltype(E)::value, false>(dspec, a, grid, lds_bytes, stream); });
+    }
+    switch (map_mode) {
+    case NGW_MAP_STRAIGHT: return ngw_part_step_straight(dspec, a, feat, grid, lds_bytes, stream);
+    case NGW_MAP_DWORD: return ngw_part_step_dword(dspec, a, feat, grid, lds_bytes, stream);
+    default: return ngw_part_step_byte(dspec, a, feat, grid, lds_bytes, stream);
+    }
+}
+#endif  // NGW_HAS(1)
+
+#if NGW_HAS(2)
+NGW_PART_FN(ngw_part_rollout_straight) { return rollout<NGW_MAP_STRAIGHT>(dspec, a, feat, grid, lds_bytes, stream); }
+#endif
+#if NGW_HAS(3)
+NGW_PART_FN(ngw_part_rollout_dword) { return rollout<NGW_MAP_DWORD>(dspec, a, feat, grid, lds_bytes, stream); }
+#endif
+#if NGW_HAS(4)
+NGW_PART_FN(ngw_part_rollout_byte) { return rollout<NGW_MAP_BYTE>(dspec, a, feat, grid, lds_bytes, stream); }
+#endif
 
 #if NGW_HAS(5)
 extern "C" hipError_t ngw_pack_launch(const NgwPack* p, hipStream_t stream) {
@@ -552,13 +672,11 @@ extern "C" hipError_t ngw_pack_launch(const NgwPack* p, hipStream_t stream) {
     uint64_t blocks = (most / 16u + 255u) / 256u;                          // one 16-byte piece per thread, up to 2048 blocks per region
     if (blocks < 1) blocks = 1;
     if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(ngw_pack_kernel, dim3((unsigned)blocks, (unsigned)p->n_regions), dim3(256), 0, stream, *p);
-    return hipGetLastError();
+    return launch_kernel<ngw_pack_kernel>(dim3((unsigned)blocks, (unsigned)p->n_regions), dim3(256), 0, stream, *p);
 }
 
 extern "C" hipError_t ngw_wire_launch(const NgwWire* p, hipStream_t stream) {
-    hipLaunchKernelGGL(ngw_wire_kernel, dim3((unsigned)((p->n + 255) / 256)), dim3(256), 0, stream, *p);
-    return hipGetLastError();
+    return launch_kernel<ngw_wire_kernel>(dim3((unsigned)((p->n + 255) / 256)), dim3(256), 0, stream, *p);
 }
 
 extern "C" hipError_t ngw_diff_launch(const NgwDiff* p, hipStream_t stream) {
@@ -568,8 +686,7 @@ extern "C" hipError_t ngw_diff_launch(const NgwDiff* p, hipStream_t stream) {
     uint64_t blocks = (most / 16u + 255u) / 256u;
     if (blocks < 1) blocks = 1;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(ngw_diff_kernel, dim3((unsigned)blocks, (unsigned)p->n_regions), dim3(256), 0, stream, *p);
-    return hipGetLastError();
+    return launch_kernel<ngw_diff_kernel>(dim3((unsigned)blocks, (unsigned)p->n_regions), dim3(256), 0, stream, *p);
 }
 
 extern "C" hipError_t ngw_diff_wire_launch(const NgwDiff* p, const NgwWire* w, hipStream_t stream) {
@@ -578,270 +695,83 @@ extern "C" hipError_t ngw_diff_wire_launch(const NgwDiff* p, const NgwWire* w, h
     uint64_t blocks = (most / 16u + 255u) / 256u;
     if (blocks < 1) blocks = 1;
     if (blocks > 4096) blocks = 4096;
-    hipLaunchKernelGGL(ngw_diff_wire_kernel, dim3((unsigned)blocks, (unsigned)p->n_regions + 1u), dim3(256), 0, stream, *p, *w);
-    return hipGetLastError();
+    return launch_kernel<ngw_diff_wire_kernel>(dim3((unsigned)blocks, (unsigned)p->n_regions + 1u), dim3(256), 0, stream, *p, *w);
 }
 
 extern "C" hipError_t ngw_agent_view_launch(const int8_t* map, const int32_t* loc, uint32_t* out, uint32_t n_dwords, int S, int V,
                                             hipStream_t stream) {
     const uint32_t W = 2u * (uint32_t)V + 1u;
     const uint32_t magicW = (uint32_t)((0x100000000ull + W - 1) / W);     // exact for operands < W * W
-    hipLaunchKernelGGL(ngw_agent_view_kernel, dim3((n_dwords + 255u) / 256u), dim3(256), 0, stream, map, loc, out, n_dwords, S, V,
-                       magicW);
-    return hipGetLastError();
+    return launch_kernel<ngw_agent_view_kernel>(dim3((n_dwords + 255u) / 256u), dim3(256), 0, stream, map, loc, out, n_dwords, S, V, magicW);
 }
 
 extern "C" hipError_t ngw_lidar_launch(const NgwLaunch* a, int map_mode, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    const void* fn = map_mode == NGW_MAP_STRAIGHT ? reinterpret_cast<const void*>(ngw_lidar_kernel<NGW_MAP_STRAIGHT>)
-                     : map_mode == NGW_MAP_DWORD  ? reinterpret_cast<const void*>(ngw_lidar_kernel<NGW_MAP_DWORD>)
-                                                  : reinterpret_cast<const void*>(ngw_lidar_kernel<NGW_MAP_BYTE>);
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    switch (map_mode) {
-    case NGW_MAP_STRAIGHT: hipLaunchKernelGGL(ngw_lidar_kernel<NGW_MAP_STRAIGHT>, dim3(grid), dim3(NGW_EPB), lds_bytes, stream, *a); break;
-    case NGW_MAP_DWORD: hipLaunchKernelGGL(ngw_lidar_kernel<NGW_MAP_DWORD>, dim3(grid), dim3(NGW_EPB), lds_bytes, stream, *a); break;
-    default: hipLaunchKernelGGL(ngw_lidar_kernel<NGW_MAP_BYTE>, dim3(grid), dim3(NGW_EPB), lds_bytes, stream, *a);
-    }
-    return hipGetLastError();
-}
-#endif  // NGW_HAS(5)
-
-namespace {
-
-#if NGW_HAS(0)
-template <int MAPMODE, int MODE, bool LIDAR>
-hipError_t launch_one(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    // CDNA4 has 160 KiB of LDS per CU; anything above the 64 KiB default needs an explicit opt-in per device.
-    static size_t lds_opt_in[64] = {0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (lds_bytes > 64 * 1024 && dev < 64 && lds_bytes > lds_opt_in[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ngw_kernel<MAPMODE, MODE, LIDAR>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        lds_opt_in[dev] = lds_bytes;
-    }
-    hipLaunchKernelGGL((ngw_kernel<MAPMODE, MODE, LIDAR>), dim3(grid), dim3(NGW_EPB), lds_bytes, stream, dspec, *a);
-    return hipGetLastError();
+    return with_map_mode(map_mode, [&](auto MM) { return launch_kernel<ngw_lidar_kernel<decltype(MM)::value>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, *a); });
 }
 
-// the general new-episode kernel: explicit resets (with or without the fused lidar observation), refills, diagnostics
-template <int MAPMODE>
-static hipError_t launch_general(const NgwDevSpec* dspec, const NgwLaunch* a, bool lidar, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    switch (a->mode) {
-    case NGW_MODE_RESET:
-        return lidar ? launch_one<MAPMODE, NGW_MODE_RESET, true>(dspec, a, grid, lds_bytes, stream)
-                     : launch_one<MAPMODE, NGW_MODE_RESET, false>(dspec, a, grid, lds_bytes, stream);
-    case NGW_MODE_REFILL: return launch_one<MAPMODE, NGW_MODE_REFILL, false>(dspec, a, grid, lds_bytes, stream);
-    case NGW_MODE_DBG_COPY: return launch_one<MAPMODE, NGW_MODE_DBG_COPY, false>(dspec, a, grid, lds_bytes, stream);
-    case NGW_MODE_DBG_NOP: return launch_one<MAPMODE, NGW_MODE_DBG_NOP, false>(dspec, a, grid, lds_bytes, stream);
+extern "C" hipError_t ngw_solo_launch(const NgwDevSpec* dspec, const NgwSolo* p, int ext, size_t lds_bytes, hipStream_t stream) {
+    return with_flag(ext != 0, [&](auto E) { return launch_kernel<ngw_solo_kernel<decltype(E)::value>>(dim3(1), dim3(NGW_EPB), lds_bytes, stream, dspec, *p); });
+}
+
+// the dedicated new-episode kernel: nw = mask words in registers (2 / 8, 0 = LDS), subset = one subset pass
+extern "C" hipError_t ngw_reset_fast_launch(const NgwDevSpec* dspec, const NgwResetFast* a, int nw, int subset, unsigned grid, size_t lds_bytes,
+                                            hipStream_t stream) {
+    auto go = [&](auto NW) {
+        return with_flag(subset != 0, [&](auto SUB) {
+            return launch_kernel<ngw_reset_fast<decltype(NW)::value, decltype(SUB)::value>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, dspec, *a);
+        });
+    };
+    switch (nw) {
+    case 0: return go(std::integral_constant<int, 0>{});
+    case 2: return go(std::integral_constant<int, 2>{});
+    case 8: return go(std::integral_constant<int, 8>{});
     default: return hipErrorInvalidValue;
     }
 }
-
-__global__ void ngw_nop_kernel(const NgwDevSpec* dspec, const NgwLaunch a) {}
-#endif  // NGW_HAS(0)
-
-}  // namespace
-
-#if NGW_HAS(5)
-extern "C" hipError_t ngw_solo_launch(const NgwDevSpec* dspec, const NgwSolo* p, int ext, size_t lds_bytes, hipStream_t stream) {
-    const void* fn = ext ? reinterpret_cast<const void*>(ngw_solo_kernel<true>) : reinterpret_cast<const void*>(ngw_solo_kernel<false>);
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    void* args[] = {const_cast<NgwDevSpec**>(&dspec), const_cast<NgwSolo*>(p)};
-    return hipLaunchKernel(fn, dim3(1), dim3(NGW_EPB), args, lds_bytes, stream);
-}
-extern "C" hipError_t ngw_reset_fast_launch(const NgwDevSpec* dspec, const NgwResetFast* a, int nw, int subset, unsigned grid, size_t lds_bytes,
-                                            hipStream_t stream) {
-    const void* fn = nullptr;
-#define NGW_RF(NWV, SV) if (nw == NWV && (subset != 0) == SV) fn = reinterpret_cast<const void*>(ngw_reset_fast<NWV, SV>)
-    NGW_RF(2, false); NGW_RF(2, true); NGW_RF(8, false); NGW_RF(8, true); NGW_RF(0, false); NGW_RF(0, true);
-#undef NGW_RF
-    if (!fn) return hipErrorInvalidValue;
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    void* args[] = {const_cast<NgwDevSpec**>(&dspec), const_cast<NgwResetFast*>(a)};
-    return hipLaunchKernel(fn, dim3(grid), dim3(NGW_EPB), args, lds_bytes, stream);
-}
 #endif  // NGW_HAS(5)
 
-// feat: the NGW_FEAT_* bits (ngw_device.h)
-extern "C" hipError_t ngw_part_step(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat, unsigned grid, size_t lds_bytes,
-                                    hipStream_t stream);
-extern "C" hipError_t ngw_part_rollout_straight(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t ngw_part_rollout_dword(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t ngw_part_rollout_byte(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
+#if NGW_HAS(6)
+NGW_PART_FN(ngw_part_step_dword) { return step_staged<NGW_MAP_DWORD>(dspec, a, feat, grid, lds_bytes, stream); }
+#endif
+#if NGW_HAS(7)
+NGW_PART_FN(ngw_part_step_byte) { return step_staged<NGW_MAP_BYTE>(dspec, a, feat, grid, lds_bytes, stream); }
+#endif
 
-// ONE batched step(): ngw_step_lean.  The staged kernels of one map addressing mode (four each) are a unit of their own.
-#define NGW_STEP_PART(NAME, MM)                                                                                                         \
-    extern "C" hipError_t NAME(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) { \
-        const bool lidar = (feat & NGW_FEAT_LIDAR) != 0, ext = (feat & NGW_FEAT_EXT) != 0;                                               \
-        if ((feat & NGW_FEAT_MASK) && !lidar)   /* fused action masks */                                                                 \
-            return ext ? launch_lean<MM, true, true, false, 0, false, true>(dspec, a, grid, lds_bytes, stream)                           \
-                       : launch_lean<MM, true, false, false, 0, false, true>(dspec, a, grid, lds_bytes, stream);                         \
-        return lidar ? (ext ? launch_lean<MM, true, true, true>(dspec, a, grid, lds_bytes, stream)                                      \
-                            : launch_lean<MM, true, false, true>(dspec, a, grid, lds_bytes, stream))                                    \
-                     : (ext ? launch_lean<MM, true, true, false>(dspec, a, grid, lds_bytes, stream)                                     \
-                            : launch_lean<MM, true, false, false>(dspec, a, grid, lds_bytes, stream));                                  \
-    }
-extern "C" hipError_t ngw_part_step_straight(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t ngw_part_step_dword(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t ngw_part_step_byte(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t ngw_part_step_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t ngw_part_step_wire(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t ngw_part_step_wire_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t ngw_part_step_mask_ns(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream);
+#if NGW_HAS(8)
+NGW_PART_FN(ngw_part_step_boards) { return step_boards<false>(dspec, a, feat, grid, lds_bytes, stream); }
+// bit rows of `rows` (a multiple of 64) maps at `map` -> `brd`; a = the launch's own LDS layout (maps at off_map, word tile at off_ltile, magicK = ceil(2^32 / BS))
+extern "C" hipError_t ngw_boards_launch(const NgwLaunch* a, int map_mode, const int8_t* map, uint32_t* brd, int64_t rows, size_t lds_bytes, hipStream_t stream) {
+    return with_map_mode(map_mode, [&](auto MM) {
+        return launch_kernel<ngw_boards_kernel<decltype(MM)::value>>(dim3((unsigned)(rows / NGW_EPB)), dim3(NGW_EPB), lds_bytes, stream, *a, map, brd);
+    });
+}
+extern "C" hipError_t ngw_lidar_boards_launch(const NgwLaunch* a, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+    return with_board_rows(a->BS, [&](auto R) { return launch_kernel<ngw_lidar_boards_kernel<decltype(R)::value>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, *a); });
+}
+#endif  // NGW_HAS(8)
+
 #if NGW_HAS(9)
 // in-place step with the fused action masks
-extern "C" hipError_t ngw_part_step_mask_ns(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    return (feat & NGW_FEAT_EXT) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false, 0, false, true>(dspec, a, grid, lds_bytes, stream)
-                      : launch_lean<NGW_MAP_STRAIGHT, false, false, false, 0, false, true>(dspec, a, grid, lds_bytes, stream);
+NGW_PART_FN(ngw_part_step_mask_ns) {
+    return with_flag((feat & NGW_FEAT_EXT) != 0, [&](auto E) { return launch_lean<NGW_MAP_STRAIGHT, false, decltype(E)::value, false, 0, false, true>(dspec, a, grid, lds_bytes, stream); });
 }
 // in-place step with the host write-through (NgwWT: ngw_step_host_packed's steady state)
-extern "C" hipError_t ngw_part_step_wire(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+NGW_PART_FN(ngw_part_step_wire) {
     if (feat & NGW_FEAT_LIDAR) return ngw_part_step_wire_boards(dspec, a, feat, grid, lds_bytes, stream);
-    return (feat & NGW_FEAT_EXT) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false, 0, true>(dspec, a, grid, lds_bytes, stream)
-                      : launch_lean<NGW_MAP_STRAIGHT, false, false, false, 0, true>(dspec, a, grid, lds_bytes, stream);
+    return with_flag((feat & NGW_FEAT_EXT) != 0, [&](auto E) { return launch_lean<NGW_MAP_STRAIGHT, false, decltype(E)::value, false, 0, true>(dspec, a, grid, lds_bytes, stream); });
 }
-#endif  // NGW_HAS(9)
-#if NGW_HAS(9)
 // the action masks of the state in HBM (ngw_mask.inc): [n_pad] uint64 words at `out`
 extern "C" hipError_t ngw_mask_launch(const NgwDevSpec* dspec, const NgwBufs* b, int64_t n, int S, int K, int ext, uint64_t* out, unsigned grid, hipStream_t stream) {
     if (n <= 0 || n > 0xFFFFFFFFll || S < 3 || S > NGW_MAX_MAP_SIZE || K < 1 || K > NGW_MAX_ITEMS) return hipErrorInvalidValue;
-    if (ext) hipLaunchKernelGGL(ngw_mask_kernel<true>, dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, out);
-    else hipLaunchKernelGGL(ngw_mask_kernel<false>, dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, out);
-    return hipGetLastError();
+    return with_flag(ext != 0, [&](auto E) { return launch_kernel<ngw_mask_kernel<decltype(E)::value>>(dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, out); });
 }
 #endif  // NGW_HAS(9)
+
 #if NGW_HAS(10)
-extern "C" hipError_t ngw_part_step_wire_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    const bool ext = (feat & NGW_FEAT_EXT) != 0;
-    if (!a->l_boards || a->BS < 4 || a->BS > 32) return hipErrorInvalidValue;
-    if (a->BS <= 12) return ext ? launch_lean<NGW_MAP_STRAIGHT, false, true, true, 12, true>(dspec, a, grid, lds_bytes, stream)
-                                : launch_lean<NGW_MAP_STRAIGHT, false, false, true, 12, true>(dspec, a, grid, lds_bytes, stream);
-    if (a->BS <= 20) return ext ? launch_lean<NGW_MAP_STRAIGHT, false, true, true, 20, true>(dspec, a, grid, lds_bytes, stream)
-                                : launch_lean<NGW_MAP_STRAIGHT, false, false, true, 20, true>(dspec, a, grid, lds_bytes, stream);
-    return ext ? launch_lean<NGW_MAP_STRAIGHT, false, true, true, 32, true>(dspec, a, grid, lds_bytes, stream)
-               : launch_lean<NGW_MAP_STRAIGHT, false, false, true, 32, true>(dspec, a, grid, lds_bytes, stream);
-}
-#endif  // NGW_HAS(10)
-#if NGW_HAS(8)
-// in-place step + the LidarInFront observation from the occupancy bit rows (ngw_boards.inc): NR = 12 / 20 / 32 register rows
-extern "C" hipError_t ngw_part_step_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    const bool ext = (feat & NGW_FEAT_EXT) != 0;
-    if (!a->l_boards || a->BS < 4 || a->BS > 32) return hipErrorInvalidValue;
-    if (a->BS <= 12) return ext ? launch_lean<NGW_MAP_STRAIGHT, false, true, true, 12>(dspec, a, grid, lds_bytes, stream)
-                                : launch_lean<NGW_MAP_STRAIGHT, false, false, true, 12>(dspec, a, grid, lds_bytes, stream);
-    if (a->BS <= 20) return ext ? launch_lean<NGW_MAP_STRAIGHT, false, true, true, 20>(dspec, a, grid, lds_bytes, stream)
-                                : launch_lean<NGW_MAP_STRAIGHT, false, false, true, 20>(dspec, a, grid, lds_bytes, stream);
-    return ext ? launch_lean<NGW_MAP_STRAIGHT, false, true, true, 32>(dspec, a, grid, lds_bytes, stream)
-               : launch_lean<NGW_MAP_STRAIGHT, false, false, true, 32>(dspec, a, grid, lds_bytes, stream);
-}
-// bit rows of `rows` (a multiple of 64) maps at `map` -> `brd`; a = the launch's own LDS layout (maps at off_map, word tile at off_ltile, magicK = ceil(2^32 / BS))
-extern "C" hipError_t ngw_boards_launch(const NgwLaunch* a, int map_mode, const int8_t* map, uint32_t* brd, int64_t rows, size_t lds_bytes, hipStream_t stream) {
-    const void* fn = map_mode == NGW_MAP_STRAIGHT ? reinterpret_cast<const void*>(ngw_boards_kernel<NGW_MAP_STRAIGHT>)
-                   : (map_mode == NGW_MAP_DWORD ? reinterpret_cast<const void*>(ngw_boards_kernel<NGW_MAP_DWORD>) : reinterpret_cast<const void*>(ngw_boards_kernel<NGW_MAP_BYTE>));
-    if (lds_bytes > 64 * 1024) {
-        hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-    }
-    void* args[] = {const_cast<NgwLaunch*>(a), &map, &brd};
-    return hipLaunchKernel(fn, dim3((unsigned)(rows / NGW_EPB)), dim3(NGW_EPB), args, lds_bytes, stream);
-}
-extern "C" hipError_t ngw_lidar_boards_launch(const NgwLaunch* a, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    if (a->BS <= 12) hipLaunchKernelGGL(ngw_lidar_boards_kernel<12>, dim3(grid), dim3(NGW_EPB), lds_bytes, stream, *a);
-    else if (a->BS <= 20) hipLaunchKernelGGL(ngw_lidar_boards_kernel<20>, dim3(grid), dim3(NGW_EPB), lds_bytes, stream, *a);
-    else hipLaunchKernelGGL(ngw_lidar_boards_kernel<32>, dim3(grid), dim3(NGW_EPB), lds_bytes, stream, *a);
-    return hipGetLastError();
-}
-#endif  // NGW_HAS(8)
-#if NGW_HAS(1)
-NGW_STEP_PART(ngw_part_step_straight, NGW_MAP_STRAIGHT)
-extern "C" hipError_t ngw_part_step(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat, unsigned grid, size_t lds_bytes,
-                                    hipStream_t stream) {
-    if (feat & NGW_FEAT_NOSTAGE) {   // no-stage: with the lidar observation, the one on the occupancy bit rows
-        if (feat & NGW_FEAT_WIRE) return ngw_part_step_wire(dspec, a, feat, grid, lds_bytes, stream);   // ... with the host write-through
-        if (feat & NGW_FEAT_LIDAR) return ngw_part_step_boards(dspec, a, feat, grid, lds_bytes, stream);
-        if (feat & NGW_FEAT_MASK) return ngw_part_step_mask_ns(dspec, a, feat, grid, lds_bytes, stream);
-        return (feat & NGW_FEAT_EXT) ? launch_lean<NGW_MAP_STRAIGHT, false, true, false>(dspec, a, grid, lds_bytes, stream)
-                          : launch_lean<NGW_MAP_STRAIGHT, false, false, false>(dspec, a, grid, lds_bytes, stream);
-    }
-    switch (map_mode) {
-    case NGW_MAP_STRAIGHT: return ngw_part_step_straight(dspec, a, feat, grid, lds_bytes, stream);
-    case NGW_MAP_DWORD: return ngw_part_step_dword(dspec, a, feat, grid, lds_bytes, stream);
-    default: return ngw_part_step_byte(dspec, a, feat, grid, lds_bytes, stream);
-    }
-}
-#endif  // NGW_HAS(1)
-#if NGW_HAS(6)
-NGW_STEP_PART(ngw_part_step_dword, NGW_MAP_DWORD)
+NGW_PART_FN(ngw_part_step_wire_boards) { return step_boards<true>(dspec, a, feat, grid, lds_bytes, stream); }
 #endif
-#if NGW_HAS(7)
-NGW_STEP_PART(ngw_part_step_byte, NGW_MAP_BYTE)
-#endif
-#undef NGW_STEP_PART
+#undef NGW_PART_FN
 
-// fused rollout: ngw_rollout_lean, one part per map addressing mode (eight kernels each: the heaviest to compile)
-#define NGW_ROLLOUT_PART(NAME, MM)                                                                                                     \
-    extern "C" hipError_t NAME(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) { \
-        const bool lidar = (feat & NGW_FEAT_LIDAR) != 0, ext = (feat & NGW_FEAT_EXT) != 0;                                             \
-        if (a->mode == NGW_MODE_ROLLOUT_ACT)                                                                                           \
-            return lidar ? (ext ? launch_rollout_lean<MM, true, true, true>(dspec, a, grid, lds_bytes, stream)                         \
-                                : launch_rollout_lean<MM, true, false, true>(dspec, a, grid, lds_bytes, stream))                       \
-                         : (ext ? launch_rollout_lean<MM, true, true, false>(dspec, a, grid, lds_bytes, stream)                        \
-                                : launch_rollout_lean<MM, true, false, false>(dspec, a, grid, lds_bytes, stream));                     \
-        return lidar ? (ext ? launch_rollout_lean<MM, false, true, true>(dspec, a, grid, lds_bytes, stream)                            \
-                            : launch_rollout_lean<MM, false, false, true>(dspec, a, grid, lds_bytes, stream))                          \
-                     : (ext ? launch_rollout_lean<MM, false, true, false>(dspec, a, grid, lds_bytes, stream)                           \
-                            : launch_rollout_lean<MM, false, false, false>(dspec, a, grid, lds_bytes, stream));                        \
-    }
-#if NGW_HAS(2)
-NGW_ROLLOUT_PART(ngw_part_rollout_straight, NGW_MAP_STRAIGHT)
-#endif
-#if NGW_HAS(3)
-NGW_ROLLOUT_PART(ngw_part_rollout_dword, NGW_MAP_DWORD)
-#endif
-#if NGW_HAS(4)
-NGW_ROLLOUT_PART(ngw_part_rollout_byte, NGW_MAP_BYTE)
-#endif
-#undef NGW_ROLLOUT_PART
-
-#if NGW_HAS(0)
-extern "C" hipError_t ngw_launch(const NgwDevSpec* dspec, const NgwLaunch* a, int map_mode, int feat, unsigned grid,
-                                 size_t lds_bytes, hipStream_t stream) {
-    if (a->mode >= 10 && a->mode <= 12) {       // diagnostics: empty kernels with other workgroup shapes over the same lanes
-        const unsigned tpb = a->mode == 10 ? 256 : (a->mode == 11 ? 1024 : 128);
-        hipLaunchKernelGGL(ngw_nop_kernel, dim3(grid * NGW_EPB / tpb), dim3(tpb), a->mode == 12 ? lds_bytes * 2 : 0, stream, dspec, *a);
-        return hipGetLastError();
-    }
-    if (a->mode == 13) {                        // the launch floor: an empty kernel in the STEP kernel's launch shape (ngw_debug_launch_floor)
-        hipLaunchKernelGGL(ngw_nop_kernel, dim3(grid), dim3(NGW_EPB), lds_bytes, stream, dspec, *a);
-        return hipGetLastError();
-    }
-    if (a->mode == NGW_MODE_STEP) return ngw_part_step(dspec, a, map_mode, feat, grid, lds_bytes, stream);
-    if (a->mode == NGW_MODE_ROLLOUT || a->mode == NGW_MODE_ROLLOUT_ACT) {
-        switch (map_mode) {
-        case NGW_MAP_STRAIGHT: return ngw_part_rollout_straight(dspec, a, feat, grid, lds_bytes, stream);
-        case NGW_MAP_DWORD: return ngw_part_rollout_dword(dspec, a, feat, grid, lds_bytes, stream);
-        default: return ngw_part_rollout_byte(dspec, a, feat, grid, lds_bytes, stream);
-        }
-    }
-    const bool lidar = (feat & NGW_FEAT_LIDAR) != 0;
-    switch (map_mode) {
-    case NGW_MAP_STRAIGHT: return launch_general<NGW_MAP_STRAIGHT>(dspec, a, lidar, grid, lds_bytes, stream);
-    case NGW_MAP_DWORD: return launch_general<NGW_MAP_DWORD>(dspec, a, lidar, grid, lds_bytes, stream);
-    default: return launch_general<NGW_MAP_BYTE>(dspec, a, lidar, grid, lds_bytes, stream);
-    }
-}
-#endif  // NGW_HAS(0)
 #if NGW_HAS(11)
 namespace {
 #include "ngw_snapshot.inc"
@@ -853,12 +783,12 @@ extern "C" hipError_t ngw_snapshot_launch(const NgwSnap* p, hipStream_t stream) 
         return hipErrorInvalidValue;
     constexpr int rows = NGW_SNAP_BLOCK / NGW_SNAP_GROUP;
     const dim3 grid((unsigned)((p->count + rows - 1) / rows)), block(NGW_SNAP_BLOCK);
-    if (p->S2 % 16 == 0) hipLaunchKernelGGL(ngw_snapshot_kernel<16>, grid, block, 0, stream, *p);
-    else if (p->S2 % 4 == 0) hipLaunchKernelGGL(ngw_snapshot_kernel<4>, grid, block, 0, stream, *p);
-    else hipLaunchKernelGGL(ngw_snapshot_kernel<1>, grid, block, 0, stream, *p);
-    return hipGetLastError();
+    if (p->S2 % 16 == 0) return launch_kernel<ngw_snapshot_kernel<16>>(grid, block, 0, stream, *p);
+    if (p->S2 % 4 == 0) return launch_kernel<ngw_snapshot_kernel<4>>(grid, block, 0, stream, *p);
+    return launch_kernel<ngw_snapshot_kernel<1>>(grid, block, 0, stream, *p);
 }
 #endif  // NGW_HAS(11)
+
 #if NGW_HAS(12)
 // the one-step lookahead table of the state in HBM (ngw_lookahead.inc): action-major [n_actions][n_pad] reward / done / info
 extern "C" hipError_t ngw_lookahead_launch(const NgwDevSpec* dspec, const NgwBufs* b, int64_t n, int64_t n_pad, int S, int K, int ext, int autoreset, int horizon,
@@ -866,11 +796,12 @@ extern "C" hipError_t ngw_lookahead_launch(const NgwDevSpec* dspec, const NgwBuf
     if (n <= 0 || n > 0xFFFFFFFFll || n_pad < n || (int64_t)grid * NGW_EPB != n_pad || S < 3 || S > NGW_MAX_MAP_SIZE || K < 1 || K > NGW_MAX_ITEMS ||
         !reward || !done || !info)
         return hipErrorInvalidValue;
-    if (ext) hipLaunchKernelGGL(ngw_lookahead_kernel<true>, dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, autoreset, horizon, (uint64_t)n_pad, reward, done, info);
-    else hipLaunchKernelGGL(ngw_lookahead_kernel<false>, dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, autoreset, horizon, (uint64_t)n_pad, reward, done, info);
-    return hipGetLastError();
+    return with_flag(ext != 0, [&](auto E) {
+        return launch_kernel<ngw_lookahead_kernel<decltype(E)::value>>(dim3(grid), dim3(NGW_EPB), 0, stream, dspec, *b, (uint32_t)n, S, K, autoreset, horizon, (uint64_t)n_pad, reward, done, info);
+    });
 }
 #endif  // NGW_HAS(12)
+
 #if NGW_HAS(13)
 // plan evaluation (ngw_plans.inc): a = the handle's rollout layout with a.actions = the plans, a.t0 = their env stride, a.n_steps, a.autoreset,
 // a.horizon; grid = n_plans * n_pad / NGW_EPB work-groups
@@ -879,13 +810,10 @@ extern "C" hipError_t ngw_plans_launch(const NgwDevSpec* dspec, const NgwLaunch*
     if (a->n <= 0 || a->n_pad < a->n || a->n_pad % NGW_EPB || pa->n_plans < 1 || a->n_steps < 1 || a->t0 < a->n || grid * NGW_EPB > 0xFFFFFFFFull ||
         a->S < 3 || a->S > NGW_MAX_MAP_SIZE || a->K < 1 || a->K > NGW_MAX_ITEMS || !a->actions || !pa->ret || !pa->length || !pa->ended || !pa->info)
         return hipErrorInvalidValue;
-    switch (map_mode) {
-    case NGW_MAP_STRAIGHT: return ext ? launch_plans_lean<NGW_MAP_STRAIGHT, true>(dspec, a, pa, (unsigned)grid, lds_bytes, stream)
-                                      : launch_plans_lean<NGW_MAP_STRAIGHT, false>(dspec, a, pa, (unsigned)grid, lds_bytes, stream);
-    case NGW_MAP_DWORD: return ext ? launch_plans_lean<NGW_MAP_DWORD, true>(dspec, a, pa, (unsigned)grid, lds_bytes, stream)
-                                   : launch_plans_lean<NGW_MAP_DWORD, false>(dspec, a, pa, (unsigned)grid, lds_bytes, stream);
-    default: return ext ? launch_plans_lean<NGW_MAP_BYTE, true>(dspec, a, pa, (unsigned)grid, lds_bytes, stream)
-                        : launch_plans_lean<NGW_MAP_BYTE, false>(dspec, a, pa, (unsigned)grid, lds_bytes, stream);
-    }
+    return with_map_mode(map_mode, [&](auto MM) {
+        return with_flag(ext != 0, [&](auto E) {
+            return launch_kernel<ngw_plans_lean<decltype(MM)::value, decltype(E)::value>>(dim3((unsigned)grid), dim3(NGW_EPB), lds_bytes, stream, dspec, *a, *pa);
+        });
+    });
 }
 #endif  // NGW_HAS(13)

@@ -234,18 +234,3 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_rollout_lean(const NgwDevSpec* __
     raise_host_flags(a.b.flags_host, flags);
 }
 
-
-template <int MAPMODE, bool SUPPLIED, bool EXT, bool LIDAR>
-hipError_t launch_rollout_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    static size_t lds_opt_in[64] = {0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (lds_bytes > 64 * 1024 && dev < 64 && lds_bytes > lds_opt_in[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ngw_rollout_lean<MAPMODE, SUPPLIED, EXT, LIDAR>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        lds_opt_in[dev] = lds_bytes;
-    }
-    hipLaunchKernelGGL((ngw_rollout_lean<MAPMODE, SUPPLIED, EXT, LIDAR>), dim3(grid), dim3(NGW_EPB), lds_bytes, stream, dspec, *a);
-    return hipGetLastError();
-}

@@ -400,15 +400,6 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
 
 template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false>
 hipError_t launch_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    static size_t lds_opt_in[64] = {0};
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (lds_bytes > 64 * 1024 && dev < 64 && lds_bytes > lds_opt_in[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        lds_opt_in[dev] = lds_bytes;
-    }
     // the leading scalar arguments (see the kernel): the state slab's base and the offsets of its arrays in 16-byte units
     char* const base = reinterpret_cast<char*>(a->b.map);
     const void* const arr[5] = {a->b.inv, a->b.loc, a->b.facing, a->b.selected, a->b.step_count};
@@ -427,7 +418,6 @@ hipError_t launch_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned gri
     } else if (NR > 0) return hipErrorInvalidValue;
     if (NR > 0 && (a->BS > NR || a->BS < 4)) return hipErrorInvalidValue;
     const uint32_t s2k = (uint32_t)a->S2 | ((uint32_t)a->K << 16) | ((uint32_t)a->S << 24);
-    hipLaunchKernelGGL((ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK>), dim3(grid), dim3(NGW_EPB), lds_bytes, stream, base, a->actions, (uint32_t)a->n, o_brd, dspec,
-                       off[0], off[1], off[2], off[3], off[4], s2k, *a);
-    return hipGetLastError();
+    return launch_kernel<ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, base, a->actions, (uint32_t)a->n, o_brd, dspec,
+                                                                                off[0], off[1], off[2], off[3], off[4], s2k, *a);
 }

@@ -83,18 +83,3 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_plans_lean(const NgwDevSpec* __re
     if (flags) atomicOr(a.b.flags, flags);
     raise_host_flags(a.b.flags_host, flags);
 }
-
-template <int MAPMODE, bool EXT>
-hipError_t launch_plans_lean(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwPlan* pa, unsigned grid, size_t lds_bytes, hipStream_t stream) {
-    static size_t lds_opt_in[64] = {0};                                            // (the opt-in above 64 KiB, per device, as launch_rollout_lean)
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return e;
-    if (lds_bytes > 64 * 1024 && dev < 64 && lds_bytes > lds_opt_in[dev]) {
-        e = hipFuncSetAttribute(reinterpret_cast<const void*>(ngw_plans_lean<MAPMODE, EXT>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-        if (e != hipSuccess) return e;
-        lds_opt_in[dev] = lds_bytes;
-    }
-    hipLaunchKernelGGL((ngw_plans_lean<MAPMODE, EXT>), dim3(grid), dim3(NGW_EPB), lds_bytes, stream, dspec, *a, *pa);
-    return hipGetLastError();
-}
