@@ -1,7 +1,9 @@
 // ngw_abi_snapshot.cpp - device-side snapshots (see ngw_host.h): buffers of saved env states and the one kernel (ngw_snapshot.inc) that moves
 // rows between them and the state slab through index lists.  A restore changes the state behind the library's back-ups, so it reports it
 // as ngw_set_state does (state_written), and then refreshes a fused lidar observation and schedules a refill of the prepared next
-// episodes, as ngw_reset does.
+// episodes, as ngw_reset does.  An expand (ngw_expand.inc) steps rows of the state slab or of a snapshot into slots of a snapshot: it commits
+// nothing, so it neither calls state_written() nor touches anything the handle derives from its state, and counts no steps against the
+// prepared-episode cadence (no reset runs).
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -120,6 +122,31 @@ int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_de
     // merely stale (their next reset runs the placement loop: same result).  A refill behind the restore prepares fresh ones, like the
     // one behind an explicit reset; with the counters kept every tag still matches and nothing is scheduled.
     return keep ? NGW_OK : steps_since_refill(h, h->prefetch_every);
+}
+
+int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, ngw_snapshot* dst,
+                        const int32_t* dst_slots_dev, int64_t count, int32_t* reward_dev, uint8_t* done_dev, uint32_t* info_dev) {
+    if (!h || !dst || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns(h, dst) || (src && !owns(h, src))) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    const int64_t src_rows = src ? src->cap : h->n;
+    if (count < 0 || count > dst->cap) return fail(NGW_E_INVALID_ARG, "expand of %lld states into a snapshot of %lld slots", (long long)count, (long long)dst->cap);
+    if (!src_idx_dev && count > src_rows) return fail(NGW_E_INVALID_ARG, "expand of %lld states from %lld %s", (long long)count, (long long)src_rows, src ? "slots" : "envs");
+    if (!h->general_ok)
+        return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps in LDS (ngw_snapshot_expand, as the fused rollouts) "
+                                       "and they need more than 160 KiB; per-launch steps and resets are available", h->proto.S);
+    if (int rc = enter(h)) return rc;
+    if (count == 0) return NGW_OK;
+    NgwLaunch a = h->proto;
+    a.b = h->b;
+    a.autoreset = h->autoreset;
+    a.horizon = h->horizon;
+    NgwExpand x{};
+    x.src = src ? src->r : state_rows(h); x.dst = dst->r;
+    x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev;
+    x.reward = reward_dev; x.done = done_dev; x.info = info_dev;
+    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows; x.dst_rows = (int32_t)dst->cap;
+    HIP_TRY(ngw_expand_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
+    return NGW_OK;
 }
 
 int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t count, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv,

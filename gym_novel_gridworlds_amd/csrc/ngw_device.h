@@ -462,4 +462,23 @@ extern "C"
 #endif
 hipError_t ngw_snapshot_launch(const struct NgwSnap* p, hipStream_t stream);
 
+/* Snapshot expand (ngw_expand.inc, ngw_abi_snapshot.cpp): pair j = row si[j] of `src` (the state slab or a snapshot) stepped once with actions[j],
+ * the stepped row - before any reset - stored to row di[j] of `dst` (a snapshot), the step's reward / done / info to element j of the three
+ * report arrays (any may be nullptr).  A NULL index list = j itself; an index outside its set skips the pair and raises NGW_F_BAD_INDEX.  src
+ * and dst may be the same rows.  The launch block is the handle's rollout layout (LDS carve-up, autoreset, horizon, the flags word). */
+struct NgwExpand {
+    NgwSnapRows src, dst;
+    const int32_t* si;
+    const int32_t* di;
+    const int32_t* actions;
+    int32_t* reward;
+    uint8_t* done;
+    uint32_t* info;
+    int32_t count, src_rows, dst_rows;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_expand_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwExpand* x, int ext, size_t lds_bytes, hipStream_t stream);
+
 #endif

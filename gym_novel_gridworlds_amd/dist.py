@@ -125,7 +125,8 @@ class ShardedVecNovelGridworld:
         return self.local.evaluate_plans(plans, device=device, copy=copy)
 
     def snapshot(self, capacity=None):
-        """A device-side snapshot of this rank's shard (VecNovelGridworld.snapshot): rank-local, env indices are the shard's own."""
+        """A device-side snapshot of this rank's shard (VecNovelGridworld.snapshot): rank-local, env indices are the shard's own - in
+        save / restore and in expand / expand_all (from_envs=True: parents are the shard's envs 0 .. num_envs-1)."""
         return self.local.snapshot(capacity)
 
     def fork(self, src, keep_episode=False):

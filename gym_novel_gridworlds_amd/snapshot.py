@@ -7,10 +7,13 @@
     snap.restore()                             # env i := slot i: the envs are back where they were, episode counters included
     snap.restore(slots=best, envs=worst)       # population methods: the states saved from the best envs over the worst
     env.fork(src)                              # env e := env src[e]
+    pool = env.snapshot(4096)                  # a node pool: tree search keeps the states it grows
+    e = pool.expand(parents, actions, children)    # slot children[j] := slot parents[j] stepped once with actions[j]; no env is touched
 
 What a restored env does next: env e, when it next resets, draws from env e's OWN stream at its (restored or kept) episode counter.  Two
 forks of one slot share the rest of the current episode and differ from their next reset on; restoring the same env from the same slot
 twice replays the same future.  reward / done / info of the last step are not part of a snapshot."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -48,6 +51,95 @@ def pair_count(n_a, n_b, default):
     if n_a is not None and n_b is not None and n_a != n_b:
         raise ValueError("index lists of different lengths: %d and %d" % (n_a, n_b))
     return n_a if n_a is not None else n_b
+
+
+def check_action_ids(actions, n_actions, name='actions'):
+    """The host-side check of one action id per pair given as a list / numpy array: integer dtype, one dimension, every id in the action
+    list (ValueError("<a> is not in list") otherwise, what step() raises).  Returns a contiguous int32 array."""
+    if actions is None:
+        raise ValueError("%s: one action id per pair expected" % name)
+    a = np.asarray(actions)
+    if a.size == 0 and a.ndim == 1:
+        return np.zeros(0, np.int32)
+    if a.dtype.kind not in 'iu':
+        raise ValueError("%s: integer action ids expected, got dtype %s" % (name, a.dtype))
+    if a.ndim != 1:
+        raise ValueError("%s: a one-dimensional list of action ids expected, got shape %s" % (name, a.shape))
+    bad = (a < 0) | (a >= n_actions)
+    if bad.any():
+        raise ValueError("%d is not in list" % int(a[bad][0]))
+    return np.ascontiguousarray(a, np.int32)
+
+
+def check_expand(parents, actions, children, n_parents, capacity, n_actions, same_buffer, device_len=None):
+    """The host-side checks of one expand call: parents index rows [0, n_parents) and may repeat, children index slots [0, capacity) and
+    must be distinct, actions are ids of the action list, the three have one length (None = no list: 0 .. count-1, which must exist), and -
+    where source and destination are the same buffer - no child is also a parent.  device_len(x): the length of x when it is a device
+    tensor to be used in place (its values are then not checked), else None.  Returns (parents, actions, children, count): contiguous
+    int32 arrays, None, or the device tensors themselves."""
+    on_dev = (lambda x: None) if device_len is None else device_len
+    n_p, n_a, n_c = on_dev(parents), on_dev(actions), on_dev(children)
+    if n_p is None and parents is not None:
+        parents = check_indices(parents, n_parents, False, 'parents')
+        n_p = int(parents.size)
+    if n_a is None:
+        actions = check_action_ids(actions, n_actions)
+        n_a = int(actions.size)
+    if n_c is None and children is not None:
+        children = check_indices(children, capacity, True, 'children')
+        n_c = int(children.size)
+    count = pair_count(pair_count(n_p, n_a, n_a), n_c, n_a)
+    if parents is None and count > n_parents:
+        raise ValueError("parents: no list given and %d pairs for %d rows" % (count, n_parents))
+    if count > capacity:
+        raise ValueError("children: %d pairs for a snapshot of %d slots" % (count, capacity))
+    if same_buffer and count and on_dev(parents) is None and on_dev(children) is None:
+        hp = np.arange(count) if parents is None else parents
+        hc = np.arange(count) if children is None else children
+        both = np.intersect1d(hp, hc)
+        if both.size:
+            raise ValueError("children: slot %d is also a parent of the same call (source and destination are one buffer)" % int(both[0]))
+    return parents, actions, children, count
+
+
+class Expansion(collections.namedtuple('Expansion', 'reward done result info')):
+    """What Snapshot.expand() returns: reward int32, done bool, result bool and info uint32 (the packed words: decode_info_words(e.info)
+    gives what step_costs() / messages() take), each [count] - what step() would have reported for each pair.  A named tuple (it unpacks
+    in that order) whose fields can also be read by name: e['reward'].  numpy arrays, or torch tensors ('info' is int32 there, the same bits)."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    @property
+    def goal(self):
+        """The step itself reported done (info bit 1, as on PlanEval: set by the goal - and by a FireWall death, which `died` tells
+        apart -, clear for a horizon cut)."""
+        return self.done & (((self.info >> 1) & 1) != 0)
+
+    @property
+    def died(self):
+        """The step ended the episode in a FireWall death (message code 14)."""
+        return self.done & (((self.info >> 8) & 255) == 14)
+
+    def reshape(self, *shape):
+        return Expansion(*[x.reshape(*shape) for x in self])
+
+
+def all_actions_pairs(parents, first_child, n_actions):
+    """expand_all's index arithmetic: every parent paired with every action id 0 .. A-1, the children in len(parents) * A consecutive slots
+    from first_child (row-major: parent p, action a -> slot first_child + p * A + a).  parents: a list / numpy array, or a torch tensor
+    (the three lists are then tensors on its device).  -> (parents, actions, children, (P, A))"""
+    A = int(n_actions)
+    if hasattr(parents, 'data_ptr'):
+        import torch
+        P = int(parents.numel())
+        ids = torch.arange(P * A, dtype=torch.int32, device=parents.device)
+        return parents.repeat_interleave(A).contiguous(), (ids % A).contiguous(), ids + int(first_child), (P, A)
+    p = np.asarray(parents)
+    P = int(p.size)
+    ids = np.arange(P * A, dtype=np.int64)
+    return np.repeat(p, A), ids % A, ids + int(first_child), (P, A)
 
 
 class Snapshot:
@@ -112,6 +204,75 @@ class Snapshot:
         e = self._dev_index(envs, self.env.num_envs, True, 'envs')
         self.env._lidar_rows_fresh = False
         self._call(_cabi.lib().ngw_snapshot_restore, s, e, self.env.num_envs, KEEP_EPISODE if keep_episode else 0)
+
+    def expand(self, parents, actions, children, from_envs=False, source=None, device=False):
+        """slot[children[j]] := the state of parent parents[j] stepped ONCE with actions[j], as the step leaves it before any reset (the
+        child of a step that ends the episode is the state the episode ended in; its episode counter is the parent's).  The parents are
+        slots of `source` (another Snapshot of the same env; default: this one) or, with from_envs=True, the env's current states.
+        Returns an Expansion of what step() would have reported for each pair: 'reward' int32, 'done' bool, 'result' bool, 'info' uint32,
+        each [count].  Nothing is committed: no env, no mask, no lookahead table, no prepared episode and no slot but the children changes,
+        and the number of pairs is not bound by num_envs.  One kernel launch.
+        Parents may repeat (the fan-out); the children of one call must be distinct, and where source and destination are one buffer no
+        child may also be a parent of the same call.  Lists and numpy arrays are checked here (range, distinct children, children disjoint
+        from parents, action ids - a bad id raises the ValueError step() raises); torch int32 tensors on the env's device are used in place,
+        unchecked: an index out of range skips that pair (F_BAD_INDEX, its reports stay 0), an id outside the action list leaves the child a
+        copy of the parent with reports 0 (F_INVALID_ACTION), see error_flags().  None for parents or children means 0 .. count-1.
+        device=True: the results as torch tensors on the env's device ('info' int32), ordered behind the launch on torch's current stream -
+        no copy, no host wait; otherwise numpy arrays after one sync."""
+        import torch
+        env = self.env
+        self._open()
+        if source is not None and from_envs:
+            raise ValueError("expand: give either source or from_envs")
+        src = self if source is None else source
+        if not from_envs:
+            if not isinstance(src, Snapshot):
+                raise ValueError("source: a Snapshot expected")
+            src._open()
+            if src.env is not env:
+                raise ValueError("source: a snapshot of another env")
+        n_parents = env.num_envs if from_envs else src.capacity
+        dev = torch.device('cuda:%d' % env.device)
+
+        def device_len(x):
+            if not isinstance(x, torch.Tensor):
+                return None
+            if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
+                raise ValueError("a contiguous one-dimensional int32 tensor on %s expected" % dev)
+            return int(x.numel())
+        p, a, c, count = check_expand(parents, actions, children, n_parents, self.capacity, env.n_actions, not from_envs and src is self, device_len)
+        ptr, uploaded = [], []
+        for x in (p, a, c):
+            if isinstance(x, np.ndarray):
+                x = torch.from_numpy(x).to(dev)
+                uploaded.append(x)
+            ptr.append(C.c_void_p(x.data_ptr()) if x is not None and count else None)
+        reward = torch.zeros(count, dtype=torch.int32, device=dev)
+        done = torch.zeros(count, dtype=torch.uint8, device=dev)
+        info = torch.zeros(count, dtype=torch.int32, device=dev)
+        if self._keep:
+            env.sync()                          # (the previous call has read its lists: they may be released now)
+            self._keep = None
+        if count:
+            # uploads, zero fills and the caller's own tensors are work of torch's current stream, the launch runs on the env's: it waits for them
+            env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, True)
+            _cabi.check(_cabi.lib().ngw_snapshot_expand(env._h, None if from_envs else src._s, ptr[0], ptr[1], self._s, ptr[2], int(count),
+                                                        C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), C.c_void_p(info.data_ptr())))
+            self._keep = uploaded or None
+        if device:
+            if count:
+                env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, False)
+            return Expansion(reward, done.view(torch.bool), (info & 1).bool(), info)
+        env.sync()
+        self._keep = None
+        words = info.cpu().numpy().view(np.uint32)
+        return Expansion(reward.cpu().numpy(), done.cpu().numpy().view(np.bool_), (words & 1).astype(np.bool_), words)
+
+    def expand_all(self, parents, first_child, from_envs=False, source=None, device=False):
+        """Every parent with every action id 0 .. A-1 (A = env.n_actions): the child of (parents[p], a) goes to slot first_child + p * A + a.
+        Returns the Expansion shaped [len(parents), A]."""
+        p, a, c, shape = all_actions_pairs(parents, first_child, self.env.n_actions)
+        return self.expand(p, a, c, from_envs=from_envs, source=source, device=device).reshape(*shape)
 
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""

@@ -45,7 +45,7 @@ extern "C" {
 /* device-side sticky error flags (ngw_error_flags) */
 #define NGW_F_INVALID_ACTION 1u
 #define NGW_F_PLACEMENT 2u
-#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore: an env or slot index outside its range (that copy was skipped) */
+#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand: an env or slot index outside its range (that copy / pair was skipped) */
 
 /* action kinds (act_kind[]); act_arg[] = recipe index (CRAFT) or item id (SELECT) */
 enum { NGW_ACT_FORWARD = 0, NGW_ACT_LEFT = 1, NGW_ACT_RIGHT = 2, NGW_ACT_BREAK = 3, NGW_ACT_PLACE = 4,
@@ -478,6 +478,37 @@ int ngw_snapshot_save(ngw_handle* h, ngw_snapshot* s, const int32_t* envs_dev, c
 int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, const int32_t* envs_dev, int64_t count, int flags);
 int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t count, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv,
                      int32_t* selected, int32_t* step_count, uint32_t* episode);
+
+/* Snapshot expand: step saved states into new slots, commit nothing (the node expansion of a tree search: beam search, MCTS, archives of
+ * states, breadth-first solvers - lookahead tables and plan evaluation return numbers and throw the stepped state away, this keeps it).
+ * For j < count: the parent is row src_idx[j] - of snapshot `src`, or, with src == NULL, the handle's env src_idx[j] -, the child is the parent
+ * stepped once with actions[j], and the child goes to slot dst_slots[j] of `dst`.  A NULL index list means 0 .. count-1, as in save and restore.
+ * The child is the full seven-array row as the step leaves it BEFORE any reset: map, agent_location, agent_facing_id, inventory and selected
+ * carry the step's effects (the one cell write, the 3 x 3 pick-up, Crate contents, a craft's inputs and output, a move, turn or jump),
+ * step_count is what the step leaves (+1, or +2 where FenceRestriction's epilogue counts twice), episode is the parent's.  No reset runs: the
+ * child of a step that ends the episode (goal, FireWall death, the horizon under autoreset) is the state the episode ended in - what terminal
+ * capture would store.  The rules are exactly those of ngw_step_device under the handle's spec, every novelty and wrapper predicate, and its
+ * autoreset setting and horizon.
+ * reward[j], done[j], info[j] (device memory, [count], any may be NULL) are what ngw_get_step_out would report for that step (the NGW_INFO_*
+ * packing); when the parent is env i's current state they equal entry (i, actions[j]) of the lookahead table.  The sticky done of a parent
+ * that already holds the goal item, with autoreset off, is reported as the step reports it; expanding an ended node is the caller's business.
+ * An action id outside [0, n_actions) behaves as in ngw_plan_eval: the child is a copy of the parent, reward, done and info are 0, and the
+ * sticky NGW_F_INVALID_ACTION is raised.
+ * A parent or destination index out of range skips that pair - nothing is stored, its reports are left untouched - and raises the sticky
+ * NGW_F_BAD_INDEX; nothing is ever addressed with it.  Parents may repeat (the fan-out); the destination slots of one call must be distinct.
+ * src == dst is allowed (a node pool in one buffer): then no destination slot of the call may also be a parent of the same call.  Device
+ * index lists are used in place, unchecked beyond range: a violated distinctness rule leaves those slots' contents unspecified and never
+ * causes an out-of-bounds access.
+ * Nothing is committed (the lookahead's list holds in full): every byte of every env's state, the last step's reward / done / info, the
+ * prepared next episodes, the mask buffer and the lookahead table and whether each is current, the lidar rows, the bit rows, the host mirrors,
+ * the rollout output rows and accumulators, the terminal-capture side set, and every slot of every snapshot that the call does not name as a
+ * destination are what they were.  Because no reset runs, the call is allowed while terminal capture is on.
+ * One kernel launch, enqueued on the handle's stream; does not wait.  A captured graph stays valid.  count == 0 is a no-op.
+ * NGW_E_INVALID_ARG: a NULL handle, dst or actions; a src or dst that is not an open snapshot of this handle; count < 0 or above dst's
+ * capacity; src_idx == NULL with count above the source's row count (src's capacity, or n_envs); maps that do not fit LDS (the kernel keeps
+ * a wavefront's 64 rows there, the fused rollouts' limit). */
+int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, ngw_snapshot* dst,
+                        const int32_t* dst_slots_dev, int64_t count, int32_t* reward_dev, uint8_t* done_dev, uint32_t* info_dev);
 
 /* One-step lookahead tables: every action's outcome for every env, without taking a step.
  * For a handle with A = n_actions the table of the CURRENT state is three arrays - reward int32, done uint8, info uint32 (the NGW_INFO_* packing).
