@@ -27,7 +27,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_lidar_row_layout', 'ngw_step_kernel_info', 'ngw_set_terminal_capture', 'ngw_get_terminal_obs', 'ngw_terminal_device_ptrs',
            'ngw_host_step_layout_packed', 'ngw_step_host_packed', 'ngw_lidar_host_rows',
            'ngw_set_action_mask', 'ngw_action_mask', 'ngw_get_action_mask', 'ngw_action_mask_device_ptr',
-           'ngw_snapshot_create', 'ngw_snapshot_destroy', 'ngw_snapshot_save', 'ngw_snapshot_restore', 'ngw_snapshot_get', 'ngw_snapshot_expand',
+           'ngw_snapshot_create', 'ngw_snapshot_destroy', 'ngw_snapshot_save', 'ngw_snapshot_restore', 'ngw_snapshot_get', 'ngw_snapshot_expand', 'ngw_snapshot_rollout',
            'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
@@ -164,6 +164,8 @@ def lib():
         L.ngw_snapshot_get.argtypes = [vp, vp, i64, i64] + [vp] * 7
     if hasattr(L, 'ngw_snapshot_expand'):
         L.ngw_snapshot_expand.argtypes = [vp, vp, vp, vp, vp, vp, i64, vp, vp, vp]
+    if hasattr(L, 'ngw_snapshot_rollout'):
+        L.ngw_snapshot_rollout.argtypes = [vp, vp, vp, vp, i64, C.c_int32, vp, vp, i64, vp, vp, vp, vp]
     if hasattr(L, 'ngw_lookahead'):
         L.ngw_lookahead.argtypes = [vp]
         L.ngw_get_lookahead.argtypes = [vp, vp, vp, vp]

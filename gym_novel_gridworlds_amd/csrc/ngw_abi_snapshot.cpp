@@ -3,7 +3,8 @@
 // as ngw_set_state does (state_written), and then refreshes a fused lidar observation and schedules a refill of the prepared next
 // episodes, as ngw_reset does.  An expand (ngw_expand.inc) steps rows of the state slab or of a snapshot into slots of a snapshot: it commits
 // nothing, so it neither calls state_written() nor touches anything the handle derives from its state, and counts no steps against the
-// prepared-episode cadence (no reset runs).
+// prepared-episode cadence (no reset runs).  A rollout (ngw_slot_rollout.inc) steps such rows through a whole action sequence and keeps the end
+// state, the numbers, or both: it commits nothing either.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -146,6 +147,39 @@ int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx
     x.reward = reward_dev; x.done = done_dev; x.info = info_dev;
     x.count = (int32_t)count; x.src_rows = (int32_t)src_rows; x.dst_rows = (int32_t)dst->cap;
     HIP_TRY(ngw_expand_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
+    return NGW_OK;
+}
+
+int ngw_snapshot_rollout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
+                         ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev,
+                         uint32_t* info_dev) {
+    if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "rollout of %d steps", (int)n_steps);
+    if (count < 0 || pair_stride < count)
+        return fail(NGW_E_INVALID_ARG, "rollout of %lld pairs with a pair stride of %lld", (long long)count, (long long)pair_stride);
+    if (!dst && !ret_dev && !length_dev && !ended_dev && !info_dev) return fail(NGW_E_INVALID_ARG, "rollout without a destination and without a report: nothing to do");
+    if (!dst && dst_slots_dev) return fail(NGW_E_INVALID_ARG, "destination slots without a destination snapshot");
+    if ((dst && !owns(h, dst)) || (src && !owns(h, src))) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    const int64_t src_rows = src ? src->cap : h->n;
+    if (count > 0x7FFFFFFFll || (dst && count > dst->cap))
+        return fail(NGW_E_INVALID_ARG, "rollout of %lld states into a snapshot of %lld slots", (long long)count, (long long)(dst ? dst->cap : 0x7FFFFFFFll));
+    if (!src_idx_dev && count > src_rows) return fail(NGW_E_INVALID_ARG, "rollout of %lld states from %lld %s", (long long)count, (long long)src_rows, src ? "slots" : "envs");
+    if (!h->general_ok)
+        return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps in LDS (ngw_snapshot_rollout, as the fused rollouts) "
+                                       "and they need more than 160 KiB; per-launch steps and resets are available", h->proto.S);
+    if (int rc = enter(h)) return rc;
+    if (count == 0) return NGW_OK;
+    NgwLaunch a = h->proto;
+    a.b = h->b;
+    a.autoreset = h->autoreset;
+    a.horizon = h->horizon;
+    NgwSlotRollout x{};
+    x.src = src ? src->r : state_rows(h);
+    if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
+    x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = pair_stride; x.n_steps = n_steps;
+    x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev;
+    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
+    HIP_TRY(ngw_slot_rollout_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
     return NGW_OK;
 }
 

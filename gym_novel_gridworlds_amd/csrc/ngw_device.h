@@ -481,4 +481,29 @@ extern "C"
 #endif
 hipError_t ngw_expand_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwExpand* x, int ext, size_t lds_bytes, hipStream_t stream);
 
+/* Snapshot rollout (ngw_slot_rollout.inc, ngw_abi_snapshot.cpp): pair j = row si[j] of `src` (the state slab or a snapshot) stepped up to n_steps
+ * times on a private copy with the actions at actions[t * stride + j] (stride >= count), by the rules of the plan kernel: it stops at the first
+ * step that ends the episode, that step counts, no reset runs.  ret / length / ended / info (any may be nullptr) take element j as NgwPlan
+ * defines them.  keep != 0: the row as the last executed step leaves it goes to row di[j] of `dst` (a snapshot); keep == 0: dst and di are not
+ * read and nothing but the reports is stored.  A NULL index list = j itself; an index outside its set skips the pair and raises
+ * NGW_F_BAD_INDEX.  src and dst may be the same rows.  The launch block is the handle's rollout layout (LDS carve-up, autoreset, horizon, the
+ * flags word). */
+struct NgwSlotRollout {
+    NgwSnapRows src, dst;
+    const int32_t* si;
+    const int32_t* di;
+    const int32_t* actions;
+    int64_t stride;
+    int32_t* ret;
+    int32_t* length;
+    uint8_t* ended;
+    uint32_t* info;
+    int32_t count, src_rows, dst_rows;
+    int32_t n_steps, keep;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_slot_rollout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream);
+
 #endif

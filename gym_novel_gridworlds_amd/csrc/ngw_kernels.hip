@@ -30,7 +30,7 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file FIFTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file SIXTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
@@ -38,7 +38,7 @@
 //   9 / 10: the host write-through step kernels, plain / with the bit-row lidar (9 also holds the standalone mask kernel and the in-place step
 //   with fused masks; 1 / 6 / 7 hold the staged ones)
 //   11: device-side snapshots (ngw_snapshot.inc)   12: one-step lookahead tables (ngw_lookahead.inc)   13: plan evaluation (ngw_plans.inc)
-//   14: snapshot expand (ngw_expand.inc)
+//   14: snapshot expand (ngw_expand.inc)   15: snapshot rollout (ngw_slot_rollout.inc; it shares ngw_expand.inc's row mover)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -390,8 +390,11 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #if NGW_HAS(13)
 #include "ngw_plans.inc"
 #endif
-#if NGW_HAS(14)
+#if NGW_HAS(14) || NGW_HAS(15)
 #include "ngw_expand.inc"
+#endif
+#if NGW_HAS(15)
+#include "ngw_slot_rollout.inc"
 #endif
 
 // ---------------------------------------------------------------- LidarInFront observation kernel (stand-alone launch)
@@ -829,13 +832,25 @@ extern "C" hipError_t ngw_expand_launch(const NgwDevSpec* dspec, const NgwLaunch
         (a->MS & 3) || !a->b.flags || !x->actions || !x->src.map || !x->dst.map)
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)(((int64_t)x->count + NGW_EPB - 1) / NGW_EPB)), block(NGW_EPB);
-    auto go = [&](auto V) {
+    return with_row_piece(a->S2, [&](auto V) {
         return with_flag(ext != 0, [&](auto E) {
             return launch_kernel<ngw_expand_kernel<decltype(V)::value, decltype(E)::value>>(grid, block, lds_bytes, stream, dspec, *a, *x);
         });
-    };
-    if (a->S2 % 16 == 0) return go(std::integral_constant<int, 16>{});
-    if (a->S2 % 4 == 0) return go(std::integral_constant<int, 4>{});
-    return go(std::integral_constant<int, 1>{});
+    });
 }
 #endif  // NGW_HAS(14)
+
+#if NGW_HAS(15)
+// snapshot rollout (ngw_slot_rollout.inc): a = the handle's rollout layout with a.autoreset, a.horizon; one wave per 64 pairs
+extern "C" hipError_t ngw_slot_rollout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream) {
+    if (x->count <= 0 || x->n_steps < 1 || x->stride < x->count || x->src_rows < 1 || a->S < 3 || a->S > NGW_MAX_MAP_SIZE || a->K < 1 || a->K > NGW_MAX_ITEMS ||
+        a->MS < a->S2 || (a->MS & 3) || !a->b.flags || !x->actions || !x->src.map || (x->keep && (!x->dst.map || x->dst_rows < 1)) || (!x->keep && x->di))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((int64_t)x->count + NGW_EPB - 1) / NGW_EPB)), block(NGW_EPB);
+    return with_row_piece(a->S2, [&](auto V) {
+        return with_flag(ext != 0, [&](auto E) {
+            return launch_kernel<ngw_slot_rollout_kernel<decltype(V)::value, decltype(E)::value>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+        });
+    });
+}
+#endif  // NGW_HAS(15)

@@ -52,3 +52,12 @@ hipError_t with_board_rows(int BS, F&& f) {
     if (BS <= 20) return f(std::integral_constant<int, 20>{});
     return f(std::integral_constant<int, 32>{});
 }
+
+// the bytes per map piece of the kernels that move single rows by index (ngw_expand.inc's expand_move_row: snapshot expand and snapshot
+// rollout): 16 / 4 where S*S is a multiple of it - every row of every set is then that aligned -, 1 = odd S*S
+template <class F>
+hipError_t with_row_piece(int S2, F&& f) {
+    if (S2 % 16 == 0) return f(std::integral_constant<int, 16>{});
+    if (S2 % 4 == 0) return f(std::integral_constant<int, 4>{});
+    return f(std::integral_constant<int, 1>{});
+}

@@ -9,6 +9,8 @@
     env.fork(src)                              # env e := env src[e]
     pool = env.snapshot(4096)                  # a node pool: tree search keeps the states it grows
     e = pool.expand(parents, actions, children)    # slot children[j] := slot parents[j] stepped once with actions[j]; no env is touched
+    r = pool.rollout(parents, plans)               # score T-step action sequences from saved slots: ret / length / ended / info, nothing kept
+    r = pool.rollout(parents, plans, children)     # ... and keep the state each sequence ends in (a macro-action applied to a node)
 
 What a restored env does next: env e, when it next resets, draws from env e's OWN stream at its (restored or kept) episode counter.  Two
 forks of one slot share the rest of the current episode and differ from their next reset on; restoring the same env from the same slot
@@ -100,6 +102,52 @@ def check_expand(parents, actions, children, n_parents, capacity, n_actions, sam
         if both.size:
             raise ValueError("children: slot %d is also a parent of the same call (source and destination are one buffer)" % int(both[0]))
     return parents, actions, children, count
+
+
+def check_plan_ids(plans, n_actions, name='plans'):
+    """The host-side check of one action sequence per pair given as a list / numpy array [count, T]: integer dtype, two dimensions, at
+    least one step, every id in the action list (ValueError("<a> is not in list") otherwise, what step() raises).  Returns a contiguous int32
+    array [count, T]."""
+    if plans is None:
+        raise ValueError("%s: one action sequence per pair expected" % name)
+    a = np.asarray(plans)
+    if a.ndim == 2 and a.shape[0] == 0 and a.shape[1] >= 1:
+        return np.zeros(a.shape, np.int32)      # (an empty list has no dtype of its own)
+    if a.dtype.kind not in 'iu':
+        raise ValueError("%s: integer action ids expected, got dtype %s" % (name, a.dtype))
+    if a.ndim != 2 or a.shape[1] < 1:
+        raise ValueError("%s: action ids shaped [count, T] with T >= 1 expected, got shape %s" % (name, a.shape))
+    bad = (a < 0) | (a >= n_actions)
+    if bad.any():
+        raise ValueError("%d is not in list" % int(a[bad][0]))
+    return np.ascontiguousarray(a, np.int32)
+
+
+def check_rollout(parents, n_plans, children, n_parents, capacity, same_buffer, device_len=None):
+    """The host-side checks of one rollout call's index lists: parents index rows [0, n_parents) and may repeat (None = 0 .. count-1, which
+    must exist); children - None: nothing is kept - index slots [0, capacity) and must be distinct; both have the plans' length n_plans,
+    and - where source and destination are the same buffer - no child is also a parent.  device_len(x): the length of x when it is a
+    device tensor to be used in place (its values are then not checked), else None.  Returns (parents, children, count): contiguous int32
+    arrays, None, or the device tensors themselves."""
+    on_dev = (lambda x: None) if device_len is None else device_len
+    n_p, n_c = on_dev(parents), on_dev(children)
+    if n_p is None and parents is not None:
+        parents = check_indices(parents, n_parents, False, 'parents')
+        n_p = int(parents.size)
+    if n_c is None and children is not None:
+        children = check_indices(children, capacity, True, 'children')
+        n_c = int(children.size)
+    count = pair_count(pair_count(n_p, n_plans, n_plans), n_c, n_plans)
+    if parents is None and count > n_parents:
+        raise ValueError("parents: no list given and %d pairs for %d rows" % (count, n_parents))
+    if children is not None and count > capacity:
+        raise ValueError("children: %d pairs for a snapshot of %d slots" % (count, capacity))
+    if same_buffer and count and children is not None and on_dev(parents) is None and on_dev(children) is None:
+        hp = np.arange(count) if parents is None else parents
+        both = np.intersect1d(hp, children)
+        if both.size:
+            raise ValueError("children: slot %d is also a parent of the same call (source and destination are one buffer)" % int(both[0]))
+    return parents, children, count
 
 
 class Expansion(collections.namedtuple('Expansion', 'reward done result info')):
@@ -273,6 +321,85 @@ class Snapshot:
         Returns the Expansion shaped [len(parents), A]."""
         p, a, c, shape = all_actions_pairs(parents, first_child, self.env.n_actions)
         return self.expand(p, a, c, from_envs=from_envs, source=source, device=device).reshape(*shape)
+
+    def rollout(self, parents, plans, children=None, from_envs=False, source=None, device=False):
+        """Pair j: the state of parent parents[j] stepped on a private copy with the T actions of plans[j], by the rules evaluate_plans()
+        applies - every novelty, the env's autoreset setting and horizon; it stops at the first step that ends the episode (goal, FireWall
+        death, the horizon under autoreset), that step counts, and no reset ever runs.  Returns a PlanEval of 'ret' int32 (sum of the
+        executed steps' rewards), 'length' int32 (steps executed, 1 .. T), 'ended' bool and 'info' uint32 (the last executed step's word;
+        .goal / .died), each [count].
+        children=None: nothing is kept - a pure evaluation (the leaf simulation of a tree search).  Otherwise slot[children[j]] := the row as
+        the last executed step leaves it, as expand() defines a child (for a stopped pair: the state the episode ended in; the episode
+        counter is the parent's) - a macro-action of T steps applied to a node.  children: a list / tensor of distinct slots of this
+        snapshot; where source and destination are one buffer they must be disjoint from the parents.
+        parents, source and from_envs mean what they mean in expand(): slots of `source` (default: this snapshot) or, with from_envs=True,
+        the env's current states; parents may repeat, None means 0 .. count-1.
+        plans: an integer array [count, T] in host memory - validated here (an id outside the action list raises the ValueError step() raises
+        and nothing launches) and uploaded step-major; or a contiguous torch int32 tensor [T, count] on the env's device, used in place and
+        unvalidated (an id outside the list is a no-op step of reward 0 that counts in 'length' and raises the sticky F_INVALID_ACTION while
+        the pair still runs).  Index tensors on the device are used in place too: an index out of range skips that pair (F_BAD_INDEX, its
+        reports stay 0).  Nothing is committed: no env, no mask, no lookahead table, no prepared episode and no slot but the children
+        changes, and the number of pairs is not bound by num_envs.  One kernel launch.
+        device=True: the results as torch tensors on the env's device ('info' int32), ordered behind the launch on torch's current stream -
+        no copy, no host wait; otherwise numpy arrays after one sync."""
+        import torch
+        from .vec_env import PlanEval
+        env = self.env
+        self._open()
+        if source is not None and from_envs:
+            raise ValueError("rollout: give either source or from_envs")
+        src = self if source is None else source
+        if not from_envs:
+            if not isinstance(src, Snapshot):
+                raise ValueError("source: a Snapshot expected")
+            src._open()
+            if src.env is not env:
+                raise ValueError("source: a snapshot of another env")
+        n_parents = env.num_envs if from_envs else src.capacity
+        dev = torch.device('cuda:%d' % env.device)
+
+        def device_len(x):
+            if not isinstance(x, torch.Tensor):
+                return None
+            if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
+                raise ValueError("a contiguous one-dimensional int32 tensor on %s expected" % dev)
+            return int(x.numel())
+        if isinstance(plans, torch.Tensor):
+            if plans.dtype != torch.int32 or plans.dim() != 2 or not plans.is_contiguous() or plans.device != dev or plans.shape[0] < 1:
+                raise ValueError("plans: a contiguous int32 tensor [T, count] on %s expected" % dev)
+            steps, n_plans, a = int(plans.shape[0]), int(plans.shape[1]), plans
+        else:
+            a = check_plan_ids(plans, env.n_actions)
+            n_plans, steps = int(a.shape[0]), int(a.shape[1])
+            a = np.ascontiguousarray(a.T)       # step-major [T, count]: 64 lanes read consecutive addresses
+        p, c, count = check_rollout(parents, n_plans, children, n_parents, self.capacity, not from_envs and src is self, device_len)
+        ptr, uploaded = [], []
+        for x in (p, a, c):
+            if isinstance(x, np.ndarray):
+                x = torch.from_numpy(x).to(dev)
+                uploaded.append(x)
+            ptr.append(C.c_void_p(x.data_ptr()) if x is not None and count else None)
+        ret = torch.zeros(count, dtype=torch.int32, device=dev)
+        length = torch.zeros(count, dtype=torch.int32, device=dev)
+        ended = torch.zeros(count, dtype=torch.uint8, device=dev)
+        info = torch.zeros(count, dtype=torch.int32, device=dev)
+        if self._keep:
+            env.sync()                          # (the previous call has read its lists: they may be released now)
+            self._keep = None
+        if count:
+            # uploads, zero fills and the caller's own tensors are work of torch's current stream, the launch runs on the env's: it waits for them
+            env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, True)
+            _cabi.check(_cabi.lib().ngw_snapshot_rollout(env._h, None if from_envs else src._s, ptr[0], ptr[1], int(count), steps,
+                                                         None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
+                                                         C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr())))
+            self._keep = uploaded or None
+        if device:
+            if count:
+                env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, False)
+            return PlanEval(ret, length, ended.view(torch.bool), info)
+        env.sync()
+        self._keep = None
+        return PlanEval(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32))
 
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""

@@ -45,7 +45,7 @@ extern "C" {
 /* device-side sticky error flags (ngw_error_flags) */
 #define NGW_F_INVALID_ACTION 1u
 #define NGW_F_PLACEMENT 2u
-#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand: an env or slot index outside its range (that copy / pair was skipped) */
+#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout: an env or slot index outside its range (that copy / pair was skipped) */
 
 /* action kinds (act_kind[]); act_arg[] = recipe index (CRAFT) or item id (SELECT) */
 enum { NGW_ACT_FORWARD = 0, NGW_ACT_LEFT = 1, NGW_ACT_RIGHT = 2, NGW_ACT_BREAK = 3, NGW_ACT_PLACE = 4,
@@ -509,6 +509,49 @@ int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t coun
  * a wavefront's 64 rows there, the fused rollouts' limit). */
 int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, ngw_snapshot* dst,
                         const int32_t* dst_slots_dev, int64_t count, int32_t* reward_dev, uint8_t* done_dev, uint32_t* info_dev);
+
+/* Snapshot rollout: roll action sequences out from saved states; optionally keep the end state.  It closes the gap between ngw_plan_eval
+ * (T-step sequences, but only from the envs' current states, and the stepped state is thrown away) and ngw_snapshot_expand (any saved slot, the
+ * stepped state kept, but exactly one step): the leaf simulation of a tree search that keeps its nodes in a snapshot pool, and the macro-action
+ * of T steps applied to a node.
+ * For j < count: the parent is row src_idx[j] of snapshot `src`, or, with src == NULL, the handle's env src_idx[j] (its current state).  A NULL
+ * index list means 0 .. count-1, as in ngw_snapshot_expand.  The action of pair j at step t is actions_dev[t * pair_stride + j], int32 in device
+ * memory, pair_stride >= count (step-major: 64 lanes read consecutive addresses).
+ * The pair is stepped from its parent on a private copy by exactly ngw_plan_eval's rules: the handle's spec, every novelty and wrapper
+ * predicate, and its autoreset setting and horizon apply; it STOPS at the first step whose `done` would be 1 - the goal (including the sticky
+ * done of a parent that already holds the goal item, with autoreset off), a FireWall death, or the horizon under autoreset -, that ending step
+ * counts, and no reset ever runs.
+ * ret[j] (int32: the sum of the executed steps' rewards), length[j] (int32: steps executed, 1 .. n_steps), ended[j] (uint8: the pair stopped at
+ * an episode end) and info[j] (uint32: the NGW_INFO_* word of the last executed step) - device memory, [count] - are as ngw_plan_eval defines
+ * them.  Any of the four pointers may be NULL.
+ * With dst != NULL, slot dst_slots[j] of `dst` (dst_slots == NULL: slots 0 .. count-1) receives the full seven-array row as the LAST EXECUTED
+ * step leaves it, by ngw_snapshot_expand's definition of a child: map, agent_location, agent_facing_id, inventory and selected carry the
+ * steps' effects, step_count is as the steps left it, episode is the parent's, and for a stopped pair the row is the state the episode ended
+ * in.  dst == NULL keeps nothing - a pure evaluation -, and dst_slots must then be NULL as well.
+ * An action id outside [0, n_actions) follows the plan convention: the step leaves the private state untouched, adds reward 0, counts in
+ * `length`, has info word 0, and raises the sticky NGW_F_INVALID_ACTION only while the pair is still running.
+ * A parent or destination index out of range follows ngw_snapshot_expand's convention: the pair is skipped - nothing is stored for it, its
+ * reports are left untouched -, the sticky NGW_F_BAD_INDEX is raised, and nothing is ever addressed with the bad index.
+ * Parents may repeat; the destination slots of one call must be distinct.  src == dst is allowed when no destination slot of the call is also a
+ * parent of the same call.  Device lists are used in place, unchecked beyond range: a violated rule leaves those slots' contents unspecified
+ * and never causes an out-of-bounds access.
+ * Nothing is committed - ngw_snapshot_expand's list holds word for word: every byte of every env's state, the last step's reward / done / info,
+ * the prepared next episodes (no step counts against the refill cadence), the mask buffer and the lookahead table and whether each is current,
+ * the lidar rows, the bit rows, the host mirrors, the rollout output rows and accumulators, the terminal-capture side set, and every slot of
+ * every snapshot that the call does not name as a destination are what they were.  Because no reset runs, the call is allowed while terminal
+ * capture is on.
+ * One kernel launch, enqueued on the handle's stream; does not wait.  A captured graph stays valid.  count == 0 is a no-op.
+ * Two identities hold:
+ *   - n_steps == 1 with dst given: the children and the reports equal ngw_snapshot_expand's for the same pairs, ret = its reward and
+ *     ended = its done (length is 1);
+ *   - src == NULL, dst == NULL and src_idx = the envs 0 .. n_envs-1: the reports equal the column ngw_plan_eval computes for the same plan.
+ * NGW_E_INVALID_ARG: a NULL handle or NULL actions; n_steps < 1; count < 0; pair_stride < count; dst == NULL with all four report pointers NULL
+ * (nothing to do); dst == NULL with dst_slots != NULL; a src or dst that is not an open snapshot of this handle; count above dst's capacity;
+ * src_idx == NULL with count above the source's row count (src's capacity, or n_envs); maps that do not fit LDS (the kernel keeps a
+ * wavefront's 64 rows there, the fused rollouts' limit). */
+int ngw_snapshot_rollout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
+                         ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev,
+                         uint32_t* info_dev);
 
 /* One-step lookahead tables: every action's outcome for every env, without taking a step.
  * For a handle with A = n_actions the table of the CURRENT state is three arrays - reward int32, done uint8, info uint32 (the NGW_INFO_* packing).
