@@ -4,7 +4,8 @@
 // episodes, as ngw_reset does.  An expand (ngw_expand.inc) steps rows of the state slab or of a snapshot into slots of a snapshot: it commits
 // nothing, so it neither calls state_written() nor touches anything the handle derives from its state, and counts no steps against the
 // prepared-episode cadence (no reset runs).  A rollout (ngw_slot_rollout.inc) steps such rows through a whole action sequence and keeps the end
-// state, the numbers, or both: it commits nothing either.
+// state, the numbers, or both: it commits nothing either.  The slot observations (ngw_slot_observe.inc) read saved rows and write the caller's
+// buffers: lidar rows, agent views, action masks of saved states.  They commit nothing, and leave the env's own observation buffers alone.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -46,6 +47,15 @@ int move_rows(ngw_handle* h, bool copies, const NgwSnapRows& src, int64_t src_ro
     a.count = (int32_t)count; a.src_rows = (int32_t)src_rows; a.dst_rows = (int32_t)dst_rows;
     a.S2 = h->proto.S2; a.K = h->proto.K; a.keep_episode = keep_episode ? 1 : 0;
     HIP_TRY(ngw_snapshot_launch(&a, h->stream));
+    return NGW_OK;
+}
+
+// what the three slot observations check alike (before anything touches the stream)
+int slot_obs_args(const ngw_handle* h, const ngw_snapshot* s, const void* out, const int32_t* slots_dev, int64_t count, const char* what) {
+    if (!h || !s || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (count < 0 || count > 0x7FFFFFFFll) return fail(NGW_E_INVALID_ARG, "%s of %lld slots", what, (long long)count);
+    if (!slots_dev && count > s->cap) return fail(NGW_E_INVALID_ARG, "%s of %lld slots from a snapshot of %lld slots", what, (long long)count, (long long)s->cap);
     return NGW_OK;
 }
 
@@ -180,6 +190,48 @@ int ngw_snapshot_rollout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_id
     x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev;
     x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
     HIP_TRY(ngw_slot_rollout_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
+    return NGW_OK;
+}
+
+int ngw_snapshot_lidar(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, int64_t count, void* rows_dev) {
+    if (int rc = slot_obs_args(h, s, rows_dev, slots_dev, count, "lidar observation")) return rc;
+    if (!h->lidar_len) return fail(NGW_E_INVALID_ARG, "ngw_snapshot_lidar before ngw_lidar_configure");
+    if (!h->lidar_lds) return fail(NGW_E_INVALID_ARG, "map_size %d: the lidar observation keeps a wavefront's 64 maps in LDS (> 160 KiB)", h->proto.S);
+    if (int rc = enter(h)) return rc;
+    if (count == 0) return NGW_OK;
+    NgwLaunch a = h->lidar_proto;                     // the stand-alone launch's LDS layout and the current row format, whichever form the env's fused path uses
+    a.b = h->b;
+    a.lout = static_cast<int32_t*>(rows_dev);
+    NgwSlotObs x{};
+    x.src = s->r; x.slots = slots_dev; x.flags = h->b.flags; x.count = (int32_t)count; x.rows = (int32_t)s->cap;
+    HIP_TRY(ngw_slot_lidar_launch(&a, &x, h->lidar_lds, h->stream));
+    return NGW_OK;
+}
+
+int ngw_snapshot_agent_view(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, int64_t count, int view_size, int8_t* view_dev, int32_t* facing_dev,
+                            int32_t* inv_dev) {
+    const void* any = view_dev ? (const void*)view_dev : (facing_dev ? (const void*)facing_dev : (const void*)inv_dev);
+    if (int rc = slot_obs_args(h, s, any, slots_dev, count, "agent view")) return rc;
+    if (view_size < 1 || view_size > 127) return fail(NGW_E_INVALID_ARG, "view_size must be in 1..127");
+    const size_t W = 2 * (size_t)view_size + 1, bytes = (size_t)count * W * W;
+    if (bytes + 4 > 0xffffffffull) return fail(NGW_E_INVALID_ARG, "agent view of %zu B exceeds the 4 GiB index range", bytes);
+    if (int rc = enter(h)) return rc;
+    if (count == 0) return NGW_OK;
+    NgwSlotObs x{};
+    x.src = s->r; x.slots = slots_dev; x.flags = h->b.flags; x.count = (int32_t)count; x.rows = (int32_t)s->cap;
+    x.view = reinterpret_cast<uint32_t*>(view_dev); x.facing = facing_dev; x.inv = inv_dev;
+    x.n_dwords = (uint32_t)((bytes + 3) / 4); x.S = h->proto.S; x.K = h->proto.K; x.V = view_size;
+    HIP_TRY(ngw_slot_view_launch(&x, h->stream));
+    return NGW_OK;
+}
+
+int ngw_snapshot_action_mask(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, int64_t count, uint64_t* masks_dev) {
+    if (int rc = slot_obs_args(h, s, masks_dev, slots_dev, count, "action masks")) return rc;
+    if (int rc = enter(h)) return rc;
+    if (count == 0) return NGW_OK;
+    NgwSlotObs x{};
+    x.src = s->r; x.slots = slots_dev; x.flags = h->b.flags; x.count = (int32_t)count; x.rows = (int32_t)s->cap;
+    HIP_TRY(ngw_slot_mask_launch(h->dspec, &x, h->proto.S, h->proto.K, h->ext, masks_dev, h->stream));
     return NGW_OK;
 }
 

@@ -506,4 +506,34 @@ extern "C"
 #endif
 hipError_t ngw_slot_rollout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream);
 
+/* Slot observations (ngw_slot_observe.inc, ngw_abi_snapshot.cpp): observations and action masks of SAVED states, gathered by slot index. Output
+ * row j of a call describes row slots[j] of `src` (a snapshot; a NULL list = j itself).  An index outside [0, rows) is never used as an address:
+ * its output row is all zeros and NGW_F_BAD_INDEX is raised in *flags.  Nothing but the output rows and the flags word is stored.  The three
+ * kernels share the struct; the fields behind `rows` are the agent-view gather's. */
+struct NgwSlotObs {
+    NgwSnapRows src;
+    const int32_t* slots;
+    uint32_t* flags;
+    int32_t count, rows;
+    uint32_t* view;       /* [count][W][W] int8 as n_dwords dwords, or nullptr */
+    int32_t* facing;      /* [count], or nullptr */
+    int32_t* inv;         /* [count][K], or nullptr */
+    uint32_t n_dwords, magicW;
+    int32_t S, K, V;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+/* a = the stand-alone lidar launch's layout (ngw_lidar_configure) with a.lout = the caller's rows ([count rounded up to 64] rows of the current format) */
+hipError_t ngw_slot_lidar_launch(const NgwLaunch* a, const struct NgwSlotObs* x, size_t lds_bytes, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_slot_view_launch(const struct NgwSlotObs* x, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+/* out[j] = the mask word of slot slots[j] ([count] words; ngw_mask.inc's predicate) */
+hipError_t ngw_slot_mask_launch(const NgwDevSpec* dspec, const struct NgwSlotObs* x, int S, int K, int ext, uint64_t* out, hipStream_t stream);
+
 #endif

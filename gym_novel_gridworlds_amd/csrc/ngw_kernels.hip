@@ -30,7 +30,7 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file SIXTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file SEVENTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
@@ -39,6 +39,7 @@
 //   with fused masks; 1 / 6 / 7 hold the staged ones)
 //   11: device-side snapshots (ngw_snapshot.inc)   12: one-step lookahead tables (ngw_lookahead.inc)   13: plan evaluation (ngw_plans.inc)
 //   14: snapshot expand (ngw_expand.inc)   15: snapshot rollout (ngw_slot_rollout.inc; it shares ngw_expand.inc's row mover)
+//   16: slot observations (ngw_slot_observe.inc: lidar rows, agent views, action masks of saved states; the lidar one shares the row mover too)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -390,11 +391,14 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #if NGW_HAS(13)
 #include "ngw_plans.inc"
 #endif
-#if NGW_HAS(14) || NGW_HAS(15)
+#if NGW_HAS(14) || NGW_HAS(15) || NGW_HAS(16)
 #include "ngw_expand.inc"
 #endif
 #if NGW_HAS(15)
 #include "ngw_slot_rollout.inc"
+#endif
+#if NGW_HAS(16)
+#include "ngw_slot_observe.inc"
 #endif
 
 // ---------------------------------------------------------------- LidarInFront observation kernel (stand-alone launch)
@@ -854,3 +858,34 @@ extern "C" hipError_t ngw_slot_rollout_launch(const NgwDevSpec* dspec, const Ngw
     });
 }
 #endif  // NGW_HAS(15)
+
+#if NGW_HAS(16)
+// slot observations (ngw_slot_observe.inc).  The lidar rows: a = the stand-alone lidar launch's layout with a.lout = the caller's rows; one wave per 64 pairs
+extern "C" hipError_t ngw_slot_lidar_launch(const NgwLaunch* a, const NgwSlotObs* x, size_t lds_bytes, hipStream_t stream) {
+    if (x->count <= 0 || x->rows < 1 || a->S < 3 || a->S > NGW_MAX_MAP_SIZE || a->K < 1 || a->K > NGW_MAX_ITEMS || a->MS < a->S2 || (a->MS & 3) || !x->flags ||
+        !x->src.map || !a->lout || !a->lcfg || a->l_rb < 1)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((int64_t)x->count + NGW_EPB - 1) / NGW_EPB)), block(NGW_EPB);
+    return with_row_piece(a->S2, [&](auto V) { return launch_kernel<ngw_slot_lidar_kernel<decltype(V)::value>>(grid, block, lds_bytes, stream, *a, *x); });
+}
+// the action masks: [count] words at `out`
+extern "C" hipError_t ngw_slot_mask_launch(const NgwDevSpec* dspec, const NgwSlotObs* x, int S, int K, int ext, uint64_t* out, hipStream_t stream) {
+    if (x->count <= 0 || x->rows < 1 || S < 3 || S > NGW_MAX_MAP_SIZE || K < 1 || K > NGW_MAX_ITEMS || !x->flags || !x->src.map || !out) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((int64_t)x->count + NGW_EPB - 1) / NGW_EPB)), block(NGW_EPB);
+    return with_flag(ext != 0, [&](auto E) { return launch_kernel<ngw_slot_mask_kernel<decltype(E)::value>>(grid, block, 0, stream, dspec, *x, S, K, out); });
+}
+// the agent views (slice 0) and facing / inventory (slice 1); magicW is set here
+extern "C" hipError_t ngw_slot_view_launch(const NgwSlotObs* x, hipStream_t stream) {
+    if (x->count <= 0 || x->rows < 1 || x->S < 3 || x->S > NGW_MAX_MAP_SIZE || x->K < 1 || x->K > NGW_MAX_ITEMS || x->V < 1 || x->V > 127 || !x->flags ||
+        !x->src.map || (!x->view && !x->facing && !x->inv))
+        return hipErrorInvalidValue;
+    NgwSlotObs p = *x;
+    const uint32_t W = 2u * (uint32_t)p.V + 1u;
+    p.magicW = (uint32_t)((0x100000000ull + W - 1) / W);                  // exact for operands < W * W
+    uint64_t most = (uint64_t)p.count * (p.inv ? (uint64_t)p.K : 1u);
+    if (p.view && p.n_dwords > most) most = p.n_dwords;
+    uint64_t blocks = (most + 255u) / 256u;
+    if (blocks > (1u << 20)) blocks = 1u << 20;                           // (both slices are grid-stride loops)
+    return launch_kernel<ngw_slot_view_kernel>(dim3((unsigned)blocks, 2u), dim3(256), 0, stream, p);
+}
+#endif  // NGW_HAS(16)

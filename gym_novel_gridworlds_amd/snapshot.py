@@ -11,6 +11,9 @@
     e = pool.expand(parents, actions, children)    # slot children[j] := slot parents[j] stepped once with actions[j]; no env is touched
     r = pool.rollout(parents, plans)               # score T-step action sequences from saved slots: ret / length / ended / info, nothing kept
     r = pool.rollout(parents, plans, children)     # ... and keep the state each sequence ends in (a macro-action applied to a node)
+    obs = pool.lidar_observation(nodes)            # look at saved slots without restoring them: LidarInFront rows,
+    view = pool.agent_view(nodes)                  # ... the AgentMap observation,
+    ok = pool.action_masks(nodes)                  # ... and the valid-action masks; no env is touched
 
 What a restored env does next: env e, when it next resets, draws from env e's OWN stream at its (restored or kept) episode counter.  Two
 forks of one slot share the rest of the current episode and differ from their next reset on; restoring the same env from the same slot
@@ -148,6 +151,20 @@ def check_rollout(parents, n_plans, children, n_parents, capacity, same_buffer, 
         if both.size:
             raise ValueError("children: slot %d is also a parent of the same call (source and destination are one buffer)" % int(both[0]))
     return parents, children, count
+
+
+def check_slots(slots, capacity, device_len=None):
+    """The host-side checks of the slot list of one slot observation (lidar_observation / agent_view / action_masks of a Snapshot): None = every
+    slot, 0 .. capacity-1; a list / numpy array indexes slots [0, capacity) and may repeat (its length is not bound by the capacity).
+    device_len(x): the length of x when it is a device tensor to be used in place (its values are then not checked), else None.  Returns
+    (slots, count): a contiguous int32 array, None, or the device tensor itself."""
+    if slots is None:
+        return None, int(capacity)
+    n = None if device_len is None else device_len(slots)
+    if n is not None:
+        return slots, int(n)
+    slots = check_indices(slots, capacity, False, 'slots')
+    return slots, int(slots.size)
 
 
 class Expansion(collections.namedtuple('Expansion', 'reward done result info')):
@@ -400,6 +417,109 @@ class Snapshot:
         env.sync()
         self._keep = None
         return PlanEval(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32))
+
+    # ------------------------------------------------------------------ slot observations (include/ngw.h ngw_snapshot_lidar / _agent_view / _action_mask)
+    def _slots_arg(self, slots):
+        """`slots` of a slot observation, checked and uploaded -> (device pointer or None, count, torch device, the uploaded tensor or None)."""
+        import torch
+        env = self.env
+        self._open()
+        dev = torch.device('cuda:%d' % env.device)
+
+        def device_len(x):
+            if not isinstance(x, torch.Tensor):
+                return None
+            if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
+                raise ValueError("slots: a contiguous one-dimensional int32 tensor on %s expected" % dev)
+            return int(x.numel())
+        s, count = check_slots(slots, self.capacity, device_len)
+        uploaded = None
+        if isinstance(s, np.ndarray):
+            s = uploaded = torch.from_numpy(s).to(dev)
+        return (C.c_void_p(s.data_ptr()) if s is not None and count else None), count, dev, uploaded
+
+    def _enqueue(self, call, count, uploaded, device):
+        """One slot observation's launch, ordered as expand() orders its own: the env's stream waits for torch's current one (uploads, the
+        allocations of the outputs, the caller's own tensors), and behind the launch either torch's stream waits for the env's (device=True:
+        no host wait) or the host does."""
+        import torch
+        env = self.env
+        if self._keep:
+            env.sync()                          # (the previous call has read its lists: they may be released now)
+            self._keep = None
+        if count:
+            env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, True)
+            _cabi.check(call())
+            self._keep = [uploaded] if uploaded is not None else None
+        if device:
+            if count:
+                env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, False)
+        else:
+            env.sync()
+            self._keep = None
+
+    def lidar_observation(self, slots=None, device=False):
+        """The LidarInFront observation of saved slots, as env.lidar_observation() returns it for envs: [count, L] in the configured dtype, or the
+        pair (beams uint8 [count, B * NC], inventory int16 [count, NI]) with the packed format.  Row j is slot slots[j] (None: every slot),
+        bit-identical to what an env holding that state would observe.  Nothing is committed: no env is touched, the env's own lidar rows
+        included.  One kernel launch (always the march over maps staged in LDS, whichever form the env's fused path uses).
+        slots: None, a list / numpy array (checked here; slots may repeat and their number is not bound by the capacity), or a contiguous torch
+        int32 tensor on the env's device, used in place and unchecked: an index out of range gives an all-zero row and raises the sticky
+        F_BAD_INDEX (error_flags()).  device=True: torch tensors on the env's device, ordered behind the launch on torch's current stream - no
+        copy, no host wait; otherwise numpy arrays after one sync."""
+        import torch
+        env = self.env
+        self._open()
+        if env.lidar is None:
+            raise ValueError("lidar_observation before env.lidar_configure")
+        ptr, count, dev, uploaded = self._slots_arg(slots)
+        pad = (count + 63) // 64 * 64           # the wave stores whole 64-row tiles
+        if env.lidar_packed:
+            rows = torch.empty((pad, env.lidar_row_bytes), dtype=torch.uint8, device=dev)
+        else:
+            rows = torch.empty((pad, env.lidar_len), dtype=torch.int32 if env.lidar_dtype == np.dtype(np.int32) else torch.int16, device=dev)
+        self._enqueue(lambda: _cabi.lib().ngw_snapshot_lidar(env._h, self._s, ptr, count, C.c_void_p(rows.data_ptr())), count, uploaded, device)
+        rows = rows[:count]
+        if not device:
+            rows = rows.cpu().numpy()
+        return env._lidar_split(rows) if env.lidar_packed else rows
+
+    def agent_view(self, slots=None, view_size=5, device=False):
+        """The AgentMap observation of saved slots: {'agent_map': int8 [count, W, W] with W = 2 * view_size + 1 (the map around each slot's agent,
+        0 outside the map), 'agent_facing_id': int32 [count], 'inventory_items_quantity': int32 [count, K]}, gathered in one kernel launch.
+        Nothing is committed.  slots and device: as in lidar_observation (an index out of range: an all-zero row, F_BAD_INDEX)."""
+        import torch
+        env = self.env
+        V = int(view_size)
+        W = 2 * V + 1
+        if not 1 <= V <= 127:
+            raise ValueError("view_size must be in 1..127")
+        ptr, count, dev, uploaded = self._slots_arg(slots)
+        flat = torch.empty((count * W * W + 3) // 4 * 4, dtype=torch.int8, device=dev)      # (the gather stores whole dwords)
+        facing = torch.empty(count, dtype=torch.int32, device=dev)
+        inv = torch.empty((count, env.n_items), dtype=torch.int32, device=dev)
+        self._enqueue(lambda: _cabi.lib().ngw_snapshot_agent_view(env._h, self._s, ptr, count, V, C.c_void_p(flat.data_ptr()), C.c_void_p(facing.data_ptr()),
+                                                                  C.c_void_p(inv.data_ptr())), count, uploaded, device)
+        view = flat[:count * W * W].view(count, W, W)
+        if not device:
+            view, facing, inv = view.cpu().numpy(), facing.cpu().numpy(), inv.cpu().numpy()
+        return {'agent_map': view, 'agent_facing_id': facing, 'inventory_items_quantity': inv}
+
+    def action_masks(self, slots=None, device=False):
+        """The valid-action masks of saved slots: bool [count, n_actions], True where step(a) from slot slots[j]'s state would report
+        info['result'] == True under every novelty and wrapper - env.action_masks()'s predicate, fed from the saved row.  Nothing is
+        committed: the env's own mask buffer is not touched and stays as current as it was.  One kernel launch.  slots and device: as in
+        lidar_observation (an index out of range: an all-False row, F_BAD_INDEX)."""
+        import torch
+        from .vec_env import unpack_action_masks
+        env = self.env
+        ptr, count, dev, uploaded = self._slots_arg(slots)
+        words = torch.empty(count, dtype=torch.int64, device=dev)
+        self._enqueue(lambda: _cabi.lib().ngw_snapshot_action_mask(env._h, self._s, ptr, count, C.c_void_p(words.data_ptr())), count, uploaded, device)
+        if device:
+            bits = torch.arange(env.n_actions, device=words.device, dtype=torch.int64)
+            return ((words[:, None] >> bits) & 1).bool()
+        return unpack_action_masks(words.cpu().numpy().view(np.uint64), env.n_actions)
 
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""

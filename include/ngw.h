@@ -45,7 +45,7 @@ extern "C" {
 /* device-side sticky error flags (ngw_error_flags) */
 #define NGW_F_INVALID_ACTION 1u
 #define NGW_F_PLACEMENT 2u
-#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout: an env or slot index outside its range (that copy / pair was skipped) */
+#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros) */
 
 /* action kinds (act_kind[]); act_arg[] = recipe index (CRAFT) or item id (SELECT) */
 enum { NGW_ACT_FORWARD = 0, NGW_ACT_LEFT = 1, NGW_ACT_RIGHT = 2, NGW_ACT_BREAK = 3, NGW_ACT_PLACE = 4,
@@ -552,6 +552,38 @@ int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx
 int ngw_snapshot_rollout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
                          ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev,
                          uint32_t* info_dev);
+
+/* Slot observations: the observation and the valid-action mask of SAVED states, gathered by slot index - the read-only side of a node pool
+ * (policy- or value-guided tree search, beam search with a learned scorer, cell descriptors of an archive: every node that is evaluated needs
+ * its observation and its mask, and restoring it into an env to look at it would commit state).
+ * `s` is an open snapshot of `h`; slots_dev is an int32 list in DEVICE memory, NULL means 0 .. count-1.  Slots may repeat, and count is not bound
+ * by the capacity unless slots_dev == NULL.  Output row j describes slot slots[j].
+ *   ngw_snapshot_lidar        row j of rows_dev is the LidarInFront observation of slot slots[j] under the handle's current configuration
+ *                             (ngw_lidar_configure) and current row format (ngw_lidar_set_output: 32 / 16 / 8 = packed, ngw_lidar_row_layout), bit-identical to
+ *                             what ngw_lidar + ngw_lidar_device_ptr give for an env that holds that state.  rows_dev has room for `count` ROUNDED UP TO A
+ *                             MULTIPLE OF 64 rows; rows past count are unspecified.  It always runs the march over maps staged in LDS (the stand-alone
+ *                             launch's form, whichever form the env's fused path uses: slots have no occupancy bit rows and get none).
+ *                             NGW_E_INVALID_ARG before ngw_lidar_configure, and where ngw_lidar is refused (maps that do not fit LDS).
+ *   ngw_snapshot_agent_view   view_dev is int8 [count][W][W], W = 2 * view_size + 1, 0 outside the map: the AgentMap window of each slot; view_size has
+ *                             ngw_agent_view's limits (1 .. 127, and the byte count within the 4 GiB index range); the buffer is rounded up to a whole
+ *                             dword.  facing_dev [count] and inv_dev [count][n_items] are the other two entries of that wrapper's observation, gathered in
+ *                             the same launch.  Any of the three pointers may be NULL, but not all of them.
+ *   ngw_snapshot_action_mask  masks_dev[j] is the uint64 mask of slot slots[j]: bit a is set exactly when step(a) from that state would report result = 1
+ *                             under the handle's spec, every novelty and wrapper predicate included (the predicate of ngw_action_mask); bits >=
+ *                             n_actions are 0.
+ * A slot index outside [0, capacity) is never used as an address: its output row is all zeros (mask 0, facing 0), and the sticky NGW_F_BAD_INDEX is
+ * raised.  count == 0 is a no-op.  Each call is ONE kernel launch, enqueued on the handle's stream; it does not wait.
+ * Nothing is committed - ngw_snapshot_expand's list holds word for word: every byte of every env's state, the last step's reward / done / info,
+ * the prepared next episodes, the mask buffer and the lookahead table and whether each is current, the lidar rows, the bit rows, the host mirrors,
+ * the rollout output rows and accumulators, the terminal-capture side set, and every slot of every snapshot are what they were.  In addition the
+ * env's own lidar buffer (ngw_lidar_device_ptr), agent-view buffer and mask buffer are not touched, and whether each is current does not change.
+ * A captured graph stays valid.  The calls are allowed with the fused lidar, the bit-row form, masks-in-step and terminal capture on.
+ * NGW_E_INVALID_ARG: a NULL handle, snapshot or output (agent view: all three outputs NULL); a snapshot that is not an open snapshot of this
+ * handle; count < 0; slots_dev == NULL with count above the capacity. */
+int ngw_snapshot_lidar(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, int64_t count, void* rows_dev);
+int ngw_snapshot_agent_view(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, int64_t count, int view_size, int8_t* view_dev, int32_t* facing_dev,
+                            int32_t* inv_dev);
+int ngw_snapshot_action_mask(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, int64_t count, uint64_t* masks_dev);
 
 /* One-step lookahead tables: every action's outcome for every env, without taking a step.
  * For a handle with A = n_actions the table of the CURRENT state is three arrays - reward int32, done uint8, info uint32 (the NGW_INFO_* packing).
