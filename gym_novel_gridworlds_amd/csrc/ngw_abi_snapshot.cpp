@@ -6,6 +6,7 @@
 // prepared-episode cadence (no reset runs).  A rollout (ngw_slot_rollout.inc) steps such rows through a whole action sequence and keeps the end
 // state, the numbers, or both: it commits nothing either.  The slot observations (ngw_slot_observe.inc) read saved rows and write the caller's
 // buffers: lidar rows, agent views, action masks of saved states.  They commit nothing, and leave the env's own observation buffers alone.
+// The state keys (ngw_keys.inc) hash rows of a snapshot or of the state slab into the caller's buffer: they commit nothing either.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -232,6 +233,22 @@ int ngw_snapshot_action_mask(ngw_handle* h, ngw_snapshot* s, const int32_t* slot
     NgwSlotObs x{};
     x.src = s->r; x.slots = slots_dev; x.flags = h->b.flags; x.count = (int32_t)count; x.rows = (int32_t)s->cap;
     HIP_TRY(ngw_slot_mask_launch(h->dspec, &x, h->proto.S, h->proto.K, h->ext, masks_dev, h->stream));
+    return NGW_OK;
+}
+
+int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev) {
+    if (!h || !keys_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!fields || (fields & ~NGW_KEY_ALL)) return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)fields);
+    const int64_t rows = s ? s->cap : h->n;
+    if (count < 0 || count > 0x7FFFFFFFll * NGW_EPB) return fail(NGW_E_INVALID_ARG, "state keys of %lld rows", (long long)count);
+    if (!idx_dev && count > rows) return fail(NGW_E_INVALID_ARG, "state keys of %lld rows from %lld %s", (long long)count, (long long)rows, s ? "slots" : "envs");
+    if (int rc = enter(h)) return rc;                 // (s == NULL: the one-env loop has ended, HBM holds the env's state - what ngw_snapshot_expand relies on)
+    if (count == 0) return NGW_OK;
+    NgwKeys x{};
+    x.src = s ? s->r : state_rows(h); x.idx = idx_dev; x.flags = h->b.flags; x.keys = keys_dev;
+    x.count = count; x.rows = (int32_t)rows; x.S2 = h->proto.S2; x.K = h->proto.K; x.fields = fields;
+    HIP_TRY(ngw_keys_launch(&x, h->stream));
     return NGW_OK;
 }
 

@@ -536,4 +536,21 @@ extern "C"
 /* out[j] = the mask word of slot slots[j] ([count] words; ngw_mask.inc's predicate) */
 hipError_t ngw_slot_mask_launch(const NgwDevSpec* dspec, const struct NgwSlotObs* x, int S, int K, int ext, uint64_t* out, hipStream_t stream);
 
+/* State keys (ngw_keys.inc, ngw_abi_snapshot.cpp): keys[j] = the 64-bit key (include/ngw.h, ngw_state_keys) of row idx[j] of `src` (a snapshot or the
+ * state slab; a NULL list = j itself) under the field selection `fields` (NGW_KEY_*).  An index outside [0, rows) is never used as an address: its
+ * key is 0 and NGW_F_BAD_INDEX is raised in *flags.  Nothing but keys[0 .. count) and the flags word is stored. */
+struct NgwKeys {
+    NgwSnapRows src;
+    const int32_t* idx;
+    uint32_t* flags;
+    uint64_t* keys;
+    int64_t count;
+    int32_t rows, S2, K;
+    uint32_t fields;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_keys_launch(const struct NgwKeys* x, hipStream_t stream);
+
 #endif

@@ -8,7 +8,8 @@
 //   ngw_abi_lookahead.cpp one-step lookahead tables: the lookahead kernel (ngw_lookahead.inc), staleness, the one-env loop's speculated records
 //   ngw_abi_plans.cpp    plan evaluation: candidate action sequences scored from the current state without committing a step (ngw_plans.inc)
 //   ngw_abi_snapshot.cpp device-side snapshots: save / restore / fork env states by index (ngw_snapshot.inc), expand saved states into new slots (ngw_expand.inc),
-//                        roll action sequences out from saved states (ngw_slot_rollout.inc), observe saved states by slot (ngw_slot_observe.inc)
+//                        roll action sequences out from saved states (ngw_slot_rollout.inc), observe saved states by slot (ngw_slot_observe.inc),
+//                        64-bit state keys of saved slots and live envs (ngw_keys.inc)
 //
 // Three rules hold in all of them:
 //   1. Guard first.  An entry point that uses the handle's stream or its device state starts with `if (int rc = enter(h)) return rc;`

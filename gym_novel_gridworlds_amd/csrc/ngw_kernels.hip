@@ -30,7 +30,7 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file SEVENTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file EIGHTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
@@ -40,6 +40,7 @@
 //   11: device-side snapshots (ngw_snapshot.inc)   12: one-step lookahead tables (ngw_lookahead.inc)   13: plan evaluation (ngw_plans.inc)
 //   14: snapshot expand (ngw_expand.inc)   15: snapshot rollout (ngw_slot_rollout.inc; it shares ngw_expand.inc's row mover)
 //   16: slot observations (ngw_slot_observe.inc: lidar rows, agent views, action masks of saved states; the lidar one shares the row mover too)
+//   17: state keys (ngw_keys.inc: 64-bit hashes of saved slots and live envs)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -399,6 +400,9 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #endif
 #if NGW_HAS(16)
 #include "ngw_slot_observe.inc"
+#endif
+#if NGW_HAS(17)
+#include "ngw_keys.inc"
 #endif
 
 // ---------------------------------------------------------------- LidarInFront observation kernel (stand-alone launch)
@@ -889,3 +893,15 @@ extern "C" hipError_t ngw_slot_view_launch(const NgwSlotObs* x, hipStream_t stre
     return launch_kernel<ngw_slot_view_kernel>(dim3((unsigned)blocks, 2u), dim3(256), 0, stream, p);
 }
 #endif  // NGW_HAS(16)
+
+#if NGW_HAS(17)
+// state keys (ngw_keys.inc): x->count keys of rows of x->src through the index list; one wave per 64 pairs
+extern "C" hipError_t ngw_keys_launch(const NgwKeys* x, hipStream_t stream) {
+    const int64_t blocks = (x->count + NGW_EPB - 1) / NGW_EPB;
+    if (x->count <= 0 || blocks > 0x7FFFFFFFll || x->rows < 1 || x->S2 < 9 || x->S2 > NGW_MAX_MAP_SIZE * NGW_MAX_MAP_SIZE || x->K < 1 || x->K > NGW_MAX_ITEMS ||
+        !x->fields || (x->fields & ~NGW_KEY_ALL) || !x->flags || !x->src.map || !x->keys)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(NGW_EPB);
+    return with_row_piece(x->S2, [&](auto V) { return launch_kernel<ngw_keys_kernel<decltype(V)::value>>(grid, block, 0, stream, *x); });
+}
+#endif  // NGW_HAS(17)

@@ -54,7 +54,7 @@ hipError_t with_board_rows(int BS, F&& f) {
 }
 
 // the bytes per map piece of the kernels that move single rows by index (ngw_expand.inc's expand_move_row: snapshot expand and snapshot
-// rollout): 16 / 4 where S*S is a multiple of it - every row of every set is then that aligned -, 1 = odd S*S
+// rollout; ngw_keys.inc's row reads): 16 / 4 where S*S is a multiple of it - every row of every set is then that aligned -, 1 = odd S*S
 template <class F>
 hipError_t with_row_piece(int S2, F&& f) {
     if (S2 % 16 == 0) return f(std::integral_constant<int, 16>{});

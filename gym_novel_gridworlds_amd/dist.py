@@ -14,6 +14,7 @@ behind each other, and the tensors handed out are safe to use on torch's current
 """
 
 from .vec_env import VecNovelGridworld
+from .state_keys import KEY_STATE
 
 
 def shard_range(global_num_envs, world, rank):
@@ -128,6 +129,11 @@ class ShardedVecNovelGridworld:
         """A device-side snapshot of this rank's shard (VecNovelGridworld.snapshot): rank-local, env indices are the shard's own - in
         save / restore and in expand / expand_all (from_envs=True: parents are the shard's envs 0 .. num_envs-1)."""
         return self.local.snapshot(capacity)
+
+    def state_keys(self, envs=None, fields=KEY_STATE, device=False):
+        """The state keys of this rank's shard (VecNovelGridworld.state_keys): `envs` are the shard's own indices; rank-local, no collective.
+        A key depends on the state alone, not on the env index or the rank, so keys compare across ranks."""
+        return self.local.state_keys(envs, fields, device)
 
     def fork(self, src, keep_episode=False):
         """Every LOCAL env e becomes a copy of local env src[e] (VecNovelGridworld.fork)."""

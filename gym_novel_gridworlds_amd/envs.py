@@ -19,6 +19,7 @@ import numpy as np
 
 from . import spaces
 from .spec import DIRECTION_ID, DIRECTION_STR, STEP_COSTS, EnvSpec
+from .state_keys import KEY_STATE
 from .vec_env import PLACEMENT_MESSAGE, VecNovelGridworld
 
 try:
@@ -323,6 +324,13 @@ class _NovelGridworldEnv(_EnvBase):
         vec = self._backend()
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
         return vec.evaluate_plans(a[None], device=device, copy=copy).row(0)
+
+    def state_key(self, fields=KEY_STATE):
+        """The 64-bit key of the current state as a Python int, computed on the device under the field selection `fields` (KEY_* bits,
+        default KEY_STATE); see VecNovelGridworld.state_keys and state_keys.py for the contract."""
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        return int(vec.state_keys(fields=fields)[0])
 
     def get_observation(self):
         assert not self.max_items < len(self.items), "Cannot have more than " + str(self.max_items) + " items"

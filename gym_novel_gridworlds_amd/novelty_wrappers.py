@@ -7,6 +7,7 @@ Accepts a single-env adapter (envs.py) - returns a wrapper that forwards reads t
 `VecNovelGridworld` / `ShardedVecNovelGridworld`, which is rebuilt IN PLACE on the edited spec and returned (the
 reference's wrappers mutate the env they wrap; a shard keeps its place in the global env index space)."""
 from .novelty import apply_novelty
+from .state_keys import KEY_STATE
 
 
 class NoveltyWrapper(object):
@@ -51,6 +52,9 @@ class NoveltyWrapper(object):
 
     def evaluate_plans(self, plans, device=False, copy=False):
         return self.env.evaluate_plans(plans, device=device, copy=copy)
+
+    def state_key(self, fields=KEY_STATE):
+        return self.env.state_key(fields)
 
     def render(self, mode='human', **kwargs):
         return self.env.render(mode, **kwargs)

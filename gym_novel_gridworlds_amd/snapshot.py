@@ -14,6 +14,8 @@
     obs = pool.lidar_observation(nodes)            # look at saved slots without restoring them: LidarInFront rows,
     view = pool.agent_view(nodes)                  # ... the AgentMap observation,
     ok = pool.action_masks(nodes)                  # ... and the valid-action masks; no env is touched
+    k = pool.keys(nodes)                           # 64-bit state keys: "are these two nodes the same state?" (state_keys.py: the contract)
+    first, inverse = pool.unique(nodes)            # ... and the groups of equal states among them
 
 What a restored env does next: env e, when it next resets, draws from env e's OWN stream at its (restored or kept) episode counter.  Two
 forks of one slot share the rest of the current episode and differ from their next reset on; restoring the same env from the same slot
@@ -24,6 +26,7 @@ import ctypes as C
 import numpy as np
 
 from . import _cabi
+from .state_keys import KEY_STATE, check_fields, unique_of_keys
 
 KEEP_EPISODE = 1          # include/ngw.h NGW_SNAP_KEEP_EPISODE
 
@@ -165,6 +168,46 @@ def check_slots(slots, capacity, device_len=None):
         return slots, int(n)
     slots = check_indices(slots, capacity, False, 'slots')
     return slots, int(slots.size)
+
+
+def index_arg(env, idx, limit, name):
+    """One index list of a call that reads rows by index (the slot observations, the state keys), checked and uploaded: None, a list / numpy
+    array (check_slots) or a contiguous torch int32 tensor on the env's device, used in place.  -> (device pointer or None, count, torch
+    device, the uploaded tensor or None)."""
+    import torch
+    dev = torch.device('cuda:%d' % env.device)
+
+    def device_len(x):
+        if not isinstance(x, torch.Tensor):
+            return None
+        if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
+            raise ValueError("%s: a contiguous one-dimensional int32 tensor on %s expected" % (name, dev))
+        return int(x.numel())
+    s, count = check_slots(idx, limit, device_len)
+    uploaded = None
+    if isinstance(s, np.ndarray):
+        s = uploaded = torch.from_numpy(s).to(dev)
+    return (C.c_void_p(s.data_ptr()) if s is not None and count else None), count, dev, uploaded
+
+
+def enqueue_ordered(env, holder, call, count, uploaded, device):
+    """One launch on the env's stream that reads and writes torch tensors: the env's stream waits for torch's current one (uploads, the
+    allocations of the outputs, the caller's own tensors), and behind the launch either torch's stream waits for the env's (device=True: no
+    host wait) or the host does.  `holder._keep` keeps an uploaded list alive until the next call of the holder has synchronised."""
+    import torch
+    if holder._keep:
+        env.sync()                              # (the previous call has read its lists: they may be released now)
+        holder._keep = None
+    if count:
+        env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, True)
+        _cabi.check(call())
+        holder._keep = [uploaded] if uploaded is not None else None
+    if device:
+        if count:
+            env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, False)
+    else:
+        env.sync()
+        holder._keep = None
 
 
 class Expansion(collections.namedtuple('Expansion', 'reward done result info')):
@@ -421,42 +464,12 @@ class Snapshot:
     # ------------------------------------------------------------------ slot observations (include/ngw.h ngw_snapshot_lidar / _agent_view / _action_mask)
     def _slots_arg(self, slots):
         """`slots` of a slot observation, checked and uploaded -> (device pointer or None, count, torch device, the uploaded tensor or None)."""
-        import torch
-        env = self.env
         self._open()
-        dev = torch.device('cuda:%d' % env.device)
-
-        def device_len(x):
-            if not isinstance(x, torch.Tensor):
-                return None
-            if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
-                raise ValueError("slots: a contiguous one-dimensional int32 tensor on %s expected" % dev)
-            return int(x.numel())
-        s, count = check_slots(slots, self.capacity, device_len)
-        uploaded = None
-        if isinstance(s, np.ndarray):
-            s = uploaded = torch.from_numpy(s).to(dev)
-        return (C.c_void_p(s.data_ptr()) if s is not None and count else None), count, dev, uploaded
+        return index_arg(self.env, slots, self.capacity, 'slots')
 
     def _enqueue(self, call, count, uploaded, device):
-        """One slot observation's launch, ordered as expand() orders its own: the env's stream waits for torch's current one (uploads, the
-        allocations of the outputs, the caller's own tensors), and behind the launch either torch's stream waits for the env's (device=True:
-        no host wait) or the host does."""
-        import torch
-        env = self.env
-        if self._keep:
-            env.sync()                          # (the previous call has read its lists: they may be released now)
-            self._keep = None
-        if count:
-            env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, True)
-            _cabi.check(call())
-            self._keep = [uploaded] if uploaded is not None else None
-        if device:
-            if count:
-                env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, False)
-        else:
-            env.sync()
-            self._keep = None
+        """One slot observation's launch, ordered as expand() orders its own (enqueue_ordered); this snapshot keeps the uploaded list."""
+        enqueue_ordered(self.env, self, call, count, uploaded, device)
 
     def lidar_observation(self, slots=None, device=False):
         """The LidarInFront observation of saved slots, as env.lidar_observation() returns it for envs: [count, L] in the configured dtype, or the
@@ -520,6 +533,30 @@ class Snapshot:
             bits = torch.arange(env.n_actions, device=words.device, dtype=torch.int64)
             return ((words[:, None] >> bits) & 1).bool()
         return unpack_action_masks(words.cpu().numpy().view(np.uint64), env.n_actions)
+
+    # ------------------------------------------------------------------ state keys (include/ngw.h ngw_state_keys; state_keys.py)
+    def keys(self, slots=None, fields=KEY_STATE, device=False):
+        """The 64-bit state keys of saved slots: numpy uint64 [count], entry j the key of slot slots[j] (None: every slot) under the field
+        selection `fields` (KEY_* bits; KEY_STATE = map | pose | inventory | selected item) - the public contract of include/ngw.h, which
+        state_keys.keys_of_rows() computes on the host for the same state.  Two slots have equal keys exactly when the selected fields are
+        equal (up to 64-bit collisions), whichever slot, snapshot, env or rank holds them.  One kernel launch, no LDS staging: it works at
+        every map size.  Nothing is committed.
+        slots and device: as in lidar_observation (an index out of range in a device list: key 0, F_BAD_INDEX).  device=True: a torch int64
+        tensor [count] over the same bits (the convention of action_mask_words), ordered behind the launch on torch's current stream."""
+        import torch
+        env = self.env
+        f = check_fields(fields)
+        ptr, count, dev, uploaded = self._slots_arg(slots)
+        words = torch.empty(count, dtype=torch.int64, device=dev)
+        self._enqueue(lambda: _cabi.lib().ngw_state_keys(env._h, self._s, ptr, count, f, C.c_void_p(words.data_ptr())), count, uploaded, device)
+        return words if device else words.cpu().numpy().view(np.uint64)
+
+    def unique(self, slots=None, fields=KEY_STATE, device=False):
+        """The groups of equal states among saved slots: (first, inverse), both int64 - inverse[j] is the group of position j of `slots`,
+        first[g] the smallest position in group g (positions index `slots`, not the pool; with slots=None they are the slots).  Built from
+        keys(): np.unique on the host, or with device=True torch.unique and a scatter-amin on the env's device (no new kernel).  The groups
+        are numbered in the order of their keys, which differs between the two (torch compares the keys as int64)."""
+        return unique_of_keys(self.keys(slots, fields, device))
 
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""

@@ -12,9 +12,15 @@ import numpy as np
 from . import _cabi
 from .novelty import apply_novelty
 from .spec import F_INVALID_ACTION, F_PLACEMENT, STEP_COSTS, EnvSpec, make_spec
+from .state_keys import KEY_STATE, check_fields
 
 _COST_F64 = np.array([float(c) for c in STEP_COSTS], np.float64)
 PLACEMENT_MESSAGE = "Cannot place items, increase map size!"          # pogostick_v1_env.py:167
+
+
+class _Keeper:
+    """Holds the index list a queued launch may still be reading (snapshot.enqueue_ordered)."""
+    _keep = None
 
 
 class _DevArray:
@@ -936,6 +942,25 @@ class VecNovelGridworld:
         s = Snapshot(self, self.num_envs if capacity is None else capacity)
         self.__dict__.setdefault('_snapshots', []).append(s)
         return s
+
+    def state_keys(self, envs=None, fields=KEY_STATE, device=False):
+        """The 64-bit state keys of the envs' CURRENT states: numpy uint64 [count], entry j the key of env envs[j] (None: every env; a list /
+        numpy array, checked, may repeat; or a torch int32 tensor on the env's device, used in place: an index out of range gives key 0 and
+        raises F_BAD_INDEX) under the field selection `fields` (KEY_* bits) - Snapshot.keys() without the save: the key of an env equals the
+        key of a slot that holds its state.  One kernel launch; nothing is committed (masks, lookahead table, lidar rows and prepared
+        episodes stay current).  device=True: a torch int64 tensor over the same bits, ordered behind the launch on torch's current
+        stream, no host wait."""
+        import torch
+        from .snapshot import enqueue_ordered, index_arg
+        f = check_fields(fields)
+        ptr, count, dev, uploaded = index_arg(self, envs, self.num_envs, 'envs')
+        words = torch.empty(count, dtype=torch.int64, device=dev)
+        keeper = self.__dict__.get('_keys_keeper')
+        if keeper is None:
+            keeper = self._keys_keeper = _Keeper()
+        enqueue_ordered(self, keeper, lambda: _cabi.lib().ngw_state_keys(self._h, None, ptr, count, f, C.c_void_p(words.data_ptr())), count, uploaded,
+                        device)
+        return words if device else words.cpu().numpy().view(np.uint64)
 
     def fork(self, src, keep_episode=False):
         """Every env e becomes a copy of env src[e] (src: num_envs indices - a list / numpy array, checked, or a torch int32 tensor on the

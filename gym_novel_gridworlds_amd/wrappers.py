@@ -120,6 +120,8 @@ class LimitActions(NoveltyWrapper):
         return self.env.evaluate_plans(limit_plan_ids(plans, self.limited_actions_id, self.actions_id, len(self.limited_actions), self.env_id),
                                        device=device, copy=copy)
 
+    # (state_key() is NoveltyWrapper's forward: a key describes the state, not the action ids, so it is the same on either side of this wrapper)
+
 
 def limit_plan_ids(plans, limited_actions_id, actions_id, n, env_id=''):
     """Plans written in LimitActions' id space -> the env's ids: every id through the two look-ups of step() (limit_column_ids, as the

@@ -45,7 +45,7 @@ extern "C" {
 /* device-side sticky error flags (ngw_error_flags) */
 #define NGW_F_INVALID_ACTION 1u
 #define NGW_F_PLACEMENT 2u
-#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros) */
+#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros); ngw_state_keys: a row index outside its range (that key is 0) */
 
 /* action kinds (act_kind[]); act_arg[] = recipe index (CRAFT) or item id (SELECT) */
 enum { NGW_ACT_FORWARD = 0, NGW_ACT_LEFT = 1, NGW_ACT_RIGHT = 2, NGW_ACT_BREAK = 3, NGW_ACT_PLACE = 4,
@@ -584,6 +584,43 @@ int ngw_snapshot_lidar(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev,
 int ngw_snapshot_agent_view(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, int64_t count, int view_size, int8_t* view_dev, int32_t* facing_dev,
                             int32_t* inv_dev);
 int ngw_snapshot_action_mask(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, int64_t count, uint64_t* masks_dev);
+
+/* State keys: a 64-bit key of a saved slot or of an env's current state, computed on the device - "are these two nodes the same state?" for
+ * transposition tables, duplicate removal, archives keyed by a cell descriptor, visit counts.  The key is a public contract, so a caller can
+ * compute the same key on the host for a state read with ngw_get_state / ngw_snapshot_get.  All arithmetic is uint64, wrapping:
+ *     mix64(x):  x ^= x >> 30;  x *= 0xBF58476D1CE4E5B9;  x ^= x >> 27;  x *= 0x94D049BB133111EB;  x ^= x >> 31
+ *     term(tag, index, value) = mix64((uint64)tag << 56 | (uint64)index << 32 | (uint32)value)
+ * and key(row, fields) is the XOR of the terms of the fields selected in `fields`:
+ *   NGW_KEY_MAP         for each group g = 0 .. ceil(S*S / 4) - 1: w = the little-endian uint32 of cells 4g .. 4g+3 of the row-major int8 map (cells
+ *                       past S*S count as 0; cell 0 is the row's first cell, wherever the row lies in memory); if w != 0: term(1, g, w)
+ *   NGW_KEY_POSE        term(2, 0, r | c << 8 | facing << 16)
+ *   NGW_KEY_INV         for each item k with inv[k] != 0: term(3, k, inv[k])
+ *   NGW_KEY_SELECTED    term(4, 0, selected)      (also when selected is 0)
+ *   NGW_KEY_STEP_COUNT  term(5, 0, step_count)
+ *   NGW_KEY_EPISODE     term(6, 0, episode)
+ * Every term is independent, so a key can be updated incrementally: changing one cell XORs its group's old term out and the new one in.
+ * NGW_KEY_STATE (the default of the Python layer) is the Markov state with autoreset off; add NGW_KEY_STEP_COUNT where a horizon applies;
+ * NGW_KEY_POSE | NGW_KEY_INV is a typical Go-Explore cell.  A never-saved slot has the key 0x43fc77d84676ced7 under NGW_KEY_STATE. */
+#define NGW_KEY_MAP 1u
+#define NGW_KEY_POSE 2u
+#define NGW_KEY_INV 4u
+#define NGW_KEY_SELECTED 8u
+#define NGW_KEY_STEP_COUNT 16u
+#define NGW_KEY_EPISODE 32u
+#define NGW_KEY_STATE 15u       /* map | pose | inventory | selected item */
+#define NGW_KEY_ALL 63u
+/* keys_dev[j] = key(row idx[j], fields), `count` of them.  `s` is an open snapshot of `h` (rows = its slots); with s == NULL the rows are the
+ * handle's envs' CURRENT states (n_envs rows), as a NULL `src` of ngw_snapshot_expand (a one-env handle's resident step loop is ended first: HBM
+ * holds the state only once it has).  idx_dev is an int32 list in DEVICE memory, NULL means 0 .. count-1 (count may then not exceed the row
+ * count); indices may repeat, and count is otherwise not bound by the row count.  An index outside [0, rows) is never used as an address: its key
+ * is 0 and the sticky NGW_F_BAD_INDEX is raised.  Exactly keys_dev[0 .. count) is written.  count == 0 is a no-op.
+ * ONE kernel launch (ngw_keys.inc), enqueued on the handle's stream; it does not wait.  It stages nothing in LDS and works at every map size.
+ * Nothing is committed - the slot observations' list holds word for word: every byte of every env's state, the last step's outputs, the
+ * prepared next episodes, the mask, lookahead, lidar and view buffers and whether each is current, the bit rows, the host mirrors and every slot
+ * of every snapshot are what they were.  A captured graph stays valid.
+ * NGW_E_INVALID_ARG: a NULL handle or output; a snapshot that is not an open snapshot of this handle; count < 0; fields == 0 or a bit above
+ * NGW_KEY_ALL; idx_dev == NULL with count above the row count. */
+int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev);
 
 /* One-step lookahead tables: every action's outcome for every env, without taking a step.
  * For a handle with A = n_actions the table of the CURRENT state is three arrays - reward int32, done uint8, info uint32 (the NGW_INFO_* packing).
