@@ -391,6 +391,7 @@ int ngw_create(const ngw_spec* spec, int64_t n_envs, int device, uint64_t seed, 
     if (const char* v = getenv("NGW_MASK_FUSED")) h->act_mask_fused = atoi(v);
     if (const char* v = getenv("NGW_API_SLICES")) h->api_slices = atoi(v);
     if (const char* v = getenv("NGW_SOLO")) h->solo_enabled = atoi(v) != 0;
+    if (const char* v = getenv("NGW_STEP_PLAIN")) h->step_plain = atoi(v) != 0;
     {
         // Which per-launch step kernel: the one that reads the <= 14 cells a step needs straight from HBM, at EVERY map size.  Up to
         // round 3 the 10 x 10 (and 6 x 6) maps - whose 64 rows arrive in one round of loads and land in LDS as they are - kept the
@@ -417,6 +418,7 @@ int ngw_create(const ngw_spec* spec, int64_t n_envs, int device, uint64_t seed, 
         const size_t BS = S <= NGW_BOARD_MAX_S ? (size_t)NGW_BOARD_STRIDE(S) : 0, total = o_brd + up(np * BS * 4);
         uint8_t* slab = nullptr;
         if (!rc) rc = dev_alloc(h, &slab, total);
+        h->slab_span = o_brd;                                          // (the arrays the step kernel's hot path addresses from the slab's base end here)
         if (!rc) {
             h->b.map = reinterpret_cast<int8_t*>(slab + o_map); h->b.inv = reinterpret_cast<int32_t*>(slab + o_inv);
             h->b.loc = reinterpret_cast<int32_t*>(slab + o_loc); h->b.facing = reinterpret_cast<int32_t*>(slab + o_fac);
@@ -481,6 +483,8 @@ int ngw_create(const ngw_spec* spec, int64_t n_envs, int device, uint64_t seed, 
             if (spec->act_kind[a] == NGW_ACT_JUMP) u.feat |= NGW_FEAT_JUMP;
             if (spec->act_kind[a] == NGW_ACT_CHOP) u.feat |= NGW_FEAT_CHOP;
         }
+        // the plain class of the in-place step kernel (ngw_device.h): what the spec and the allocation decide; the launcher adds what the launch decides
+        h->plain_class = ngw_step_plain_class(K, u.feat, u.n_entities, u.ext_near, u.place_near, h->slab_span, (uint64_t)np * 4) != 0;
         for (int j = 0; j < spec->n_start; j++)
             for (int q = 0; q < spec->start_qty[j]; q++) hs.place_seq[hs.n_place++] = spec->start_item[j];
         for (int a = 0; a < spec->n_actions; a++) {

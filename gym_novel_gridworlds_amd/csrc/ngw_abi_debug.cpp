@@ -122,4 +122,10 @@ int ngw_debug_launch_floor(ngw_handle* h, int32_t n_launches, int graph, double*
     return rc;
 }
 
+// The plain spec class of the in-place step kernel as a function of made-up numbers (ngw_step_plain_class, ngw_device.h): what a test asks
+// about spans nobody would allocate.  feat_jump: the spec has a Jump action.  (Not an entry point of the C-ABI: no handle, no stream, no state.)
+int ngwh_step_plain_class(int32_t K, int32_t feat_jump, int32_t n_entities, int32_t ext_near, int32_t place_near, uint64_t slab_span, uint64_t out_span) {
+    return ngw_step_plain_class(K, feat_jump ? NGW_FEAT_JUMP : 0, n_entities, ext_near, place_near, slab_span, out_span);
+}
+
 }  // extern "C"

@@ -244,11 +244,16 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
         q.b = h->b; q.mode = mode; q.n_steps = 1; q.actions = actions_dev; q.autoreset = h->autoreset; q.horizon = h->horizon; q.stamps = h->proto.stamps;
         q.seq = o.wire ? h->wt_seq : o.seq; q.action0 = o.action0; q.use_action0 = o.actions;
         fused_mask = want_mask && h->act_mask_fused && !boards && !o.wire;
-        HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, NGW_FEAT_NOSTAGE | ext | (boards ? NGW_FEAT_LIDAR : 0) | (o.wire ? NGW_FEAT_WIRE : 0) | (fused_mask ? NGW_FEAT_MASK : 0),
-                           grid, h->ns_lds, h->stream));
+        // the plain instantiation: the handle's class, and a launch that brings the caller's int32 row and fuses nothing; the host API's steps (they
+        // report a sequence number) stay on the general one in every form, also where they stage an int32 row
+        const bool plain = step_plain(h) && !o.wire && !fused_mask && o.actions == LaunchOpts::ACT_I32 && q.seq == 0;
+        h->last_step_plain = plain;
+        HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, NGW_FEAT_NOSTAGE | ext | (boards ? NGW_FEAT_LIDAR : 0) | (o.wire ? NGW_FEAT_WIRE : 0) | (fused_mask ? NGW_FEAT_MASK : 0) |
+                           (plain ? NGW_FEAT_PLAIN : 0), grid, h->ns_lds, h->stream));
         taken = true;
     }
     if (!taken) {
+        if (mode == NGW_MODE_STEP) h->last_step_plain = false;
         if (!h->general_ok)
             return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps in LDS (fused rollouts, the fused lidar epilogue) "
                                            "and they need more than 160 KiB; per-launch steps and resets are available", h->proto.S);
@@ -287,6 +292,7 @@ int launch_step_slice(ngw_handle* h, const uint8_t* actions_u8_dev, int64_t firs
     q.mode = NGW_MODE_STEP; q.n_steps = 1; q.actions = reinterpret_cast<const int32_t*>(actions_u8_dev); q.autoreset = h->autoreset; q.horizon = h->horizon;
     q.stamps = nullptr; q.seq = 0; q.action0 = 0; q.use_action0 = 2;
     const unsigned grid = (unsigned)((count + NGW_EPB - 1) / NGW_EPB);
+    h->last_step_plain = false;                                                    // (byte actions: the general instantiation)
     HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, NGW_FEAT_NOSTAGE | (h->ext ? NGW_FEAT_EXT : 0) | (h->boards_on ? NGW_FEAT_LIDAR : 0), grid, h->ns_lds, h->stream));
     return NGW_OK;
 }
@@ -621,7 +627,10 @@ int ngw_get_reset_prefetch_depth(ngw_handle* h, int32_t* depth) {
 
 int ngw_step_kernel_info(ngw_handle* h, int32_t* map_in_place) {
     if (!h || !map_in_place) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    *map_in_place = step_in_place(h) ? 1 : 0;
+    // flag 1: as ever.  Flag 2: batched steps with an int32 action row run the plain instantiation (the handle is in the class, NGW_STEP_PLAIN
+    // has not switched it off, nothing fused is on).  Flag 4: the last per-launch step did (a replayed graph: the launches it captured); never
+    // reported for a handle that has left the in-place kernel since.
+    *map_in_place = (step_in_place(h) ? 1 : 0) | (step_plain(h) && !(h->act_mask_on && h->act_mask_fused) ? 2 : 0) | (h->last_step_plain && step_in_place(h) ? 4 : 0);
     return NGW_OK;
 }
 

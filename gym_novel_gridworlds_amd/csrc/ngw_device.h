@@ -232,7 +232,17 @@ enum { NGW_FEAT_LIDAR = 1,    /* fused LidarInFront epilogue (with NGW_FEAT_NOST
        NGW_FEAT_EXT = 2,      /* wrapper predicates (FireWall / FenceRestriction / Crate) */
        NGW_FEAT_NOSTAGE = 8,  /* NGW_MODE_STEP: the in-place step kernel (maps read where they lie, no staging through LDS) */
        NGW_FEAT_WIRE = 16,    /* ... its host write-through form (NgwWT) */
-       NGW_FEAT_MASK = 32 };  /* fused action masks (plain steps only: ngw_step_lean<..., MASK>) */
+       NGW_FEAT_MASK = 32,    /* fused action masks (plain steps only: ngw_step_lean<..., MASK>) */
+       NGW_FEAT_PLAIN = 64 }; /* ... the in-place kernel's instantiation for the plain spec class (ngw_step_plain_class), int32 action rows only */
+
+/* The plain spec class of the in-place step kernel (ngw_step_lean<..., PLAIN>, ngw_lean_step.inc), decided once per handle: at most 12 items
+ * (three 16-byte chunks hold an inventory row), no Jump action, no entities, both "near" rules look for the same item, and every byte the hot
+ * path addresses lies within 4 GB of its array's scalar base - slab_span: from the state slab's base to the end of its last array over n_pad
+ * rows; out_span: the longest of the reward / done / info arrays (allocations of their own) and of the caller's action row.  What a launch adds
+ * to it (in place, no wrapper predicates, nothing fused, no write-through, an int32 action row) is the launcher's to check. */
+static inline int ngw_step_plain_class(int K, int feat_u /* NgwStepU::feat */, int n_entities, int ext_near, int place_near, uint64_t slab_span, uint64_t out_span) {
+    return K >= 4 && K <= 12 && !(feat_u & NGW_FEAT_JUMP) && n_entities == 0 && ext_near == place_near && slab_span < (1ull << 32) && out_span < (1ull << 32);
+}
 #ifdef __cplusplus
 extern "C"
 #endif

@@ -169,6 +169,10 @@ struct ngw_handle {
     NgwResetFast rf{};                    // its arguments, laid out once (layout_reset_fast)
     int rf_nw = -1, rf_additem = 0;       // rf_nw < 0: not applicable to this spec / layout
     size_t rf_lds = 0;
+    int step_plain = 1;                   // NGW_STEP_PLAIN=0 (A/B): the general in-place kernel also where the plain instantiation applies
+    uint64_t slab_span = 0;               // bytes from the state slab's base to the end of step_count, its last array the plain kernel addresses
+    bool plain_class = false;             // the spec and the slab are in the plain class (ngw_step_plain_class, decided in ngw_create)
+    bool last_step_plain = false;         // the last per-launch step ran the plain instantiation (ngw_step_kernel_info)
     int nostage = 0;                      // per-launch steps through the lean kernel without map staging (every size but 10 x 10 / 6 x 6; NGW_NOSTAGE=<min S*S>: A/B)
     NgwLaunch ns_proto{};                 // its launch prototype (small LDS layout)
     size_t ns_lds = 0;
@@ -299,6 +303,8 @@ int check_actions(const int32_t* actions, size_t n, int A);   // NGW_E_INVALID_A
 
 // Which kernel an NGW_MODE_STEP launch runs: the in-place step kernel (no map staging) unless the fused lidar needs the maps in LDS for its march.
 inline bool step_in_place(const ngw_handle* h) { return h->nostage && (!h->lidar_fused || h->boards_on); }
+// ... and whether a launch of it takes the plain instantiation: the handle's class (spec and slab), the switch, and what the handle has switched on since
+inline bool step_plain(const ngw_handle* h) { return h->plain_class && h->step_plain && step_in_place(h) && !h->ext && !h->boards_on; }
 
 // The *_device_ptr(s) getters of buffers that are allocated on first use (action masks, the lookahead table): exempt from rule 1 - they end the
 // one-env loop only if they have to allocate (the allocation zero-fills on the handle's stream); once the buffer exists they hand it out while the loop runs.

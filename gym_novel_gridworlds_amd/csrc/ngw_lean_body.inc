@@ -9,7 +9,8 @@ __device__ __forceinline__ uint32_t bit_of(uint32_t x, uint32_t k) { return (x >
 // Condition bits NGW_CB_* of one lane for one action entry: most bits depend on the state only (the block in front, its 4-neighbourhood,
 // the cell two ahead, the uniform inventory slots); MISSING, NEED_TABLE and NO_ARG_ITEM depend on the entry (recipe inputs in e1 / e2 -
 // the caller read their slots iv0..iv3 -, the table flag and argument of e0).  axe_ok / missing: what lean_body needs of them besides.
-template <class UT>
+// NEAR2 = false: the caller knows that both "near" rules look for the same item (the plain step kernel's spec class): no second test at all.
+template <bool NEAR2 = true, class UT>
 __device__ __forceinline__ uint32_t lean_cond_bits(const UT& U, uint32_t e0, uint32_t e2, int front, int front2, bool ok2, bool okN, bool okS, bool okW,
                                                    bool okE, int nbN, int nbS, int nbW, int nbE, int inv_place, int inv_axe, int inv_arg,
                                                    int iv0, int iv1, int iv2, int iv3, int sel, bool& axe_ok, uint32_t& missing) {
@@ -19,7 +20,7 @@ __device__ __forceinline__ uint32_t lean_cond_bits(const UT& U, uint32_t e0, uin
     const bool near_place = (okN && nbN == nearP) || (okS && nbS == nearP) || (okW && nbW == nearP) || (okE && nbE == nearP);
     bool near_ext = near_place;                                                    // Pogostick: both rules look for a tree_log
     // (scalar parameters: a uniform skip where both rules look for the same item; parameters pinned in VGPRs - the fused rollout - : no branch)
-    if (!__is_same(UT, NgwStepU) || nearE != nearP) {
+    if (NEAR2 && (!__is_same(UT, NgwStepU) || nearE != nearP)) {
         const bool ne = !nearE || (okN && nbN == nearE) || (okS && nbS == nearE) || (okW && nbW == nearE) || (okE && nbE == nearE);
         near_ext = nearE != nearP ? ne : near_place;
     }
@@ -212,7 +213,11 @@ __device__ __forceinline__ LeanUV lean_uv(const NgwStepU& U) {
 // HOOK: work of the caller that only needs data of the FIRST round trip (the bit-row lidar's rotations of its rows): run once the step's
 // cell reads are out and nothing of them has been waited for yet - a wave that is alone on its SIMD has nothing else to do there.
 struct NoHook { __device__ __forceinline__ void operator()() const {} };
-template <bool STAGE, bool WT, bool EXT, bool HW = false, class UT, class HOOK = NoHook>
+// TR: what the spec can hold at all, as compile-time facts.  LeanFull: everything, behind the wave-uniform skips below.  LeanPlain: the plain
+// step kernel's spec class (ngw_lean_step.inc: no Jump action, no entities, one "near" item) - the skips and what they guard are not compiled.
+struct LeanFull { static constexpr bool jump = true, entities = true, near2 = true; };
+struct LeanPlain { static constexpr bool jump = false, entities = false, near2 = false; };
+template <bool STAGE, bool WT, bool EXT, bool HW = false, class TR = LeanFull, class UT, class HOOK = NoHook>
 __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint32_t e0, uint32_t e1, uint32_t e2, uint32_t e3, uint32_t e4, uint32_t e5, bool live,
                                              bool valid, int S, int K, int8_t* mp, int32_t* inv, char* bmap, char* binv, uint32_t mapoff,
                                              uint32_t rowoff, int r, int c, int f, int sel, int steps0, int autoreset, int horizon, const HOOK& hook = HOOK(),
@@ -232,11 +237,12 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
     int nbN = cell_at(okN ? fcell - S : fcell), nbS = cell_at(okS ? fcell + S : fcell);
     int nbW = cell_at(okW ? fcell - 1 : fcell), nbE = cell_at(okE ? fcell + 1 : fcell);
     const int fr2 = fr + dr, fc2 = fc + dc;
-    const bool ok2 = fr2 >= 0 && fr2 <= S - 1 && fc2 >= 0 && fc2 <= S - 1;
+    const bool ok2 = TR::jump && fr2 >= 0 && fr2 <= S - 1 && fc2 >= 0 && fc2 <= S - 1;
     int front2 = 1;
-    if (U.feat & NGW_FEAT_JUMP) front2 = cell_at(ok2 ? fcell + dcell : fcell);
+    if (TR::jump && (U.feat & NGW_FEAT_JUMP)) front2 = cell_at(ok2 ? fcell + dcell : fcell);
     hook();
-    PIN_V(front); PIN_V(nbN); PIN_V(nbS); PIN_V(nbW); PIN_V(nbE); PIN_V(front2);
+    PIN_V(front); PIN_V(nbN); PIN_V(nbS); PIN_V(nbW); PIN_V(nbE);
+    if (TR::jump) PIN_V(front2);
     PIN_V(inv_place); PIN_V(inv_axe); PIN_V(inv_arg); PIN_V(inv_goal); PIN_V(iv0); PIN_V(iv1); PIN_V(iv2); PIN_V(iv3);
     // ---- L1: the slot a success changes (the block in front, or the entry's const slot)
     const int slot = lean_slot(e3, e5, front);
@@ -246,7 +252,7 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
     // ---- condition bits NGW_CB_* of this lane
     bool axe_ok;
     uint32_t missing;
-    const uint32_t cb = lean_cond_bits(U, e0, e2, front, front2, ok2, okN, okS, okW, okE, nbN, nbS, nbW, nbE, inv_place, inv_axe, inv_arg,
+    const uint32_t cb = lean_cond_bits<TR::near2>(U, e0, e2, front, front2, ok2, okN, okS, okW, okE, nbN, nbS, nbW, nbE, inv_place, inv_axe, inv_arg,
                                        iv0, iv1, iv2, iv3, sel, axe_ok, missing);
 
     // ---- outcome: s = 1 if condition A holds, else 2 if B holds, else 0 (success)
@@ -265,7 +271,7 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
     int rew = lean_reward(U, e0, e5, cb, succ, axe_ok);
     // ---- effects of a success
     const uint32_t mv = lean_move(e4, succ);
-    const int nr = mv == 1 ? fr : (mv == 2 ? fr2 : r), nc = mv == 1 ? fc : (mv == 2 ? fc2 : c);
+    const int nr = mv == 1 ? fr : (TR::jump && mv == 2 ? fr2 : r), nc = mv == 1 ? fc : (TR::jump && mv == 2 ? fc2 : c);
     // turn LUT: 2 bits per (turn, facing): none {0,1,2,3}, left {2,3,1,0} (:258-268), right {3,2,0,1} (:269-279)
     const int nf = (int)((0x4B1EE4u >> (((e4 >> 25) & 0x18u) + 2u * (uint32_t)f)) & 3u);
     const int nsel = (succ && (e4 >> 31)) ? aarg : sel;
@@ -303,7 +309,7 @@ __device__ __forceinline__ LeanOut lean_body(const UT& U, const NgwExtU& X, uint
     }
     if (upd) { inv[slot] = inv_slot + delta; if (WT) stg<int>(binv, rowoff + 4u * (uint32_t)slot, inv_slot + delta); if (HW) stgs<int>(hinv, rowoff + 4u * (uint32_t)slot, inv_slot + delta); }
     uint32_t grab = 0;
-    if (U.n_entities) {                                                            // grab_entities :538-554 (3x3 incl. own cell)
+    if (TR::entities && U.n_entities) {                                            // grab_entities :538-554 (3x3 incl. own cell)
         const int ac = nr * S + nc;
         int ev[9];
         bool found = false;

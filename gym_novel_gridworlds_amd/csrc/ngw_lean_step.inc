@@ -68,48 +68,69 @@ __device__ __forceinline__ void wire_done(const NgwWT& W, const uint32_t* dev_fl
 // MASK: the fused action masks - after the step, every lane evaluates the mask of the state it leaves (the post-step pose and cells, or the
 // new episode's first state where the launch started one) with lane_mask (ngw_mask.inc) and stores it to NgwDevSpec::amask.  Plain steps
 // only (no lidar epilogue, no host write-through): with those the library runs the standalone mask kernel behind the step.
-template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false>
+//
+// PLAIN: the instantiation for the plain spec class (ngw_step_plain_class, ngw_device.h: in place, nothing fused, K <= 12, no Jump action, no
+// entities, one "near" item, every array within 4 GB of the slab's base) and launches that bring the caller's int32 action row.  What the class
+// never has is not compiled: three inventory chunks instead of six, one action load and no select, no Jump cell / entity block / second
+// neighbourhood test in lean_body.  A `PLAIN ? x : y` below picks at compile time: the general form compiles y alone.  Every address is the ONE preloaded
+// scalar base plus a 32-bit lane offset that already holds the block's share, so no 64-bit scalar base is built per array.
+template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false, bool PLAIN = false>
 __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int32_t* actions, uint32_t n32, uint32_t o_brd, const NgwDevSpec* __restrict__ dspec,
                                                          uint32_t o_inv, uint32_t o_loc, uint32_t o_fac, uint32_t o_sel, uint32_t o_stp, uint32_t s2k,
                                                          const NgwLaunch a) {
     static_assert(!LIDAR || STAGE || NR > 0, "the fused LidarInFront epilogue marches over the map in LDS, or reads NR bit rows");
     static_assert(!HW || !STAGE, "the host write-through form is the in-place kernel's");
     static_assert(!MASK || (!LIDAR && !HW), "the fused masks are the plain step's");
+    static_assert(!PLAIN || (!STAGE && !EXT && !LIDAR && !HW && !MASK), "the plain class: in place, nothing fused");
     constexpr bool BRD = LIDAR && !STAGE;
+    constexpr int NQ = PLAIN ? 3 : IQ;                                             // 16-byte chunks of an inventory row (PLAIN: K <= 12)
+    using TR = std::conditional_t<PLAIN, LeanPlain, LeanFull>;
     constexpr int NRR = NR > 0 ? NR : 4;
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     STAMP_DECL;
     STAMP(0);
     // Addresses are a per-block SCALAR base (SGPR pair) + a 32-bit per-lane offset: no 64-bit vector arithmetic anywhere.
+    // PLAIN: ONE scalar base, the slab's, for every state array; the array's offset and the block's share are in the lane's 32-bit offset
+    // (the launcher checked the spans).
     const uint32_t bid = blockIdx.x, tid = threadIdx.x;
     const int64_t n = (int64_t)n32;
     const int S2 = (int)(s2k & 0xFFFFu), K = (int)((s2k >> 16) & 0xFFu);
     const int Sb = (int)(s2k >> 24), BSb = (Sb + 3) & ~3;                           // (map size and board stride: the prologue's board loads need them)
     const int npieces = 4 * S2;
-    const int nlive = (int)min((int64_t)EPB, n - (int64_t)bid * EPB);              // every state array is n_pad long
+    // every state array is n_pad long  (PLAIN: n < 2^32 and bid * 64 < n: 32 bits hold the difference)
+    const int nlive = PLAIN ? (int)min((uint32_t)EPB, n32 - bid * (uint32_t)EPB) : (int)min((int64_t)EPB, n - (int64_t)bid * EPB);
     const bool live = (int)tid < nlive;
-    char* const bmap = sbase + (uint64_t)bid * (uint32_t)(EPB * S2);
-    char* const binv = sbase + 16ull * o_inv + (uint64_t)bid * (uint32_t)(EPB * 4 * K);
-    char* const bloc = sbase + 16ull * o_loc + (uint64_t)bid * (EPB * 8);
-    char* const bfac = sbase + 16ull * o_fac + (uint64_t)bid * (EPB * 4);
-    char* const bsel = sbase + 16ull * o_sel + (uint64_t)bid * EPB;
-    char* const bstp = sbase + 16ull * o_stp + (uint64_t)bid * (EPB * 4);
+    char* const bmap = PLAIN ? sbase : sbase + (uint64_t)bid * (uint32_t)(EPB * S2);
+    char* const binv = PLAIN ? sbase : sbase + 16ull * o_inv + (uint64_t)bid * (uint32_t)(EPB * 4 * K);
+    char* const bloc = PLAIN ? sbase : sbase + 16ull * o_loc + (uint64_t)bid * (EPB * 8);
+    char* const bfac = PLAIN ? sbase : sbase + 16ull * o_fac + (uint64_t)bid * (EPB * 4);
+    char* const bsel = PLAIN ? sbase : sbase + 16ull * o_sel + (uint64_t)bid * EPB;
+    char* const bstp = PLAIN ? sbase : sbase + 16ull * o_stp + (uint64_t)bid * (EPB * 4);
     char* const bbrd = sbase + 16ull * o_brd + (uint64_t)bid * (uint32_t)(EPB * 4 * BSb);
     const uint32_t brow = tid * 4u * (uint32_t)BSb;                                // this lane's bit rows inside the block's chunk
-    const char* const bact = reinterpret_cast<const char*>(actions) + (uint64_t)bid * (EPB * 4);
+    const char* const bact = PLAIN ? reinterpret_cast<const char*>(actions) : reinterpret_cast<const char*>(actions) + (uint64_t)bid * (EPB * 4);
 
     // ---- every global load of the launch, issued back to back.  The small per-env loads go FIRST: vmcnt retires in issue
     //      order, so the action's descriptor fetch (ds_bpermute), the address arithmetic and the inventory rows' way into
     //      LDS proceed while the 7 KB of map pieces are still in flight.
-    const int2 rc = ldg<int2>(bloc, tid * 8u);
-    const int f = ldg<int>(bfac, tid * 4u);
-    const int action_ld = ldg<int>(bact, 4u * (uint32_t)min((int)tid, nlive - 1)); // the caller's array is n long
+    const uint32_t oloc = PLAIN ? 16u * o_loc + bid * (uint32_t)(EPB * 8) + tid * 8u : tid * 8u;
+    const int2 rc = ldg<int2>(bloc, oloc);
+    const uint32_t ofac = PLAIN ? 16u * o_fac + bid * (uint32_t)(EPB * 4) + tid * 4u : tid * 4u;
+    const int f = ldg<int>(bfac, ofac);
+    const uint32_t oact = 4u * ((PLAIN ? bid * (uint32_t)EPB : 0u) + (uint32_t)min((int)tid, nlive - 1));   // the caller's array is n long
+    const int action_ld = ldg<int>(bact, oact);
     // (the host step's narrow wire format, use_action0 == 2: the same buffer holds ONE BYTE per env - ngw_step_host_packed's own
     //  page-locked staging, 4 n bytes long, read in place across PCIe; both loads go out, the launch block says which one counts)
-    const int action_u8 = ldg<uint8_t>(reinterpret_cast<const char*>(actions) + (uint64_t)bid * EPB, (uint32_t)min((int)tid, nlive - 1));
-    const int action = a.use_action0 == 1 ? a.action0 : (a.use_action0 == 2 ? action_u8 : action_ld);   // (1: one-env handles, the action came with the arguments)
-    const int sel = ldg<uint8_t>(bsel, tid);
-    const int steps0 = ldg<int>(bstp, tid * 4u);
+    //  (PLAIN: the launcher sends only int32 rows here)
+    int action = action_ld;
+    if constexpr (!PLAIN) {
+        const int action_u8 = ldg<uint8_t>(reinterpret_cast<const char*>(actions) + (uint64_t)bid * EPB, (uint32_t)min((int)tid, nlive - 1));
+        action = a.use_action0 == 1 ? a.action0 : (a.use_action0 == 2 ? action_u8 : action_ld);   // (1: one-env handles, the action came with the arguments)
+    }
+    const uint32_t osel = PLAIN ? 16u * o_sel + bid * (uint32_t)EPB + tid : tid;
+    const int sel = ldg<uint8_t>(bsel, osel);
+    const uint32_t ostp = PLAIN ? 16u * o_stp + bid * (uint32_t)(EPB * 4) + tid * 4u : tid * 4u;
+    const int steps0 = ldg<int>(bstp, ostp);
     // lane l holds the micro-op entry of action l (zeros beyond the table: what an invalid action id fetches)
     uint32_t t0, t1, t2, t3, t4, t5;
     {   // (lanes beyond the table hold a copy of its last entry: no lane fetches from them - an invalid action id reads lane 63's
@@ -119,15 +140,16 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
         const bool in_table = tid < NGW_MAX_ACTIONS;
         t0 = in_table ? x0.x : 0u; t1 = in_table ? x0.y : 0u; t2 = in_table ? x1.x : 0u; t3 = in_table ? x1.y : 0u; t4 = in_table ? x2.x : 0u; t5 = in_table ? x2.y : 0u;
     }
-    const uint32_t rowoff = tid * 4u * (uint32_t)K;                                // this lane's inventory row inside the block's chunk
+    // this lane's inventory row inside the block's chunk  (PLAIN: inside the slab; built while the loads above are in flight)
+    const uint32_t rowoff = (PLAIN ? 16u * o_inv + bid * (uint32_t)(EPB * 4 * K) : 0u) + tid * 4u * (uint32_t)K;
     // 16-B chunks of the inventory row, every one clamped to the row end (K >= 4): a chunk beyond the row re-reads the last one -
     // ALL of them unconditionally.  (A uniform "K <= 12: skip the upper three" around the loads looked cheaper and cost a full
     // memory round trip: the values of the skipped chunks were merged with copies of chunk 2 where the branch ends, behind a
     // wait for every load issued so far - and the map pieces below went out only after that.)
-    u32x4 q[IQ];
-    const bool inv_short = K <= 12;
+    u32x4 q[NQ];
+    const bool inv_short = PLAIN || K <= 12;
 #pragma unroll
-    for (int j = 0; j < IQ; j++) q[j] = ldg<u32x4>(binv, rowoff + 4u * (uint32_t)min(4 * j, K - 4));
+    for (int j = 0; j < NQ; j++) q[j] = ldg<u32x4>(binv, rowoff + 4u * (uint32_t)min(4 * j, K - 4));
     u32x4 buf[PB];
     if (STAGE) {
 #pragma unroll
@@ -179,7 +201,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
     }
     if (!inv_short) {
 #pragma unroll
-        for (int j = 3; j < IQ; j++) {
+        for (int j = 3; j < NQ; j++) {
             const int o = min(4 * j, K - 4);
             inv[o] = (int)q[j].x; inv[o + 1] = (int)q[j].y; inv[o + 2] = (int)q[j].z; inv[o + 3] = (int)q[j].w;
         }
@@ -227,7 +249,8 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
             PIN_V(wr0); PIN_V(wr1); PIN_V(wr2);
         }
     };
-    const LeanOut o = lean_body<STAGE, true, EXT, HW>(U, X, e0, e1, e2, e3, e4, e5, live, valid, a.S, K, mp, inv, bmap, binv, tid * (uint32_t)S2, rowoff,
+    const uint32_t mapoff = (PLAIN ? bid * (uint32_t)(EPB * S2) : 0u) + tid * (uint32_t)S2;                     // this lane's map, likewise
+    const LeanOut o = lean_body<STAGE, true, EXT, HW, TR>(U, X, e0, e1, e2, e3, e4, e5, live, valid, PLAIN ? Sb : a.S, K, mp, inv, bmap, binv, mapoff, rowoff,
                                                  rc.x, rc.y, f, sel, steps0, a.autoreset, a.horizon, brd_hook, hmap, hinv);
     uint32_t flags = o.flags;
     STAMP(4);
@@ -253,9 +276,15 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
     }
     STAMP(5);
     // (every state / output array is n_pad long: lanes beyond n write their own padding rows - zeros - instead of being masked off)
-    stg<int>(reinterpret_cast<char*>(a.b.reward) + (uint64_t)bid * (EPB * 4), tid * 4u, o.reward);
-    stg<uint8_t>(reinterpret_cast<char*>(a.b.done) + (uint64_t)bid * EPB, tid, (uint8_t)o.ended);
-    stg<uint32_t>(reinterpret_cast<char*>(a.b.info) + (uint64_t)bid * (EPB * 4), tid * 4u, o.info);
+    if constexpr (PLAIN) {                                                         // (n_pad * 4 < 2^32: the block's share fits the lane offset)
+        stg<int>(a.b.reward, bid * (uint32_t)(EPB * 4) + tid * 4u, o.reward);
+        stg<uint8_t>(a.b.done, bid * (uint32_t)EPB + tid, (uint8_t)o.ended);
+        stg<uint32_t>(a.b.info, bid * (uint32_t)(EPB * 4) + tid * 4u, o.info);
+    } else {
+        stg<int>(reinterpret_cast<char*>(a.b.reward) + (uint64_t)bid * (EPB * 4), tid * 4u, o.reward);
+        stg<uint8_t>(reinterpret_cast<char*>(a.b.done) + (uint64_t)bid * EPB, tid, (uint8_t)o.ended);
+        stg<uint32_t>(reinterpret_cast<char*>(a.b.info) + (uint64_t)bid * (EPB * 4), tid * 4u, o.info);
+    }
     // Two tails, so that NO scalar of the hot path is live across the cold region (the register allocator otherwise parks half of
     // them in VGPR lanes from the prologue on: 50 v_writelane / 66 v_readlane in round 3's kernel, on a path bound by issue):
     //   * no lane resets (99 launches in 100 at H = 100): pose stores, epilogue, done;
@@ -264,10 +293,10 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
     //     pointer and the launch's sequence number.
     if (!__any(o.do_reset)) {
         // fused LidarInFront observation of the state this step produced (observation_wrappers.py:67-78): map and inventory row are in LDS
-        stg<int2>(bloc, tid * 8u, int2{o.r, o.c});
-        stg<int>(bfac, tid * 4u, o.f);
-        stg<uint8_t>(bsel, tid, (uint8_t)o.sel);
-        stg<int>(bstp, tid * 4u, o.steps);
+        stg<int2>(bloc, oloc, int2{o.r, o.c});
+        stg<int>(bfac, ofac, o.f);
+        stg<uint8_t>(bsel, osel, (uint8_t)o.sel);
+        stg<int>(bstp, ostp, o.steps);
         if (HW) wire_outputs(W, bid, tid, live, o.r, o.c, o.f, o.sel, o.reward, o.ended, o.info);
         // (tried: the output and pose stores AFTER the epilogue, in case the epilogue's register re-use waited for their acknowledgement -
         //  no gain, 8.05 against 7.8 us per step; the stores stay where they overlap the epilogue)
@@ -277,9 +306,6 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
             // a cell write sits in front of an agent that did not move (its column when it faces north / south; its row is `roww`), an entity
             // pick-up clears cells one step away on every line
             STAMP_SUB(a, 0);
-#ifdef NGW_EXP_NOEPI
-            return;
-#endif
             const int nr = live ? o.r : 1, nc = live ? o.c : 1;                    // (rows beyond n hold zeros: a pose inside the map keeps every read in bounds)
             BoardPatch pt = {0u, 0u, 0u, 0u};
             if (o.wcell && bfc == nc) { if (o.cellv) pt.col_set = 1u << bfr; else pt.col_clr = 1u << bfr; }
@@ -291,10 +317,10 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
             }
             const uint32_t ring = 1u | (1u << (Sb - 1));
             wave_lds_sync();                                                       // (the tile was zeroed, the item tables written, by other lanes)
-            lidar_boards_rows<NRR>(a, lds, (int)tid, R, Rd, Ra, roww | ring, pt, Sb, S2, nr, nc, o.f, bmap, tid * (uint32_t)S2, inv, lid0, lid1, bid, HW ? W.rows : nullptr);
+            lidar_boards_rows<NRR>(a, lds, (int)tid, R, Rd, Ra, roww | ring, pt, Sb, S2, nr, nc, o.f, bmap, mapoff, inv, lid0, lid1, bid, HW ? W.rows : nullptr);
         }
         if (MASK) {                                                                // the post-step state: pose in registers, map in LDS (staged) or
-            const uint32_t mo = tid * (uint32_t)S2;                                //   HBM (this lane's own writes), inventory row in LDS
+            const uint32_t mo = mapoff;                                            //   HBM (this lane's own writes), inventory row in LDS
             auto cell = [&](int q) -> int { return STAGE ? (int)mp[q] : (int)ldg<int8_t>(bmap, mo + (uint32_t)q); };
             const uint64_t m = lane_mask<EXT>(dspec, a.S, K, live ? o.r : 1, live ? o.c : 1, live ? o.f : 0, o.sel, inv, cell);
             uint64_t* const am = dspec->amask;
@@ -398,7 +424,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
 }
 
 
-template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false>
+template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false, bool PLAIN = false>
 hipError_t launch_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned grid, size_t lds_bytes, hipStream_t stream) {
     // the leading scalar arguments (see the kernel): the state slab's base and the offsets of its arrays in 16-byte units
     char* const base = reinterpret_cast<char*>(a->b.map);
@@ -418,6 +444,16 @@ hipError_t launch_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned gri
     } else if (NR > 0) return hipErrorInvalidValue;
     if (NR > 0 && (a->BS > NR || a->BS < 4)) return hipErrorInvalidValue;
     const uint32_t s2k = (uint32_t)a->S2 | ((uint32_t)a->K << 16) | ((uint32_t)a->S << 24);
-    return launch_kernel<ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, base, a->actions, (uint32_t)a->n, o_brd, dspec,
+    if constexpr (PLAIN) {
+        // the plain instantiation addresses everything as one base + 32 bits and reads the int32 row only: a launch that does not fit (a handle's
+        // ngw_step_plain_class said so once; slices and other callers hand their own blocks) runs the general instantiation - never an error
+        const uint64_t np = (uint64_t)a->n_pad, ends[6] = {np * (uint64_t)a->S2, 16ull * off[0] + np * 4u * (uint64_t)a->K, 16ull * off[1] + np * 8u,
+                                                             16ull * off[2] + np * 4u, 16ull * off[3] + np, 16ull * off[4] + np * 4u};
+        uint64_t span = 0;
+        for (uint64_t e : ends) span = e > span ? e : span;
+        if (!ngw_step_plain_class(a->K, 0, 0, 0, 0, span, np * 4u) || a->use_action0 != 0)
+            return launch_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK, false>(dspec, a, grid, lds_bytes, stream);
+    }
+    return launch_kernel<ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK, PLAIN>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, base, a->actions, (uint32_t)a->n, o_brd, dspec,
                                                                                 off[0], off[1], off[2], off[3], off[4], s2k, *a);
 }

@@ -616,7 +616,16 @@ class VecNovelGridworld:
         wave's maps through LDS (include/ngw.h ngw_step_kernel_info)."""
         v = C.c_int32()
         _cabi.check(_cabi.lib().ngw_step_kernel_info(self._h, C.byref(v)))
-        return bool(v.value)
+        return bool(v.value & 1)                                     # (the word's other flags: step_kernel_plain)
+
+    @property
+    def step_kernel_plain(self):
+        """(handle, last): `handle` - batched steps that bring an int32 action row run the in-place kernel's instantiation for the plain
+        spec class (at most 12 items, no Jump action, no entities, one "near" item, nothing fused; NGW_STEP_PLAIN=0 switches it off);
+        `last` - the last per-launch step (or the launches a graph captured) ran it.  Flags 2 and 4 of ngw_step_kernel_info's word."""
+        v = C.c_int32()
+        _cabi.check(_cabi.lib().ngw_step_kernel_info(self._h, C.byref(v)))
+        return bool(v.value & 2), bool(v.value & 4)
 
     @property
     def reset_prefetch_depth(self):

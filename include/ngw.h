@@ -394,7 +394,11 @@ int ngw_terminal_device_ptrs(ngw_handle* h, void** map, void** loc, void** facin
 
 /* Which per-launch step kernel this handle's ngw_step* calls run right now: *map_in_place = 1 - the one that reads the <= 14 map
  * cells a step needs straight from HBM (the default at every map size), 0 - the one that stages the wave's 64 maps through
- * LDS (any size while the fused lidar epilogue is on, or where NGW_NOSTAGE says so).  What bench.py names its kernel from. */
+ * LDS (any size while the fused lidar epilogue is on, or where NGW_NOSTAGE says so).  What bench.py names its kernel from.
+ * The word carries two more flags, so test it with `& 1`, not `== 1`.  Flag 2 - batched steps that bring an int32 action row run the in-place kernel's instantiation for the plain
+ * spec class (at most 12 items, no Jump action, no entities, both "near" rules on one item, no wrapper predicates, nothing fused, every
+ * array within 4 GB of its base; NGW_STEP_PLAIN=0 switches it off); flag 4 - the last per-launch step, or the launches the current graph
+ * captured, ran it (byte and one-env actions, host write-through and the host API's steps, which report a sequence number, never do). */
 int ngw_step_kernel_info(ngw_handle* h, int32_t* map_in_place);
 
 /* LidarInFront: configure once, then ngw_lidar() computes the observation of the CURRENT state of every env into a device
