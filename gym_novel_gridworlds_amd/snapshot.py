@@ -61,6 +61,18 @@ def pair_count(n_a, n_b, default):
     return n_a if n_a is not None else n_b
 
 
+def _check_ids(a, n_actions, name, shape_error):
+    """The dtype and range checks check_action_ids and check_plan_ids share; shape_error: None, or what is wrong with a.shape."""
+    if a.dtype.kind not in 'iu':
+        raise ValueError("%s: integer action ids expected, got dtype %s" % (name, a.dtype))
+    if shape_error:
+        raise ValueError("%s: %s expected, got shape %s" % (name, shape_error, a.shape))
+    bad = (a < 0) | (a >= n_actions)
+    if bad.any():
+        raise ValueError("%d is not in list" % int(a[bad][0]))
+    return np.ascontiguousarray(a, np.int32)
+
+
 def check_action_ids(actions, n_actions, name='actions'):
     """The host-side check of one action id per pair given as a list / numpy array: integer dtype, one dimension, every id in the action
     list (ValueError("<a> is not in list") otherwise, what step() raises).  Returns a contiguous int32 array."""
@@ -68,46 +80,8 @@ def check_action_ids(actions, n_actions, name='actions'):
         raise ValueError("%s: one action id per pair expected" % name)
     a = np.asarray(actions)
     if a.size == 0 and a.ndim == 1:
-        return np.zeros(0, np.int32)
-    if a.dtype.kind not in 'iu':
-        raise ValueError("%s: integer action ids expected, got dtype %s" % (name, a.dtype))
-    if a.ndim != 1:
-        raise ValueError("%s: a one-dimensional list of action ids expected, got shape %s" % (name, a.shape))
-    bad = (a < 0) | (a >= n_actions)
-    if bad.any():
-        raise ValueError("%d is not in list" % int(a[bad][0]))
-    return np.ascontiguousarray(a, np.int32)
-
-
-def check_expand(parents, actions, children, n_parents, capacity, n_actions, same_buffer, device_len=None):
-    """The host-side checks of one expand call: parents index rows [0, n_parents) and may repeat, children index slots [0, capacity) and
-    must be distinct, actions are ids of the action list, the three have one length (None = no list: 0 .. count-1, which must exist), and -
-    where source and destination are the same buffer - no child is also a parent.  device_len(x): the length of x when it is a device
-    tensor to be used in place (its values are then not checked), else None.  Returns (parents, actions, children, count): contiguous
-    int32 arrays, None, or the device tensors themselves."""
-    on_dev = (lambda x: None) if device_len is None else device_len
-    n_p, n_a, n_c = on_dev(parents), on_dev(actions), on_dev(children)
-    if n_p is None and parents is not None:
-        parents = check_indices(parents, n_parents, False, 'parents')
-        n_p = int(parents.size)
-    if n_a is None:
-        actions = check_action_ids(actions, n_actions)
-        n_a = int(actions.size)
-    if n_c is None and children is not None:
-        children = check_indices(children, capacity, True, 'children')
-        n_c = int(children.size)
-    count = pair_count(pair_count(n_p, n_a, n_a), n_c, n_a)
-    if parents is None and count > n_parents:
-        raise ValueError("parents: no list given and %d pairs for %d rows" % (count, n_parents))
-    if count > capacity:
-        raise ValueError("children: %d pairs for a snapshot of %d slots" % (count, capacity))
-    if same_buffer and count and on_dev(parents) is None and on_dev(children) is None:
-        hp = np.arange(count) if parents is None else parents
-        hc = np.arange(count) if children is None else children
-        both = np.intersect1d(hp, hc)
-        if both.size:
-            raise ValueError("children: slot %d is also a parent of the same call (source and destination are one buffer)" % int(both[0]))
-    return parents, actions, children, count
+        return np.zeros(0, np.int32)            # (an empty list has no dtype of its own)
+    return _check_ids(a, n_actions, name, a.ndim != 1 and "a one-dimensional list of action ids")
 
 
 def check_plan_ids(plans, n_actions, name='plans'):
@@ -119,14 +93,47 @@ def check_plan_ids(plans, n_actions, name='plans'):
     a = np.asarray(plans)
     if a.ndim == 2 and a.shape[0] == 0 and a.shape[1] >= 1:
         return np.zeros(a.shape, np.int32)      # (an empty list has no dtype of its own)
-    if a.dtype.kind not in 'iu':
-        raise ValueError("%s: integer action ids expected, got dtype %s" % (name, a.dtype))
-    if a.ndim != 2 or a.shape[1] < 1:
-        raise ValueError("%s: action ids shaped [count, T] with T >= 1 expected, got shape %s" % (name, a.shape))
-    bad = (a < 0) | (a >= n_actions)
-    if bad.any():
-        raise ValueError("%d is not in list" % int(a[bad][0]))
-    return np.ascontiguousarray(a, np.int32)
+    return _check_ids(a, n_actions, name, (a.ndim != 2 or a.shape[1] < 1) and "action ids shaped [count, T] with T >= 1")
+
+
+def _check_pairs(parents, middle, check_middle, children, n_parents, capacity, same_buffer, device_len, children_default):
+    """What check_expand and check_rollout share.  middle: the argument between parents and children, checked by check_middle where it is
+    no device tensor, or - check_middle None - its length.  children_default: children=None means slots 0 .. count-1 (expand), not "nothing
+    is kept" (rollout).  Returns (parents, middle, children, count)."""
+    on_dev = device_len or (lambda x: None)
+    n_p, n_m, n_c = on_dev(parents), on_dev(middle) if check_middle else middle, on_dev(children)
+    host_lists = n_p is None and n_c is None
+    if n_p is None and parents is not None:
+        parents = check_indices(parents, n_parents, False, 'parents')
+        n_p = int(parents.size)
+    if n_m is None:
+        middle = check_middle(middle)
+        n_m = int(middle.size)
+    if n_c is None and children is not None:
+        children = check_indices(children, capacity, True, 'children')
+        n_c = int(children.size)
+    count = pair_count(pair_count(n_p, n_m, n_m), n_c, n_m)
+    kept = children_default or children is not None
+    if parents is None and count > n_parents:
+        raise ValueError("parents: no list given and %d pairs for %d rows" % (count, n_parents))
+    if kept and count > capacity:
+        raise ValueError("children: %d pairs for a snapshot of %d slots" % (count, capacity))
+    if same_buffer and count and kept and host_lists:
+        hp = np.arange(count) if parents is None else parents
+        hc = np.arange(count) if children is None else children
+        both = np.intersect1d(hp, hc)
+        if both.size:
+            raise ValueError("children: slot %d is also a parent of the same call (source and destination are one buffer)" % int(both[0]))
+    return parents, middle, children, count
+
+
+def check_expand(parents, actions, children, n_parents, capacity, n_actions, same_buffer, device_len=None):
+    """The host-side checks of one expand call: parents index rows [0, n_parents) and may repeat, children index slots [0, capacity) and
+    must be distinct, actions are ids of the action list, the three have one length (None = no list: 0 .. count-1, which must exist), and -
+    where source and destination are the same buffer - no child is also a parent.  device_len(x): the length of x when it is a device
+    tensor to be used in place (its values are then not checked), else None.  Returns (parents, actions, children, count): contiguous
+    int32 arrays, None, or the device tensors themselves."""
+    return _check_pairs(parents, actions, lambda a: check_action_ids(a, n_actions), children, n_parents, capacity, same_buffer, device_len, True)
 
 
 def check_rollout(parents, n_plans, children, n_parents, capacity, same_buffer, device_len=None):
@@ -135,30 +142,13 @@ def check_rollout(parents, n_plans, children, n_parents, capacity, same_buffer, 
     and - where source and destination are the same buffer - no child is also a parent.  device_len(x): the length of x when it is a
     device tensor to be used in place (its values are then not checked), else None.  Returns (parents, children, count): contiguous int32
     arrays, None, or the device tensors themselves."""
-    on_dev = (lambda x: None) if device_len is None else device_len
-    n_p, n_c = on_dev(parents), on_dev(children)
-    if n_p is None and parents is not None:
-        parents = check_indices(parents, n_parents, False, 'parents')
-        n_p = int(parents.size)
-    if n_c is None and children is not None:
-        children = check_indices(children, capacity, True, 'children')
-        n_c = int(children.size)
-    count = pair_count(pair_count(n_p, n_plans, n_plans), n_c, n_plans)
-    if parents is None and count > n_parents:
-        raise ValueError("parents: no list given and %d pairs for %d rows" % (count, n_parents))
-    if children is not None and count > capacity:
-        raise ValueError("children: %d pairs for a snapshot of %d slots" % (count, capacity))
-    if same_buffer and count and children is not None and on_dev(parents) is None and on_dev(children) is None:
-        hp = np.arange(count) if parents is None else parents
-        both = np.intersect1d(hp, children)
-        if both.size:
-            raise ValueError("children: slot %d is also a parent of the same call (source and destination are one buffer)" % int(both[0]))
-    return parents, children, count
+    p, _, c, count = _check_pairs(parents, n_plans, None, children, n_parents, capacity, same_buffer, device_len, False)
+    return p, c, count
 
 
-def check_slots(slots, capacity, device_len=None):
-    """The host-side checks of the slot list of one slot observation (lidar_observation / agent_view / action_masks of a Snapshot): None = every
-    slot, 0 .. capacity-1; a list / numpy array indexes slots [0, capacity) and may repeat (its length is not bound by the capacity).
+def check_slots(slots, capacity, device_len=None, distinct=False, name='slots'):
+    """The host-side checks of one index list that reads or writes rows [0, capacity) (the slot observations, the state keys, save / restore):
+    None = every row, 0 .. capacity-1; a list / numpy array may repeat unless `distinct` (its length is not bound by the capacity).
     device_len(x): the length of x when it is a device tensor to be used in place (its values are then not checked), else None.  Returns
     (slots, count): a contiguous int32 array, None, or the device tensor itself."""
     if slots is None:
@@ -166,42 +156,62 @@ def check_slots(slots, capacity, device_len=None):
     n = None if device_len is None else device_len(slots)
     if n is not None:
         return slots, int(n)
-    slots = check_indices(slots, capacity, False, 'slots')
+    slots = check_indices(slots, capacity, distinct, name)
     return slots, int(slots.size)
 
 
-def index_arg(env, idx, limit, name):
-    """One index list of a call that reads rows by index (the slot observations, the state keys), checked and uploaded: None, a list / numpy
-    array (check_slots) or a contiguous torch int32 tensor on the env's device, used in place.  -> (device pointer or None, count, torch
-    device, the uploaded tensor or None)."""
+def tensor_len(dev, name, x):
+    """The one check of an argument that may be a device tensor used in place: the length of x when it is a contiguous one-dimensional int32
+    torch tensor on `dev` (the env's torch device), None when it is no tensor, ValueError for any other tensor."""
+    import torch
+    if not isinstance(x, torch.Tensor):
+        return None
+    if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
+        raise ValueError("%s: a contiguous one-dimensional int32 tensor on %s expected" % (name, dev))
+    return int(x.numel())
+
+
+def upload(dev, count, *args):
+    """The checked arguments of one call (None, numpy arrays, device tensors) -> ([a device pointer each; None for None and where count is 0],
+    [the tensors uploaded here]).  The only place a host array becomes a device tensor."""
+    import torch
+    ptrs, uploaded = [], []
+    for x in args:
+        if isinstance(x, np.ndarray):
+            x = torch.from_numpy(x).to(dev)
+            uploaded.append(x)
+        ptrs.append(C.c_void_p(x.data_ptr()) if x is not None and count else None)
+    return ptrs, uploaded
+
+
+def index_arg(env, idx, limit, name, distinct=False):
+    """One index list of a call that moves or reads rows by index (save / restore, the slot observations, the state keys), checked and
+    uploaded: None, a list / numpy array (check_indices) or a contiguous torch int32 tensor on the env's device, used in place.
+    -> (device pointer or None, count - `limit` without a list -, torch device, [the uploaded tensor] or [])."""
     import torch
     dev = torch.device('cuda:%d' % env.device)
-
-    def device_len(x):
-        if not isinstance(x, torch.Tensor):
-            return None
-        if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
-            raise ValueError("%s: a contiguous one-dimensional int32 tensor on %s expected" % (name, dev))
-        return int(x.numel())
-    s, count = check_slots(idx, limit, device_len)
-    uploaded = None
-    if isinstance(s, np.ndarray):
-        s = uploaded = torch.from_numpy(s).to(dev)
-    return (C.c_void_p(s.data_ptr()) if s is not None and count else None), count, dev, uploaded
+    s, count = check_slots(idx, limit, lambda x: tensor_len(dev, name, x), distinct, name)
+    (ptr,), uploaded = upload(dev, count, s)
+    return ptr, count, dev, uploaded
 
 
-def enqueue_ordered(env, holder, call, count, uploaded, device):
+def enqueue_ordered(env, holder, call, count, uploaded, device, behind=True):
     """One launch on the env's stream that reads and writes torch tensors: the env's stream waits for torch's current one (uploads, the
-    allocations of the outputs, the caller's own tensors), and behind the launch either torch's stream waits for the env's (device=True: no
-    host wait) or the host does.  `holder._keep` keeps an uploaded list alive until the next call of the holder has synchronised."""
+    allocations of the outputs, the caller's own tensors) unless that stream has finished all its work, and behind the launch either torch's stream waits for the env's (device=True: no
+    host wait) or the host does - or, behind=False (a call without outputs: save / restore), nothing does.  `holder._keep` keeps the
+    uploaded lists alive until the next call of the holder has synchronised."""
     import torch
     if holder._keep:
         env.sync()                              # (the previous call has read its lists: they may be released now)
         holder._keep = None
     if count:
-        env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, True)
+        ahead = torch.cuda.current_stream(env.device)
+        if not ahead.query():                   # (an idle stream has nothing to wait for: the wait alone costs a restore + step + save loop 40 %)
+            env.stream_order(ahead.cuda_stream, True)
         _cabi.check(call())
-        holder._keep = [uploaded] if uploaded is not None else None
+        holder._keep = uploaded or None
+    if not behind:
+        return
     if device:
         if count:
             env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, False)
@@ -270,48 +280,43 @@ class Snapshot:
             raise ValueError("snapshot is closed")
         return self._s
 
-    def _dev_index(self, idx, limit, distinct, name):
-        """-> (device pointer or None, length or None, the uploaded tensor or None)."""
-        if idx is None:
-            return None, None, None
-        import torch
-        dev = torch.device('cuda:%d' % self.env.device)
-        if isinstance(idx, torch.Tensor):
-            if idx.dtype != torch.int32 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != dev:
-                raise ValueError("%s: a contiguous one-dimensional int32 tensor on %s expected" % (name, dev))
-            return idx.data_ptr(), int(idx.numel()), None
-        a = check_indices(idx, limit, distinct, name)
-        t = torch.from_numpy(a).to(dev)
-        return t.data_ptr(), int(a.size), t
-
-    def _call(self, fn, first, second, default_count, *extra):
-        import torch
+    def _copy(self, fn, src, n_src, src_name, dst, n_dst, dst_name, *extra):
+        """save / restore: fn copies row src[j] to row dst[j] (None: 0 .. count-1; the destinations distinct); ordered as restore() says."""
         env = self.env
-        count = pair_count(first[1], second[1], default_count)
-        uploaded = [t for t in (first[2], second[2]) if t is not None]
-        if self._keep:
-            env.sync()                          # (the previous call has read its lists: they may be released now)
-            self._keep = None
-        if uploaded:
-            torch.cuda.current_stream(env.device).synchronize()   # the uploads ran on torch's stream, the copy runs on the env's
-        _cabi.check(fn(env._h, self._open(), C.c_void_p(first[0]), C.c_void_p(second[0]), int(count), *extra))
-        self._keep = uploaded or None
+        self._open()
+        p_src, c_src, _, up_src = index_arg(env, src, n_src, src_name)
+        p_dst, c_dst, _, up_dst = index_arg(env, dst, n_dst, dst_name, distinct=True)
+        count = pair_count(None if src is None else c_src, None if dst is None else c_dst, env.num_envs)
+        enqueue_ordered(env, self, lambda: fn(env._h, self._s, p_src, p_dst, count, *extra), count, up_src + up_dst, True, behind=False)
 
     def save(self, envs=None, slots=None):
-        """slot[slots[j]] := state of env envs[j].  The slots of one call must be distinct."""
-        self._open()
-        e = self._dev_index(envs, self.env.num_envs, False, 'envs')
-        s = self._dev_index(slots, self.capacity, True, 'slots')
-        self._call(_cabi.lib().ngw_snapshot_save, e, s, self.env.num_envs)
+        """slot[slots[j]] := state of env envs[j].  The slots of one call must be distinct.  Ordered as restore() is."""
+        self._copy(_cabi.lib().ngw_snapshot_save, envs, self.env.num_envs, 'envs', slots, self.capacity, 'slots')
 
     def restore(self, slots=None, envs=None, keep_episode=False):
         """state of env envs[j] := slot[slots[j]].  Slots may repeat (the fork); the envs of one call must be distinct; envs not named
-        keep their state.  keep_episode: the destination envs keep their own episode counters."""
-        self._open()
-        s = self._dev_index(slots, self.capacity, False, 'slots')
-        e = self._dev_index(envs, self.env.num_envs, True, 'envs')
+        keep their state.  keep_episode: the destination envs keep their own episode counters.
+        No host wait: the copy runs on the env's stream, which first waits for torch's current stream (an uploaded list, an index tensor
+        computed there).  Torch's stream is NOT ordered behind the copy (that edge made a restore + step + save loop several times
+        slower): an index tensor must stay unchanged until the env's stream has passed the call, as the class says."""
         self.env._lidar_rows_fresh = False
-        self._call(_cabi.lib().ngw_snapshot_restore, s, e, self.env.num_envs, KEEP_EPISODE if keep_episode else 0)
+        self._copy(_cabi.lib().ngw_snapshot_restore, slots, self.capacity, 'slots', envs, self.env.num_envs, 'envs', KEEP_EPISODE if keep_episode else 0)
+
+    def _source(self, source, from_envs, what):
+        """Where the parents of one `what` (expand / rollout) call live -> (the source snapshot's C handle - None: the env's current states -,
+        n_parents, whether source and destination are one buffer)."""
+        self._open()
+        if source is not None and from_envs:
+            raise ValueError("%s: give either source or from_envs" % what)
+        if from_envs:
+            return None, self.env.num_envs, False
+        src = self if source is None else source
+        if not isinstance(src, Snapshot):
+            raise ValueError("source: a Snapshot expected")
+        src._open()
+        if src.env is not self.env:
+            raise ValueError("source: a snapshot of another env")
+        return src._s, src.capacity, src is self
 
     def expand(self, parents, actions, children, from_envs=False, source=None, device=False):
         """slot[children[j]] := the state of parent parents[j] stepped ONCE with actions[j], as the step leaves it before any reset (the
@@ -329,50 +334,19 @@ class Snapshot:
         no copy, no host wait; otherwise numpy arrays after one sync."""
         import torch
         env = self.env
-        self._open()
-        if source is not None and from_envs:
-            raise ValueError("expand: give either source or from_envs")
-        src = self if source is None else source
-        if not from_envs:
-            if not isinstance(src, Snapshot):
-                raise ValueError("source: a Snapshot expected")
-            src._open()
-            if src.env is not env:
-                raise ValueError("source: a snapshot of another env")
-        n_parents = env.num_envs if from_envs else src.capacity
+        src, n_parents, same_buffer = self._source(source, from_envs, 'expand')
         dev = torch.device('cuda:%d' % env.device)
-
-        def device_len(x):
-            if not isinstance(x, torch.Tensor):
-                return None
-            if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
-                raise ValueError("a contiguous one-dimensional int32 tensor on %s expected" % dev)
-            return int(x.numel())
-        p, a, c, count = check_expand(parents, actions, children, n_parents, self.capacity, env.n_actions, not from_envs and src is self, device_len)
-        ptr, uploaded = [], []
-        for x in (p, a, c):
-            if isinstance(x, np.ndarray):
-                x = torch.from_numpy(x).to(dev)
-                uploaded.append(x)
-            ptr.append(C.c_void_p(x.data_ptr()) if x is not None and count else None)
+        p, a, c, count = check_expand(parents, actions, children, n_parents, self.capacity, env.n_actions, same_buffer,
+                                      lambda x: tensor_len(dev, 'expand', x))
+        ptr, uploaded = upload(dev, count, p, a, c)
         reward = torch.zeros(count, dtype=torch.int32, device=dev)
         done = torch.zeros(count, dtype=torch.uint8, device=dev)
         info = torch.zeros(count, dtype=torch.int32, device=dev)
-        if self._keep:
-            env.sync()                          # (the previous call has read its lists: they may be released now)
-            self._keep = None
-        if count:
-            # uploads, zero fills and the caller's own tensors are work of torch's current stream, the launch runs on the env's: it waits for them
-            env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, True)
-            _cabi.check(_cabi.lib().ngw_snapshot_expand(env._h, None if from_envs else src._s, ptr[0], ptr[1], self._s, ptr[2], int(count),
-                                                        C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), C.c_void_p(info.data_ptr())))
-            self._keep = uploaded or None
+        enqueue_ordered(env, self, lambda: _cabi.lib().ngw_snapshot_expand(
+            env._h, src, ptr[0], ptr[1], self._s, ptr[2], int(count), C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()),
+            C.c_void_p(info.data_ptr())), count, uploaded, device)
         if device:
-            if count:
-                env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, False)
             return Expansion(reward, done.view(torch.bool), (info & 1).bool(), info)
-        env.sync()
-        self._keep = None
         words = info.cpu().numpy().view(np.uint32)
         return Expansion(reward.cpu().numpy(), done.cpu().numpy().view(np.bool_), (words & 1).astype(np.bool_), words)
 
@@ -405,25 +379,8 @@ class Snapshot:
         import torch
         from .vec_env import PlanEval
         env = self.env
-        self._open()
-        if source is not None and from_envs:
-            raise ValueError("rollout: give either source or from_envs")
-        src = self if source is None else source
-        if not from_envs:
-            if not isinstance(src, Snapshot):
-                raise ValueError("source: a Snapshot expected")
-            src._open()
-            if src.env is not env:
-                raise ValueError("source: a snapshot of another env")
-        n_parents = env.num_envs if from_envs else src.capacity
+        src, n_parents, same_buffer = self._source(source, from_envs, 'rollout')
         dev = torch.device('cuda:%d' % env.device)
-
-        def device_len(x):
-            if not isinstance(x, torch.Tensor):
-                return None
-            if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
-                raise ValueError("a contiguous one-dimensional int32 tensor on %s expected" % dev)
-            return int(x.numel())
         if isinstance(plans, torch.Tensor):
             if plans.dtype != torch.int32 or plans.dim() != 2 or not plans.is_contiguous() or plans.device != dev or plans.shape[0] < 1:
                 raise ValueError("plans: a contiguous int32 tensor [T, count] on %s expected" % dev)
@@ -432,38 +389,22 @@ class Snapshot:
             a = check_plan_ids(plans, env.n_actions)
             n_plans, steps = int(a.shape[0]), int(a.shape[1])
             a = np.ascontiguousarray(a.T)       # step-major [T, count]: 64 lanes read consecutive addresses
-        p, c, count = check_rollout(parents, n_plans, children, n_parents, self.capacity, not from_envs and src is self, device_len)
-        ptr, uploaded = [], []
-        for x in (p, a, c):
-            if isinstance(x, np.ndarray):
-                x = torch.from_numpy(x).to(dev)
-                uploaded.append(x)
-            ptr.append(C.c_void_p(x.data_ptr()) if x is not None and count else None)
+        p, c, count = check_rollout(parents, n_plans, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'rollout', x))
+        ptr, uploaded = upload(dev, count, p, a, c)
         ret = torch.zeros(count, dtype=torch.int32, device=dev)
         length = torch.zeros(count, dtype=torch.int32, device=dev)
         ended = torch.zeros(count, dtype=torch.uint8, device=dev)
         info = torch.zeros(count, dtype=torch.int32, device=dev)
-        if self._keep:
-            env.sync()                          # (the previous call has read its lists: they may be released now)
-            self._keep = None
-        if count:
-            # uploads, zero fills and the caller's own tensors are work of torch's current stream, the launch runs on the env's: it waits for them
-            env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, True)
-            _cabi.check(_cabi.lib().ngw_snapshot_rollout(env._h, None if from_envs else src._s, ptr[0], ptr[1], int(count), steps,
-                                                         None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
-                                                         C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr())))
-            self._keep = uploaded or None
+        enqueue_ordered(env, self, lambda: _cabi.lib().ngw_snapshot_rollout(
+            env._h, src, ptr[0], ptr[1], int(count), steps, None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
+            C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr())), count, uploaded, device)
         if device:
-            if count:
-                env.stream_order(torch.cuda.current_stream(env.device).cuda_stream, False)
             return PlanEval(ret, length, ended.view(torch.bool), info)
-        env.sync()
-        self._keep = None
         return PlanEval(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32))
 
     # ------------------------------------------------------------------ slot observations (include/ngw.h ngw_snapshot_lidar / _agent_view / _action_mask)
     def _slots_arg(self, slots):
-        """`slots` of a slot observation, checked and uploaded -> (device pointer or None, count, torch device, the uploaded tensor or None)."""
+        """`slots` of a slot observation, checked and uploaded -> what index_arg returns."""
         self._open()
         return index_arg(self.env, slots, self.capacity, 'slots')
 
@@ -524,14 +465,13 @@ class Snapshot:
         committed: the env's own mask buffer is not touched and stays as current as it was.  One kernel launch.  slots and device: as in
         lidar_observation (an index out of range: an all-False row, F_BAD_INDEX)."""
         import torch
-        from .vec_env import unpack_action_masks
+        from .vec_env import unpack_action_masks, unpack_action_masks_device
         env = self.env
         ptr, count, dev, uploaded = self._slots_arg(slots)
         words = torch.empty(count, dtype=torch.int64, device=dev)
         self._enqueue(lambda: _cabi.lib().ngw_snapshot_action_mask(env._h, self._s, ptr, count, C.c_void_p(words.data_ptr())), count, uploaded, device)
         if device:
-            bits = torch.arange(env.n_actions, device=words.device, dtype=torch.int64)
-            return ((words[:, None] >> bits) & 1).bool()
+            return unpack_action_masks_device(words, env.n_actions)
         return unpack_action_masks(words.cpu().numpy().view(np.uint64), env.n_actions)
 
     # ------------------------------------------------------------------ state keys (include/ngw.h ngw_state_keys; state_keys.py)

@@ -38,6 +38,13 @@ def unpack_action_masks(words, n_actions):
     return np.unpackbits(bits, axis=1, bitorder='little')[:, :n_actions].astype(bool)
 
 
+def unpack_action_masks_device(words, n_actions):
+    """unpack_action_masks with torch ops: a torch int64 tensor [N] of the same words -> a bool tensor [N, n_actions] on its device."""
+    import torch
+    bits = torch.arange(n_actions, device=words.device, dtype=torch.int64)
+    return ((words[:, None] >> bits) & 1).bool()
+
+
 def decode_info_words(words):
     """Packed info words (include/ngw.h NGW_INFO_*) of any shape -> a StepInfo that decodes 'result', 'step_cost_code', 'message_code',
     'message_arg' and 'step_cost' when they are read: what VecNovelGridworld.step_costs / .messages take.  For a lookahead table hand in
@@ -729,10 +736,7 @@ class VecNovelGridworld:
         report info['result'] == True.  device=True: a torch bool tensor on the handle's device, expanded from the packed words with torch
         ops.  The host array is a new array either way; `copy` is accepted for symmetry with the other observation calls."""
         if device:
-            import torch
-            w = self.action_mask_words(device=True)
-            bits = torch.arange(self.n_actions, device=w.device, dtype=torch.int64)
-            return ((w[:, None] >> bits) & 1).bool()
+            return unpack_action_masks_device(self.action_mask_words(device=True), self.n_actions)
         return unpack_action_masks(self.action_mask_words(), self.n_actions)
 
     # ------------------------------------------------------------------ one-step lookahead tables (include/ngw.h ngw_lookahead)
