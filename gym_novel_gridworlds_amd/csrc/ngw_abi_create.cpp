@@ -600,6 +600,7 @@ int ngw_destroy(ngw_handle* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void* p : h->allocs) (void)hipFree(p);
     for (ngw_snapshot* s : h->snaps) delete s;                       // (their slabs were in `allocs`)
+    for (ngw_key_table* t : h->tables) delete t;                     // (likewise)
     for (void* p : h->host_allocs) (void)hipHostFree(p);
     drop_graph(h);
     if (h->info_host) (void)hipHostFree(h->info_host);

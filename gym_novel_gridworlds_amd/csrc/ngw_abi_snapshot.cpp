@@ -1,7 +1,7 @@
 // ngw_abi_snapshot.cpp - device-side snapshots (see ngw_host.h): buffers of saved env states and the one kernel (ngw_snapshot.inc) that moves
 // rows between them and the state slab through index lists.  A restore changes the state behind the library's back-ups, so it reports it
 // as ngw_set_state does (state_written), and then refreshes a fused lidar observation and schedules a refill of the prepared next
-// episodes, as ngw_reset does.  An expand (ngw_expand.inc) steps rows of the state slab or of a snapshot into slots of a snapshot: it commits
+// episodes, as ngw_reset does.  A copy moves rows from slot to slot, inside one snapshot or between two, through the same kernel.  An expand (ngw_expand.inc) steps rows of the state slab or of a snapshot into slots of a snapshot: it commits
 // nothing, so it neither calls state_written() nor touches anything the handle derives from its state, and counts no steps against the
 // prepared-episode cadence (no reset runs).  A rollout (ngw_slot_rollout.inc) steps such rows through a whole action sequence and keeps the end
 // state, the numbers, or both: it commits nothing either.  The slot observations (ngw_slot_observe.inc) read saved rows and write the caller's
@@ -134,6 +134,18 @@ int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_de
     // merely stale (their next reset runs the placement loop: same result).  A refill behind the restore prepares fresh ones, like the
     // one behind an explicit reset; with the counters kept every tag still matches and nothing is scheduled.
     return keep ? NGW_OK : steps_since_refill(h, h->prefetch_every);
+}
+
+int ngw_snapshot_copy(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, ngw_snapshot* dst, const int32_t* dst_idx_dev, int64_t count) {
+    if (!h || !src || !dst) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns(h, src) || !owns(h, dst)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (count < 0 || count > dst->cap) return fail(NGW_E_INVALID_ARG, "copy of %lld states into a snapshot of %lld slots", (long long)count, (long long)dst->cap);
+    if (!src_idx_dev && count > src->cap) return fail(NGW_E_INVALID_ARG, "copy of %lld states from a snapshot of %lld slots", (long long)count, (long long)src->cap);
+    if (src == dst && !src_idx_dev && !dst_idx_dev && count) return fail(NGW_E_INVALID_ARG, "copy of slots 0 .. %lld of a snapshot onto themselves", (long long)count - 1);
+    if (int rc = enter(h)) return rc;
+    // the whole row, the episode counter included; the plain copies only between two buffers (rows of one buffer go through the kernel, whose
+    // pairs are disjoint by the call's contract)
+    return move_rows(h, src != dst && dst->memcpy_path != 0, src->r, src->cap, src_idx_dev, dst->r, dst->cap, dst_idx_dev, count, false);
 }
 
 int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, ngw_snapshot* dst,

@@ -563,4 +563,30 @@ extern "C"
 #endif
 hipError_t ngw_keys_launch(const struct NgwKeys* x, hipStream_t stream);
 
+/* Key table (ngw_table.inc, ngw_abi_table.cpp): an open-addressing set of 64-bit keys in device memory.  key[] and stamp[] hold mask + 1 words
+ * (a power of two); key 0 marks an empty bucket, a stamp is the smallest base + position that ever offered the bucket's key (all ones: none yet).
+ * One insert is two launches: the probe places or finds keys[j], writes its bucket to where[j] (-1: key 0, or no bucket left - NGW_F_TABLE_FULL in
+ * *flags) and lowers the bucket's stamp to base + j; the second launch sets fresh[j] = (stamp[where[j]] == base + j).  A lookup probes with plain
+ * loads and stores nothing but where[0 .. count).  `fresh` is not read by the probe and may be nullptr for a lookup. */
+struct NgwTable {
+    uint64_t* key;
+    uint64_t* stamp;
+    unsigned long long* stored;   /* keys in the table */
+    uint32_t* flags;
+    const uint64_t* keys;         /* [count] */
+    int32_t* where;               /* [count] */
+    uint8_t* fresh;               /* [count] */
+    uint64_t base, mask;
+    int64_t count;
+};
+#define NGW_TABLE_BLOCK 256      /* threads per workgroup: four waves, one key per lane */
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_table_insert_launch(const struct NgwTable* x, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_table_lookup_launch(const struct NgwTable* x, hipStream_t stream);
+
 #endif

@@ -10,6 +10,7 @@
 //   ngw_abi_snapshot.cpp device-side snapshots: save / restore / fork env states by index (ngw_snapshot.inc), expand saved states into new slots (ngw_expand.inc),
 //                        roll action sequences out from saved states (ngw_slot_rollout.inc), observe saved states by slot (ngw_slot_observe.inc),
 //                        64-bit state keys of saved slots and live envs (ngw_keys.inc)
+//   ngw_abi_table.cpp    device-side key tables: a hash set of such keys that outlives the call - insert, lookup, count, clear (ngw_table.inc)
 //
 // Three rules hold in all of them:
 //   1. Guard first.  An entry point that uses the handle's stream or its device state starts with `if (int rc = enter(h)) return rc;`
@@ -61,6 +62,14 @@ struct ngw_snapshot {
     void* slab = nullptr;
     int memcpy_path = 0;                  // NGW_SNAP_MEMCPY=1 when it was created: a save / restore without index lists runs as seven device-to-device copies instead of the kernel (A/B)
     NgwSnapRows r{};
+};
+
+// A device-side key table (ngw_abi_table.cpp): key[buckets] | stamp[buckets] | the counter of stored keys, in ONE allocation of its handle.
+struct ngw_key_table {
+    int64_t cap = 0;
+    uint64_t buckets = 0;                 // the smallest power of two >= 2 * cap
+    uint64_t* slab = nullptr;
+    uint64_t base = 0;                    // keys ever offered since the last clear: the stamp of position j of an insert is base + j
 };
 
 struct ngw_handle {
@@ -205,7 +214,8 @@ struct ngw_handle {
     int32_t plan_cap = 0, plan_n = 0;
     int plan_major = 0;                   // NGW_PLAN_ORDER=plan when the buffers were first allocated: the plan-major block order (A/B, tools/plan_cost.py)
     std::vector<ngw_snapshot*> snaps;     // open snapshots (ngw_snapshot_create); their slabs are in `allocs`, ngw_destroy deletes what is left
-    long long solo_starts = 0;            // launches of the one-env resident loop (ngw_debug_solo_starts)
+    std::vector<ngw_key_table*> tables;   // open key tables (ngw_key_table_create); likewise
+    long long solo_starts = 0;           // launches of the one-env resident loop (ngw_debug_solo_starts)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;
     int graph_steps = 0;

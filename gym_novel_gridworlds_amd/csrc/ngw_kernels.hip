@@ -30,7 +30,7 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file EIGHTEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file NINETEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
@@ -40,7 +40,7 @@
 //   11: device-side snapshots (ngw_snapshot.inc)   12: one-step lookahead tables (ngw_lookahead.inc)   13: plan evaluation (ngw_plans.inc)
 //   14: snapshot expand (ngw_expand.inc)   15: snapshot rollout (ngw_slot_rollout.inc; it shares ngw_expand.inc's row mover)
 //   16: slot observations (ngw_slot_observe.inc: lidar rows, agent views, action masks of saved states; the lidar one shares the row mover too)
-//   17: state keys (ngw_keys.inc: 64-bit hashes of saved slots and live envs)
+//   17: state keys (ngw_keys.inc: 64-bit hashes of saved slots and live envs)   18: the key table (ngw_table.inc: a hash set of such keys)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -403,6 +403,9 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #endif
 #if NGW_HAS(17)
 #include "ngw_keys.inc"
+#endif
+#if NGW_HAS(18)
+#include "ngw_table.inc"
 #endif
 
 // ---------------------------------------------------------------- LidarInFront observation kernel (stand-alone launch)
@@ -907,3 +910,23 @@ extern "C" hipError_t ngw_keys_launch(const NgwKeys* x, hipStream_t stream) {
     return with_row_piece(x->S2, [&](auto V) { return launch_kernel<ngw_keys_kernel<decltype(V)::value>>(grid, block, 0, stream, *x); });
 }
 #endif  // NGW_HAS(17)
+
+#if NGW_HAS(18)
+// the key table (ngw_table.inc): x->count keys offered to / looked up in the table of x->mask + 1 buckets; one lane per key
+static bool table_args_ok(const NgwTable* x, bool insert) {
+    const int64_t blocks = (x->count + NGW_TABLE_BLOCK - 1) / NGW_TABLE_BLOCK;
+    return x->count > 0 && blocks <= 0x7FFFFFFFll && x->key && x->stamp && x->stored && x->flags && x->keys && x->where && (!insert || x->fresh) &&
+           x->mask >= 1 && x->mask < 0x7FFFFFFFull && (x->mask & (x->mask + 1)) == 0;
+}
+extern "C" hipError_t ngw_table_insert_launch(const NgwTable* x, hipStream_t stream) {
+    if (!table_args_ok(x, true)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((x->count + NGW_TABLE_BLOCK - 1) / NGW_TABLE_BLOCK)), block(NGW_TABLE_BLOCK);
+    const hipError_t e = launch_kernel<ngw_table_probe_kernel<true>>(grid, block, 0, stream, *x);
+    return e != hipSuccess ? e : launch_kernel<ngw_table_fresh_kernel>(grid, block, 0, stream, *x);
+}
+extern "C" hipError_t ngw_table_lookup_launch(const NgwTable* x, hipStream_t stream) {
+    if (!table_args_ok(x, false)) return hipErrorInvalidValue;
+    const dim3 grid((unsigned)((x->count + NGW_TABLE_BLOCK - 1) / NGW_TABLE_BLOCK)), block(NGW_TABLE_BLOCK);
+    return launch_kernel<ngw_table_probe_kernel<false>>(grid, block, 0, stream, *x);
+}
+#endif  // NGW_HAS(18)

@@ -12,7 +12,9 @@
 // When they are (always in the contiguous case, one permuted row in four otherwise) the group moves a byte head up to the next dword
 // boundary, aligned dwords, and a byte tail; otherwise bytes all the way.
 //
-// Rows of one call never overlap (the host side's contract: distinct destination rows), source and destination are different allocations.
+// Rows of one call never overlap (the host side's contract: distinct destination rows).  Source and destination are different allocations, or -
+// a slot-to-slot copy inside one snapshot (ngw_snapshot_copy) - rows of one allocation of which no destination is also a source: the kernel
+// addresses whole rows of either set by index and assumes nothing about which set is the state slab.
 
 template <typename T>
 __device__ __forceinline__ void snap_copy(void* dst, const void* src, int n, int g) {

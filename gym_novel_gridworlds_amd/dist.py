@@ -135,6 +135,15 @@ class ShardedVecNovelGridworld:
         A key depends on the state alone, not on the env index or the rank, so keys compare across ranks."""
         return self.local.state_keys(envs, fields, device)
 
+    def key_table(self, capacity):
+        """A device-side key table of this rank's shard (VecNovelGridworld.key_table): rank-local, no collective.  Keys are rank-independent
+        by contract, so every rank may offer its own states' keys to its own table; the tables are not merged."""
+        return self.local.key_table(capacity)
+
+    def insert_state_keys(self, table, envs=None, fields=KEY_STATE, device=False):
+        """The keys of this rank's envs offered to `table` (VecNovelGridworld.insert_state_keys)."""
+        return self.local.insert_state_keys(table, envs, fields, device)
+
     def fork(self, src, keep_episode=False):
         """Every LOCAL env e becomes a copy of local env src[e] (VecNovelGridworld.fork)."""
         return self.local.fork(src, keep_episode)

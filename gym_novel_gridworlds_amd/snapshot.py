@@ -16,6 +16,8 @@
     ok = pool.action_masks(nodes)                  # ... and the valid-action masks; no env is touched
     k = pool.keys(nodes)                           # 64-bit state keys: "are these two nodes the same state?" (state_keys.py: the contract)
     first, inverse = pool.unique(nodes)            # ... and the groups of equal states among them
+    k, found = pool.insert_keys(table, nodes)      # ... and which of them no earlier call has seen (key_table.py: env.key_table(capacity))
+    archive.copy(nodes[found.fresh], free, source=pool)   # slot to slot, unchanged: the new ones move from a scratch pool into an archive pool
 
 What a restored env does next: env e, when it next resets, draws from env e's OWN stream at its (restored or kept) episode counter.  Two
 forks of one slot share the rest of the current episode and differ from their next reset on; restoring the same env from the same slot
@@ -146,6 +148,34 @@ def check_rollout(parents, n_plans, children, n_parents, capacity, same_buffer, 
     return p, c, count
 
 
+def check_copy(src_slots, dst_slots, n_src, capacity, same_buffer, device_len=None):
+    """The host-side checks of one slot-to-slot copy, as check_expand checks children: src_slots index rows [0, n_src) and may repeat,
+    dst_slots index slots [0, capacity) and must be distinct, both have one length (None = no list: 0 .. count-1, which must exist; without
+    any list: every slot of the source), and - where source and destination are the same buffer - no destination is also a source.
+    device_len as in check_expand.  Returns (src_slots, dst_slots, count)."""
+    on_dev = device_len or (lambda x: None)
+    n_s, n_d = on_dev(src_slots), on_dev(dst_slots)
+    host_lists = n_s is None and n_d is None
+    if n_s is None and src_slots is not None:
+        src_slots = check_indices(src_slots, n_src, False, 'src_slots')
+        n_s = int(src_slots.size)
+    if n_d is None and dst_slots is not None:
+        dst_slots = check_indices(dst_slots, capacity, True, 'dst_slots')
+        n_d = int(dst_slots.size)
+    count = pair_count(n_s, n_d, int(n_src))
+    if src_slots is None and count > n_src:
+        raise ValueError("src_slots: no list given and %d pairs for %d slots" % (count, n_src))
+    if count > capacity:
+        raise ValueError("dst_slots: %d pairs for a snapshot of %d slots" % (count, capacity))
+    if same_buffer and count and host_lists:
+        hs = np.arange(count) if src_slots is None else src_slots
+        hd = np.arange(count) if dst_slots is None else dst_slots
+        both = np.intersect1d(hs, hd)
+        if both.size:
+            raise ValueError("dst_slots: slot %d is also a source of the same call (source and destination are one buffer)" % int(both[0]))
+    return src_slots, dst_slots, count
+
+
 def check_slots(slots, capacity, device_len=None, distinct=False, name='slots'):
     """The host-side checks of one index list that reads or writes rows [0, capacity) (the slot observations, the state keys, save / restore):
     None = every row, 0 .. capacity-1; a list / numpy array may repeat unless `distinct` (its length is not bound by the capacity).
@@ -160,14 +190,15 @@ def check_slots(slots, capacity, device_len=None, distinct=False, name='slots'):
     return slots, int(slots.size)
 
 
-def tensor_len(dev, name, x):
-    """The one check of an argument that may be a device tensor used in place: the length of x when it is a contiguous one-dimensional int32
-    torch tensor on `dev` (the env's torch device), None when it is no tensor, ValueError for any other tensor."""
+def tensor_len(dev, name, x, dtype='int32'):
+    """The one check of an argument that may be a device tensor used in place: the length of x when it is a contiguous one-dimensional
+    torch tensor of `dtype` (int32: an index list; int64: a key list) on `dev` (the env's torch device), None when it is no tensor, ValueError
+    for any other tensor."""
     import torch
     if not isinstance(x, torch.Tensor):
         return None
-    if x.dtype != torch.int32 or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
-        raise ValueError("%s: a contiguous one-dimensional int32 tensor on %s expected" % (name, dev))
+    if x.dtype != getattr(torch, dtype) or x.dim() != 1 or not x.is_contiguous() or x.device != dev:
+        raise ValueError("%s: a contiguous one-dimensional %s tensor on %s expected" % (name, dtype, dev))
     return int(x.numel())
 
 
@@ -301,6 +332,22 @@ class Snapshot:
         slower): an index tensor must stay unchanged until the env's stream has passed the call, as the class says."""
         self.env._lidar_rows_fresh = False
         self._copy(_cabi.lib().ngw_snapshot_restore, slots, self.capacity, 'slots', envs, self.env.num_envs, 'envs', KEEP_EPISODE if keep_episode else 0)
+
+    def copy(self, src_slots, dst_slots, source=None):
+        """slot[dst_slots[j]] := slot[src_slots[j]] of `source` (another Snapshot of the same env; default: this one), unchanged: the whole
+        row, episode counter included - a search moves the children that turned out to be new from a scratch pool into an archive pool
+        without restoring them into envs.  Sources may repeat; the destinations of one call must be distinct, and inside one buffer no
+        destination may also be a source.  Lists and numpy arrays are checked here, as expand() checks children; torch int32 tensors on the
+        env's device are used in place, unchecked: an index out of range skips that copy (F_BAD_INDEX).  None means 0 .. count-1 (without
+        any list: every slot of the source).  Ordered like save(): no host wait, torch's stream is not ordered behind the copy."""
+        import torch
+        env = self.env
+        src, n_src, same_buffer = self._source(source, False, 'copy')
+        dev = torch.device('cuda:%d' % env.device)
+        s, d, count = check_copy(src_slots, dst_slots, n_src, self.capacity, same_buffer, lambda x: tensor_len(dev, 'copy', x))
+        ptr, uploaded = upload(dev, count, s, d)
+        enqueue_ordered(env, self, lambda: _cabi.lib().ngw_snapshot_copy(env._h, src, ptr[0], self._s, ptr[1], int(count)), count, uploaded, True,
+                        behind=False)
 
     def _source(self, source, from_envs, what):
         """Where the parents of one `what` (expand / rollout) call live -> (the source snapshot's C handle - None: the env's current states -,
@@ -497,6 +544,15 @@ class Snapshot:
         keys(): np.unique on the host, or with device=True torch.unique and a scatter-amin on the env's device (no new kernel).  The groups
         are numbered in the order of their keys, which differs between the two (torch compares the keys as int64)."""
         return unique_of_keys(self.keys(slots, fields, device))
+
+    def insert_keys(self, table, slots=None, fields=KEY_STATE, device=False):
+        """keys(slots, fields) offered to `table` (a KeyTable of the same env): (keys, KeyInsert(where, fresh)) - which of these slots hold a
+        state the table has not seen before.  The keys stay on the device between the two calls: no host wait in between.  device=True: all
+        three as torch tensors, ordered behind the launches on torch's current stream; otherwise numpy arrays (keys uint64)."""
+        table._open_for(self.env)
+        keys = self.keys(slots, fields, device=True)
+        found = table.insert(keys, device=device)
+        return (keys if device else keys.cpu().numpy().view(np.uint64)), found
 
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""

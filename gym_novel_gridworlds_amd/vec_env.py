@@ -975,6 +975,24 @@ class VecNovelGridworld:
                         device)
         return words if device else words.cpu().numpy().view(np.uint64)
 
+    # ------------------------------------------------------------------ device-side key tables (key_table.py, include/ngw.h ngw_key_table_*)
+    def key_table(self, capacity):
+        """A hash set of 64-bit keys on the device with room for `capacity` of them: KeyTable.insert / lookup / clear / close, len().  It
+        answers "have I seen this state before?" across calls, where Snapshot.unique() groups equal states within one call.  It belongs
+        to this env and is closed with it, and by an in-place rebuild() (inject_novelty)."""
+        from .key_table import KeyTable
+        t = KeyTable(self, capacity)
+        self.__dict__.setdefault('_key_tables', []).append(t)
+        return t
+
+    def insert_state_keys(self, table, envs=None, fields=KEY_STATE, device=False):
+        """state_keys(envs, fields) offered to `table` (a KeyTable of this env): (keys, KeyInsert(where, fresh)) - Snapshot.insert_keys() for
+        the envs' CURRENT states; the keys stay on the device between the two calls."""
+        table._open_for(self)
+        keys = self.state_keys(envs, fields, device=True)
+        found = table.insert(keys, device=device)
+        return (keys if device else keys.cpu().numpy().view(np.uint64)), found
+
     def fork(self, src, keep_episode=False):
         """Every env e becomes a copy of env src[e] (src: num_envs indices - a list / numpy array, checked, or a torch int32 tensor on the
         env's device), through an internal scratch snapshot: all states are saved first, so src may name any env, itself included.  The
@@ -988,13 +1006,14 @@ class VecNovelGridworld:
         s.restore(slots=src, keep_episode=keep_episode)
 
     def _drop_snapshots(self, sync=True):
-        """The handle is going: its snapshots' buffers go with it (ngw_destroy), the Python objects raise from now on."""
-        snaps = self.__dict__.get('_snapshots', ())
+        """The handle is going: its snapshots' and key tables' buffers go with it (ngw_destroy), the Python objects raise from now on."""
+        snaps = list(self.__dict__.get('_snapshots', ())) + list(self.__dict__.get('_key_tables', ()))
         if sync and self._h and any(s._keep for s in snaps):
             self.sync()                                       # (a queued save / restore may still be reading its uploaded index lists)
         for s in snaps:
             s._invalidate()
         self.__dict__['_snapshots'] = []
+        self.__dict__['_key_tables'] = []
         self.__dict__.pop('_fork_snap', None)
 
     # ------------------------------------------------------------------ timing (bench roofline leg) / hipGraph stepping

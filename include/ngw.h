@@ -46,6 +46,7 @@ extern "C" {
 #define NGW_F_INVALID_ACTION 1u
 #define NGW_F_PLACEMENT 2u
 #define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros); ngw_state_keys: a row index outside its range (that key is 0) */
+#define NGW_F_TABLE_FULL 8u     /* ngw_key_table_insert: a key found neither itself nor a free bucket after probing every bucket (it was refused: where = -1, fresh = 0) */
 
 /* action kinds (act_kind[]); act_arg[] = recipe index (CRAFT) or item id (SELECT) */
 enum { NGW_ACT_FORWARD = 0, NGW_ACT_LEFT = 1, NGW_ACT_RIGHT = 2, NGW_ACT_BREAK = 3, NGW_ACT_PLACE = 4,
@@ -482,6 +483,15 @@ int ngw_snapshot_save(ngw_handle* h, ngw_snapshot* s, const int32_t* envs_dev, c
 int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, const int32_t* envs_dev, int64_t count, int flags);
 int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t count, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv,
                      int32_t* selected, int32_t* step_count, uint32_t* episode);
+/* Slot to slot, unchanged: slot dst_idx[j] of `dst` := slot src_idx[j] of `src` for j < count - the whole seven-array row, the episode counter
+ * included (a search moves the children that turned out to be new from a scratch pool into an archive pool without committing them to an env).
+ * Index lists are int32 arrays in DEVICE memory, NULL means 0 .. count-1; an index out of range skips that copy and raises NGW_F_BAD_INDEX.
+ * Sources may repeat; the destinations of one call must be distinct.  src == dst is allowed when no destination of the call is also a source
+ * of the same call (both lists NULL is then refused); a violated rule leaves those slots unspecified and never addresses out of bounds.
+ * The same kernel as save and restore, one launch on the handle's stream; does not wait; nothing else changes.
+ * NGW_E_INVALID_ARG: a NULL handle or snapshot; one that is not an open snapshot of this handle; count < 0 or above dst's capacity; src_idx == NULL
+ * with count above src's capacity. */
+int ngw_snapshot_copy(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, ngw_snapshot* dst, const int32_t* dst_idx_dev, int64_t count);
 
 /* Snapshot expand: step saved states into new slots, commit nothing (the node expansion of a tree search: beam search, MCTS, archives of
  * states, breadth-first solvers - lookahead tables and plan evaluation return numbers and throw the stepped state away, this keeps it).
@@ -625,6 +635,38 @@ int ngw_snapshot_action_mask(ngw_handle* h, ngw_snapshot* s, const int32_t* slot
  * NGW_E_INVALID_ARG: a NULL handle or output; a snapshot that is not an open snapshot of this handle; count < 0; fields == 0 or a bit above
  * NGW_KEY_ALL; idx_dev == NULL with count above the row count. */
 int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev);
+
+/* Key table: an open-addressing hash set of 64-bit keys in device memory - "have I seen this state BEFORE?" across the calls of a search that
+ * runs many iterations (transposition tables, duplicate removal in breadth-first solvers, Go-Explore archives, count-based bonuses).  A table
+ * belongs to the handle that created it; it stores keys and nothing else: a caller keeps what it wants per state (visit counts, the best return,
+ * the archive slot) in arrays of its own of `buckets` entries, indexed by `where`.
+ *   buckets  the smallest power of two >= 2 * capacity (not stored in the ABI: compute it); capacity in [1, 2^29].
+ *   insert   for j < count: where[j] (int32) = the bucket that holds keys[j], and fresh[j] (uint8, 0 / 1) = 1 exactly when keys[j] was not in the
+ *            table before this call AND j is the smallest position of this call that holds that key.  `fresh` is deterministic: it does not depend
+ *            on the order in which the device runs the keys.  Equal keys get equal `where`, in this call and in every later one until the table is
+ *            cleared; different keys get different `where`; every value lies in [0, buckets).  WHICH bucket a key gets is not part of the contract:
+ *            it may depend on races between different keys that collide.
+ *   lookup   where[j] = the bucket that holds keys[j], or -1 when the table does not hold it.  It changes nothing.
+ *   count    *n = the number of keys in the table (a stream-ordered copy of a device counter; waits for the stream).
+ *   clear    empties the table.
+ * Key 0 is never stored: it is the empty-bucket mark, and what ngw_state_keys returns for a bad index (which has raised NGW_F_BAD_INDEX already).
+ * For key 0, where = -1 and fresh = 0, and no flag is raised.
+ * There is no probe limit short of the table: a key that finds neither itself nor a free bucket after probing EVERY bucket is refused - where = -1,
+ * fresh = 0, and the sticky NGW_F_TABLE_FULL (ngw_error_flags) is raised; a refusal therefore means that all `buckets` buckets are occupied.
+ * keys_dev (uint64 [count]), where_dev (int32 [count]) and fresh_dev (uint8 [count]) are DEVICE memory; exactly [0 .. count) of each output is
+ * written.  count == 0 is a no-op.  Insert is two kernel launches (ngw_table.inc: the probe, then `fresh` from the buckets' stamps), lookup one;
+ * all are enqueued on the handle's stream and do not wait.  Every call of one table must run on the handle's stream in the order of the calls:
+ * concurrent inserts into one table from two streams are not supported.  The calls write no env state: nothing is committed, every derived buffer
+ * stays as current as it was, a captured graph stays valid.
+ * ngw_key_table_destroy waits for the stream (queued calls may still use the table) and frees it; ngw_destroy frees what is still open.
+ * NGW_E_INVALID_ARG: a NULL handle, table, keys or output; a table that is not an open table of this handle; capacity outside [1, 2^29]; count < 0. */
+typedef struct ngw_key_table ngw_key_table;
+int ngw_key_table_create(ngw_handle* h, int64_t capacity, ngw_key_table** out);
+int ngw_key_table_destroy(ngw_handle* h, ngw_key_table* t);
+int ngw_key_table_clear(ngw_handle* h, ngw_key_table* t);
+int ngw_key_table_insert(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_dev, int64_t count, int32_t* where_dev, uint8_t* fresh_dev);
+int ngw_key_table_lookup(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_dev, int64_t count, int32_t* where_dev);
+int ngw_key_table_count(ngw_handle* h, ngw_key_table* t, int64_t* n);
 
 /* One-step lookahead tables: every action's outcome for every env, without taking a step.
  * For a handle with A = n_actions the table of the CURRENT state is three arrays - reward int32, done uint8, info uint32 (the NGW_INFO_* packing).
