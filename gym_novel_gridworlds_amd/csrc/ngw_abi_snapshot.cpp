@@ -7,6 +7,7 @@
 // state, the numbers, or both: it commits nothing either.  The slot observations (ngw_slot_observe.inc) read saved rows and write the caller's
 // buffers: lidar rows, agent views, action masks of saved states.  They commit nothing, and leave the env's own observation buffers alone.
 // The state keys (ngw_keys.inc) hash rows of a snapshot or of the state slab into the caller's buffer: they commit nothing either.
+// The successor keys (ngw_successors.inc) are the keys of every action's child of such rows, with no child stored: they commit nothing either.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -261,6 +262,34 @@ int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64
     x.src = s ? s->r : state_rows(h); x.idx = idx_dev; x.flags = h->b.flags; x.keys = keys_dev;
     x.count = count; x.rows = (int32_t)rows; x.S2 = h->proto.S2; x.K = h->proto.K; x.fields = fields;
     HIP_TRY(ngw_keys_launch(&x, h->stream));
+    return NGW_OK;
+}
+
+int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev, int32_t* reward_dev,
+                       uint8_t* done_dev, uint32_t* info_dev) {
+    if (!h || !keys_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!fields || (fields & ~NGW_KEY_ALL)) return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)fields);
+    const int64_t rows = s ? s->cap : h->n, A = h->spec.n_actions;
+    // (the flattened [count * A] keys are what ngw_state_keys and the key table take: the same range)
+    if (count < 0 || count > 0x7FFFFFFFll * NGW_EPB / A) return fail(NGW_E_INVALID_ARG, "successor keys of %lld rows by %lld actions", (long long)count, (long long)A);
+    if (!idx_dev && count > rows) return fail(NGW_E_INVALID_ARG, "successor keys of %lld rows from %lld %s", (long long)count, (long long)rows, s ? "slots" : "envs");
+    const size_t lds = NGW_SUCC_LDS_BYTES(h->proto.MS, h->proto.KP);
+    if (lds > NGW_SUCC_LDS_MAX)
+        return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps two sets of a wavefront's 64 maps in LDS (ngw_successor_keys: the stepped rows and "
+                                       "the parents they are compared with) and they need %zu B, more than 160 KiB; ngw_snapshot_expand followed by "
+                                       "ngw_state_keys is available", h->proto.S, lds);
+    if (int rc = enter(h)) return rc;                 // (s == NULL: the one-env loop has ended, HBM holds the env's state)
+    if (count == 0) return NGW_OK;
+    NgwLaunch a = h->proto;
+    a.b = h->b;
+    a.autoreset = h->autoreset;
+    a.horizon = h->horizon;
+    NgwSuccessors x{};
+    x.src = s ? s->r : state_rows(h); x.idx = idx_dev; x.keys = keys_dev;
+    x.reward = reward_dev; x.done = done_dev; x.info = info_dev;
+    x.count = count; x.rows = (int32_t)rows; x.fields = fields;
+    HIP_TRY(ngw_successors_launch(h->dspec, &a, &x, h->ext, h->stream));
     return NGW_OK;
 }
 

@@ -563,6 +563,29 @@ extern "C"
 #endif
 hipError_t ngw_keys_launch(const struct NgwKeys* x, hipStream_t stream);
 
+/* Successor keys (ngw_successors.inc, ngw_abi_snapshot.cpp): for parent j = row idx[j] of `src` (a snapshot or the state slab; a NULL list = j itself)
+ * and every action a of the spec, keys[j * A + a] = the key under `fields` of the row ngw_expand_kernel would store for (j, a), and reward / done /
+ * info [j * A + a] (any may be nullptr) what it would report.  An index outside [0, rows) is never used as an address: its A keys and reports are 0
+ * and NGW_F_BAD_INDEX is raised.  Nothing but [0, count * A) of the given arrays and the flags word is stored.  The launch block is the handle's
+ * (S, K, MS, KP, autoreset, horizon, the flags word); the kernel keeps two sets of 64 rows in LDS, carved by itself. */
+struct NgwSuccessors {
+    NgwSnapRows src;
+    const int32_t* idx;
+    uint64_t* keys;
+    int32_t* reward;
+    uint8_t* done;
+    uint32_t* info;
+    int64_t count;
+    int32_t rows;
+    uint32_t fields;
+};
+#define NGW_SUCC_LDS_BYTES(MS, KP) ((size_t)2 * NGW_EPB * ((size_t)(MS) + 4u * (size_t)(KP)))   /* a work and a pristine set of 64 rows */
+#define NGW_SUCC_LDS_MAX ((size_t)160 * 1024)                                                    /* what a CU of gfx950 has */
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_successors_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwSuccessors* x, int ext, hipStream_t stream);
+
 /* Key table (ngw_table.inc, ngw_abi_table.cpp): an open-addressing set of 64-bit keys in device memory.  key[] and stamp[] hold mask + 1 words
  * (a power of two); key 0 marks an empty bucket, a stamp is the smallest base + position that ever offered the bucket's key (all ones: none yet).
  * One insert is two launches: the probe places or finds keys[j], writes its bucket to where[j] (-1: key 0, or no bucket left - NGW_F_TABLE_FULL in

@@ -30,7 +30,7 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file NINETEEN times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file TWENTY times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
@@ -41,6 +41,7 @@
 //   14: snapshot expand (ngw_expand.inc)   15: snapshot rollout (ngw_slot_rollout.inc; it shares ngw_expand.inc's row mover)
 //   16: slot observations (ngw_slot_observe.inc: lidar rows, agent views, action masks of saved states; the lidar one shares the row mover too)
 //   17: state keys (ngw_keys.inc: 64-bit hashes of saved slots and live envs)   18: the key table (ngw_table.inc: a hash set of such keys)
+//   19: successor keys (ngw_successors.inc: the key of every action's child; it shares ngw_expand.inc's row mover and ngw_keys.inc's terms)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -392,7 +393,7 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #if NGW_HAS(13)
 #include "ngw_plans.inc"
 #endif
-#if NGW_HAS(14) || NGW_HAS(15) || NGW_HAS(16)
+#if NGW_HAS(14) || NGW_HAS(15) || NGW_HAS(16) || NGW_HAS(19)
 #include "ngw_expand.inc"
 #endif
 #if NGW_HAS(15)
@@ -401,8 +402,11 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #if NGW_HAS(16)
 #include "ngw_slot_observe.inc"
 #endif
-#if NGW_HAS(17)
+#if NGW_HAS(17) || NGW_HAS(19)
 #include "ngw_keys.inc"
+#endif
+#if NGW_HAS(19)
+#include "ngw_successors.inc"
 #endif
 #if NGW_HAS(18)
 #include "ngw_table.inc"
@@ -910,6 +914,24 @@ extern "C" hipError_t ngw_keys_launch(const NgwKeys* x, hipStream_t stream) {
     return with_row_piece(x->S2, [&](auto V) { return launch_kernel<ngw_keys_kernel<decltype(V)::value>>(grid, block, 0, stream, *x); });
 }
 #endif  // NGW_HAS(17)
+
+#if NGW_HAS(19)
+// successor keys (ngw_successors.inc): a = the handle's launch block with a.autoreset, a.horizon (S, K, MS, KP and the flags word are read; the
+// kernel carves its own LDS: NGW_SUCC_LDS_BYTES); one wave per 64 parents
+extern "C" hipError_t ngw_successors_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwSuccessors* x, int ext, hipStream_t stream) {
+    const int64_t blocks = (x->count + NGW_EPB - 1) / NGW_EPB;
+    if (x->count <= 0 || blocks > 0x7FFFFFFFll || x->rows < 1 || a->S < 3 || a->S > NGW_MAX_MAP_SIZE || a->K < 1 || a->K > NGW_MAX_ITEMS || a->MS < a->S2 ||
+        (a->MS & 3) || a->KP < a->K || NGW_SUCC_LDS_BYTES(a->MS, a->KP) > NGW_SUCC_LDS_MAX || !x->fields || (x->fields & ~NGW_KEY_ALL) || !a->b.flags ||
+        !x->src.map || !x->keys)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks), block(NGW_EPB);
+    return with_row_piece(a->S2, [&](auto V) {
+        return with_flag(ext != 0, [&](auto E) {
+            return launch_kernel<ngw_successors_kernel<decltype(V)::value, decltype(E)::value>>(grid, block, NGW_SUCC_LDS_BYTES(a->MS, a->KP), stream, dspec, *a, *x);
+        });
+    });
+}
+#endif  // NGW_HAS(19)
 
 #if NGW_HAS(18)
 // the key table (ngw_table.inc): x->count keys offered to / looked up in the table of x->mask + 1 buckets; one lane per key

@@ -32,6 +32,8 @@ __device__ __forceinline__ uint64_t key_term(uint32_t tag, uint32_t index, uint3
 }
 // the term of map group `grp` whose four cells are the little-endian dword w; an all-air group contributes nothing
 __device__ __forceinline__ uint64_t key_map_term(uint32_t grp, uint32_t w) { return w ? key_term(1u, grp, w) : 0ull; }
+// the term of inventory entry `item` that holds v; an empty entry contributes nothing
+__device__ __forceinline__ uint64_t key_inv_term(uint32_t item, uint32_t v) { return v ? key_term(3u, item, v) : 0ull; }
 
 // XOR over the 16 lanes of a DPP row, left in every lane of it
 __device__ __forceinline__ uint32_t key_row_xor(uint32_t v) {
@@ -70,10 +72,7 @@ __device__ __forceinline__ uint64_t key_row_part(const int8_t* __restrict__ map,
         }
     }
     if (fields & NGW_KEY_INV)
-        for (int p = g; p < K; p += NGW_SNAP_GROUP) {
-            const uint32_t v = (uint32_t)inv[p];
-            if (v) k ^= key_term(3u, (uint32_t)p, v);
-        }
+        for (int p = g; p < K; p += NGW_SNAP_GROUP) k ^= key_inv_term((uint32_t)p, (uint32_t)inv[p]);
     return k;
 }
 

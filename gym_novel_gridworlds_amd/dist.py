@@ -144,6 +144,15 @@ class ShardedVecNovelGridworld:
         """The keys of this rank's envs offered to `table` (VecNovelGridworld.insert_state_keys)."""
         return self.local.insert_state_keys(table, envs, fields, device)
 
+    def successor_keys(self, envs=None, fields=KEY_STATE, device=False, reports=True):
+        """The successor keys of this rank's shard (VecNovelGridworld.successor_keys): `envs` are the shard's own indices; rank-local, no
+        collective.  Keys are rank-independent, so the children's keys compare across ranks as the states' own keys do."""
+        return self.local.successor_keys(envs, fields, device, reports)
+
+    def insert_successor_keys(self, table, envs=None, fields=KEY_STATE, device=False):
+        """The successor keys of this rank's envs offered to `table` (VecNovelGridworld.insert_successor_keys)."""
+        return self.local.insert_successor_keys(table, envs, fields, device)
+
     def fork(self, src, keep_episode=False):
         """Every LOCAL env e becomes a copy of local env src[e] (VecNovelGridworld.fork)."""
         return self.local.fork(src, keep_episode)

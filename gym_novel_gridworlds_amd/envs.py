@@ -332,6 +332,15 @@ class _NovelGridworldEnv(_EnvBase):
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
         return int(vec.state_keys(fields=fields)[0])
 
+    def successor_keys(self, fields=KEY_STATE, device=False, reports=True):
+        """The key of the state every action would leave this env in (before any reset), without taking a step: a SuccessorKeys of 'keys'
+        uint64 [A] - entry a is what state_key(fields) would return after step(a) - and, unless reports=False, lookahead()'s 'reward' / 'done'
+        / 'result' / 'info' [A]; see VecNovelGridworld.successor_keys."""
+        from .snapshot import SuccessorKeys
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        return SuccessorKeys(*[None if x is None else x[0] for x in vec.successor_keys(fields=fields, device=device, reports=reports)])
+
     def get_observation(self):
         assert not self.max_items < len(self.items), "Cannot have more than " + str(self.max_items) + " items"
         return {'map': self.map, 'agent_location': self.agent_location, 'agent_facing_id': self.agent_facing_id,

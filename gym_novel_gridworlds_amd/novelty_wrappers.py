@@ -56,6 +56,9 @@ class NoveltyWrapper(object):
     def state_key(self, fields=KEY_STATE):
         return self.env.state_key(fields)
 
+    def successor_keys(self, fields=KEY_STATE, device=False, reports=True):
+        return self.env.successor_keys(fields=fields, device=device, reports=reports)
+
     def render(self, mode='human', **kwargs):
         return self.env.render(mode, **kwargs)
 

@@ -18,6 +18,7 @@
     first, inverse = pool.unique(nodes)            # ... and the groups of equal states among them
     k, found = pool.insert_keys(table, nodes)      # ... and which of them no earlier call has seen (key_table.py: env.key_table(capacity))
     archive.copy(nodes[found.fresh], free, source=pool)   # slot to slot, unchanged: the new ones move from a scratch pool into an archive pool
+    s, found = pool.insert_successor_keys(table, nodes)   # the keys of every action's child, no child stored: expand only fresh_pairs(found.fresh)
 
 What a restored env does next: env e, when it next resets, draws from env e's OWN stream at its (restored or kept) episode counter.  Two
 forks of one slot share the rest of the current episode and differ from their next reset on; restoring the same env from the same slot
@@ -291,6 +292,82 @@ def all_actions_pairs(parents, first_child, n_actions):
     return np.repeat(p, A), ids % A, ids + int(first_child), (P, A)
 
 
+class SuccessorKeys(collections.namedtuple('SuccessorKeys', 'keys reward done result info')):
+    """What successor_keys() returns, each [count, A]: 'keys' - entry (j, a) the key of the child an expand of parent j with action a would
+    write, numpy uint64 or a torch int64 tensor over the same bits - and the Expansion fields of that expand: 'reward' int32, 'done' bool,
+    'result' bool, 'info' uint32 (int32 as a tensor).  With reports=False the four report fields are None.  Fields by name too: s['keys']."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    @property
+    def goal(self):
+        """Expansion.goal of every (parent, action)."""
+        return Expansion.goal.fget(self)
+
+    @property
+    def died(self):
+        """Expansion.died of every (parent, action)."""
+        return Expansion.died.fget(self)
+
+
+def fresh_pairs(fresh):
+    """The (parent position, action id) of every True of a [count, A] `fresh` (insert_successor_keys), in row-major order - the order of the
+    flattened keys, so position j * A + a maps back by divmod.  numpy arrays (int64), or torch tensors for a tensor."""
+    A = int(fresh.shape[1])
+    if hasattr(fresh, 'data_ptr'):
+        import torch
+        pos = torch.nonzero(fresh.reshape(-1)).reshape(-1)
+        return torch.div(pos, A, rounding_mode='floor'), pos % A
+    return divmod(np.flatnonzero(np.asarray(fresh).reshape(-1)), A)
+
+
+class MapsTooLarge(_cabi.NgwError, ValueError):
+    """successor_keys on a handle whose maps the call cannot hold: the library's refusal (NGW_E_INVALID_ARG, a ValueError as every argument
+    error is) - and an NgwError, because no argument of the call is wrong: the handle cannot serve it."""
+
+
+def successor_keys_call(env, holder, s, idx, limit, name, fields, device, reports):
+    """The one launch behind Snapshot.successor_keys (s: the snapshot's C handle) and VecNovelGridworld.successor_keys (s None: the envs'
+    current states): idx indexes rows [0, limit); `holder` keeps an uploaded list alive.  -> SuccessorKeys."""
+    import torch
+    f = check_fields(fields)
+    ptr, count, dev, uploaded = index_arg(env, idx, limit, name)
+    A = env.n_actions
+    keys = torch.empty((count, A), dtype=torch.int64, device=dev)
+    reward = torch.empty((count, A), dtype=torch.int32, device=dev) if reports else None
+    done = torch.empty((count, A), dtype=torch.uint8, device=dev) if reports else None
+    info = torch.empty((count, A), dtype=torch.int32, device=dev) if reports else None
+    p = [None if x is None else C.c_void_p(x.data_ptr()) for x in (keys, reward, done, info)]
+    try:
+        enqueue_ordered(env, holder, lambda: _cabi.lib().ngw_successor_keys(env._h, s, ptr, count, f, *p), count, uploaded, device)
+    except ValueError as e:
+        if str(e).startswith('map_size'):
+            raise MapsTooLarge(str(e)) from None
+        raise
+    if reports:
+        succ = SuccessorKeys(keys, reward, done.view(torch.bool), (info & 1).bool(), info)
+    else:
+        succ = SuccessorKeys(keys, None, None, None, None)
+    return succ if device else successors_to_host(succ)
+
+
+def successors_to_host(succ):
+    """A SuccessorKeys of device tensors as numpy arrays (keys uint64, info uint32: the same bits)."""
+    host = lambda x, view=None: None if x is None else (x.cpu().numpy() if view is None else x.cpu().numpy().view(view))   # noqa: E731
+    return SuccessorKeys(host(succ.keys, np.uint64), host(succ.reward), host(succ.done), host(succ.result), host(succ.info, np.uint32))
+
+
+def insert_successors(succ, table, device):
+    """insert_successor_keys behind the launch: succ (device tensors [count, A]) with its keys flattened row-major into table.insert - no
+    host wait in between -, where / fresh reshaped back to [count, A].  -> (SuccessorKeys as `device` asks, KeyInsert)."""
+    from .key_table import KeyInsert
+    shape = tuple(succ.keys.shape)
+    found = table.insert(succ.keys.reshape(-1), device=device)
+    return (succ if device else successors_to_host(succ)), KeyInsert(found.where.reshape(shape), found.fresh.reshape(shape))
+
+
 class Snapshot:
     """`capacity` slots of saved env states in the env's device memory.  Belongs to the env that made it (VecNovelGridworld.snapshot);
     closed by close(), by the env's close() and by an in-place rebuild() (inject_novelty) - a closed snapshot raises on use.
@@ -553,6 +630,26 @@ class Snapshot:
         keys = self.keys(slots, fields, device=True)
         found = table.insert(keys, device=device)
         return (keys if device else keys.cpu().numpy().view(np.uint64)), found
+
+    # ------------------------------------------------------------------ successor keys (include/ngw.h ngw_successor_keys)
+    def successor_keys(self, slots=None, fields=KEY_STATE, device=False, reports=True):
+        """The key of every action's child of saved slots, with no child stored: a SuccessorKeys whose fields are [count, A] - keys[j, a] is
+        exactly keys(fields) of the child expand() would write for parent slots[j] (None: every slot) and action a, and reward / done /
+        result / info [j, a] exactly what that expand would report (under the env's autoreset setting and horizon; .goal / .died as on an
+        Expansion).  reports=False: keys only, the report fields are None.  keys.reshape(-1) is in the pair numbering of expand_all (parent j,
+        action a at j * A + a) and goes into KeyTable.insert as it is; insert_successor_keys() does both.  One kernel launch; nothing is
+        committed.  Maps up to 34 x 34 (two sets of a wavefront's rows in LDS); beyond that the call raises and expand() + keys() remain.
+        slots and device: as in keys() (an index out of range in a device list: a row of zeros in every field, F_BAD_INDEX)."""
+        self._open()
+        return successor_keys_call(self.env, self, self._s, slots, self.capacity, 'slots', fields, device, reports)
+
+    def insert_successor_keys(self, table, slots=None, fields=KEY_STATE, device=False):
+        """successor_keys(slots, fields) offered to `table` (a KeyTable of the same env): (SuccessorKeys, KeyInsert(where, fresh)), where and
+        fresh shaped [count, A] - fresh[j, a]: the child of (slots[j], a) is a state the table has not seen, and no earlier (parent, action) of
+        this call in row-major order leads to it.  fresh_pairs(fresh) gives the (parent position, action) lists an expand() of exactly the new
+        states takes.  The keys stay on the device between the two calls: no host wait in between."""
+        table._open_for(self.env)
+        return insert_successors(self.successor_keys(slots, fields, device=True), table, device)
 
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""

@@ -968,10 +968,7 @@ class VecNovelGridworld:
         f = check_fields(fields)
         ptr, count, dev, uploaded = index_arg(self, envs, self.num_envs, 'envs')
         words = torch.empty(count, dtype=torch.int64, device=dev)
-        keeper = self.__dict__.get('_keys_keeper')
-        if keeper is None:
-            keeper = self._keys_keeper = _Keeper()
-        enqueue_ordered(self, keeper, lambda: _cabi.lib().ngw_state_keys(self._h, None, ptr, count, f, C.c_void_p(words.data_ptr())), count, uploaded,
+        enqueue_ordered(self, self._keeper(), lambda: _cabi.lib().ngw_state_keys(self._h, None, ptr, count, f, C.c_void_p(words.data_ptr())), count, uploaded,
                         device)
         return words if device else words.cpu().numpy().view(np.uint64)
 
@@ -992,6 +989,26 @@ class VecNovelGridworld:
         keys = self.state_keys(envs, fields, device=True)
         found = table.insert(keys, device=device)
         return (keys if device else keys.cpu().numpy().view(np.uint64)), found
+
+    def _keeper(self):
+        keeper = self.__dict__.get('_keys_keeper')
+        if keeper is None:
+            keeper = self._keys_keeper = _Keeper()
+        return keeper
+
+    def successor_keys(self, envs=None, fields=KEY_STATE, device=False, reports=True):
+        """The key of every action's child of the envs' CURRENT states, with no child stored: Snapshot.successor_keys() without the save - a
+        SuccessorKeys of [count, A] fields, keys[j, a] the key of the state step(a) would leave env envs[j] in before any reset, reward / done
+        / result / info [j, a] what lookahead() reports for it.  envs as in state_keys().  One kernel launch; nothing is committed."""
+        from .snapshot import successor_keys_call
+        return successor_keys_call(self, self._keeper(), None, envs, self.num_envs, 'envs', fields, device, reports)
+
+    def insert_successor_keys(self, table, envs=None, fields=KEY_STATE, device=False):
+        """successor_keys(envs, fields) offered to `table` (a KeyTable of this env): Snapshot.insert_successor_keys() for the envs' CURRENT
+        states."""
+        from .snapshot import insert_successors
+        table._open_for(self)
+        return insert_successors(self.successor_keys(envs, fields, device=True), table, device)
 
     def fork(self, src, keep_episode=False):
         """Every env e becomes a copy of env src[e] (src: num_envs indices - a list / numpy array, checked, or a torch int32 tensor on the

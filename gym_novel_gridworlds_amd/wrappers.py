@@ -15,6 +15,7 @@ import numpy as np
 
 from . import spaces
 from .novelty_wrappers import NoveltyWrapper
+from .state_keys import KEY_STATE
 from .vec_env import VecNovelGridworld
 
 
@@ -119,6 +120,28 @@ class LimitActions(NoveltyWrapper):
         runs."""
         return self.env.evaluate_plans(limit_plan_ids(plans, self.limited_actions_id, self.actions_id, len(self.limited_actions), self.env_id),
                                        device=device, copy=copy)
+
+    def successor_keys(self, fields=KEY_STATE, device=False, reports=True):
+        """The env's successor keys in the limited id space: entry i of every field is the env's entry of the action limited id i steps (the
+        columns lookahead() selects); a limited id step() would refuse has key 0 and reports 0."""
+        from .snapshot import SuccessorKeys
+        n = len(self.limited_actions)
+        t = self.env.successor_keys(fields=fields, device=device, reports=reports)
+        ids = limit_column_ids(self.limited_actions_id, self.actions_id, n, t.keys.shape[-1])
+
+        def cols(x):
+            if x is None:
+                return None
+            if device:
+                import torch
+                out = torch.zeros(tuple(x.shape[:-1]) + (n,), dtype=x.dtype, device=x.device)
+            else:
+                out = np.zeros(x.shape[:-1] + (n,), x.dtype)
+            for i, j in enumerate(ids):
+                if j is not None:
+                    out[..., i] = x[..., j]
+            return out
+        return SuccessorKeys(*[cols(x) for x in t])
 
     # (state_key() is NoveltyWrapper's forward: a key describes the state, not the action ids, so it is the same on either side of this wrapper)
 

@@ -636,6 +636,30 @@ int ngw_snapshot_action_mask(ngw_handle* h, ngw_snapshot* s, const int32_t* slot
  * NGW_KEY_ALL; idx_dev == NULL with count above the row count. */
 int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev);
 
+/* Successor keys: the key of every action's child, with no child stored - "which of this node's children are new?" before any of them is written.
+ * With A = the spec's n_actions, for j < count and a < A:
+ *     keys_dev[j * A + a] = exactly the key ngw_state_keys(..., fields) would return for the child ngw_snapshot_expand would write for parent idx[j]
+ *                           and action a (the state the step leaves before any reset; the episode counter is the parent's; NGW_KEY_STEP_COUNT sees
+ *                           the stepped count),
+ *     reward_dev / done_dev / info_dev [j * A + a] (each NULL or [count][A]) = exactly what that expand would report, under the handle's autoreset
+ *                           setting and horizon.
+ * Position j * A + a is the pair numbering of an expand of every action, so the flattened keys go straight into ngw_key_table_insert and a fresh
+ * position maps back to (parent, action) by division.  `s`, idx_dev, count and the index rules are ngw_state_keys': s == NULL means the envs'
+ * current states; idx_dev is an int32 list in DEVICE memory, NULL means 0 .. count-1 (count may then not exceed the row count); parents may repeat
+ * and count is otherwise not bound by the row count; an index outside [0, rows) is never used as an address: its A keys are 0 (which the key table
+ * never stores), its reports are 0, and the sticky NGW_F_BAD_INDEX is raised.  Exactly [0, count * A) of each given array is written.
+ * ONE kernel launch (ngw_successors.inc), enqueued on the handle's stream; it does not wait.  It keeps two sets of a wavefront's 64 rows in LDS
+ * (the stepped rows and the parents they are compared with): 2 * 64 * (MS + 4 * KP) bytes, MS = the map's LDS stride, KP = n_items | 1.  That fits
+ * the 160 KiB of a CU for every map_size up to 34 in every configuration; a handle with larger maps is refused (NGW_E_INVALID_ARG), and
+ * ngw_snapshot_expand followed by ngw_state_keys remains.
+ * Nothing is committed, as for ngw_state_keys: no env, slot, mask, lookahead table, mirror or prepared episode changes, and a captured graph
+ * stays valid.
+ * NGW_E_INVALID_ARG: a NULL handle or keys_dev; a snapshot that is not an open snapshot of this handle; fields == 0 or a bit above NGW_KEY_ALL;
+ * count < 0; idx_dev == NULL with count above the row count; count * A beyond the index range of a launch (2^31 - 1 wavefronts of keys); maps
+ * the call cannot hold. */
+int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev, int32_t* reward_dev,
+                       uint8_t* done_dev, uint32_t* info_dev);
+
 /* Key table: an open-addressing hash set of 64-bit keys in device memory - "have I seen this state BEFORE?" across the calls of a search that
  * runs many iterations (transposition tables, duplicate removal in breadth-first solvers, Go-Explore archives, count-based bonuses).  A table
  * belongs to the handle that created it; it stores keys and nothing else: a caller keeps what it wants per state (visit counts, the best return,
