@@ -8,6 +8,7 @@
 // buffers: lidar rows, agent views, action masks of saved states.  They commit nothing, and leave the env's own observation buffers alone.
 // The state keys (ngw_keys.inc) hash rows of a snapshot or of the state slab into the caller's buffer: they commit nothing either.
 // The successor keys (ngw_successors.inc) are the keys of every action's child of such rows, with no child stored: they commit nothing either.
+// A playout (ngw_playout.inc) is a rollout whose actions the kernel draws among the valid ones of each step: it commits nothing either.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -59,6 +60,32 @@ int slot_obs_args(const ngw_handle* h, const ngw_snapshot* s, const void* out, c
     if (count < 0 || count > 0x7FFFFFFFll) return fail(NGW_E_INVALID_ARG, "%s of %lld slots", what, (long long)count);
     if (!slots_dev && count > s->cap) return fail(NGW_E_INVALID_ARG, "%s of %lld slots from a snapshot of %lld slots", what, (long long)count, (long long)s->cap);
     return NGW_OK;
+}
+
+// what a rollout and a playout check alike about their pairs (before anything touches the stream): where the parents live and how many rows
+// that is (-> src_rows), where the end states go, and that the handle's maps fit the kernels' LDS layout.  what / call: "rollout", "ngw_snapshot_rollout"
+int step_pairs_args(const ngw_handle* h, const ngw_snapshot* src, const int32_t* src_idx_dev, const ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count,
+                    const char* what, const char* call, int64_t* src_rows) {
+    if (!dst && dst_slots_dev) return fail(NGW_E_INVALID_ARG, "destination slots without a destination snapshot");
+    if ((dst && !owns(h, dst)) || (src && !owns(h, src))) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    *src_rows = src ? src->cap : h->n;
+    if (count > 0x7FFFFFFFll || (dst && count > dst->cap))
+        return fail(NGW_E_INVALID_ARG, "%s of %lld states into a snapshot of %lld slots", what, (long long)count, (long long)(dst ? dst->cap : 0x7FFFFFFFll));
+    if (!src_idx_dev && count > *src_rows)
+        return fail(NGW_E_INVALID_ARG, "%s of %lld states from %lld %s", what, (long long)count, (long long)*src_rows, src ? "slots" : "envs");
+    if (!h->general_ok)
+        return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps in LDS (%s, as the fused rollouts) "
+                                       "and they need more than 160 KiB; per-launch steps and resets are available", h->proto.S, call);
+    return NGW_OK;
+}
+
+// the launch block of the kernels that step saved rows: the handle's rollout layout with its buffers, autoreset setting and horizon
+NgwLaunch step_block(const ngw_handle* h) {
+    NgwLaunch a = h->proto;
+    a.b = h->b;
+    a.autoreset = h->autoreset;
+    a.horizon = h->horizon;
+    return a;
 }
 
 }  // namespace
@@ -161,10 +188,7 @@ int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx
                                        "and they need more than 160 KiB; per-launch steps and resets are available", h->proto.S);
     if (int rc = enter(h)) return rc;
     if (count == 0) return NGW_OK;
-    NgwLaunch a = h->proto;
-    a.b = h->b;
-    a.autoreset = h->autoreset;
-    a.horizon = h->horizon;
+    const NgwLaunch a = step_block(h);
     NgwExpand x{};
     x.src = src ? src->r : state_rows(h); x.dst = dst->r;
     x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev;
@@ -182,21 +206,11 @@ int ngw_snapshot_rollout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_id
     if (count < 0 || pair_stride < count)
         return fail(NGW_E_INVALID_ARG, "rollout of %lld pairs with a pair stride of %lld", (long long)count, (long long)pair_stride);
     if (!dst && !ret_dev && !length_dev && !ended_dev && !info_dev) return fail(NGW_E_INVALID_ARG, "rollout without a destination and without a report: nothing to do");
-    if (!dst && dst_slots_dev) return fail(NGW_E_INVALID_ARG, "destination slots without a destination snapshot");
-    if ((dst && !owns(h, dst)) || (src && !owns(h, src))) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
-    const int64_t src_rows = src ? src->cap : h->n;
-    if (count > 0x7FFFFFFFll || (dst && count > dst->cap))
-        return fail(NGW_E_INVALID_ARG, "rollout of %lld states into a snapshot of %lld slots", (long long)count, (long long)(dst ? dst->cap : 0x7FFFFFFFll));
-    if (!src_idx_dev && count > src_rows) return fail(NGW_E_INVALID_ARG, "rollout of %lld states from %lld %s", (long long)count, (long long)src_rows, src ? "slots" : "envs");
-    if (!h->general_ok)
-        return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps in LDS (ngw_snapshot_rollout, as the fused rollouts) "
-                                       "and they need more than 160 KiB; per-launch steps and resets are available", h->proto.S);
+    int64_t src_rows;
+    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "rollout", "ngw_snapshot_rollout", &src_rows)) return rc;
     if (int rc = enter(h)) return rc;
     if (count == 0) return NGW_OK;
-    NgwLaunch a = h->proto;
-    a.b = h->b;
-    a.autoreset = h->autoreset;
-    a.horizon = h->horizon;
+    const NgwLaunch a = step_block(h);
     NgwSlotRollout x{};
     x.src = src ? src->r : state_rows(h);
     if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
@@ -204,6 +218,29 @@ int ngw_snapshot_rollout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_id
     x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev;
     x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
     HIP_TRY(ngw_slot_rollout_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
+    return NGW_OK;
+}
+
+int ngw_snapshot_playout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                         ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev,
+                         int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride) {
+    if (!h) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "playout of %d steps", (int)n_steps);
+    if (count < 0 || (actions_dev && actions_stride < count))
+        return fail(NGW_E_INVALID_ARG, "playout of %lld pairs with an action stride of %lld", (long long)count, (long long)actions_stride);
+    int64_t src_rows;
+    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "playout", "ngw_snapshot_playout", &src_rows)) return rc;
+    if (int rc = enter(h)) return rc;
+    if (count == 0) return NGW_OK;
+    const NgwLaunch a = step_block(h);
+    NgwPlayout x{};
+    x.src = src ? src->r : state_rows(h);
+    if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
+    x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = actions_stride; x.n_steps = n_steps;
+    x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev; x.first_action = first_action_dev;
+    x.seed = seed; x.first_pair = first_pair;
+    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
+    HIP_TRY(ngw_playout_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
     return NGW_OK;
 }
 
@@ -281,10 +318,7 @@ int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, i
                                        "ngw_state_keys is available", h->proto.S, lds);
     if (int rc = enter(h)) return rc;                 // (s == NULL: the one-env loop has ended, HBM holds the env's state)
     if (count == 0) return NGW_OK;
-    NgwLaunch a = h->proto;
-    a.b = h->b;
-    a.autoreset = h->autoreset;
-    a.horizon = h->horizon;
+    const NgwLaunch a = step_block(h);
     NgwSuccessors x{};
     x.src = s ? s->r : state_rows(h); x.idx = idx_dev; x.keys = keys_dev;
     x.reward = reward_dev; x.done = done_dev; x.info = info_dev;

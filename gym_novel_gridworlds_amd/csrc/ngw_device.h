@@ -516,6 +516,30 @@ extern "C"
 #endif
 hipError_t ngw_slot_rollout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream);
 
+/* Snapshot playout (ngw_playout.inc, ngw_abi_snapshot.cpp): NgwSlotRollout's pairs, index rules, stop rule and destination, with the actions drawn in
+ * the kernel by the choice rule of include/ngw.h (ngw_snapshot_playout): pair j is pair number first_pair + j of the stream of `seed`.  The drawn
+ * action of pair j at step t goes to actions[t * stride + j] (nullptr: not recorded; -1 for a step the pair did not execute), the first one to
+ * first_action[j].  A skipped pair's reports are stored as 0 and its actions as -1. */
+struct NgwPlayout {
+    NgwSnapRows src, dst;
+    const int32_t* si;
+    const int32_t* di;
+    int32_t* actions;
+    int64_t stride;
+    int32_t* ret;
+    int32_t* length;
+    uint8_t* ended;
+    uint32_t* info;
+    int32_t* first_action;
+    uint64_t seed, first_pair;
+    int32_t count, src_rows, dst_rows;
+    int32_t n_steps, keep;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_playout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream);
+
 /* Slot observations (ngw_slot_observe.inc, ngw_abi_snapshot.cpp): observations and action masks of SAVED states, gathered by slot index. Output
  * row j of a call describes row slots[j] of `src` (a snapshot; a NULL list = j itself).  An index outside [0, rows) is never used as an address:
  * its output row is all zeros and NGW_F_BAD_INDEX is raised in *flags.  Nothing but the output rows and the flags word is stored.  The three

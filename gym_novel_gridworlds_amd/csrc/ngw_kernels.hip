@@ -30,7 +30,7 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file TWENTY times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file TWENTY-ONE times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
@@ -42,6 +42,7 @@
 //   16: slot observations (ngw_slot_observe.inc: lidar rows, agent views, action masks of saved states; the lidar one shares the row mover too)
 //   17: state keys (ngw_keys.inc: 64-bit hashes of saved slots and live envs)   18: the key table (ngw_table.inc: a hash set of such keys)
 //   19: successor keys (ngw_successors.inc: the key of every action's child; it shares ngw_expand.inc's row mover and ngw_keys.inc's terms)
+//   20: snapshot playout (ngw_playout.inc: valid-action random playouts from saved rows; it shares ngw_expand.inc's row mover and ngw_mask.inc's walk)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -393,11 +394,14 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #if NGW_HAS(13)
 #include "ngw_plans.inc"
 #endif
-#if NGW_HAS(14) || NGW_HAS(15) || NGW_HAS(16) || NGW_HAS(19)
+#if NGW_HAS(14) || NGW_HAS(15) || NGW_HAS(16) || NGW_HAS(19) || NGW_HAS(20)
 #include "ngw_expand.inc"
 #endif
 #if NGW_HAS(15)
 #include "ngw_slot_rollout.inc"
+#endif
+#if NGW_HAS(20)
+#include "ngw_playout.inc"
 #endif
 #if NGW_HAS(16)
 #include "ngw_slot_observe.inc"
@@ -871,6 +875,21 @@ extern "C" hipError_t ngw_slot_rollout_launch(const NgwDevSpec* dspec, const Ngw
     });
 }
 #endif  // NGW_HAS(15)
+
+#if NGW_HAS(20)
+// snapshot playout (ngw_playout.inc): a = the handle's rollout layout with a.autoreset, a.horizon; one wave per 64 pairs
+extern "C" hipError_t ngw_playout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream) {
+    if (x->count <= 0 || x->n_steps < 1 || (x->actions && x->stride < x->count) || x->src_rows < 1 || a->S < 3 || a->S > NGW_MAX_MAP_SIZE || a->K < 1 ||
+        a->K > NGW_MAX_ITEMS || a->MS < a->S2 || (a->MS & 3) || !a->b.flags || !x->src.map || (x->keep && (!x->dst.map || x->dst_rows < 1)) || (!x->keep && x->di))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((int64_t)x->count + NGW_EPB - 1) / NGW_EPB)), block(NGW_EPB);
+    return with_row_piece(a->S2, [&](auto V) {
+        return with_flag(ext != 0, [&](auto E) {
+            return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+        });
+    });
+}
+#endif  // NGW_HAS(20)
 
 #if NGW_HAS(16)
 // slot observations (ngw_slot_observe.inc).  The lidar rows: a = the stand-alone lidar launch's layout with a.lout = the caller's rows; one wave per 64 pairs

@@ -50,8 +50,8 @@ struct LeanFront {
     bool ok2;
     int front2;
 };
-template <class CELL>
-__device__ __forceinline__ LeanFront lean_front_cells(const NgwStepU& U, int S, int r, int c, int f, const CELL& cell_at) {
+template <class UT, class CELL>
+__device__ __forceinline__ LeanFront lean_front_cells(const UT& U, int S, int r, int c, int f, const CELL& cell_at) {
     LeanFront q;
     const int dr = (f == 0) ? -1 : (f == 1 ? 1 : 0), dc = (f == 2) ? -1 : (f == 3 ? 1 : 0);
     q.fr = r + dr; q.fc = c + dc; q.dcell = dr * S + dc; q.fcell = r * S + c + q.dcell;
@@ -93,20 +93,15 @@ __device__ __forceinline__ LeanLane lean_load_lane(const NgwBufs& b, uint32_t n3
     return l;
 }
 
-// The mask of one lane's env from its pose and selected item, its inventory row (a lane-private LDS row) and its map (cell_at: a cell
-// index -> the item there).  Fetches the table (lane l holds entry l), the uniform parameters and the wrapper predicates itself, so that a
-// caller has nothing of them live across its own work.  All lanes of the wave must be active (the loop is wave-uniform).
-template <bool EXT, class CELL>
-__device__ __forceinline__ uint64_t lane_mask(const NgwDevSpec* __restrict__ dspec, int S, int K, int r, int c, int f, int sel, const int32_t* inv,
-                                              const CELL& cell_at) {
-    const LeanTable t = lean_fetch_table(dspec);
-    NgwStepU U;
-    NgwExtU X;
-    lean_fetch_uniforms<EXT>(dspec, U, X);
+// The walk over the entries: the mask of one lane's state from its pose and selected item, its inventory row (a lane-private LDS row) and its map
+// (cell_at: a cell index -> the item there), fed the table (lane l holds entry l), the uniform parameters and the wrapper predicates the caller
+// holds; A = the number of entries to walk.  All lanes of the wave must be active (the loop is wave-uniform).
+template <bool EXT, class UT, class CELL>
+__device__ __forceinline__ uint64_t lean_mask_walk(const LeanTable& t, const UT& U, const NgwExtU& X, int A, int S, int K, int r, int c, int f, int sel,
+                                                   const int32_t* inv, const CELL& cell_at) {
     const LeanFront q = lean_front_cells(U, S, r, c, f, cell_at);
     const int inv_place = inv[U.place_item], inv_axe = inv[U.axe_item];
     uint64_t mask = 0;
-    const int A = min(U.n_actions, NGW_MAX_ACTIONS);
     for (int a = 0; a < A; a++) {
         const uint32_t e0 = (uint32_t)__builtin_amdgcn_readlane((int)t.t0, a), e1 = (uint32_t)__builtin_amdgcn_readlane((int)t.t1, a);
         const uint32_t e2 = (uint32_t)__builtin_amdgcn_readlane((int)t.t2, a), e4 = (uint32_t)__builtin_amdgcn_readlane((int)t.t4, a);
@@ -123,6 +118,18 @@ __device__ __forceinline__ uint64_t lane_mask(const NgwDevSpec* __restrict__ dsp
         mask |= (uint64_t)(lean_result(s, xb) ? 1u : 0u) << a;
     }
     return mask;
+}
+
+// The mask of one lane's env: fetches the table, the uniform parameters and the wrapper predicates itself, so that a caller has nothing of
+// them live across its own work, and walks the spec's entries.
+template <bool EXT, class CELL>
+__device__ __forceinline__ uint64_t lane_mask(const NgwDevSpec* __restrict__ dspec, int S, int K, int r, int c, int f, int sel, const int32_t* inv,
+                                              const CELL& cell_at) {
+    const LeanTable t = lean_fetch_table(dspec);
+    NgwStepU U;
+    NgwExtU X;
+    lean_fetch_uniforms<EXT>(dspec, U, X);
+    return lean_mask_walk<EXT>(t, U, X, min(U.n_actions, NGW_MAX_ACTIONS), S, K, r, c, f, sel, inv, cell_at);
 }
 
 // The standalone form: the masks of the state held in HBM, [n_pad] words at `out` (padding rows 0).

@@ -1,0 +1,153 @@
+// ngw_playout.inc - snapshot playout (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc and ngw_expand.inc; a unit of its
+// own; host side: ngw_abi_snapshot.cpp).
+//
+// Pair j of a call: the parent is row si[j] of the source set (the state slab, or a snapshot); it is stepped on a private copy up to n_steps
+// times by the rules of ngw_slot_rollout_kernel - it stops at the first step whose `done` would be 1, that step counts, no reset ever runs -
+// with actions DRAWN HERE: at every step uniformly among the actions that would succeed from the state the pair is in (include/ngw.h, the
+// choice rule of ngw_snapshot_playout: mask word, Philox word, the k-th set bit).  Nothing here restates a game rule: the mask is
+// lean_mask_walk's, the step is lean_body, the generator is philox_block.
+//
+// Shape: ngw_slot_rollout_kernel's, with the choice in the place of the plan read.  One work-group is one wave: 64 consecutive pairs.
+//   1. Stage-in, as ngw_slot_rollout.inc step 1: indices checked, loads on clamped indices (a skipped pair and a lane past `count` stage row 0
+//      of the source), pose / selected item / step count / episode counter into registers, the 64 parent rows into the handle's LDS layout
+//      with expand_move_row.
+//   2. Barrier; the T-loop on the lane's own LDS row.  Each iteration: the mask of the lane's state (lean_mask_walk over the table the lanes
+//      hold - entries read with v_readlane, a wave-uniform loop: EVERY lane runs it, the lanes of ended or skipped pairs on their frozen rows,
+//      and discard the result), one Philox block every fourth step, the k-th set bit, the entry fetched with ds_bpermute (lane 63 holds the
+//      all-zero entry), lean_body<STAGE = true, WT = false, EXT> with `alive` in the place of `live`.  The loop ends once no lane of the wave
+//      is alive (wave-uniform: the wave is the whole work-group); the steps a pair did not execute are recorded as -1.
+//   3. Barrier; the end states to their slots (where they are kept), the reports, the flags - as ngw_slot_rollout.inc step 3; a skipped pair's
+//      reports are stored as 0 and its first action as -1.
+// No reset path is in this kernel and no store to a.b.* but the flags word.  Source and destination may be the same allocation (see
+// ngw_slot_rollout.inc).
+//
+// x.actions (may be nullptr): int32, the action of pair j at step t to [t * x.stride + j] (stride >= count) - the layout ngw_slot_rollout_kernel reads.
+
+// the id of the (k + 1)-th set bit of m, counted from bit 0 (k < popcount(m)): six halvings, branch-free per lane
+__device__ __forceinline__ int playout_kth_bit(uint64_t m, uint32_t k) {
+    int pos = 0;
+#pragma unroll
+    for (int width = 32; width >= 1; width >>= 1) {
+        const uint32_t below = (uint32_t)__popcll((m >> pos) & ((1ull << width) - 1ull));
+        if (k >= below) { pos += width; k -= below; }
+    }
+    return pos;
+}
+
+template <int VEC, bool EXT>
+__global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* __restrict__ dspec, const NgwLaunch a, const NgwPlayout x) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    const uint32_t tid = threadIdx.x;
+    const int64_t pair = (int64_t)blockIdx.x * EPB + tid;
+    const int S = a.S, K = a.K, S2 = a.S2;
+    const bool keep = x.keep != 0;
+    // ---- 1. this lane's pair
+    const bool inside = pair < (int64_t)x.count;
+    int si = 0, di = 0;
+    if (inside) {
+        si = x.si ? x.si[pair] : (int)pair;
+        di = x.di ? x.di[pair] : (int)pair;
+    }
+    const bool ok = inside && (uint32_t)si < (uint32_t)x.src_rows && (!keep || (uint32_t)di < (uint32_t)x.dst_rows);
+    uint32_t flags = (inside && !ok) ? NGW_F_BAD_INDEX : 0u;
+    const int sic = ok ? si : 0, dic = ok ? di : -1;
+    const int2 rc = reinterpret_cast<const int2*>(x.src.loc)[sic];
+    int r = rc.x, c = rc.y;
+    int f = x.src.facing[sic];
+    int sel = x.src.selected[sic];
+    int steps = x.src.step_count[sic];
+    const uint32_t episode = x.src.episode[sic];
+    LeanTable t = lean_fetch_table(dspec);
+    if (tid >= NGW_MAX_ACTIONS) t = LeanTable{0u, 0u, 0u, 0u, 0u, 0u};             // (lane 63 holds the all-zero entry: a no-op)
+    NgwStepU U;
+    NgwExtU X;
+    lean_fetch_uniforms<EXT>(dspec, U, X);
+    // the 64 parent rows into the handle's LDS layout
+    uint32_t* const lds_map = lds + a.off_map;
+    int32_t* const lds_inv = reinterpret_cast<int32_t*>(lds + a.off_inv);
+    const int g = (int)(tid % NGW_SNAP_GROUP), q = (int)(tid / NGW_SNAP_GROUP);
+    const int MSdw = a.MS >> 2, KP = a.KP;
+    constexpr int ROWS = EPB / NGW_SNAP_GROUP;                                     // rows per round
+#pragma unroll 4
+    for (int it = 0; it < EPB / ROWS; it++) {
+        const int j = it * ROWS + q;
+        const int sj = __builtin_amdgcn_ds_bpermute(j << 2, sic);
+        expand_move_row<VEC, true>(x.src.map + (size_t)sj * (size_t)S2, x.src.inv + (size_t)sj * (size_t)K, lds_map + j * MSdw, lds_inv + j * KP, S2, K, g);
+    }
+    __syncthreads();
+    // ---- 2. up to n_steps steps of this lane's row
+    int8_t* const mp = reinterpret_cast<int8_t*>(lds_map) + tid * a.MS;
+    int32_t* const inv = lds_inv + tid * KP;
+    const int n_steps = x.n_steps;
+    const int64_t tstride = x.stride;
+    int32_t* const rec = x.actions ? x.actions + pair : nullptr;                   // (only ever dereferenced by a lane inside `count`)
+    const int A = min(U.n_actions, NGW_MAX_ACTIONS);                               // the walk's bound: a scalar
+    const uint64_t all_actions = (1ull << A) - 1ull;                               // (A <= 48)
+    int autoreset = a.autoreset, horizon = a.horizon;
+    const LeanUV UV = lean_uv(U);
+    int Sv = S, Kv = K;                                                            // (as in the plan kernel: only vector instructions read them inside the loop)
+    PIN_V(Sv); PIN_V(Kv); PIN_V(autoreset); PIN_V(horizon);
+    // the pair's stream: key = (lo32(seed), hi32(seed) ^ NGW_PLAYOUT_TAG), counter = (t >> 2, 0, lo32(p), hi32(p)) with p = first_pair + j
+    const uint64_t p = x.first_pair + (uint64_t)pair;
+    uint32_t key0 = (uint32_t)x.seed, key1 = (uint32_t)(x.seed >> 32) ^ NGW_PLAYOUT_TAG;
+    PIN_V(key0); PIN_V(key1);                                                      // (in VGPRs, as in the fused rollout: the round keys are not hoisted into SGPRs)
+    uint32_t w0 = 0, w1 = 0, w2 = 0, w3 = 0;
+    auto cell_at = [&](int cell) -> int { return (int)mp[cell]; };
+    bool alive = ok;
+    int ret = 0, len = 0, ended = 0, first = -1;
+    uint32_t info = 0;
+    int s = 0;
+    for (; s < n_steps; s++) {
+        if ((s & 3) == 0) philox_block((uint32_t)s >> 2, 0u, (uint32_t)p, (uint32_t)(p >> 32), key0, key1, w0, w1, w2, w3);   // (uniform: s is a scalar)
+        // the choice: uniform over the actions that would succeed from here; every action where none would
+        uint64_t m = lean_mask_walk<EXT>(t, UV, X, A, Sv, Kv, r, c, f, sel, inv, cell_at);
+        if (m == 0) m = all_actions;
+        const uint32_t qq = (uint32_t)s & 3u;
+        const uint32_t w = qq == 0 ? w0 : (qq == 1 ? w1 : (qq == 2 ? w2 : w3));
+        const uint32_t k = __umulhi(w, (uint32_t)__popcll(m));
+        const int action = alive ? playout_kth_bit(m, k) : -1;
+        if (rec && inside) rec[(int64_t)s * tstride] = action;
+        if (s == 0) first = action;
+        const int ai = (alive ? action : 63) << 2;
+        const uint32_t e0 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t0), e1 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t1);
+        const uint32_t e2 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t2), e3 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t3);
+        const uint32_t e4 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t4), e5 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t5);
+        const LeanOut o = lean_body<true, false, EXT>(UV, X, e0, e1, e2, e3, e4, e5, alive, alive, Sv, Kv, mp, inv, nullptr, nullptr, 0u, 0u, r, c, f, sel, steps,
+                                                      autoreset, horizon);
+        r = o.r; c = o.c; f = o.f; sel = o.sel; steps = o.steps;                   // (a no-op entry hands them back unchanged: an ended pair stays frozen)
+        flags |= o.flags;
+        if (alive) {
+            ret += o.reward; len += 1; info = o.info;
+            if (o.ended) { ended = 1; alive = false; }                             // the ending step counts; no reset runs, the pair is over
+        }
+        if (!__any(alive)) { s++; break; }
+    }
+    if (rec && inside)
+        for (; s < n_steps; s++) rec[(int64_t)s * tstride] = -1;                   // the steps no pair of this wave executed
+    __syncthreads();
+    // ---- 3. the end states to their slots with the scalars (where they are kept), the reports
+    if (keep) {
+#pragma unroll 4
+        for (int it = 0; it < EPB / ROWS; it++) {
+            const int j = it * ROWS + q;
+            const int dj = __builtin_amdgcn_ds_bpermute(j << 2, dic);
+            if (dj >= 0)
+                expand_move_row<VEC, false>(x.dst.map + (size_t)dj * (size_t)S2, x.dst.inv + (size_t)dj * (size_t)K, lds_map + j * MSdw, lds_inv + j * KP, S2, K, g);
+        }
+        if (ok) {
+            reinterpret_cast<int2*>(x.dst.loc)[di] = int2{r, c};
+            x.dst.facing[di] = f;
+            x.dst.selected[di] = (uint8_t)sel;
+            x.dst.step_count[di] = steps;
+            x.dst.episode[di] = episode;
+        }
+    }
+    if (inside) {                                                                  // (a skipped pair: alive was never set, so these are 0 / -1)
+        if (x.ret) x.ret[pair] = ret;
+        if (x.length) x.length[pair] = len;
+        if (x.ended) x.ended[pair] = (uint8_t)ended;
+        if (x.info) x.info[pair] = info;
+        if (x.first_action) x.first_action[pair] = first;
+    }
+    if (flags) atomicOr(a.b.flags, flags);
+}

@@ -125,6 +125,12 @@ class ShardedVecNovelGridworld:
             plans = plans[self.first:self.first + self.num_envs]
         return self.local.evaluate_plans(plans, device=device, copy=copy)
 
+    def playouts(self, n_playouts, steps, seed, device=False):
+        """Valid-action random playouts from the current states of this rank's shard (VecNovelGridworld.playouts): [num_envs, P] fields;
+        rank-local, no collective.  The local env numbers its pairs from env_index_base * P (= first * P), so the ranks together return what
+        one unsharded env over all the envs returns."""
+        return self.local.playouts(n_playouts, steps, seed, device=device)
+
     def snapshot(self, capacity=None):
         """A device-side snapshot of this rank's shard (VecNovelGridworld.snapshot): rank-local, env indices are the shard's own - in
         save / restore and in expand / expand_all (from_envs=True: parents are the shard's envs 0 .. num_envs-1)."""

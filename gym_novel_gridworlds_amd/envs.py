@@ -325,6 +325,14 @@ class _NovelGridworldEnv(_EnvBase):
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
         return vec.evaluate_plans(a[None], device=device, copy=copy).row(0)
 
+    def playouts(self, n_playouts, steps, seed, device=False):
+        """P = n_playouts valid-action random playouts of up to `steps` steps from the current state, without taking a step: a Playout of
+        'ret' int32, 'length' int32, 'ended' bool, 'info' uint32 and 'first_action' int32, each [P]; playout q is pair q of the stream of
+        `seed`; see VecNovelGridworld.playouts."""
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        return vec.playouts(n_playouts, steps, seed, device=device).row(0)
+
     def state_key(self, fields=KEY_STATE):
         """The 64-bit key of the current state as a Python int, computed on the device under the field selection `fields` (KEY_* bits,
         default KEY_STATE); see VecNovelGridworld.state_keys and state_keys.py for the contract."""

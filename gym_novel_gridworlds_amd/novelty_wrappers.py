@@ -53,6 +53,9 @@ class NoveltyWrapper(object):
     def evaluate_plans(self, plans, device=False, copy=False):
         return self.env.evaluate_plans(plans, device=device, copy=copy)
 
+    def playouts(self, n_playouts, steps, seed, device=False):
+        return self.env.playouts(n_playouts, steps, seed, device=device)
+
     def state_key(self, fields=KEY_STATE):
         return self.env.state_key(fields)
 

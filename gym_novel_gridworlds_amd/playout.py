@@ -1,0 +1,99 @@
+"""The playout choice rule on the host: the public contract of include/ngw.h (ngw_snapshot_playout) in numpy, with a Philox4x32-10 of its
+own - the counterpart of state_keys.keys_of_rows.  A host that knows a pair's state before step t (its valid-action mask word: env.action_mask_words,
+Snapshot.action_masks) computes here the action the device drew for it:
+
+    m = the mask word; all n_actions bits where it is 0
+    w = word (t & 3) of Philox4x32-10, counter (t >> 2, 0, lo32(p), hi32(p)), key (lo32(seed), hi32(seed) ^ PLAYOUT_TAG)
+    k = (w * popcount(m)) >> 32;  the action is the id of the (k + 1)-th set bit of m, counted from bit 0
+
+p is the pair's global number (first_pair + its position in the call).  Nothing here touches the device."""
+import collections
+
+import numpy as np
+
+PLAYOUT_TAG = 0x504C4159          # include/ngw.h NGW_PLAYOUT_TAG
+_M0, _M1, _W0, _W1 = 0xD2511F53, 0xCD9E8D57, 0x9E3779B9, 0xBB67AE85
+_LO = np.uint64(0xFFFFFFFF)
+_S32 = np.uint64(32)
+
+
+class Playout(collections.namedtuple('Playout', 'ret length ended info first_action actions')):
+    """What playout() / playouts() return: PlanEval's 'ret' int32, 'length' int32, 'ended' bool and 'info' uint32 (the last executed step's
+    word), 'first_action' int32 (the action drawn at step 0: what a flat Monte-Carlo search groups the returns by), each [count] ([N, P] from
+    playouts(), [P] on the single-env adapter), and 'actions' int32 [T, count] ([T, N, P]; [T, P]): the action of every executed step, -1 for
+    a step the pair did not execute - or None where the call did not record them.  A named tuple whose fields can also be read by name:
+    p['ret'].  numpy arrays, or torch tensors ('info' is int32 there, the same bits)."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    @property
+    def goal(self):
+        """The playout ended by the step itself reporting done (info bit 1, as on PlanEval; clear for a horizon cut)."""
+        return self.ended & (((self.info >> 1) & 1) != 0)
+
+    @property
+    def died(self):
+        """The playout ended in a FireWall death (message code 14)."""
+        return self.ended & (((self.info >> 8) & 255) == 14)
+
+    def shaped(self, *shape):
+        """The per-pair fields reshaped to `shape`, the recorded actions to [T, *shape]."""
+        a = self.actions
+        return Playout(*[x.reshape(*shape) for x in self[:5]], None if a is None else a.reshape(a.shape[0], *shape))
+
+    def row(self, i):
+        """Env i's rows of an [N, P] result (the single-env adapter's view)."""
+        a = self.actions
+        return Playout(*[x[i] for x in self[:5]], None if a is None else a[:, i])
+
+
+def philox4x32_10(counter, key):
+    """Philox4x32-10 over arrays: counter = four uint32 arrays (broadcastable), key = two -> the four output words, uint32 arrays."""
+    c0, c1, c2, c3 = [np.asarray(x, np.uint64) & _LO for x in np.broadcast_arrays(*counter)]
+    k0, k1 = [np.asarray(x, np.uint64) & _LO for x in key]
+    for _ in range(10):
+        p0, p1 = np.uint64(_M0) * c0, np.uint64(_M1) * c2          # 32 x 32 -> 64 bits: no overflow in uint64
+        c0, c1, c2, c3 = (p1 >> _S32) ^ c1 ^ k0, p1 & _LO, (p0 >> _S32) ^ c3 ^ k1, p0 & _LO
+        k0, k1 = (k0 + np.uint64(_W0)) & _LO, (k1 + np.uint64(_W1)) & _LO
+    return tuple(x.astype(np.uint32) for x in (c0, c1, c2, c3))
+
+
+def playout_words(seed, pairs, t):
+    """w of the contract for the global pair numbers `pairs` (uint64 values, any shape) at step t (an int, or an array broadcastable
+    against pairs) -> uint32."""
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    p = np.asarray(pairs).astype(np.uint64)
+    t = np.asarray(t, np.int64)
+    if (t < 0).any():
+        raise ValueError("t: steps are numbered from 0")
+    p, t = np.broadcast_arrays(p, t)
+    zero = np.zeros(p.shape, np.uint64)
+    words = philox4x32_10(((t >> 2).astype(np.uint64), zero, p & _LO, p >> _S32), (np.uint64(seed & 0xFFFFFFFF), np.uint64((seed >> 32) ^ PLAYOUT_TAG)))
+    return np.choose(t & 3, words)
+
+
+def kth_set_bit(words, k):
+    """The id of the (k + 1)-th set bit of each uint64 word, counted from bit 0 (k < popcount(word))."""
+    w = np.asarray(words, np.uint64)
+    bits = ((w[..., None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).astype(np.int64)
+    return np.argmax(np.cumsum(bits, -1) > np.asarray(k, np.int64)[..., None], -1).astype(np.int32)
+
+
+def choose_actions(mask_words, seed, pairs, t, n_actions):
+    """The action the playout contract draws for each pair: mask_words = the uint64 valid-action words of the pairs' states before step t
+    (int64 words over the same bits are taken too), pairs = their global pair numbers, t = the step (an int or an array), n_actions = the
+    length of the action list.  -> int32, shaped as mask_words."""
+    n_actions = int(n_actions)
+    if not 1 <= n_actions < 64:
+        raise ValueError("n_actions: %d outside [1, 64)" % n_actions)
+    m = np.asarray(mask_words)
+    m = m.view(np.uint64) if m.dtype == np.int64 else m.astype(np.uint64)
+    every = np.uint64((1 << n_actions) - 1)
+    if (m & ~every).any():
+        raise ValueError("mask_words: a bit at or above n_actions = %d is set" % n_actions)
+    m = np.where(m == 0, every, m)
+    n = ((m[..., None] >> np.arange(64, dtype=np.uint64)) & np.uint64(1)).sum(-1).astype(np.uint64)
+    w = np.broadcast_to(playout_words(seed, pairs, t), m.shape).astype(np.uint64)
+    return kth_set_bit(m, (w * n) >> _S32)

@@ -149,6 +149,24 @@ def check_rollout(parents, n_plans, children, n_parents, capacity, same_buffer, 
     return p, c, count
 
 
+def check_playout(parents, steps, children, n_parents, capacity, same_buffer, device_len=None):
+    """The host-side checks of one playout call: `steps` is an integer >= 1, and the index lists are a rollout's (check_rollout) - with no
+    plans to count the pairs, the number of pairs is the length of parents, or of children where parents is None (0 .. count-1).  Returns
+    (parents, children, count, steps)."""
+    if isinstance(steps, bool) or not isinstance(steps, (int, np.integer)):
+        raise ValueError("steps: an integer number of steps expected, got %r" % (steps,))
+    if steps < 1:
+        raise ValueError("steps: at least one step expected, got %d" % steps)
+    given = parents if parents is not None else children
+    if given is None:
+        raise ValueError("parents: without parents and children the number of pairs is not known")
+    n = None if device_len is None else device_len(given)
+    if n is None:
+        n = len(given)
+    p, c, count = check_rollout(parents, int(n), children, n_parents, capacity, same_buffer, device_len)
+    return p, c, count, int(steps)
+
+
 def check_copy(src_slots, dst_slots, n_src, capacity, same_buffer, device_len=None):
     """The host-side checks of one slot-to-slot copy, as check_expand checks children: src_slots index rows [0, n_src) and may repeat,
     dst_slots index slots [0, capacity) and must be distinct, both have one length (None = no list: 0 .. count-1, which must exist; without
@@ -321,6 +339,35 @@ def fresh_pairs(fresh):
         pos = torch.nonzero(fresh.reshape(-1)).reshape(-1)
         return torch.div(pos, A, rounding_mode='floor'), pos % A
     return divmod(np.flatnonzero(np.asarray(fresh).reshape(-1)), A)
+
+
+def playout_call(env, holder, src, dst, parents, children, count, steps, seed, first_pair, record, device):
+    """The one launch behind Snapshot.playout and VecNovelGridworld.playouts: src / dst are snapshots' C handles (src None: the envs' current
+    states; dst None: nothing is kept), parents / children the checked lists (check_playout); `holder` keeps the uploaded lists alive.
+    -> Playout of [count] fields, actions [steps, count] with `record`."""
+    import torch
+    from .playout import Playout
+    seed, first_pair = int(seed), int(first_pair)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError("seed: %d outside [0, 2^64)" % seed)
+    if not 0 <= first_pair < 1 << 64:
+        raise ValueError("first_pair: %d outside [0, 2^64)" % first_pair)
+    dev = torch.device('cuda:%d' % env.device)
+    ptr, uploaded = upload(dev, count, parents, children)
+    ret = torch.zeros(count, dtype=torch.int32, device=dev)
+    length = torch.zeros(count, dtype=torch.int32, device=dev)
+    ended = torch.zeros(count, dtype=torch.uint8, device=dev)
+    info = torch.zeros(count, dtype=torch.int32, device=dev)
+    first = torch.full((count,), -1, dtype=torch.int32, device=dev)
+    actions = torch.full((steps, count), -1, dtype=torch.int32, device=dev) if record else None
+    out = [C.c_void_p(x.data_ptr()) for x in (ret, length, ended, info, first)]
+    enqueue_ordered(env, holder, lambda: _cabi.lib().ngw_snapshot_playout(
+        env._h, src, ptr[0], int(count), steps, seed, first_pair, dst, ptr[1], *out, C.c_void_p(actions.data_ptr()) if record and count else None,
+        int(count)), count, uploaded, device)
+    if device:
+        return Playout(ret, length, ended.view(torch.bool), info, first, actions)
+    return Playout(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32), first.cpu().numpy(),
+                   None if actions is None else actions.cpu().numpy())
 
 
 class MapsTooLarge(_cabi.NgwError, ValueError):
@@ -525,6 +572,26 @@ class Snapshot:
         if device:
             return PlanEval(ret, length, ended.view(torch.bool), info)
         return PlanEval(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32))
+
+    def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False):
+        """Pair j: the state of parent parents[j] stepped on a private copy up to `steps` times by rollout()'s rules, with a random policy in
+        the place of a plan: at every step the action is drawn uniformly among the actions that would succeed from the state the pair is in
+        (every action where none would) - the default-policy simulation of a tree search's leaf, in one kernel launch.  The draw is the
+        public contract of include/ngw.h, which playout.choose_actions() computes on the host: it depends on (seed, first_pair + j, the step)
+        and the state only, so the same parent repeated gives differing playouts, and a call split in two with first_pair set gives the
+        rows of the whole one.  Returns a Playout of 'ret', 'length', 'ended', 'info' as rollout() reports them, 'first_action' int32 (the
+        action of step 0), each [count], and 'actions': with record=True int32 [steps, count], the action of every executed step (-1 for a
+        step the pair did not execute) - as a device tensor it is what rollout() takes as plans, so a playout can be replayed -, else None.
+        parents, children, source, from_envs and device mean what they mean in rollout(): children=None keeps nothing, otherwise
+        slot[children[j]] := the row as the last executed step leaves it.  Index tensors on the device are used in place: an index out of
+        range skips that pair (F_BAD_INDEX; its reports are 0, its actions -1).  Nothing is committed: no env, no mask, no lookahead table,
+        no prepared episode and no slot but the children changes."""
+        import torch
+        env = self.env
+        src, n_parents, same_buffer = self._source(source, from_envs, 'playout')
+        dev = torch.device('cuda:%d' % env.device)
+        p, c, count, steps = check_playout(parents, steps, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'playout', x))
+        return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device)
 
     # ------------------------------------------------------------------ slot observations (include/ngw.h ngw_snapshot_lidar / _agent_view / _action_mask)
     def _slots_arg(self, slots):

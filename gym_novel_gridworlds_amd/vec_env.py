@@ -1010,6 +1010,24 @@ class VecNovelGridworld:
         table._open_for(self)
         return insert_successors(self.successor_keys(envs, fields, device=True), table, device)
 
+    def playouts(self, n_playouts, steps, seed, device=False):
+        """P = n_playouts valid-action random playouts of up to `steps` steps from every env's CURRENT state, without taking a step and
+        without a snapshot of the caller's: Snapshot.playout(from_envs=True) with the parents repeat(arange(N), P).  Returns a Playout whose
+        fields are [N, P] ('actions' is None: Snapshot.playout records them).  Playout q of env i is pair (env_index_base + i) * P + q of the
+        stream of `seed` (the contract of include/ngw.h; playout.choose_actions on the host), so the ranks of a sharded env return what one
+        unsharded env returns.  One kernel launch; nothing is committed.  device=True: torch tensors on the env's device, ordered behind
+        the launch on torch's current stream."""
+        import torch
+        from .snapshot import check_playout, playout_call
+        P = int(n_playouts)
+        if P < 1:
+            raise ValueError("n_playouts: at least one playout per env expected, got %d" % P)
+        N = self.num_envs
+        dev = torch.device('cuda:%d' % self.device)
+        parents = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(P).contiguous()
+        _, _, count, steps = check_playout(parents, steps, None, N, 0, False, lambda x: None if x is None else int(x.numel()))
+        return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device).shaped(N, P)
+
     def fork(self, src, keep_episode=False):
         """Every env e becomes a copy of env src[e] (src: num_envs indices - a list / numpy array, checked, or a torch int32 tensor on the
         env's device), through an internal scratch snapshot: all states are saved first, so src may name any env, itself included.  The

@@ -143,6 +143,43 @@ class LimitActions(NoveltyWrapper):
             return out
         return SuccessorKeys(*[cols(x) for x in t])
 
+    def playouts(self, n_playouts, steps, seed, device=False):
+        """The env's playouts under this wrapper's action list: at every step the action is drawn among the LIMITED actions that would
+        succeed (every limited action where none would), and 'first_action' holds limited ids.  The draw needs the limited list as the
+        kernel's own action table, so the playouts run on a one-env batched env whose table is the limited one (limit_actions_vec, kept
+        from call to call) holding a copy of the current state; they equal what limit_actions_vec() of a batched env gives for that
+        state."""
+        adapter = self.unwrapped
+        vec = adapter._backend()
+        adapter._push(vec)                                   # (attributes the caller edited since the last step go to the device first)
+        env_actions = self.actions_id
+        names = sorted(self.limited_actions)
+        for name in names:
+            assert name in env_actions, _NOT_AN_ACTION.format(name=name, env_id=self.env_id)
+        kept = self.__dict__.get('_playout_env')
+        if kept is None or kept[0] is not vec or kept[1] != names:
+            if kept is not None:
+                kept[2].close()
+            kept = self.__dict__['_playout_env'] = (vec, names, limit_actions_vec(vec, names))
+        limited = kept[2]
+        st = vec.get_state()
+        limited.set_state(0, map=st['map'], loc=st['loc'], facing=st['facing'], inv=st['inv'], selected=st['selected'], step_count=st['step_count'])
+        play = limited.playouts(n_playouts, steps, seed, device=device).row(0)
+        ids = [self.limited_actions_id[name] for name in names]
+        if ids == list(range(len(names))):
+            return play
+        if device:                                           # (a table of its own, set_limited_actions_id: the kernel's id i is this wrapper's ids[i])
+            import torch
+            lut = torch.tensor(ids, dtype=play.first_action.dtype, device=play.first_action.device)
+            return play._replace(first_action=lut[play.first_action.long()])
+        return play._replace(first_action=np.asarray(ids, np.int32)[play.first_action])
+
+    def close(self):
+        kept = self.__dict__.pop('_playout_env', None)
+        if kept is not None:
+            kept[2].close()
+        return self.env.close()
+
     # (state_key() is NoveltyWrapper's forward: a key describes the state, not the action ids, so it is the same on either side of this wrapper)
 
 

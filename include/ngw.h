@@ -45,7 +45,7 @@ extern "C" {
 /* device-side sticky error flags (ngw_error_flags) */
 #define NGW_F_INVALID_ACTION 1u
 #define NGW_F_PLACEMENT 2u
-#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros); ngw_state_keys: a row index outside its range (that key is 0) */
+#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout / ngw_snapshot_playout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros); ngw_state_keys: a row index outside its range (that key is 0) */
 #define NGW_F_TABLE_FULL 8u     /* ngw_key_table_insert: a key found neither itself nor a free bucket after probing every bucket (it was refused: where = -1, fresh = 0) */
 
 /* action kinds (act_kind[]); act_arg[] = recipe index (CRAFT) or item id (SELECT) */
@@ -659,6 +659,38 @@ int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64
  * the call cannot hold. */
 int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev, int32_t* reward_dev,
                        uint8_t* done_dev, uint32_t* info_dev);
+
+/* Playouts: "from this node, play n_steps steps of a random policy and report what happened" - the default-policy simulation of MCTS, flat
+ * Monte-Carlo and Go-Explore.  The policy is uniform over the actions that WOULD SUCCEED from the state the pair is in at that step, which
+ * only the device knows inside a rollout; the actions are therefore drawn in the kernel.  The choice is a public contract, like the state
+ * key, so a host can reproduce any playout from (seed, pair number, step) and the state.  For pair j of a call - global pair number
+ * p = first_pair + j, a uint64 - at step t (0-based):
+ *     m  = the valid-action mask word of the pair's state before step t: bit a is set exactly when step(a) would report result = 1 (the
+ *          predicate of ngw_action_mask / ngw_snapshot_action_mask);  if m == 0 (no action would succeed): m = all n_actions bits
+ *     n  = popcount(m)
+ *     w  = word (t & 3) of Philox4x32-10 with counter (t >> 2, 0, lo32(p), hi32(p)) and key (lo32(seed), hi32(seed) ^ NGW_PLAYOUT_TAG) - the
+ *          generator and word order of ngw_rollout under another tag: a playout and a fused rollout of one seed are unrelated
+ *     k  = ((uint64)w * n) >> 32;  the action is the id of the (k + 1)-th set bit of m, counted from bit 0.
+ * The draw depends on (seed, p, t) and the state only: not on the slot, the env index, the rank, how the pairs fall into wavefronts, or how
+ * many steps earlier calls ran.
+ * Everything else follows ngw_snapshot_rollout: src / src_idx_dev / dst / dst_slots_dev / count mean what they mean there (src == NULL: the
+ * envs' current states; dst == NULL: nothing is kept, and dst_slots_dev must then be NULL); the pair steps a private copy of the parent row, it
+ * stops at the first step whose `done` would be 1 (goal, FireWall death, the horizon under autoreset), that step counts, no reset ever runs,
+ * and an ended pair draws nothing more.  ret / length / ended / info take element j as ngw_snapshot_rollout defines them; first_action_dev[j]
+ * (int32) is the action of step 0 - what a flat Monte-Carlo search groups the returns by -; actions_dev (int32) takes the action of pair j at
+ * step t at [t * actions_stride + j], the layout ngw_snapshot_rollout reads, so a recorded playout can be replayed; a step the pair did not
+ * execute holds -1.  Every output pointer may be NULL.
+ * A parent or destination index out of range skips the pair: nothing is ever addressed with the bad index, its four reports are stored as 0,
+ * its first action and its column of actions_dev as -1, no slot is written for it, and the sticky NGW_F_BAD_INDEX is raised.
+ * Nothing is committed - ngw_snapshot_rollout's list holds word for word.  One kernel launch (ngw_playout.inc), enqueued on the handle's
+ * stream; does not wait.  A captured graph stays valid.  count == 0 is a no-op.  A one-env handle's resident step loop is ended first.
+ * NGW_E_INVALID_ARG: a NULL handle; n_steps < 1; count < 0; actions_dev given with actions_stride < count; dst == NULL with dst_slots_dev !=
+ * NULL; a src or dst that is not an open snapshot of this handle; count above dst's capacity; src_idx_dev == NULL with count above the source's
+ * row count; maps that do not fit LDS (ngw_snapshot_rollout's limit). */
+#define NGW_PLAYOUT_TAG 0x504C4159u
+int ngw_snapshot_playout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                         ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev,
+                         int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride);
 
 /* Key table: an open-addressing hash set of 64-bit keys in device memory - "have I seen this state BEFORE?" across the calls of a search that
  * runs many iterations (transposition tables, duplicate removal in breadth-first solvers, Go-Explore archives, count-based bonuses).  A table
