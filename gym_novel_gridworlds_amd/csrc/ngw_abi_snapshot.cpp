@@ -9,6 +9,7 @@
 // The state keys (ngw_keys.inc) hash rows of a snapshot or of the state slab into the caller's buffer: they commit nothing either.
 // The successor keys (ngw_successors.inc) are the keys of every action's child of such rows, with no child stored: they commit nothing either.
 // A playout (ngw_playout.inc) is a rollout whose actions the kernel draws among the valid ones of each step: it commits nothing either.
+// The weighted choice (ngw_sample.inc) draws one action per row by the caller's weights among the valid ones: it commits nothing either.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -221,9 +222,10 @@ int ngw_snapshot_rollout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_id
     return NGW_OK;
 }
 
-int ngw_snapshot_playout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
-                         ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev,
-                         int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride) {
+int ngw_snapshot_playout_weighted(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed,
+                                  uint64_t first_pair, const float* weights_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev,
+                                  int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev,
+                                  int64_t actions_stride) {
     if (!h) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "playout of %d steps", (int)n_steps);
     if (count < 0 || (actions_dev && actions_stride < count))
@@ -238,10 +240,17 @@ int ngw_snapshot_playout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_id
     if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
     x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = actions_stride; x.n_steps = n_steps;
     x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev; x.first_action = first_action_dev;
-    x.seed = seed; x.first_pair = first_pair;
+    x.seed = seed; x.first_pair = first_pair; x.weights = weights_dev;
     x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
     HIP_TRY(ngw_playout_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
     return NGW_OK;
+}
+
+int ngw_snapshot_playout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                         ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev,
+                         int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride) {
+    return ngw_snapshot_playout_weighted(h, src, src_idx_dev, count, n_steps, seed, first_pair, nullptr, dst, dst_slots_dev, ret_dev, length_dev, ended_dev, info_dev,
+                                         first_action_dev, actions_dev, actions_stride);
 }
 
 int ngw_snapshot_lidar(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, int64_t count, void* rows_dev) {
@@ -283,6 +292,25 @@ int ngw_snapshot_action_mask(ngw_handle* h, ngw_snapshot* s, const int32_t* slot
     NgwSlotObs x{};
     x.src = s->r; x.slots = slots_dev; x.flags = h->b.flags; x.count = (int32_t)count; x.rows = (int32_t)s->cap;
     HIP_TRY(ngw_slot_mask_launch(h->dspec, &x, h->proto.S, h->proto.K, h->ext, masks_dev, h->stream));
+    return NGW_OK;
+}
+
+int ngw_sample_actions(ngw_handle* h, ngw_snapshot* src, const int32_t* idx_dev, int64_t count, const float* weights_dev, int64_t weight_stride,
+                       uint64_t seed, uint64_t first_pair, uint32_t t, int32_t* actions_dev, float* mass_dev, uint64_t* masks_dev) {
+    if (!h || !weights_dev || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (src && !owns(h, src)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    const int64_t rows = src ? src->cap : h->n;
+    if (count < 0 || count > 0x7FFFFFFFll || weight_stride < count)
+        return fail(NGW_E_INVALID_ARG, "sampled actions of %lld states with a weight stride of %lld", (long long)count, (long long)weight_stride);
+    if (!idx_dev && count > rows) return fail(NGW_E_INVALID_ARG, "sampled actions of %lld states from %lld %s", (long long)count, (long long)rows, src ? "slots" : "envs");
+    if (int rc = enter(h)) return rc;                 // (src == NULL: the one-env loop has ended, HBM holds the env's state)
+    if (count == 0) return NGW_OK;
+    NgwSample x{};
+    x.src = src ? src->r : state_rows(h); x.idx = idx_dev; x.flags = h->b.flags;
+    x.weights = weights_dev; x.stride = weight_stride; x.seed = seed; x.first_pair = first_pair; x.t = t;
+    x.actions = actions_dev; x.mass = mass_dev; x.masks = masks_dev;
+    x.count = (int32_t)count; x.rows = (int32_t)rows;
+    HIP_TRY(ngw_sample_launch(h->dspec, &x, h->proto.S, h->proto.K, h->ext, h->stream));
     return NGW_OK;
 }
 

@@ -534,6 +534,7 @@ struct NgwPlayout {
     uint64_t seed, first_pair;
     int32_t count, src_rows, dst_rows;
     int32_t n_steps, keep;
+    const float* weights; /* nullptr: the uniform rule; else [n_actions] float32, the weighted rule of ngw_sample_actions at every step (last: the fields before it keep their offsets) */
 };
 #ifdef __cplusplus
 extern "C"
@@ -569,6 +570,29 @@ extern "C"
 #endif
 /* out[j] = the mask word of slot slots[j] ([count] words; ngw_mask.inc's predicate) */
 hipError_t ngw_slot_mask_launch(const NgwDevSpec* dspec, const struct NgwSlotObs* x, int S, int K, int ext, uint64_t* out, hipStream_t stream);
+
+/* The weighted choice (ngw_sample.inc, ngw_abi_snapshot.cpp): for pair j < count, row idx[j] of `src` (a snapshot or the state slab; a NULL list = j
+ * itself) gets one action drawn by the rule of include/ngw.h (ngw_sample_actions) from the weights weights[a * stride + j] (stride >= count), as pair
+ * number first_pair + j of the stream of `seed` at step number t.  actions[j] int32, mass[j] float32 and masks[j] (mass, masks: may be nullptr).
+ * An index outside [0, rows) is never used as an address: its outputs are -1 / 0 / 0 and NGW_F_BAD_INDEX is raised in *flags; a bad weight
+ * raises NGW_F_BAD_WEIGHT.  Nothing but the three outputs and the flags word is stored. */
+struct NgwSample {
+    NgwSnapRows src;
+    const int32_t* idx;
+    const float* weights;
+    int64_t stride;
+    uint64_t seed, first_pair;
+    uint32_t* flags;
+    int32_t* actions;
+    float* mass;
+    uint64_t* masks;
+    int32_t count, rows;
+    uint32_t t;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_sample_launch(const NgwDevSpec* dspec, const struct NgwSample* x, int S, int K, int ext, hipStream_t stream);
 
 /* State keys (ngw_keys.inc, ngw_abi_snapshot.cpp): keys[j] = the 64-bit key (include/ngw.h, ngw_state_keys) of row idx[j] of `src` (a snapshot or the
  * state slab; a NULL list = j itself) under the field selection `fields` (NGW_KEY_*).  An index outside [0, rows) is never used as an address: its

@@ -30,7 +30,7 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file TWENTY-ONE times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file TWENTY-TWO times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
@@ -43,6 +43,7 @@
 //   17: state keys (ngw_keys.inc: 64-bit hashes of saved slots and live envs)   18: the key table (ngw_table.inc: a hash set of such keys)
 //   19: successor keys (ngw_successors.inc: the key of every action's child; it shares ngw_expand.inc's row mover and ngw_keys.inc's terms)
 //   20: snapshot playout (ngw_playout.inc: valid-action random playouts from saved rows; it shares ngw_expand.inc's row mover and ngw_mask.inc's walk)
+//   21: the weighted choice among valid actions (ngw_sample.inc: one action per state by caller-supplied weights; its selection function is part 20's too)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -399,6 +400,9 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #endif
 #if NGW_HAS(15)
 #include "ngw_slot_rollout.inc"
+#endif
+#if NGW_HAS(20) || NGW_HAS(21)
+#include "ngw_sample.inc"
 #endif
 #if NGW_HAS(20)
 #include "ngw_playout.inc"
@@ -885,11 +889,24 @@ extern "C" hipError_t ngw_playout_launch(const NgwDevSpec* dspec, const NgwLaunc
     const dim3 grid((unsigned)(((int64_t)x->count + NGW_EPB - 1) / NGW_EPB)), block(NGW_EPB);
     return with_row_piece(a->S2, [&](auto V) {
         return with_flag(ext != 0, [&](auto E) {
-            return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+            return with_flag(x->weights != nullptr, [&](auto W) {
+                return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, decltype(W)::value>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+            });
         });
     });
 }
 #endif  // NGW_HAS(20)
+
+#if NGW_HAS(21)
+// the weighted choice (ngw_sample.inc): x->count pairs of rows of x->src through the index list; one wave per 64 pairs, no dynamic LDS
+extern "C" hipError_t ngw_sample_launch(const NgwDevSpec* dspec, const NgwSample* x, int S, int K, int ext, hipStream_t stream) {
+    if (x->count <= 0 || x->rows < 1 || x->stride < x->count || S < 3 || S > NGW_MAX_MAP_SIZE || K < 1 || K > NGW_MAX_ITEMS || !x->flags || !x->src.map ||
+        !x->weights || !x->actions)
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((int64_t)x->count + NGW_EPB - 1) / NGW_EPB)), block(NGW_EPB);
+    return with_flag(ext != 0, [&](auto E) { return launch_kernel<ngw_sample_kernel<decltype(E)::value>>(grid, block, 0, stream, dspec, *x, S, K); });
+}
+#endif  // NGW_HAS(21)
 
 #if NGW_HAS(16)
 // slot observations (ngw_slot_observe.inc).  The lidar rows: a = the stand-alone lidar launch's layout with a.lout = the caller's rows; one wave per 64 pairs

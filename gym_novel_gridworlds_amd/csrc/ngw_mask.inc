@@ -93,6 +93,25 @@ __device__ __forceinline__ LeanLane lean_load_lane(const NgwBufs& b, uint32_t n3
     return l;
 }
 
+// lean_load_lane, gathered: pose, selected item and map base come from row `row` of the set, the inventory row goes into the lane's private LDS row
+// (the slot masks of ngw_slot_observe.inc and the weighted choice of ngw_sample.inc).
+__device__ __forceinline__ LeanLane lean_gather_lane(const NgwSnapRows& s, int row, bool live, int S, int K, int32_t* inv_lds) {
+    const uint32_t tid = threadIdx.x;
+    const int KP = K | 1;
+    LeanLane l;
+    l.live = live;
+    l.bmap = reinterpret_cast<const char*>(s.map) + (size_t)row * (size_t)(S * S);
+    l.mapoff = 0u;
+    const int2 rc = reinterpret_cast<const int2*>(s.loc)[row];
+    const int f0 = s.facing[row];
+    l.sel = s.selected[row];
+    l.inv = inv_lds + tid * KP;
+    const int32_t* const ginv = s.inv + (size_t)row * (size_t)K;
+    for (int k = 0; k < K; k++) l.inv[k] = ginv[k];
+    l.r = rc.x; l.c = rc.y; l.f = f0 & 3;
+    return l;
+}
+
 // The walk over the entries: the mask of one lane's state from its pose and selected item, its inventory row (a lane-private LDS row) and its map
 // (cell_at: a cell index -> the item there), fed the table (lane l holds entry l), the uniform parameters and the wrapper predicates the caller
 // holds; A = the number of entries to walk.  All lanes of the wave must be active (the loop is wave-uniform).

@@ -1,10 +1,10 @@
-// ngw_playout.inc - snapshot playout (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc and ngw_expand.inc; a unit of its
+// ngw_playout.inc - snapshot playout (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc, ngw_expand.inc and ngw_sample.inc; a unit of its
 // own; host side: ngw_abi_snapshot.cpp).
 //
 // Pair j of a call: the parent is row si[j] of the source set (the state slab, or a snapshot); it is stepped on a private copy up to n_steps
 // times by the rules of ngw_slot_rollout_kernel - it stops at the first step whose `done` would be 1, that step counts, no reset ever runs -
 // with actions DRAWN HERE: at every step uniformly among the actions that would succeed from the state the pair is in (include/ngw.h, the
-// choice rule of ngw_snapshot_playout: mask word, Philox word, the k-th set bit).  Nothing here restates a game rule: the mask is
+// choice rule of ngw_snapshot_playout: mask word, Philox word, the k-th set bit; playout_kth_bit is ngw_sample.inc's).  Nothing here restates a game rule: the mask is
 // lean_mask_walk's, the step is lean_body, the generator is philox_block.
 //
 // Shape: ngw_slot_rollout_kernel's, with the choice in the place of the plan read.  One work-group is one wave: 64 consecutive pairs.
@@ -21,20 +21,13 @@
 // No reset path is in this kernel and no store to a.b.* but the flags word.  Source and destination may be the same allocation (see
 // ngw_slot_rollout.inc).
 //
+// WEIGHTED (ngw_snapshot_playout_weighted): x.weights holds one float32 per action, lane a keeps x.weights[a] in a register, and the choice of
+// every step is sample_choice (ngw_sample.inc) on the step's own m and w - the weighted rule of ngw_sample_actions, the uniform rule where
+// the valid actions' mass is 0.  WEIGHTED = false is the kernel as it was.
+//
 // x.actions (may be nullptr): int32, the action of pair j at step t to [t * x.stride + j] (stride >= count) - the layout ngw_slot_rollout_kernel reads.
 
-// the id of the (k + 1)-th set bit of m, counted from bit 0 (k < popcount(m)): six halvings, branch-free per lane
-__device__ __forceinline__ int playout_kth_bit(uint64_t m, uint32_t k) {
-    int pos = 0;
-#pragma unroll
-    for (int width = 32; width >= 1; width >>= 1) {
-        const uint32_t below = (uint32_t)__popcll((m >> pos) & ((1ull << width) - 1ull));
-        if (k >= below) { pos += width; k -= below; }
-    }
-    return pos;
-}
-
-template <int VEC, bool EXT>
+template <int VEC, bool EXT, bool WEIGHTED>
 __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* __restrict__ dspec, const NgwLaunch a, const NgwPlayout x) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t tid = threadIdx.x;
@@ -62,6 +55,9 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
     NgwStepU U;
     NgwExtU X;
     lean_fetch_uniforms<EXT>(dspec, U, X);
+    float xw = 0.0f;                                                               // WEIGHTED: lane a holds x[a], the walk reads it with v_readlane
+    if constexpr (WEIGHTED)
+        if ((int)tid < min(U.n_actions, NGW_MAX_ACTIONS)) xw = x.weights[tid];     // (the array holds n_actions floats and no more)
     // the 64 parent rows into the handle's LDS layout
     uint32_t* const lds_map = lds + a.off_map;
     int32_t* const lds_inv = reinterpret_cast<int32_t*>(lds + a.off_inv);
@@ -104,8 +100,16 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
         if (m == 0) m = all_actions;
         const uint32_t qq = (uint32_t)s & 3u;
         const uint32_t w = qq == 0 ? w0 : (qq == 1 ? w1 : (qq == 2 ? w2 : w3));
-        const uint32_t k = __umulhi(w, (uint32_t)__popcll(m));
-        const int action = alive ? playout_kth_bit(m, k) : -1;
+        int action;
+        if constexpr (WEIGHTED) {                                                  // rules 3 - 6 of ngw_sample_actions on this m and this w; every lane walks
+            float mass;
+            const int drawn = sample_choice(m, w, A, [&](int a) -> float { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, xw), a)); },
+                                            mass, flags);
+            action = alive ? drawn : -1;
+        } else {                                                                   // (written as it always was: the instruction stream of this form is unchanged)
+            const uint32_t k = __umulhi(w, (uint32_t)__popcll(m));
+            action = alive ? playout_kth_bit(m, k) : -1;
+        }
         if (rec && inside) rec[(int64_t)s * tstride] = action;
         if (s == 0) first = action;
         const int ai = (alive ? action : 63) << 2;

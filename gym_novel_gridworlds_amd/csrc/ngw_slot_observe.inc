@@ -49,25 +49,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_lidar_kernel(const NgwLaunch
 }
 
 // ---------------------------------------------------------------- action masks
-// lean_load_lane, gathered: pose, selected item and map base come from row `row` of the set, the inventory row goes into the lane's private LDS row.
-__device__ __forceinline__ LeanLane lean_gather_lane(const NgwSnapRows& s, int row, bool live, int S, int K, int32_t* inv_lds) {
-    const uint32_t tid = threadIdx.x;
-    const int KP = K | 1;
-    LeanLane l;
-    l.live = live;
-    l.bmap = reinterpret_cast<const char*>(s.map) + (size_t)row * (size_t)(S * S);
-    l.mapoff = 0u;
-    const int2 rc = reinterpret_cast<const int2*>(s.loc)[row];
-    const int f0 = s.facing[row];
-    l.sel = s.selected[row];
-    l.inv = inv_lds + tid * KP;
-    const int32_t* const ginv = s.inv + (size_t)row * (size_t)K;
-    for (int k = 0; k < K; k++) l.inv[k] = ginv[k];
-    l.r = rc.x; l.c = rc.y; l.f = f0 & 3;
-    return l;
-}
-
-// ngw_mask_kernel over gathered lanes: one lane per pair, every lane stays active through lane_mask (its walk is wave-uniform), a lane that is not
+// ngw_mask_kernel over gathered lanes (lean_gather_lane, ngw_mask.inc): one lane per pair, every lane stays active through lane_mask (its walk is wave-uniform), a lane that is not
 // live stores 0, stores are bounded by count.
 template <bool EXT>
 __global__ void __launch_bounds__(NGW_EPB) ngw_slot_mask_kernel(const NgwDevSpec* __restrict__ dspec, const NgwSlotObs x, int S, int K, uint64_t* __restrict__ out) {

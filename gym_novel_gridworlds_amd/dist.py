@@ -125,11 +125,21 @@ class ShardedVecNovelGridworld:
             plans = plans[self.first:self.first + self.num_envs]
         return self.local.evaluate_plans(plans, device=device, copy=copy)
 
-    def playouts(self, n_playouts, steps, seed, device=False):
+    def sample_actions(self, weights, seed, t=0, envs=None, device=False):
+        """One weighted choice among the valid actions per env of this rank's shard (VecNovelGridworld.sample_actions): rank-local, no
+        collective; weights are the shard's rows.  The local env numbers its pairs from env_index_base (= first), so the ranks together
+        return what one unsharded env over all the envs returns."""
+        return self.local.sample_actions(weights, seed, t=t, envs=envs, device=device)
+
+    def step_sampled(self, weights, seed, t=0):
+        """sample_actions + step_device on this rank's shard (VecNovelGridworld.step_sampled)."""
+        return self.local.step_sampled(weights, seed, t=t)
+
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None):
         """Valid-action random playouts from the current states of this rank's shard (VecNovelGridworld.playouts): [num_envs, P] fields;
         rank-local, no collective.  The local env numbers its pairs from env_index_base * P (= first * P), so the ranks together return what
         one unsharded env over all the envs returns."""
-        return self.local.playouts(n_playouts, steps, seed, device=device)
+        return self.local.playouts(n_playouts, steps, seed, device=device, weights=weights)
 
     def snapshot(self, capacity=None):
         """A device-side snapshot of this rank's shard (VecNovelGridworld.snapshot): rank-local, env indices are the shard's own - in

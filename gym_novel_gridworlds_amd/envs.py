@@ -325,13 +325,21 @@ class _NovelGridworldEnv(_EnvBase):
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
         return vec.evaluate_plans(a[None], device=device, copy=copy).row(0)
 
-    def playouts(self, n_playouts, steps, seed, device=False):
+    def sample_action(self, weights, seed, t=0):
+        """One action for the current state, drawn with probability proportional to weights[A] among the actions the state accepts:
+        (action, mass, mask_word) as Python scalars; see VecNovelGridworld.sample_actions."""
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        s = vec.sample_actions(np.asarray(weights)[None], seed, t=t)
+        return int(s.action[0]), float(s.mass[0]), int(s.mask_words[0])
+
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None):
         """P = n_playouts valid-action random playouts of up to `steps` steps from the current state, without taking a step: a Playout of
         'ret' int32, 'length' int32, 'ended' bool, 'info' uint32 and 'first_action' int32, each [P]; playout q is pair q of the stream of
         `seed`; see VecNovelGridworld.playouts."""
         vec = self._backend()
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
-        return vec.playouts(n_playouts, steps, seed, device=device).row(0)
+        return vec.playouts(n_playouts, steps, seed, device=device, weights=weights).row(0)
 
     def state_key(self, fields=KEY_STATE):
         """The 64-bit key of the current state as a Python int, computed on the device under the field selection `fields` (KEY_* bits,

@@ -53,8 +53,11 @@ class NoveltyWrapper(object):
     def evaluate_plans(self, plans, device=False, copy=False):
         return self.env.evaluate_plans(plans, device=device, copy=copy)
 
-    def playouts(self, n_playouts, steps, seed, device=False):
-        return self.env.playouts(n_playouts, steps, seed, device=device)
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None):
+        return self.env.playouts(n_playouts, steps, seed, device=device, weights=weights)
+
+    def sample_action(self, weights, seed, t=0):
+        return self.env.sample_action(weights, seed, t=t)
 
     def state_key(self, fields=KEY_STATE):
         return self.env.state_key(fields)

@@ -341,9 +341,10 @@ def fresh_pairs(fresh):
     return divmod(np.flatnonzero(np.asarray(fresh).reshape(-1)), A)
 
 
-def playout_call(env, holder, src, dst, parents, children, count, steps, seed, first_pair, record, device):
+def playout_call(env, holder, src, dst, parents, children, count, steps, seed, first_pair, record, device, weights=None):
     """The one launch behind Snapshot.playout and VecNovelGridworld.playouts: src / dst are snapshots' C handles (src None: the envs' current
     states; dst None: nothing is kept), parents / children the checked lists (check_playout); `holder` keeps the uploaded lists alive.
+    weights: None (the uniform rule), or one float32 per action from the host or the device (sample.check_weights).
     -> Playout of [count] fields, actions [steps, count] with `record`."""
     import torch
     from .playout import Playout
@@ -354,6 +355,12 @@ def playout_call(env, holder, src, dst, parents, children, count, steps, seed, f
         raise ValueError("first_pair: %d outside [0, 2^64)" % first_pair)
     dev = torch.device('cuda:%d' % env.device)
     ptr, uploaded = upload(dev, count, parents, children)
+    wt = None
+    if weights is not None:
+        from .sample import check_weights
+        wt, mine = check_weights(weights, count, env.n_actions, dev, per_pair=False)
+        if mine:
+            uploaded = uploaded + [wt]
     ret = torch.zeros(count, dtype=torch.int32, device=dev)
     length = torch.zeros(count, dtype=torch.int32, device=dev)
     ended = torch.zeros(count, dtype=torch.uint8, device=dev)
@@ -361,9 +368,13 @@ def playout_call(env, holder, src, dst, parents, children, count, steps, seed, f
     first = torch.full((count,), -1, dtype=torch.int32, device=dev)
     actions = torch.full((steps, count), -1, dtype=torch.int32, device=dev) if record else None
     out = [C.c_void_p(x.data_ptr()) for x in (ret, length, ended, info, first)]
-    enqueue_ordered(env, holder, lambda: _cabi.lib().ngw_snapshot_playout(
-        env._h, src, ptr[0], int(count), steps, seed, first_pair, dst, ptr[1], *out, C.c_void_p(actions.data_ptr()) if record and count else None,
-        int(count)), count, uploaded, device)
+    recorded = C.c_void_p(actions.data_ptr()) if record and count else None
+    if wt is None:                              # (the call as it always was)
+        call = lambda: _cabi.lib().ngw_snapshot_playout(env._h, src, ptr[0], int(count), steps, seed, first_pair, dst, ptr[1], *out, recorded, int(count))   # noqa: E731
+    else:
+        call = lambda: _cabi.lib().ngw_snapshot_playout_weighted(env._h, src, ptr[0], int(count), steps, seed, first_pair, C.c_void_p(wt.data_ptr()), dst,   # noqa: E731
+                                                                 ptr[1], *out, recorded, int(count))
+    enqueue_ordered(env, holder, call, count, uploaded, device)
     if device:
         return Playout(ret, length, ended.view(torch.bool), info, first, actions)
     return Playout(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32), first.cpu().numpy(),
@@ -573,7 +584,7 @@ class Snapshot:
             return PlanEval(ret, length, ended.view(torch.bool), info)
         return PlanEval(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32))
 
-    def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False):
+    def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False, weights=None):
         """Pair j: the state of parent parents[j] stepped on a private copy up to `steps` times by rollout()'s rules, with a random policy in
         the place of a plan: at every step the action is drawn uniformly among the actions that would succeed from the state the pair is in
         (every action where none would) - the default-policy simulation of a tree search's leaf, in one kernel launch.  The draw is the
@@ -585,13 +596,17 @@ class Snapshot:
         parents, children, source, from_envs and device mean what they mean in rollout(): children=None keeps nothing, otherwise
         slot[children[j]] := the row as the last executed step leaves it.  Index tensors on the device are used in place: an index out of
         range skips that pair (F_BAD_INDEX; its reports are 0, its actions -1).  Nothing is committed: no env, no mask, no lookahead table,
-        no prepared episode and no slot but the children changes."""
+        no prepared episode and no slot but the children changes.
+        weights: None, or float32 [A] - a list / numpy array, or a torch tensor on the env's device used in place: a "heavy" playout.  Every
+        step's action is then drawn with probability proportional to the weights among the valid actions (uniformly among them where none
+        of them has a weight): rules 3 - 6 of ngw_sample_actions on the playout's own mask word and Philox word, which
+        sample.choose_weighted(..., words=playout.playout_words(...)) computes on the host.  A bad weight raises F_BAD_WEIGHT."""
         import torch
         env = self.env
         src, n_parents, same_buffer = self._source(source, from_envs, 'playout')
         dev = torch.device('cuda:%d' % env.device)
         p, c, count, steps = check_playout(parents, steps, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'playout', x))
-        return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device)
+        return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights)
 
     # ------------------------------------------------------------------ slot observations (include/ngw.h ngw_snapshot_lidar / _agent_view / _action_mask)
     def _slots_arg(self, slots):
@@ -664,6 +679,19 @@ class Snapshot:
         if device:
             return unpack_action_masks_device(words, env.n_actions)
         return unpack_action_masks(words.cpu().numpy().view(np.uint64), env.n_actions)
+
+    def sample_actions(self, slots, weights, seed, first_pair=0, t=0, device=False):
+        """VecNovelGridworld.sample_actions over saved slots: one action per entry of `slots`, drawn with probability proportional to
+        weights among the actions that slot's state accepts - the prior-guided expansion step of a tree search over a node pool.  slots as
+        in lidar_observation (they may repeat, and their number is not bound by the capacity; None: every slot); weights a host array
+        [count, A] or a torch float32 tensor [A, count] on the env's device, used in place.  Entry j is pair first_pair + j of the stream of
+        `seed` at step number t (the contract of include/ngw.h; sample.choose_weighted on the host), so the same slot repeated gives
+        independent draws and a call split in two with first_pair set gives the rows of the whole one.  Returns Sampled(action, mass,
+        mask_words), each [count]; an index out of range in a device list: action -1, mass 0, word 0, F_BAD_INDEX.  One kernel launch at
+        every map size; nothing is committed."""
+        from .sample import sample_call
+        self._open()
+        return sample_call(self.env, self, self._s, slots, self.capacity, 'slots', weights, seed, first_pair, t, device)
 
     # ------------------------------------------------------------------ state keys (include/ngw.h ngw_state_keys; state_keys.py)
     def keys(self, slots=None, fields=KEY_STATE, device=False):

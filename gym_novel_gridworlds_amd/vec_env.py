@@ -1010,13 +1010,40 @@ class VecNovelGridworld:
         table._open_for(self)
         return insert_successors(self.successor_keys(envs, fields, device=True), table, device)
 
-    def playouts(self, n_playouts, steps, seed, device=False):
+    def sample_actions(self, weights, seed, t=0, envs=None, device=False):
+        """One action per env, drawn with probability proportional to the caller's weights among the actions the env's CURRENT state accepts
+        (every action where it accepts none) - invalid-action masking, the normalisation and the draw of a policy-gradient loop in one
+        kernel launch.  weights: a host array [count, A] of non-negative numbers (checked for shape and dtype, transposed and uploaded), or
+        a torch float32 tensor [A, count] on the env's device - action-major - that is used in place.  Returns Sampled(action int32, mass
+        float32, mask_words uint64), each [count]: mass is the sum of the valid actions' weights, so log pi(a) = log weights[a] - log mass
+        (0 where no valid action had a weight and the choice was uniform among the valid ones); mask_words is the valid-action word the
+        choice was made under.  The choice is the public contract of include/ngw.h (ngw_sample_actions), which sample.choose_weighted
+        computes on the host bit for bit: it depends on (seed, env_index_base + j, t), the state and the weights alone, so the ranks of a
+        sharded env return what one unsharded env returns; pass a new t (or seed) for every step of a trajectory.  A weight below 2^-64
+        counts as 0; a negative, NaN or larger-than-2^64 weight counts as 0 too and raises the sticky F_BAD_WEIGHT (error_flags()), from the
+        host and from the device alike.  envs as in state_keys() (an index out of range in a device list: action -1, mass 0, word 0,
+        F_BAD_INDEX).  Nothing is committed.  device=True: torch tensors on the env's device (the words int64 over the same bits), ordered
+        behind the launch on torch's current stream, no host wait."""
+        from .sample import sample_call
+        return sample_call(self, self._keeper(), None, envs, self.num_envs, 'envs', weights, seed, self.env_index_base, t, device)
+
+    def step_sampled(self, weights, seed, t=0):
+        """sample_actions(weights, seed, t, device=True) followed by step_device on the sampled actions: two launches on the env's stream with
+        no host wait in between.  Returns the Sampled tuple on the device - the actions the step took, the mass and the mask words of the
+        state BEFORE the step; the step's outputs are where step_device leaves them (device_outputs())."""
+        s = self.sample_actions(weights, seed, t, device=True)
+        self._keeper()._keep = (self._keeper()._keep or []) + [s.action]     # (the step reads the tensor after this call returns)
+        self.step_device(s.action.data_ptr())
+        return s
+
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None):
         """P = n_playouts valid-action random playouts of up to `steps` steps from every env's CURRENT state, without taking a step and
         without a snapshot of the caller's: Snapshot.playout(from_envs=True) with the parents repeat(arange(N), P).  Returns a Playout whose
         fields are [N, P] ('actions' is None: Snapshot.playout records them).  Playout q of env i is pair (env_index_base + i) * P + q of the
         stream of `seed` (the contract of include/ngw.h; playout.choose_actions on the host), so the ranks of a sharded env return what one
         unsharded env returns.  One kernel launch; nothing is committed.  device=True: torch tensors on the env's device, ordered behind
-        the launch on torch's current stream."""
+        the launch on torch's current stream.  weights: float32 [A] (host or device) - every step's action is then drawn with probability
+        proportional to them among the valid ones (Snapshot.playout)."""
         import torch
         from .snapshot import check_playout, playout_call
         P = int(n_playouts)
@@ -1026,7 +1053,7 @@ class VecNovelGridworld:
         dev = torch.device('cuda:%d' % self.device)
         parents = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(P).contiguous()
         _, _, count, steps = check_playout(parents, steps, None, N, 0, False, lambda x: None if x is None else int(x.numel()))
-        return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device).shaped(N, P)
+        return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights).shaped(N, P)
 
     def fork(self, src, keep_episode=False):
         """Every env e becomes a copy of env src[e] (src: num_envs indices - a list / numpy array, checked, or a torch int32 tensor on the

@@ -143,12 +143,9 @@ class LimitActions(NoveltyWrapper):
             return out
         return SuccessorKeys(*[cols(x) for x in t])
 
-    def playouts(self, n_playouts, steps, seed, device=False):
-        """The env's playouts under this wrapper's action list: at every step the action is drawn among the LIMITED actions that would
-        succeed (every limited action where none would), and 'first_action' holds limited ids.  The draw needs the limited list as the
-        kernel's own action table, so the playouts run on a one-env batched env whose table is the limited one (limit_actions_vec, kept
-        from call to call) holding a copy of the current state; they equal what limit_actions_vec() of a batched env gives for that
-        state."""
+    def _limited_env(self):
+        """-> (the one-env batched env whose action table is this wrapper's list - limit_actions_vec, kept from call to call - holding a copy
+        of the adapter's current state, this wrapper's id of each of its actions): what playouts() and sample_action() run on."""
         adapter = self.unwrapped
         vec = adapter._backend()
         adapter._push(vec)                                   # (attributes the caller edited since the last step go to the device first)
@@ -164,9 +161,36 @@ class LimitActions(NoveltyWrapper):
         limited = kept[2]
         st = vec.get_state()
         limited.set_state(0, map=st['map'], loc=st['loc'], facing=st['facing'], inv=st['inv'], selected=st['selected'], step_count=st['step_count'])
-        play = limited.playouts(n_playouts, steps, seed, device=device).row(0)
-        ids = [self.limited_actions_id[name] for name in names]
-        if ids == list(range(len(names))):
+        return limited, [self.limited_actions_id[name] for name in names]
+
+    def sample_action(self, weights, seed, t=0):
+        """The env's sample_action under this wrapper's action list: weights has one entry per limited id, the action is drawn among the
+        LIMITED actions that would succeed and is a limited id; bit i of the mask word is limited id i.  Runs where playouts() runs."""
+        w = np.asarray(weights)
+        if w.shape != (len(self.limited_actions),):
+            raise ValueError("weights: one weight per limited action expected, shape [%d], got %s" % (len(self.limited_actions), list(w.shape)))
+        limited, ids = self._limited_env()
+        s = limited.sample_actions(w[ids][None], seed, t=t)          # (the kernel's action i is this wrapper's ids[i])
+        word = sum(1 << ids[i] for i in range(len(ids)) if (int(s.mask_words[0]) >> i) & 1)
+        return ids[int(s.action[0])], float(s.mass[0]), word
+
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None):
+        """The env's playouts under this wrapper's action list: at every step the action is drawn among the LIMITED actions that would
+        succeed (every limited action where none would), and 'first_action' holds limited ids.  The draw needs the limited list as the
+        kernel's own action table, so the playouts run on a one-env batched env whose table is the limited one (limit_actions_vec, kept
+        from call to call) holding a copy of the current state; they equal what limit_actions_vec() of a batched env gives for that
+        state.  weights: one per limited id."""
+        limited, ids = self._limited_env()
+        if weights is not None and not hasattr(weights, 'device'):
+            w = np.asarray(weights)
+            if w.shape != (len(ids),):
+                raise ValueError("weights: one weight per limited action expected, shape [%d], got %s" % (len(ids), list(w.shape)))
+            weights = w[ids]                                 # (the kernel's action i is this wrapper's ids[i])
+        elif weights is not None and ids != list(range(len(ids))):
+            import torch
+            weights = weights[torch.tensor(ids, device=weights.device)].contiguous()
+        play = limited.playouts(n_playouts, steps, seed, device=device, weights=weights).row(0)
+        if ids == list(range(len(ids))):
             return play
         if device:                                           # (a table of its own, set_limited_actions_id: the kernel's id i is this wrapper's ids[i])
             import torch

@@ -47,6 +47,7 @@ extern "C" {
 #define NGW_F_PLACEMENT 2u
 #define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout / ngw_snapshot_playout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros); ngw_state_keys: a row index outside its range (that key is 0) */
 #define NGW_F_TABLE_FULL 8u     /* ngw_key_table_insert: a key found neither itself nor a free bucket after probing every bucket (it was refused: where = -1, fresh = 0) */
+#define NGW_F_BAD_WEIGHT 16u    /* ngw_sample_actions / ngw_snapshot_playout_weighted: a weight that is negative, NaN or above 2^64 (it counted as 0) */
 
 /* action kinds (act_kind[]); act_arg[] = recipe index (CRAFT) or item id (SELECT) */
 enum { NGW_ACT_FORWARD = 0, NGW_ACT_LEFT = 1, NGW_ACT_RIGHT = 2, NGW_ACT_BREAK = 3, NGW_ACT_PLACE = 4,
@@ -691,6 +692,50 @@ int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, i
 int ngw_snapshot_playout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
                          ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev,
                          int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride);
+
+/* Weighted choice among valid actions: "for each state, pick an action with probability proportional to my weight, among the actions the state
+ * accepts" - invalid-action masking as a policy-gradient loop, a policy-guided tree search and a biased ("heavy") playout need it, in one
+ * launch.  The choice is a public contract, like the playout rule above, in integers and IEEE binary32, so a host reproduces it bit for bit.
+ * For pair j of a call - global pair number p = first_pair + j, a uint64 - at step number t, with the caller's float32 weights x[a]:
+ *   1. m  = the valid-action mask word of the pair's state (the predicate of ngw_action_mask, every novelty and wrapper predicate included);
+ *           if m == 0: m = all n_actions bits.  This is the playout rule's m.
+ *   2. w  = word (t & 3) of Philox4x32-10 with counter (t >> 2, 0, lo32(p), hi32(p)) and key (lo32(seed), hi32(seed) ^ NGW_SAMPLE_TAG).
+ *   3. the cleaned weight v[a], a < n_actions: x[a] if bit a of m is set and 2^-64 <= x[a] <= 2^64, else +0.  A weight that is negative, NaN or
+ *      above 2^64 (infinity included) raises the sticky NGW_F_BAD_WEIGHT, whether or not action a is valid; a weight in [0, 2^-64) is silently 0
+ *      (an underflowed softmax is legitimate; -0.0 compares equal to 0 and is such a weight).
+ *   4. c[-1] = 0, c[a] = c[a-1] + v[a] in binary32, round-to-nearest-even, in action order, every add a plain add (never fused with a
+ *      multiply);  mass = c[n_actions - 1].
+ *   5. mass > 0:  u = float(w >> 8) * 2^-24 (exact, in [0, 1));  thr = u * mass (one binary32 multiply);  the action is the smallest a with
+ *      v[a] > 0 and c[a] > thr.  The bounds of rule 3 keep every intermediate normal and finite for up to 48 actions, so no flush-to-zero or
+ *      overflow question arises; thr < mass always holds - should no a qualify, the action is the last a with v[a] > 0.
+ *   6. mass == 0: the playout rule on this w:  k = ((uint64)w * popcount(m)) >> 32, the (k + 1)-th set bit of m; mass is reported as 0.
+ * The draw depends on (seed, p, t), the state and the weights only: not on the slot, the env index, the rank or the wavefront.  mass is returned
+ * so that the caller forms log pi(a) = log x[a] - log mass itself: the kernel divides nothing and calls no transcendental function.
+ *
+ * ngw_sample_actions: src == NULL: the envs' current states, else a snapshot's slots; idx_dev: int32 row indices in device memory (NULL =
+ * 0 .. count-1; indices may repeat, count is not bound by the row count with a list).  weights_dev: float32 in device memory, action-major:
+ * x[a] of pair j at [a * weight_stride + j], weight_stride >= count.  actions_dev[j] (int32) = the action, mass_dev[j] (float32, may be NULL) =
+ * mass, masks_dev[j] (uint64, may be NULL) = m as rule 1 defines it - the word a learner stores to recompute masked log-probabilities.
+ * A row index out of range is never used as an address: that pair gets action -1, mass 0 and mask 0, and the sticky NGW_F_BAD_INDEX is raised
+ * (its weights are still checked for NGW_F_BAD_WEIGHT).  One kernel launch (ngw_sample.inc) on the handle's stream; does not wait.  A
+ * captured graph stays valid.  count == 0 is a no-op.  Map cells are read in place: every map size the handle supports.  Nothing is committed:
+ * no env state, no step output, no mask buffer or its currency, no lookahead table, no lidar row, no prepared episode and no slot changes -
+ * ngw_snapshot_action_mask's list word for word.  A one-env handle's resident step loop is ended first.
+ * NGW_E_INVALID_ARG: a NULL handle, weights_dev or actions_dev; count < 0; weight_stride < count; a src that is not an open snapshot of this
+ * handle; idx_dev == NULL with count above the source's row count. */
+#define NGW_SAMPLE_TAG 0x53414D50u
+int ngw_sample_actions(ngw_handle* h, ngw_snapshot* src, const int32_t* idx_dev, int64_t count, const float* weights_dev, int64_t weight_stride,
+                       uint64_t seed, uint64_t first_pair, uint32_t t, int32_t* actions_dev, float* mass_dev, uint64_t* masks_dev);
+
+/* ngw_snapshot_playout with a weighted policy: weights_dev = n_actions float32 in device memory, one per action, the same for every pair and
+ * step.  Every step's choice is rules 3 - 6 above applied to the playout's own m and its own w (NGW_PLAYOUT_TAG and the playout's counter, both
+ * unchanged): proportional to the weights among the valid actions, the uniform rule where their mass is 0.  A bad weight raises
+ * NGW_F_BAD_WEIGHT.  Everything else - arguments, reports, errors, the map-size limit - is ngw_snapshot_playout's; weights_dev == NULL is
+ * that call. */
+int ngw_snapshot_playout_weighted(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed,
+                                  uint64_t first_pair, const float* weights_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev,
+                                  int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev,
+                                  int64_t actions_stride);
 
 /* Key table: an open-addressing hash set of 64-bit keys in device memory - "have I seen this state BEFORE?" across the calls of a search that
  * runs many iterations (transposition tables, duplicate removal in breadth-first solvers, Go-Explore archives, count-based bonuses).  A table
