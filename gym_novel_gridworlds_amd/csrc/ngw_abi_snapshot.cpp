@@ -9,6 +9,7 @@
 // The state keys (ngw_keys.inc) hash rows of a snapshot or of the state slab into the caller's buffer: they commit nothing either.
 // The successor keys (ngw_successors.inc) are the keys of every action's child of such rows, with no child stored: they commit nothing either.
 // A playout (ngw_playout.inc) is a rollout whose actions the kernel draws among the valid ones of each step: it commits nothing either.
+// The path forms of both (ngw_path.inc) add per-pair step limits and the key of every visited state: they commit nothing either.
 // The weighted choice (ngw_sample.inc) draws one action per row by the caller's weights among the valid ones: it commits nothing either.
 #include "ngw_host.h"
 
@@ -87,6 +88,88 @@ NgwLaunch step_block(const ngw_handle* h) {
     a.autoreset = h->autoreset;
     a.horizon = h->horizon;
     return a;
+}
+
+// what the path forms ask for beyond a plain rollout / playout; nullptr = the plain call
+struct PathArgs {
+    const int32_t* limits;
+    uint32_t fields;
+    uint64_t* keys;
+    int64_t keys_stride;
+};
+
+// the path arguments of one call, checked (before anything touches the stream) -> the LDS bytes of the launch
+int path_args(const ngw_handle* h, const PathArgs& pa, int64_t count, const char* what, const char* call, size_t* lds) {
+    if (pa.keys && (!pa.fields || (pa.fields & ~NGW_KEY_ALL)))
+        return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)pa.fields);
+    if (pa.keys && pa.keys_stride < count) return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a key stride of %lld", what, (long long)count, (long long)pa.keys_stride);
+    *lds = NGW_PATH_LDS_BYTES(h->lds_bytes, h->proto.KP);
+    if (*lds > NGW_PATH_LDS_MAX)
+        return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps and a second copy of their inventories in LDS (%s) and they need "
+                                       "%zu B, more than 160 KiB; the plain call is available", h->proto.S, call, *lds);
+    return NGW_OK;
+}
+
+// a rollout, plain (pa == nullptr: the kernel as it always was) or in its path form
+int rollout_call(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps, ngw_snapshot* dst,
+                 const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, const PathArgs* pa) {
+    if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "rollout of %d steps", (int)n_steps);
+    if (count < 0 || pair_stride < count)
+        return fail(NGW_E_INVALID_ARG, "rollout of %lld pairs with a pair stride of %lld", (long long)count, (long long)pair_stride);
+    if (!dst && !ret_dev && !length_dev && !ended_dev && !info_dev && !(pa && pa->keys))
+        return fail(NGW_E_INVALID_ARG, "rollout without a destination and without a report: nothing to do");
+    int64_t src_rows;
+    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "rollout", pa ? "ngw_snapshot_rollout_path" : "ngw_snapshot_rollout", &src_rows)) return rc;
+    size_t lds = h->lds_bytes;
+    if (pa)
+        if (int rc = path_args(h, *pa, count, "rollout", "ngw_snapshot_rollout_path", &lds)) return rc;
+    if (int rc = enter(h)) return rc;
+    if (count == 0) return NGW_OK;
+    const NgwLaunch a = step_block(h);
+    NgwSlotRollout x{};
+    x.src = src ? src->r : state_rows(h);
+    if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
+    x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = pair_stride; x.n_steps = n_steps;
+    x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev;
+    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
+    if (pa) {
+        x.limits = pa->limits; x.keys = pa->keys; x.keys_stride = pa->keys_stride; x.fields = pa->fields; x.off_shadow = (uint32_t)(h->lds_bytes / 4);
+        HIP_TRY(ngw_slot_rollout_path_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
+    } else
+        HIP_TRY(ngw_slot_rollout_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
+    return NGW_OK;
+}
+
+// a playout, likewise
+int playout_call(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                 const float* weights_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev,
+                 uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride, const PathArgs* pa) {
+    if (!h) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "playout of %d steps", (int)n_steps);
+    if (count < 0 || (actions_dev && actions_stride < count))
+        return fail(NGW_E_INVALID_ARG, "playout of %lld pairs with an action stride of %lld", (long long)count, (long long)actions_stride);
+    int64_t src_rows;
+    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "playout", pa ? "ngw_snapshot_playout_path" : "ngw_snapshot_playout", &src_rows)) return rc;
+    size_t lds = h->lds_bytes;
+    if (pa)
+        if (int rc = path_args(h, *pa, count, "playout", "ngw_snapshot_playout_path", &lds)) return rc;
+    if (int rc = enter(h)) return rc;
+    if (count == 0) return NGW_OK;
+    const NgwLaunch a = step_block(h);
+    NgwPlayout x{};
+    x.src = src ? src->r : state_rows(h);
+    if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
+    x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = actions_stride; x.n_steps = n_steps;
+    x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev; x.first_action = first_action_dev;
+    x.seed = seed; x.first_pair = first_pair; x.weights = weights_dev;
+    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
+    if (pa) {
+        x.limits = pa->limits; x.keys = pa->keys; x.keys_stride = pa->keys_stride; x.fields = pa->fields; x.off_shadow = (uint32_t)(h->lds_bytes / 4);
+        HIP_TRY(ngw_playout_path_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
+    } else
+        HIP_TRY(ngw_playout_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
+    return NGW_OK;
 }
 
 }  // namespace
@@ -202,48 +285,31 @@ int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx
 int ngw_snapshot_rollout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
                          ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev,
                          uint32_t* info_dev) {
-    if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "rollout of %d steps", (int)n_steps);
-    if (count < 0 || pair_stride < count)
-        return fail(NGW_E_INVALID_ARG, "rollout of %lld pairs with a pair stride of %lld", (long long)count, (long long)pair_stride);
-    if (!dst && !ret_dev && !length_dev && !ended_dev && !info_dev) return fail(NGW_E_INVALID_ARG, "rollout without a destination and without a report: nothing to do");
-    int64_t src_rows;
-    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "rollout", "ngw_snapshot_rollout", &src_rows)) return rc;
-    if (int rc = enter(h)) return rc;
-    if (count == 0) return NGW_OK;
-    const NgwLaunch a = step_block(h);
-    NgwSlotRollout x{};
-    x.src = src ? src->r : state_rows(h);
-    if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
-    x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = pair_stride; x.n_steps = n_steps;
-    x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev;
-    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
-    HIP_TRY(ngw_slot_rollout_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
-    return NGW_OK;
+    return rollout_call(h, src, src_idx_dev, actions_dev, pair_stride, n_steps, dst, dst_slots_dev, count, ret_dev, length_dev, ended_dev, info_dev, nullptr);
+}
+
+int ngw_snapshot_rollout_path(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
+                              const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev,
+                              uint8_t* ended_dev, uint32_t* info_dev, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride) {
+    const PathArgs pa{limits_dev, fields, keys_dev, keys_stride};
+    return rollout_call(h, src, src_idx_dev, actions_dev, pair_stride, n_steps, dst, dst_slots_dev, count, ret_dev, length_dev, ended_dev, info_dev, &pa);
 }
 
 int ngw_snapshot_playout_weighted(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed,
                                   uint64_t first_pair, const float* weights_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev,
                                   int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev,
                                   int64_t actions_stride) {
-    if (!h) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "playout of %d steps", (int)n_steps);
-    if (count < 0 || (actions_dev && actions_stride < count))
-        return fail(NGW_E_INVALID_ARG, "playout of %lld pairs with an action stride of %lld", (long long)count, (long long)actions_stride);
-    int64_t src_rows;
-    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "playout", "ngw_snapshot_playout", &src_rows)) return rc;
-    if (int rc = enter(h)) return rc;
-    if (count == 0) return NGW_OK;
-    const NgwLaunch a = step_block(h);
-    NgwPlayout x{};
-    x.src = src ? src->r : state_rows(h);
-    if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
-    x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = actions_stride; x.n_steps = n_steps;
-    x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev; x.first_action = first_action_dev;
-    x.seed = seed; x.first_pair = first_pair; x.weights = weights_dev;
-    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
-    HIP_TRY(ngw_playout_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
-    return NGW_OK;
+    return playout_call(h, src, src_idx_dev, count, n_steps, seed, first_pair, weights_dev, dst, dst_slots_dev, ret_dev, length_dev, ended_dev, info_dev,
+                        first_action_dev, actions_dev, actions_stride, nullptr);
+}
+
+int ngw_snapshot_playout_path(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                              const float* weights_dev, const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev,
+                              int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride,
+                              uint32_t fields, uint64_t* keys_dev, int64_t keys_stride) {
+    const PathArgs pa{limits_dev, fields, keys_dev, keys_stride};
+    return playout_call(h, src, src_idx_dev, count, n_steps, seed, first_pair, weights_dev, dst, dst_slots_dev, ret_dev, length_dev, ended_dev, info_dev,
+                        first_action_dev, actions_dev, actions_stride, &pa);
 }
 
 int ngw_snapshot_playout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,

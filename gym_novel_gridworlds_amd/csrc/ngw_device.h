@@ -510,11 +510,25 @@ struct NgwSlotRollout {
     uint32_t* info;
     int32_t count, src_rows, dst_rows;
     int32_t n_steps, keep;
+    /* the path form (ngw_path.inc; last: the fields before them keep their offsets).  limits: nullptr, or [count] int32, pair j executes at most
+     * min(n_steps, max(limits[j], 0)) steps.  keys: nullptr, or the key under `fields` of the state after step t to keys[t * keys_stride + j]
+     * (0 for a step the pair did not execute); off_shadow: the dword offset in LDS of the 64 * KP inventory shadows. */
+    const int32_t* limits;
+    uint64_t* keys;
+    int64_t keys_stride;
+    uint32_t fields, off_shadow;
 };
+#define NGW_PATH_LDS_MAX ((size_t)160 * 1024)                                                                   /* what a CU of gfx950 has */
+#define NGW_PATH_LDS_BYTES(lds_bytes, KP) ((size_t)(lds_bytes) + (size_t)NGW_EPB * 4u * (size_t)(KP))   /* the handle's layout and the inventory shadows behind it */
 #ifdef __cplusplus
 extern "C"
 #endif
 hipError_t ngw_slot_rollout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+/* the path form: x->limits / x->keys are read, lds_bytes = NGW_PATH_LDS_BYTES(the handle's, a->KP) with x->off_shadow = the handle's in dwords */
+hipError_t ngw_slot_rollout_path_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream);
 
 /* Snapshot playout (ngw_playout.inc, ngw_abi_snapshot.cpp): NgwSlotRollout's pairs, index rules, stop rule and destination, with the actions drawn in
  * the kernel by the choice rule of include/ngw.h (ngw_snapshot_playout): pair j is pair number first_pair + j of the stream of `seed`.  The drawn
@@ -535,11 +549,23 @@ struct NgwPlayout {
     int32_t count, src_rows, dst_rows;
     int32_t n_steps, keep;
     const float* weights; /* nullptr: the uniform rule; else [n_actions] float32, the weighted rule of ngw_sample_actions at every step (last: the fields before it keep their offsets) */
+    /* the path form (ngw_path.inc, as in NgwSlotRollout; last: the fields before them keep their offsets).  limits: nullptr, or [count] int32, pair j executes at most
+     * min(n_steps, max(limits[j], 0)) steps.  keys: nullptr, or the key under `fields` of the state after step t to keys[t * keys_stride + j]
+     * (0 for a step the pair did not execute); off_shadow: the dword offset in LDS of the 64 * KP inventory shadows. */
+    const int32_t* limits;
+    uint64_t* keys;
+    int64_t keys_stride;
+    uint32_t fields, off_shadow;
 };
 #ifdef __cplusplus
 extern "C"
 #endif
 hipError_t ngw_playout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+/* the path form, as ngw_slot_rollout_path_launch */
+hipError_t ngw_playout_path_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream);
 
 /* Slot observations (ngw_slot_observe.inc, ngw_abi_snapshot.cpp): observations and action masks of SAVED states, gathered by slot index. Output
  * row j of a call describes row slots[j] of `src` (a snapshot; a NULL list = j itself).  An index outside [0, rows) is never used as an address:

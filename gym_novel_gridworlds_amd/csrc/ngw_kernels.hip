@@ -30,7 +30,7 @@
 #include "../../include/ngw.h"
 #include "ngw_device.h"
 
-// The library is built from this file TWENTY-TWO times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
+// The library is built from this file TWENTY-FOUR times, in parallel (Makefile): -DNGW_PART=n keeps the launchers - and with them the
 // kernel instantiations - of one part; without NGW_PART (make asm) everything is in one unit.
 //   0: ngw_launch + the general kernel   1 / 6 / 7: step kernels per map addressing mode (1 also holds the in-place ones)
 //   2 / 3 / 4: rollout kernels per map addressing mode   5: new-episode (reset_fast), lidar, diff / wire / pack / agent-view kernels
@@ -44,6 +44,7 @@
 //   19: successor keys (ngw_successors.inc: the key of every action's child; it shares ngw_expand.inc's row mover and ngw_keys.inc's terms)
 //   20: snapshot playout (ngw_playout.inc: valid-action random playouts from saved rows; it shares ngw_expand.inc's row mover and ngw_mask.inc's walk)
 //   21: the weighted choice among valid actions (ngw_sample.inc: one action per state by caller-supplied weights; its selection function is part 20's too)
+//   22 / 23: the path forms of the snapshot rollout / the snapshot playout (ngw_path.inc: the key of every visited state, per-pair step limits)
 #ifdef NGW_PART
 #define NGW_HAS(p) (NGW_PART == (p))
 #else
@@ -395,23 +396,26 @@ __device__ __forceinline__ void stgs16(void* base, uint32_t off, u32x4 v) {
 #if NGW_HAS(13)
 #include "ngw_plans.inc"
 #endif
-#if NGW_HAS(14) || NGW_HAS(15) || NGW_HAS(16) || NGW_HAS(19) || NGW_HAS(20)
+#if NGW_HAS(14) || NGW_HAS(15) || NGW_HAS(16) || NGW_HAS(19) || NGW_HAS(20) || NGW_HAS(22) || NGW_HAS(23)
 #include "ngw_expand.inc"
 #endif
-#if NGW_HAS(15)
+#if NGW_HAS(15) || NGW_HAS(17) || NGW_HAS(19) || NGW_HAS(20) || NGW_HAS(22) || NGW_HAS(23)
+#include "ngw_keys.inc"
+#endif
+#if NGW_HAS(15) || NGW_HAS(20) || NGW_HAS(22) || NGW_HAS(23)
+#include "ngw_path.inc"
+#endif
+#if NGW_HAS(15) || NGW_HAS(22)
 #include "ngw_slot_rollout.inc"
 #endif
-#if NGW_HAS(20) || NGW_HAS(21)
+#if NGW_HAS(20) || NGW_HAS(21) || NGW_HAS(23)
 #include "ngw_sample.inc"
 #endif
-#if NGW_HAS(20)
+#if NGW_HAS(20) || NGW_HAS(23)
 #include "ngw_playout.inc"
 #endif
 #if NGW_HAS(16)
 #include "ngw_slot_observe.inc"
-#endif
-#if NGW_HAS(17) || NGW_HAS(19)
-#include "ngw_keys.inc"
 #endif
 #if NGW_HAS(19)
 #include "ngw_successors.inc"
@@ -896,6 +900,47 @@ extern "C" hipError_t ngw_playout_launch(const NgwDevSpec* dspec, const NgwLaunc
     });
 }
 #endif  // NGW_HAS(20)
+
+#if NGW_HAS(22) || NGW_HAS(23)
+// what the two path launches check beyond the plain ones: a field selection where keys are asked for, a stride that holds the pairs, the shadows inside LDS
+static bool path_args_ok(const NgwLaunch* a, int64_t count, const uint64_t* keys, int64_t keys_stride, uint32_t fields, uint32_t off_shadow, size_t lds_bytes) {
+    return (!keys || (fields && !(fields & ~NGW_KEY_ALL) && keys_stride >= count)) && a->KP >= a->K &&
+           ((size_t)off_shadow + (size_t)NGW_EPB * (size_t)a->KP) * 4u <= lds_bytes && lds_bytes <= NGW_PATH_LDS_MAX;
+}
+#endif
+#if NGW_HAS(22)
+// the path form of the snapshot rollout (ngw_slot_rollout.inc, PATH): lds_bytes = NGW_PATH_LDS_BYTES(the handle's, KP)
+extern "C" hipError_t ngw_slot_rollout_path_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream) {
+    if (x->count <= 0 || x->n_steps < 1 || x->stride < x->count || x->src_rows < 1 || a->S < 3 || a->S > NGW_MAX_MAP_SIZE || a->K < 1 || a->K > NGW_MAX_ITEMS ||
+        a->MS < a->S2 || (a->MS & 3) || !a->b.flags || !x->actions || !x->src.map || (x->keep && (!x->dst.map || x->dst_rows < 1)) || (!x->keep && x->di) ||
+        !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((int64_t)x->count + NGW_EPB - 1) / NGW_EPB)), block(NGW_EPB);
+    return with_row_piece(a->S2, [&](auto V) {
+        return with_flag(ext != 0, [&](auto E) {
+            return launch_kernel<ngw_slot_rollout_kernel<decltype(V)::value, decltype(E)::value, true>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+        });
+    });
+}
+#endif  // NGW_HAS(22)
+
+#if NGW_HAS(23)
+// the path form of the snapshot playout (ngw_playout.inc, PATH)
+extern "C" hipError_t ngw_playout_path_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream) {
+    if (x->count <= 0 || x->n_steps < 1 || (x->actions && x->stride < x->count) || x->src_rows < 1 || a->S < 3 || a->S > NGW_MAX_MAP_SIZE || a->K < 1 ||
+        a->K > NGW_MAX_ITEMS || a->MS < a->S2 || (a->MS & 3) || !a->b.flags || !x->src.map || (x->keep && (!x->dst.map || x->dst_rows < 1)) || (!x->keep && x->di) ||
+        !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)(((int64_t)x->count + NGW_EPB - 1) / NGW_EPB)), block(NGW_EPB);
+    return with_row_piece(a->S2, [&](auto V) {
+        return with_flag(ext != 0, [&](auto E) {
+            return with_flag(x->weights != nullptr, [&](auto W) {
+                return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, decltype(W)::value, true>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+            });
+        });
+    });
+}
+#endif  // NGW_HAS(23)
 
 #if NGW_HAS(21)
 // the weighted choice (ngw_sample.inc): x->count pairs of rows of x->src through the index list; one wave per 64 pairs, no dynamic LDS

@@ -25,9 +25,13 @@
 // every step is sample_choice (ngw_sample.inc) on the step's own m and w - the weighted rule of ngw_sample_actions, the uniform rule where
 // the valid actions' mass is 0.  WEIGHTED = false is the kernel as it was.
 //
+// PATH (ngw_snapshot_playout_path): x.limits and x.keys as in ngw_slot_rollout_kernel<.., PATH = true> - the limit folds into `alive` before the
+// choice, so a limited playout is the prefix of the unlimited one and the actions beyond the limit are recorded as -1.  PATH = false is the
+// kernel as it was.
+//
 // x.actions (may be nullptr): int32, the action of pair j at step t to [t * x.stride + j] (stride >= count) - the layout ngw_slot_rollout_kernel reads.
 
-template <int VEC, bool EXT, bool WEIGHTED>
+template <int VEC, bool EXT, bool WEIGHTED, bool PATH = false>
 __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* __restrict__ dspec, const NgwLaunch a, const NgwPlayout x) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t tid = threadIdx.x;
@@ -92,8 +96,15 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
     bool alive = ok;
     int ret = 0, len = 0, ended = 0, first = -1;
     uint32_t info = 0;
+    PathLane<PATH> pa;
+    if constexpr (PATH) {
+        pa.limit = x.limits && ok ? min(max(x.limits[pair], 0), n_steps) : n_steps;
+        pa.kout = x.keys && inside ? x.keys + pair : nullptr;
+        if (x.keys) pa.pk = path_begin(lds_map + tid * MSdw, inv, lds + x.off_shadow + tid * KP, S2, K, x.fields, episode);
+    }
     int s = 0;
     for (; s < n_steps; s++) {
+        if constexpr (PATH) alive = alive && s < pa.limit;
         if ((s & 3) == 0) philox_block((uint32_t)s >> 2, 0u, (uint32_t)p, (uint32_t)(p >> 32), key0, key1, w0, w1, w2, w3);   // (uniform: s is a scalar)
         // the choice: uniform over the actions that would succeed from here; every action where none would
         uint64_t m = lean_mask_walk<EXT>(t, UV, X, A, Sv, Kv, r, c, f, sel, inv, cell_at);
@@ -116,16 +127,26 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
         const uint32_t e0 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t0), e1 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t1);
         const uint32_t e2 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t2), e3 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t3);
         const uint32_t e4 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t4), e5 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t5);
+        if constexpr (PATH)
+            if (x.keys) pa.grp = path_front_group(pa.pk, Sv, r, c, f, pa.before);
         const LeanOut o = lean_body<true, false, EXT>(UV, X, e0, e1, e2, e3, e4, e5, alive, alive, Sv, Kv, mp, inv, nullptr, nullptr, 0u, 0u, r, c, f, sel, steps,
                                                       autoreset, horizon);
         r = o.r; c = o.c; f = o.f; sel = o.sel; steps = o.steps;                   // (a no-op entry hands them back unchanged: an ended pair stays frozen)
         flags |= o.flags;
+        if constexpr (PATH)
+            if (x.keys) {                                                          // (wave-uniform; every lane walks it: path_after_step votes)
+                const uint64_t key = path_after_step(pa.pk, o, pa.grp, pa.before, inv, Kv, x.fields);
+                if (pa.kout) pa.kout[(int64_t)s * x.keys_stride] = alive ? key : 0ull;
+            }
         if (alive) {
             ret += o.reward; len += 1; info = o.info;
             if (o.ended) { ended = 1; alive = false; }                             // the ending step counts; no reset runs, the pair is over
         }
         if (!__any(alive)) { s++; break; }
     }
+    if constexpr (PATH)
+        if (pa.kout)
+            for (int u = s; u < n_steps; u++) pa.kout[(int64_t)u * x.keys_stride] = 0ull;
     if (rec && inside)
         for (; s < n_steps; s++) rec[(int64_t)s * tstride] = -1;                   // the steps no pair of this wave executed
     __syncthreads();

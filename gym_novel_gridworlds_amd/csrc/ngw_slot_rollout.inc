@@ -25,8 +25,12 @@
 // Source and destination may be the same allocation, so neither is __restrict__ against the other; within a wave every load of a parent
 // row is done before the first store of an end state (the barriers), across waves the call's contract keeps them apart.
 //
+// PATH (ngw_snapshot_rollout_path): x.limits cuts pair j after min(n_steps, max(limits[j], 0)) steps - the limit folds into `alive` before the
+// plan read is used, a cut pair is not `ended` -, and x.keys takes the key of the state after every executed step (ngw_path.inc), 0 for the
+// others, 64 lanes on consecutive addresses.  PATH = false is the kernel as it was.
+//
 // x.actions: int32, the action of pair j at step t at [t * x.stride + j] (stride >= count): 64 lanes read consecutive addresses.
-template <int VEC, bool EXT>
+template <int VEC, bool EXT, bool PATH = false>
 __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevSpec* __restrict__ dspec, const NgwLaunch a, const NgwSlotRollout x) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t tid = threadIdx.x;
@@ -81,7 +85,15 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
     bool alive = ok;
     int ret = 0, len = 0, ended = 0;
     uint32_t info = 0;
+    PathLane<PATH> pa;
+    if constexpr (PATH) {
+        pa.limit = x.limits && ok ? min(max(x.limits[pair], 0), n_steps) : n_steps;
+        pa.kout = x.keys && inside ? x.keys + pair : nullptr;
+        pa.kdone = 0;
+        if (x.keys) pa.pk = path_begin(lds_map + tid * MSdw, inv, lds + x.off_shadow + tid * KP, S2, K, x.fields, episode);
+    }
     for (int s = 0; s < n_steps; s++) {
+        if constexpr (PATH) alive = alive && s < pa.limit;
         const int action = act_next;
         if (s + 1 < n_steps && inside) act_next = pl[(int64_t)(s + 1) * tstride];  // the next step's row is requested one step ahead
         const bool valid = alive && (uint32_t)action < (uint32_t)n_actions;
@@ -89,17 +101,28 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
         const uint32_t e0 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t0), e1 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t1);
         const uint32_t e2 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t2), e3 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t3);
         const uint32_t e4 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t4), e5 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t5);
+        if constexpr (PATH)
+            if (x.keys) pa.grp = path_front_group(pa.pk, Sv, r, c, f, pa.before);
         // `alive` in the place of `live`: an id outside the action list raises NGW_F_INVALID_ACTION only while the pair still runs
         const LeanOut o = lean_body<true, false, EXT>(UV, X, e0, e1, e2, e3, e4, e5, alive, valid, Sv, Kv, mp, inv, nullptr, nullptr, 0u, 0u, r, c, f, sel, steps,
                                                       autoreset, horizon);
         r = o.r; c = o.c; f = o.f; sel = o.sel; steps = o.steps;                   // (a no-op entry hands them back unchanged: an ended pair stays frozen)
         flags |= o.flags;
+        if constexpr (PATH)
+            if (x.keys) {                                                          // (wave-uniform; every lane walks it: path_after_step votes)
+                const uint64_t key = path_after_step(pa.pk, o, pa.grp, pa.before, inv, Kv, x.fields);
+                if (pa.kout) pa.kout[(int64_t)s * x.keys_stride] = alive ? key : 0ull;
+                pa.kdone = s + 1;
+            }
         if (alive) {                                                               // (an invalid id: reward 0, info 0, not an end - lean_epilogue)
             ret += o.reward; len += 1; info = o.info;
             if (o.ended) { ended = 1; alive = false; }                             // the ending step counts; no reset runs, the pair is over
         }
         if (!__any(alive)) break;
     }
+    if constexpr (PATH)
+        if (pa.kout)
+            for (int s = pa.kdone; s < n_steps; s++) pa.kout[(int64_t)s * x.keys_stride] = 0ull;   // the steps no pair of this wave executed
     __syncthreads();
     // ---- 3. the end states to their slots with the scalars (where they are kept), the reports
     if (keep) {

@@ -333,13 +333,15 @@ class _NovelGridworldEnv(_EnvBase):
         s = vec.sample_actions(np.asarray(weights)[None], seed, t=t)
         return int(s.action[0]), float(s.mass[0]), int(s.mask_words[0])
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE):
         """P = n_playouts valid-action random playouts of up to `steps` steps from the current state, without taking a step: a Playout of
         'ret' int32, 'length' int32, 'ended' bool, 'info' uint32 and 'first_action' int32, each [P]; playout q is pair q of the stream of
-        `seed`; see VecNovelGridworld.playouts."""
+        `seed`; see VecNovelGridworld.playouts.  path_keys=True: a PlayoutPath, whose 'keys' [steps, P] hold the key under `fields` of the
+        state each playout is in after every executed step (0 for the others)."""
         vec = self._backend()
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
-        return vec.playouts(n_playouts, steps, seed, device=device, weights=weights).row(0)
+        path = dict(path_keys=True, fields=fields) if path_keys else {}
+        return vec.playouts(n_playouts, steps, seed, device=device, weights=weights, **path).row(0)
 
     def state_key(self, fields=KEY_STATE):
         """The 64-bit key of the current state as a Python int, computed on the device under the field selection `fields` (KEY_* bits,

@@ -53,8 +53,9 @@ class NoveltyWrapper(object):
     def evaluate_plans(self, plans, device=False, copy=False):
         return self.env.evaluate_plans(plans, device=device, copy=copy)
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None):
-        return self.env.playouts(n_playouts, steps, seed, device=device, weights=weights)
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE):
+        path = dict(path_keys=True, fields=fields) if path_keys else {}
+        return self.env.playouts(n_playouts, steps, seed, device=device, weights=weights, **path)
 
     def sample_action(self, weights, seed, t=0):
         return self.env.sample_action(weights, seed, t=t)

@@ -49,6 +49,29 @@ class Playout(collections.namedtuple('Playout', 'ret length ended info first_act
         return Playout(*[x[i] for x in self[:5]], None if a is None else a[:, i])
 
 
+class PlayoutPath(collections.namedtuple('PlayoutPath', 'ret length ended info first_action actions keys')):
+    """What playout(path_keys=True) / playouts(path_keys=True) return: Playout's fields and 'keys' [T, count] ([T, N, P]; [T, P]): entry
+    (t, j) the key (state_keys) of the state pair j is in after it has executed step t, 0 for a step it did not execute - numpy uint64, or a
+    torch int64 tensor over the same bits.  Flattened it is what KeyTable.insert takes, and snapshot.fresh_steps maps `fresh` back."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    goal = Playout.goal
+    died = Playout.died
+
+    def shaped(self, *shape):
+        """The per-pair fields reshaped to `shape`, the recorded actions and the keys to [T, *shape]."""
+        a, k = self.actions, self.keys
+        return PlayoutPath(*[x.reshape(*shape) for x in self[:5]], None if a is None else a.reshape(a.shape[0], *shape), k.reshape(k.shape[0], *shape))
+
+    def row(self, i):
+        """Env i's rows of an [N, P] result (the single-env adapter's view)."""
+        a = self.actions
+        return PlayoutPath(*[x[i] for x in self[:5]], None if a is None else a[:, i], self.keys[:, i])
+
+
 def philox4x32_10(counter, key):
     """Philox4x32-10 over arrays: counter = four uint32 arrays (broadcastable), key = two -> the four output words, uint32 arrays."""
     c0, c1, c2, c3 = [np.asarray(x, np.uint64) & _LO for x in np.broadcast_arrays(*counter)]

@@ -167,6 +167,26 @@ def check_playout(parents, steps, children, n_parents, capacity, same_buffer, de
     return p, c, count, int(steps)
 
 
+def check_limits(limits, count, steps, device_len=None):
+    """The host-side check of the per-pair step limits of a rollout / playout: None; a list / numpy array of `count` integers in [0, steps]
+    (ValueError otherwise) -> a contiguous int32 array; or - device_len(x) gives its length - a device int32 tensor of `count` elements, used
+    in place with its VALUES unchecked (the kernel clamps them to [0, steps])."""
+    if limits is None:
+        return None
+    n = None if device_len is None else device_len(limits)
+    if n is None:
+        a = np.asarray(limits)
+        if a.ndim != 1 or (a.size and (a.dtype == np.bool_ or not np.issubdtype(a.dtype, np.integer))):
+            raise ValueError("limits: a one-dimensional list of integers expected")
+        if a.size and (a.min() < 0 or a.max() > steps):
+            bad = a[(a < 0) | (a > steps)][0]
+            raise ValueError("limits: %d outside [0, %d]" % (int(bad), steps))
+        limits, n = np.ascontiguousarray(a, dtype=np.int32), int(a.size)
+    if n != count:
+        raise ValueError("limits: %d limits for %d pairs" % (n, count))
+    return limits
+
+
 def check_copy(src_slots, dst_slots, n_src, capacity, same_buffer, device_len=None):
     """The host-side checks of one slot-to-slot copy, as check_expand checks children: src_slots index rows [0, n_src) and may repeat,
     dst_slots index slots [0, capacity) and must be distinct, both have one length (None = no list: 0 .. count-1, which must exist; without
@@ -341,13 +361,46 @@ def fresh_pairs(fresh):
     return divmod(np.flatnonzero(np.asarray(fresh).reshape(-1)), A)
 
 
-def playout_call(env, holder, src, dst, parents, children, count, steps, seed, first_pair, record, device, weights=None):
+def fresh_steps(fresh):
+    """The (step t, pair j) of every True of a [T, count] `fresh` (the flattened path keys of a rollout / playout offered to
+    KeyTable.insert), in row-major order - position t * count + j maps back by divmod, so a fresh key names the EARLIEST step that reached
+    its state.  numpy arrays (int64), or torch tensors for a tensor.  limits = t + 1 replays pair j up to that state."""
+    n = int(fresh.shape[1])
+    if hasattr(fresh, 'data_ptr'):
+        import torch
+        pos = torch.nonzero(fresh.reshape(-1)).reshape(-1)
+        return torch.div(pos, n, rounding_mode='floor'), pos % n
+    return divmod(np.flatnonzero(np.asarray(fresh).reshape(-1)), n)
+
+
+def path_outputs(dev, limits, path_keys, fields, count, steps):
+    """What a path call adds to a plain one -> (the checked limits, the fields word, the keys tensor [steps, count] int64 or None)."""
+    import torch
+    lim = check_limits(limits, count, steps, lambda x: tensor_len(dev, 'limits', x))
+    if not path_keys:
+        return lim, 0, None
+    return lim, check_fields(KEY_STATE if fields is None else fields), torch.zeros((steps, count), dtype=torch.int64, device=dev)
+
+
+def path_call(env, holder, call, count, uploaded, device):
+    """enqueue_ordered for a path call: the library's map-size refusal is MapsTooLarge, as for successor_keys."""
+    try:
+        enqueue_ordered(env, holder, call, count, uploaded, device)
+    except ValueError as e:
+        if str(e).startswith('map_size'):
+            raise MapsTooLarge(str(e)) from None
+        raise
+
+
+def playout_call(env, holder, src, dst, parents, children, count, steps, seed, first_pair, record, device, weights=None, limits=None, path_keys=False,
+                 fields=None):
     """The one launch behind Snapshot.playout and VecNovelGridworld.playouts: src / dst are snapshots' C handles (src None: the envs' current
     states; dst None: nothing is kept), parents / children the checked lists (check_playout); `holder` keeps the uploaded lists alive.
     weights: None (the uniform rule), or one float32 per action from the host or the device (sample.check_weights).
-    -> Playout of [count] fields, actions [steps, count] with `record`."""
+    -> Playout of [count] fields, actions [steps, count] with `record`.  limits / path_keys / fields: the path form (Snapshot.playout);
+    with path_keys a PlayoutPath."""
     import torch
-    from .playout import Playout
+    from .playout import Playout, PlayoutPath
     seed, first_pair = int(seed), int(first_pair)
     if not 0 <= seed < 1 << 64:
         raise ValueError("seed: %d outside [0, 2^64)" % seed)
@@ -369,16 +422,29 @@ def playout_call(env, holder, src, dst, parents, children, count, steps, seed, f
     actions = torch.full((steps, count), -1, dtype=torch.int32, device=dev) if record else None
     out = [C.c_void_p(x.data_ptr()) for x in (ret, length, ended, info, first)]
     recorded = C.c_void_p(actions.data_ptr()) if record and count else None
-    if wt is None:                              # (the call as it always was)
+    keys = None
+    if limits is not None or path_keys:
+        lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
+        (lim_ptr,), up = upload(dev, count, lim)
+        uploaded = uploaded + up
+        call = lambda: _cabi.lib().ngw_snapshot_playout_path(   # noqa: E731
+            env._h, src, ptr[0], int(count), steps, seed, first_pair, None if wt is None else C.c_void_p(wt.data_ptr()), lim_ptr, dst, ptr[1], *out, recorded,
+            int(count), f, C.c_void_p(keys.data_ptr()) if keys is not None and count else None, int(count))
+    elif wt is None:                            # (the call as it always was)
         call = lambda: _cabi.lib().ngw_snapshot_playout(env._h, src, ptr[0], int(count), steps, seed, first_pair, dst, ptr[1], *out, recorded, int(count))   # noqa: E731
     else:
         call = lambda: _cabi.lib().ngw_snapshot_playout_weighted(env._h, src, ptr[0], int(count), steps, seed, first_pair, C.c_void_p(wt.data_ptr()), dst,   # noqa: E731
                                                                  ptr[1], *out, recorded, int(count))
-    enqueue_ordered(env, holder, call, count, uploaded, device)
+    if limits is not None or path_keys:
+        path_call(env, holder, call, count, uploaded, device)
+    else:
+        enqueue_ordered(env, holder, call, count, uploaded, device)
     if device:
-        return Playout(ret, length, ended.view(torch.bool), info, first, actions)
-    return Playout(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32), first.cpu().numpy(),
+        play = Playout(ret, length, ended.view(torch.bool), info, first, actions)
+        return play if keys is None else PlayoutPath(*play, keys)
+    play = Playout(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32), first.cpu().numpy(),
                    None if actions is None else actions.cpu().numpy())
+    return play if keys is None else PlayoutPath(*play, keys.cpu().numpy().view(np.uint64))
 
 
 class MapsTooLarge(_cabi.NgwError, ValueError):
@@ -538,7 +604,7 @@ class Snapshot:
         p, a, c, shape = all_actions_pairs(parents, first_child, self.env.n_actions)
         return self.expand(p, a, c, from_envs=from_envs, source=source, device=device).reshape(*shape)
 
-    def rollout(self, parents, plans, children=None, from_envs=False, source=None, device=False):
+    def rollout(self, parents, plans, children=None, from_envs=False, source=None, device=False, limits=None, path_keys=False, fields=KEY_STATE):
         """Pair j: the state of parent parents[j] stepped on a private copy with the T actions of plans[j], by the rules evaluate_plans()
         applies - every novelty, the env's autoreset setting and horizon; it stops at the first step that ends the episode (goal, FireWall
         death, the horizon under autoreset), that step counts, and no reset ever runs.  Returns a PlanEval of 'ret' int32 (sum of the
@@ -557,9 +623,16 @@ class Snapshot:
         reports stay 0).  Nothing is committed: no env, no mask, no lookahead table, no prepared episode and no slot but the children
         changes, and the number of pairs is not bound by num_envs.  One kernel launch.
         device=True: the results as torch tensors on the env's device ('info' int32), ordered behind the launch on torch's current stream -
-        no copy, no host wait; otherwise numpy arrays after one sync."""
+        no copy, no host wait; otherwise numpy arrays after one sync.
+        limits: None, or one step limit per pair - a list / numpy array of integers in [0, T] (checked here), or a torch int32 tensor on the
+        env's device used in place (clamped to [0, T]): pair j executes at most limits[j] steps.  A pair cut by its limit is not 'ended', its
+        'info' is its last executed step's; limit 0 reports zeros and leaves the child a copy of the parent.
+        path_keys=True: a RolloutPath, whose 'keys' [T, count] hold the key under `fields` (state_keys; what keys() returns for the child
+        the pair would leave had it stopped there) of the state after every executed step and 0 for the others - uint64, or an int64 tensor
+        with device=True.  Flattened it is what KeyTable.insert takes; fresh_steps() maps `fresh` back to (t, j), and a rollout of the same
+        plans with limits = t + 1 materialises that state.  Maps the path form cannot hold raise MapsTooLarge."""
         import torch
-        from .vec_env import PlanEval
+        from .vec_env import PlanEval, RolloutPath
         env = self.env
         src, n_parents, same_buffer = self._source(source, from_envs, 'rollout')
         dev = torch.device('cuda:%d' % env.device)
@@ -577,14 +650,26 @@ class Snapshot:
         length = torch.zeros(count, dtype=torch.int32, device=dev)
         ended = torch.zeros(count, dtype=torch.uint8, device=dev)
         info = torch.zeros(count, dtype=torch.int32, device=dev)
-        enqueue_ordered(env, self, lambda: _cabi.lib().ngw_snapshot_rollout(
-            env._h, src, ptr[0], ptr[1], int(count), steps, None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
-            C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr())), count, uploaded, device)
+        keys = None
+        if limits is None and not path_keys:    # (the call as it always was)
+            enqueue_ordered(env, self, lambda: _cabi.lib().ngw_snapshot_rollout(
+                env._h, src, ptr[0], ptr[1], int(count), steps, None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
+                C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr())), count, uploaded, device)
+        else:
+            lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
+            (lim_ptr,), up = upload(dev, count, lim)
+            path_call(env, self, lambda: _cabi.lib().ngw_snapshot_rollout_path(
+                env._h, src, ptr[0], ptr[1], int(count), steps, lim_ptr, None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
+                C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr()), f,
+                C.c_void_p(keys.data_ptr()) if keys is not None and count else None, int(count)), count, uploaded + up, device)
         if device:
-            return PlanEval(ret, length, ended.view(torch.bool), info)
-        return PlanEval(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32))
+            ev = PlanEval(ret, length, ended.view(torch.bool), info)
+            return ev if keys is None else RolloutPath(*ev, keys)
+        ev = PlanEval(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32))
+        return ev if keys is None else RolloutPath(*ev, keys.cpu().numpy().view(np.uint64))
 
-    def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False, weights=None):
+    def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False, weights=None,
+                limits=None, path_keys=False, fields=KEY_STATE):
         """Pair j: the state of parent parents[j] stepped on a private copy up to `steps` times by rollout()'s rules, with a random policy in
         the place of a plan: at every step the action is drawn uniformly among the actions that would succeed from the state the pair is in
         (every action where none would) - the default-policy simulation of a tree search's leaf, in one kernel launch.  The draw is the
@@ -600,13 +685,19 @@ class Snapshot:
         weights: None, or float32 [A] - a list / numpy array, or a torch tensor on the env's device used in place: a "heavy" playout.  Every
         step's action is then drawn with probability proportional to the weights among the valid actions (uniformly among them where none
         of them has a weight): rules 3 - 6 of ngw_sample_actions on the playout's own mask word and Philox word, which
-        sample.choose_weighted(..., words=playout.playout_words(...)) computes on the host.  A bad weight raises F_BAD_WEIGHT."""
+        sample.choose_weighted(..., words=playout.playout_words(...)) computes on the host.  A bad weight raises F_BAD_WEIGHT.
+        limits, path_keys, fields: as in rollout().  The draws depend on (seed, pair, step) and the state only, so a limited playout is the
+        prefix of the unlimited one, and the recorded actions beyond the limit are -1.  With path_keys=True a PlayoutPath: the Playout
+        fields and 'keys' [steps, count]."""
         import torch
         env = self.env
         src, n_parents, same_buffer = self._source(source, from_envs, 'playout')
         dev = torch.device('cuda:%d' % env.device)
         p, c, count, steps = check_playout(parents, steps, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'playout', x))
-        return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights)
+        if limits is None and not path_keys:    # (the call as it always was)
+            return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights)
+        return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights, limits=limits,
+                            path_keys=path_keys, fields=fields)
 
     # ------------------------------------------------------------------ slot observations (include/ngw.h ngw_snapshot_lidar / _agent_view / _action_mask)
     def _slots_arg(self, slots):

@@ -89,6 +89,19 @@ class PlanEval(collections.namedtuple('PlanEval', 'ret length ended info')):
         return PlanEval(*[x[i] for x in self])
 
 
+class RolloutPath(collections.namedtuple('RolloutPath', 'ret length ended info keys')):
+    """What Snapshot.rollout(path_keys=True) returns: PlanEval's 'ret', 'length', 'ended' and 'info', each [count], and 'keys' [T, count]:
+    entry (t, j) the key (state_keys) of the state pair j is in after it has executed step t, 0 for a step it did not execute - numpy
+    uint64, or a torch int64 tensor over the same bits.  A named tuple whose fields can also be read by name: r['keys']."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    goal = PlanEval.goal
+    died = PlanEval.died
+
+
 class StepInfo(dict):
     """info of a batched step: 'result' bool[N], 'step_cost_code', 'message_code', 'message_arg' - and 'step_cost' f64[N].  Fields
     that are not there yet are made when they are first asked for: 'step_cost' is looked up from the codes (a 65 536-element
@@ -1036,14 +1049,15 @@ class VecNovelGridworld:
         self.step_device(s.action.data_ptr())
         return s
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None):
         """P = n_playouts valid-action random playouts of up to `steps` steps from every env's CURRENT state, without taking a step and
         without a snapshot of the caller's: Snapshot.playout(from_envs=True) with the parents repeat(arange(N), P).  Returns a Playout whose
         fields are [N, P] ('actions' is None: Snapshot.playout records them).  Playout q of env i is pair (env_index_base + i) * P + q of the
         stream of `seed` (the contract of include/ngw.h; playout.choose_actions on the host), so the ranks of a sharded env return what one
         unsharded env returns.  One kernel launch; nothing is committed.  device=True: torch tensors on the env's device, ordered behind
         the launch on torch's current stream.  weights: float32 [A] (host or device) - every step's action is then drawn with probability
-        proportional to them among the valid ones (Snapshot.playout)."""
+        proportional to them among the valid ones (Snapshot.playout).  path_keys=True: a PlayoutPath whose 'keys' [T, N, P] hold the key
+        under `fields` (default KEY_STATE) of the state every playout is in after each executed step, 0 for the others (Snapshot.playout)."""
         import torch
         from .snapshot import check_playout, playout_call
         P = int(n_playouts)
@@ -1053,7 +1067,10 @@ class VecNovelGridworld:
         dev = torch.device('cuda:%d' % self.device)
         parents = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(P).contiguous()
         _, _, count, steps = check_playout(parents, steps, None, N, 0, False, lambda x: None if x is None else int(x.numel()))
-        return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights).shaped(N, P)
+        if not path_keys:                       # (the call as it always was)
+            return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights).shaped(N, P)
+        return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights,
+                            path_keys=True, fields=fields).shaped(N, P)
 
     def fork(self, src, keep_episode=False):
         """Every env e becomes a copy of env src[e] (src: num_envs indices - a list / numpy array, checked, or a torch int32 tensor on the

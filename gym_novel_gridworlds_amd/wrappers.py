@@ -174,12 +174,12 @@ class LimitActions(NoveltyWrapper):
         word = sum(1 << ids[i] for i in range(len(ids)) if (int(s.mask_words[0]) >> i) & 1)
         return ids[int(s.action[0])], float(s.mass[0]), word
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None):
         """The env's playouts under this wrapper's action list: at every step the action is drawn among the LIMITED actions that would
         succeed (every limited action where none would), and 'first_action' holds limited ids.  The draw needs the limited list as the
         kernel's own action table, so the playouts run on a one-env batched env whose table is the limited one (limit_actions_vec, kept
         from call to call) holding a copy of the current state; they equal what limit_actions_vec() of a batched env gives for that
-        state.  weights: one per limited id."""
+        state.  weights: one per limited id.  path_keys / fields: as on the env - the keys do not depend on the action id space."""
         limited, ids = self._limited_env()
         if weights is not None and not hasattr(weights, 'device'):
             w = np.asarray(weights)
@@ -189,7 +189,8 @@ class LimitActions(NoveltyWrapper):
         elif weights is not None and ids != list(range(len(ids))):
             import torch
             weights = weights[torch.tensor(ids, device=weights.device)].contiguous()
-        play = limited.playouts(n_playouts, steps, seed, device=device, weights=weights).row(0)
+        path = dict(path_keys=True, fields=fields) if path_keys else {}
+        play = limited.playouts(n_playouts, steps, seed, device=device, weights=weights, **path).row(0)
         if ids == list(range(len(ids))):
             return play
         if device:                                           # (a table of its own, set_limited_actions_id: the kernel's id i is this wrapper's ids[i])

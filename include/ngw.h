@@ -737,6 +737,43 @@ int ngw_snapshot_playout_weighted(ngw_handle* h, ngw_snapshot* src, const int32_
                                   int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev,
                                   int64_t actions_stride);
 
+/* Path keys and per-pair step limits: ngw_snapshot_rollout / ngw_snapshot_playout(_weighted) that also report the key of EVERY state a pair
+ * passes through, not only where it stops - what a Go-Explore archive (every new cell along an exploration run), a per-step visit count and
+ * loop detection inside a playout need, without stepping one step at a time.
+ * Path keys (keys_dev != NULL).  For pair j and step t in 0 .. n_steps-1:
+ *   keys_dev[t * keys_stride + j] (uint64, device memory, keys_stride >= count) = the key under `fields` (ngw_state_keys) of the state pair j is
+ *   in after it has executed step t: bit for bit what ngw_state_keys returns for the slot the same call would write into dst for pair j if the
+ *   pair stopped after step t.  The state after an ending step is the state the episode ended in, as ngw_snapshot_expand / ngw_snapshot_rollout
+ *   define a child: NGW_KEY_EPISODE uses the parent's episode counter, NGW_KEY_STEP_COUNT the step count after step t (FenceRestriction's
+ *   second count included); cells past S*S in the last map group count as 0, as everywhere.
+ *   The key is 0 for every step the pair did not execute: after its episode ended, beyond its limit, or for a pair skipped with
+ *   NGW_F_BAD_INDEX.  0 is the value the key table never stores, so the flattened [n_steps * keys_stride] array can be offered to
+ *   ngw_key_table_insert / _lookup as it is, and position t * count + j makes "fresh" mean "the earliest step that reached it".
+ *   Exactly [t * keys_stride, t * keys_stride + count) of every step row t < n_steps is written.
+ * Limits (limits_dev != NULL: int32 [count], device memory).  Pair j executes at most min(n_steps, max(limits_dev[j], 0)) steps; values
+ *   outside [0, n_steps] are clamped, no flag is raised.  A pair cut by its limit is NOT `ended`; its info is the word of its last executed
+ *   step.  A limit of 0 gives length = ret = info = 0 and, with a destination, an unchanged copy of the parent.  In a playout the draws depend
+ *   on (seed, p, t) and the state only, so a limited playout is the prefix of the unlimited one, and recorded actions beyond the limit are -1.
+ *   With limits[j] = t + 1, a replay of the recorded actions through ngw_snapshot_rollout_path leaves in dst exactly the state whose key is
+ *   keys[t * keys_stride + j].
+ * keys_dev may be NULL (limits only; fields is then ignored) and limits_dev may be NULL; with both NULL the calls compute what the plain calls
+ * compute.  A rollout with keys_dev needs neither a destination nor a report.  weights_dev == NULL is the uniform rule.  Everything else -
+ * arguments, reports, index rules, ordering, the stream, what is (not) committed: nothing - is the plain calls'.  One kernel launch
+ * (ngw_slot_rollout.inc / ngw_playout.inc in their PATH form, ngw_path.inc): the running key is updated for the dwords a step changes, no
+ * row leaves LDS.  Map sizes: the calls keep one set of a wavefront's 64 rows in LDS, as the plain calls do, and 64 * (K | 1) dwords of
+ * inventory shadows behind it; they serve every configuration whose two together fit 160 KiB - every configuration up to 32 x 32 and well
+ * beyond; a handle within those last 256 * (K | 1) bytes of the plain calls' own limit is refused here while the plain calls still run.
+ * NGW_E_INVALID_ARG: what the plain calls refuse; keys_dev with fields == 0 or a bit outside NGW_KEY_ALL; keys_dev with keys_stride < count;
+ * rows and shadows that do not fit LDS. */
+int ngw_snapshot_rollout_path(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
+                              const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev,
+                              uint8_t* ended_dev, uint32_t* info_dev, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride);
+int ngw_snapshot_playout_path(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                              const float* weights_dev /* NULL: the uniform rule */, const int32_t* limits_dev, ngw_snapshot* dst,
+                              const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev,
+                              int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride, uint32_t fields, uint64_t* keys_dev,
+                              int64_t keys_stride);
+
 /* Key table: an open-addressing hash set of 64-bit keys in device memory - "have I seen this state BEFORE?" across the calls of a search that
  * runs many iterations (transposition tables, duplicate removal in breadth-first solvers, Go-Explore archives, count-based bonuses).  A table
  * belongs to the handle that created it; it stores keys and nothing else: a caller keeps what it wants per state (visit counts, the best return,
