@@ -81,7 +81,7 @@ int layout_lds(ngw_handle* h) {
             p.off_ltab = off; if (!h->lidar_world) off += 4 * NGW_LIDAR_MAX_BEAMS * NGW_LIDAR_MAX_RANGE * 2 / 4;
             if (!alias) { p.off_ltile = off; off += tile_all; }
         }
-        // Philox word ring of the reset path (ngw_kernels.hip PHILOX_RING, 8 KB).  With the fused lidar epilogue it shares the
+        // Philox word ring of the reset path (ngw_newepisode.inc PHILOX_RING, 8 KB).  With the fused lidar epilogue it shares the
         // observation tile's region when that is big enough (the tile is rebuilt after any reset, the ring is dead by then): 8 KB
         // more would take an int32-row wave past 40 KB and a CU from four resident waves to three - measured as 13.6 -> 21.7 us per
         // batched step.  The ring is used when the reset has no shuffled-subset pass (those draw hundreds of words per lane:

@@ -1,5 +1,10 @@
-// ngw_boards.inc — the O(1) LidarInFront observation on occupancy bit rows (included by ngw_kernels.hip, inside its namespace,
-// before ngw_lean.inc: the in-place step kernel fuses lidar_boards_rows as its epilogue).
+// ngw_boards.inc — the O(1) LidarInFront observation on occupancy bit rows (the in-place step kernel of ngw_lean.inc
+// fuses lidar_boards_rows as its epilogue).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lidar_march.inc"     // the row formats and the observation tile
+
+namespace {
 //
 // The reference's default LidarInFront (observation_wrappers.py:10-80, num_beams = 8) shoots the four axes and the four true
 // diagonals: np.round(np.cos(pi / 4), 2) = 0.71 for BOTH coordinates and round(0.71 k) is the same number for the row and the
@@ -17,7 +22,7 @@
 //   * a ray's first block is one shift / mask and one find-first-bit on its line (the wall ring stops every ray);
 //   * ONE byte read per ray - the hit cell's item id, from the map row in HBM - names the channel.
 // 8 byte reads per env instead of 64 - 336, nothing staged, the in-place step kernel stays, and the cost no longer depends on S*S.
-// Other beam counts keep the marches of ngw_kernels.hip.
+// Other beam counts keep the marches of ngw_lidar_march.inc.
 
 constexpr uint32_t LIDAR8_MAGIC71 = 60492498u;                                     // ceil(2^32 / 71): x / 71 == umulhi(x, .) for x < 2^15
 // first range k with round(0.71 k) = d (d >= 1): floor((100 d + 20) / 71); checked against the host's table by ngw_lidar_configure
@@ -300,3 +305,5 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_lidar_boards_kernel(const NgwLaun
     wave_lds_sync();
     lidar_boards_rows<NR>(a, lds, (int)tid, R, Rd, Ra, roww, BoardPatch{0u, 0u, 0u, 0u}, S, S2, r, c, f, bmap, tid * (uint32_t)S2, inv, id0, id1, bid);
 }
+
+}  // namespace

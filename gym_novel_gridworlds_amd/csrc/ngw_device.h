@@ -1,4 +1,4 @@
-// ngw_device.h — launch descriptor shared by the kernel TU (ngw_kernels.hip) and the C-ABI TU (ngw_abi.cpp).
+// ngw_device.h — launch descriptors and launcher declarations shared by the device units (ngw_unit_*.hip) and the C-ABI's host side (ngw_abi_*.cpp).
 #ifndef NGW_DEVICE_H
 #define NGW_DEVICE_H
 #include <stdint.h>
@@ -227,7 +227,8 @@ struct NgwDevSpec {
     uint64_t* amask;             /* [n_pad] action masks (ngw_mask.inc): the fused form of the step kernel stores the post-step masks here; nullptr until allocated */
 };
 
-/* ngw_launch's `feat`: which instantiation of the kernel that `mode` names the host dispatch (end of ngw_kernels.hip) picks. */
+/* ngw_launch's `feat`: which instantiation of the kernel that `mode` names the host dispatch (ngw_launch in ngw_unit_general.hip, ngw_part_step in
+ * ngw_unit_step_straight.hip) picks. */
 enum { NGW_FEAT_LIDAR = 1,    /* fused LidarInFront epilogue (with NGW_FEAT_NOSTAGE: the one on the occupancy bit rows) */
        NGW_FEAT_EXT = 2,      /* wrapper predicates (FireWall / FenceRestriction / Crate) */
        NGW_FEAT_NOSTAGE = 8,  /* NGW_MODE_STEP: the in-place step kernel (maps read where they lie, no staging through LDS) */

@@ -1,5 +1,9 @@
-// ngw_expand.inc - snapshot expand (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc; a unit of its own; host side:
-// ngw_abi_snapshot.cpp).
+// ngw_expand.inc - snapshot expand (a unit of its own; host side: ngw_abi_snapshot.cpp).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lean.inc"            // lean_body and its table fetches
+
+namespace {
 //
 // Pair j of a call: the parent is row si[j] of the source set (the state slab, or a snapshot), the child is the parent stepped ONCE with
 // actions[j] by the rules of ngw_step_device, and goes to row di[j] of the destination snapshot as the step leaves it BEFORE any reset: no
@@ -123,3 +127,12 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_expand_kernel(const NgwDevSpec* _
     }
     if (flags) atomicOr(a.b.flags, flags);
 }
+
+// what the launchers of the kernels that step saved rows several times (ngw_slot_rollout.inc, ngw_playout.inc: X = NgwSlotRollout / NgwPlayout) check alike
+template <class X>
+bool slot_step_args_ok(const NgwLaunch* a, const X* x) {
+    return x->count > 0 && x->n_steps >= 1 && x->src_rows >= 1 && a->S >= 3 && a->S <= NGW_MAX_MAP_SIZE && a->K >= 1 && a->K <= NGW_MAX_ITEMS && a->MS >= a->S2 &&
+           !(a->MS & 3) && a->b.flags && x->src.map && (!x->keep || (x->dst.map && x->dst_rows >= 1)) && (x->keep || !x->di);
+}
+
+}  // namespace

@@ -1,4 +1,8 @@
-// ngw_keys.inc - device-side state keys (included by ngw_kernels.hip, inside its namespace; a unit of its own; host side: ngw_abi_snapshot.cpp).
+// ngw_keys.inc - device-side state keys (a unit of its own; host side: ngw_abi_snapshot.cpp).
+#pragma once
+#include "ngw_common.inc"
+
+namespace {
 //
 // keys[j] = the 64-bit key of row idx[j] of a set of state rows (a snapshot, or the state slab) under the field selection `fields`.  The key is
 // a public contract (include/ngw.h, ngw_state_keys): the XOR of independent terms
@@ -113,3 +117,5 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_keys_kernel(const NgwKeys x) {
     if (inside) x.keys[pair] = ok ? key : 0ull;
     if (inside && !ok) atomicOr(x.flags, NGW_F_BAD_INDEX);
 }
+
+}  // namespace

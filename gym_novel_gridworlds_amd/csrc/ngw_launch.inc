@@ -1,5 +1,16 @@
-// ngw_launch.inc — how every kernel of the library is launched, and how a runtime flag picks a kernel instantiation (host code; included by
-// ngw_kernels.hip inside its namespace, before the kernels' own files; <atomic> and <type_traits> come from there).
+// ngw_launch.inc — how every kernel of the library is launched, and how a runtime flag picks a kernel instantiation (host code; part of
+// ngw_common.inc).
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stddef.h>
+#include <stdint.h>
+
+#include <atomic>
+#include <type_traits>
+
+#include "ngw_device.h"
+
+namespace {
 
 // The one launch: the opt-in to more than the default 64 KiB of dynamic LDS (CDNA4 has 160 KiB per CU), then the kernel, in the <<< >>> form
 // (the arguments are converted to the kernel's parameter types in its own order).  The opt-in is per kernel and device and is repeated only
@@ -61,3 +72,8 @@ hipError_t with_row_piece(int S2, F&& f) {
     if (S2 % 4 == 0) return f(std::integral_constant<int, 4>{});
     return f(std::integral_constant<int, 1>{});
 }
+
+// the work-groups of a kernel that gives each of `count` items one lane: whole waves of NGW_EPB
+constexpr int64_t blocks_for(int64_t count) { return (count + NGW_EPB - 1) / NGW_EPB; }
+
+}  // namespace

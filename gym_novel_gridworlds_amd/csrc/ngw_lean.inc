@@ -1,4 +1,11 @@
-// ngw_lean.inc — the per-launch step kernel and the fused rollout of everything but the fused lidar epilogue (included by ngw_kernels.hip, inside its namespace).
+// ngw_lean.inc — the per-launch step kernel and the fused rollout of everything but the fused lidar epilogue.
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_newepisode.inc"      // new_episode, the Philox sources, the signals towards the host
+#include "ngw_lidar_march.inc"     // lidar_epilogue: the fused observation of the staged kernels
+#include "ngw_boards.inc"          // lidar_boards_rows: the fused observation of the in-place kernel
+
+namespace {
 //
 // One launch = one batched step().  Profiling the general kernel (ngw_kernel<., STEP>) with in-kernel clock stamps
 // (tools/stamp_timeline.py) showed a wave spending more cycles on loop-invariant address arithmetic hoisted out of its
@@ -23,3 +30,5 @@
 #include "ngw_mask.inc"
 #include "ngw_lean_step.inc"
 #include "ngw_lean_rollout.inc"
+
+}  // namespace

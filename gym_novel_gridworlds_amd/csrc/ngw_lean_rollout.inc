@@ -234,3 +234,15 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_rollout_lean(const NgwDevSpec* __
     raise_host_flags(a.b.flags_host, flags);
 }
 
+// fused rollout: ngw_rollout_lean, one unit per map addressing mode (eight kernels each: the heaviest to compile)
+template <int MM>
+hipError_t rollout(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+    return with_flag(a->mode == NGW_MODE_ROLLOUT_ACT, [&](auto SUP) {
+        return with_flag((feat & NGW_FEAT_LIDAR) != 0, [&](auto L) {
+            return with_flag((feat & NGW_FEAT_EXT) != 0, [&](auto E) {
+                return launch_kernel<ngw_rollout_lean<MM, decltype(SUP)::value, decltype(E)::value, decltype(L)::value>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, dspec, *a);
+            });
+        });
+    });
+}
+

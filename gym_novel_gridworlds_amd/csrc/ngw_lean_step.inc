@@ -457,3 +457,26 @@ hipError_t launch_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned gri
     return launch_kernel<ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK, PLAIN>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, base, a->actions, (uint32_t)a->n, o_brd, dspec,
                                                                                 off[0], off[1], off[2], off[3], off[4], s2k, *a);
 }
+
+// ONE batched step(): ngw_step_lean.  The staged kernels of one map addressing mode (six each: plain and fused lidar, the plain ones also with
+// fused action masks, all with and without the wrapper predicates) are a unit of their own.
+template <int MM>
+hipError_t step_staged(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+    const bool lidar = (feat & NGW_FEAT_LIDAR) != 0, ext = (feat & NGW_FEAT_EXT) != 0;
+    if ((feat & NGW_FEAT_MASK) && !lidar)   // fused action masks
+        return with_flag(ext, [&](auto E) { return launch_lean<MM, true, decltype(E)::value, false, 0, false, true>(dspec, a, grid, lds_bytes, stream); });
+    return with_flag(lidar, [&](auto L) {
+        return with_flag(ext, [&](auto E) { return launch_lean<MM, true, decltype(E)::value, decltype(L)::value>(dspec, a, grid, lds_bytes, stream); });
+    });
+}
+
+// in-place step + the LidarInFront observation from the occupancy bit rows (ngw_boards.inc): NR = 12 / 20 / 32 register rows; HW: with the host write-through
+template <bool HW>
+hipError_t step_boards(const NgwDevSpec* dspec, const NgwLaunch* a, int feat, unsigned grid, size_t lds_bytes, hipStream_t stream) {
+    if (!a->l_boards) return hipErrorInvalidValue;
+    return with_board_rows(a->BS, [&](auto R) {
+        return with_flag((feat & NGW_FEAT_EXT) != 0, [&](auto E) {
+            return launch_lean<NGW_MAP_STRAIGHT, false, decltype(E)::value, true, decltype(R)::value, HW>(dspec, a, grid, lds_bytes, stream);
+        });
+    });
+}

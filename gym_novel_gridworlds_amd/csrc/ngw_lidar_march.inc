@@ -1,6 +1,10 @@
-// ngw_lidar_march.inc - the LidarInFront observation MARCHED over a map in LDS (included by ngw_kernels.hip, inside its namespace): row formats and the observation tile,
+// ngw_lidar_march.inc - the LidarInFront observation MARCHED over a map in LDS: row formats and the observation tile,
 // the constant-offset march of the reference's default 8 beams on 10 x 10, the world-frame and the per-lane-table marches of every other beam count.  (The default 8 beams on
 // maps up to 32 x 32 no longer march: ngw_boards.inc finds the first hits on occupancy bit rows.)
+#pragma once
+#include "ngw_common.inc"
+
+namespace {
 
 // ---------------------------------------------------------------- LidarInFront observation (shared by every kernel that produces it)
 // observation_wrappers.py:32-78 on the LDS map.  The wave's 64 rows are built in an LDS tile that is the exact HBM image of
@@ -306,3 +310,5 @@ __device__ __forceinline__ void lidar_epilogue(const NgwLaunch& a, uint32_t* lds
     }
     STAMP_SUB(a, 5);
 }
+
+}  // namespace

@@ -1,4 +1,9 @@
-// ngw_lookahead.inc - one-step lookahead tables (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc; a unit of its own).
+// ngw_lookahead.inc - one-step lookahead tables (a unit of its own).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lean.inc"            // the predicate and the functions lean_body is made of
+
+namespace {
 //
 // Entry (i, a) of the table is what ngw_get_step_out would report for env i if ngw_step_device were called now with action a for that env:
 // reward, done and the packed info word, under the handle's spec (every novelty and wrapper predicate) and its autoreset setting.  Nothing
@@ -118,3 +123,5 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_lookahead_kernel(const NgwDevSpec
         stg<uint32_t>(o_info + row * 4u, tid * 4u, o.info);
     }
 }
+
+}  // namespace

@@ -1,6 +1,10 @@
-// ngw_newepisode.inc - what makes a new episode, per lane (included by ngw_kernels.hip, inside its namespace): the Philox word sources, the numpy-shaped bounded draw,
+// ngw_newepisode.inc - what makes a new episode, per lane: the Philox word sources, the numpy-shaped bounded draw,
 // the signals towards the host (sticky flags, mirror, sequence word), the placement chain on the lane's map (reset_lane) with its shuffled-subset passes, the prepared-row
 // copy of one lane, and the two entry points the kernels call (new_episode out of line, new_episode_inline).
+#pragma once
+#include "ngw_common.inc"
+
+namespace {
 
 // ---------------------------------------------------------------- Philox4x32-10 (counter-based, per env & episode)
 // Two word sources with one interface (same stream: block b = counter (b, episode, env_lo, env_hi) yields words 4b .. 4b+3).
@@ -512,3 +516,5 @@ __device__ __forceinline__ uint32_t new_episode_inline(const NgwDevSpec* dspec, 
     const ResetArgs a = {dspec, ru.perm, ru.n_pad, ru.seed, ru.S, ru.S2, ru.K, ru.CW, ru.perm_lds, ru.magicS, rs0, rs1, rs2, rs3, pw0, pw1, pw2, pw3};
     return reset_lane<PhiloxRegs>(a, mp, inv, cand, place_seq, perm_lds, nullptr, env_global, env_local, episode);
 }
+
+}  // namespace

@@ -1,5 +1,11 @@
-// ngw_path.inc - path keys (included by ngw_kernels.hip, inside its namespace, after ngw_keys.inc and before ngw_slot_rollout.inc / ngw_playout.inc:
-// the pieces the PATH forms of ngw_slot_rollout_kernel and ngw_playout_kernel share; host side: ngw_abi_snapshot.cpp).
+// ngw_path.inc - path keys: the pieces the PATH forms of ngw_slot_rollout_kernel (ngw_slot_rollout.inc) and ngw_playout_kernel
+// (ngw_playout.inc) share, and what their launchers check for them (host side: ngw_abi_snapshot.cpp).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lean.inc"            // LeanOut: what a step changed
+#include "ngw_keys.inc"            // the terms of a key
+
+namespace {
 //
 // keys[t * stride + j] = the key ngw_state_keys would return under `fields` for the row pair j is in after it has executed step t (include/ngw.h,
 // ngw_snapshot_rollout_path), 0 for a step it did not execute.  A key is an XOR of independent terms, so the T-loop carries it along: the map
@@ -102,3 +108,11 @@ __device__ __forceinline__ uint64_t path_after_step(PathKeys& pk, const LeanOut&
     if (fields & NGW_KEY_STEP_COUNT) key ^= key_term(5u, 0u, (uint32_t)o.steps);
     return key;
 }
+
+// what the two path launches check beyond the plain ones: a field selection where keys are asked for, a stride that holds the pairs, the shadows inside LDS
+inline bool path_args_ok(const NgwLaunch* a, int64_t count, const uint64_t* keys, int64_t keys_stride, uint32_t fields, uint32_t off_shadow, size_t lds_bytes) {
+    return (!keys || (fields && !(fields & ~NGW_KEY_ALL) && keys_stride >= count)) && a->KP >= a->K &&
+           ((size_t)off_shadow + (size_t)NGW_EPB * (size_t)a->KP) * 4u <= lds_bytes && lds_bytes <= NGW_PATH_LDS_MAX;
+}
+
+}  // namespace

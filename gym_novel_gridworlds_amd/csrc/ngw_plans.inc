@@ -1,4 +1,9 @@
-// ngw_plans.inc - plan evaluation (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc; a unit of its own).
+// ngw_plans.inc - plan evaluation (a unit of its own).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lean.inc"            // the fused rollout's stage-in and lean_body
+
+namespace {
 //
 // Result (i, p) is what env i would collect if the caller's plan p - n_steps action ids - were stepped from its CURRENT state with
 // ngw_step_device: the sum of the rewards, the number of steps taken, whether the plan ran into an episode end, and the info word of its last
@@ -83,3 +88,5 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_plans_lean(const NgwDevSpec* __re
     if (flags) atomicOr(a.b.flags, flags);
     raise_host_flags(a.b.flags_host, flags);
 }
+
+}  // namespace

@@ -1,5 +1,12 @@
-// ngw_playout.inc - snapshot playout (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc, ngw_expand.inc and ngw_sample.inc; a unit of its
-// own; host side: ngw_abi_snapshot.cpp).
+// ngw_playout.inc - snapshot playout (two units: the plain and the PATH form; host side: ngw_abi_snapshot.cpp).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lean.inc"            // lean_body, lean_mask_walk
+#include "ngw_expand.inc"          // expand_move_row: the row mover
+#include "ngw_sample.inc"          // the choice among the valid actions
+#include "ngw_path.inc"            // the PATH form's keys and step limits
+
+namespace {
 //
 // Pair j of a call: the parent is row si[j] of the source set (the state slab, or a snapshot); it is stepped on a private copy up to n_steps
 // times by the rules of ngw_slot_rollout_kernel - it stops at the first step whose `done` would be 1, that step counts, no reset ever runs -
@@ -176,3 +183,21 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
     }
     if (flags) atomicOr(a.b.flags, flags);
 }
+
+// a = the handle's rollout layout with a.autoreset, a.horizon; one wave per 64 pairs.  PATH: lds_bytes = NGW_PATH_LDS_BYTES(the handle's, KP)
+template <bool PATH>
+hipError_t playout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream) {
+    if (!slot_step_args_ok(a, x) || (x->actions && x->stride < x->count) ||
+        (PATH && !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes)))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks_for(x->count)), block(NGW_EPB);
+    return with_row_piece(a->S2, [&](auto V) {
+        return with_flag(ext != 0, [&](auto E) {
+            return with_flag(x->weights != nullptr, [&](auto W) {
+                return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, decltype(W)::value, PATH>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+            });
+        });
+    });
+}
+
+}  // namespace

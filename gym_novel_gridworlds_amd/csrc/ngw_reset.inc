@@ -1,4 +1,9 @@
-// ngw_reset.inc — the dedicated new-episode kernel (included by ngw_kernels.hip, inside its namespace).
+// ngw_reset.inc — the dedicated new-episode kernel.
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_newepisode.inc"      // the Philox stream, the prepared rows, the signals towards the host
+
+namespace {
 //
 // reset() of the plain configurations, of AddItem / Crate (pogostick_v1_env.py:86-181, novelty_wrappers.py:1013-1034, :1071)
 // and of ReplaceItem / FireWall of the wall ring (:1129-1160), for explicit resets (ngw_reset) and for preparing next
@@ -720,3 +725,5 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_reset_fast(const NgwDevSpec* __re
     STAMP_FLUSH(a);
 #endif
 }
+
+}  // namespace

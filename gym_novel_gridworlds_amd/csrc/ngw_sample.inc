@@ -1,5 +1,9 @@
-// ngw_sample.inc - the weighted choice among valid actions (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc and before
-// ngw_playout.inc; the kernel is a unit of its own; host side: ngw_abi_snapshot.cpp).
+// ngw_sample.inc - the weighted choice among valid actions (the kernel is a unit of its own; host side: ngw_abi_snapshot.cpp).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lean.inc"            // lane_mask, lean_gather_lane, philox_block
+
+namespace {
 //
 // Two things live here.  The choice itself - sample_choice, rules 3 - 6 of include/ngw.h (ngw_sample_actions), with playout_kth_bit for the
 // uniform rule it falls back to - is what ngw_sample_kernel below and ngw_playout_kernel<.., WEIGHTED = true> (ngw_playout.inc) both call:
@@ -53,7 +57,6 @@ __device__ __forceinline__ int sample_choice(uint64_t m, uint32_t w, int A, cons
     return mass > 0.0f ? weighted : uniform;
 }
 
-#if NGW_HAS(21)
 // ---------------------------------------------------------------- one weighted choice per state
 // ngw_slot_mask_kernel with the choice behind the mask: one lane per pair, 64 pairs per wave.  Lane j reads idx[j] (NULL: j), checks it against
 // the row count and CLAMPS a bad one to row 0 - nothing is addressed with the bad one -, gathers the row's pose and inventory
@@ -92,4 +95,5 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_sample_kernel(const NgwDevSpec* _
     }
     if (flags) atomicOr(x.flags, flags);
 }
-#endif  // NGW_HAS(21)
+
+}  // namespace

@@ -1,5 +1,11 @@
-// ngw_slot_observe.inc - observations of saved states (included by ngw_kernels.hip, inside its namespace, after ngw_expand.inc; a unit of its own; host
-// side: ngw_abi_snapshot.cpp).
+// ngw_slot_observe.inc - observations of saved states (a unit of its own; host side: ngw_abi_snapshot.cpp).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lidar_march.inc"     // lidar_epilogue: the row builder
+#include "ngw_lean.inc"            // lane_mask, lean_gather_lane
+#include "ngw_expand.inc"          // expand_move_row: the row mover
+
+namespace {
 //
 // The read-only side of a node pool: the LidarInFront row, the AgentMap window and the action mask of row slots[j] of a snapshot go to row j of
 // the caller's buffer.  Nothing but those rows and the sticky error flags is stored, and nothing here restates a game rule or an observation: the
@@ -129,3 +135,5 @@ __global__ __launch_bounds__(256) void ngw_slot_view_kernel(const NgwSlotObs x) 
         x.view[t] = word;
     }
 }
+
+}  // namespace

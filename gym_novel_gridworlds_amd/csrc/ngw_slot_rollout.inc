@@ -1,5 +1,11 @@
-// ngw_slot_rollout.inc - snapshot rollout (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc and ngw_expand.inc; a unit of
-// its own; host side: ngw_abi_snapshot.cpp).
+// ngw_slot_rollout.inc - snapshot rollout (two units: the plain and the PATH form; host side: ngw_abi_snapshot.cpp).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lean.inc"            // lean_body and its table fetches
+#include "ngw_expand.inc"          // expand_move_row: the row mover
+#include "ngw_path.inc"            // the PATH form's keys and step limits
+
+namespace {
 //
 // Pair j of a call: the parent is row si[j] of the source set (the state slab, or a snapshot); it is stepped on a private copy with the
 // pair's n_steps actions by the rules of ngw_plan_eval - it stops at the first step whose `done` would be 1, that step counts, no reset ever
@@ -149,3 +155,19 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
     }
     if (flags) atomicOr(a.b.flags, flags);
 }
+
+// a = the handle's rollout layout with a.autoreset, a.horizon; one wave per 64 pairs.  PATH: lds_bytes = NGW_PATH_LDS_BYTES(the handle's, KP)
+template <bool PATH>
+hipError_t slot_rollout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream) {
+    if (!slot_step_args_ok(a, x) || x->stride < x->count || !x->actions ||
+        (PATH && !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes)))
+        return hipErrorInvalidValue;
+    const dim3 grid((unsigned)blocks_for(x->count)), block(NGW_EPB);
+    return with_row_piece(a->S2, [&](auto V) {
+        return with_flag(ext != 0, [&](auto E) {
+            return launch_kernel<ngw_slot_rollout_kernel<decltype(V)::value, decltype(E)::value, PATH>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+        });
+    });
+}
+
+}  // namespace

@@ -1,5 +1,9 @@
 // ngw_snapshot.inc - device-side snapshots: rows of the seven state arrays moved between the state slab and a snapshot buffer, in either
-// direction, through index lists (NgwSnap in ngw_device.h; host side: ngw_abi_snapshot.cpp).
+// direction, through index lists (NgwSnap in ngw_device.h; a unit of its own; host side: ngw_abi_snapshot.cpp).
+#pragma once
+#include "ngw_common.inc"
+
+namespace {
 //
 // A row is small and oddly sized (S*S map bytes + 4*K inventory bytes + 21 bytes of scalars: 188 B at 10 x 10 with K = 17), so one lane
 // per env would issue 25 dword loads whose 64 addresses lie 100 B apart - most of every memory transaction unused.  Instead
@@ -60,3 +64,5 @@ __global__ void __launch_bounds__(NGW_SNAP_BLOCK) ngw_snapshot_kernel(const NgwS
     if (g == NGW_SNAP_GROUP - 4 && !a.keep_episode) a.dst.episode[di] = a.src.episode[si];
     if (g == NGW_SNAP_GROUP - 5) a.dst.selected[di] = a.src.selected[si];
 }
+
+}  // namespace

@@ -1,4 +1,9 @@
-// ngw_solo.inc — the one-env handle's resident step loop (included by ngw_kernels.hip, inside its namespace, after ngw_lean.inc).
+// ngw_solo.inc — the one-env handle's resident step loop.
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lean.inc"            // lean_body: the one step
+
+namespace {
 //
 // BASELINE configs[0] is ONE env driven from a Python loop (reference tests/random_action.py:51-64).  A launch per step() costs such
 // a handle ~3 us of hipLaunchKernel on the host and ~7 us until the results are visible - more than the reference's own Python spends on a
@@ -144,3 +149,5 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_solo_kernel(const NgwDevSpec* __r
     __threadfence_system();
     if (tid == 0) *(volatile uint32_t*)(p.out + 1) = 1u;                           // exited: the state in HBM is the committed one, sequence number out[0]
 }
+
+}  // namespace

@@ -1,5 +1,11 @@
-// ngw_successors.inc - successor keys (included by ngw_kernels.hip, inside its namespace, after ngw_expand.inc and ngw_keys.inc; a unit of its own;
-// host side: ngw_abi_snapshot.cpp).
+// ngw_successors.inc - successor keys (a unit of its own; host side: ngw_abi_snapshot.cpp).
+#pragma once
+#include "ngw_common.inc"
+#include "ngw_lean.inc"            // lean_body and its table fetches
+#include "ngw_expand.inc"          // expand_move_row: the row mover
+#include "ngw_keys.inc"            // the terms of a key
+
+namespace {
 //
 // keys[j * A + a] = the key ngw_state_keys would return under `fields` for the child that ngw_snapshot_expand would write for parent idx[j] and
 // action a, for every a in 0 .. A-1 (A = n_actions), and reward / done / info [j * A + a] what that expand would report.  No child is written:
@@ -137,3 +143,5 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_successors_kernel(const NgwDevSpe
     // ---- 5. the flags
     if (flags) atomicOr(a.b.flags, flags);
 }
+
+}  // namespace

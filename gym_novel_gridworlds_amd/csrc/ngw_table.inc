@@ -1,4 +1,8 @@
-// ngw_table.inc - the device-side key table (included by ngw_kernels.hip, inside its namespace; a unit of its own; host side: ngw_abi_table.cpp).
+// ngw_table.inc - the device-side key table (a unit of its own; host side: ngw_abi_table.cpp).
+#pragma once
+#include "ngw_common.inc"
+
+namespace {
 //
 // An open-addressing set of 64-bit keys: "have I seen this state before?" for a search that runs many iterations.  Storage is two arrays of
 // `buckets` (a power of two) 64-bit words: key[] (0 = empty) and stamp[] (all ones = nobody has offered this bucket's key yet), and one counter.
@@ -61,3 +65,5 @@ __global__ void __launch_bounds__(NGW_TABLE_BLOCK) ngw_table_fresh_kernel(const 
     const int32_t w = x.where[j];
     x.fresh[j] = ((uint64_t)(int64_t)w <= x.mask && x.stamp[w] == x.base + (uint64_t)j) ? 1 : 0;
 }
+
+}  // namespace
