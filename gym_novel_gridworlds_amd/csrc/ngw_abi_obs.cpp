@@ -4,6 +4,23 @@
 
 using namespace ngwh;
 
+// LDS of the stand-alone lidar launch: item tables | per-lane ray table (only when the rays are not world-frame) | observation
+// tile | guard | maps | guard | inventory rows.  After its hit a ray's remaining cells may fall outside the lane's own map: the
+// guards keep those (ignored) reads inside the allocation.
+size_t ngwh::lidar_layout(const ngw_handle* h, NgwLaunch& q) {
+    const uint32_t guard = (uint32_t)((h->lidar_range * (q.S + 1) + 15) / 16 * 4);        // dwords
+    uint32_t off = 0;
+    q.off_litem = off; off += 2 * NGW_MAX_ITEMS / 4;
+    off = (off + 3u) & ~3u;
+    q.off_ltab = off; if (!h->lidar_world) off += 4 * NGW_LIDAR_MAX_BEAMS * NGW_LIDAR_MAX_RANGE * 2 / 4;
+    q.off_ltile = off; off += (uint32_t)(NGW_EPB * q.l_rb / 4) + NGW_EPB / 4;             // + one dump byte per lane
+    off = ((off + 3u) & ~3u) + guard;
+    q.off_map = off; off += (uint32_t)(NGW_EPB * q.MS / 4) + guard;
+    off = (off + 3u) & ~3u;
+    q.off_inv = off; off += (uint32_t)(q.KP * NGW_EPB);
+    return (size_t)off * 4;
+}
+
 namespace {
 
 // Boards mode on / off: decided from (fused, eligible table); call BEFORE upload_reset_u (the no-stage launch prototype carries the mode),
@@ -25,26 +42,14 @@ int boards_mode_changed(ngw_handle* h, bool was) {
     return NGW_OK;
 }
 
-// LDS of the stand-alone lidar launch: item tables | per-lane ray table (only when the rays are not world-frame) | observation
-// tile | guard | maps | guard | inventory rows.  After its hit a ray's remaining cells may fall outside the lane's own map: the
-// guards keep those (ignored) reads inside the allocation.
 int layout_lidar(ngw_handle* h) {
     NgwLaunch& q = h->lidar_proto;
     q = h->proto;
     q.b = h->b;
     lidar_format(h, q);
-    const uint32_t guard = (uint32_t)((h->lidar_range * (q.S + 1) + 15) / 16 * 4);        // dwords
-    uint32_t off = 0;
-    q.off_litem = off; off += 2 * NGW_MAX_ITEMS / 4;
-    off = (off + 3u) & ~3u;
-    q.off_ltab = off; if (!h->lidar_world) off += 4 * NGW_LIDAR_MAX_BEAMS * NGW_LIDAR_MAX_RANGE * 2 / 4;
-    q.off_ltile = off; off += (uint32_t)(NGW_EPB * q.l_rb / 4) + NGW_EPB / 4;             // + one dump byte per lane
-    off = ((off + 3u) & ~3u) + guard;
-    q.off_map = off; off += (uint32_t)(NGW_EPB * q.MS / 4) + guard;
-    off = (off + 3u) & ~3u;
-    q.off_inv = off; off += (uint32_t)(q.KP * NGW_EPB);
-    if ((size_t)off * 4 > 160 * 1024) return fail(NGW_E_INVALID_ARG, "lidar observation of %d values needs %zu B of LDS (> 160 KiB)", h->lidar_len, (size_t)off * 4);
-    h->lidar_lds = (size_t)off * 4;
+    const size_t bytes = lidar_layout(h, q);
+    if (bytes > 160 * 1024) return fail(NGW_E_INVALID_ARG, "lidar observation of %d values needs %zu B of LDS (> 160 KiB)", h->lidar_len, bytes);
+    h->lidar_lds = bytes;
     return NGW_OK;
 }
 

@@ -10,6 +10,8 @@
 // The successor keys (ngw_successors.inc) are the keys of every action's child of such rows, with no child stored: they commit nothing either.
 // A playout (ngw_playout.inc) is a rollout whose actions the kernel draws among the valid ones of each step: it commits nothing either.
 // The path forms of both (ngw_path.inc) add per-pair step limits and the key of every visited state: they commit nothing either.
+// The trajectory forms (ngw_traj.inc) add the per-step rewards, mask words and LidarInFront rows of such a path: they commit nothing either, and
+// leave the env's own lidar rows alone.
 // The weighted choice (ngw_sample.inc) draws one action per row by the caller's weights among the valid ones: it commits nothing either.
 #include "ngw_host.h"
 
@@ -110,33 +112,94 @@ int path_args(const ngw_handle* h, const PathArgs& pa, int64_t count, const char
     return NGW_OK;
 }
 
-// a rollout, plain (pa == nullptr: the kernel as it always was) or in its path form
+// what the trajectory forms ask for beyond the path forms; nullptr = the path (or plain) call
+struct TrajArgs {
+    int32_t* rewards;
+    int64_t rewards_stride;
+    uint64_t* masks;                          // (playouts)
+    int64_t masks_stride;
+    void* obs;
+    int64_t obs_stride;
+};
+
+// the trajectory arguments of one call, checked (before anything touches the stream) -> the launch block's source, the LDS bytes of the launch and
+// where the inventory shadows sit.  Without observations: the path form's layout and its map limit.  With them: the stand-alone lidar launch's
+// layout (ngw_lidar_configure), and the shadows behind it only where keys are asked for.
+int traj_args(const ngw_handle* h, const PathArgs& pa, const TrajArgs& ta, int64_t count, const char* what, const char* call, size_t* lds, uint32_t* off_shadow) {
+    if (ta.rewards && ta.rewards_stride < count)
+        return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a reward stride of %lld", what, (long long)count, (long long)ta.rewards_stride);
+    if (ta.masks && ta.masks_stride < count)
+        return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a mask stride of %lld", what, (long long)count, (long long)ta.masks_stride);
+    if (!ta.obs) {
+        *off_shadow = (uint32_t)(h->lds_bytes / 4);
+        return path_args(h, pa, count, what, call, lds);
+    }
+    if (pa.keys && (!pa.fields || (pa.fields & ~NGW_KEY_ALL)))
+        return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)pa.fields);
+    if (pa.keys && pa.keys_stride < count) return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a key stride of %lld", what, (long long)count, (long long)pa.keys_stride);
+    if (!h->lidar_len) return fail(NGW_E_INVALID_ARG, "%s with observations before ngw_lidar_configure", call);
+    if (ta.obs_stride % NGW_EPB || ta.obs_stride < (count + NGW_EPB - 1) / NGW_EPB * NGW_EPB)
+        return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with an observation stride of %lld rows: a multiple of 64 that holds the pairs rounded up to 64 expected",
+                    what, (long long)count, (long long)ta.obs_stride);
+    if (reinterpret_cast<uintptr_t>(ta.obs) & 15u) return fail(NGW_E_INVALID_ARG, "%s: the observation rows must be 16-byte aligned", what);
+    NgwLaunch q = h->proto;                          // (the size alone: a handle whose maps the lidar launch cannot hold has no lidar_proto)
+    lidar_format(h, q);
+    const size_t rows = lidar_layout(h, q);
+    *off_shadow = (uint32_t)(rows / 4);
+    *lds = rows + (pa.keys ? (size_t)NGW_EPB * 4u * (size_t)h->proto.KP : 0u);
+    if (*lds > NGW_PATH_LDS_MAX || (h->general_ok && !h->lidar_lds))   // (general_ok == 0 with a layout that would fit: the plain refusal follows)
+        return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps between two guards, the lidar tables and a tile of 64 observation rows%s in "
+                                       "LDS (%s) and they need %zu B, more than 160 KiB; the call without observations %s", h->proto.S,
+                    pa.keys ? " and a second copy of the inventories" : "", call, *lds, h->general_ok ? "has its own limit" : "is refused too");
+    return NGW_OK;
+}
+
+// the launch block of an observing trajectory call: the stand-alone lidar launch's layout and row format with the handle's buffers, autoreset setting and horizon
+NgwLaunch traj_obs_block(const ngw_handle* h) {
+    NgwLaunch a = h->lidar_proto;
+    a.b = h->b;
+    a.lout = nullptr;                                // (every tile goes to the caller's rows)
+    a.autoreset = h->autoreset;
+    a.horizon = h->horizon;
+    return a;
+}
+
+// a rollout, plain (pa == nullptr: the kernel as it always was), in its path form, or (ta != nullptr, with pa) in its trajectory form
 int rollout_call(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps, ngw_snapshot* dst,
-                 const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, const PathArgs* pa) {
+                 const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, const PathArgs* pa,
+                 const TrajArgs* ta = nullptr) {
     if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "rollout of %d steps", (int)n_steps);
     if (count < 0 || pair_stride < count)
         return fail(NGW_E_INVALID_ARG, "rollout of %lld pairs with a pair stride of %lld", (long long)count, (long long)pair_stride);
-    if (!dst && !ret_dev && !length_dev && !ended_dev && !info_dev && !(pa && pa->keys))
+    if (!dst && !ret_dev && !length_dev && !ended_dev && !info_dev && !(pa && pa->keys) && !(ta && (ta->rewards || ta->obs)))
         return fail(NGW_E_INVALID_ARG, "rollout without a destination and without a report: nothing to do");
     int64_t src_rows;
-    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "rollout", pa ? "ngw_snapshot_rollout_path" : "ngw_snapshot_rollout", &src_rows)) return rc;
     size_t lds = h->lds_bytes;
-    if (pa)
+    uint32_t off_shadow = (uint32_t)(h->lds_bytes / 4);
+    if (ta)                                          // (ahead of the plain refusal of large maps: this one names the bytes)
+        if (int rc = traj_args(h, *pa, *ta, count, "rollout", "ngw_snapshot_rollout_traj", &lds, &off_shadow)) return rc;
+    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "rollout",
+                                 ta ? "ngw_snapshot_rollout_traj" : (pa ? "ngw_snapshot_rollout_path" : "ngw_snapshot_rollout"), &src_rows))
+        return rc;
+    if (pa && !ta)
         if (int rc = path_args(h, *pa, count, "rollout", "ngw_snapshot_rollout_path", &lds)) return rc;
     if (int rc = enter(h)) return rc;
     if (count == 0) return NGW_OK;
-    const NgwLaunch a = step_block(h);
+    const NgwLaunch a = ta && ta->obs ? traj_obs_block(h) : step_block(h);
     NgwSlotRollout x{};
     x.src = src ? src->r : state_rows(h);
     if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
     x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = pair_stride; x.n_steps = n_steps;
     x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev;
     x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
-    if (pa) {
-        x.limits = pa->limits; x.keys = pa->keys; x.keys_stride = pa->keys_stride; x.fields = pa->fields; x.off_shadow = (uint32_t)(h->lds_bytes / 4);
+    if (pa) { x.limits = pa->limits; x.keys = pa->keys; x.keys_stride = pa->keys_stride; x.fields = pa->fields; x.off_shadow = off_shadow; }
+    if (ta) {
+        x.rewards = ta->rewards; x.rewards_stride = ta->rewards_stride; x.obs = ta->obs; x.obs_stride = ta->obs_stride;
+        HIP_TRY(ngw_slot_rollout_traj_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
+    } else if (pa)
         HIP_TRY(ngw_slot_rollout_path_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
-    } else
+    else
         HIP_TRY(ngw_slot_rollout_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
     return NGW_OK;
 }
@@ -144,19 +207,24 @@ int rollout_call(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, c
 // a playout, likewise
 int playout_call(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
                  const float* weights_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev,
-                 uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride, const PathArgs* pa) {
+                 uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride, const PathArgs* pa, const TrajArgs* ta = nullptr) {
     if (!h) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "playout of %d steps", (int)n_steps);
     if (count < 0 || (actions_dev && actions_stride < count))
         return fail(NGW_E_INVALID_ARG, "playout of %lld pairs with an action stride of %lld", (long long)count, (long long)actions_stride);
     int64_t src_rows;
-    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "playout", pa ? "ngw_snapshot_playout_path" : "ngw_snapshot_playout", &src_rows)) return rc;
     size_t lds = h->lds_bytes;
-    if (pa)
+    uint32_t off_shadow = (uint32_t)(h->lds_bytes / 4);
+    if (ta)                                          // (ahead of the plain refusal of large maps: this one names the bytes)
+        if (int rc = traj_args(h, *pa, *ta, count, "playout", "ngw_snapshot_playout_traj", &lds, &off_shadow)) return rc;
+    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "playout",
+                                 ta ? "ngw_snapshot_playout_traj" : (pa ? "ngw_snapshot_playout_path" : "ngw_snapshot_playout"), &src_rows))
+        return rc;
+    if (pa && !ta)
         if (int rc = path_args(h, *pa, count, "playout", "ngw_snapshot_playout_path", &lds)) return rc;
     if (int rc = enter(h)) return rc;
     if (count == 0) return NGW_OK;
-    const NgwLaunch a = step_block(h);
+    const NgwLaunch a = ta && ta->obs ? traj_obs_block(h) : step_block(h);
     NgwPlayout x{};
     x.src = src ? src->r : state_rows(h);
     if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
@@ -164,10 +232,14 @@ int playout_call(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, i
     x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev; x.first_action = first_action_dev;
     x.seed = seed; x.first_pair = first_pair; x.weights = weights_dev;
     x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
-    if (pa) {
-        x.limits = pa->limits; x.keys = pa->keys; x.keys_stride = pa->keys_stride; x.fields = pa->fields; x.off_shadow = (uint32_t)(h->lds_bytes / 4);
+    if (pa) { x.limits = pa->limits; x.keys = pa->keys; x.keys_stride = pa->keys_stride; x.fields = pa->fields; x.off_shadow = off_shadow; }
+    if (ta) {
+        x.rewards = ta->rewards; x.rewards_stride = ta->rewards_stride; x.masks = ta->masks; x.masks_stride = ta->masks_stride;
+        x.obs = ta->obs; x.obs_stride = ta->obs_stride;
+        HIP_TRY(ngw_playout_traj_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
+    } else if (pa)
         HIP_TRY(ngw_playout_path_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
-    } else
+    else
         HIP_TRY(ngw_playout_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
     return NGW_OK;
 }
@@ -310,6 +382,26 @@ int ngw_snapshot_playout_path(ngw_handle* h, ngw_snapshot* src, const int32_t* s
     const PathArgs pa{limits_dev, fields, keys_dev, keys_stride};
     return playout_call(h, src, src_idx_dev, count, n_steps, seed, first_pair, weights_dev, dst, dst_slots_dev, ret_dev, length_dev, ended_dev, info_dev,
                         first_action_dev, actions_dev, actions_stride, &pa);
+}
+
+int ngw_snapshot_rollout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
+                              const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev,
+                              uint8_t* ended_dev, uint32_t* info_dev, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev,
+                              int64_t rewards_stride, void* obs_dev, int64_t obs_stride) {
+    const PathArgs pa{limits_dev, fields, keys_dev, keys_stride};
+    const TrajArgs ta{rewards_dev, rewards_stride, nullptr, 0, obs_dev, obs_stride};
+    return rollout_call(h, src, src_idx_dev, actions_dev, pair_stride, n_steps, dst, dst_slots_dev, count, ret_dev, length_dev, ended_dev, info_dev, &pa, &ta);
+}
+
+int ngw_snapshot_playout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                              const float* weights_dev, const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev,
+                              int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride,
+                              uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev, int64_t rewards_stride, uint64_t* masks_dev,
+                              int64_t masks_stride, void* obs_dev, int64_t obs_stride) {
+    const PathArgs pa{limits_dev, fields, keys_dev, keys_stride};
+    const TrajArgs ta{rewards_dev, rewards_stride, masks_dev, masks_stride, obs_dev, obs_stride};
+    return playout_call(h, src, src_idx_dev, count, n_steps, seed, first_pair, weights_dev, dst, dst_slots_dev, ret_dev, length_dev, ended_dev, info_dev,
+                        first_action_dev, actions_dev, actions_stride, &pa, &ta);
 }
 
 int ngw_snapshot_playout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,

@@ -518,6 +518,14 @@ struct NgwSlotRollout {
     uint64_t* keys;
     int64_t keys_stride;
     uint32_t fields, off_shadow;
+    /* the trajectory form (TRAJ; last again).  rewards: nullptr, or the reward of step t of pair j to rewards[t * rewards_stride + j], 0 for a step the
+     * pair did not execute.  obs: nullptr, or the LidarInFront row (the launch block's format, l_rb bytes) of the parent to row j and of the state
+     * step t leaves to row (t + 1) * obs_stride + j, all zeros for a step the pair did not execute; obs_stride is a multiple of 64 rows and holds
+     * `count` rounded up to 64: a wave stores whole 64-row tiles.  With obs the launch block is the stand-alone lidar launch's layout. */
+    int32_t* rewards;
+    int64_t rewards_stride;
+    void* obs;
+    int64_t obs_stride;
 };
 #define NGW_PATH_LDS_MAX ((size_t)160 * 1024)                                                                   /* what a CU of gfx950 has */
 #define NGW_PATH_LDS_BYTES(lds_bytes, KP) ((size_t)(lds_bytes) + (size_t)NGW_EPB * 4u * (size_t)(KP))   /* the handle's layout and the inventory shadows behind it */
@@ -557,6 +565,16 @@ struct NgwPlayout {
     uint64_t* keys;
     int64_t keys_stride;
     uint32_t fields, off_shadow;
+    /* the trajectory form (TRAJ; last again).  rewards: nullptr, or the reward of step t of pair j to rewards[t * rewards_stride + j], 0 for a step the
+     * pair did not execute.  obs: nullptr, or the LidarInFront row (the launch block's format, l_rb bytes) of the parent to row j and of the state
+     * step t leaves to row (t + 1) * obs_stride + j, all zeros for a step the pair did not execute; obs_stride is a multiple of 64 rows and holds
+     * `count` rounded up to 64: a wave stores whole 64-row tiles.  With obs the launch block is the stand-alone lidar launch's layout. */
+    int32_t* rewards;
+    int64_t rewards_stride;
+    uint64_t* masks;      /* nullptr, or the mask word the choice of step t was made under (after the all-actions replacement) to masks[t * masks_stride + j], 0 likewise */
+    int64_t masks_stride;
+    void* obs;
+    int64_t obs_stride;
 };
 #ifdef __cplusplus
 extern "C"
@@ -567,6 +585,17 @@ extern "C"
 #endif
 /* the path form, as ngw_slot_rollout_path_launch */
 hipError_t ngw_playout_path_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+/* the trajectory forms (PATH and TRAJ): x->rewards / x->masks / x->obs are read too.  Without x->obs: the path launch's block and lds_bytes.  With
+ * it: a = the stand-alone lidar launch's layout (ngw_lidar_configure) with a->autoreset, a->horizon, x->off_shadow behind it where x->keys is
+ * set, lds_bytes = that layout's (+ the shadows) */
+hipError_t ngw_slot_rollout_traj_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_playout_traj_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream);
 
 /* Slot observations (ngw_slot_observe.inc, ngw_abi_snapshot.cpp): observations and action masks of SAVED states, gathered by slot index. Output
  * row j of a call describes row slots[j] of `src` (a snapshot; a NULL list = j itself).  An index outside [0, rows) is never used as an address:

@@ -303,6 +303,8 @@ void adapt_cadence(ngw_handle* h);
 int rebuild_boards(ngw_handle* h, const int8_t* map, uint32_t* brd, int64_t rows);
 int launch_lidar_boards(ngw_handle* h);            // boards mode: the LidarInFront observation of the current state from the bit rows, as its own launch
 void drop_graph(ngw_handle* h);
+// ngw_abi_obs.cpp
+size_t lidar_layout(const ngw_handle* h, NgwLaunch& q);   // the stand-alone lidar launch's LDS carve-up into q (S, MS, KP and the row format set) -> its bytes, whatever they come to
 // ngw_abi_mask.cpp
 int launch_act_mask(ngw_handle* h);                 // the masks of the state in HBM, on the handle's stream (allocates the buffer on first use)
 int alloc_act_mask(ngw_handle* h);                  // the mask buffer, published to NgwDevSpec::amask (no-op once allocated)

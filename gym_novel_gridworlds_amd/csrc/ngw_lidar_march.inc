@@ -243,23 +243,29 @@ __device__ __forceinline__ void lidar_zero_tile(const NgwLaunch& a, uint32_t* ld
     }
 }
 
+// Inside a T-loop (the TRAJ forms of ngw_slot_rollout_kernel / ngw_playout_kernel: one call per step) two things differ, both defaulted so that
+// every other caller compiles to what it always did: tab_staged = the caller staged the per-lane ray table ONCE with lidar_stage_table (the
+// table does not change between the calls: T copies of 8 KiB saved), and tile_out = where THIS call's 64-row tile goes (nullptr: rows
+// 64 * blockIdx.x .. of a.lout).
+__device__ __forceinline__ void lidar_stage_table(const NgwLaunch& a, uint32_t* lds, int tid) {
+    const u32x4* src = reinterpret_cast<const u32x4*>(a.lcfg->off);
+    LDS_AS u32x4* dst = (LDS_AS u32x4*)(lds + a.off_ltab);
+    u32x4 tb[8];
+#pragma unroll
+    for (int j = 0; j < 8; j++) tb[j] = src[tid + EPB * j];
+#pragma unroll
+    for (int j = 0; j < 8; j++) dst[tid + EPB * j] = tb[j];
+}
+
 __device__ __forceinline__ void lidar_epilogue(const NgwLaunch& a, uint32_t* lds, int tid, bool live, const int8_t* agent, int f, const int32_t* inv,
-                                               bool zeroed = false) {
+                                               bool zeroed = false, bool tab_staged = false, char* tile_out = nullptr) {
     const int B = a.l_beams, R = a.l_range, NC = a.l_chan, NI = a.l_inv, rb = a.l_rb, npc = 4 * rb;   // 64 rows = 4 * rb pieces of 16 B
     const int sh = a.l_fmt == NGW_LFMT_I32 ? 2 : (a.l_fmt == NGW_LFMT_I16 ? 1 : 0);                   // beam entry = 1 << sh bytes
     LDS_AS u32x4* t4 = (LDS_AS u32x4*)(lds + a.off_ltile);
     wave_lds_sync();
     STAMP_SUB(a, 0);
     if (!zeroed) lidar_zero_tile(a, lds, tid);
-    if (!a.l_world) {                                                              // (uniform) the per-lane ray table, staged now: 8 KiB
-        const u32x4* src = reinterpret_cast<const u32x4*>(a.lcfg->off);
-        LDS_AS u32x4* dst = (LDS_AS u32x4*)(lds + a.off_ltab);
-        u32x4 tb[8];
-#pragma unroll
-        for (int j = 0; j < 8; j++) tb[j] = src[tid + EPB * j];
-#pragma unroll
-        for (int j = 0; j < 8; j++) dst[tid + EPB * j] = tb[j];
-    }
+    if (!tab_staged && !a.l_world) lidar_stage_table(a, lds, tid);                 // (uniform) the per-lane ray table, staged now: 8 KiB
     wave_lds_sync();
     STAMP_SUB(a, 1);
     const LDS_AS uint8_t* chan_of_item = (const LDS_AS uint8_t*)(lds + a.off_litem);
@@ -299,7 +305,7 @@ __device__ __forceinline__ void lidar_epilogue(const NgwLaunch& a, uint32_t* lds
     }
     wave_lds_sync();
     STAMP_SUB(a, 4);
-    GLOBAL_AS u32x4* g4 = (GLOBAL_AS u32x4*)(reinterpret_cast<char*>(a.lout) + (uint64_t)blockIdx.x * (uint32_t)(EPB * rb));
+    GLOBAL_AS u32x4* g4 = (GLOBAL_AS u32x4*)(tile_out ? tile_out : reinterpret_cast<char*>(a.lout) + (uint64_t)blockIdx.x * (uint32_t)(EPB * rb));
     for (int base = 0; base < npc; base += EPB * 4) {                              // four pieces per lane in flight
         u32x4 v[4];
 #pragma unroll

@@ -5,6 +5,7 @@
 #include "ngw_expand.inc"          // expand_move_row: the row mover
 #include "ngw_sample.inc"          // the choice among the valid actions
 #include "ngw_path.inc"            // the PATH form's keys and step limits
+#include "ngw_traj.inc"            // the TRAJ form's per-step rewards, mask words and lidar rows
 
 namespace {
 //
@@ -36,9 +37,14 @@ namespace {
 // choice, so a limited playout is the prefix of the unlimited one and the actions beyond the limit are recorded as -1.  PATH = false is the
 // kernel as it was.
 //
+// TRAJ (ngw_snapshot_playout_traj; a PATH form): x.rewards, x.masks and x.obs take the reward, the mask word m (after the all-actions replacement)
+// and the LidarInFront rows of every step as ngw_traj.inc lays them out - 0 / zero rows for a step the pair did not execute; with x.obs the launch
+// block is the stand-alone lidar launch's layout and every lane of the wave reaches every row set (the loop is wave-uniform).  TRAJ = false is
+// the kernel as it was.
+//
 // x.actions (may be nullptr): int32, the action of pair j at step t to [t * x.stride + j] (stride >= count) - the layout ngw_slot_rollout_kernel reads.
 
-template <int VEC, bool EXT, bool WEIGHTED, bool PATH = false>
+template <int VEC, bool EXT, bool WEIGHTED, bool PATH = false, bool TRAJ = false>
 __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* __restrict__ dspec, const NgwLaunch a, const NgwPlayout x) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t tid = threadIdx.x;
@@ -81,6 +87,8 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
         const int sj = __builtin_amdgcn_ds_bpermute(j << 2, sic);
         expand_move_row<VEC, true>(x.src.map + (size_t)sj * (size_t)S2, x.src.inv + (size_t)sj * (size_t)K, lds_map + j * MSdw, lds_inv + j * KP, S2, K, g);
     }
+    if constexpr (TRAJ)
+        if (x.obs) traj_obs_begin(a, lds, tid);
     __syncthreads();
     // ---- 2. up to n_steps steps of this lane's row
     int8_t* const mp = reinterpret_cast<int8_t*>(lds_map) + tid * a.MS;
@@ -108,6 +116,12 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
         pa.limit = x.limits && ok ? min(max(x.limits[pair], 0), n_steps) : n_steps;
         pa.kout = x.keys && inside ? x.keys + pair : nullptr;
         if (x.keys) pa.pk = path_begin(lds_map + tid * MSdw, inv, lds + x.off_shadow + tid * KP, S2, K, x.fields, episode);
+    }
+    TrajLane<TRAJ> tr;
+    if constexpr (TRAJ) {
+        tr.rew = x.rewards && inside ? x.rewards + pair : nullptr;
+        tr.msk = x.masks && inside ? x.masks + pair : nullptr;
+        if (x.obs) traj_obs_rows(a, lds, tid, ok, mp, S, r, c, f, inv, x.obs, x.obs_stride, 0);   // row block 0: the parents
     }
     int s = 0;
     for (; s < n_steps; s++) {
@@ -145,6 +159,11 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
                 const uint64_t key = path_after_step(pa.pk, o, pa.grp, pa.before, inv, Kv, x.fields);
                 if (pa.kout) pa.kout[(int64_t)s * x.keys_stride] = alive ? key : 0ull;
             }
+        if constexpr (TRAJ) {                                                      // (`alive` still says: this pair executed this step)
+            if (tr.rew) tr.rew[(int64_t)s * x.rewards_stride] = alive ? o.reward : 0;
+            if (tr.msk) tr.msk[(int64_t)s * x.masks_stride] = alive ? m : 0ull;
+            if (x.obs) traj_obs_rows(a, lds, tid, alive, mp, S, r, c, f, inv, x.obs, x.obs_stride, s + 1);
+        }
         if (alive) {
             ret += o.reward; len += 1; info = o.info;
             if (o.ended) { ended = 1; alive = false; }                             // the ending step counts; no reset runs, the pair is over
@@ -154,6 +173,13 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
     if constexpr (PATH)
         if (pa.kout)
             for (int u = s; u < n_steps; u++) pa.kout[(int64_t)u * x.keys_stride] = 0ull;
+    if constexpr (TRAJ) {
+        if (tr.rew)
+            for (int u = s; u < n_steps; u++) tr.rew[(int64_t)u * x.rewards_stride] = 0;
+        if (tr.msk)
+            for (int u = s; u < n_steps; u++) tr.msk[(int64_t)u * x.masks_stride] = 0ull;
+        if (x.obs) traj_zero_tiles(a, tid, x.obs, x.obs_stride, s, n_steps);
+    }
     if (rec && inside)
         for (; s < n_steps; s++) rec[(int64_t)s * tstride] = -1;                   // the steps no pair of this wave executed
     __syncthreads();
@@ -184,17 +210,20 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
     if (flags) atomicOr(a.b.flags, flags);
 }
 
-// a = the handle's rollout layout with a.autoreset, a.horizon; one wave per 64 pairs.  PATH: lds_bytes = NGW_PATH_LDS_BYTES(the handle's, KP)
-template <bool PATH>
+// a = the handle's rollout layout with a.autoreset, a.horizon; one wave per 64 pairs.  PATH: lds_bytes = NGW_PATH_LDS_BYTES(the handle's, KP).
+// TRAJ: as PATH, or with x->obs the stand-alone lidar launch's layout (ngw_device.h, ngw_playout_traj_launch)
+template <bool PATH, bool TRAJ = false>
 hipError_t playout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream) {
     if (!slot_step_args_ok(a, x) || (x->actions && x->stride < x->count) ||
-        (PATH && !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes)))
+        (PATH && !TRAJ && !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes)) ||
+        (TRAJ && !traj_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes, x->rewards, x->rewards_stride, x->masks, x->masks_stride,
+                               x->obs, x->obs_stride)))
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks_for(x->count)), block(NGW_EPB);
     return with_row_piece(a->S2, [&](auto V) {
         return with_flag(ext != 0, [&](auto E) {
             return with_flag(x->weights != nullptr, [&](auto W) {
-                return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, decltype(W)::value, PATH>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+                return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, decltype(W)::value, PATH, TRAJ>>(grid, block, lds_bytes, stream, dspec, *a, *x);
             });
         });
     });

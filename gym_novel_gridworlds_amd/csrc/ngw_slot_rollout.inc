@@ -4,6 +4,7 @@
 #include "ngw_lean.inc"            // lean_body and its table fetches
 #include "ngw_expand.inc"          // expand_move_row: the row mover
 #include "ngw_path.inc"            // the PATH form's keys and step limits
+#include "ngw_traj.inc"            // the TRAJ form's per-step rewards and lidar rows
 
 namespace {
 //
@@ -35,8 +36,12 @@ namespace {
 // plan read is used, a cut pair is not `ended` -, and x.keys takes the key of the state after every executed step (ngw_path.inc), 0 for the
 // others, 64 lanes on consecutive addresses.  PATH = false is the kernel as it was.
 //
+// TRAJ (ngw_snapshot_rollout_traj; a PATH form): x.rewards and x.obs take the reward and the LidarInFront rows of every step as ngw_traj.inc lays
+// them out - 0 / zero rows for a step the pair did not execute; with x.obs the launch block is the stand-alone lidar launch's layout and every
+// lane of the wave reaches every row set (the loop is wave-uniform).  TRAJ = false is the kernel as it was.
+//
 // x.actions: int32, the action of pair j at step t at [t * x.stride + j] (stride >= count): 64 lanes read consecutive addresses.
-template <int VEC, bool EXT, bool PATH = false>
+template <int VEC, bool EXT, bool PATH = false, bool TRAJ = false>
 __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevSpec* __restrict__ dspec, const NgwLaunch a, const NgwSlotRollout x) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t tid = threadIdx.x;
@@ -78,6 +83,8 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
         const int sj = __builtin_amdgcn_ds_bpermute(j << 2, sic);
         expand_move_row<VEC, true>(x.src.map + (size_t)sj * (size_t)S2, x.src.inv + (size_t)sj * (size_t)K, lds_map + j * MSdw, lds_inv + j * KP, S2, K, g);
     }
+    if constexpr (TRAJ)
+        if (x.obs) traj_obs_begin(a, lds, tid);
     __syncthreads();
     // ---- 2. up to n_steps steps of this lane's row
     int8_t* const mp = reinterpret_cast<int8_t*>(lds_map) + tid * a.MS;
@@ -97,6 +104,12 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
         pa.kout = x.keys && inside ? x.keys + pair : nullptr;
         pa.kdone = 0;
         if (x.keys) pa.pk = path_begin(lds_map + tid * MSdw, inv, lds + x.off_shadow + tid * KP, S2, K, x.fields, episode);
+    }
+    TrajLane<TRAJ> tr;
+    if constexpr (TRAJ) {
+        tr.rew = x.rewards && inside ? x.rewards + pair : nullptr;
+        tr.done = 0;
+        if (x.obs) traj_obs_rows(a, lds, tid, ok, mp, S, r, c, f, inv, x.obs, x.obs_stride, 0);   // row block 0: the parents
     }
     for (int s = 0; s < n_steps; s++) {
         if constexpr (PATH) alive = alive && s < pa.limit;
@@ -120,6 +133,11 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
                 if (pa.kout) pa.kout[(int64_t)s * x.keys_stride] = alive ? key : 0ull;
                 pa.kdone = s + 1;
             }
+        if constexpr (TRAJ) {                                                      // (`alive` still says: this pair executed this step)
+            if (tr.rew) tr.rew[(int64_t)s * x.rewards_stride] = alive ? o.reward : 0;
+            if (x.obs) traj_obs_rows(a, lds, tid, alive, mp, S, r, c, f, inv, x.obs, x.obs_stride, s + 1);
+            tr.done = s + 1;
+        }
         if (alive) {                                                               // (an invalid id: reward 0, info 0, not an end - lean_epilogue)
             ret += o.reward; len += 1; info = o.info;
             if (o.ended) { ended = 1; alive = false; }                             // the ending step counts; no reset runs, the pair is over
@@ -129,6 +147,11 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
     if constexpr (PATH)
         if (pa.kout)
             for (int s = pa.kdone; s < n_steps; s++) pa.kout[(int64_t)s * x.keys_stride] = 0ull;   // the steps no pair of this wave executed
+    if constexpr (TRAJ) {
+        if (tr.rew)
+            for (int s = tr.done; s < n_steps; s++) tr.rew[(int64_t)s * x.rewards_stride] = 0;
+        if (x.obs) traj_zero_tiles(a, tid, x.obs, x.obs_stride, tr.done, n_steps);
+    }
     __syncthreads();
     // ---- 3. the end states to their slots with the scalars (where they are kept), the reports
     if (keep) {
@@ -156,16 +179,19 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
     if (flags) atomicOr(a.b.flags, flags);
 }
 
-// a = the handle's rollout layout with a.autoreset, a.horizon; one wave per 64 pairs.  PATH: lds_bytes = NGW_PATH_LDS_BYTES(the handle's, KP)
-template <bool PATH>
+// a = the handle's rollout layout with a.autoreset, a.horizon; one wave per 64 pairs.  PATH: lds_bytes = NGW_PATH_LDS_BYTES(the handle's, KP).
+// TRAJ: as PATH, or with x->obs the stand-alone lidar launch's layout (ngw_device.h, ngw_slot_rollout_traj_launch)
+template <bool PATH, bool TRAJ = false>
 hipError_t slot_rollout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream) {
     if (!slot_step_args_ok(a, x) || x->stride < x->count || !x->actions ||
-        (PATH && !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes)))
+        (PATH && !TRAJ && !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes)) ||
+        (TRAJ && !traj_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes, x->rewards, x->rewards_stride, nullptr, 0, x->obs,
+                               x->obs_stride)))
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks_for(x->count)), block(NGW_EPB);
     return with_row_piece(a->S2, [&](auto V) {
         return with_flag(ext != 0, [&](auto E) {
-            return launch_kernel<ngw_slot_rollout_kernel<decltype(V)::value, decltype(E)::value, PATH>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+            return launch_kernel<ngw_slot_rollout_kernel<decltype(V)::value, decltype(E)::value, PATH, TRAJ>>(grid, block, lds_bytes, stream, dspec, *a, *x);
         });
     });
 }

@@ -19,6 +19,7 @@ import numpy as np
 
 from . import spaces
 from .spec import DIRECTION_ID, DIRECTION_STR, STEP_COSTS, EnvSpec
+from .playout import traj_keywords
 from .state_keys import KEY_STATE
 from .vec_env import PLACEMENT_MESSAGE, VecNovelGridworld
 
@@ -333,14 +334,17 @@ class _NovelGridworldEnv(_EnvBase):
         s = vec.sample_actions(np.asarray(weights)[None], seed, t=t)
         return int(s.action[0]), float(s.mass[0]), int(s.mask_words[0])
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None):
         """P = n_playouts valid-action random playouts of up to `steps` steps from the current state, without taking a step: a Playout of
         'ret' int32, 'length' int32, 'ended' bool, 'info' uint32 and 'first_action' int32, each [P]; playout q is pair q of the stream of
         `seed`; see VecNovelGridworld.playouts.  path_keys=True: a PlayoutPath, whose 'keys' [steps, P] hold the key under `fields` of the
-        state each playout is in after every executed step (0 for the others)."""
+        state each playout is in after every executed step (0 for the others).  rewards / masks / observe='lidar': a PlayoutTraj with
+        'rewards' [steps, P], 'masks' [steps, P] and 'obs' [steps + 1, P, row] (VecNovelGridworld.playouts; the lidar must be configured on the
+        batched backend)."""
         vec = self._backend()
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
         path = dict(path_keys=True, fields=fields) if path_keys else {}
+        path.update(traj_keywords(rewards, masks, observe))
         return vec.playouts(n_playouts, steps, seed, device=device, weights=weights, **path).row(0)
 
     def state_key(self, fields=KEY_STATE):

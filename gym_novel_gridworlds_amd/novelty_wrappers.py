@@ -7,6 +7,7 @@ Accepts a single-env adapter (envs.py) - returns a wrapper that forwards reads t
 `VecNovelGridworld` / `ShardedVecNovelGridworld`, which is rebuilt IN PLACE on the edited spec and returned (the
 reference's wrappers mutate the env they wrap; a shard keeps its place in the global env index space)."""
 from .novelty import apply_novelty
+from .playout import traj_keywords
 from .state_keys import KEY_STATE
 
 
@@ -53,8 +54,9 @@ class NoveltyWrapper(object):
     def evaluate_plans(self, plans, device=False, copy=False):
         return self.env.evaluate_plans(plans, device=device, copy=copy)
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None):
         path = dict(path_keys=True, fields=fields) if path_keys else {}
+        path.update(traj_keywords(rewards, masks, observe))
         return self.env.playouts(n_playouts, steps, seed, device=device, weights=weights, **path)
 
     def sample_action(self, weights, seed, t=0):

@@ -72,6 +72,58 @@ class PlayoutPath(collections.namedtuple('PlayoutPath', 'ret length ended info f
         return PlayoutPath(*[x[i] for x in self[:5]], None if a is None else a[:, i], self.keys[:, i])
 
 
+def traj_keywords(rewards, masks, observe):
+    """The trajectory keywords a forwarding playouts() passes on: only those that are switched on, so a call without them is the call it always was."""
+    kw = {}
+    if rewards:
+        kw['rewards'] = True
+    if masks:
+        kw['masks'] = True
+    if observe is not None:
+        kw['observe'] = observe
+    return kw
+
+
+def map_obs(obs, fn):
+    """fn applied to the observation rows of a trajectory result: one array, or the (beams, inventory) pair of the packed lidar format; None stays None."""
+    if obs is None:
+        return None
+    return tuple(fn(x) for x in obs) if isinstance(obs, tuple) else fn(obs)
+
+
+class PlayoutTraj(collections.namedtuple('PlayoutTraj', 'ret length ended info first_action actions keys rewards masks obs')):
+    """What playout() / playouts() return with rewards=True, masks=True or observe='lidar': PlayoutPath's fields ('keys' None without
+    path_keys) and, each None where it was not asked for,
+      'rewards' int32 [T, count] ([T, N, P]; [T, P]): the reward of step t of pair j, 0 for a step it did not execute - rewards.sum(0) == ret;
+      'masks'   uint64 [T, count] (a torch int64 tensor over the same bits): the valid-action word the choice of step t was made under, after
+                the "no action would succeed -> every action" replacement, 0 for a step not executed - choose_actions(masks[t], seed, pairs, t, A)
+                is actions[t];
+      'obs'     [T + 1, count, row] ([T + 1, N, P, row]; [T + 1, P, row]) in the env's lidar format, as Snapshot.lidar_observation returns rows
+                (the packed format: the pair (beams uint8, inventory int16)): obs[0] the parents, obs[t + 1] the state step t leaves (before any
+                reset), all-zero rows for steps not executed.  (obs[t], actions[t], rewards[t], obs[t + 1]) is a transition for t < length;
+                snapshot.transitions(result) lists those (t, j)."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    goal = Playout.goal
+    died = Playout.died
+
+    def shaped(self, *shape):
+        """The per-pair fields reshaped to `shape`, the per-step fields to [T, *shape], the rows to [T + 1, *shape, row]."""
+        def steps(x):
+            return None if x is None else x.reshape(x.shape[0], *shape)
+        return PlayoutTraj(*[x.reshape(*shape) for x in self[:5]], steps(self.actions), steps(self.keys), steps(self.rewards), steps(self.masks),
+                           map_obs(self.obs, lambda x: x.reshape(x.shape[0], *shape, x.shape[-1])))
+
+    def row(self, i):
+        """Env i's rows of an [N, P] result (the single-env adapter's view)."""
+        def steps(x):
+            return None if x is None else x[:, i]
+        return PlayoutTraj(*[x[i] for x in self[:5]], steps(self.actions), steps(self.keys), steps(self.rewards), steps(self.masks), map_obs(self.obs, steps))
+
+
 def philox4x32_10(counter, key):
     """Philox4x32-10 over arrays: counter = four uint32 arrays (broadcastable), key = two -> the four output words, uint32 arrays."""
     c0, c1, c2, c3 = [np.asarray(x, np.uint64) & _LO for x in np.broadcast_arrays(*counter)]

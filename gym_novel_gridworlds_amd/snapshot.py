@@ -373,6 +373,86 @@ def fresh_steps(fresh):
     return divmod(np.flatnonzero(np.asarray(fresh).reshape(-1)), n)
 
 
+def transitions(result):
+    """The (step t, pair j) of every step a rollout / playout result executed - t < length[j] -, in row-major order (all pairs of step 0, then of
+    step 1, ...): numpy arrays (int64), or torch tensors for a result on the device.  With them a dataset is three gathers:
+    obs[t, j], actions[t, j], rewards[t, j] -> obs[t + 1, j] (an [N, P] result: j numbers its pairs row-major, reshape the fields to [T, N * P]).
+    T is read off the first per-step field the result holds."""
+    length = result.length
+    steps = None
+    for name in ('rewards', 'masks', 'keys', 'actions', 'obs'):
+        x = getattr(result, name, None)
+        if x is not None:
+            x = x[0] if isinstance(x, tuple) else x
+            steps = int(x.shape[0]) - (1 if name == 'obs' else 0)
+            break
+    if steps is None:
+        raise ValueError("transitions: the result holds no per-step field")
+    if hasattr(length, 'data_ptr'):
+        import torch
+        ran = torch.arange(steps, device=length.device)[:, None] < length.reshape(1, -1)
+        pos = torch.nonzero(ran.reshape(-1)).reshape(-1)
+        n = max(int(length.numel()), 1)
+        return torch.div(pos, n, rounding_mode='floor'), pos % n
+    length = np.asarray(length).reshape(-1)
+    ran = np.arange(steps)[:, None] < length[None, :]
+    return divmod(np.flatnonzero(ran.reshape(-1)), max(int(length.size), 1))
+
+
+def check_observe(env, observe):
+    """The `observe` keyword of a rollout / playout: None, or 'lidar' on an env with a lidar configured."""
+    if observe is None:
+        return False
+    if observe != 'lidar':
+        raise ValueError("observe: None or 'lidar' expected, got %r" % (observe,))
+    if env.lidar is None:
+        refused = getattr(env, 'lidar_refused', None)    # (lidar_configure found the maps too large for the observation's LDS layout, and said so)
+        if refused:
+            raise MapsTooLarge("map_size %d: observe='lidar' keeps a wavefront's 64 maps in the lidar observation's LDS layout, which this env cannot "
+                               "hold - %s; rewards / masks alone keep the path form's limit" % (env.map_size, refused))
+        raise ValueError("observe='lidar' before env.lidar_configure (LidarInFront)")
+    return True
+
+
+def traj_outputs(env, dev, rewards, masks, observe, count, steps):
+    """What a trajectory call adds to a path call -> (rewards int32 [steps, count] or None, masks int64 [steps, count] or None, the row buffer
+    [steps + 1, count rounded up to 64, row] or None - a wave stores whole 64-row tiles, as in lidar_observation -, its stride in rows).  Only what
+    was asked for is allocated; the rows take (steps + 1) * pad * row bytes of device memory."""
+    import torch
+    rew = torch.zeros((steps, count), dtype=torch.int32, device=dev) if rewards else None
+    msk = torch.zeros((steps, count), dtype=torch.int64, device=dev) if masks else None
+    rows, pad = None, (count + 63) // 64 * 64
+    if observe:
+        if env.lidar_packed:
+            shape, dtype = (steps + 1, pad, env.lidar_row_bytes), torch.uint8
+        else:
+            shape, dtype = (steps + 1, pad, env.lidar_len), torch.int32 if env.lidar_dtype == np.dtype(np.int32) else torch.int16
+        rows = torch.empty(shape, dtype=dtype, device=dev)           # (every row of every block is written: whole tiles)
+    return rew, msk, rows, pad
+
+
+def traj_results(env, rew, msk, rows, count, device):
+    """The three buffers as the result's fields: on the device as they are (the rows cut to `count` per block), else numpy; packed rows split."""
+    if rows is not None:
+        rows = rows[:, :count]
+    if not device:
+        rew = None if rew is None else rew.cpu().numpy()
+        msk = None if msk is None else msk.cpu().numpy().view(np.uint64)
+        rows = None if rows is None else rows.cpu().numpy()
+    if rows is not None and env.lidar_packed:            # (env._lidar_split, over the last axis)
+        beams, tail = rows[..., :env.lidar.num_beams * len(env.lidar.lidar_items_id)], rows[..., env._lidar_inv_off:]
+        if isinstance(tail, np.ndarray):
+            rows = (beams, tail.view(np.int16))
+        else:
+            import torch
+            rows = (beams, tail.view(torch.int16))
+    return rew, msk, rows
+
+
+def _ptr(x, count):
+    return C.c_void_p(x.data_ptr()) if x is not None and count else None
+
+
 def path_outputs(dev, limits, path_keys, fields, count, steps):
     """What a path call adds to a plain one -> (the checked limits, the fields word, the keys tensor [steps, count] int64 or None)."""
     import torch
@@ -393,14 +473,16 @@ def path_call(env, holder, call, count, uploaded, device):
 
 
 def playout_call(env, holder, src, dst, parents, children, count, steps, seed, first_pair, record, device, weights=None, limits=None, path_keys=False,
-                 fields=None):
+                 fields=None, rewards=False, masks=False, observe=None):
     """The one launch behind Snapshot.playout and VecNovelGridworld.playouts: src / dst are snapshots' C handles (src None: the envs' current
     states; dst None: nothing is kept), parents / children the checked lists (check_playout); `holder` keeps the uploaded lists alive.
     weights: None (the uniform rule), or one float32 per action from the host or the device (sample.check_weights).
     -> Playout of [count] fields, actions [steps, count] with `record`.  limits / path_keys / fields: the path form (Snapshot.playout);
-    with path_keys a PlayoutPath."""
+    with path_keys a PlayoutPath.  rewards / masks / observe: the trajectory form (Snapshot.playout): a PlayoutTraj; `observe` has been through
+    check_observe at the caller (before it touched a handle)."""
     import torch
-    from .playout import Playout, PlayoutPath
+    from .playout import Playout, PlayoutPath, PlayoutTraj
+    traj = observe is not None or bool(rewards) or bool(masks)
     seed, first_pair = int(seed), int(first_pair)
     if not 0 <= seed < 1 << 64:
         raise ValueError("seed: %d outside [0, 2^64)" % seed)
@@ -423,7 +505,15 @@ def playout_call(env, holder, src, dst, parents, children, count, steps, seed, f
     out = [C.c_void_p(x.data_ptr()) for x in (ret, length, ended, info, first)]
     recorded = C.c_void_p(actions.data_ptr()) if record and count else None
     keys = None
-    if limits is not None or path_keys:
+    if traj:
+        lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
+        (lim_ptr,), up = upload(dev, count, lim)
+        uploaded = uploaded + up
+        rew, msk, rows, pad = traj_outputs(env, dev, rewards, masks, observe is not None, count, steps)
+        call = lambda: _cabi.lib().ngw_snapshot_playout_traj(   # noqa: E731
+            env._h, src, ptr[0], int(count), steps, seed, first_pair, None if wt is None else C.c_void_p(wt.data_ptr()), lim_ptr, dst, ptr[1], *out, recorded,
+            int(count), f, _ptr(keys, count), int(count), _ptr(rew, count), int(count), _ptr(msk, count), int(count), _ptr(rows, count), int(pad))
+    elif limits is not None or path_keys:
         lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
         (lim_ptr,), up = upload(dev, count, lim)
         uploaded = uploaded + up
@@ -435,15 +525,21 @@ def playout_call(env, holder, src, dst, parents, children, count, steps, seed, f
     else:
         call = lambda: _cabi.lib().ngw_snapshot_playout_weighted(env._h, src, ptr[0], int(count), steps, seed, first_pair, C.c_void_p(wt.data_ptr()), dst,   # noqa: E731
                                                                  ptr[1], *out, recorded, int(count))
-    if limits is not None or path_keys:
+    if traj or limits is not None or path_keys:
         path_call(env, holder, call, count, uploaded, device)
     else:
         enqueue_ordered(env, holder, call, count, uploaded, device)
+    if traj and count == 0 and rows is not None:
+        rows.zero_()
     if device:
         play = Playout(ret, length, ended.view(torch.bool), info, first, actions)
+        if traj:
+            return PlayoutTraj(*play, keys, *traj_results(env, rew, msk, rows, count, True))
         return play if keys is None else PlayoutPath(*play, keys)
     play = Playout(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32), first.cpu().numpy(),
                    None if actions is None else actions.cpu().numpy())
+    if traj:
+        return PlayoutTraj(*play, None if keys is None else keys.cpu().numpy().view(np.uint64), *traj_results(env, rew, msk, rows, count, False))
     return play if keys is None else PlayoutPath(*play, keys.cpu().numpy().view(np.uint64))
 
 
@@ -604,7 +700,8 @@ class Snapshot:
         p, a, c, shape = all_actions_pairs(parents, first_child, self.env.n_actions)
         return self.expand(p, a, c, from_envs=from_envs, source=source, device=device).reshape(*shape)
 
-    def rollout(self, parents, plans, children=None, from_envs=False, source=None, device=False, limits=None, path_keys=False, fields=KEY_STATE):
+    def rollout(self, parents, plans, children=None, from_envs=False, source=None, device=False, limits=None, path_keys=False, fields=KEY_STATE,
+                rewards=False, masks=False, observe=None):
         """Pair j: the state of parent parents[j] stepped on a private copy with the T actions of plans[j], by the rules evaluate_plans()
         applies - every novelty, the env's autoreset setting and horizon; it stops at the first step that ends the episode (goal, FireWall
         death, the horizon under autoreset), that step counts, and no reset ever runs.  Returns a PlanEval of 'ret' int32 (sum of the
@@ -630,10 +727,22 @@ class Snapshot:
         path_keys=True: a RolloutPath, whose 'keys' [T, count] hold the key under `fields` (state_keys; what keys() returns for the child
         the pair would leave had it stopped there) of the state after every executed step and 0 for the others - uint64, or an int64 tensor
         with device=True.  Flattened it is what KeyTable.insert takes; fresh_steps() maps `fresh` back to (t, j), and a rollout of the same
-        plans with limits = t + 1 materialises that state.  Maps the path form cannot hold raise MapsTooLarge."""
+        plans with limits = t + 1 materialises that state.  Maps the path form cannot hold raise MapsTooLarge.
+        rewards=True / observe='lidar': a RolloutTraj - the fields above ('keys' None without path_keys), 'rewards' int32 [T, count] (the reward
+        of step t of pair j, 0 for a step it did not execute; rewards.sum(0) == ret) and 'obs' [T + 1, count, row]: LidarInFront rows in the
+        env's configured format, as lidar_observation() returns them (the packed format: the pair (beams, inventory)) - obs[0] the parents,
+        obs[t + 1] the state step t leaves, before any reset (the last row of an ended pair is the state its episode ended in), all-zero rows
+        for steps not executed.  (obs[t], plans[j, t], rewards[t], obs[t + 1]) is a transition for t < length[j]; transitions() lists them.
+        Still one kernel launch and no row leaves the chip's local memory; the rows take (T + 1) * count (rounded up to 64) * row bytes of
+        device memory - 65 536 pairs of 64 steps with 80-byte rows are 340 MB - and only what is asked for is allocated.  observe needs
+        env.lidar_configure (ValueError otherwise); maps its layout cannot hold raise MapsTooLarge while rewards=True alone keeps the path
+        form's limit.  A parent index out of range gives zeros in both fields, obs[0] included.  masks=True is a playout's keyword: ValueError."""
         import torch
-        from .vec_env import PlanEval, RolloutPath
+        from .vec_env import PlanEval, RolloutPath, RolloutTraj
         env = self.env
+        if masks:
+            raise ValueError("masks=True: a rollout makes no choice, so there is no mask word to record (playout() records them)")
+        traj = check_observe(env, observe) or bool(rewards)
         src, n_parents, same_buffer = self._source(source, from_envs, 'rollout')
         dev = torch.device('cuda:%d' % env.device)
         if isinstance(plans, torch.Tensor):
@@ -651,6 +760,21 @@ class Snapshot:
         ended = torch.zeros(count, dtype=torch.uint8, device=dev)
         info = torch.zeros(count, dtype=torch.int32, device=dev)
         keys = None
+        if traj:
+            lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
+            (lim_ptr,), up = upload(dev, count, lim)
+            rew, _, rows, pad = traj_outputs(env, dev, rewards, False, observe is not None, count, steps)
+            path_call(env, self, lambda: _cabi.lib().ngw_snapshot_rollout_traj(
+                env._h, src, ptr[0], ptr[1], int(count), steps, lim_ptr, None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
+                C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr()), f, _ptr(keys, count), int(count),
+                _ptr(rew, count), int(count), _ptr(rows, count), int(pad)), count, uploaded + up, device)
+            if count == 0 and rows is not None:
+                rows.zero_()
+            rew, _, rows = traj_results(env, rew, None, rows, count, device)
+            if device:
+                return RolloutTraj(ret, length, ended.view(torch.bool), info, keys, rew, rows)
+            return RolloutTraj(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32),
+                               None if keys is None else keys.cpu().numpy().view(np.uint64), rew, rows)
         if limits is None and not path_keys:    # (the call as it always was)
             enqueue_ordered(env, self, lambda: _cabi.lib().ngw_snapshot_rollout(
                 env._h, src, ptr[0], ptr[1], int(count), steps, None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
@@ -669,7 +793,7 @@ class Snapshot:
         return ev if keys is None else RolloutPath(*ev, keys.cpu().numpy().view(np.uint64))
 
     def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False, weights=None,
-                limits=None, path_keys=False, fields=KEY_STATE):
+                limits=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None):
         """Pair j: the state of parent parents[j] stepped on a private copy up to `steps` times by rollout()'s rules, with a random policy in
         the place of a plan: at every step the action is drawn uniformly among the actions that would succeed from the state the pair is in
         (every action where none would) - the default-policy simulation of a tree search's leaf, in one kernel launch.  The draw is the
@@ -688,12 +812,22 @@ class Snapshot:
         sample.choose_weighted(..., words=playout.playout_words(...)) computes on the host.  A bad weight raises F_BAD_WEIGHT.
         limits, path_keys, fields: as in rollout().  The draws depend on (seed, pair, step) and the state only, so a limited playout is the
         prefix of the unlimited one, and the recorded actions beyond the limit are -1.  With path_keys=True a PlayoutPath: the Playout
-        fields and 'keys' [steps, count]."""
+        fields and 'keys' [steps, count].
+        rewards=True / masks=True / observe='lidar': a PlayoutTraj - the fields above ('keys' None without path_keys), 'rewards' and 'obs' as
+        rollout() defines them, and 'masks' uint64 [steps, count] (a torch int64 tensor over the same bits): the valid-action word the choice
+        of step t was made under, after the "no action would succeed -> every action" replacement, 0 for a step not executed - so
+        playout.choose_actions(masks[t], seed, first_pair + arange(count), t, A) is actions[t], and sample.choose_weighted does the same for a
+        weighted playout: what a learner stores to recompute masked log-probabilities.  The memory, the refusals and the zero rows are
+        rollout()'s."""
         import torch
         env = self.env
+        check_observe(env, observe)
         src, n_parents, same_buffer = self._source(source, from_envs, 'playout')
         dev = torch.device('cuda:%d' % env.device)
         p, c, count, steps = check_playout(parents, steps, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'playout', x))
+        if rewards or masks or observe is not None:
+            return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights, limits=limits,
+                                path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe)
         if limits is None and not path_keys:    # (the call as it always was)
             return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights)
         return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights, limits=limits,

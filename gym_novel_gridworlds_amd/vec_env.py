@@ -102,6 +102,20 @@ class RolloutPath(collections.namedtuple('RolloutPath', 'ret length ended info k
     died = PlanEval.died
 
 
+class RolloutTraj(collections.namedtuple('RolloutTraj', 'ret length ended info keys rewards obs')):
+    """What Snapshot.rollout(rewards=True / observe='lidar') returns: RolloutPath's fields ('keys' None without path_keys) and, each None where
+    it was not asked for, 'rewards' int32 [T, count] (the reward of step t of pair j, 0 for a step it did not execute: rewards.sum(0) == ret) and
+    'obs' [T + 1, count, row] in the env's lidar format (obs[0] the parents, obs[t + 1] the state step t leaves, zero rows for steps not executed;
+    the packed format: the pair (beams, inventory)) - see playout.PlayoutTraj."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    goal = PlanEval.goal
+    died = PlanEval.died
+
+
 class StepInfo(dict):
     """info of a batched step: 'result' bool[N], 'step_cost_code', 'message_code', 'message_arg' - and 'step_cost' f64[N].  Fields
     that are not there yet are made when they are first asked for: 'step_cost' is looked up from the codes (a 65 536-element
@@ -874,7 +888,16 @@ class VecNovelGridworld:
         self.lidar = lidar_config if lidar_config is not None else LidarConfig(self.spec, num_beams)
         self._lidar_c = self.lidar.compile(self.spec)
         L = _cabi.lib()
-        _cabi.check(L.ngw_lidar_configure(self._h, C.byref(self._lidar_c)))
+        self.lidar_refused = None
+        try:
+            _cabi.check(L.ngw_lidar_configure(self._h, C.byref(self._lidar_c)))
+        except ValueError as e:
+            self.lidar = None                                 # (not configured: nothing below ran)
+            if ' B of LDS' in str(e):                         # the maps do not fit the observation's LDS layout: the handle cannot serve it
+                from .snapshot import MapsTooLarge
+                self.lidar_refused = str(e)
+                raise MapsTooLarge(str(e)) from None
+            raise
         self.lidar_len = self.lidar.obs_len(self.spec)
         self.lidar_packed = isinstance(dtype, str) and dtype == 'packed'
         self.lidar_dtype = np.dtype(np.uint8) if self.lidar_packed else np.dtype(dtype)
@@ -1049,7 +1072,7 @@ class VecNovelGridworld:
         self.step_device(s.action.data_ptr())
         return s
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None):
         """P = n_playouts valid-action random playouts of up to `steps` steps from every env's CURRENT state, without taking a step and
         without a snapshot of the caller's: Snapshot.playout(from_envs=True) with the parents repeat(arange(N), P).  Returns a Playout whose
         fields are [N, P] ('actions' is None: Snapshot.playout records them).  Playout q of env i is pair (env_index_base + i) * P + q of the
@@ -1057,9 +1080,12 @@ class VecNovelGridworld:
         unsharded env returns.  One kernel launch; nothing is committed.  device=True: torch tensors on the env's device, ordered behind
         the launch on torch's current stream.  weights: float32 [A] (host or device) - every step's action is then drawn with probability
         proportional to them among the valid ones (Snapshot.playout).  path_keys=True: a PlayoutPath whose 'keys' [T, N, P] hold the key
-        under `fields` (default KEY_STATE) of the state every playout is in after each executed step, 0 for the others (Snapshot.playout)."""
+        under `fields` (default KEY_STATE) of the state every playout is in after each executed step, 0 for the others (Snapshot.playout).
+        rewards=True / masks=True / observe='lidar': a PlayoutTraj with 'rewards' [T, N, P], 'masks' [T, N, P] and 'obs' [T + 1, N, P, row] - every
+        step's reward, the mask word its choice was made under and the LidarInFront rows before and after it (Snapshot.playout; obs takes
+        (T + 1) * N * P rows of device memory)."""
         import torch
-        from .snapshot import check_playout, playout_call
+        from .snapshot import check_observe, check_playout, playout_call
         P = int(n_playouts)
         if P < 1:
             raise ValueError("n_playouts: at least one playout per env expected, got %d" % P)
@@ -1067,6 +1093,10 @@ class VecNovelGridworld:
         dev = torch.device('cuda:%d' % self.device)
         parents = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(P).contiguous()
         _, _, count, steps = check_playout(parents, steps, None, N, 0, False, lambda x: None if x is None else int(x.numel()))
+        check_observe(self, observe)
+        if rewards or masks or observe is not None:
+            return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights,
+                                path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe).shaped(N, P)
         if not path_keys:                       # (the call as it always was)
             return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights).shaped(N, P)
         return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights,

@@ -15,6 +15,7 @@ import numpy as np
 
 from . import spaces
 from .novelty_wrappers import NoveltyWrapper
+from .playout import traj_keywords
 from .state_keys import KEY_STATE
 from .vec_env import VecNovelGridworld
 
@@ -174,12 +175,14 @@ class LimitActions(NoveltyWrapper):
         word = sum(1 << ids[i] for i in range(len(ids)) if (int(s.mask_words[0]) >> i) & 1)
         return ids[int(s.action[0])], float(s.mass[0]), word
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None):
         """The env's playouts under this wrapper's action list: at every step the action is drawn among the LIMITED actions that would
         succeed (every limited action where none would), and 'first_action' holds limited ids.  The draw needs the limited list as the
         kernel's own action table, so the playouts run on a one-env batched env whose table is the limited one (limit_actions_vec, kept
         from call to call) holding a copy of the current state; they equal what limit_actions_vec() of a batched env gives for that
-        state.  weights: one per limited id.  path_keys / fields: as on the env - the keys do not depend on the action id space."""
+        state.  weights: one per limited id.  path_keys / fields: as on the env - the keys do not depend on the action id space.
+        rewards / masks / observe: as on the env; bit i of a mask word is limited id i, consistent with the actions reported here.  observe needs
+        the lidar configured on the adapter's batched backend (the limited env takes its configuration over)."""
         limited, ids = self._limited_env()
         if weights is not None and not hasattr(weights, 'device'):
             w = np.asarray(weights)
@@ -190,9 +193,19 @@ class LimitActions(NoveltyWrapper):
             import torch
             weights = weights[torch.tensor(ids, device=weights.device)].contiguous()
         path = dict(path_keys=True, fields=fields) if path_keys else {}
+        path.update(traj_keywords(rewards, masks, observe))
+        if observe is not None:                              # the rows are the backend's: its lidar as it is configured NOW, not as it was when the limited env was made
+            vec = self.unwrapped._backend()
+            mine, theirs = [(e.lidar, e.lidar_packed, e.lidar_dtype) for e in (limited, vec)]
+            if vec.lidar is not None and mine != theirs:
+                limited.lidar_configure(vec.lidar, fused=False, dtype='packed' if vec.lidar_packed else vec.lidar_dtype)
+            elif vec.lidar is None:
+                limited.lidar = None                         # (observe then raises what it raises on the env)
         play = limited.playouts(n_playouts, steps, seed, device=device, weights=weights, **path).row(0)
         if ids == list(range(len(ids))):
             return play
+        if masks:                                            # (the kernel's bit i is this wrapper's bit ids[i])
+            play = play._replace(masks=limit_mask_words(play.masks, ids))
         if device:                                           # (a table of its own, set_limited_actions_id: the kernel's id i is this wrapper's ids[i])
             import torch
             lut = torch.tensor(ids, dtype=play.first_action.dtype, device=play.first_action.device)
@@ -248,10 +261,18 @@ def limit_mask_columns(inner, limited_actions_id, actions_id, n, dtype=bool):
     return out
 
 
-def limit_actions_vec(venv, limited_actions):
-    """Batched form: a new VecNovelGridworld whose action ids ARE the limited ids (LUT edit, no translation pass)."""
-    assert isinstance(venv, VecNovelGridworld)
-    spec = copy.deepcopy(venv.spec)
+def limit_mask_words(words, ids):
+    """Mask words of an env whose action i is a wrapper's limited id ids[i] -> the words in the wrapper's id space (bit i moves to bit ids[i]).
+    numpy uint64, or torch int64 over the same bits."""
+    out = words * 0
+    for i, j in enumerate(ids):
+        out = out | (((words >> i) & 1) << j)
+    return out
+
+
+def limited_spec(spec, limited_actions):
+    """A copy of `spec` whose action list is `limited_actions` in sorted order: limit_actions_vec's spec edit."""
+    spec = copy.deepcopy(spec)
     limited = {action: i for i, action in enumerate(sorted(limited_actions))}
     for action in limited:
         assert action in spec.actions_id, action + " is not a valid action for " + spec.env_id
@@ -261,6 +282,13 @@ def limit_actions_vec(venv, limited_actions):
     spec.craft_actions_id = {a: i for a, i in limited.items() if a.startswith('Craft_')}
     spec.select_actions_id = {a: i for a, i in limited.items() if a.startswith('Select_')}
     spec.action_space_n = len(limited)
+    return spec
+
+
+def limit_actions_vec(venv, limited_actions):
+    """Batched form: a new VecNovelGridworld whose action ids ARE the limited ids (LUT edit, no translation pass)."""
+    assert isinstance(venv, VecNovelGridworld)
+    spec = limited_spec(venv.spec, limited_actions)
     # (the prepared-episode settings travel as the caller CHOSE them: 'auto' stays adaptive on the derived env)
     new = VecNovelGridworld(spec=spec, num_envs=venv.num_envs, device=venv.device, seed=venv.seed, autoreset=venv.autoreset,
                             horizon=venv.horizon, env_index_base=venv.env_index_base, reset_prefetch=venv._prefetch_arg,

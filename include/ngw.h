@@ -774,6 +774,48 @@ int ngw_snapshot_playout_path(ngw_handle* h, ngw_snapshot* src, const int32_t* s
                               int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride, uint32_t fields, uint64_t* keys_dev,
                               int64_t keys_stride);
 
+/* Trajectories: ngw_snapshot_rollout_path / ngw_snapshot_playout_path that also record every step of every pair - the reward, the mask word the
+ * choice was made under, and the LidarInFront observation before and after it - so that the runs of a search are a dataset (behaviour cloning,
+ * offline RL, value targets, a world model) without replaying them one step at a time through saved slots.  All arrays are device memory; each is
+ * recorded only where its pointer is not NULL.  A pair EXECUTES step t while it is not skipped (NGW_F_BAD_INDEX), t is below its limit and no
+ * earlier step ended its episode.
+ * Rewards (rewards_dev != NULL; int32).  rewards_dev[t * rewards_stride + j], rewards_stride >= count: the reward of step t of pair j, 0 for a
+ *   step it did not execute; the column of pair j sums to ret[j].  Exactly [t * rewards_stride, t * rewards_stride + count) of every step row
+ *   t < n_steps is written.
+ * Masks (masks_dev != NULL; uint64; playouts).  masks_dev[t * masks_stride + j], masks_stride >= count: the valid-action word m of the state pair j
+ *   was in before step t, AFTER rule 1's replacement (all n_actions bits where no action would succeed) - the word the choice rule of
+ *   ngw_snapshot_playout / rules 3 - 6 of ngw_sample_actions were applied to, so the rule on (m, seed, first_pair + j, t) reproduces the recorded
+ *   action.  0 for a step the pair did not execute.  Written like the rewards.
+ * Observations (obs_dev != NULL).  Rows of the handle's current lidar format (ngw_lidar_row_layout: row_bytes each; packed, int16 or int32), the
+ *   rows ngw_snapshot_lidar returns for a slot holding that state.  Row numbering: the buffer is n_steps + 1 ROW BLOCKS of obs_stride rows;
+ *   row j of block 0 is the observation of the parent of pair j, row j of block t + 1 the observation of the state step t leaves - before any
+ *   reset, as every slot call defines a child: the last non-zero row of an ended pair shows the state its episode ended in.  A row is all zeros
+ *   for a step the pair did not execute, and in every block - block 0 included - for a skipped pair.  So (row t, action t, reward t, row t + 1)
+ *   is a transition for t < length[j].  One wavefront serves 64 consecutive pairs and stores its 64 rows of a block as ONE tile: obs_stride must
+ *   be a multiple of 64 and at least count rounded up to 64, obs_dev 16-byte aligned, and rows count .. of every block (up to the next multiple
+ *   of 64) are written with zeros; rows beyond that are not touched.  The buffer is (n_steps + 1) * obs_stride * row_bytes bytes: 65 536 pairs
+ *   of 64 steps with 80-byte rows are 340 MB.  ngw_lidar_configure must have been called; the env's own lidar rows are not touched.
+ * With the three pointers NULL the calls compute what the path calls compute.  A rollout with rewards_dev or obs_dev needs neither a destination
+ * nor a report.  Everything else - limits, keys, arguments, reports, index rules, ordering, the stream, what is committed: nothing - is the path
+ * calls'.  One kernel launch (ngw_slot_rollout.inc / ngw_playout.inc in their TRAJ form, ngw_traj.inc); no row leaves LDS.
+ * Map sizes.  Without obs_dev: the path calls' layout and limit.  With obs_dev the wavefront's 64 rows lie in the layout of the stand-alone lidar
+ *   launch (ngw_lidar / ngw_snapshot_lidar: the item tables, an 8 KiB ray table unless the rays are world-frame, the tile of 64 rows, the maps
+ *   between two guards of max_range * (S + 1) bytes, the inventories), with the 64 * (K | 1) dwords of inventory shadows behind it where keys_dev
+ *   is set too; a handle whose layout exceeds 160 KiB is refused (the message starts with "map_size" and names the bytes) while the call without
+ *   obs_dev still runs.  Every configuration up to 32 x 32 fits, in every row format.
+ * NGW_E_INVALID_ARG: what the path calls refuse; rewards_stride / masks_stride < count; obs_dev before ngw_lidar_configure, misaligned, or with
+ * an obs_stride that is no multiple of 64 or below count rounded up to 64; a layout that does not fit LDS. */
+int ngw_snapshot_rollout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
+                              const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev,
+                              uint8_t* ended_dev, uint32_t* info_dev, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev,
+                              int64_t rewards_stride, void* obs_dev, int64_t obs_stride);
+int ngw_snapshot_playout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                              const float* weights_dev /* NULL: the uniform rule */, const int32_t* limits_dev, ngw_snapshot* dst,
+                              const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev,
+                              int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride, uint32_t fields, uint64_t* keys_dev,
+                              int64_t keys_stride, int32_t* rewards_dev, int64_t rewards_stride, uint64_t* masks_dev, int64_t masks_stride, void* obs_dev,
+                              int64_t obs_stride);
+
 /* Key table: an open-addressing hash set of 64-bit keys in device memory - "have I seen this state BEFORE?" across the calls of a search that
  * runs many iterations (transposition tables, duplicate removal in breadth-first solvers, Go-Explore archives, count-based bonuses).  A table
  * belongs to the handle that created it; it stores keys and nothing else: a caller keeps what it wants per state (visit counts, the best return,
