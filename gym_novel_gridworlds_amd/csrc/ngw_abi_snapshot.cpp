@@ -57,6 +57,17 @@ int move_rows(ngw_handle* h, bool copies, const NgwSnapRows& src, int64_t src_ro
     return NGW_OK;
 }
 
+// where the rows a call reads live: a snapshot's slots, or (s == NULL) the state slab's envs.  Only behind owns(): a closed snapshot is not dereferenced
+struct Source { NgwSnapRows r; int64_t rows; const char* unit; };   // (unit: the word of the "from %lld %s" messages)
+Source source_of(const ngw_handle* h, const ngw_snapshot* s) { return s ? Source{s->r, s->cap, "slots"} : Source{state_rows(h), h->n, "envs"}; }
+
+// a key selection; with `what`, also the stride of the [step][pair] keys a path or trajectory call writes
+int key_args(uint32_t fields, const char* what = nullptr, int64_t count = 0, int64_t stride = 0) {
+    if (!fields || (fields & ~NGW_KEY_ALL)) return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)fields);
+    if (what && stride < count) return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a key stride of %lld", what, (long long)count, (long long)stride);
+    return NGW_OK;
+}
+
 // what the three slot observations check alike (before anything touches the stream)
 int slot_obs_args(const ngw_handle* h, const ngw_snapshot* s, const void* out, const int32_t* slots_dev, int64_t count, const char* what) {
     if (!h || !s || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
@@ -66,77 +77,89 @@ int slot_obs_args(const ngw_handle* h, const ngw_snapshot* s, const void* out, c
     return NGW_OK;
 }
 
-// what a rollout and a playout check alike about their pairs (before anything touches the stream): where the parents live and how many rows
-// that is (-> src_rows), where the end states go, and that the handle's maps fit the kernels' LDS layout.  what / call: "rollout", "ngw_snapshot_rollout"
+// ... and fill alike
+NgwSlotObs slot_obs(const ngw_handle* h, const ngw_snapshot* s, const int32_t* slots_dev, int64_t count) {
+    NgwSlotObs x{};
+    x.src = s->r; x.slots = slots_dev; x.flags = h->b.flags; x.count = (int32_t)count; x.rows = (int32_t)s->cap;
+    return x;
+}
+
+// what an expand, a rollout and a playout check alike about their pairs (before anything touches the stream): where the parents live (-> from),
+// where the children or end states go - count in [0, the destination's slots] -, and that the handle's maps fit the kernels' LDS layout.  A negative
+// count is an expand's to refuse here (it has a destination); rollouts and playouts have refused it before.  what / call: "rollout", "ngw_snapshot_rollout"
 int step_pairs_args(const ngw_handle* h, const ngw_snapshot* src, const int32_t* src_idx_dev, const ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count,
-                    const char* what, const char* call, int64_t* src_rows) {
+                    const char* what, const char* call, Source* from) {
     if (!dst && dst_slots_dev) return fail(NGW_E_INVALID_ARG, "destination slots without a destination snapshot");
     if ((dst && !owns(h, dst)) || (src && !owns(h, src))) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
-    *src_rows = src ? src->cap : h->n;
-    if (count > 0x7FFFFFFFll || (dst && count > dst->cap))
+    *from = source_of(h, src);
+    if (count < 0 || count > 0x7FFFFFFFll || (dst && count > dst->cap))
         return fail(NGW_E_INVALID_ARG, "%s of %lld states into a snapshot of %lld slots", what, (long long)count, (long long)(dst ? dst->cap : 0x7FFFFFFFll));
-    if (!src_idx_dev && count > *src_rows)
-        return fail(NGW_E_INVALID_ARG, "%s of %lld states from %lld %s", what, (long long)count, (long long)*src_rows, src ? "slots" : "envs");
+    if (!src_idx_dev && count > from->rows)
+        return fail(NGW_E_INVALID_ARG, "%s of %lld states from %lld %s", what, (long long)count, (long long)from->rows, from->unit);
     if (!h->general_ok)
         return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps in LDS (%s, as the fused rollouts) "
                                        "and they need more than 160 KiB; per-launch steps and resets are available", h->proto.S, call);
     return NGW_OK;
 }
 
-// the launch block of the kernels that step saved rows: the handle's rollout layout with its buffers, autoreset setting and horizon
-NgwLaunch step_block(const ngw_handle* h) {
-    NgwLaunch a = h->proto;
+// the launch block of the kernels that step saved rows: the handle's rollout layout - for an observing trajectory call the stand-alone lidar launch's
+// layout and row format - with the handle's buffers, autoreset setting and horizon
+NgwLaunch step_block(const ngw_handle* h, bool observing = false) {
+    NgwLaunch a = observing ? h->lidar_proto : h->proto;
     a.b = h->b;
+    if (observing) a.lout = nullptr;                 // (every tile goes to the caller's rows)
     a.autoreset = h->autoreset;
     a.horizon = h->horizon;
     return a;
 }
 
-// what the path forms ask for beyond a plain rollout / playout; nullptr = the plain call
-struct PathArgs {
-    const int32_t* limits;
-    uint32_t fields;
-    uint64_t* keys;
-    int64_t keys_stride;
+// what the path forms ask for beyond a plain rollout / playout, and the trajectory forms beyond those (masks: playouts)
+struct PathArgs { const int32_t* limits; uint32_t fields; uint64_t* keys; int64_t keys_stride; };
+struct TrajArgs { int32_t* rewards; int64_t rewards_stride; uint64_t* masks; int64_t masks_stride; void* obs; int64_t obs_stride; };
+// where the actions come from: a plan [n_steps][stride], or the kernel draws them (weights NULL: the uniform rule; actions NULL: not recorded)
+struct Plan { const int32_t* actions; int64_t stride; };
+struct Draw { uint64_t seed, first_pair; const float* weights; int32_t* first_action; int32_t* actions; int64_t stride; };
+
+// The one request behind the seven exported rollouts and playouts: step `count` pairs of saved rows up to n_steps times.  The form is the entry
+// point's, never read off the pointers: a path call without limits and keys is still a path call.  The entry points fill it by member name.
+enum Form { PLAIN, PATH, TRAJ };
+struct Pairs {
+    ngw_snapshot* src; const int32_t* src_idx;       // the parents: a snapshot's slots (NULL: the envs' current states), list NULL = 0 .. count-1
+    ngw_snapshot* dst; const int32_t* dst_slots;     // where the end states go (NULL: nothing is kept)
+    int64_t count; int32_t n_steps;
+    int32_t* ret; int32_t* length; uint8_t* ended; uint32_t* info;   // the four reports, any may be NULL
+    Form form; PathArgs pa; TrajArgs ta;             // (pa: PATH and TRAJ, ta: TRAJ; zeros otherwise)
+    bool draws; Plan plan; Draw draw;                // (the one `draws` names; zeros otherwise)
 };
 
-// the path arguments of one call, checked (before anything touches the stream) -> the LDS bytes of the launch
-int path_args(const ngw_handle* h, const PathArgs& pa, int64_t count, const char* what, const char* call, size_t* lds) {
-    if (pa.keys && (!pa.fields || (pa.fields & ~NGW_KEY_ALL)))
-        return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)pa.fields);
-    if (pa.keys && pa.keys_stride < count) return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a key stride of %lld", what, (long long)count, (long long)pa.keys_stride);
-    *lds = NGW_PATH_LDS_BYTES(h->lds_bytes, h->proto.KP);
-    if (*lds > NGW_PATH_LDS_MAX)
-        return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps and a second copy of their inventories in LDS (%s) and they need "
-                                       "%zu B, more than 160 KiB; the plain call is available", h->proto.S, call, *lds);
-    return NGW_OK;
-}
+// the six launchers and the entry points they serve, by where the actions come from and by form
+template <class X>
+using PairsLaunch = hipError_t (*)(const NgwDevSpec*, const NgwLaunch*, const X*, int, size_t, hipStream_t);
+const PairsLaunch<NgwSlotRollout> ROLLOUT_LAUNCH[3] = {ngw_slot_rollout_launch, ngw_slot_rollout_path_launch, ngw_slot_rollout_traj_launch};
+const PairsLaunch<NgwPlayout> PLAYOUT_LAUNCH[3] = {ngw_playout_launch, ngw_playout_path_launch, ngw_playout_traj_launch};
+const char* const PAIRS_CALL[2][3] = {{"ngw_snapshot_rollout", "ngw_snapshot_rollout_path", "ngw_snapshot_rollout_traj"},
+                                      {"ngw_snapshot_playout", "ngw_snapshot_playout_path", "ngw_snapshot_playout_traj"}};
 
-// what the trajectory forms ask for beyond the path forms; nullptr = the path (or plain) call
-struct TrajArgs {
-    int32_t* rewards;
-    int64_t rewards_stride;
-    uint64_t* masks;                          // (playouts)
-    int64_t masks_stride;
-    void* obs;
-    int64_t obs_stride;
-};
-
-// the trajectory arguments of one call, checked (before anything touches the stream) -> the launch block's source, the LDS bytes of the launch and
-// where the inventory shadows sit.  Without observations: the path form's layout and its map limit.  With them: the stand-alone lidar launch's
-// layout (ngw_lidar_configure), and the shadows behind it only where keys are asked for.
-int traj_args(const ngw_handle* h, const PathArgs& pa, const TrajArgs& ta, int64_t count, const char* what, const char* call, size_t* lds, uint32_t* off_shadow) {
+// The path and trajectory arguments of one request, checked (before anything touches the stream) -> the LDS bytes of the launch and where the
+// inventory shadows sit.  Without observations: the path form's layout and its map limit.  With them: the stand-alone lidar launch's layout
+// (ngw_lidar_configure), and the shadows behind it only where keys are asked for.
+int path_traj_args(const ngw_handle* h, const Pairs& p, const char* what, const char* call, size_t* lds, uint32_t* off_shadow) {
+    const PathArgs& pa = p.pa;
+    const TrajArgs& ta = p.ta;
+    const int64_t count = p.count;
     if (ta.rewards && ta.rewards_stride < count)
         return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a reward stride of %lld", what, (long long)count, (long long)ta.rewards_stride);
     if (ta.masks && ta.masks_stride < count)
         return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a mask stride of %lld", what, (long long)count, (long long)ta.masks_stride);
+    if (pa.keys)
+        if (int rc = key_args(pa.fields, what, count, pa.keys_stride)) return rc;
     if (!ta.obs) {
-        *off_shadow = (uint32_t)(h->lds_bytes / 4);
-        return path_args(h, pa, count, what, call, lds);
+        *lds = NGW_PATH_LDS_BYTES(h->lds_bytes, h->proto.KP);
+        if (*lds > NGW_PATH_LDS_MAX)
+            return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps and a second copy of their inventories in LDS (%s) and they need "
+                                           "%zu B, more than 160 KiB; the plain call is available", h->proto.S, call, *lds);
+        return NGW_OK;
     }
-    if (pa.keys && (!pa.fields || (pa.fields & ~NGW_KEY_ALL)))
-        return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)pa.fields);
-    if (pa.keys && pa.keys_stride < count) return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a key stride of %lld", what, (long long)count, (long long)pa.keys_stride);
     if (!h->lidar_len) return fail(NGW_E_INVALID_ARG, "%s with observations before ngw_lidar_configure", call);
     if (ta.obs_stride % NGW_EPB || ta.obs_stride < (count + NGW_EPB - 1) / NGW_EPB * NGW_EPB)
         return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with an observation stride of %lld rows: a multiple of 64 that holds the pairs rounded up to 64 expected",
@@ -154,93 +177,52 @@ int traj_args(const ngw_handle* h, const PathArgs& pa, const TrajArgs& ta, int64
     return NGW_OK;
 }
 
-// the launch block of an observing trajectory call: the stand-alone lidar launch's layout and row format with the handle's buffers, autoreset setting and horizon
-NgwLaunch traj_obs_block(const ngw_handle* h) {
-    NgwLaunch a = h->lidar_proto;
-    a.b = h->b;
-    a.lout = nullptr;                                // (every tile goes to the caller's rows)
-    a.autoreset = h->autoreset;
-    a.horizon = h->horizon;
-    return a;
+// what NgwSlotRollout and NgwPlayout hold alike, out of the request
+template <class X>
+void fill_pairs(X& x, const Pairs& p, const Source& from, uint32_t off_shadow) {
+    x.src = from.r; x.src_rows = (int32_t)from.rows; x.si = p.src_idx; x.di = p.dst_slots;
+    if (p.dst) { x.dst = p.dst->r; x.dst_rows = (int32_t)p.dst->cap; x.keep = 1; }
+    x.count = (int32_t)p.count; x.n_steps = p.n_steps;
+    x.ret = p.ret; x.length = p.length; x.ended = p.ended; x.info = p.info;
+    if (p.form != PLAIN) { x.limits = p.pa.limits; x.keys = p.pa.keys; x.keys_stride = p.pa.keys_stride; x.fields = p.pa.fields; x.off_shadow = off_shadow; }
+    if (p.form == TRAJ) { x.rewards = p.ta.rewards; x.rewards_stride = p.ta.rewards_stride; x.obs = p.ta.obs; x.obs_stride = p.ta.obs_stride; }
 }
 
-// a rollout, plain (pa == nullptr: the kernel as it always was), in its path form, or (ta != nullptr, with pa) in its trajectory form
-int rollout_call(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps, ngw_snapshot* dst,
-                 const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, const PathArgs* pa,
-                 const TrajArgs* ta = nullptr) {
-    if (!h || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "rollout of %d steps", (int)n_steps);
-    if (count < 0 || pair_stride < count)
-        return fail(NGW_E_INVALID_ARG, "rollout of %lld pairs with a pair stride of %lld", (long long)count, (long long)pair_stride);
-    if (!dst && !ret_dev && !length_dev && !ended_dev && !info_dev && !(pa && pa->keys) && !(ta && (ta->rewards || ta->obs)))
+// one request served: every check (in the order the entry points have always made them) before enter(h) and the first use of the stream, then one launch
+int step_pairs(ngw_handle* h, const Pairs& p) {
+    const char* const what = p.draws ? "playout" : "rollout";
+    const char* const call = PAIRS_CALL[p.draws][p.form];
+    const int64_t stride = p.draws ? p.draw.stride : p.plan.stride;
+    if (!h || (!p.draws && !p.plan.actions)) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (p.n_steps < 1) return fail(NGW_E_INVALID_ARG, "%s of %d steps", what, (int)p.n_steps);
+    if (p.count < 0 || ((!p.draws || p.draw.actions) && stride < p.count))
+        return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with %s stride of %lld", what, (long long)p.count, p.draws ? "an action" : "a pair", (long long)stride);
+    if (!p.draws && !p.dst && !p.ret && !p.length && !p.ended && !p.info && !p.pa.keys && !p.ta.rewards && !p.ta.obs)
         return fail(NGW_E_INVALID_ARG, "rollout without a destination and without a report: nothing to do");
-    int64_t src_rows;
+    Source from;
     size_t lds = h->lds_bytes;
     uint32_t off_shadow = (uint32_t)(h->lds_bytes / 4);
-    if (ta)                                          // (ahead of the plain refusal of large maps: this one names the bytes)
-        if (int rc = traj_args(h, *pa, *ta, count, "rollout", "ngw_snapshot_rollout_traj", &lds, &off_shadow)) return rc;
-    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "rollout",
-                                 ta ? "ngw_snapshot_rollout_traj" : (pa ? "ngw_snapshot_rollout_path" : "ngw_snapshot_rollout"), &src_rows))
-        return rc;
-    if (pa && !ta)
-        if (int rc = path_args(h, *pa, count, "rollout", "ngw_snapshot_rollout_path", &lds)) return rc;
+    if (p.form == TRAJ)                              // (ahead of the plain refusal of large maps: this one names the bytes)
+        if (int rc = path_traj_args(h, p, what, call, &lds, &off_shadow)) return rc;
+    if (int rc = step_pairs_args(h, p.src, p.src_idx, p.dst, p.dst_slots, p.count, what, call, &from)) return rc;
+    if (p.form == PATH)
+        if (int rc = path_traj_args(h, p, what, call, &lds, &off_shadow)) return rc;
     if (int rc = enter(h)) return rc;
-    if (count == 0) return NGW_OK;
-    const NgwLaunch a = ta && ta->obs ? traj_obs_block(h) : step_block(h);
-    NgwSlotRollout x{};
-    x.src = src ? src->r : state_rows(h);
-    if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
-    x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = pair_stride; x.n_steps = n_steps;
-    x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev;
-    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
-    if (pa) { x.limits = pa->limits; x.keys = pa->keys; x.keys_stride = pa->keys_stride; x.fields = pa->fields; x.off_shadow = off_shadow; }
-    if (ta) {
-        x.rewards = ta->rewards; x.rewards_stride = ta->rewards_stride; x.obs = ta->obs; x.obs_stride = ta->obs_stride;
-        HIP_TRY(ngw_slot_rollout_traj_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
-    } else if (pa)
-        HIP_TRY(ngw_slot_rollout_path_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
-    else
-        HIP_TRY(ngw_slot_rollout_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
-    return NGW_OK;
-}
-
-// a playout, likewise
-int playout_call(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
-                 const float* weights_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev,
-                 uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride, const PathArgs* pa, const TrajArgs* ta = nullptr) {
-    if (!h) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (n_steps < 1) return fail(NGW_E_INVALID_ARG, "playout of %d steps", (int)n_steps);
-    if (count < 0 || (actions_dev && actions_stride < count))
-        return fail(NGW_E_INVALID_ARG, "playout of %lld pairs with an action stride of %lld", (long long)count, (long long)actions_stride);
-    int64_t src_rows;
-    size_t lds = h->lds_bytes;
-    uint32_t off_shadow = (uint32_t)(h->lds_bytes / 4);
-    if (ta)                                          // (ahead of the plain refusal of large maps: this one names the bytes)
-        if (int rc = traj_args(h, *pa, *ta, count, "playout", "ngw_snapshot_playout_traj", &lds, &off_shadow)) return rc;
-    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "playout",
-                                 ta ? "ngw_snapshot_playout_traj" : (pa ? "ngw_snapshot_playout_path" : "ngw_snapshot_playout"), &src_rows))
-        return rc;
-    if (pa && !ta)
-        if (int rc = path_args(h, *pa, count, "playout", "ngw_snapshot_playout_path", &lds)) return rc;
-    if (int rc = enter(h)) return rc;
-    if (count == 0) return NGW_OK;
-    const NgwLaunch a = ta && ta->obs ? traj_obs_block(h) : step_block(h);
-    NgwPlayout x{};
-    x.src = src ? src->r : state_rows(h);
-    if (dst) { x.dst = dst->r; x.dst_rows = (int32_t)dst->cap; x.keep = 1; }
-    x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev; x.stride = actions_stride; x.n_steps = n_steps;
-    x.ret = ret_dev; x.length = length_dev; x.ended = ended_dev; x.info = info_dev; x.first_action = first_action_dev;
-    x.seed = seed; x.first_pair = first_pair; x.weights = weights_dev;
-    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows;
-    if (pa) { x.limits = pa->limits; x.keys = pa->keys; x.keys_stride = pa->keys_stride; x.fields = pa->fields; x.off_shadow = off_shadow; }
-    if (ta) {
-        x.rewards = ta->rewards; x.rewards_stride = ta->rewards_stride; x.masks = ta->masks; x.masks_stride = ta->masks_stride;
-        x.obs = ta->obs; x.obs_stride = ta->obs_stride;
-        HIP_TRY(ngw_playout_traj_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
-    } else if (pa)
-        HIP_TRY(ngw_playout_path_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
-    else
-        HIP_TRY(ngw_playout_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
+    if (p.count == 0) return NGW_OK;
+    const NgwLaunch a = step_block(h, p.ta.obs != nullptr);
+    if (!p.draws) {
+        NgwSlotRollout x{};
+        fill_pairs(x, p, from, off_shadow);
+        x.actions = p.plan.actions; x.stride = p.plan.stride;
+        HIP_TRY(ROLLOUT_LAUNCH[p.form](h->dspec, &a, &x, h->ext, lds, h->stream));
+    } else {
+        NgwPlayout x{};
+        fill_pairs(x, p, from, off_shadow);
+        x.actions = p.draw.actions; x.stride = p.draw.stride; x.first_action = p.draw.first_action;
+        x.seed = p.draw.seed; x.first_pair = p.draw.first_pair; x.weights = p.draw.weights;
+        if (p.form == TRAJ) { x.masks = p.ta.masks; x.masks_stride = p.ta.masks_stride; }
+        HIP_TRY(PLAYOUT_LAUNCH[p.form](h->dspec, &a, &x, h->ext, lds, h->stream));
+    }
     return NGW_OK;
 }
 
@@ -335,21 +317,16 @@ int ngw_snapshot_copy(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_d
 int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, ngw_snapshot* dst,
                         const int32_t* dst_slots_dev, int64_t count, int32_t* reward_dev, uint8_t* done_dev, uint32_t* info_dev) {
     if (!h || !dst || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns(h, dst) || (src && !owns(h, src))) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
-    const int64_t src_rows = src ? src->cap : h->n;
-    if (count < 0 || count > dst->cap) return fail(NGW_E_INVALID_ARG, "expand of %lld states into a snapshot of %lld slots", (long long)count, (long long)dst->cap);
-    if (!src_idx_dev && count > src_rows) return fail(NGW_E_INVALID_ARG, "expand of %lld states from %lld %s", (long long)count, (long long)src_rows, src ? "slots" : "envs");
-    if (!h->general_ok)
-        return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps in LDS (ngw_snapshot_expand, as the fused rollouts) "
-                                       "and they need more than 160 KiB; per-launch steps and resets are available", h->proto.S);
+    Source from;
+    if (int rc = step_pairs_args(h, src, src_idx_dev, dst, dst_slots_dev, count, "expand", "ngw_snapshot_expand", &from)) return rc;
     if (int rc = enter(h)) return rc;
     if (count == 0) return NGW_OK;
     const NgwLaunch a = step_block(h);
     NgwExpand x{};
-    x.src = src ? src->r : state_rows(h); x.dst = dst->r;
+    x.src = from.r; x.dst = dst->r;
     x.si = src_idx_dev; x.di = dst_slots_dev; x.actions = actions_dev;
     x.reward = reward_dev; x.done = done_dev; x.info = info_dev;
-    x.count = (int32_t)count; x.src_rows = (int32_t)src_rows; x.dst_rows = (int32_t)dst->cap;
+    x.count = (int32_t)count; x.src_rows = (int32_t)from.rows; x.dst_rows = (int32_t)dst->cap;
     HIP_TRY(ngw_expand_launch(h->dspec, &a, &x, h->ext, h->lds_bytes, h->stream));
     return NGW_OK;
 }
@@ -357,40 +334,60 @@ int ngw_snapshot_expand(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx
 int ngw_snapshot_rollout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
                          ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev,
                          uint32_t* info_dev) {
-    return rollout_call(h, src, src_idx_dev, actions_dev, pair_stride, n_steps, dst, dst_slots_dev, count, ret_dev, length_dev, ended_dev, info_dev, nullptr);
+    Pairs p{};
+    p.src = src; p.src_idx = src_idx_dev; p.dst = dst; p.dst_slots = dst_slots_dev; p.count = count; p.n_steps = n_steps;
+    p.ret = ret_dev; p.length = length_dev; p.ended = ended_dev; p.info = info_dev;
+    p.form = PLAIN; p.plan.actions = actions_dev; p.plan.stride = pair_stride;
+    return step_pairs(h, p);
 }
 
 int ngw_snapshot_rollout_path(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
                               const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev,
                               uint8_t* ended_dev, uint32_t* info_dev, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride) {
-    const PathArgs pa{limits_dev, fields, keys_dev, keys_stride};
-    return rollout_call(h, src, src_idx_dev, actions_dev, pair_stride, n_steps, dst, dst_slots_dev, count, ret_dev, length_dev, ended_dev, info_dev, &pa);
+    Pairs p{};
+    p.src = src; p.src_idx = src_idx_dev; p.dst = dst; p.dst_slots = dst_slots_dev; p.count = count; p.n_steps = n_steps;
+    p.ret = ret_dev; p.length = length_dev; p.ended = ended_dev; p.info = info_dev;
+    p.form = PATH; p.plan.actions = actions_dev; p.plan.stride = pair_stride;
+    p.pa.limits = limits_dev; p.pa.fields = fields; p.pa.keys = keys_dev; p.pa.keys_stride = keys_stride;
+    return step_pairs(h, p);
 }
 
 int ngw_snapshot_playout_weighted(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed,
                                   uint64_t first_pair, const float* weights_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev,
                                   int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev,
                                   int64_t actions_stride) {
-    return playout_call(h, src, src_idx_dev, count, n_steps, seed, first_pair, weights_dev, dst, dst_slots_dev, ret_dev, length_dev, ended_dev, info_dev,
-                        first_action_dev, actions_dev, actions_stride, nullptr);
+    Pairs p{};
+    p.src = src; p.src_idx = src_idx_dev; p.dst = dst; p.dst_slots = dst_slots_dev; p.count = count; p.n_steps = n_steps;
+    p.ret = ret_dev; p.length = length_dev; p.ended = ended_dev; p.info = info_dev;
+    p.form = PLAIN; p.draws = true; p.draw.seed = seed; p.draw.first_pair = first_pair; p.draw.weights = weights_dev;
+    p.draw.first_action = first_action_dev; p.draw.actions = actions_dev; p.draw.stride = actions_stride;
+    return step_pairs(h, p);
 }
 
 int ngw_snapshot_playout_path(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
                               const float* weights_dev, const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev,
                               int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride,
                               uint32_t fields, uint64_t* keys_dev, int64_t keys_stride) {
-    const PathArgs pa{limits_dev, fields, keys_dev, keys_stride};
-    return playout_call(h, src, src_idx_dev, count, n_steps, seed, first_pair, weights_dev, dst, dst_slots_dev, ret_dev, length_dev, ended_dev, info_dev,
-                        first_action_dev, actions_dev, actions_stride, &pa);
+    Pairs p{};
+    p.src = src; p.src_idx = src_idx_dev; p.dst = dst; p.dst_slots = dst_slots_dev; p.count = count; p.n_steps = n_steps;
+    p.ret = ret_dev; p.length = length_dev; p.ended = ended_dev; p.info = info_dev;
+    p.form = PATH; p.draws = true; p.draw.seed = seed; p.draw.first_pair = first_pair; p.draw.weights = weights_dev;
+    p.draw.first_action = first_action_dev; p.draw.actions = actions_dev; p.draw.stride = actions_stride;
+    p.pa.limits = limits_dev; p.pa.fields = fields; p.pa.keys = keys_dev; p.pa.keys_stride = keys_stride;
+    return step_pairs(h, p);
 }
 
 int ngw_snapshot_rollout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
                               const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev,
                               uint8_t* ended_dev, uint32_t* info_dev, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev,
                               int64_t rewards_stride, void* obs_dev, int64_t obs_stride) {
-    const PathArgs pa{limits_dev, fields, keys_dev, keys_stride};
-    const TrajArgs ta{rewards_dev, rewards_stride, nullptr, 0, obs_dev, obs_stride};
-    return rollout_call(h, src, src_idx_dev, actions_dev, pair_stride, n_steps, dst, dst_slots_dev, count, ret_dev, length_dev, ended_dev, info_dev, &pa, &ta);
+    Pairs p{};
+    p.src = src; p.src_idx = src_idx_dev; p.dst = dst; p.dst_slots = dst_slots_dev; p.count = count; p.n_steps = n_steps;
+    p.ret = ret_dev; p.length = length_dev; p.ended = ended_dev; p.info = info_dev;
+    p.form = TRAJ; p.plan.actions = actions_dev; p.plan.stride = pair_stride;
+    p.pa.limits = limits_dev; p.pa.fields = fields; p.pa.keys = keys_dev; p.pa.keys_stride = keys_stride;
+    p.ta.rewards = rewards_dev; p.ta.rewards_stride = rewards_stride; p.ta.obs = obs_dev; p.ta.obs_stride = obs_stride;
+    return step_pairs(h, p);
 }
 
 int ngw_snapshot_playout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
@@ -398,10 +395,14 @@ int ngw_snapshot_playout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* s
                               int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride,
                               uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev, int64_t rewards_stride, uint64_t* masks_dev,
                               int64_t masks_stride, void* obs_dev, int64_t obs_stride) {
-    const PathArgs pa{limits_dev, fields, keys_dev, keys_stride};
-    const TrajArgs ta{rewards_dev, rewards_stride, masks_dev, masks_stride, obs_dev, obs_stride};
-    return playout_call(h, src, src_idx_dev, count, n_steps, seed, first_pair, weights_dev, dst, dst_slots_dev, ret_dev, length_dev, ended_dev, info_dev,
-                        first_action_dev, actions_dev, actions_stride, &pa, &ta);
+    Pairs p{};
+    p.src = src; p.src_idx = src_idx_dev; p.dst = dst; p.dst_slots = dst_slots_dev; p.count = count; p.n_steps = n_steps;
+    p.ret = ret_dev; p.length = length_dev; p.ended = ended_dev; p.info = info_dev;
+    p.form = TRAJ; p.draws = true; p.draw.seed = seed; p.draw.first_pair = first_pair; p.draw.weights = weights_dev;
+    p.draw.first_action = first_action_dev; p.draw.actions = actions_dev; p.draw.stride = actions_stride;
+    p.pa.limits = limits_dev; p.pa.fields = fields; p.pa.keys = keys_dev; p.pa.keys_stride = keys_stride;
+    p.ta.rewards = rewards_dev; p.ta.rewards_stride = rewards_stride; p.ta.obs = obs_dev; p.ta.obs_stride = obs_stride; p.ta.masks = masks_dev; p.ta.masks_stride = masks_stride;
+    return step_pairs(h, p);
 }
 
 int ngw_snapshot_playout(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
@@ -420,8 +421,7 @@ int ngw_snapshot_lidar(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev,
     NgwLaunch a = h->lidar_proto;                     // the stand-alone launch's LDS layout and the current row format, whichever form the env's fused path uses
     a.b = h->b;
     a.lout = static_cast<int32_t*>(rows_dev);
-    NgwSlotObs x{};
-    x.src = s->r; x.slots = slots_dev; x.flags = h->b.flags; x.count = (int32_t)count; x.rows = (int32_t)s->cap;
+    NgwSlotObs x = slot_obs(h, s, slots_dev, count);
     HIP_TRY(ngw_slot_lidar_launch(&a, &x, h->lidar_lds, h->stream));
     return NGW_OK;
 }
@@ -435,8 +435,7 @@ int ngw_snapshot_agent_view(ngw_handle* h, ngw_snapshot* s, const int32_t* slots
     if (bytes + 4 > 0xffffffffull) return fail(NGW_E_INVALID_ARG, "agent view of %zu B exceeds the 4 GiB index range", bytes);
     if (int rc = enter(h)) return rc;
     if (count == 0) return NGW_OK;
-    NgwSlotObs x{};
-    x.src = s->r; x.slots = slots_dev; x.flags = h->b.flags; x.count = (int32_t)count; x.rows = (int32_t)s->cap;
+    NgwSlotObs x = slot_obs(h, s, slots_dev, count);
     x.view = reinterpret_cast<uint32_t*>(view_dev); x.facing = facing_dev; x.inv = inv_dev;
     x.n_dwords = (uint32_t)((bytes + 3) / 4); x.S = h->proto.S; x.K = h->proto.K; x.V = view_size;
     HIP_TRY(ngw_slot_view_launch(&x, h->stream));
@@ -447,8 +446,7 @@ int ngw_snapshot_action_mask(ngw_handle* h, ngw_snapshot* s, const int32_t* slot
     if (int rc = slot_obs_args(h, s, masks_dev, slots_dev, count, "action masks")) return rc;
     if (int rc = enter(h)) return rc;
     if (count == 0) return NGW_OK;
-    NgwSlotObs x{};
-    x.src = s->r; x.slots = slots_dev; x.flags = h->b.flags; x.count = (int32_t)count; x.rows = (int32_t)s->cap;
+    NgwSlotObs x = slot_obs(h, s, slots_dev, count);
     HIP_TRY(ngw_slot_mask_launch(h->dspec, &x, h->proto.S, h->proto.K, h->ext, masks_dev, h->stream));
     return NGW_OK;
 }
@@ -457,17 +455,17 @@ int ngw_sample_actions(ngw_handle* h, ngw_snapshot* src, const int32_t* idx_dev,
                        uint64_t seed, uint64_t first_pair, uint32_t t, int32_t* actions_dev, float* mass_dev, uint64_t* masks_dev) {
     if (!h || !weights_dev || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (src && !owns(h, src)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
-    const int64_t rows = src ? src->cap : h->n;
+    const Source from = source_of(h, src);
     if (count < 0 || count > 0x7FFFFFFFll || weight_stride < count)
         return fail(NGW_E_INVALID_ARG, "sampled actions of %lld states with a weight stride of %lld", (long long)count, (long long)weight_stride);
-    if (!idx_dev && count > rows) return fail(NGW_E_INVALID_ARG, "sampled actions of %lld states from %lld %s", (long long)count, (long long)rows, src ? "slots" : "envs");
+    if (!idx_dev && count > from.rows) return fail(NGW_E_INVALID_ARG, "sampled actions of %lld states from %lld %s", (long long)count, (long long)from.rows, from.unit);
     if (int rc = enter(h)) return rc;                 // (src == NULL: the one-env loop has ended, HBM holds the env's state)
     if (count == 0) return NGW_OK;
     NgwSample x{};
-    x.src = src ? src->r : state_rows(h); x.idx = idx_dev; x.flags = h->b.flags;
+    x.src = from.r; x.idx = idx_dev; x.flags = h->b.flags;
     x.weights = weights_dev; x.stride = weight_stride; x.seed = seed; x.first_pair = first_pair; x.t = t;
     x.actions = actions_dev; x.mass = mass_dev; x.masks = masks_dev;
-    x.count = (int32_t)count; x.rows = (int32_t)rows;
+    x.count = (int32_t)count; x.rows = (int32_t)from.rows;
     HIP_TRY(ngw_sample_launch(h->dspec, &x, h->proto.S, h->proto.K, h->ext, h->stream));
     return NGW_OK;
 }
@@ -475,15 +473,15 @@ int ngw_sample_actions(ngw_handle* h, ngw_snapshot* src, const int32_t* idx_dev,
 int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev) {
     if (!h || !keys_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
-    if (!fields || (fields & ~NGW_KEY_ALL)) return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)fields);
-    const int64_t rows = s ? s->cap : h->n;
+    if (int rc = key_args(fields)) return rc;
+    const Source from = source_of(h, s);
     if (count < 0 || count > 0x7FFFFFFFll * NGW_EPB) return fail(NGW_E_INVALID_ARG, "state keys of %lld rows", (long long)count);
-    if (!idx_dev && count > rows) return fail(NGW_E_INVALID_ARG, "state keys of %lld rows from %lld %s", (long long)count, (long long)rows, s ? "slots" : "envs");
+    if (!idx_dev && count > from.rows) return fail(NGW_E_INVALID_ARG, "state keys of %lld rows from %lld %s", (long long)count, (long long)from.rows, from.unit);
     if (int rc = enter(h)) return rc;                 // (s == NULL: the one-env loop has ended, HBM holds the env's state - what ngw_snapshot_expand relies on)
     if (count == 0) return NGW_OK;
     NgwKeys x{};
-    x.src = s ? s->r : state_rows(h); x.idx = idx_dev; x.flags = h->b.flags; x.keys = keys_dev;
-    x.count = count; x.rows = (int32_t)rows; x.S2 = h->proto.S2; x.K = h->proto.K; x.fields = fields;
+    x.src = from.r; x.idx = idx_dev; x.flags = h->b.flags; x.keys = keys_dev;
+    x.count = count; x.rows = (int32_t)from.rows; x.S2 = h->proto.S2; x.K = h->proto.K; x.fields = fields;
     HIP_TRY(ngw_keys_launch(&x, h->stream));
     return NGW_OK;
 }
@@ -492,11 +490,12 @@ int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, i
                        uint8_t* done_dev, uint32_t* info_dev) {
     if (!h || !keys_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
-    if (!fields || (fields & ~NGW_KEY_ALL)) return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)fields);
-    const int64_t rows = s ? s->cap : h->n, A = h->spec.n_actions;
+    if (int rc = key_args(fields)) return rc;
+    const Source from = source_of(h, s);
+    const int64_t A = h->spec.n_actions;
     // (the flattened [count * A] keys are what ngw_state_keys and the key table take: the same range)
     if (count < 0 || count > 0x7FFFFFFFll * NGW_EPB / A) return fail(NGW_E_INVALID_ARG, "successor keys of %lld rows by %lld actions", (long long)count, (long long)A);
-    if (!idx_dev && count > rows) return fail(NGW_E_INVALID_ARG, "successor keys of %lld rows from %lld %s", (long long)count, (long long)rows, s ? "slots" : "envs");
+    if (!idx_dev && count > from.rows) return fail(NGW_E_INVALID_ARG, "successor keys of %lld rows from %lld %s", (long long)count, (long long)from.rows, from.unit);
     const size_t lds = NGW_SUCC_LDS_BYTES(h->proto.MS, h->proto.KP);
     if (lds > NGW_SUCC_LDS_MAX)
         return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps two sets of a wavefront's 64 maps in LDS (ngw_successor_keys: the stepped rows and "
@@ -506,9 +505,9 @@ int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, i
     if (count == 0) return NGW_OK;
     const NgwLaunch a = step_block(h);
     NgwSuccessors x{};
-    x.src = s ? s->r : state_rows(h); x.idx = idx_dev; x.keys = keys_dev;
+    x.src = from.r; x.idx = idx_dev; x.keys = keys_dev;
     x.reward = reward_dev; x.done = done_dev; x.info = info_dev;
-    x.count = count; x.rows = (int32_t)rows; x.fields = fields;
+    x.count = count; x.rows = (int32_t)from.rows; x.fields = fields;
     HIP_TRY(ngw_successors_launch(h->dspec, &a, &x, h->ext, h->stream));
     return NGW_OK;
 }

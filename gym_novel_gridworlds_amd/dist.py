@@ -140,9 +140,8 @@ class ShardedVecNovelGridworld:
         rank-local, no collective.  The local env numbers its pairs from env_index_base * P (= first * P), so the ranks together return what
         one unsharded env over all the envs returns - with path_keys=True the keys [steps, num_envs, P] included: a key describes a state, not
         where it is stored.  rewards / masks / observe: the trajectory fields of the shard's playouts (VecNovelGridworld.playouts), likewise."""
-        from .playout import traj_keywords
-        path = dict(path_keys=True, fields=fields) if path_keys else {}
-        path.update(traj_keywords(rewards, masks, observe))
+        from .playout import forward_keywords
+        path = forward_keywords(path_keys, fields, rewards, masks, observe)
         return self.local.playouts(n_playouts, steps, seed, device=device, weights=weights, **path)
 
     def snapshot(self, capacity=None):

@@ -19,7 +19,7 @@ import numpy as np
 
 from . import spaces
 from .spec import DIRECTION_ID, DIRECTION_STR, STEP_COSTS, EnvSpec
-from .playout import traj_keywords
+from .playout import forward_keywords
 from .state_keys import KEY_STATE
 from .vec_env import PLACEMENT_MESSAGE, VecNovelGridworld
 
@@ -343,8 +343,7 @@ class _NovelGridworldEnv(_EnvBase):
         batched backend)."""
         vec = self._backend()
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
-        path = dict(path_keys=True, fields=fields) if path_keys else {}
-        path.update(traj_keywords(rewards, masks, observe))
+        path = forward_keywords(path_keys, fields, rewards, masks, observe)
         return vec.playouts(n_playouts, steps, seed, device=device, weights=weights, **path).row(0)
 
     def state_key(self, fields=KEY_STATE):

@@ -7,7 +7,7 @@ Accepts a single-env adapter (envs.py) - returns a wrapper that forwards reads t
 `VecNovelGridworld` / `ShardedVecNovelGridworld`, which is rebuilt IN PLACE on the edited spec and returned (the
 reference's wrappers mutate the env they wrap; a shard keeps its place in the global env index space)."""
 from .novelty import apply_novelty
-from .playout import traj_keywords
+from .playout import forward_keywords
 from .state_keys import KEY_STATE
 
 
@@ -55,8 +55,7 @@ class NoveltyWrapper(object):
         return self.env.evaluate_plans(plans, device=device, copy=copy)
 
     def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None):
-        path = dict(path_keys=True, fields=fields) if path_keys else {}
-        path.update(traj_keywords(rewards, masks, observe))
+        path = forward_keywords(path_keys, fields, rewards, masks, observe)
         return self.env.playouts(n_playouts, steps, seed, device=device, weights=weights, **path)
 
     def sample_action(self, weights, seed, t=0):

@@ -72,9 +72,20 @@ class PlayoutPath(collections.namedtuple('PlayoutPath', 'ret length ended info f
         return PlayoutPath(*[x[i] for x in self[:5]], None if a is None else a[:, i], self.keys[:, i])
 
 
-def traj_keywords(rewards, masks, observe):
-    """The trajectory keywords a forwarding playouts() passes on: only those that are switched on, so a call without them is the call it always was."""
-    kw = {}
+def pairs_symbol(kind, weighted=False, path=False, traj=False):
+    """The C entry point (include/ngw.h) behind one rollout / playout call: kind 'rollout' or 'playout'; traj - rewards, masks or observations are
+    asked for; path - step limits or path keys are; weighted - a playout draws by weights.  The form is the entry point's: any traj is `_traj`,
+    any other path `_path`, else the plain call (a weighted playout: `_weighted`; a rollout draws nothing).  The one place that names the seven."""
+    if kind not in ('rollout', 'playout'):
+        raise ValueError("kind: 'rollout' or 'playout' expected, got %r" % (kind,))
+    form = '_traj' if traj else ('_path' if path else ('_weighted' if weighted and kind == 'playout' else ''))
+    return 'ngw_snapshot_%s%s' % (kind, form)
+
+
+def forward_keywords(path_keys=False, fields=None, rewards=False, masks=False, observe=None):
+    """The path and trajectory keywords a forwarding playouts() passes on: only those that are switched on (`fields` with path_keys), so a call
+    without them is the call it always was."""
+    kw = dict(path_keys=True, fields=fields) if path_keys else {}
     if rewards:
         kw['rewards'] = True
     if masks:

@@ -431,14 +431,21 @@ def traj_outputs(env, dev, rewards, masks, observe, count, steps):
     return rew, msk, rows, pad
 
 
+def host(x, view=None):
+    """One device result as the host's: a numpy array, its bits seen as `view` where one is given (uint8 -> bool, int32 -> uint32, int64 -> uint64);
+    None stays None."""
+    if x is None:
+        return None
+    x = x.cpu().numpy()
+    return x if view is None else x.view(view)
+
+
 def traj_results(env, rew, msk, rows, count, device):
     """The three buffers as the result's fields: on the device as they are (the rows cut to `count` per block), else numpy; packed rows split."""
     if rows is not None:
         rows = rows[:, :count]
     if not device:
-        rew = None if rew is None else rew.cpu().numpy()
-        msk = None if msk is None else msk.cpu().numpy().view(np.uint64)
-        rows = None if rows is None else rows.cpu().numpy()
+        rew, msk, rows = host(rew), host(msk, np.uint64), host(rows)
     if rows is not None and env.lidar_packed:            # (env._lidar_split, over the last axis)
         beams, tail = rows[..., :env.lidar.num_beams * len(env.lidar.lidar_items_id)], rows[..., env._lidar_inv_off:]
         if isinstance(tail, np.ndarray):
@@ -472,75 +479,68 @@ def path_call(env, holder, call, count, uploaded, device):
         raise
 
 
-def playout_call(env, holder, src, dst, parents, children, count, steps, seed, first_pair, record, device, weights=None, limits=None, path_keys=False,
-                 fields=None, rewards=False, masks=False, observe=None):
-    """The one launch behind Snapshot.playout and VecNovelGridworld.playouts: src / dst are snapshots' C handles (src None: the envs' current
-    states; dst None: nothing is kept), parents / children the checked lists (check_playout); `holder` keeps the uploaded lists alive.
-    weights: None (the uniform rule), or one float32 per action from the host or the device (sample.check_weights).
-    -> Playout of [count] fields, actions [steps, count] with `record`.  limits / path_keys / fields: the path form (Snapshot.playout);
-    with path_keys a PlayoutPath.  rewards / masks / observe: the trajectory form (Snapshot.playout): a PlayoutTraj; `observe` has been through
-    check_observe at the caller (before it touched a handle)."""
+def pairs_call(env, holder, kind, src, dst, parents, children, count, steps, device, plans=None, seed=0, first_pair=0, record=False, weights=None, limits=None,
+               path_keys=False, fields=None, rewards=False, masks=False, observe=None):
+    """The one launch behind Snapshot.rollout (kind 'rollout': `plans` the checked step-major [steps, count] actions), Snapshot.playout and
+    VecNovelGridworld.playouts (kind 'playout': seed / first_pair / record, and weights: None - the uniform rule - or one float32 per action from the
+    host or the device, sample.check_weights).  src / dst are snapshots' C handles (src None: the envs' current states; dst None: nothing is kept),
+    parents / children the checked lists (check_rollout / check_playout); `holder` keeps the uploaded lists alive.  limits / path_keys / fields: the
+    path form; rewards / masks / observe: the trajectory form - `observe` has been through check_observe at the caller (before it touched a handle).
+    The entry point is playout.pairs_symbol's.  -> PlanEval / RolloutPath (with path_keys) / RolloutTraj, or Playout (actions [steps, count] with
+    `record`) / PlayoutPath / PlayoutTraj, as the callers' docstrings define them."""
     import torch
-    from .playout import Playout, PlayoutPath, PlayoutTraj
+    from .playout import Playout, PlayoutPath, PlayoutTraj, pairs_symbol
+    from .vec_env import PlanEval, RolloutPath, RolloutTraj
+    draws = kind == 'playout'
     traj = observe is not None or bool(rewards) or bool(masks)
+    path = traj or limits is not None or bool(path_keys)
+    name = pairs_symbol(kind, weights is not None, path, traj)
     seed, first_pair = int(seed), int(first_pair)
-    if not 0 <= seed < 1 << 64:
+    if not 0 <= seed < 1 << 64:                 # (refused before anything is uploaded or allocated)
         raise ValueError("seed: %d outside [0, 2^64)" % seed)
     if not 0 <= first_pair < 1 << 64:
         raise ValueError("first_pair: %d outside [0, 2^64)" % first_pair)
     dev = torch.device('cuda:%d' % env.device)
-    ptr, uploaded = upload(dev, count, parents, children)
-    wt = None
-    if weights is not None:
-        from .sample import check_weights
-        wt, mine = check_weights(weights, count, env.n_actions, dev, per_pair=False)
-        if mine:
-            uploaded = uploaded + [wt]
-    ret = torch.zeros(count, dtype=torch.int32, device=dev)
-    length = torch.zeros(count, dtype=torch.int32, device=dev)
+    ptr, uploaded = upload(dev, count, parents, children, plans)
+    ret, length, info = [torch.zeros(count, dtype=torch.int32, device=dev) for _ in range(3)]
     ended = torch.zeros(count, dtype=torch.uint8, device=dev)
-    info = torch.zeros(count, dtype=torch.int32, device=dev)
-    first = torch.full((count,), -1, dtype=torch.int32, device=dev)
-    actions = torch.full((steps, count), -1, dtype=torch.int32, device=dev) if record else None
-    out = [C.c_void_p(x.data_ptr()) for x in (ret, length, ended, info, first)]
-    recorded = C.c_void_p(actions.data_ptr()) if record and count else None
-    keys = None
+    reports = [C.c_void_p(x.data_ptr()) for x in (ret, length, ended, info)]
+    first = actions = keys = rew = msk = rows = None
+    if draws:
+        wt = []
+        if weights is not None:
+            from .sample import check_weights
+            w, mine = check_weights(weights, count, env.n_actions, dev, per_pair=False)
+            uploaded, wt = uploaded + ([w] if mine else []), [C.c_void_p(w.data_ptr())]
+        elif path:
+            wt = [None]                         # (only the plain unweighted entry point has no weights argument)
+        first = torch.full((count,), -1, dtype=torch.int32, device=dev)
+        actions = torch.full((steps, count), -1, dtype=torch.int32, device=dev) if record else None
+        head = [env._h, src, ptr[0], int(count), steps, seed, first_pair] + wt
+        tail = [dst, ptr[1]] + reports + [C.c_void_p(first.data_ptr()), _ptr(actions, count), int(count)]
+    else:
+        head = [env._h, src, ptr[0], ptr[2], int(count), steps]
+        tail = [dst, ptr[1], int(count)] + reports
+    if path:
+        lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
+        (lim_ptr,), up = upload(dev, count, lim)
+        uploaded, head, tail = uploaded + up, head + [lim_ptr], tail + [f, _ptr(keys, count), int(count)]
     if traj:
-        lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
-        (lim_ptr,), up = upload(dev, count, lim)
-        uploaded = uploaded + up
         rew, msk, rows, pad = traj_outputs(env, dev, rewards, masks, observe is not None, count, steps)
-        call = lambda: _cabi.lib().ngw_snapshot_playout_traj(   # noqa: E731
-            env._h, src, ptr[0], int(count), steps, seed, first_pair, None if wt is None else C.c_void_p(wt.data_ptr()), lim_ptr, dst, ptr[1], *out, recorded,
-            int(count), f, _ptr(keys, count), int(count), _ptr(rew, count), int(count), _ptr(msk, count), int(count), _ptr(rows, count), int(pad))
-    elif limits is not None or path_keys:
-        lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
-        (lim_ptr,), up = upload(dev, count, lim)
-        uploaded = uploaded + up
-        call = lambda: _cabi.lib().ngw_snapshot_playout_path(   # noqa: E731
-            env._h, src, ptr[0], int(count), steps, seed, first_pair, None if wt is None else C.c_void_p(wt.data_ptr()), lim_ptr, dst, ptr[1], *out, recorded,
-            int(count), f, C.c_void_p(keys.data_ptr()) if keys is not None and count else None, int(count))
-    elif wt is None:                            # (the call as it always was)
-        call = lambda: _cabi.lib().ngw_snapshot_playout(env._h, src, ptr[0], int(count), steps, seed, first_pair, dst, ptr[1], *out, recorded, int(count))   # noqa: E731
-    else:
-        call = lambda: _cabi.lib().ngw_snapshot_playout_weighted(env._h, src, ptr[0], int(count), steps, seed, first_pair, C.c_void_p(wt.data_ptr()), dst,   # noqa: E731
-                                                                 ptr[1], *out, recorded, int(count))
-    if traj or limits is not None or path_keys:
-        path_call(env, holder, call, count, uploaded, device)
-    else:
-        enqueue_ordered(env, holder, call, count, uploaded, device)
-    if traj and count == 0 and rows is not None:
+        tail += [_ptr(rew, count), int(count)] + ([_ptr(msk, count), int(count)] if draws else []) + [_ptr(rows, count), int(pad)]
+    (path_call if path else enqueue_ordered)(env, holder, lambda: getattr(_cabi.lib(), name)(*head, *tail), count, uploaded, device)
+    if count == 0 and rows is not None:
         rows.zero_()
     if device:
-        play = Playout(ret, length, ended.view(torch.bool), info, first, actions)
-        if traj:
-            return PlayoutTraj(*play, keys, *traj_results(env, rew, msk, rows, count, True))
-        return play if keys is None else PlayoutPath(*play, keys)
-    play = Playout(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32), first.cpu().numpy(),
-                   None if actions is None else actions.cpu().numpy())
+        res = [ret, length, ended.view(torch.bool), info] + ([first, actions] if draws else [])
+    else:
+        res = [host(ret), host(length), host(ended, np.bool_), host(info, np.uint32)] + ([host(first), host(actions)] if draws else [])
+        keys = host(keys, np.uint64)
     if traj:
-        return PlayoutTraj(*play, None if keys is None else keys.cpu().numpy().view(np.uint64), *traj_results(env, rew, msk, rows, count, False))
-    return play if keys is None else PlayoutPath(*play, keys.cpu().numpy().view(np.uint64))
+        rew, msk, rows = traj_results(env, rew, msk, rows, count, device)
+        return PlayoutTraj(*res, keys, rew, msk, rows) if draws else RolloutTraj(*res, keys, rew, rows)
+    plain, keyed = (Playout, PlayoutPath) if draws else (PlanEval, RolloutPath)
+    return plain(*res) if keys is None else keyed(*res, keys)
 
 
 class MapsTooLarge(_cabi.NgwError, ValueError):
@@ -738,11 +738,10 @@ class Snapshot:
         env.lidar_configure (ValueError otherwise); maps its layout cannot hold raise MapsTooLarge while rewards=True alone keeps the path
         form's limit.  A parent index out of range gives zeros in both fields, obs[0] included.  masks=True is a playout's keyword: ValueError."""
         import torch
-        from .vec_env import PlanEval, RolloutPath, RolloutTraj
         env = self.env
         if masks:
             raise ValueError("masks=True: a rollout makes no choice, so there is no mask word to record (playout() records them)")
-        traj = check_observe(env, observe) or bool(rewards)
+        check_observe(env, observe)
         src, n_parents, same_buffer = self._source(source, from_envs, 'rollout')
         dev = torch.device('cuda:%d' % env.device)
         if isinstance(plans, torch.Tensor):
@@ -754,43 +753,8 @@ class Snapshot:
             n_plans, steps = int(a.shape[0]), int(a.shape[1])
             a = np.ascontiguousarray(a.T)       # step-major [T, count]: 64 lanes read consecutive addresses
         p, c, count = check_rollout(parents, n_plans, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'rollout', x))
-        ptr, uploaded = upload(dev, count, p, a, c)
-        ret = torch.zeros(count, dtype=torch.int32, device=dev)
-        length = torch.zeros(count, dtype=torch.int32, device=dev)
-        ended = torch.zeros(count, dtype=torch.uint8, device=dev)
-        info = torch.zeros(count, dtype=torch.int32, device=dev)
-        keys = None
-        if traj:
-            lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
-            (lim_ptr,), up = upload(dev, count, lim)
-            rew, _, rows, pad = traj_outputs(env, dev, rewards, False, observe is not None, count, steps)
-            path_call(env, self, lambda: _cabi.lib().ngw_snapshot_rollout_traj(
-                env._h, src, ptr[0], ptr[1], int(count), steps, lim_ptr, None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
-                C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr()), f, _ptr(keys, count), int(count),
-                _ptr(rew, count), int(count), _ptr(rows, count), int(pad)), count, uploaded + up, device)
-            if count == 0 and rows is not None:
-                rows.zero_()
-            rew, _, rows = traj_results(env, rew, None, rows, count, device)
-            if device:
-                return RolloutTraj(ret, length, ended.view(torch.bool), info, keys, rew, rows)
-            return RolloutTraj(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32),
-                               None if keys is None else keys.cpu().numpy().view(np.uint64), rew, rows)
-        if limits is None and not path_keys:    # (the call as it always was)
-            enqueue_ordered(env, self, lambda: _cabi.lib().ngw_snapshot_rollout(
-                env._h, src, ptr[0], ptr[1], int(count), steps, None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
-                C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr())), count, uploaded, device)
-        else:
-            lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
-            (lim_ptr,), up = upload(dev, count, lim)
-            path_call(env, self, lambda: _cabi.lib().ngw_snapshot_rollout_path(
-                env._h, src, ptr[0], ptr[1], int(count), steps, lim_ptr, None if c is None else self._s, ptr[2], int(count), C.c_void_p(ret.data_ptr()),
-                C.c_void_p(length.data_ptr()), C.c_void_p(ended.data_ptr()), C.c_void_p(info.data_ptr()), f,
-                C.c_void_p(keys.data_ptr()) if keys is not None and count else None, int(count)), count, uploaded + up, device)
-        if device:
-            ev = PlanEval(ret, length, ended.view(torch.bool), info)
-            return ev if keys is None else RolloutPath(*ev, keys)
-        ev = PlanEval(ret.cpu().numpy(), length.cpu().numpy(), ended.cpu().numpy().view(np.bool_), info.cpu().numpy().view(np.uint32))
-        return ev if keys is None else RolloutPath(*ev, keys.cpu().numpy().view(np.uint64))
+        return pairs_call(env, self, 'rollout', src, None if c is None else self._s, p, c, count, steps, device, plans=a, limits=limits, path_keys=path_keys,
+                          fields=fields, rewards=rewards, observe=observe)
 
     def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False, weights=None,
                 limits=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None):
@@ -825,13 +789,8 @@ class Snapshot:
         src, n_parents, same_buffer = self._source(source, from_envs, 'playout')
         dev = torch.device('cuda:%d' % env.device)
         p, c, count, steps = check_playout(parents, steps, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'playout', x))
-        if rewards or masks or observe is not None:
-            return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights, limits=limits,
-                                path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe)
-        if limits is None and not path_keys:    # (the call as it always was)
-            return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights)
-        return playout_call(env, self, src, None if c is None else self._s, p, c, count, steps, seed, first_pair, record, device, weights, limits=limits,
-                            path_keys=path_keys, fields=fields)
+        return pairs_call(env, self, 'playout', src, None if c is None else self._s, p, c, count, steps, device, seed=seed, first_pair=first_pair, record=record,
+                          weights=weights, limits=limits, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe)
 
     # ------------------------------------------------------------------ slot observations (include/ngw.h ngw_snapshot_lidar / _agent_view / _action_mask)
     def _slots_arg(self, slots):

@@ -1085,7 +1085,7 @@ class VecNovelGridworld:
         step's reward, the mask word its choice was made under and the LidarInFront rows before and after it (Snapshot.playout; obs takes
         (T + 1) * N * P rows of device memory)."""
         import torch
-        from .snapshot import check_observe, check_playout, playout_call
+        from .snapshot import check_observe, check_playout, pairs_call
         P = int(n_playouts)
         if P < 1:
             raise ValueError("n_playouts: at least one playout per env expected, got %d" % P)
@@ -1094,13 +1094,8 @@ class VecNovelGridworld:
         parents = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(P).contiguous()
         _, _, count, steps = check_playout(parents, steps, None, N, 0, False, lambda x: None if x is None else int(x.numel()))
         check_observe(self, observe)
-        if rewards or masks or observe is not None:
-            return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights,
-                                path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe).shaped(N, P)
-        if not path_keys:                       # (the call as it always was)
-            return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights).shaped(N, P)
-        return playout_call(self, self._keeper(), None, None, parents, None, count, steps, seed, self.env_index_base * P, False, device, weights,
-                            path_keys=True, fields=fields).shaped(N, P)
+        return pairs_call(self, self._keeper(), 'playout', None, None, parents, None, count, steps, device, seed=seed, first_pair=self.env_index_base * P,
+                          weights=weights, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe).shaped(N, P)
 
     def fork(self, src, keep_episode=False):
         """Every env e becomes a copy of env src[e] (src: num_envs indices - a list / numpy array, checked, or a torch int32 tensor on the

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import spaces
 from .novelty_wrappers import NoveltyWrapper
-from .playout import traj_keywords
+from .playout import forward_keywords
 from .state_keys import KEY_STATE
 from .vec_env import VecNovelGridworld
 
@@ -192,8 +192,7 @@ class LimitActions(NoveltyWrapper):
         elif weights is not None and ids != list(range(len(ids))):
             import torch
             weights = weights[torch.tensor(ids, device=weights.device)].contiguous()
-        path = dict(path_keys=True, fields=fields) if path_keys else {}
-        path.update(traj_keywords(rewards, masks, observe))
+        path = forward_keywords(path_keys, fields, rewards, masks, observe)
         if observe is not None:                              # the rows are the backend's: its lidar as it is configured NOW, not as it was when the limited env was made
             vec = self.unwrapped._backend()
             mine, theirs = [(e.lidar, e.lidar_packed, e.lidar_dtype) for e in (limited, vec)]
