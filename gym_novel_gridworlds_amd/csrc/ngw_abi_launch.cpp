@@ -848,6 +848,9 @@ int ngw_graph_launch(ngw_handle* h, int32_t reps) {
             if (int rc = capture_graph(h, acts, stride, k)) return rc;
         }
         state_written(h);
+        // the captured step launches read the bit rows as they are: capture_graph rebuilt them for the capture only, and a fused rollout or a
+        // state injection since then has left them stale - the rebuild an eager step launch starts with
+        if (int rc = ensure_boards(h)) return rc;
         if (h->graph_open && h->prefetch_every > 0 && h->since_refill + h->graph_steps > h->cadence) {
             if (int rc = launch_refill(h)) return rc;                               // (an open graph: the cadence is kept between its replays)
         }

@@ -1,0 +1,777 @@
+"""Model-based fuzz of the whole search surface of one handle: the driver and the model (tests/test_search_fuzz.py runs it against the HIP
+path, tests/test_search_fuzz_cpu.py against an oracle-backed stand-in and against seeded faults).
+
+run_case() draws the handle's settings and 6 - 12 calls - writers of live state, writers of snapshot slots, read-only calls - performs each on the
+env under test and on the model, and compares after EVERY call: the seven state arrays, every open snapshot, the call's own return value, the
+fused lidar rows, the action-mask words, the terminal-observation rows and the error flags.  The model is the CPU oracle for the live envs,
+snapshot_oracle.NumpySnapshot for the slots, key_table_oracle.KeyTableModel for the tables and the row-level reference functions of
+tests/*_oracle.py for everything a call returns; nothing in it calls the HIP library or the package's own host restatements of the contracts
+(path keys are hashed here from the rows path_key_oracle hands back, by state_key_oracle's rule).
+
+Every draw depends on the RandomState, the settings and the model alone - never on a value the env under test returned - and every draw of a call is
+made before the model decides whether the call is refused, so the walk of a seed is the same walk on every backend.  The one state-dependent exit is
+"Cannot place items": both sides must fail, and the case ends.
+
+What the env under test must offer beyond VecNovelGridworld's own surface: to_device(numpy array) -> what the device-input forms take, and
+ptr_of(that) -> what step_device_many / rollout_actions / graph_build take.  No GPU import at module level."""
+import os
+
+import numpy as np
+
+import expand_oracle as XO
+import key_table_oracle as KT
+import lookahead_oracle as LO
+import mask_oracle as M
+import ngw_testlib as T
+import path_key_oracle as KO
+import plan_oracle as PL
+import playout_oracle as PO
+import sample_oracle as SA
+import slot_observe_oracle as OO
+import slot_rollout_oracle as RO
+import snapshot_oracle as SO
+import state_key_oracle as SK
+import successor_key_oracle as SU
+import trajectory_oracle as TO
+from oracle import ngw_oracle as NO
+
+STATE_KEYS = SO.STATE_KEYS
+SUCC_MAX_MAP = 34                    # Snapshot.successor_keys: "Maps up to 34 x 34 ... beyond that the call raises" (MapsTooLarge)
+MAX_PAIRS, MAX_STEPS, MAX_PLANS = 130, 8, 3
+TABLE_CAPACITY = 2048                # 4096 buckets: a case offers at most ~2000 distinct keys, so probes collide and the table never fills
+FIELD_CHOICES = (SK.STATE, SK.ALL, SK.MAP | SK.POSE, SK.INV | SK.SELECTED, SK.STEP_COUNT | SK.EPISODE | SK.POSE, SK.MAP)
+
+# call kinds and how often each is drawn (tests/test_search_fuzz_cpu.py holds the coverage these give for the committed seed)
+KINDS = {
+    # writers of live state
+    'step': 3, 'dev': 2, 'rollout': 2, 'rollact': 2, 'reset': 2, 'mask_reset': 2, 'state_steps': 2, 'state_rows': 2, 'step_sampled': 2,
+    'restore': 4, 'fork': 2, 'graph_launch': 2,
+    # writers of slots only
+    'save': 2, 'copy': 2, 'expand': 4, 'expand_all': 2, 'srollout_kids': 4, 'splayout_kids': 4,
+    # read-only
+    'mask_words': 2, 'lookahead': 2, 'plans': 2, 'state_keys': 2, 'succ_keys': 2, 'insert_state_keys': 2, 'insert_succ_keys': 2, 'table_insert': 2,
+    'table_lookup': 2, 'sample': 2, 'playouts': 4, 'srollout': 4, 'splayout': 4, 'slot_lidar': 2, 'slot_view': 2, 'slot_masks': 2, 'slot_keys': 2,
+    'slot_unique': 2, 'slot_insert_keys': 2, 'agent_view': 2, 'lidar': 2,
+}
+READ_ONLY = ('mask_words', 'lookahead', 'plans', 'state_keys', 'succ_keys', 'insert_state_keys', 'insert_succ_keys', 'table_insert', 'table_lookup', 'sample',
+             'playouts', 'srollout', 'splayout', 'slot_lidar', 'slot_view', 'slot_masks', 'slot_keys', 'slot_unique', 'slot_insert_keys', 'agent_view', 'lidar')
+ROLLOUT_FORMS = ('plain', 'path', 'traj')
+PLAYOUT_FORMS = ('plain', 'weighted', 'path', 'traj')
+PLAYOUTS_FORMS = ('plain', 'weights', 'path_keys', 'rewards', 'masks', 'observe')
+
+
+class Refused(Exception):
+    """The model's prediction: the env under test must raise `error` (a class) for this call, and nothing may change."""
+
+    def __init__(self, error):
+        Exception.__init__(self, error.__name__)
+        self.error = error
+
+
+# ---------------------------------------------------------------- small helpers
+def host(x):
+    """A result of either kind (numpy / torch, a tuple of them, None) as numpy."""
+    if x is None:
+        return None
+    if isinstance(x, tuple):
+        return tuple(host(y) for y in x)
+    return x if isinstance(x, np.ndarray) else (x.cpu().numpy() if hasattr(x, 'cpu') else np.asarray(x))
+
+
+def same_bits(g, e):
+    """g seen in e's dtype where the two differ only in signedness / bool-ness (a tensor's int64 words are the host's uint64)."""
+    g, e = np.asarray(g), np.asarray(e)
+    if g.dtype != e.dtype:
+        if g.dtype.kind in 'iu' and e.dtype.kind in 'iu' and g.dtype.itemsize == e.dtype.itemsize:
+            g = np.ascontiguousarray(g).view(e.dtype)
+        elif e.dtype == np.bool_:
+            g = g.astype(np.bool_)
+        else:
+            g = g.astype(e.dtype)
+    return g
+
+
+def eq(name, g, e, where):
+    assert (g is None) == (e is None), "%s: %s is %s" % (where, name, 'missing' if g is None else 'not expected')
+    if e is None:
+        return
+    g = same_bits(host(g), e)
+    e = np.asarray(e)
+    assert g.shape == e.shape, "%s: %s shape %r expected %r" % (where, name, g.shape, e.shape)
+    bad = np.argwhere(g != e)
+    assert not len(bad), "%s: %s differs at %d of %d places, first %s: got %r expected %r" % (
+        where, name, len(bad), e.size, tuple(bad[0]), g[tuple(bad[0])], e[tuple(bad[0])])
+
+
+def fast_keys(rows, fields):
+    """uint64 [n]: state_key_oracle.keys_of(rows, 0 .. n-1, fields), every distinct value of a field hashed once (successor_key_oracle)."""
+    n = len(rows['facing'])
+    key = np.zeros(n, np.uint64)
+    if n:
+        for bit in SK.SINGLE:
+            if fields & bit:
+                key = key ^ SU.single_field_keys(rows, bit)
+    return key
+
+
+def rows_of(src):
+    """A dict of the seven arrays of an oracle State or a NumpySnapshot (views, not copies)."""
+    return src.rows if isinstance(src, SO.NumpySnapshot) else {k: getattr(src, k) for k in STATE_KEYS}
+
+
+def rows_at(src, idx):
+    r = rows_of(src)
+    idx = np.asarray(idx, np.int64)
+    return {k: r[k][idx] for k in STATE_KEYS}
+
+
+def ref_pairs(spec, rows, parents, kind, autoreset, horizon, plans=None, steps=None, seed=0, first_pair=0, weights=None, limits=None, path_keys=False,
+              fields=SK.STATE, rewards=False, masks=False, lc=None):
+    """What one rollout / playout call must return and leave, from the row-level references: -> dict(ends, rep, actions [T, count], keys, rewards,
+    masks, obs); the last four None where the call does not ask for them.  plans [count, T] for kind 'rollout'; weights [A] or None, steps and
+    seed for kind 'playout'; lc: the LidarConfig with observe='lidar'."""
+    parents = np.asarray(parents, np.int64)
+    if kind == 'playout':
+        if weights is None:
+            ends, rep, actions, _ = PO.oracle_playout(spec, rows, parents, steps, seed, first_pair, autoreset, horizon)
+        else:
+            ends, rep, actions, _ = SA.oracle_weighted_playout(spec, rows, parents, steps, seed, weights, first_pair, autoreset, horizon)
+    else:
+        plans = np.asarray(plans)
+        actions, steps = np.ascontiguousarray(plans.T), plans.shape[1]
+    out = dict(keys=None, rewards=None, masks=None, obs=None)
+    traj = rewards or masks or lc is not None
+    if not (traj or limits is not None or path_keys):
+        if kind == 'rollout':
+            ends, rep, _ = RO.oracle_slot_rollout(spec, rows, parents, plans, autoreset, horizon)
+    else:
+        if traj:
+            e = TO.oracle_traj(spec, rows, parents, actions, limits, autoreset, horizon, fields, lc)
+            ends, rp, states = e['ends'], e['reports'], e['states']
+            out.update(rewards=e['rewards'] if rewards else None, masks=e['masks'] if masks else None, obs=e['obs'])
+        else:
+            _, rp, ends, states, _ = KO.oracle_path(spec, rows, parents, actions, limits, autoreset, horizon, fields)
+        if kind == 'playout':                            # a limited playout is the prefix of the unlimited one: the actions beyond it are -1
+            actions = np.where(np.arange(steps)[:, None] < rp['length'][None, :], actions, -1).astype(np.int32)
+            rep = dict(rp, first_action=actions[0].copy())
+        else:
+            rep = rp
+        if path_keys:                                    # the key of every visited row, by state_key_oracle's rule
+            keys = np.zeros((steps, len(parents)), np.uint64)
+            at = sorted(states)
+            if at:
+                kk = fast_keys({k: np.stack([np.asarray(states[i][k]) for i in at]) for k in STATE_KEYS}, fields)
+                for (t, j), v in zip(at, kk):
+                    keys[t, j] = v
+            out['keys'] = keys
+    out.update(ends=ends, rep=rep, actions=np.asarray(actions, np.int32))
+    return out
+
+
+def check_pairs(got, exp, kind, record, where):
+    """A PlanEval / RolloutPath / RolloutTraj / Playout / PlayoutPath / PlayoutTraj (any leading shape) against ref_pairs' dict."""
+    steps = exp['actions'].shape[0]
+    for k in ('ret', 'length', 'ended', 'info') + (('first_action',) if kind == 'playout' else ()):
+        eq(k, host(getattr(got, k)).reshape(-1), exp['rep'][k], where)
+    if kind == 'playout':
+        eq('actions', None if got.actions is None else host(got.actions).reshape(steps, -1), exp['actions'] if record else None, where)
+    for k in ('keys', 'rewards', 'masks'):
+        g = getattr(got, k, None)
+        eq(k, None if g is None else host(g).reshape(steps, -1), exp[k], where)
+    g = getattr(got, 'obs', None)
+    eq('obs', None if g is None else TO.widen(g).reshape(steps + 1, -1, exp['obs'].shape[-1] if exp['obs'] is not None else 1), exp['obs'], where)
+
+
+def state_dict(st):
+    return {k: getattr(st, k).copy() for k in STATE_KEYS}
+
+
+# ---------------------------------------------------------------- one case
+class Case:
+    """The env under test, the model and the bookkeeping of one case."""
+
+    def __init__(self, rs, cfg, case, make_env, log):
+        self.rs, self.cfg, self.case, self.log = rs, cfg, case, log or (lambda *a: None)
+        spec = self.spec = T.build_spec(cfg)
+        self.A, self.S, self.K = len(spec.actions_id), spec.map_size, len(spec.items_id)
+        S = self.S
+        n = self.n = int(rs.choice([1, 63, 64, 65, 130])) if S <= 16 else int(rs.choice([1, 64, 65]))
+        self.horizon = int(rs.choice([0, 5, 23]))
+        self.autoreset = bool(rs.randint(0, 4)) or self.horizon > 0
+        prefetch = rs.choice(['auto', 0, 3])
+        self.prefetch = prefetch if prefetch == 'auto' else int(prefetch)
+        self.depth = int(rs.choice([0, 1, 2]))
+        self.term = bool(rs.randint(0, 4) == 0)
+        self.seed, self.base = int(rs.randint(0, 2 ** 31)), int(rs.randint(0, 10 ** 6))
+        self.small_block = bool(rs.randint(0, 2))
+        self.fused = bool(rs.randint(0, 2))
+        self.beams = int(rs.choice([4, 8]))
+        self.fmt = [np.int16, np.int32, 'packed'][int(rs.randint(0, 3))]
+        self.masks_on = bool(rs.randint(0, 2))
+        self.caps = [int(rs.choice([n, 2 * n + 3])), max(n, 3 * self.A)]
+        self.dev_forms = True
+        self.settings = 'n=%d H=%d auto=%d prefetch=%s depth=%d term=%d base=%d block=%d lidar=%s/%d/%s masks=%d caps=%s' % (
+            n, self.horizon, self.autoreset, self.prefetch, self.depth, self.term, self.base, self.small_block, 'fused' if self.fused else 'call', self.beams,
+            getattr(self.fmt, '__name__', self.fmt), self.masks_on, self.caps)
+        self.tag = '%s case %d (%s)' % (cfg, case, self.settings)
+        from gym_novel_gridworlds_amd.lidar import LidarConfig
+        self.lc = LidarConfig(spec, self.beams)
+        self.cc = self.lc.compile(spec)
+        zc = os.environ.pop('NGW_ZC_BYTES', None)        # the small page-locked block: set only around construction, then restored
+        if self.small_block:
+            os.environ['NGW_ZC_BYTES'] = '2048'
+        try:
+            self.v = make_env(spec=spec, num_envs=n, seed=self.seed, autoreset=self.autoreset, horizon=self.horizon, reset_prefetch=self.prefetch,
+                              env_index_base=self.base, reset_prefetch_depth=self.depth, terminal_capture=self.term)
+        finally:
+            os.environ.pop('NGW_ZC_BYTES', None)
+            if zc is not None:
+                os.environ['NGW_ZC_BYTES'] = zc
+        cs = spec.compile()
+        self.o = NO.Oracle(cs, n, seed=self.seed, autoreset=self.autoreset, horizon=self.horizon, env_index_base=self.base)
+        self.o2 = NO.Oracle(cs, n, autoreset=False)      # stepped beside the model where terminal rows are kept: the state an episode ended in
+        self.snaps = [SO.NumpySnapshot(S, self.K, c) for c in self.caps]
+        self.filled = [np.zeros(c, bool) for c in self.caps]      # never-saved slots are not read: a zero map has no walls to stop an agent
+        self.table, self.book = KT.KeyTableModel(), KT.WhereBook(0)
+        self.term_rows = dict(map=np.zeros((n, S * S), np.int8), loc=np.zeros((n, 2), np.int32), facing=np.zeros(n, np.int32), inv=np.zeros((n, self.K), np.int32))
+        self.term_known = np.zeros(n, bool)
+        self.ofail = 0
+        self.flags = 0
+        self.lidar_stale = False
+        self.t_roll = 0
+        self.graph = None
+
+    # -------------------------------------------------------------- the model's own steps
+    def mstep(self, a):
+        """One batched step of the model; with terminal capture on, the rows the ended episodes ended in are kept."""
+        o = self.o
+        a = np.ascontiguousarray(a, np.int32)
+        if self.term and self.autoreset:
+            for dst, src in zip(self.o2.st.arrays() + [self.o2.st.episode], o.st.arrays() + [o.st.episode]):
+                dst[...] = src
+            self.o2.step(a)
+        self.ofail |= int(o.step(a) != 0)
+        if self.term and self.autoreset:
+            idx = np.nonzero(o.done)[0]
+            for k in ('map', 'loc', 'facing', 'inv'):
+                self.term_rows[k][idx] = getattr(self.o2.st, k)[idx]
+            self.term_known[idx] = True
+        self.lidar_stale = False
+
+    def dev(self, a):
+        return self.v.to_device(np.ascontiguousarray(a))
+
+    def maybe_dev(self, a, on):
+        return self.dev(a) if on and a is not None else a
+
+    def idx(self, a):
+        return None if a is None else np.ascontiguousarray(a, np.int32)
+
+    def both_reset(self, mask):
+        v, o = self.v, self.o
+        try:
+            v.reset(mask)
+        except AssertionError as ex:
+            assert 'Cannot place items' in str(ex), self.tag
+            assert (o.reset(mask) if mask is not None else o.reset()) != 0, self.tag + ': only the env under test failed to place'
+            return False
+        assert (o.reset(mask) if mask is not None else o.reset()) == 0, self.tag + ': only the oracle failed to place'
+        self.lidar_stale = False
+        return True
+
+    # -------------------------------------------------------------- comparisons after every call
+    def check_all(self, where, after_steps_injection=False):
+        v, o = self.v, self.o
+        hs = v.get_state()
+        for k in STATE_KEYS:
+            bad = np.nonzero((hs[k] != getattr(o.st, k)).reshape(self.n, -1).any(1))[0]
+            assert bad.size == 0, "%s: %s differs for %d envs, first env %d" % (where, k, bad.size, bad[0])
+        for i, (snap, model) in enumerate(zip(self.vsnaps, self.snaps)):
+            XO.assert_rows(snap.state(), model.rows, '%s: snapshot %d' % (where, i))
+        if self.fused and not self.lidar_stale:
+            got = host(v.lidar_observation())
+            got = v.lidar_widen(got) if isinstance(got, tuple) else got
+            exp = NO.lidar(self.cc, self.S, self.K, o.st.map, o.st.loc, o.st.facing, o.st.inv)
+            bad = np.nonzero((got != exp).any(1))[0]
+            assert bad.size == 0, "%s: fused lidar rows differ for %d envs, first env %d" % (where, bad.size, bad[0])
+        if self.masks_on:
+            eq('action mask words', v.action_mask_words(), M.oracle_mask_words(self.spec, o.st), where)
+        if after_steps_injection:
+            return
+        if self.term:
+            got = v.terminal_observation()
+            idx = np.nonzero(self.term_known)[0]
+            for k, name in (('map', 'map'), ('loc', 'agent_location'), ('facing', 'agent_facing_id'), ('inv', 'inventory_items_quantity')):
+                g = np.asarray(got[name]).reshape(self.n, -1)[idx]
+                assert (g == self.term_rows[k].reshape(self.n, -1)[idx]).all(), "%s: terminal observation rows (%s) differ" % (where, name)
+        assert v.error_flags() == self.flags, "%s: error flags %#x, the model says %#x" % (where, v.error_flags(), self.flags)
+
+    # -------------------------------------------------------------- draws shared by the slot calls
+    def draw_source(self, rs, max_pairs, dst=None, need_dst=True):
+        """-> (source snapshot index or None for the live envs, destination snapshot index, parents, children): parents may repeat and name filled
+        slots (or envs) only, children are distinct slots of the destination and, inside one buffer, disjoint from the parents."""
+        from_envs = bool(rs.randint(0, 2))
+        d = int(rs.randint(0, 2)) if dst is None else dst
+        s = int(rs.randint(0, 2))
+        c = int(rs.randint(1, max_pairs + 1))
+        u, w = rs.randint(0, 1 << 30, c), rs.permutation(self.caps[d])
+        if not self.filled[s].any():
+            s = 0                                        # (snapshot 0 holds every env's state from the start of the case)
+        if from_envs:
+            parents, s = u % self.n, None
+            children = w[:c]
+        else:
+            live = np.nonzero(self.filled[s])[0]
+            parents = live[u % len(live)]
+            free = w[~np.isin(w, parents)] if s == d else w
+            if not len(free):                            # one buffer and no slot left beside the parents: the other snapshot takes the children
+                d = 1 - d
+                free = rs.permutation(self.caps[d])
+            children = free[:c]
+        if need_dst:
+            parents = parents[:len(children)]
+        return s, d, parents.astype(np.int32), children.astype(np.int32)
+
+    def src_rows(self, s):
+        return self.o.st if s is None else self.snaps[s]
+
+    def src_kw(self, s, d):
+        return dict(from_envs=True) if s is None else (dict(source=self.vsnaps[s]) if s != d else {})
+
+    def write_children(self, d, children, ends):
+        for k in STATE_KEYS:
+            self.snaps[d].rows[k][children] = ends[k]
+        self.filled[d][children] = True
+
+    def filled_slots(self, rs, max_count):
+        s = int(rs.randint(0, 2))
+        u = rs.randint(0, 1 << 30, int(rs.randint(1, max_count + 1)))
+        if not self.filled[s].any():
+            s = 0
+        live = np.nonzero(self.filled[s])[0]
+        return s, live[u % len(live)].astype(np.int32)
+
+    def envs_list(self, rs, max_count):
+        """None (every env) one time in three, else a list with repeats."""
+        u = rs.randint(0, 1 << 30, int(rs.randint(1, max_count + 1)))
+        return None if rs.randint(0, 3) == 0 else (u % self.n).astype(np.int32)
+
+    def draw_keys(self, rs, count):
+        """Keys for the table's own calls: some it holds, some new, a zero, and repeats."""
+        held = list(self.table.order)
+        fresh = [int(x) for x in rs.randint(1, 1 << 62, count)]
+        pick = rs.randint(0, 4, count)
+        at = rs.randint(0, 1 << 30, count)
+        keys = []
+        for j in range(count):
+            if pick[j] == 0 and held:
+                keys.append(held[at[j] % len(held)])
+            elif pick[j] == 1 and keys:
+                keys.append(keys[at[j] % len(keys)])
+            elif pick[j] == 2 and at[j] % 4 == 0:
+                keys.append(0)
+            else:
+                keys.append(fresh[j])
+        return np.array(keys, np.uint64)
+
+    def check_insert(self, keys, found, where):
+        fresh, stored = self.table.insert(keys)
+        eq('fresh', host(found.fresh).reshape(-1), fresh, where)
+        self.book.check(keys, host(found.where).reshape(-1), stored, where)
+        assert len(self.vtable) == len(self.table), "%s: the table holds %d keys, the model %d" % (where, len(self.vtable), len(self.table))
+
+    # -------------------------------------------------------------- the calls
+    def call(self, kind, where):
+        """Draws, predicts, performs and compares one call.  -> the form it took (for the coverage count) or raises Refused."""
+        rs, v, o, n, A, spec = self.rs, self.v, self.o, self.n, self.A, self.spec
+        on_dev = bool(rs.randint(0, 2))
+        ar, H = self.autoreset, self.horizon
+        form = ''
+        if kind == 'step':
+            for _ in range(int(rs.randint(1, 5))):
+                a = rs.randint(0, A, size=n).astype(np.int32)
+                self.mstep(a)
+                obs, reward, done, info = v.step(a)
+                assert (reward == o.reward).all() and (done == o.done.astype(bool)).all() and (info['message_code'] == o.msg_code).all(), where
+                if not self.ofail:
+                    assert (np.asarray(obs['map']).reshape(n, -1) == o.st.map).all() and (obs['inventory_items_quantity'] == o.st.inv).all(), where + ': host observation'
+                    assert (obs['agent_location'] == o.st.loc).all() and (obs['agent_facing_id'] == o.st.facing).all(), where + ': host observation'
+                    if self.fused:                        # the rows the host step itself delivered (write-through / copy behind the launch)
+                        got = host(v.lidar_observation())
+                        got = v.lidar_widen(got) if isinstance(got, tuple) else got
+                        assert (got == NO.lidar(self.cc, self.S, self.K, o.st.map, o.st.loc, o.st.facing, o.st.inv)).all(), where + ': lidar rows of the host step'
+        elif kind in ('dev', 'rollact'):
+            k = int(rs.randint(1, MAX_STEPS + 1))
+            an = rs.randint(0, A, size=(k, n)).astype(np.int32)
+            acts = self.dev(an)
+            for i in range(k):
+                self.mstep(an[i])
+            (v.step_device_many if kind == 'dev' else v.rollout_actions)(v.ptr_of(acts), n, k)
+        elif kind == 'rollout':
+            k = int(rs.randint(1, 30))
+            if not ar and rs.randint(0, 2):
+                k = 1 + k % 4
+            before = o.st.episode.copy()
+            self.ofail |= int(o.rollout(k, self.seed ^ 77, self.t_roll) != 0)
+            v.rollout(k, action_seed=self.seed ^ 77, t0=self.t_roll)
+            self.t_roll += k
+            self.term_known &= o.st.episode == before     # (generated actions: the model has no per-step view of where these episodes ended)
+            self.lidar_stale = False
+        elif kind in ('reset', 'mask_reset'):
+            m = (rs.randint(0, 3, size=n) == 0).astype(np.uint8) if kind == 'mask_reset' else None
+            if not self.both_reset(m):
+                return None
+        elif kind == 'state_steps':
+            sc = rs.randint(0, max(H, 5), size=n).astype(np.int32)
+            v.set_state(0, step_count=sc)
+            o.st.step_count[:] = sc
+        elif kind == 'state_rows':                          # map, pose and inventory rows of other envs of the model, over a run of envs
+            m = int(rs.randint(1, n + 1))
+            first = int(rs.randint(0, n - m + 1))
+            src = rs.randint(0, n, m)
+            rows = {k: getattr(o.st, k)[src].copy() for k in ('map', 'loc', 'inv')}
+            v.set_state(first, map=rows['map'], loc=rows['loc'], inv=rows['inv'])
+            for k in rows:
+                getattr(o.st, k)[first:first + m] = rows[k]
+            self.lidar_stale = True                       # (no launch: the fused rows are the last launch's)
+        elif kind == 'step_sampled':
+            w = SA.random_weights(rs, n, A)
+            seed, t = int(rs.randint(0, 2 ** 31)), int(rs.randint(0, 1000))
+            exp = SA.oracle_sample(spec, o.st, np.arange(n), w, seed, self.base, t)
+            self.mstep(exp[0])
+            got = v.step_sampled(self.dev(np.ascontiguousarray(w.T)) if on_dev else w, seed, t)
+            v.sync()
+            g = host(tuple(got))
+            SA.assert_sampled((g[0], g[1], same_bits(g[2], np.zeros(0, np.uint64))), exp, where)
+        elif kind == 'restore':
+            keep = bool(rs.randint(0, 2))
+            s, slots = self.filled_slots(rs, n)
+            envs = rs.permutation(n)[:len(slots)].astype(np.int32)
+            if self.filled[s][:n].all() and self.caps[s] >= n and rs.randint(0, 4) == 0:
+                slots = envs = None                       # the whole batch, no lists
+            else:
+                slots = slots[:len(envs)]
+            self.snaps[s].restore(o.st, slots, envs, keep)
+            self.vsnaps[s].restore(slots=self.maybe_dev(slots, on_dev), envs=self.maybe_dev(envs, on_dev), keep_episode=keep)
+            self.lidar_stale = False
+            form = 'keep' if keep else 'episode'
+        elif kind == 'fork':
+            keep = bool(rs.randint(0, 2))
+            src = rs.randint(0, n, n).astype(np.int32)
+            tmp = SO.NumpySnapshot(self.S, self.K, n)
+            tmp.save(o.st)
+            tmp.restore(o.st, src, None, keep)
+            v.fork(self.maybe_dev(src, on_dev), keep_episode=keep)
+            self.lidar_stale = False
+        elif kind == 'graph_launch':
+            reps = int(rs.randint(1, 3))
+            for _ in range(reps):
+                for a in self.graph[0]:
+                    self.mstep(a)
+            v.graph_launch(reps)
+        elif kind == 'save':
+            d = int(rs.randint(0, 2))
+            c = int(rs.randint(1, min(n, self.caps[d]) + 1))
+            envs, slots = rs.randint(0, n, c).astype(np.int32), rs.permutation(self.caps[d])[:c].astype(np.int32)
+            self.snaps[d].save(o.st, envs, slots)
+            self.filled[d][slots] = True
+            self.vsnaps[d].save(envs=self.maybe_dev(envs, on_dev), slots=self.maybe_dev(slots, on_dev))
+        elif kind == 'copy':
+            s, d, src, dst = self.draw_source_slots(rs)
+            for k in STATE_KEYS:
+                self.snaps[d].rows[k][dst] = self.snaps[s].rows[k][src]
+            self.filled[d][dst] = True
+            self.vsnaps[d].copy(self.maybe_dev(src, on_dev), self.maybe_dev(dst, on_dev), source=None if s == d else self.vsnaps[s])
+            form = 'within' if s == d else 'between'
+        elif kind == 'expand':
+            s, d, parents, children = self.draw_source(rs, MAX_PAIRS)
+            actions = rs.randint(0, A, len(parents)).astype(np.int32)
+            kids, rep = XO.oracle_expand(spec, rows_of(self.src_rows(s)), parents, actions, ar, H)
+            self.write_children(d, children, kids)
+            got = self.vsnaps[d].expand(self.maybe_dev(parents, on_dev), self.maybe_dev(actions, on_dev), self.maybe_dev(children, on_dev), device=on_dev,
+                                        **self.src_kw(s, d))
+            for k in ('reward', 'done', 'result', 'info'):
+                eq(k, got[k], rep[k], where)
+            form = 'envs' if s is None else 'slots'
+        elif kind == 'expand_all':
+            s, _, parents, _ = self.draw_source(rs, 3, dst=1, need_dst=False)
+            if s == 1:                                    # (the children go to snapshot 1: the parents come from the envs or snapshot 0)
+                s, parents = 0, (parents % n).astype(np.int32)
+            first = int(rs.randint(0, self.caps[1] - len(parents) * A + 1))
+            pp, aa = np.repeat(parents, A), np.tile(np.arange(A), len(parents))
+            kids, rep = XO.oracle_expand(spec, rows_of(self.src_rows(s)), pp, aa, ar, H)
+            self.write_children(1, first + np.arange(len(pp)), kids)
+            got = self.vsnaps[1].expand_all(self.maybe_dev(parents, on_dev), first, device=on_dev, **self.src_kw(s, 1))
+            for k in ('reward', 'done', 'result', 'info'):
+                eq(k, host(got[k]).reshape(-1), rep[k], where)
+                assert tuple(got[k].shape) == (len(parents), A), where
+            form = 'envs' if s is None else 'slots'
+        elif kind in ('srollout', 'srollout_kids', 'splayout', 'splayout_kids'):
+            form = self.pair_call(kind, where, on_dev)
+        elif kind == 'playouts':
+            form = PLAYOUTS_FORMS[int(rs.randint(0, len(PLAYOUTS_FORMS)))]
+            P = int(rs.randint(1, min(MAX_PLANS, MAX_PAIRS // n) + 1))
+            steps, seed = int(rs.randint(1, MAX_STEPS + 1)), int(rs.randint(0, 2 ** 31))
+            w = (rs.rand(A) * (rs.rand(A) < 0.8)).astype(np.float32)
+            fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
+            kw, rkw = {}, {}
+            if form == 'weights':
+                kw['weights'], rkw['weights'] = (self.dev(w) if on_dev else w), w
+            elif form == 'path_keys':
+                kw.update(path_keys=True, fields=fields); rkw.update(path_keys=True, fields=fields)
+            elif form == 'rewards':
+                kw['rewards'] = rkw['rewards'] = True
+            elif form == 'masks':
+                kw['masks'] = rkw['masks'] = True
+            elif form == 'observe':
+                kw['observe'], rkw['lc'] = 'lidar', self.lc
+            exp = ref_pairs(spec, rows_of(o.st), np.repeat(np.arange(n), P), 'playout', ar, H, steps=steps, seed=seed, first_pair=self.base * P, **rkw)
+            got = v.playouts(P, steps, seed, device=on_dev, **kw)
+            assert tuple(got.ret.shape) == (n, P), where
+            check_pairs(got, exp, 'playout', False, where)
+        elif kind == 'mask_words':
+            eq('action mask words', v.action_mask_words(device=on_dev, copy=bool(rs.randint(0, 2))), M.oracle_mask_words(spec, o.st), where)
+        elif kind == 'lookahead':
+            exp = LO.oracle_lookahead(spec, o.st, ar, H)
+            got = v.lookahead(device=on_dev, copy=bool(rs.randint(0, 2)))
+            for k in ('reward', 'done', 'result', 'info'):
+                eq(k, got[k], exp[k], where)
+        elif kind == 'plans':
+            P, steps = int(rs.randint(1, MAX_PLANS + 1)), int(rs.randint(1, MAX_STEPS + 1))
+            plans = rs.randint(0, A, (n, P, steps)).astype(np.int32)
+            exp = PL.oracle_plans(spec, o.st, plans, ar, H)
+            got = v.evaluate_plans(self.dev(np.ascontiguousarray(plans.transpose(2, 1, 0))) if on_dev else plans, device=bool(rs.randint(0, 2)))
+            for k in ('ret', 'length', 'ended', 'info'):
+                eq(k, got[k], exp[k], where)
+        elif kind in ('state_keys', 'insert_state_keys'):
+            envs = self.envs_list(rs, MAX_PAIRS)
+            fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
+            exp = fast_keys(rows_at(o.st, np.arange(n) if envs is None else envs), fields)
+            if kind == 'state_keys':
+                eq('keys', v.state_keys(self.maybe_dev(envs, on_dev), fields, device=on_dev), exp, where)
+            else:
+                keys, found = v.insert_state_keys(self.vtable, self.maybe_dev(envs, on_dev), fields, device=on_dev)
+                eq('keys', keys, exp, where)
+                self.check_insert(exp, found, where)
+        elif kind in ('succ_keys', 'insert_succ_keys'):
+            envs = self.envs_list(rs, MAX_PAIRS if kind == 'succ_keys' else 8)
+            if kind == 'insert_succ_keys' and envs is None:
+                envs = np.arange(min(n, 8), dtype=np.int32)
+            fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
+            reports = bool(rs.randint(0, 4))
+            if self.S > SUCC_MAX_MAP:
+                from gym_novel_gridworlds_amd.snapshot import MapsTooLarge
+                raise Refused(MapsTooLarge)
+            ex = SU.Successors(spec, o.st, np.arange(n) if envs is None else envs, ar, H)
+            if kind == 'succ_keys':
+                SU.assert_successors(v.successor_keys(self.maybe_dev(envs, on_dev), fields, device=on_dev, reports=reports), ex, fields, where, reports)
+            else:
+                got, found = v.insert_successor_keys(self.vtable, self.maybe_dev(envs, on_dev), fields, device=on_dev)
+                SU.assert_successors(got, ex, fields, where)
+                assert tuple(found.fresh.shape) == tuple(ex.keys(fields).shape), where
+                self.check_insert(ex.keys(fields).reshape(-1), found, where)
+        elif kind == 'table_insert':
+            keys = self.draw_keys(rs, int(rs.randint(1, 65)))
+            found = self.vtable.insert(self.dev(keys.view(np.int64)) if on_dev else (keys if rs.randint(0, 2) else keys.view(np.int64)), device=on_dev)
+            self.check_insert(keys, found, where)
+        elif kind == 'table_lookup':
+            keys = self.draw_keys(rs, int(rs.randint(1, 65)))
+            where_ = self.vtable.lookup(self.dev(keys.view(np.int64)) if on_dev else keys, device=on_dev)
+            self.book.check(keys, host(where_), self.table.contains(keys), where)
+            assert len(self.vtable) == len(self.table), where
+        elif kind == 'sample':
+            envs = self.envs_list(rs, MAX_PAIRS)
+            idx = np.arange(n) if envs is None else envs
+            w = SA.random_weights(rs, len(idx), A)
+            seed, t = int(rs.randint(0, 2 ** 31)), int(rs.randint(0, 1000))
+            exp = SA.oracle_sample(spec, o.st, idx, w, seed, self.base, t)
+            got = v.sample_actions(self.dev(np.ascontiguousarray(w.T)) if on_dev else w, seed, t, self.maybe_dev(envs, on_dev), device=on_dev)
+            g = host(tuple(got))
+            SA.assert_sampled((g[0], g[1], same_bits(g[2], np.zeros(0, np.uint64))), exp, where)
+        elif kind in ('slot_lidar', 'slot_view', 'slot_masks', 'slot_keys', 'slot_unique', 'slot_insert_keys'):
+            s, slots = self.filled_slots(rs, MAX_PAIRS)
+            snap, rows, arg = self.vsnaps[s], self.snaps[s].rows, self.maybe_dev(slots, on_dev)
+            fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
+            V = int(rs.choice([1, 2, 5]))
+            if kind == 'slot_lidar':
+                OO.assert_lidar(v, snap.lidar_observation(arg, device=on_dev), spec, self.lc, rows, slots, where)
+            elif kind == 'slot_view':
+                OO.assert_view(snap.agent_view(arg, V, device=on_dev), rows, slots, V, where)
+            elif kind == 'slot_masks':
+                OO.assert_masks(snap.action_masks(arg, device=on_dev), spec, rows, slots, where)
+            else:
+                exp = fast_keys(rows_at(self.snaps[s], slots), fields)
+                if kind == 'slot_keys':
+                    eq('keys', snap.keys(arg, fields, device=on_dev), exp, where)
+                elif kind == 'slot_unique':
+                    first, inverse = host(tuple(snap.unique(arg, fields, device=on_dev)))
+                    seen = {}
+                    want = np.array([seen.setdefault(int(k), j) for j, k in enumerate(exp.tolist())], np.int64)
+                    eq('unique: the first position of every group', np.asarray(first)[np.asarray(inverse)], want, where)
+                    assert len(first) == len(seen), where
+                else:
+                    keys, found = snap.insert_keys(self.vtable, arg, fields, device=on_dev)
+                    eq('keys', keys, exp, where)
+                    self.check_insert(exp, found, where)
+        elif kind == 'agent_view':
+            V = int(rs.choice([1, 2, 5]))
+            eq('agent view', v.agent_view(V, device=on_dev, copy=bool(rs.randint(0, 2))), NO.agent_view(o.st.map, o.st.loc, V), where)
+        elif kind == 'lidar':
+            got = host(v.lidar_observation(device=on_dev))
+            if not (self.fused and self.lidar_stale):     # (fused: the rows are the last launch's, and set_state launches nothing)
+                eq('lidar rows', v.lidar_widen(got) if isinstance(got, tuple) else got, NO.lidar(self.cc, self.S, self.K, o.st.map, o.st.loc, o.st.facing, o.st.inv), where)
+        else:
+            raise AssertionError('unknown call kind ' + kind)
+        return form
+
+    def draw_source_slots(self, rs):
+        """A slot-to-slot copy: -> (source snapshot, destination snapshot, src slots - filled, may repeat -, dst slots - distinct, and inside one
+        buffer no source)."""
+        s, d = int(rs.randint(0, 2)), int(rs.randint(0, 2))
+        c = int(rs.randint(1, min(MAX_PAIRS, max(1, self.caps[d] // 2)) + 1))
+        u, w = rs.randint(0, 1 << 30, c), rs.permutation(self.caps[d])
+        if not self.filled[s].any():
+            s = 0
+        live = np.nonzero(self.filled[s])[0]
+        src = live[u % len(live)]
+        free = w[~np.isin(w, src)] if s == d else w
+        if not len(free):
+            d = 1 - d
+            free = rs.permutation(self.caps[d])
+        dst = free[:c]
+        return s, d, src[:len(dst)].astype(np.int32), dst.astype(np.int32)
+
+    def pair_call(self, kind, where, on_dev):
+        """Snapshot.rollout / Snapshot.playout, with and without children, every form from slots and from the live envs."""
+        rs, spec, A = self.rs, self.spec, self.A
+        playout, kids = kind.startswith('splayout'), kind.endswith('_kids')
+        forms = PLAYOUT_FORMS if playout else ROLLOUT_FORMS
+        form = forms[int(rs.randint(0, len(forms)))]
+        s, d, parents, children = self.draw_source(rs, MAX_PAIRS, need_dst=kids)
+        if not kids:
+            children = None
+        count = len(parents)
+        steps, seed, first_pair = int(rs.randint(1, MAX_STEPS + 1)), int(rs.randint(0, 2 ** 31)), int(rs.randint(0, 2 ** 40))
+        plans = rs.randint(0, A, (count, steps)).astype(np.int32)
+        w = (rs.rand(A) * (rs.rand(A) < 0.8)).astype(np.float32)
+        limits = rs.randint(0, steps + 1, count).astype(np.int32) if rs.randint(0, 2) else None
+        fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
+        record, with_keys, with_obs, with_masks = bool(rs.randint(0, 2)), bool(rs.randint(0, 2)), bool(rs.randint(0, 2)), bool(rs.randint(0, 2))
+        kw, rkw = {}, {}
+        if form == 'weighted' or (playout and form != 'plain' and rs.randint(0, 3) == 0):
+            kw['weights'], rkw['weights'] = (self.dev(w) if on_dev else w), w
+        if form in ('path', 'traj'):
+            if limits is not None:
+                kw['limits'], rkw['limits'] = self.maybe_dev(limits, on_dev), limits
+            if with_keys or (form == 'path' and limits is None):
+                kw.update(path_keys=True, fields=fields); rkw.update(path_keys=True, fields=fields)
+        if form == 'traj':
+            kw['rewards'] = rkw['rewards'] = True
+            if with_obs:
+                kw['observe'], rkw['lc'] = 'lidar', self.lc
+            if playout and with_masks:
+                kw['masks'] = rkw['masks'] = True
+        if playout:
+            exp = ref_pairs(spec, rows_of(self.src_rows(s)), parents, 'playout', self.autoreset, self.horizon, steps=steps, seed=seed, first_pair=first_pair, **rkw)
+        else:
+            exp = ref_pairs(spec, rows_of(self.src_rows(s)), parents, 'rollout', self.autoreset, self.horizon, plans=plans, **rkw)
+        if kids:
+            self.write_children(d, children, exp['ends'])
+        snap, src = self.vsnaps[d], self.src_kw(s, d)
+        p, c = self.maybe_dev(parents, on_dev), self.maybe_dev(children, on_dev)
+        if playout:
+            got = snap.playout(p, steps, seed, children=c, first_pair=first_pair, record=record, device=on_dev, **src, **kw)
+        else:
+            got = snap.rollout(p, self.dev(np.ascontiguousarray(plans.T)) if on_dev else plans, children=c, device=on_dev, **src, **kw)
+        check_pairs(got, exp, 'playout' if playout else 'rollout', record, where)
+        return '%s/%s' % (form, 'envs' if s is None else 'slots')
+
+    # -------------------------------------------------------------- the walk
+    def run(self):
+        rs, v, o, n, A = self.rs, self.v, self.o, self.n, self.A
+        tag, log = self.tag, self.log
+        v.lidar_configure(self.lc, fused=self.fused, dtype=self.fmt)
+        if self.masks_on:
+            v.set_action_masks(True)
+        self.vsnaps = [v.snapshot(c) for c in self.caps]
+        self.vtable = v.key_table(TABLE_CAPACITY)
+        self.book = KT.WhereBook(self.vtable.buckets)
+        names = sorted(KINDS)
+        p = np.array([KINDS[k] for k in names], np.float64)
+        p /= p.sum()
+        n_calls = int(rs.randint(6, 13))
+        kinds = [names[i] for i in rs.choice(len(names), n_calls, p=p)]
+        gk = int(rs.randint(1, 4))
+        gacts = rs.randint(0, A, size=(gk, n)).astype(np.int32)
+        if not self.both_reset(None):
+            log('(case)', 'placement', '')
+            v.close()
+            return
+        self.snaps[0].save(o.st, np.arange(n), np.arange(n))   # every env's first state: slots 0 .. n-1 of snapshot 0 stay readable all case long
+        self.filled[0][:n] = True
+        self.vsnaps[0].save(envs=np.arange(n), slots=np.arange(n))
+        self.graph = (gacts, self.dev(gacts))               # one graph, built early; graph_launch is a call kind
+        v.graph_build(v.ptr_of(self.graph[1]), n, gk)
+        self.check_all(tag + ' setup')
+        try:
+            for call, kind in enumerate(kinds):
+                where = '%s call %d %s' % (tag, call, kind)
+                if kind in READ_ONLY:
+                    before = state_dict(o.st)
+                try:
+                    form = self.call(kind, where)
+                except Refused as r:
+                    try:
+                        self.perform_refused(kind)
+                    except r.error:
+                        pass
+                    else:
+                        raise AssertionError('%s: the model predicts %s, the env under test raised nothing' % (where, r.error.__name__))
+                    log(kind, 'refused', '')
+                    self.check_all(where + ' (refused)')
+                    continue
+                except AssertionError:
+                    raise
+                except Exception as ex:                   # a refusal the model did not predict
+                    raise AssertionError('%s: %s: %s' % (where, type(ex).__name__, ex))
+                if form is None:                          # a reset that could not place its items, on both sides
+                    log('(case)', 'placement', kind)
+                    break
+                log(kind, 'executed', form)
+                if self.ofail:                            # an in-step reset could not place its items: the env under test must say so too
+                    try:
+                        v.get_state(); v._raise_flags()
+                    except AssertionError as ex:
+                        assert 'Cannot place items' in str(ex), where
+                    else:
+                        raise AssertionError(where + ': only the oracle failed to place')
+                    log('(case)', 'placement', kind)
+                    break
+                if kind in READ_ONLY:
+                    assert all((before[k] == getattr(o.st, k)).all() for k in STATE_KEYS), where + ': the model itself moved'
+                self.check_all(where, after_steps_injection=kind == 'state_steps')
+            else:
+                log('(case)', 'completed', '')
+        except AssertionError as ex:
+            if 'Cannot place items' not in str(ex) or not self.ofail:
+                raise
+            log('(case)', 'placement', '')
+        v.close()
+
+    def perform_refused(self, kind):
+        """The refused call on the env under test, in its simplest form (the refusal does not depend on the arguments)."""
+        if kind == 'succ_keys':
+            self.v.successor_keys()
+        elif kind == 'insert_succ_keys':
+            self.v.insert_successor_keys(self.vtable, np.zeros(1, np.int32))
+        else:
+            raise AssertionError('no refusal is documented for ' + kind)
+
+
+def run_case(rs, cfg, case, make_env, log=None):
+    """One whole case: settings and calls drawn from `rs`, performed on make_env(...)'s env and on the model, compared after every call."""
+    Case(rs, cfg, case, make_env, log).run()
+
+
+def chunk_cfgs(chunk, chunks):
+    return sorted(T.CFGS)[chunk::chunks]

@@ -1,0 +1,290 @@
+"""An oracle-backed stand-in with the whole search surface of VecNovelGridworld, for the CPU walk of tests/search_fuzz.py: the existing
+stand-ins composed by inheritance (trajectory_oracle.OracleVecTraj and its bases, successor_key_oracle.OracleVecSuccessors,
+lookahead_oracle.OracleVecLook, plan_oracle.OracleVecPlans, key_table_oracle.stand_in_table for the table's host checks) and the surface they lack
+written from the row-level reference functions.  Settings it has no notion of are accepted and ignored (prepared episodes, the page-locked block,
+the fused lidar's format); a "device" input is the host array in the device form's layout, wrapped in Dev.  No GPU."""
+import numpy as np
+
+import key_table_oracle as KT
+import lookahead_oracle as LO
+import mask_oracle as M
+import plan_oracle as PL
+import playout_oracle as PO
+import sample_oracle as SA
+import search_fuzz as F
+import slot_observe_oracle as OO
+import snapshot_oracle as SO
+import state_key_oracle as SK
+import successor_key_oracle as SU
+import trajectory_oracle as TO
+from gym_novel_gridworlds_amd.key_table import KeyInsert, check_keys
+from gym_novel_gridworlds_amd.playout import Playout, PlayoutPath, PlayoutTraj
+from gym_novel_gridworlds_amd.sample import Sampled
+from gym_novel_gridworlds_amd.snapshot import Expansion, MapsTooLarge, SuccessorKeys, insert_successors
+from gym_novel_gridworlds_amd.state_keys import unique_of_keys
+from gym_novel_gridworlds_amd.vec_env import PLACEMENT_MESSAGE, PlanEval, RolloutPath, RolloutTraj
+from oracle import ngw_oracle as NO
+
+STATE_KEYS = SO.STATE_KEYS
+
+
+class Dev:
+    """A host array that stands for a device tensor: the layout is the device form's."""
+
+    def __init__(self, a):
+        self.a = np.ascontiguousarray(a)
+
+
+def un(x):
+    return x.a if isinstance(x, Dev) else x
+
+
+def is_dev(x):
+    return isinstance(x, Dev)
+
+
+def pair_result(kind, e, record, path_keys, traj):
+    rep = e['rep']
+    if kind == 'rollout':
+        head = [rep['ret'], rep['length'], rep['ended'], rep['info']]
+        if traj:
+            return RolloutTraj(*head, e['keys'], e['rewards'], e['obs'])
+        return RolloutPath(*head, e['keys']) if path_keys else PlanEval(*head)
+    head = [rep['ret'], rep['length'], rep['ended'], rep['info'], rep['first_action'], e['actions'] if record else None]
+    if traj:
+        return PlayoutTraj(*head, e['keys'], e['rewards'], e['masks'], e['obs'])
+    return PlayoutPath(*head, e['keys']) if path_keys else Playout(*head)
+
+
+class StandInSnapshot(PO._BoundPlayoutSnapshot, SU._BoundSuccessorSnapshot):
+    """The bound snapshots of the existing stand-ins, with every form of rollout / playout, copy, the slot observers, keys and the key-table calls."""
+
+    def save(self, envs=None, slots=None):
+        super().save(un(envs), un(slots))
+
+    def restore(self, slots=None, envs=None, keep_episode=False):
+        super().restore(un(slots), un(envs), keep_episode)
+
+    def copy(self, src_slots, dst_slots, source=None):
+        src = self if source is None else source
+        for k in STATE_KEYS:
+            self.model.rows[k][un(dst_slots)] = src.model.rows[k][un(src_slots)]
+
+    def _parent_rows(self, from_envs, source):
+        return self.env.o.st if from_envs else (self if source is None else source).model
+
+    def expand(self, parents, actions, children, from_envs=False, source=None, device=False):
+        return super().expand(un(parents), un(actions), un(children), from_envs=from_envs, source=source)
+
+    def expand_all(self, parents, first_child, from_envs=False, source=None, device=False):
+        return super().expand_all(un(parents), first_child, from_envs=from_envs, source=source)
+
+    def _pairs(self, kind, parents, children, from_envs, source, record=False, **kw):
+        env = self.env
+        lc = env.lidar if kw.pop('observe', None) is not None else None
+        traj = lc is not None or kw.get('rewards') or kw.get('masks')
+        kw['limits'] = un(kw.get('limits'))
+        kw['weights'] = un(kw.get('weights'))
+        if kind == 'rollout':
+            kw.pop('weights')
+        if kw.get('fields') is None:
+            kw['fields'] = SK.STATE
+        e = F.ref_pairs(env.spec, F.rows_of(self._parent_rows(from_envs, source)), un(parents), kind, env.o.autoreset, env.o.horizon, lc=lc, **kw)
+        if children is not None:
+            for k in STATE_KEYS:
+                self.model.rows[k][un(children)] = e['ends'][k]
+        return pair_result(kind, e, record, kw.get('path_keys'), traj)
+
+    def rollout(self, parents, plans, children=None, from_envs=False, source=None, device=False, limits=None, path_keys=False, fields=SK.STATE, rewards=False,
+                masks=False, observe=None):
+        plans = un(plans).T if is_dev(plans) else np.asarray(plans)
+        return self._pairs('rollout', parents, children, from_envs, source, plans=plans, limits=limits, path_keys=path_keys, fields=fields, rewards=rewards,
+                           observe=observe)
+
+    def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False, weights=None, limits=None,
+                path_keys=False, fields=SK.STATE, rewards=False, masks=False, observe=None):
+        return self._pairs('playout', parents, children, from_envs, source, record=record, steps=steps, seed=seed, first_pair=first_pair, weights=weights,
+                           limits=limits, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe)
+
+    def lidar_observation(self, slots=None, device=False):
+        return OO.expect_lidar(self.env.spec, self.env.lidar, self.model.rows, un(slots))
+
+    def agent_view(self, slots=None, view_size=5, device=False):
+        return OO.expect_view(self.model.rows, un(slots), view_size)
+
+    def action_masks(self, slots=None, device=False):
+        return OO.expect_masks(self.env.spec, self.model.rows, un(slots))
+
+    def keys(self, slots=None, fields=SK.STATE, device=False):
+        return F.fast_keys(F.rows_at(self.model, un(slots)), fields)
+
+    def unique(self, slots=None, fields=SK.STATE, device=False):
+        return unique_of_keys(self.keys(slots, fields))
+
+    def insert_keys(self, table, slots=None, fields=SK.STATE, device=False):
+        keys = self.keys(slots, fields)
+        return keys, table.insert(keys)
+
+    def successor_keys(self, slots=None, fields=SK.STATE, device=False, reports=True):
+        self.env._succ_limit()
+        return super().successor_keys(un(slots), fields, reports=reports)
+
+
+class StandInTable:
+    """KeyTable over key_table_oracle's model; the host-side argument checks are the product's (a stand_in_table runs them)."""
+
+    def __init__(self, env, capacity):
+        self.checks = KT.stand_in_table(capacity, env)
+        self.buckets, self.capacity, self.model = self.checks.buckets, capacity, KT.KeyTableModel()
+
+    def _keys(self, keys):
+        k, _ = check_keys(un(keys))
+        return k.view(np.uint64)
+
+    def insert(self, keys, device=False):
+        k = self._keys(keys)
+        fresh, stored = self.model.insert(k)
+        where = np.array([self.model.order[int(x)] if s else -1 for x, s in zip(k.tolist(), stored)], np.int32).reshape(len(k))
+        return KeyInsert(where, fresh)
+
+    def lookup(self, keys, device=False):
+        return np.array([self.model.order.get(int(x), -1) for x in self._keys(keys).tolist()], np.int32)
+
+    def __len__(self):
+        return len(self.model)
+
+
+class StandIn(TO.OracleVecTraj, SU.OracleVecSuccessors, LO.OracleVecLook, PL.OracleVecPlans):
+    device = 0
+
+    def __init__(self, spec, num_envs=1, seed=0, autoreset=False, horizon=0, env_index_base=0, terminal_capture=False, **ignored):
+        super().__init__(spec, num_envs, seed=seed, env_index_base=env_index_base, autoreset=autoreset, horizon=horizon)
+        self.term_on, self._flags, self._graph = bool(terminal_capture), 0, None
+        n, S, K = num_envs, spec.map_size, len(spec.items_id)
+        self._term = dict(map=np.zeros((n, S, S), np.int8), agent_location=np.zeros((n, 2), np.int32), agent_facing_id=np.zeros(n, np.int32),
+                          inventory_items_quantity=np.zeros((n, K), np.int32))
+
+    _h = True
+
+    def to_device(self, a):
+        return Dev(a)
+
+    def ptr_of(self, x):
+        return x
+
+    # ---- the handle's own calls
+    def _step(self, a):
+        o = self.o
+        a = np.ascontiguousarray(a, np.int32)
+        if self.term_on and o.autoreset:
+            o2 = NO.Oracle(o.cspec, o.n, autoreset=False)
+            o2.st = o.st.copy()
+            o2.step(a)
+        self._flags |= int(o.step(a))
+        if self.term_on and o.autoreset:
+            idx = np.nonzero(o.done)[0]
+            t = self._term
+            t['map'].reshape(o.n, -1)[idx] = o2.st.map[idx]
+            t['agent_location'][idx], t['agent_facing_id'][idx], t['inventory_items_quantity'][idx] = o2.st.loc[idx], o2.st.facing[idx], o2.st.inv[idx]
+
+    def _raise_flags(self):
+        if self._flags & 2:
+            raise AssertionError(PLACEMENT_MESSAGE)
+
+    def error_flags(self):
+        return self._flags
+
+    def step(self, actions, copy=False, with_obs=True):
+        self._step(actions)
+        o, st = self.o, self.o.st
+        self._raise_flags()
+        info = {'result': o.result.astype(bool), 'step_cost_code': o.cost_code, 'message_code': o.msg_code, 'message_arg': o.msg_arg}
+        obs = {'map': st.map, 'agent_location': st.loc, 'agent_facing_id': st.facing, 'inventory_items_quantity': st.inv}
+        return obs, o.reward.copy(), o.done.astype(bool), info
+
+    def step_device_many(self, acts, stride, k):
+        for i in range(k):
+            self._step(un(acts)[i])
+
+    rollout_actions = step_device_many
+
+    def rollout(self, n_steps, action_seed=1234, t0=0):
+        self._flags |= int(self.o.rollout(n_steps, action_seed, t0))
+
+    def graph_build(self, acts, stride, k):
+        self._graph = un(acts)[:k].copy()
+
+    def graph_launch(self, reps=1):
+        for _ in range(reps):
+            for a in self._graph:
+                self._step(a)
+
+    def terminal_observation(self, device=False):
+        return self._term
+
+    def set_action_masks(self, on=True):
+        pass
+
+    def lidar_configure(self, lidar_config=None, num_beams=8, fused=False, dtype=np.int32):
+        super().lidar_configure(lidar_config, num_beams, fused, dtype)
+        self._lidar_c = self.lidar.compile(self.spec)
+
+    def lidar_observation(self, device=False, copy=False):
+        st = self.o.st
+        return NO.lidar(self._lidar_c, self.spec.map_size, len(self.spec.items_id), st.map, st.loc, st.facing, st.inv)
+
+    def lidar_widen(self, pair, dtype=np.int32):
+        return np.concatenate([pair[0].astype(dtype), pair[1].astype(dtype)], 1)
+
+    def action_mask_words(self, device=False, copy=False):
+        return M.oracle_mask_words(self.spec, self.o.st)
+
+    def snapshot(self, capacity=None):
+        s = StandInSnapshot(self, self.num_envs if capacity is None else capacity)
+        self.__dict__.setdefault('_snapshots', []).append(s)
+        return s
+
+    def fork(self, src, keep_episode=False):
+        super().fork(un(src), keep_episode)
+
+    def key_table(self, capacity):
+        return StandInTable(self, capacity)
+
+    def evaluate_plans(self, plans, device=False, copy=False):
+        return super().evaluate_plans(un(plans).transpose(2, 1, 0) if is_dev(plans) else plans)
+
+    def state_keys(self, envs=None, fields=SK.STATE, device=False):
+        return F.fast_keys(F.rows_at(self.o.st, np.arange(self.num_envs) if envs is None else un(envs)), fields)
+
+    def insert_state_keys(self, table, envs=None, fields=SK.STATE, device=False):
+        keys = self.state_keys(envs, fields)
+        return keys, table.insert(keys)
+
+    def _succ_limit(self):
+        if self.spec.map_size > F.SUCC_MAX_MAP:
+            raise MapsTooLarge("map_size %d: beyond the successor keys' two sets of rows" % self.spec.map_size)
+
+    def successor_keys(self, envs=None, fields=SK.STATE, device=False, reports=True):
+        self._succ_limit()
+        return super().successor_keys(un(envs), fields, reports=reports)
+
+    def insert_successor_keys(self, table, envs=None, fields=SK.STATE, device=False):
+        s = self.successor_keys(envs, fields)
+        found = table.insert(s.keys.reshape(-1))
+        return s, KeyInsert(found.where.reshape(s.keys.shape), found.fresh.reshape(s.keys.shape))
+
+    def sample_actions(self, weights, seed, t=0, envs=None, device=False):
+        w = un(weights).T if is_dev(weights) else weights
+        return super().sample_actions(w, seed, t, un(envs))
+
+    def step_sampled(self, weights, seed, t=0):
+        s = self.sample_actions(weights, seed, t)
+        self._step(s.action)
+        return s
+
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, **kw):
+        return super().playouts(n_playouts, steps, seed, weights=un(weights), **kw)
+
+
+def make_stand_in(**kw):
+    return StandIn(**kw)

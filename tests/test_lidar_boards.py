@@ -214,3 +214,34 @@ def test_bit_row_lidar_behind_the_pipelined_host_step(n, slices, dtype, monkeypa
     st = v.get_state()
     assert (st['map'] == o.st.map).all() and (st['inv'] == o.st.inv).all() and (st['episode'] == o.st.episode).all()
     v.close()
+
+
+@pytest.mark.parametrize('stale_by', ['rollout', 'set_state'])
+def test_graph_replay_rebuilds_bit_rows_left_stale_since_its_capture(stale_by):
+    """A graph captured while the bit rows were current, replayed after a fused rollout (it steps the maps in LDS) or a state injection with maps
+    has left them stale: the replay starts with the rebuild an eager step launch starts with.  (Found by tests/test_search_fuzz.py: a captured
+    graph replayed after another call kind had written the maps gave lidar rows marched on the maps of the capture.)"""
+    import torch
+    spec = T.build_spec('stk_bi_axe10')
+    A, n = len(spec.actions_id), 130
+    v, o, cc = _pair(spec, n, 31, 0)
+    check = _checker(v, o, cc, spec)
+    v.reset(); o.reset(); check('reset')
+    acts = torch.randint(0, A, (2, n), dtype=torch.int32, device='cuda')
+    torch.cuda.synchronize()
+    an = acts.cpu().numpy()
+    v.graph_build(acts.data_ptr(), n, 2)
+    if stale_by == 'rollout':
+        v.rollout(12, action_seed=3, t0=0); o.rollout(12, 3, 0); check('rollout')
+    else:
+        perm = np.roll(np.arange(n), 1)
+        rows = dict(map=o.st.map[perm].copy(), loc=o.st.loc[perm].copy(), inv=o.st.inv[perm].copy())
+        v.set_state(0, **rows)
+        o.st.map[...], o.st.loc[...], o.st.inv[...] = rows['map'], rows['loc'], rows['inv']
+    v.graph_launch(1)
+    for t in range(2):
+        o.step(an[t])
+    check('graph replay after ' + stale_by)
+    st = v.get_state()
+    assert (st['map'] == o.st.map).all() and (st['loc'] == o.st.loc).all() and (st['inv'] == o.st.inv).all() and v.error_flags() == 0
+    v.close()

@@ -1,0 +1,50 @@
+"""Randomised call sequences over the whole search surface of one handle, HIP path against the model of tests/search_fuzz.py: action masks,
+snapshots (save, restore, copy, fork), expand, slot rollouts and playouts in every form, slot observers, lookahead, plan evaluation, state /
+successor / path keys, the key table, weighted sampling, step_sampled, trajectories and a captured graph, interleaved with the steps, rollouts, resets
+and state injections of tests/test_fuzz_parity.py - everything compared after every call, under drawn handle settings (prepared episodes and their
+depth, the small page-locked block, env_index_base, fused lidar formats, masks in the step, terminal capture, batches that are no whole number of
+wavefronts).
+
+One case per configuration and chunk by default; NGW_FUZZ_SECONDS=<s> runs longer (a soak), NGW_FUZZ_SEED=<n> draws other sequences: a failure
+message names the configuration, the case, the settings, the call's index and kind, and with the seed that reproduces it.  Six chunks: the model
+side of one chunk, walked on the CPU against the stand-in (tests/test_search_fuzz_cpu.py; the stand-in computes everything a second time), was
+measured at 2.0, 1.2, 0.9, 1.3, 1.4 and 1.8 s for the committed seed, with the per-call maxima as the issue set them (130 pairs, 8 steps, 3 plans);
+on the MI355X a chunk takes 0.3 - 0.5 s (2.8 s for the first, which loads the library).  Needs an MI355X."""
+import os
+import time
+
+import numpy as np
+import pytest
+
+import search_fuzz as F
+
+pytestmark = pytest.mark.gpu
+CHUNKS = 6
+BUDGET = float(os.environ.get('NGW_FUZZ_SECONDS', '0'))
+SEED = int(os.environ.get('NGW_FUZZ_SEED', '7100'))        # (tests/test_fuzz_parity.py starts from 1000)
+
+
+def make_env(**kw):
+    import torch
+    from gym_novel_gridworlds_amd import VecNovelGridworld
+    v = VecNovelGridworld(**kw)
+
+    def to_device(a):
+        t = torch.from_numpy(np.ascontiguousarray(a)).cuda()
+        torch.cuda.synchronize()
+        return t
+    v.to_device, v.ptr_of = to_device, lambda t: t.data_ptr()
+    return v
+
+
+@pytest.mark.parametrize('chunk', range(CHUNKS))
+def test_random_search_call_sequences_match_model(chunk):
+    rs = np.random.RandomState(SEED + chunk)
+    t_end = time.time() + (BUDGET / CHUNKS if BUDGET > 0 else 0)
+    case = 0
+    while True:
+        for cfg in F.chunk_cfgs(chunk, CHUNKS):
+            F.run_case(rs, cfg, case, make_env)
+            case += 1
+        if time.time() >= t_end:
+            break
