@@ -30,12 +30,18 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_snapshot_create', 'ngw_snapshot_destroy', 'ngw_snapshot_save', 'ngw_snapshot_restore', 'ngw_snapshot_get', 'ngw_snapshot_expand', 'ngw_snapshot_rollout',
            'ngw_snapshot_lidar', 'ngw_snapshot_agent_view', 'ngw_snapshot_action_mask', 'ngw_state_keys', 'ngw_snapshot_copy', 'ngw_successor_keys', 'ngw_snapshot_playout',
            'ngw_snapshot_playout_weighted', 'ngw_sample_actions', 'ngw_snapshot_rollout_path', 'ngw_snapshot_playout_path',
-           'ngw_snapshot_rollout_traj', 'ngw_snapshot_playout_traj',
+           'ngw_snapshot_rollout_traj', 'ngw_snapshot_playout_traj', 'ngw_snapshot_rollout_traj_views', 'ngw_snapshot_playout_traj_views',
            'ngw_key_table_create', 'ngw_key_table_destroy', 'ngw_key_table_clear', 'ngw_key_table_insert', 'ngw_key_table_lookup', 'ngw_key_table_count',
            'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
 _lib = None
+
+
+class TrajViews(C.Structure):
+    """include/ngw.h ngw_traj_views: the AgentMap outputs of a trajectory call - device pointers (any may be NULL, not all), the stride of a row
+    block in rows."""
+    _fields_ = [('view_size', C.c_int32), ('view_dev', C.c_void_p), ('facing_dev', C.c_void_p), ('inv_dev', C.c_void_p), ('stride', C.c_int64)]
 
 
 class NgwError(RuntimeError):
@@ -181,6 +187,9 @@ def lib():
     if hasattr(L, 'ngw_snapshot_playout_traj'):
         L.ngw_snapshot_playout_traj.argtypes = [vp, vp, vp, i64, C.c_int32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64, C.c_uint32, vp, i64,
                                                 vp, i64, vp, i64, vp, i64]
+    if hasattr(L, 'ngw_snapshot_rollout_traj_views'):        # (each its _traj twin and a trailing const ngw_traj_views*)
+        L.ngw_snapshot_rollout_traj_views.argtypes = L.ngw_snapshot_rollout_traj.argtypes + [C.POINTER(TrajViews)]
+        L.ngw_snapshot_playout_traj_views.argtypes = L.ngw_snapshot_playout_traj.argtypes + [C.POINTER(TrajViews)]
     if hasattr(L, 'ngw_snapshot_playout_weighted'):
         L.ngw_snapshot_playout_weighted.argtypes = [vp, vp, vp, i64, C.c_int32, C.c_uint64, C.c_uint64, vp, vp, vp, vp, vp, vp, vp, vp, vp, i64]
     if hasattr(L, 'ngw_sample_actions'):

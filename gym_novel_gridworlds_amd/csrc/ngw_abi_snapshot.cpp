@@ -11,7 +11,8 @@
 // A playout (ngw_playout.inc) is a rollout whose actions the kernel draws among the valid ones of each step: it commits nothing either.
 // The path forms of both (ngw_path.inc) add per-pair step limits and the key of every visited state: they commit nothing either.
 // The trajectory forms (ngw_traj.inc) add the per-step rewards, mask words and LidarInFront rows of such a path: they commit nothing either, and
-// leave the env's own lidar rows alone.
+// leave the env's own lidar rows alone.  Their AgentMap views (the _traj_views entry points) are outputs of the same launches under the path form's
+// layout: no lidar is needed or touched.
 // The weighted choice (ngw_sample.inc) draws one action per row by the caller's weights among the valid ones: it commits nothing either.
 #include "ngw_host.h"
 
@@ -115,7 +116,7 @@ NgwLaunch step_block(const ngw_handle* h, bool observing = false) {
 
 // what the path forms ask for beyond a plain rollout / playout, and the trajectory forms beyond those (masks: playouts)
 struct PathArgs { const int32_t* limits; uint32_t fields; uint64_t* keys; int64_t keys_stride; };
-struct TrajArgs { int32_t* rewards; int64_t rewards_stride; uint64_t* masks; int64_t masks_stride; void* obs; int64_t obs_stride; };
+struct TrajArgs { int32_t* rewards; int64_t rewards_stride; uint64_t* masks; int64_t masks_stride; void* obs; int64_t obs_stride; NgwTrajViews vw; bool views; };
 // where the actions come from: a plan [n_steps][stride], or the kernel draws them (weights NULL: the uniform rule; actions NULL: not recorded)
 struct Plan { const int32_t* actions; int64_t stride; };
 struct Draw { uint64_t seed, first_pair; const float* weights; int32_t* first_action; int32_t* actions; int64_t stride; };
@@ -139,10 +140,12 @@ const PairsLaunch<NgwSlotRollout> ROLLOUT_LAUNCH[3] = {ngw_slot_rollout_launch, 
 const PairsLaunch<NgwPlayout> PLAYOUT_LAUNCH[3] = {ngw_playout_launch, ngw_playout_path_launch, ngw_playout_traj_launch};
 const char* const PAIRS_CALL[2][3] = {{"ngw_snapshot_rollout", "ngw_snapshot_rollout_path", "ngw_snapshot_rollout_traj"},
                                       {"ngw_snapshot_playout", "ngw_snapshot_playout_path", "ngw_snapshot_playout_traj"}};
+const char* const VIEWS_CALL[2] = {"ngw_snapshot_rollout_traj_views", "ngw_snapshot_playout_traj_views"};   // (TRAJ with a views struct)
 
 // The path and trajectory arguments of one request, checked (before anything touches the stream) -> the LDS bytes of the launch and where the
 // inventory shadows sit.  Without observations: the path form's layout and its map limit.  With them: the stand-alone lidar launch's layout
-// (ngw_lidar_configure), and the shadows behind it only where keys are asked for.
+// (ngw_lidar_configure), and the shadows behind it only where keys are asked for.  With AgentMap views: the handle's rollout layout as it is, and
+// the shadows behind it only where keys are asked for - the views need no LDS of their own.
 int path_traj_args(const ngw_handle* h, const Pairs& p, const char* what, const char* call, size_t* lds, uint32_t* off_shadow) {
     const PathArgs& pa = p.pa;
     const TrajArgs& ta = p.ta;
@@ -153,6 +156,28 @@ int path_traj_args(const ngw_handle* h, const Pairs& p, const char* what, const 
         return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a mask stride of %lld", what, (long long)count, (long long)ta.masks_stride);
     if (pa.keys)
         if (int rc = key_args(pa.fields, what, count, pa.keys_stride)) return rc;
+    if (ta.views) {
+        const NgwTrajViews& v = ta.vw;
+        if (!v.view && !v.facing && !v.inv) return fail(NGW_E_INVALID_ARG, "%s: views without a view, a facing and an inventory pointer: nothing to record", call);
+        if (ta.obs) return fail(NGW_E_INVALID_ARG, "%s: lidar rows and views in one call; a call observes one kind", call);
+        if (v.V < 1 || v.V > NGW_TRAJ_VIEW_MAX) return fail(NGW_E_INVALID_ARG, "view_size must be in 1..%d", NGW_TRAJ_VIEW_MAX);
+        if (v.stride % NGW_EPB || v.stride < (count + NGW_EPB - 1) / NGW_EPB * NGW_EPB)
+            return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a view stride of %lld rows: a multiple of 64 that holds the pairs rounded up to 64 expected", what,
+                        (long long)count, (long long)v.stride);
+        if (reinterpret_cast<uintptr_t>(v.view) & 15u) return fail(NGW_E_INVALID_ARG, "%s: the view windows must be 16-byte aligned", what);
+        if ((reinterpret_cast<uintptr_t>(v.facing) | reinterpret_cast<uintptr_t>(v.inv)) & 3u)
+            return fail(NGW_E_INVALID_ARG, "%s: the facing ids and the inventories must be 4-byte aligned", what);
+        *lds = h->lds_bytes + (pa.keys ? (size_t)NGW_EPB * 4u * (size_t)h->proto.KP : 0u);
+        if (!h->general_ok)                          // (the handle kept no rollout layout: its maps and inventories alone are what can be named)
+            return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps in LDS (%s) under the handle's rollout layout, whose maps and inventories "
+                                           "alone take %zu B and which exceeds 160 KiB as a whole; per-launch steps with ngw_agent_view are available", h->proto.S, call,
+                        (size_t)NGW_EPB * (size_t)h->proto.MS + (size_t)NGW_EPB * 4u * (size_t)h->proto.KP);
+        if (*lds > NGW_PATH_LDS_MAX)
+            return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps%s in LDS (%s) and they need %zu B, more than 160 KiB; %s", h->proto.S,
+                        pa.keys ? " and a second copy of their inventories" : "", call, *lds,
+                        pa.keys ? "the views without keys have the handle's own limit" : "per-launch steps with ngw_agent_view are available");
+        return NGW_OK;
+    }
     if (!ta.obs) {
         *lds = NGW_PATH_LDS_BYTES(h->lds_bytes, h->proto.KP);
         if (*lds > NGW_PATH_LDS_MAX)
@@ -177,6 +202,13 @@ int path_traj_args(const ngw_handle* h, const Pairs& p, const char* what, const 
     return NGW_OK;
 }
 
+// the caller's views struct into the request (NULL: the _traj call as it always was)
+void views_arg(TrajArgs& ta, const ngw_traj_views* v) {
+    if (!v) return;
+    ta.views = true;
+    ta.vw.view = v->view_dev; ta.vw.facing = v->facing_dev; ta.vw.inv = v->inv_dev; ta.vw.stride = v->stride; ta.vw.V = v->view_size;
+}
+
 // what NgwSlotRollout and NgwPlayout hold alike, out of the request
 template <class X>
 void fill_pairs(X& x, const Pairs& p, const Source& from, uint32_t off_shadow) {
@@ -186,18 +218,19 @@ void fill_pairs(X& x, const Pairs& p, const Source& from, uint32_t off_shadow) {
     x.ret = p.ret; x.length = p.length; x.ended = p.ended; x.info = p.info;
     if (p.form != PLAIN) { x.limits = p.pa.limits; x.keys = p.pa.keys; x.keys_stride = p.pa.keys_stride; x.fields = p.pa.fields; x.off_shadow = off_shadow; }
     if (p.form == TRAJ) { x.rewards = p.ta.rewards; x.rewards_stride = p.ta.rewards_stride; x.obs = p.ta.obs; x.obs_stride = p.ta.obs_stride; }
+    if (p.form == TRAJ && p.ta.views) x.vw = p.ta.vw;
 }
 
 // one request served: every check (in the order the entry points have always made them) before enter(h) and the first use of the stream, then one launch
 int step_pairs(ngw_handle* h, const Pairs& p) {
     const char* const what = p.draws ? "playout" : "rollout";
-    const char* const call = PAIRS_CALL[p.draws][p.form];
+    const char* const call = p.ta.views ? VIEWS_CALL[p.draws] : PAIRS_CALL[p.draws][p.form];
     const int64_t stride = p.draws ? p.draw.stride : p.plan.stride;
     if (!h || (!p.draws && !p.plan.actions)) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (p.n_steps < 1) return fail(NGW_E_INVALID_ARG, "%s of %d steps", what, (int)p.n_steps);
     if (p.count < 0 || ((!p.draws || p.draw.actions) && stride < p.count))
         return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with %s stride of %lld", what, (long long)p.count, p.draws ? "an action" : "a pair", (long long)stride);
-    if (!p.draws && !p.dst && !p.ret && !p.length && !p.ended && !p.info && !p.pa.keys && !p.ta.rewards && !p.ta.obs)
+    if (!p.draws && !p.dst && !p.ret && !p.length && !p.ended && !p.info && !p.pa.keys && !p.ta.rewards && !p.ta.obs && !p.ta.views)
         return fail(NGW_E_INVALID_ARG, "rollout without a destination and without a report: nothing to do");
     Source from;
     size_t lds = h->lds_bytes;
@@ -381,12 +414,21 @@ int ngw_snapshot_rollout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* s
                               const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev,
                               uint8_t* ended_dev, uint32_t* info_dev, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev,
                               int64_t rewards_stride, void* obs_dev, int64_t obs_stride) {
+    return ngw_snapshot_rollout_traj_views(h, src, src_idx_dev, actions_dev, pair_stride, n_steps, limits_dev, dst, dst_slots_dev, count, ret_dev, length_dev, ended_dev,
+                                           info_dev, fields, keys_dev, keys_stride, rewards_dev, rewards_stride, obs_dev, obs_stride, nullptr);
+}
+
+int ngw_snapshot_rollout_traj_views(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride, int32_t n_steps,
+                                    const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev, int32_t* length_dev,
+                                    uint8_t* ended_dev, uint32_t* info_dev, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev,
+                                    int64_t rewards_stride, void* obs_dev, int64_t obs_stride, const ngw_traj_views* views) {
     Pairs p{};
     p.src = src; p.src_idx = src_idx_dev; p.dst = dst; p.dst_slots = dst_slots_dev; p.count = count; p.n_steps = n_steps;
     p.ret = ret_dev; p.length = length_dev; p.ended = ended_dev; p.info = info_dev;
     p.form = TRAJ; p.plan.actions = actions_dev; p.plan.stride = pair_stride;
     p.pa.limits = limits_dev; p.pa.fields = fields; p.pa.keys = keys_dev; p.pa.keys_stride = keys_stride;
     p.ta.rewards = rewards_dev; p.ta.rewards_stride = rewards_stride; p.ta.obs = obs_dev; p.ta.obs_stride = obs_stride;
+    views_arg(p.ta, views);
     return step_pairs(h, p);
 }
 
@@ -395,6 +437,16 @@ int ngw_snapshot_playout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* s
                               int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride,
                               uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev, int64_t rewards_stride, uint64_t* masks_dev,
                               int64_t masks_stride, void* obs_dev, int64_t obs_stride) {
+    return ngw_snapshot_playout_traj_views(h, src, src_idx_dev, count, n_steps, seed, first_pair, weights_dev, limits_dev, dst, dst_slots_dev, ret_dev, length_dev,
+                                           ended_dev, info_dev, first_action_dev, actions_dev, actions_stride, fields, keys_dev, keys_stride, rewards_dev, rewards_stride,
+                                           masks_dev, masks_stride, obs_dev, obs_stride, nullptr);
+}
+
+int ngw_snapshot_playout_traj_views(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                                    const float* weights_dev, const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev,
+                                    int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev,
+                                    int64_t actions_stride, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev, int64_t rewards_stride,
+                                    uint64_t* masks_dev, int64_t masks_stride, void* obs_dev, int64_t obs_stride, const ngw_traj_views* views) {
     Pairs p{};
     p.src = src; p.src_idx = src_idx_dev; p.dst = dst; p.dst_slots = dst_slots_dev; p.count = count; p.n_steps = n_steps;
     p.ret = ret_dev; p.length = length_dev; p.ended = ended_dev; p.info = info_dev;
@@ -402,6 +454,7 @@ int ngw_snapshot_playout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* s
     p.draw.first_action = first_action_dev; p.draw.actions = actions_dev; p.draw.stride = actions_stride;
     p.pa.limits = limits_dev; p.pa.fields = fields; p.pa.keys = keys_dev; p.pa.keys_stride = keys_stride;
     p.ta.rewards = rewards_dev; p.ta.rewards_stride = rewards_stride; p.ta.obs = obs_dev; p.ta.obs_stride = obs_stride; p.ta.masks = masks_dev; p.ta.masks_stride = masks_stride;
+    views_arg(p.ta, views);
     return step_pairs(h, p);
 }
 

@@ -499,6 +499,20 @@ hipError_t ngw_expand_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const 
  * read and nothing but the reports is stored.  A NULL index list = j itself; an index outside its set skips the pair and raises
  * NGW_F_BAD_INDEX.  src and dst may be the same rows.  The launch block is the handle's rollout layout (LDS carve-up, autoreset, horizon, the
  * flags word). */
+/* The AgentMap outputs of a trajectory call (ngw_traj.inc; include/ngw.h ngw_traj_views): any pointer may be nullptr, all three nullptr = no views.
+ * view: int8 [n_steps + 1][stride][W * W], W = 2 * V + 1; facing: int32 [n_steps + 1][stride]; inv: int32 [n_steps + 1][stride][K]; row j of block
+ * 0 the parent of pair j, of block t + 1 the state step t leaves, zeros for a step the pair did not execute.  stride: rows per block, a multiple of
+ * 64 that holds `count` rounded up to 64 - a wave stores its 64 rows of a block as one run of dwords.  magicW / magicWW: ceil(2^32 / W), ceil(2^32 /
+ * (W * W)) - exact for the operands below 64 * W * W the kernel divides (V <= NGW_TRAJ_VIEW_MAX); the launchers fill them in. */
+struct NgwTrajViews {
+    int8_t* view;
+    int32_t* facing;
+    int32_t* inv;
+    int64_t stride;
+    int32_t V;
+    uint32_t magicW, magicWW;
+};
+
 struct NgwSlotRollout {
     NgwSnapRows src, dst;
     const int32_t* si;
@@ -526,6 +540,7 @@ struct NgwSlotRollout {
     int64_t rewards_stride;
     void* obs;
     int64_t obs_stride;
+    struct NgwTrajViews vw; /* the AgentMap views in the place of obs (last again): the launch block stays the path form's */
 };
 #define NGW_PATH_LDS_MAX ((size_t)160 * 1024)                                                                   /* what a CU of gfx950 has */
 #define NGW_PATH_LDS_BYTES(lds_bytes, KP) ((size_t)(lds_bytes) + (size_t)NGW_EPB * 4u * (size_t)(KP))   /* the handle's layout and the inventory shadows behind it */
@@ -575,6 +590,7 @@ struct NgwPlayout {
     int64_t masks_stride;
     void* obs;
     int64_t obs_stride;
+    struct NgwTrajViews vw; /* the AgentMap views in the place of obs (last again): the launch block stays the path form's */
 };
 #ifdef __cplusplus
 extern "C"
@@ -590,7 +606,8 @@ extern "C"
 #endif
 /* the trajectory forms (PATH and TRAJ): x->rewards / x->masks / x->obs are read too.  Without x->obs: the path launch's block and lds_bytes.  With
  * it: a = the stand-alone lidar launch's layout (ngw_lidar_configure) with a->autoreset, a->horizon, x->off_shadow behind it where x->keys is
- * set, lds_bytes = that layout's (+ the shadows) */
+ * set, lds_bytes = that layout's (+ the shadows).  With x->vw (and no x->obs): the handle's rollout layout, lds_bytes = the handle's (+ the shadows
+ * where x->keys is set); vw.magicW / vw.magicWW are the launcher's to fill */
 hipError_t ngw_slot_rollout_traj_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwSlotRollout* x, int ext, size_t lds_bytes, hipStream_t stream);
 #ifdef __cplusplus
 extern "C"

@@ -40,7 +40,8 @@ namespace {
 // TRAJ (ngw_snapshot_playout_traj; a PATH form): x.rewards, x.masks and x.obs take the reward, the mask word m (after the all-actions replacement)
 // and the LidarInFront rows of every step as ngw_traj.inc lays them out - 0 / zero rows for a step the pair did not execute; with x.obs the launch
 // block is the stand-alone lidar launch's layout and every lane of the wave reaches every row set (the loop is wave-uniform).  TRAJ = false is
-// the kernel as it was.
+// the kernel as it was.  x.vw (AgentMap views, ngw_traj.inc) takes the window, the facing id and the inventory of the same states by the same block
+// rule under the PATH form's launch block: run-time outputs of this form, all nullptr = the form as it was.
 //
 // x.actions (may be nullptr): int32, the action of pair j at step t to [t * x.stride + j] (stride >= count) - the layout ngw_slot_rollout_kernel reads.
 
@@ -122,6 +123,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
         tr.rew = x.rewards && inside ? x.rewards + pair : nullptr;
         tr.msk = x.masks && inside ? x.masks + pair : nullptr;
         if (x.obs) traj_obs_rows(a, lds, tid, ok, mp, S, r, c, f, inv, x.obs, x.obs_stride, 0);   // row block 0: the parents
+        if (traj_views_on(x.vw)) traj_view_rows(a, x.vw, lds, tid, ok, r, c, f, 0);
     }
     int s = 0;
     for (; s < n_steps; s++) {
@@ -163,6 +165,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
             if (tr.rew) tr.rew[(int64_t)s * x.rewards_stride] = alive ? o.reward : 0;
             if (tr.msk) tr.msk[(int64_t)s * x.masks_stride] = alive ? m : 0ull;
             if (x.obs) traj_obs_rows(a, lds, tid, alive, mp, S, r, c, f, inv, x.obs, x.obs_stride, s + 1);
+            if (traj_views_on(x.vw)) traj_view_rows(a, x.vw, lds, tid, alive, r, c, f, s + 1);
         }
         if (alive) {
             ret += o.reward; len += 1; info = o.info;
@@ -179,6 +182,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
         if (tr.msk)
             for (int u = s; u < n_steps; u++) tr.msk[(int64_t)u * x.masks_stride] = 0ull;
         if (x.obs) traj_zero_tiles(a, tid, x.obs, x.obs_stride, s, n_steps);
+        if (traj_views_on(x.vw)) traj_zero_views(a, x.vw, tid, s, n_steps);
     }
     if (rec && inside)
         for (; s < n_steps; s++) rec[(int64_t)s * tstride] = -1;                   // the steps no pair of this wave executed
@@ -217,13 +221,15 @@ hipError_t playout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const Ngw
     if (!slot_step_args_ok(a, x) || (x->actions && x->stride < x->count) ||
         (PATH && !TRAJ && !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes)) ||
         (TRAJ && !traj_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes, x->rewards, x->rewards_stride, x->masks, x->masks_stride,
-                               x->obs, x->obs_stride)))
+                               x->obs, x->obs_stride, x->vw)))
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks_for(x->count)), block(NGW_EPB);
+    NgwPlayout y = *x;
+    if (TRAJ) y.vw = traj_views_ready(x->vw);
     return with_row_piece(a->S2, [&](auto V) {
         return with_flag(ext != 0, [&](auto E) {
             return with_flag(x->weights != nullptr, [&](auto W) {
-                return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, decltype(W)::value, PATH, TRAJ>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+                return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, decltype(W)::value, PATH, TRAJ>>(grid, block, lds_bytes, stream, dspec, *a, y);
             });
         });
     });

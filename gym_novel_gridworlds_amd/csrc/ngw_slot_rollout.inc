@@ -39,6 +39,8 @@ namespace {
 // TRAJ (ngw_snapshot_rollout_traj; a PATH form): x.rewards and x.obs take the reward and the LidarInFront rows of every step as ngw_traj.inc lays
 // them out - 0 / zero rows for a step the pair did not execute; with x.obs the launch block is the stand-alone lidar launch's layout and every
 // lane of the wave reaches every row set (the loop is wave-uniform).  TRAJ = false is the kernel as it was.
+// x.vw (AgentMap views, ngw_traj.inc) takes the window, the facing id and the inventory of the same states by the same block rule under the PATH
+// form's launch block: run-time outputs of this form, all nullptr = the form as it was.
 //
 // x.actions: int32, the action of pair j at step t at [t * x.stride + j] (stride >= count): 64 lanes read consecutive addresses.
 template <int VEC, bool EXT, bool PATH = false, bool TRAJ = false>
@@ -110,6 +112,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
         tr.rew = x.rewards && inside ? x.rewards + pair : nullptr;
         tr.done = 0;
         if (x.obs) traj_obs_rows(a, lds, tid, ok, mp, S, r, c, f, inv, x.obs, x.obs_stride, 0);   // row block 0: the parents
+        if (traj_views_on(x.vw)) traj_view_rows(a, x.vw, lds, tid, ok, r, c, f, 0);
     }
     for (int s = 0; s < n_steps; s++) {
         if constexpr (PATH) alive = alive && s < pa.limit;
@@ -136,6 +139,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
         if constexpr (TRAJ) {                                                      // (`alive` still says: this pair executed this step)
             if (tr.rew) tr.rew[(int64_t)s * x.rewards_stride] = alive ? o.reward : 0;
             if (x.obs) traj_obs_rows(a, lds, tid, alive, mp, S, r, c, f, inv, x.obs, x.obs_stride, s + 1);
+            if (traj_views_on(x.vw)) traj_view_rows(a, x.vw, lds, tid, alive, r, c, f, s + 1);
             tr.done = s + 1;
         }
         if (alive) {                                                               // (an invalid id: reward 0, info 0, not an end - lean_epilogue)
@@ -151,6 +155,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_rollout_kernel(const NgwDevS
         if (tr.rew)
             for (int s = tr.done; s < n_steps; s++) tr.rew[(int64_t)s * x.rewards_stride] = 0;
         if (x.obs) traj_zero_tiles(a, tid, x.obs, x.obs_stride, tr.done, n_steps);
+        if (traj_views_on(x.vw)) traj_zero_views(a, x.vw, tid, tr.done, n_steps);
     }
     __syncthreads();
     // ---- 3. the end states to their slots with the scalars (where they are kept), the reports
@@ -186,12 +191,14 @@ hipError_t slot_rollout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, cons
     if (!slot_step_args_ok(a, x) || x->stride < x->count || !x->actions ||
         (PATH && !TRAJ && !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes)) ||
         (TRAJ && !traj_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes, x->rewards, x->rewards_stride, nullptr, 0, x->obs,
-                               x->obs_stride)))
+                               x->obs_stride, x->vw)))
         return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks_for(x->count)), block(NGW_EPB);
+    NgwSlotRollout y = *x;
+    if (TRAJ) y.vw = traj_views_ready(x->vw);
     return with_row_piece(a->S2, [&](auto V) {
         return with_flag(ext != 0, [&](auto E) {
-            return launch_kernel<ngw_slot_rollout_kernel<decltype(V)::value, decltype(E)::value, PATH, TRAJ>>(grid, block, lds_bytes, stream, dspec, *a, *x);
+            return launch_kernel<ngw_slot_rollout_kernel<decltype(V)::value, decltype(E)::value, PATH, TRAJ>>(grid, block, lds_bytes, stream, dspec, *a, y);
         });
     });
 }

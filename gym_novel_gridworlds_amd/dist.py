@@ -135,13 +135,15 @@ class ShardedVecNovelGridworld:
         """sample_actions + step_device on this rank's shard (VecNovelGridworld.step_sampled)."""
         return self.local.step_sampled(weights, seed, t=t)
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None,
+                 view_size=5):
         """Valid-action random playouts from the current states of this rank's shard (VecNovelGridworld.playouts): [num_envs, P] fields;
         rank-local, no collective.  The local env numbers its pairs from env_index_base * P (= first * P), so the ranks together return what
         one unsharded env over all the envs returns - with path_keys=True the keys [steps, num_envs, P] included: a key describes a state, not
-        where it is stored.  rewards / masks / observe: the trajectory fields of the shard's playouts (VecNovelGridworld.playouts), likewise."""
+        where it is stored.  rewards / masks / observe: the trajectory fields of the shard's playouts (VecNovelGridworld.playouts), likewise -
+        observe='agent_view' with view_size included: the ranks' dicts concatenate over the env axis as the lidar rows do."""
         from .playout import forward_keywords
-        path = forward_keywords(path_keys, fields, rewards, masks, observe)
+        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size)
         return self.local.playouts(n_playouts, steps, seed, device=device, weights=weights, **path)
 
     def snapshot(self, capacity=None):

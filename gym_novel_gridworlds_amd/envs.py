@@ -334,16 +334,18 @@ class _NovelGridworldEnv(_EnvBase):
         s = vec.sample_actions(np.asarray(weights)[None], seed, t=t)
         return int(s.action[0]), float(s.mass[0]), int(s.mask_words[0])
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None,
+                 view_size=5):
         """P = n_playouts valid-action random playouts of up to `steps` steps from the current state, without taking a step: a Playout of
         'ret' int32, 'length' int32, 'ended' bool, 'info' uint32 and 'first_action' int32, each [P]; playout q is pair q of the stream of
         `seed`; see VecNovelGridworld.playouts.  path_keys=True: a PlayoutPath, whose 'keys' [steps, P] hold the key under `fields` of the
         state each playout is in after every executed step (0 for the others).  rewards / masks / observe='lidar': a PlayoutTraj with
         'rewards' [steps, P], 'masks' [steps, P] and 'obs' [steps + 1, P, row] (VecNovelGridworld.playouts; the lidar must be configured on the
-        batched backend)."""
+        batched backend).  observe='agent_view' (view_size=V): 'obs' is the AgentMap dict - 'agent_map' [steps + 1, P, W, W], 'agent_facing_id'
+        [steps + 1, P], 'inventory_items_quantity' [steps + 1, P, K] -, no lidar needed."""
         vec = self._backend()
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
-        path = forward_keywords(path_keys, fields, rewards, masks, observe)
+        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size)
         return vec.playouts(n_playouts, steps, seed, device=device, weights=weights, **path).row(0)
 
     def state_key(self, fields=KEY_STATE):

@@ -72,19 +72,20 @@ class PlayoutPath(collections.namedtuple('PlayoutPath', 'ret length ended info f
         return PlayoutPath(*[x[i] for x in self[:5]], None if a is None else a[:, i], self.keys[:, i])
 
 
-def pairs_symbol(kind, weighted=False, path=False, traj=False):
+def pairs_symbol(kind, weighted=False, path=False, traj=False, views=False):
     """The C entry point (include/ngw.h) behind one rollout / playout call: kind 'rollout' or 'playout'; traj - rewards, masks or observations are
-    asked for; path - step limits or path keys are; weighted - a playout draws by weights.  The form is the entry point's: any traj is `_traj`,
-    any other path `_path`, else the plain call (a weighted playout: `_weighted`; a rollout draws nothing).  The one place that names the seven."""
+    asked for; path - step limits or path keys are; weighted - a playout draws by weights; views - the observations are AgentMap views (a trajectory
+    call by itself).  The form is the entry point's: views are `_traj_views`, any other traj is `_traj`, any other path `_path`, else the plain call
+    (a weighted playout: `_weighted`; a rollout draws nothing).  The one place that names the nine."""
     if kind not in ('rollout', 'playout'):
         raise ValueError("kind: 'rollout' or 'playout' expected, got %r" % (kind,))
-    form = '_traj' if traj else ('_path' if path else ('_weighted' if weighted and kind == 'playout' else ''))
+    form = '_traj_views' if views else ('_traj' if traj else ('_path' if path else ('_weighted' if weighted and kind == 'playout' else '')))
     return 'ngw_snapshot_%s%s' % (kind, form)
 
 
-def forward_keywords(path_keys=False, fields=None, rewards=False, masks=False, observe=None):
-    """The path and trajectory keywords a forwarding playouts() passes on: only those that are switched on (`fields` with path_keys), so a call
-    without them is the call it always was."""
+def forward_keywords(path_keys=False, fields=None, rewards=False, masks=False, observe=None, view_size=5):
+    """The path and trajectory keywords a forwarding playouts() passes on: only those that are switched on (`fields` with path_keys; `view_size`
+    with observe='agent_view', or where it is not its default - the env then refuses it), so a call without them is the call it always was."""
     kw = dict(path_keys=True, fields=fields) if path_keys else {}
     if rewards:
         kw['rewards'] = True
@@ -92,13 +93,18 @@ def forward_keywords(path_keys=False, fields=None, rewards=False, masks=False, o
         kw['masks'] = True
     if observe is not None:
         kw['observe'] = observe
+    if observe == 'agent_view' or not (isinstance(view_size, int) and view_size == 5):
+        kw['view_size'] = view_size
     return kw
 
 
 def map_obs(obs, fn):
-    """fn applied to the observation rows of a trajectory result: one array, or the (beams, inventory) pair of the packed lidar format; None stays None."""
+    """fn applied to the observation rows of a trajectory result: one array, the (beams, inventory) pair of the packed lidar format, or the dict
+    of observe='agent_view' (fn on every value); None stays None."""
     if obs is None:
         return None
+    if isinstance(obs, dict):
+        return {k: fn(x) for k, x in obs.items()}
     return tuple(fn(x) for x in obs) if isinstance(obs, tuple) else fn(obs)
 
 
@@ -112,7 +118,9 @@ class PlayoutTraj(collections.namedtuple('PlayoutTraj', 'ret length ended info f
       'obs'     [T + 1, count, row] ([T + 1, N, P, row]; [T + 1, P, row]) in the env's lidar format, as Snapshot.lidar_observation returns rows
                 (the packed format: the pair (beams uint8, inventory int16)): obs[0] the parents, obs[t + 1] the state step t leaves (before any
                 reset), all-zero rows for steps not executed.  (obs[t], actions[t], rewards[t], obs[t + 1]) is a transition for t < length;
-                snapshot.transitions(result) lists those (t, j)."""
+                snapshot.transitions(result) lists those (t, j).  With observe='agent_view' it is the dict Snapshot.agent_view returns, every
+                value with the same two leading axes: 'agent_map' int8 [T + 1, count, W, W], 'agent_facing_id' int32 [T + 1, count],
+                'inventory_items_quantity' int32 [T + 1, count, K]."""
     __slots__ = ()
 
     def __getitem__(self, key):
@@ -122,11 +130,12 @@ class PlayoutTraj(collections.namedtuple('PlayoutTraj', 'ret length ended info f
     died = Playout.died
 
     def shaped(self, *shape):
-        """The per-pair fields reshaped to `shape`, the per-step fields to [T, *shape], the rows to [T + 1, *shape, row]."""
+        """The per-pair fields reshaped to `shape`, the per-step fields to [T, *shape], the rows to [T + 1, *shape, row] (every value of a dict
+        of views likewise: [T + 1, *shape, ...])."""
         def steps(x):
             return None if x is None else x.reshape(x.shape[0], *shape)
         return PlayoutTraj(*[x.reshape(*shape) for x in self[:5]], steps(self.actions), steps(self.keys), steps(self.rewards), steps(self.masks),
-                           map_obs(self.obs, lambda x: x.reshape(x.shape[0], *shape, x.shape[-1])))
+                           map_obs(self.obs, lambda x: x.reshape(x.shape[0], *shape, *x.shape[2:])))
 
     def row(self, i):
         """Env i's rows of an [N, P] result (the single-env adapter's view)."""

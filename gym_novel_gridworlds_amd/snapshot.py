@@ -383,7 +383,7 @@ def transitions(result):
     for name in ('rewards', 'masks', 'keys', 'actions', 'obs'):
         x = getattr(result, name, None)
         if x is not None:
-            x = x[0] if isinstance(x, tuple) else x
+            x = x[0] if isinstance(x, tuple) else (next(iter(x.values())) if isinstance(x, dict) else x)
             steps = int(x.shape[0]) - (1 if name == 'obs' else 0)
             break
     if steps is None:
@@ -399,12 +399,24 @@ def transitions(result):
     return divmod(np.flatnonzero(ran.reshape(-1)), max(int(length.size), 1))
 
 
-def check_observe(env, observe):
-    """The `observe` keyword of a rollout / playout: None, or 'lidar' on an env with a lidar configured."""
+VIEW_SIZE_MAX = 16        # include/ngw.h NGW_TRAJ_VIEW_MAX
+
+
+def check_observe(env, observe, view_size=5):
+    """The `observe` and `view_size` keywords of a rollout / playout: None -> False; 'lidar' on an env with a lidar configured -> True;
+    'agent_view' (no lidar needed) with an integer view_size in 1 .. VIEW_SIZE_MAX -> 'agent_view'.  view_size belongs to 'agent_view': with any
+    other `observe` it stays at its default.  Everything else is a ValueError, before a handle is touched."""
+    default = isinstance(view_size, (int, np.integer)) and not isinstance(view_size, bool) and view_size == 5
+    if isinstance(observe, str) and observe == 'agent_view':
+        if isinstance(view_size, bool) or not isinstance(view_size, (int, np.integer)) or not 1 <= view_size <= VIEW_SIZE_MAX:
+            raise ValueError("view_size: an integer in 1..%d expected, got %r" % (VIEW_SIZE_MAX, view_size))
+        return 'agent_view'
+    if observe is not None and not (isinstance(observe, str) and observe == 'lidar'):
+        raise ValueError("observe: None or 'lidar' or 'agent_view' expected, got %r" % (observe,))
+    if not default:
+        raise ValueError("view_size=%r without observe='agent_view': the window belongs to the AgentMap observation" % (view_size,))
     if observe is None:
         return False
-    if observe != 'lidar':
-        raise ValueError("observe: None or 'lidar' expected, got %r" % (observe,))
     if env.lidar is None:
         refused = getattr(env, 'lidar_refused', None)    # (lidar_configure found the maps too large for the observation's LDS layout, and said so)
         if refused:
@@ -414,15 +426,21 @@ def check_observe(env, observe):
     return True
 
 
-def traj_outputs(env, dev, rewards, masks, observe, count, steps):
+def traj_outputs(env, dev, rewards, masks, observe, count, steps, view_size=5):
     """What a trajectory call adds to a path call -> (rewards int32 [steps, count] or None, masks int64 [steps, count] or None, the row buffer
     [steps + 1, count rounded up to 64, row] or None - a wave stores whole 64-row tiles, as in lidar_observation -, its stride in rows).  Only what
-    was asked for is allocated; the rows take (steps + 1) * pad * row bytes of device memory."""
+    was asked for is allocated; the rows take (steps + 1) * pad * row bytes of device memory.  observe: check_observe's result; 'agent_view' makes
+    the row buffer the dict of Snapshot.agent_view, every value [steps + 1, pad, ...]."""
     import torch
     rew = torch.zeros((steps, count), dtype=torch.int32, device=dev) if rewards else None
     msk = torch.zeros((steps, count), dtype=torch.int64, device=dev) if masks else None
     rows, pad = None, (count + 63) // 64 * 64
-    if observe:
+    if observe == 'agent_view':
+        W = 2 * int(view_size) + 1
+        rows = {'agent_map': torch.empty((steps + 1, pad, W, W), dtype=torch.int8, device=dev),           # (every row of every block is written: whole tiles)
+                'agent_facing_id': torch.empty((steps + 1, pad), dtype=torch.int32, device=dev),
+                'inventory_items_quantity': torch.empty((steps + 1, pad, env.n_items), dtype=torch.int32, device=dev)}
+    elif observe:
         if env.lidar_packed:
             shape, dtype = (steps + 1, pad, env.lidar_row_bytes), torch.uint8
         else:
@@ -442,6 +460,9 @@ def host(x, view=None):
 
 def traj_results(env, rew, msk, rows, count, device):
     """The three buffers as the result's fields: on the device as they are (the rows cut to `count` per block), else numpy; packed rows split."""
+    if isinstance(rows, dict):                           # (observe='agent_view')
+        rows = {k: x[:, :count] for k, x in rows.items()}
+        return (rew, msk, rows) if device else (host(rew), host(msk, np.uint64), {k: host(x) for k, x in rows.items()})
     if rows is not None:
         rows = rows[:, :count]
     if not device:
@@ -480,13 +501,13 @@ def path_call(env, holder, call, count, uploaded, device):
 
 
 def pairs_call(env, holder, kind, src, dst, parents, children, count, steps, device, plans=None, seed=0, first_pair=0, record=False, weights=None, limits=None,
-               path_keys=False, fields=None, rewards=False, masks=False, observe=None):
+               path_keys=False, fields=None, rewards=False, masks=False, observe=None, view_size=5):
     """The one launch behind Snapshot.rollout (kind 'rollout': `plans` the checked step-major [steps, count] actions), Snapshot.playout and
     VecNovelGridworld.playouts (kind 'playout': seed / first_pair / record, and weights: None - the uniform rule - or one float32 per action from the
     host or the device, sample.check_weights).  src / dst are snapshots' C handles (src None: the envs' current states; dst None: nothing is kept),
     parents / children the checked lists (check_rollout / check_playout); `holder` keeps the uploaded lists alive.  limits / path_keys / fields: the
-    path form; rewards / masks / observe: the trajectory form - `observe` has been through check_observe at the caller (before it touched a handle).
-    The entry point is playout.pairs_symbol's.  -> PlanEval / RolloutPath (with path_keys) / RolloutTraj, or Playout (actions [steps, count] with
+    path form; rewards / masks / observe / view_size: the trajectory form - `observe` has been through check_observe at the caller (before it touched
+    a handle).  The entry point is playout.pairs_symbol's.  -> PlanEval / RolloutPath (with path_keys) / RolloutTraj, or Playout (actions [steps, count] with
     `record`) / PlayoutPath / PlayoutTraj, as the callers' docstrings define them."""
     import torch
     from .playout import Playout, PlayoutPath, PlayoutTraj, pairs_symbol
@@ -494,7 +515,8 @@ def pairs_call(env, holder, kind, src, dst, parents, children, count, steps, dev
     draws = kind == 'playout'
     traj = observe is not None or bool(rewards) or bool(masks)
     path = traj or limits is not None or bool(path_keys)
-    name = pairs_symbol(kind, weights is not None, path, traj)
+    views = isinstance(observe, str) and observe == 'agent_view'
+    name = pairs_symbol(kind, weights is not None, path, traj, views)
     seed, first_pair = int(seed), int(first_pair)
     if not 0 <= seed < 1 << 64:                 # (refused before anything is uploaded or allocated)
         raise ValueError("seed: %d outside [0, 2^64)" % seed)
@@ -526,11 +548,17 @@ def pairs_call(env, holder, kind, src, dst, parents, children, count, steps, dev
         (lim_ptr,), up = upload(dev, count, lim)
         uploaded, head, tail = uploaded + up, head + [lim_ptr], tail + [f, _ptr(keys, count), int(count)]
     if traj:
-        rew, msk, rows, pad = traj_outputs(env, dev, rewards, masks, observe is not None, count, steps)
-        tail += [_ptr(rew, count), int(count)] + ([_ptr(msk, count), int(count)] if draws else []) + [_ptr(rows, count), int(pad)]
+        rew, msk, rows, pad = traj_outputs(env, dev, rewards, masks, 'agent_view' if views else observe is not None, count, steps, view_size)
+        tail += [_ptr(rew, count), int(count)] + ([_ptr(msk, count), int(count)] if draws else [])
+        if views:                                        # (the lidar rows' place stays empty; the three buffers travel in one struct)
+            vw = _cabi.TrajViews(int(view_size), *[x.data_ptr() for x in (rows['agent_map'], rows['agent_facing_id'], rows['inventory_items_quantity'])], int(pad))
+            tail += [None, 0, C.byref(vw) if count else None]
+        else:
+            tail += [_ptr(rows, count), int(pad)]
     (path_call if path else enqueue_ordered)(env, holder, lambda: getattr(_cabi.lib(), name)(*head, *tail), count, uploaded, device)
     if count == 0 and rows is not None:
-        rows.zero_()
+        for x in (rows.values() if views else [rows]):
+            x.zero_()
     if device:
         res = [ret, length, ended.view(torch.bool), info] + ([first, actions] if draws else [])
     else:
@@ -701,7 +729,7 @@ class Snapshot:
         return self.expand(p, a, c, from_envs=from_envs, source=source, device=device).reshape(*shape)
 
     def rollout(self, parents, plans, children=None, from_envs=False, source=None, device=False, limits=None, path_keys=False, fields=KEY_STATE,
-                rewards=False, masks=False, observe=None):
+                rewards=False, masks=False, observe=None, view_size=5):
         """Pair j: the state of parent parents[j] stepped on a private copy with the T actions of plans[j], by the rules evaluate_plans()
         applies - every novelty, the env's autoreset setting and horizon; it stops at the first step that ends the episode (goal, FireWall
         death, the horizon under autoreset), that step counts, and no reset ever runs.  Returns a PlanEval of 'ret' int32 (sum of the
@@ -736,12 +764,17 @@ class Snapshot:
         Still one kernel launch and no row leaves the chip's local memory; the rows take (T + 1) * count (rounded up to 64) * row bytes of
         device memory - 65 536 pairs of 64 steps with 80-byte rows are 340 MB - and only what is asked for is allocated.  observe needs
         env.lidar_configure (ValueError otherwise); maps its layout cannot hold raise MapsTooLarge while rewards=True alone keeps the path
-        form's limit.  A parent index out of range gives zeros in both fields, obs[0] included.  masks=True is a playout's keyword: ValueError."""
+        form's limit.  A parent index out of range gives zeros in both fields, obs[0] included.  masks=True is a playout's keyword: ValueError.
+        observe='agent_view' (with view_size=V, 1 .. 16, default 5): 'obs' is the AgentMap observation instead, the dict agent_view() returns with the
+        same block rule - 'agent_map' int8 [T + 1, count, W, W] (W = 2 * V + 1, the window around the agent, unrotated, 0 outside the map),
+        'agent_facing_id' int32 [T + 1, count], 'inventory_items_quantity' int32 [T + 1, count, K]; all three all-zero for steps not executed.  It
+        needs no lidar, runs under the path form's layout and keeps its map-size limit; (T + 1) * count (rounded up to 64) * (W * W + 4 + 4 * K)
+        bytes of device memory.  view_size without observe='agent_view' is a ValueError unless it is the default."""
         import torch
         env = self.env
         if masks:
             raise ValueError("masks=True: a rollout makes no choice, so there is no mask word to record (playout() records them)")
-        check_observe(env, observe)
+        check_observe(env, observe, view_size)
         src, n_parents, same_buffer = self._source(source, from_envs, 'rollout')
         dev = torch.device('cuda:%d' % env.device)
         if isinstance(plans, torch.Tensor):
@@ -754,10 +787,10 @@ class Snapshot:
             a = np.ascontiguousarray(a.T)       # step-major [T, count]: 64 lanes read consecutive addresses
         p, c, count = check_rollout(parents, n_plans, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'rollout', x))
         return pairs_call(env, self, 'rollout', src, None if c is None else self._s, p, c, count, steps, device, plans=a, limits=limits, path_keys=path_keys,
-                          fields=fields, rewards=rewards, observe=observe)
+                          fields=fields, rewards=rewards, observe=observe, view_size=view_size)
 
     def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False, weights=None,
-                limits=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None):
+                limits=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None, view_size=5):
         """Pair j: the state of parent parents[j] stepped on a private copy up to `steps` times by rollout()'s rules, with a random policy in
         the place of a plan: at every step the action is drawn uniformly among the actions that would succeed from the state the pair is in
         (every action where none would) - the default-policy simulation of a tree search's leaf, in one kernel launch.  The draw is the
@@ -782,15 +815,16 @@ class Snapshot:
         of step t was made under, after the "no action would succeed -> every action" replacement, 0 for a step not executed - so
         playout.choose_actions(masks[t], seed, first_pair + arange(count), t, A) is actions[t], and sample.choose_weighted does the same for a
         weighted playout: what a learner stores to recompute masked log-probabilities.  The memory, the refusals and the zero rows are
-        rollout()'s."""
+        rollout()'s, and so is observe='agent_view' with view_size."""
         import torch
         env = self.env
-        check_observe(env, observe)
+        check_observe(env, observe, view_size)
         src, n_parents, same_buffer = self._source(source, from_envs, 'playout')
         dev = torch.device('cuda:%d' % env.device)
         p, c, count, steps = check_playout(parents, steps, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'playout', x))
         return pairs_call(env, self, 'playout', src, None if c is None else self._s, p, c, count, steps, device, seed=seed, first_pair=first_pair, record=record,
-                          weights=weights, limits=limits, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe)
+                          weights=weights, limits=limits, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe,
+                          view_size=view_size)
 
     # ------------------------------------------------------------------ slot observations (include/ngw.h ngw_snapshot_lidar / _agent_view / _action_mask)
     def _slots_arg(self, slots):

@@ -175,14 +175,16 @@ class LimitActions(NoveltyWrapper):
         word = sum(1 << ids[i] for i in range(len(ids)) if (int(s.mask_words[0]) >> i) & 1)
         return ids[int(s.action[0])], float(s.mass[0]), word
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None):
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None,
+                 view_size=5):
         """The env's playouts under this wrapper's action list: at every step the action is drawn among the LIMITED actions that would
         succeed (every limited action where none would), and 'first_action' holds limited ids.  The draw needs the limited list as the
         kernel's own action table, so the playouts run on a one-env batched env whose table is the limited one (limit_actions_vec, kept
         from call to call) holding a copy of the current state; they equal what limit_actions_vec() of a batched env gives for that
         state.  weights: one per limited id.  path_keys / fields: as on the env - the keys do not depend on the action id space.
         rewards / masks / observe: as on the env; bit i of a mask word is limited id i, consistent with the actions reported here.  observe needs
-        the lidar configured on the adapter's batched backend (the limited env takes its configuration over)."""
+        the lidar configured on the adapter's batched backend (the limited env takes its configuration over).  observe='agent_view' / view_size:
+        the AgentMap dict, which does not depend on the action id space and needs no lidar."""
         limited, ids = self._limited_env()
         if weights is not None and not hasattr(weights, 'device'):
             w = np.asarray(weights)
@@ -192,8 +194,8 @@ class LimitActions(NoveltyWrapper):
         elif weights is not None and ids != list(range(len(ids))):
             import torch
             weights = weights[torch.tensor(ids, device=weights.device)].contiguous()
-        path = forward_keywords(path_keys, fields, rewards, masks, observe)
-        if observe is not None:                              # the rows are the backend's: its lidar as it is configured NOW, not as it was when the limited env was made
+        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size)
+        if observe is not None and not (isinstance(observe, str) and observe == 'agent_view'):   # (the views need no lidar) the rows are the backend's: its lidar as it is configured NOW, not as it was when the limited env was made
             vec = self.unwrapped._backend()
             mine, theirs = [(e.lidar, e.lidar_packed, e.lidar_dtype) for e in (limited, vec)]
             if vec.lidar is not None and mine != theirs:

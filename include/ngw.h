@@ -816,6 +816,51 @@ int ngw_snapshot_playout_traj(ngw_handle* h, ngw_snapshot* src, const int32_t* s
                               int64_t keys_stride, int32_t* rewards_dev, int64_t rewards_stride, uint64_t* masks_dev, int64_t masks_stride, void* obs_dev,
                               int64_t obs_stride);
 
+/* Trajectories that observe AgentMap views: the two calls above with the observation of ngw_snapshot_agent_view in the place of the lidar rows -
+ * the egocentric window, the facing id and the inventory of the parent and of the state every step leaves.  `views` names the outputs, all device
+ * memory, each recorded only where its pointer is not NULL (not all three NULL):
+ *   view_dev    int8  [n_steps + 1][stride][W][W], W = 2 * view_size + 1: cell (i, k) of a window is map cell (r - view_size + i, c - view_size + k)
+ *               of the state, (r, c) the agent's cell, 0 outside the map; the window is NOT rotated with the facing (the reference's get_agentView).
+ *   facing_dev  int32 [n_steps + 1][stride]: the facing id.
+ *   inv_dev     int32 [n_steps + 1][stride][K]: the inventory, K = the spec's item count.
+ * Row numbering is the lidar rows': n_steps + 1 ROW BLOCKS of `stride` rows each, row j of block 0 is the parent of pair j, row j of block t + 1 the
+ * state step t leaves, before any reset; every row is exactly what ngw_snapshot_agent_view returns for a slot holding that state.  All three are
+ * all zeros for a step the pair did not execute (its episode is over, its limit is reached) and in every block - block 0 included - for a skipped
+ * pair (NGW_F_BAD_INDEX).  One wavefront serves 64 consecutive pairs and stores its 64 rows of a block as one run of consecutive dwords: stride
+ * must be a multiple of 64 and at least count rounded up to 64, view_dev 16-byte aligned (facing_dev, inv_dev: 4), and rows count .. of every block
+ * (up to the next multiple of 64) are written with zeros; rows beyond that are not touched.  Offsets are 64-bit: the buffers may exceed 4 GiB.
+ * view_size is in [1, NGW_TRAJ_VIEW_MAX].  obs_dev must be NULL: a call observes one kind.  ngw_lidar_configure is not needed, and nothing of the
+ * lidar - configured or not, fused or not - is read or written.
+ * Everything else - rewards, masks, limits, keys, reports, index rules, ordering, the stream, what is committed: nothing - is the _traj calls', which
+ * are these calls with views == NULL.  One kernel launch (the same kernels: the view outputs are run-time arguments of the TRAJ forms); the windows
+ * are built from the wavefront's 64 maps in LDS, no row leaves it.
+ * Map sizes.  The launch runs under the handle's rollout layout - the path calls' layout - with the 64 * (K | 1) dwords of inventory shadows behind it
+ *   only where keys_dev is set; the views need no LDS of their own.  So every handle the path calls serve is served - the Pogostick spec up to
+ *   47 x 47, with keys too; with a fused int32 lidar of 8 beams (a larger layout of the handle's own) up to 45 x 45 without keys and 44 x 44 with
+ *   them (45 x 45: 164 432 B) - while the lidar rows stop at 46 x 46 / 44 x 44 by their own layout.  A handle beyond it is refused: the message
+ *   starts with "map_size" and names the bytes.
+ * NGW_E_INVALID_ARG: what the _traj calls refuse; a NULL handle; views with all three pointers NULL; view_size outside [1, NGW_TRAJ_VIEW_MAX]; a stride
+ * that is no multiple of 64 or below count rounded up to 64; a view_dev that is not 16-byte aligned; obs_dev and views both set; a layout that does
+ * not fit LDS. */
+#define NGW_TRAJ_VIEW_MAX 16
+typedef struct ngw_traj_views {
+    int32_t view_size;
+    int8_t* view_dev;
+    int32_t* facing_dev;
+    int32_t* inv_dev;
+    int64_t stride;
+} ngw_traj_views;
+int ngw_snapshot_rollout_traj_views(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, const int32_t* actions_dev, int64_t pair_stride,
+                                    int32_t n_steps, const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count, int32_t* ret_dev,
+                                    int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, uint32_t fields, uint64_t* keys_dev, int64_t keys_stride,
+                                    int32_t* rewards_dev, int64_t rewards_stride, void* obs_dev, int64_t obs_stride, const ngw_traj_views* views);
+int ngw_snapshot_playout_traj_views(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed,
+                                    uint64_t first_pair, const float* weights_dev /* NULL: the uniform rule */, const int32_t* limits_dev, ngw_snapshot* dst,
+                                    const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev,
+                                    int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride, uint32_t fields, uint64_t* keys_dev,
+                                    int64_t keys_stride, int32_t* rewards_dev, int64_t rewards_stride, uint64_t* masks_dev, int64_t masks_stride, void* obs_dev,
+                                    int64_t obs_stride, const ngw_traj_views* views);
+
 /* Key table: an open-addressing hash set of 64-bit keys in device memory - "have I seen this state BEFORE?" across the calls of a search that
  * runs many iterations (transposition tables, duplicate removal in breadth-first solvers, Go-Explore archives, count-based bonuses).  A table
  * belongs to the handle that created it; it stores keys and nothing else: a caller keeps what it wants per state (visit counts, the best return,
