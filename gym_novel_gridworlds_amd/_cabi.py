@@ -30,7 +30,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_snapshot_create', 'ngw_snapshot_destroy', 'ngw_snapshot_save', 'ngw_snapshot_restore', 'ngw_snapshot_get', 'ngw_snapshot_expand', 'ngw_snapshot_rollout',
            'ngw_snapshot_lidar', 'ngw_snapshot_agent_view', 'ngw_snapshot_action_mask', 'ngw_state_keys', 'ngw_snapshot_copy', 'ngw_successor_keys', 'ngw_snapshot_playout',
            'ngw_snapshot_playout_weighted', 'ngw_sample_actions', 'ngw_snapshot_rollout_path', 'ngw_snapshot_playout_path',
-           'ngw_snapshot_rollout_traj', 'ngw_snapshot_playout_traj', 'ngw_snapshot_rollout_traj_views', 'ngw_snapshot_playout_traj_views',
+           'ngw_snapshot_rollout_traj', 'ngw_snapshot_playout_traj', 'ngw_snapshot_rollout_traj_views', 'ngw_snapshot_playout_traj_views', 'ngw_snapshot_playout_guided',
            'ngw_key_table_create', 'ngw_key_table_destroy', 'ngw_key_table_clear', 'ngw_key_table_insert', 'ngw_key_table_lookup', 'ngw_key_table_count',
            'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
@@ -211,6 +211,8 @@ def lib():
         L.ngw_key_table_insert.argtypes = [vp, vp, vp, i64, vp, vp]
         L.ngw_key_table_lookup.argtypes = [vp, vp, vp, i64, vp]
         L.ngw_key_table_count.argtypes = [vp, vp, C.POINTER(i64)]
+    if hasattr(L, 'ngw_snapshot_playout_guided'):            # (the _traj_views playout, then the table, its weight rows, where + stride, depth, outside)
+        L.ngw_snapshot_playout_guided.argtypes = L.ngw_snapshot_playout_traj_views.argtypes + [vp, vp, vp, i64, vp, i32]
     if hasattr(L, 'ngw_lookahead'):
         L.ngw_lookahead.argtypes = [vp]
         L.ngw_get_lookahead.argtypes = [vp, vp, vp, vp]

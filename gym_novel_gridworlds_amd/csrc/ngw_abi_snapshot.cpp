@@ -13,6 +13,8 @@
 // The trajectory forms (ngw_traj.inc) add the per-step rewards, mask words and LidarInFront rows of such a path: they commit nothing either, and
 // leave the env's own lidar rows alone.  Their AgentMap views (the _traj_views entry points) are outputs of the same launches under the path form's
 // layout: no lidar is needed or touched.
+// A guided playout (ngw_playout.inc, GUIDED) reads a key table and the caller's weight rows at every step: it commits nothing either, and leaves
+// the table as it was.
 // The weighted choice (ngw_sample.inc) draws one action per row by the caller's weights among the valid ones: it commits nothing either.
 #include "ngw_host.h"
 
@@ -31,6 +33,13 @@ NgwSnapRows state_rows(const ngw_handle* h) {
 bool owns(const ngw_handle* h, const ngw_snapshot* s) {
     for (const ngw_snapshot* q : h->snaps)
         if (q == s) return true;
+    return false;
+}
+
+// is `t` an open key table of `h`?  (by address, as owns())
+bool owns_table(const ngw_handle* h, const ngw_key_table* t) {
+    for (const ngw_key_table* q : h->tables)
+        if (q == t) return true;
     return false;
 }
 
@@ -120,8 +129,11 @@ struct TrajArgs { int32_t* rewards; int64_t rewards_stride; uint64_t* masks; int
 // where the actions come from: a plan [n_steps][stride], or the kernel draws them (weights NULL: the uniform rule; actions NULL: not recorded)
 struct Plan { const int32_t* actions; int64_t stride; };
 struct Draw { uint64_t seed, first_pair; const float* weights; int32_t* first_action; int32_t* actions; int64_t stride; };
+// what a guided playout asks for beyond a trajectory playout: the table its states are looked up in, the [buckets][n_actions] weight rows, where the
+// buckets and the depths go, and what a state outside the table does (include/ngw.h NGW_OUTSIDE_*)
+struct GuideArgs { ngw_key_table* table; const float* rows; int32_t* where; int64_t where_stride; int32_t* depth; int32_t outside; };
 
-// The one request behind the seven exported rollouts and playouts: step `count` pairs of saved rows up to n_steps times.  The form is the entry
+// The one request behind the eight exported rollouts and playouts: step `count` pairs of saved rows up to n_steps times.  The form is the entry
 // point's, never read off the pointers: a path call without limits and keys is still a path call.  The entry points fill it by member name.
 enum Form { PLAIN, PATH, TRAJ };
 struct Pairs {
@@ -131,6 +143,7 @@ struct Pairs {
     int32_t* ret; int32_t* length; uint8_t* ended; uint32_t* info;   // the four reports, any may be NULL
     Form form; PathArgs pa; TrajArgs ta;             // (pa: PATH and TRAJ, ta: TRAJ; zeros otherwise)
     bool draws; Plan plan; Draw draw;                // (the one `draws` names; zeros otherwise)
+    bool guided; GuideArgs ga;                       // (a TRAJ playout whose weights a key table chooses; zeros otherwise)
 };
 
 // the six launchers and the entry points they serve, by where the actions come from and by form
@@ -141,15 +154,18 @@ const PairsLaunch<NgwPlayout> PLAYOUT_LAUNCH[3] = {ngw_playout_launch, ngw_playo
 const char* const PAIRS_CALL[2][3] = {{"ngw_snapshot_rollout", "ngw_snapshot_rollout_path", "ngw_snapshot_rollout_traj"},
                                       {"ngw_snapshot_playout", "ngw_snapshot_playout_path", "ngw_snapshot_playout_traj"}};
 const char* const VIEWS_CALL[2] = {"ngw_snapshot_rollout_traj_views", "ngw_snapshot_playout_traj_views"};   // (TRAJ with a views struct)
+const char* const GUIDED_CALL = "ngw_snapshot_playout_guided";                                                // (TRAJ with a table: views or not)
 
 // The path and trajectory arguments of one request, checked (before anything touches the stream) -> the LDS bytes of the launch and where the
 // inventory shadows sit.  Without observations: the path form's layout and its map limit.  With them: the stand-alone lidar launch's layout
 // (ngw_lidar_configure), and the shadows behind it only where keys are asked for.  With AgentMap views: the handle's rollout layout as it is, and
-// the shadows behind it only where keys are asked for - the views need no LDS of their own.
+// the shadows behind it only where keys are asked for - the views need no LDS of their own.  A guided playout keeps the running key whether or not
+// keys are asked for: it has the shadows wherever a keyed call has them.
 int path_traj_args(const ngw_handle* h, const Pairs& p, const char* what, const char* call, size_t* lds, uint32_t* off_shadow) {
     const PathArgs& pa = p.pa;
     const TrajArgs& ta = p.ta;
     const int64_t count = p.count;
+    const bool shadows = pa.keys || p.guided;
     if (ta.rewards && ta.rewards_stride < count)
         return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a reward stride of %lld", what, (long long)count, (long long)ta.rewards_stride);
     if (ta.masks && ta.masks_stride < count)
@@ -167,15 +183,15 @@ int path_traj_args(const ngw_handle* h, const Pairs& p, const char* what, const 
         if (reinterpret_cast<uintptr_t>(v.view) & 15u) return fail(NGW_E_INVALID_ARG, "%s: the view windows must be 16-byte aligned", what);
         if ((reinterpret_cast<uintptr_t>(v.facing) | reinterpret_cast<uintptr_t>(v.inv)) & 3u)
             return fail(NGW_E_INVALID_ARG, "%s: the facing ids and the inventories must be 4-byte aligned", what);
-        *lds = h->lds_bytes + (pa.keys ? (size_t)NGW_EPB * 4u * (size_t)h->proto.KP : 0u);
+        *lds = h->lds_bytes + (shadows ? (size_t)NGW_EPB * 4u * (size_t)h->proto.KP : 0u);
         if (!h->general_ok)                          // (the handle kept no rollout layout: its maps and inventories alone are what can be named)
             return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps in LDS (%s) under the handle's rollout layout, whose maps and inventories "
                                            "alone take %zu B and which exceeds 160 KiB as a whole; per-launch steps with ngw_agent_view are available", h->proto.S, call,
                         (size_t)NGW_EPB * (size_t)h->proto.MS + (size_t)NGW_EPB * 4u * (size_t)h->proto.KP);
         if (*lds > NGW_PATH_LDS_MAX)
             return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps%s in LDS (%s) and they need %zu B, more than 160 KiB; %s", h->proto.S,
-                        pa.keys ? " and a second copy of their inventories" : "", call, *lds,
-                        pa.keys ? "the views without keys have the handle's own limit" : "per-launch steps with ngw_agent_view are available");
+                        shadows ? " and a second copy of their inventories" : "", call, *lds,
+                        shadows ? "the views without keys have the handle's own limit" : "per-launch steps with ngw_agent_view are available");
         return NGW_OK;
     }
     if (!ta.obs) {
@@ -194,11 +210,11 @@ int path_traj_args(const ngw_handle* h, const Pairs& p, const char* what, const 
     lidar_format(h, q);
     const size_t rows = lidar_layout(h, q);
     *off_shadow = (uint32_t)(rows / 4);
-    *lds = rows + (pa.keys ? (size_t)NGW_EPB * 4u * (size_t)h->proto.KP : 0u);
+    *lds = rows + (shadows ? (size_t)NGW_EPB * 4u * (size_t)h->proto.KP : 0u);
     if (*lds > NGW_PATH_LDS_MAX || (h->general_ok && !h->lidar_lds))   // (general_ok == 0 with a layout that would fit: the plain refusal follows)
         return fail(NGW_E_INVALID_ARG, "map_size %d: this call keeps a wavefront's 64 maps between two guards, the lidar tables and a tile of 64 observation rows%s in "
                                        "LDS (%s) and they need %zu B, more than 160 KiB; the call without observations %s", h->proto.S,
-                    pa.keys ? " and a second copy of the inventories" : "", call, *lds, h->general_ok ? "has its own limit" : "is refused too");
+                    shadows ? " and a second copy of the inventories" : "", call, *lds, h->general_ok ? "has its own limit" : "is refused too");
     return NGW_OK;
 }
 
@@ -224,7 +240,7 @@ void fill_pairs(X& x, const Pairs& p, const Source& from, uint32_t off_shadow) {
 // one request served: every check (in the order the entry points have always made them) before enter(h) and the first use of the stream, then one launch
 int step_pairs(ngw_handle* h, const Pairs& p) {
     const char* const what = p.draws ? "playout" : "rollout";
-    const char* const call = p.ta.views ? VIEWS_CALL[p.draws] : PAIRS_CALL[p.draws][p.form];
+    const char* const call = p.guided ? GUIDED_CALL : (p.ta.views ? VIEWS_CALL[p.draws] : PAIRS_CALL[p.draws][p.form]);
     const int64_t stride = p.draws ? p.draw.stride : p.plan.stride;
     if (!h || (!p.draws && !p.plan.actions)) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (p.n_steps < 1) return fail(NGW_E_INVALID_ARG, "%s of %d steps", what, (int)p.n_steps);
@@ -232,6 +248,18 @@ int step_pairs(ngw_handle* h, const Pairs& p) {
         return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with %s stride of %lld", what, (long long)p.count, p.draws ? "an action" : "a pair", (long long)stride);
     if (!p.draws && !p.dst && !p.ret && !p.length && !p.ended && !p.info && !p.pa.keys && !p.ta.rewards && !p.ta.obs && !p.ta.views)
         return fail(NGW_E_INVALID_ARG, "rollout without a destination and without a report: nothing to do");
+    if (p.guided) {                                  // (the table and the rows: before anything touches the stream)
+        const GuideArgs& g = p.ga;
+        if (!g.table || !g.rows) return fail(NGW_E_INVALID_ARG, "NULL argument");
+        if (!owns_table(h, g.table)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
+        if (g.outside != NGW_OUTSIDE_DEFAULT && g.outside != NGW_OUTSIDE_STOP)
+            return fail(NGW_E_INVALID_ARG, "outside %d: NGW_OUTSIDE_DEFAULT or NGW_OUTSIDE_STOP expected", (int)g.outside);
+        if (g.table->buckets < 2 || g.table->buckets > (1ull << 30) || (g.table->buckets & (g.table->buckets - 1)))   // (what ngw_key_table_create makes; the kernel's bucket is an int32)
+            return fail(NGW_E_INVALID_ARG, "%s: a key table of %llu buckets; a power of two in [2, 2^30] expected", GUIDED_CALL, (unsigned long long)g.table->buckets);
+        if (int rc = key_args(p.pa.fields)) return rc;   // (the state that is looked up is named by `fields`, keys recorded or not)
+        if (g.where && g.where_stride < p.count)
+            return fail(NGW_E_INVALID_ARG, "%s of %lld pairs with a bucket stride of %lld", what, (long long)p.count, (long long)g.where_stride);
+    }
     Source from;
     size_t lds = h->lds_bytes;
     uint32_t off_shadow = (uint32_t)(h->lds_bytes / 4);
@@ -254,6 +282,13 @@ int step_pairs(ngw_handle* h, const Pairs& p) {
         x.actions = p.draw.actions; x.stride = p.draw.stride; x.first_action = p.draw.first_action;
         x.seed = p.draw.seed; x.first_pair = p.draw.first_pair; x.weights = p.draw.weights;
         if (p.form == TRAJ) { x.masks = p.ta.masks; x.masks_stride = p.ta.masks_stride; }
+        if (p.guided) {
+            const ngw_key_table* const t = p.ga.table;
+            x.tkey = t->slab; x.tmask = t->buckets - 1; x.table_weights = p.ga.rows; x.tw_stride = h->spec.n_actions;
+            x.where = p.ga.where; x.where_stride = p.ga.where_stride; x.depth = p.ga.depth; x.stop = p.ga.outside == NGW_OUTSIDE_STOP;
+            HIP_TRY(ngw_playout_guided_launch(h->dspec, &a, &x, h->ext, lds, h->stream));
+            return NGW_OK;
+        }
         HIP_TRY(PLAYOUT_LAUNCH[p.form](h->dspec, &a, &x, h->ext, lds, h->stream));
     }
     return NGW_OK;
@@ -455,6 +490,25 @@ int ngw_snapshot_playout_traj_views(ngw_handle* h, ngw_snapshot* src, const int3
     p.pa.limits = limits_dev; p.pa.fields = fields; p.pa.keys = keys_dev; p.pa.keys_stride = keys_stride;
     p.ta.rewards = rewards_dev; p.ta.rewards_stride = rewards_stride; p.ta.obs = obs_dev; p.ta.obs_stride = obs_stride; p.ta.masks = masks_dev; p.ta.masks_stride = masks_stride;
     views_arg(p.ta, views);
+    return step_pairs(h, p);
+}
+
+int ngw_snapshot_playout_guided(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                                const float* weights_dev, const int32_t* limits_dev, ngw_snapshot* dst, const int32_t* dst_slots_dev, int32_t* ret_dev,
+                                int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev, int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride,
+                                uint32_t fields, uint64_t* keys_dev, int64_t keys_stride, int32_t* rewards_dev, int64_t rewards_stride, uint64_t* masks_dev,
+                                int64_t masks_stride, void* obs_dev, int64_t obs_stride, const ngw_traj_views* views, ngw_key_table* table,
+                                const float* table_weights_dev, int32_t* where_dev, int64_t where_stride, int32_t* depth_dev, int32_t outside) {
+    Pairs p{};
+    p.src = src; p.src_idx = src_idx_dev; p.dst = dst; p.dst_slots = dst_slots_dev; p.count = count; p.n_steps = n_steps;
+    p.ret = ret_dev; p.length = length_dev; p.ended = ended_dev; p.info = info_dev;
+    p.form = TRAJ; p.draws = true; p.draw.seed = seed; p.draw.first_pair = first_pair; p.draw.weights = weights_dev;
+    p.draw.first_action = first_action_dev; p.draw.actions = actions_dev; p.draw.stride = actions_stride;
+    p.pa.limits = limits_dev; p.pa.fields = fields; p.pa.keys = keys_dev; p.pa.keys_stride = keys_stride;
+    p.ta.rewards = rewards_dev; p.ta.rewards_stride = rewards_stride; p.ta.obs = obs_dev; p.ta.obs_stride = obs_stride; p.ta.masks = masks_dev; p.ta.masks_stride = masks_stride;
+    views_arg(p.ta, views);
+    p.guided = true;
+    p.ga.table = table; p.ga.rows = table_weights_dev; p.ga.where = where_dev; p.ga.where_stride = where_stride; p.ga.depth = depth_dev; p.ga.outside = outside;
     return step_pairs(h, p);
 }
 

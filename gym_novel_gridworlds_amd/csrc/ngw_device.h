@@ -591,6 +591,19 @@ struct NgwPlayout {
     void* obs;
     int64_t obs_stride;
     struct NgwTrajViews vw; /* the AgentMap views in the place of obs (last again): the launch block stays the path form's */
+    /* the guided form (GUIDED; last again; read by ngw_playout_guided_launch alone).  tkey: the key[] array of a key table of tmask + 1 buckets (a power
+     * of two), only read.  table_weights: float32 [tmask + 1][tw_stride], row b the weights of the steps taken from the state bucket b holds; a state
+     * the table does not hold draws by `weights` (nullptr: the uniform rule) or, with stop != 0, ends the pair there as a limit would.  where: nullptr,
+     * or the bucket of the state pair j was in before step t to where[t * where_stride + j], -1 for a miss and for a step the pair did not execute;
+     * depth: nullptr, or [count], the leading executed steps with where >= 0.  fields is never 0 and the shadows lie behind the layout whether or not
+     * keys is set: the running key is what is looked up. */
+    const uint64_t* tkey;
+    uint64_t tmask;
+    const float* table_weights;
+    int32_t* where;
+    int64_t where_stride;
+    int32_t* depth;
+    int32_t tw_stride, stop;
 };
 #ifdef __cplusplus
 extern "C"
@@ -613,6 +626,12 @@ hipError_t ngw_slot_rollout_traj_launch(const NgwDevSpec* dspec, const NgwLaunch
 extern "C"
 #endif
 hipError_t ngw_playout_traj_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+/* the guided form (PATH, TRAJ and GUIDED): ngw_playout_traj_launch's block and lds_bytes with the shadows ALWAYS behind the layout (x->off_shadow), and
+ * x->tkey / x->tmask / x->table_weights / x->tw_stride / x->stop read; x->fields is a non-empty selection whether or not x->keys is set */
+hipError_t ngw_playout_guided_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream);
 
 /* Slot observations (ngw_slot_observe.inc, ngw_abi_snapshot.cpp): observations and action masks of SAVED states, gathered by slot index. Output
  * row j of a call describes row slots[j] of `src` (a snapshot; a NULL list = j itself).  An index outside [0, rows) is never used as an address:

@@ -74,6 +74,16 @@ __device__ __forceinline__ int path_front_group(const PathKeys& pk, int S, int r
     return grp;
 }
 
+// the key of the state the running parts and these registers describe: the parts and the scalar terms.  Right behind path_begin, with the
+// parent's registers, it is the parent's key - what the GUIDED playout looks up before step 0
+__device__ __forceinline__ uint64_t path_key(const PathKeys& pk, uint32_t fields, int r, int c, int f, int sel, int steps) {
+    uint64_t key = pk.map ^ pk.inv ^ pk.episode;
+    if (fields & NGW_KEY_POSE) key ^= key_term(2u, 0u, (uint32_t)(r | c << 8 | f << 16));
+    if (fields & NGW_KEY_SELECTED) key ^= key_term(4u, 0u, (uint32_t)sel);
+    if (fields & NGW_KEY_STEP_COUNT) key ^= key_term(5u, 0u, (uint32_t)steps);
+    return key;
+}
+
 // the step is done: the parts follow the row, and the key of the state it left
 __device__ __forceinline__ uint64_t path_after_step(PathKeys& pk, const LeanOut& o, int grp, uint32_t before, const int32_t* inv, int K, uint32_t fields) {
     if (pk.k_map) {
@@ -102,11 +112,7 @@ __device__ __forceinline__ uint64_t path_after_step(PathKeys& pk, const LeanOut&
 #pragma unroll 1
         for (; i < K; i++) one(i);
     }
-    uint64_t key = pk.map ^ pk.inv ^ pk.episode;
-    if (fields & NGW_KEY_POSE) key ^= key_term(2u, 0u, (uint32_t)(o.r | o.c << 8 | o.f << 16));
-    if (fields & NGW_KEY_SELECTED) key ^= key_term(4u, 0u, (uint32_t)o.sel);
-    if (fields & NGW_KEY_STEP_COUNT) key ^= key_term(5u, 0u, (uint32_t)o.steps);
-    return key;
+    return path_key(pk, fields, o.r, o.c, o.f, o.sel, o.steps);
 }
 
 // what the two path launches check beyond the plain ones: a field selection where keys are asked for, a stride that holds the pairs, the shadows inside LDS

@@ -6,6 +6,7 @@
 #include "ngw_sample.inc"          // the choice among the valid actions
 #include "ngw_path.inc"            // the PATH form's keys and step limits
 #include "ngw_traj.inc"            // the TRAJ form's per-step rewards, mask words and lidar rows
+#include "ngw_table.inc"           // table_find: the GUIDED form's look-up
 
 namespace {
 //
@@ -43,9 +44,19 @@ namespace {
 // the kernel as it was.  x.vw (AgentMap views, ngw_traj.inc) takes the window, the facing id and the inventory of the same states by the same block
 // rule under the PATH form's launch block: run-time outputs of this form, all nullptr = the form as it was.
 //
+// GUIDED (ngw_snapshot_playout_guided; a PATH and TRAJ form, instantiated in ngw_unit_playout_guided.hip alone): the rule of include/ngw.h.  The
+// running key is kept whether or not x.keys is set, and the key a step leaves is the key the next step looks up: one key per step.  Before the
+// choice an alive lane walks the table (table_find: per-lane divergent, read-only, bounded by the buckets, waits for nobody) for the key of the
+// state it is in; x.stop with a miss clears `alive` there, in the place of the limit.  The step's weights are the lane's ROW: x.table_weights +
+// b * x.tw_stride on a hit, x.weights on a miss - nullptr reads as zeros, and mass 0 is the uniform rule on the same w, so the form needs no
+// WEIGHTED twin -, read in place by sample_choice: 2 * A dwords per lane and step, a row contiguous.  A frozen lane (b = -1) reads x.weights or
+// nothing and its result, its F_BAD_WEIGHT included, is discarded.  x.where[t * x.where_stride + j] takes b of every executed step (-1: a miss,
+// or not executed), x.depth[j] the leading executed steps with b >= 0.  The wave-uniform parts - lean_mask_walk, sample_choice's two walks,
+// path_after_step's votes - are outside the divergent walk.  GUIDED = false is the kernel as it was.
+//
 // x.actions (may be nullptr): int32, the action of pair j at step t to [t * x.stride + j] (stride >= count) - the layout ngw_slot_rollout_kernel reads.
 
-template <int VEC, bool EXT, bool WEIGHTED, bool PATH = false, bool TRAJ = false>
+template <int VEC, bool EXT, bool WEIGHTED, bool PATH = false, bool TRAJ = false, bool GUIDED = false>
 __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* __restrict__ dspec, const NgwLaunch a, const NgwPlayout x) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t tid = threadIdx.x;
@@ -116,7 +127,14 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
     if constexpr (PATH) {
         pa.limit = x.limits && ok ? min(max(x.limits[pair], 0), n_steps) : n_steps;
         pa.kout = x.keys && inside ? x.keys + pair : nullptr;
-        if (x.keys) pa.pk = path_begin(lds_map + tid * MSdw, inv, lds + x.off_shadow + tid * KP, S2, K, x.fields, episode);
+        if (GUIDED || x.keys) pa.pk = path_begin(lds_map + tid * MSdw, inv, lds + x.off_shadow + tid * KP, S2, K, x.fields, episode);
+    }
+    uint64_t kcur = 0;                                                             // GUIDED: the key of the state the pair is in before the step under way
+    int depth = 0;
+    int32_t* wrec = nullptr;
+    if constexpr (GUIDED) {
+        kcur = path_key(pa.pk, x.fields, r, c, f, sel, steps);
+        wrec = x.where && inside ? x.where + pair : nullptr;
     }
     TrajLane<TRAJ> tr;
     if constexpr (TRAJ) {
@@ -135,7 +153,18 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
         const uint32_t qq = (uint32_t)s & 3u;
         const uint32_t w = qq == 0 ? w0 : (qq == 1 ? w1 : (qq == 2 ? w2 : w3));
         int action;
-        if constexpr (WEIGHTED) {                                                  // rules 3 - 6 of ngw_sample_actions on this m and this w; every lane walks
+        if constexpr (GUIDED) {
+            const int b = (alive && kcur) ? table_find(x.tkey, x.tmask, kcur) : -1;     // (only alive lanes walk; key 0 is never stored)
+            if (x.stop && b < 0) alive = false;                                    // the leaf: as if limits[j] were s
+            if (wrec) wrec[(int64_t)s * x.where_stride] = alive ? b : -1;
+            if (alive && b >= 0 && depth == s) depth++;
+            const float* const row = b >= 0 ? x.table_weights + (size_t)b * (size_t)x.tw_stride : x.weights;
+            float mass;
+            uint32_t wf = 0;
+            const int drawn = sample_choice(m, w, A, [&](int a) -> float { return row ? row[a] : 0.0f; }, mass, wf);
+            if (alive) flags |= wf;                                                // (a bad weight counts where its row was read for a step that ran)
+            action = alive ? drawn : -1;
+        } else if constexpr (WEIGHTED) {                                                  // rules 3 - 6 of ngw_sample_actions on this m and this w; every lane walks
             float mass;
             const int drawn = sample_choice(m, w, A, [&](int a) -> float { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, xw), a)); },
                                             mass, flags);
@@ -151,15 +180,16 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
         const uint32_t e2 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t2), e3 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t3);
         const uint32_t e4 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t4), e5 = (uint32_t)__builtin_amdgcn_ds_bpermute(ai, (int)t.t5);
         if constexpr (PATH)
-            if (x.keys) pa.grp = path_front_group(pa.pk, Sv, r, c, f, pa.before);
+            if (GUIDED || x.keys) pa.grp = path_front_group(pa.pk, Sv, r, c, f, pa.before);
         const LeanOut o = lean_body<true, false, EXT>(UV, X, e0, e1, e2, e3, e4, e5, alive, alive, Sv, Kv, mp, inv, nullptr, nullptr, 0u, 0u, r, c, f, sel, steps,
                                                       autoreset, horizon);
         r = o.r; c = o.c; f = o.f; sel = o.sel; steps = o.steps;                   // (a no-op entry hands them back unchanged: an ended pair stays frozen)
         flags |= o.flags;
         if constexpr (PATH)
-            if (x.keys) {                                                          // (wave-uniform; every lane walks it: path_after_step votes)
+            if (GUIDED || x.keys) {                                                // (wave-uniform; every lane walks it: path_after_step votes)
                 const uint64_t key = path_after_step(pa.pk, o, pa.grp, pa.before, inv, Kv, x.fields);
                 if (pa.kout) pa.kout[(int64_t)s * x.keys_stride] = alive ? key : 0ull;
+                if constexpr (GUIDED) kcur = key;                                  // (a frozen lane's row did not move: its key stays what it was)
             }
         if constexpr (TRAJ) {                                                      // (`alive` still says: this pair executed this step)
             if (tr.rew) tr.rew[(int64_t)s * x.rewards_stride] = alive ? o.reward : 0;
@@ -183,6 +213,11 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
             for (int u = s; u < n_steps; u++) tr.msk[(int64_t)u * x.masks_stride] = 0ull;
         if (x.obs) traj_zero_tiles(a, tid, x.obs, x.obs_stride, s, n_steps);
         if (traj_views_on(x.vw)) traj_zero_views(a, x.vw, tid, s, n_steps);
+    }
+    if constexpr (GUIDED) {
+        if (wrec)
+            for (int u = s; u < n_steps; u++) wrec[(int64_t)u * x.where_stride] = -1;
+        if (x.depth && inside) x.depth[pair] = depth;
     }
     if (rec && inside)
         for (; s < n_steps; s++) rec[(int64_t)s * tstride] = -1;                   // the steps no pair of this wave executed
@@ -216,21 +251,31 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
 
 // a = the handle's rollout layout with a.autoreset, a.horizon; one wave per 64 pairs.  PATH: lds_bytes = NGW_PATH_LDS_BYTES(the handle's, KP).
 // TRAJ: as PATH, or with x->obs the stand-alone lidar launch's layout (ngw_device.h, ngw_playout_traj_launch)
-template <bool PATH, bool TRAJ = false>
+// GUIDED: as TRAJ, with the shadows behind the layout whether or not x->keys is set, the table, the rows and x->where / x->depth
+template <bool PATH, bool TRAJ = false, bool GUIDED = false>
 hipError_t playout_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const NgwPlayout* x, int ext, size_t lds_bytes, hipStream_t stream) {
     if (!slot_step_args_ok(a, x) || (x->actions && x->stride < x->count) ||
         (PATH && !TRAJ && !path_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes)) ||
         (TRAJ && !traj_args_ok(a, x->count, x->keys, x->keys_stride, x->fields, x->off_shadow, lds_bytes, x->rewards, x->rewards_stride, x->masks, x->masks_stride,
                                x->obs, x->obs_stride, x->vw)))
         return hipErrorInvalidValue;
+    if constexpr (GUIDED)
+        if (!x->tkey || !x->table_weights || x->tmask < 1 || x->tmask >= 0x7FFFFFFFull || (x->tmask & (x->tmask + 1)) || x->tw_stride < 1 ||
+            (x->where && x->where_stride < x->count) || !x->fields || (x->fields & ~NGW_KEY_ALL) ||
+            ((size_t)x->off_shadow + (size_t)NGW_EPB * (size_t)a->KP) * 4u > lds_bytes ||
+            ((size_t)a->off_inv + (size_t)NGW_EPB * (size_t)a->KP) * 4u > (size_t)x->off_shadow * 4u)
+            return hipErrorInvalidValue;
     const dim3 grid((unsigned)blocks_for(x->count)), block(NGW_EPB);
     NgwPlayout y = *x;
     if (TRAJ) y.vw = traj_views_ready(x->vw);
     return with_row_piece(a->S2, [&](auto V) {
         return with_flag(ext != 0, [&](auto E) {
-            return with_flag(x->weights != nullptr, [&](auto W) {
-                return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, decltype(W)::value, PATH, TRAJ>>(grid, block, lds_bytes, stream, dspec, *a, y);
-            });
+            if constexpr (GUIDED)                                                  // (the weights are run-time rows: no WEIGHTED twin)
+                return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, false, true, true, true>>(grid, block, lds_bytes, stream, dspec, *a, y);
+            else
+                return with_flag(x->weights != nullptr, [&](auto W) {
+                    return launch_kernel<ngw_playout_kernel<decltype(V)::value, decltype(E)::value, decltype(W)::value, PATH, TRAJ>>(grid, block, lds_bytes, stream, dspec, *a, y);
+                });
         });
     });
 }

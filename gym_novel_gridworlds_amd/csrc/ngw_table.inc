@@ -19,8 +19,10 @@ namespace {
 // new key the smallest wins whatever order the lanes ran in: `fresh` is deterministic where the choice of the bucket is not.
 // The two launches are not folded into one: position j may only be called fresh once EVERY lane of the call that carries the same key has made
 // its atomic min, which one launch could only know by waiting for other work-groups.
-// Lookup (table_probe<false>): the same walk with plain loads; it ends at the key or at an empty bucket.
+// Lookup (table_probe<false>): the same walk with plain loads; it ends at the key or at an empty bucket.  The walk is table_find below - the
+// one statement of the read-only probe, which the guided playout (ngw_playout.inc, GUIDED) calls for the state a pair is in at every step.
 // No early exit: every lane reaches the wave-wide count of placed keys (one atomic add per wave).
+// The kernels are the table unit's alone (ngw_unit_table.hip defines NGW_TABLE_UNIT); every other unit that includes this file gets the walk.
 
 __device__ __forceinline__ uint64_t table_mix64(uint64_t x) {
     x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
@@ -28,6 +30,20 @@ __device__ __forceinline__ uint64_t table_mix64(uint64_t x) {
     return x ^ (x >> 31);
 }
 
+// The read-only walk: the bucket of `key[]` (mask + 1 of them, a power of two) that holds `key` (never 0: the caller answers -1 for it), or -1
+// where the walk meets an empty bucket or has looked at every bucket.  Plain loads, no store, no wait for another lane; it diverges per lane
+// and is bounded by the number of buckets.  Every address is b & mask: inside the table whatever the key.
+__device__ __forceinline__ int32_t table_find(const uint64_t* __restrict__ keys, uint64_t mask, uint64_t key) {
+    uint64_t b = table_mix64(key) & mask;
+    for (uint64_t n = 0; n <= mask; n++, b = (b + 1) & mask) {
+        const uint64_t cur = keys[b];
+        if (!cur) break;                                           // absent
+        if (cur == key) return (int32_t)b;
+    }
+    return -1;
+}
+
+#ifdef NGW_TABLE_UNIT
 template <bool INSERT>
 __global__ void __launch_bounds__(NGW_TABLE_BLOCK) ngw_table_probe_kernel(const NgwTable x) {
     const int64_t j = (int64_t)blockIdx.x * NGW_TABLE_BLOCK + threadIdx.x;
@@ -35,13 +51,14 @@ __global__ void __launch_bounds__(NGW_TABLE_BLOCK) ngw_table_probe_kernel(const 
     const uint64_t key = inside ? x.keys[j] : 0ull;               // (key 0 is never stored: the empty mark, and ngw_state_keys' answer to a bad index)
     int32_t where = -1;
     bool placed = false, refused = false;
-    if (key) {
+    if constexpr (!INSERT) {
+        if (key) where = table_find(x.key, x.mask, key);
+    } else if (key) {
         uint64_t b = table_mix64(key) & x.mask;
-        refused = INSERT;
+        refused = true;
         for (uint64_t n = 0; n <= x.mask; n++, b = (b + 1) & x.mask) {
-            uint64_t cur = INSERT ? __hip_atomic_load(x.key + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : x.key[b];
+            uint64_t cur = __hip_atomic_load(x.key + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             if (!cur) {
-                if (!INSERT) break;                                // absent
                 if (__hip_atomic_compare_exchange_strong(x.key + b, &cur, key, __ATOMIC_RELAXED, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) {
                     placed = true;
                     cur = key;
@@ -49,7 +66,7 @@ __global__ void __launch_bounds__(NGW_TABLE_BLOCK) ngw_table_probe_kernel(const 
             }
             if (cur == key) { where = (int32_t)b; refused = false; break; }
         }
-        if (INSERT && where >= 0) __hip_atomic_fetch_min(x.stamp + where, x.base + (uint64_t)j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (where >= 0) __hip_atomic_fetch_min(x.stamp + where, x.base + (uint64_t)j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     if (inside) x.where[j] = where;
     if (INSERT) {
@@ -65,5 +82,6 @@ __global__ void __launch_bounds__(NGW_TABLE_BLOCK) ngw_table_fresh_kernel(const 
     const int32_t w = x.where[j];
     x.fresh[j] = ((uint64_t)(int64_t)w <= x.mask && x.stamp[w] == x.base + (uint64_t)j) ? 1 : 0;
 }
+#endif  // NGW_TABLE_UNIT
 
 }  // namespace

@@ -1,5 +1,6 @@
 // ngw_unit_table.hip — the key table (ngw_table.inc): a hash set of state keys.
 #include "ngw_common.inc"
+#define NGW_TABLE_UNIT                                            // the three kernels are this unit's; the walk (table_find) is everybody's
 #include "ngw_table.inc"
 
 // x->count keys offered to / looked up in the table of x->mask + 1 buckets; one lane per key

@@ -136,14 +136,16 @@ class ShardedVecNovelGridworld:
         return self.local.step_sampled(weights, seed, t=t)
 
     def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None,
-                 view_size=5):
+                 view_size=5, table=None, table_weights=None, outside='default'):
         """Valid-action random playouts from the current states of this rank's shard (VecNovelGridworld.playouts): [num_envs, P] fields;
         rank-local, no collective.  The local env numbers its pairs from env_index_base * P (= first * P), so the ranks together return what
         one unsharded env over all the envs returns - with path_keys=True the keys [steps, num_envs, P] included: a key describes a state, not
         where it is stored.  rewards / masks / observe: the trajectory fields of the shard's playouts (VecNovelGridworld.playouts), likewise -
-        observe='agent_view' with view_size included: the ranks' dicts concatenate over the env axis as the lidar rows do."""
+        observe='agent_view' with view_size included: the ranks' dicts concatenate over the env axis as the lidar rows do.  table / table_weights /
+        outside: a guided playout (VecNovelGridworld.playouts) on this rank's own table (key_table() is rank-local; buckets are not comparable
+        across ranks, keys are) - passed through, no collective."""
         from .playout import forward_keywords
-        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size)
+        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size, table, table_weights, outside)
         return self.local.playouts(n_playouts, steps, seed, device=device, weights=weights, **path)
 
     def snapshot(self, capacity=None):

@@ -335,18 +335,24 @@ class _NovelGridworldEnv(_EnvBase):
         return int(s.action[0]), float(s.mass[0]), int(s.mask_words[0])
 
     def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None,
-                 view_size=5):
+                 view_size=5, table=None, table_weights=None, outside='default'):
         """P = n_playouts valid-action random playouts of up to `steps` steps from the current state, without taking a step: a Playout of
         'ret' int32, 'length' int32, 'ended' bool, 'info' uint32 and 'first_action' int32, each [P]; playout q is pair q of the stream of
         `seed`; see VecNovelGridworld.playouts.  path_keys=True: a PlayoutPath, whose 'keys' [steps, P] hold the key under `fields` of the
         state each playout is in after every executed step (0 for the others).  rewards / masks / observe='lidar': a PlayoutTraj with
         'rewards' [steps, P], 'masks' [steps, P] and 'obs' [steps + 1, P, row] (VecNovelGridworld.playouts; the lidar must be configured on the
         batched backend).  observe='agent_view' (view_size=V): 'obs' is the AgentMap dict - 'agent_map' [steps + 1, P, W, W], 'agent_facing_id'
-        [steps + 1, P], 'inventory_items_quantity' [steps + 1, P, K] -, no lidar needed."""
+        [steps + 1, P], 'inventory_items_quantity' [steps + 1, P, K] -, no lidar needed.  table (a KeyTable of the batched backend:
+        env.unwrapped._backend().key_table(...)) / table_weights [table.buckets, A] / outside: a guided playout (Snapshot.playout) - a
+        PlayoutGuided with 'where' [steps, P] and 'depth' [P]."""
         vec = self._backend()
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
-        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size)
+        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size, table, table_weights, outside)
         return vec.playouts(n_playouts, steps, seed, device=device, weights=weights, **path).row(0)
+
+    def key_table(self, capacity):
+        """A device-side key table of this env's batched backend (VecNovelGridworld.key_table): what playouts(table=...) takes."""
+        return self._backend().key_table(capacity)
 
     def state_key(self, fields=KEY_STATE):
         """The 64-bit key of the current state as a Python int, computed on the device under the field selection `fields` (KEY_* bits,

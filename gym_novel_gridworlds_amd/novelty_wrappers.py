@@ -55,8 +55,8 @@ class NoveltyWrapper(object):
         return self.env.evaluate_plans(plans, device=device, copy=copy)
 
     def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None,
-                 view_size=5):
-        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size)
+                 view_size=5, table=None, table_weights=None, outside='default'):
+        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size, table, table_weights, outside)
         return self.env.playouts(n_playouts, steps, seed, device=device, weights=weights, **path)
 
     def sample_action(self, weights, seed, t=0):

@@ -72,21 +72,36 @@ class PlayoutPath(collections.namedtuple('PlayoutPath', 'ret length ended info f
         return PlayoutPath(*[x[i] for x in self[:5]], None if a is None else a[:, i], self.keys[:, i])
 
 
-def pairs_symbol(kind, weighted=False, path=False, traj=False, views=False):
+def pairs_symbol(kind, weighted=False, path=False, traj=False, views=False, guided=False):
     """The C entry point (include/ngw.h) behind one rollout / playout call: kind 'rollout' or 'playout'; traj - rewards, masks or observations are
     asked for; path - step limits or path keys are; weighted - a playout draws by weights; views - the observations are AgentMap views (a trajectory
     call by itself).  The form is the entry point's: views are `_traj_views`, any other traj is `_traj`, any other path `_path`, else the plain call
-    (a weighted playout: `_weighted`; a rollout draws nothing).  The one place that names the nine."""
+    (a weighted playout: `_weighted`; a rollout draws nothing).  guided - a playout looks its states up in a key table: `_playout_guided`, whatever
+    else is set (a rollout takes plans: ValueError).  The one place that names the ten."""
     if kind not in ('rollout', 'playout'):
         raise ValueError("kind: 'rollout' or 'playout' expected, got %r" % (kind,))
+    if guided:
+        if kind != 'playout':
+            raise ValueError("guided: a rollout takes plans, only a playout is guided by a key table")
+        return 'ngw_snapshot_playout_guided'
     form = '_traj_views' if views else ('_traj' if traj else ('_path' if path else ('_weighted' if weighted and kind == 'playout' else '')))
     return 'ngw_snapshot_%s%s' % (kind, form)
 
 
-def forward_keywords(path_keys=False, fields=None, rewards=False, masks=False, observe=None, view_size=5):
-    """The path and trajectory keywords a forwarding playouts() passes on: only those that are switched on (`fields` with path_keys; `view_size`
-    with observe='agent_view', or where it is not its default - the env then refuses it), so a call without them is the call it always was."""
+OUTSIDE = {'default': 0, 'stop': 1}          # include/ngw.h NGW_OUTSIDE_*
+
+
+def forward_keywords(path_keys=False, fields=None, rewards=False, masks=False, observe=None, view_size=5, table=None, table_weights=None, outside='default'):
+    """The path, trajectory and guidance keywords a forwarding playouts() passes on: only those that are switched on (`fields` with path_keys or a
+    table; `view_size` with observe='agent_view', or where it is not its default - the env then refuses it; `table_weights` and `outside` with a
+    table, or where they are not their defaults - likewise), so a call without them is the call it always was."""
     kw = dict(path_keys=True, fields=fields) if path_keys else {}
+    if table is not None:
+        kw.update(table=table, fields=fields)
+    if table_weights is not None:
+        kw['table_weights'] = table_weights
+    if table is not None or not (isinstance(outside, str) and outside == 'default'):
+        kw['outside'] = outside
     if rewards:
         kw['rewards'] = True
     if masks:
@@ -142,6 +157,91 @@ class PlayoutTraj(collections.namedtuple('PlayoutTraj', 'ret length ended info f
         def steps(x):
             return None if x is None else x[:, i]
         return PlayoutTraj(*[x[i] for x in self[:5]], steps(self.actions), steps(self.keys), steps(self.rewards), steps(self.masks), map_obs(self.obs, steps))
+
+
+class PlayoutGuided(collections.namedtuple('PlayoutGuided', 'ret length ended info first_action actions keys rewards masks obs where depth')):
+    """What playout() / playouts() return with table=: PlayoutTraj's fields (each per-step one None where it was not asked for) and
+      'where' int32 [T, count] ([T, N, P]; [T, P]): the bucket KeyTable.lookup returns for the state pair j was in BEFORE step t, for every executed
+              step; -1 where the table did not hold that state and -1 for a step the pair did not execute ('actions' tells the two apart);
+      'depth' int32 [count] ([N, P]; [P]): the number of leading executed steps with where >= 0 - how far the pair stayed inside the table.
+    tree_steps(result) lists the (bucket, action, t, j) of every executed in-table step: what a backup index_add_s into its [buckets, A] arrays."""
+    __slots__ = ()
+
+    def __getitem__(self, key):
+        return getattr(self, key) if isinstance(key, str) else tuple.__getitem__(self, key)
+
+    goal = Playout.goal
+    died = Playout.died
+
+    def shaped(self, *shape):
+        """The per-pair fields reshaped to `shape`, the per-step fields to [T, *shape], the rows to [T + 1, *shape, row]."""
+        t = PlayoutTraj(*self[:10]).shaped(*shape)
+        return PlayoutGuided(*t, self.where.reshape(self.where.shape[0], *shape), self.depth.reshape(*shape))
+
+    def row(self, i):
+        """Env i's rows of an [N, P] result (the single-env adapter's view)."""
+        return PlayoutGuided(*PlayoutTraj(*self[:10]).row(i), self.where[:, i], self.depth[i])
+
+
+def tree_steps(result):
+    """The executed in-table steps of a guided playout recorded with record=True: (bucket, action, t, j), four one-dimensional arrays of equal
+    length - every (t, j) with result.where[t, j] >= 0, in step-major order; j indexes the flattened pair axes.  numpy int64 from a host result, torch
+    int64 on the result's device otherwise (no host wait).  With them a backup over [buckets, A] tensors is one index_add_ each:
+    N.view(-1).index_add_(0, bucket * A + action, ones) and Q.view(-1).index_add_(0, bucket * A + action, result.ret.reshape(-1)[j].float())."""
+    where, actions = result.where, result.actions
+    if actions is None:
+        raise ValueError("tree_steps: the result holds no actions (playout(..., record=True) records them)")
+    steps = int(where.shape[0])
+    if hasattr(where, 'data_ptr'):
+        import torch
+        w, a = where.reshape(steps, -1), actions.reshape(steps, -1)
+        n = max(int(w.shape[1]), 1)
+        pos = torch.nonzero(w.reshape(-1) >= 0).reshape(-1)
+        return w.reshape(-1)[pos].long(), a.reshape(-1)[pos].long(), torch.div(pos, n, rounding_mode='floor'), pos % n
+    w, a = np.asarray(where).reshape(steps, -1), np.asarray(actions).reshape(steps, -1)
+    pos = np.flatnonzero(w.reshape(-1) >= 0)
+    t, j = divmod(pos, max(int(w.shape[1]), 1))
+    return w.reshape(-1)[pos].astype(np.int64), a.reshape(-1)[pos].astype(np.int64), t, j
+
+
+def check_guide(env, table, table_weights, outside, fields):
+    """The guidance keywords of a playout, checked before a handle is touched -> None without a table, else (the outside flag, the fields word).
+    table: a KeyTable of `env`, open; table_weights: required with it (its form is check_table_weights'); outside: 'default' or 'stop'; fields: a
+    non-empty selection - it names the state that is looked up."""
+    if not (isinstance(outside, str) and outside in OUTSIDE):
+        raise ValueError("outside: 'default' or 'stop' expected, got %r" % (outside,))
+    if table is None:
+        if table_weights is not None:
+            raise ValueError("table_weights without table: the rows belong to a key table's buckets")
+        if outside != 'default':
+            raise ValueError("outside=%r without table: there is no table to be outside of" % (outside,))
+        return None
+    from .key_table import KeyTable
+    from .state_keys import KEY_STATE, check_fields
+    if not isinstance(table, KeyTable):
+        raise ValueError("table: a KeyTable expected")
+    table._open_for(env)
+    if table_weights is None:
+        raise ValueError("table without table_weights: a float32 [table.buckets, A] array of weight rows expected")
+    if fields is not None and not isinstance(fields, bool) and isinstance(fields, (int, np.integer)) and int(fields) == 0:
+        raise ValueError("fields == 0: the look-up needs a non-empty selection of KEY_* bits")
+    return OUTSIDE[outside], check_fields(KEY_STATE if fields is None else fields)
+
+
+def check_table_weights(table_weights, buckets, n_actions, dev):
+    """table_weights of a guided playout -> (a contiguous float32 torch tensor [buckets, n_actions] on `dev`, whether it was uploaded here).  A torch
+    tensor must be exactly that and is used in place; anything else is a host array of that shape and is uploaded."""
+    import torch
+    shape = (int(buckets), int(n_actions))
+    if isinstance(table_weights, torch.Tensor):
+        if table_weights.dtype != torch.float32 or tuple(table_weights.shape) != shape or not table_weights.is_contiguous() or table_weights.device != dev:
+            raise ValueError("table_weights: a contiguous float32 tensor %s on %s expected, got %s %s on %s" % (
+                list(shape), dev, table_weights.dtype, list(table_weights.shape), table_weights.device))
+        return table_weights, False
+    w = np.asarray(table_weights)
+    if w.dtype.kind not in 'fiu' or w.shape != shape:
+        raise ValueError("table_weights: a float32 array %s expected, got %s %s" % (list(shape), w.dtype, list(w.shape)))
+    return torch.from_numpy(np.ascontiguousarray(w, np.float32)).to(dev), True
 
 
 def philox4x32_10(counter, key):

@@ -501,22 +501,24 @@ def path_call(env, holder, call, count, uploaded, device):
 
 
 def pairs_call(env, holder, kind, src, dst, parents, children, count, steps, device, plans=None, seed=0, first_pair=0, record=False, weights=None, limits=None,
-               path_keys=False, fields=None, rewards=False, masks=False, observe=None, view_size=5):
+               path_keys=False, fields=None, rewards=False, masks=False, observe=None, view_size=5, table=None, table_weights=None, guide=None):
     """The one launch behind Snapshot.rollout (kind 'rollout': `plans` the checked step-major [steps, count] actions), Snapshot.playout and
     VecNovelGridworld.playouts (kind 'playout': seed / first_pair / record, and weights: None - the uniform rule - or one float32 per action from the
     host or the device, sample.check_weights).  src / dst are snapshots' C handles (src None: the envs' current states; dst None: nothing is kept),
     parents / children the checked lists (check_rollout / check_playout); `holder` keeps the uploaded lists alive.  limits / path_keys / fields: the
     path form; rewards / masks / observe / view_size: the trajectory form - `observe` has been through check_observe at the caller (before it touched
-    a handle).  The entry point is playout.pairs_symbol's.  -> PlanEval / RolloutPath (with path_keys) / RolloutTraj, or Playout (actions [steps, count] with
+    a handle).  table / table_weights / guide: the guided form of a playout - `guide` is playout.check_guide's answer (made at the caller, before it touched a
+    handle), None without a table; the result is then a PlayoutGuided.  The entry point is playout.pairs_symbol's.  -> PlanEval / RolloutPath (with path_keys) / RolloutTraj, or Playout (actions [steps, count] with
     `record`) / PlayoutPath / PlayoutTraj, as the callers' docstrings define them."""
     import torch
-    from .playout import Playout, PlayoutPath, PlayoutTraj, pairs_symbol
+    from .playout import Playout, PlayoutGuided, PlayoutPath, PlayoutTraj, check_table_weights, pairs_symbol
     from .vec_env import PlanEval, RolloutPath, RolloutTraj
     draws = kind == 'playout'
-    traj = observe is not None or bool(rewards) or bool(masks)
+    guided = guide is not None
+    traj = guided or observe is not None or bool(rewards) or bool(masks)
     path = traj or limits is not None or bool(path_keys)
     views = isinstance(observe, str) and observe == 'agent_view'
-    name = pairs_symbol(kind, weights is not None, path, traj, views)
+    name = pairs_symbol(kind, weights is not None, path, traj, views, guided)
     seed, first_pair = int(seed), int(first_pair)
     if not 0 <= seed < 1 << 64:                 # (refused before anything is uploaded or allocated)
         raise ValueError("seed: %d outside [0, 2^64)" % seed)
@@ -527,7 +529,10 @@ def pairs_call(env, holder, kind, src, dst, parents, children, count, steps, dev
     ret, length, info = [torch.zeros(count, dtype=torch.int32, device=dev) for _ in range(3)]
     ended = torch.zeros(count, dtype=torch.uint8, device=dev)
     reports = [C.c_void_p(x.data_ptr()) for x in (ret, length, ended, info)]
-    first = actions = keys = rew = msk = rows = None
+    first = actions = keys = rew = msk = rows = where = depth = None
+    if guided:                                  # (the rows: checked and uploaded before anything is enqueued)
+        tw, mine = check_table_weights(table_weights, table.buckets, env.n_actions, dev)
+        uploaded = uploaded + ([tw] if mine else [])
     if draws:
         wt = []
         if weights is not None:
@@ -545,6 +550,8 @@ def pairs_call(env, holder, kind, src, dst, parents, children, count, steps, dev
         tail = [dst, ptr[1], int(count)] + reports
     if path:
         lim, f, keys = path_outputs(dev, limits, path_keys, fields, count, steps)
+        if guided:
+            f = guide[1]                        # (the look-up's selection, keys recorded or not)
         (lim_ptr,), up = upload(dev, count, lim)
         uploaded, head, tail = uploaded + up, head + [lim_ptr], tail + [f, _ptr(keys, count), int(count)]
     if traj:
@@ -554,7 +561,11 @@ def pairs_call(env, holder, kind, src, dst, parents, children, count, steps, dev
             vw = _cabi.TrajViews(int(view_size), *[x.data_ptr() for x in (rows['agent_map'], rows['agent_facing_id'], rows['inventory_items_quantity'])], int(pad))
             tail += [None, 0, C.byref(vw) if count else None]
         else:
-            tail += [_ptr(rows, count), int(pad)]
+            tail += [_ptr(rows, count), int(pad)] + ([None] if guided else [])
+    if guided:
+        where = torch.full((steps, count), -1, dtype=torch.int32, device=dev)
+        depth = torch.zeros(count, dtype=torch.int32, device=dev)
+        tail += [table._open(), C.c_void_p(tw.data_ptr()), _ptr(where, count), int(count), _ptr(depth, count), guide[0]]
     (path_call if path else enqueue_ordered)(env, holder, lambda: getattr(_cabi.lib(), name)(*head, *tail), count, uploaded, device)
     if count == 0 and rows is not None:
         for x in (rows.values() if views else [rows]):
@@ -566,6 +577,8 @@ def pairs_call(env, holder, kind, src, dst, parents, children, count, steps, dev
         keys = host(keys, np.uint64)
     if traj:
         rew, msk, rows = traj_results(env, rew, msk, rows, count, device)
+        if guided:
+            return PlayoutGuided(*res, keys, rew, msk, rows, where if device else host(where), depth if device else host(depth))
         return PlayoutTraj(*res, keys, rew, msk, rows) if draws else RolloutTraj(*res, keys, rew, rows)
     plain, keyed = (Playout, PlayoutPath) if draws else (PlanEval, RolloutPath)
     return plain(*res) if keys is None else keyed(*res, keys)
@@ -790,7 +803,8 @@ class Snapshot:
                           fields=fields, rewards=rewards, observe=observe, view_size=view_size)
 
     def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False, weights=None,
-                limits=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None, view_size=5):
+                limits=None, path_keys=False, fields=KEY_STATE, rewards=False, masks=False, observe=None, view_size=5, table=None, table_weights=None,
+                outside='default'):
         """Pair j: the state of parent parents[j] stepped on a private copy up to `steps` times by rollout()'s rules, with a random policy in
         the place of a plan: at every step the action is drawn uniformly among the actions that would succeed from the state the pair is in
         (every action where none would) - the default-policy simulation of a tree search's leaf, in one kernel launch.  The draw is the
@@ -815,16 +829,33 @@ class Snapshot:
         of step t was made under, after the "no action would succeed -> every action" replacement, 0 for a step not executed - so
         playout.choose_actions(masks[t], seed, first_pair + arange(count), t, A) is actions[t], and sample.choose_weighted does the same for a
         weighted playout: what a learner stores to recompute masked log-probabilities.  The memory, the refusals and the zero rows are
-        rollout()'s, and so is observe='agent_view' with view_size."""
+        rollout()'s, and so is observe='agent_view' with view_size.
+        table=KeyTable, table_weights=[table.buckets, A]: a GUIDED playout - a policy that depends on the state, applied inside the launch.  At
+        every step the pair's current state (its key under `fields`: what keys() returns for it; the parent's at step 0, keys[t - 1] later) is
+        looked up in `table`; where the table holds it (bucket b = table.lookup(key)) the step's weights are row b of table_weights, otherwise
+        they are `weights` (the uniform rule without them) - or, with outside='stop', the pair stops there as if limits[j] were t: not 'ended',
+        a kept child receives the state it is in (the leaf of a tree descent).  The choice is the weighted rule on the playout's own mask and
+        Philox word; a zero-mass row falls back to the uniform rule, and a bad weight raises F_BAD_WEIGHT only from a row a pair actually read.
+        table_weights: a contiguous float32 torch tensor [table.buckets, A] on the env's device, used in place (complete on torch's current
+        stream before the call, unchanged until the env's stream has passed it), or a host array of that shape, uploaded (buckets * A * 4 bytes
+        per call).  Returns a PlayoutGuided: the PlayoutTraj fields (the per-step ones None unless asked for), 'where' int32 [steps, count] -
+        the bucket of every executed step, -1 for a miss and for a step not executed - and 'depth' int32 [count], the leading in-table steps.
+        playout.tree_steps(result) lists (bucket, action, t, j) of the in-table steps for the backup, and with path_keys=True the new leaves'
+        keys go straight to table.insert.  With an empty table the call is bit-identical to the call without one; with every row equal to
+        `weights`, to the weighted playout.  The table is only read; an insert concurrent with the call is not supported.  One kernel launch.
+        Refused before a handle is touched: a table of another env, a closed table, table_weights without table (and the reverse), a wrong shape,
+        dtype or device, an unknown `outside`, fields == 0.  The running key needs the inventory shadows: the map limit is the keyed call's."""
         import torch
+        from .playout import check_guide
         env = self.env
         check_observe(env, observe, view_size)
+        guide = check_guide(env, table, table_weights, outside, fields)
         src, n_parents, same_buffer = self._source(source, from_envs, 'playout')
         dev = torch.device('cuda:%d' % env.device)
         p, c, count, steps = check_playout(parents, steps, children, n_parents, self.capacity, same_buffer, lambda x: tensor_len(dev, 'playout', x))
         return pairs_call(env, self, 'playout', src, None if c is None else self._s, p, c, count, steps, device, seed=seed, first_pair=first_pair, record=record,
                           weights=weights, limits=limits, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe,
-                          view_size=view_size)
+                          view_size=view_size, table=table, table_weights=table_weights, guide=guide)
 
     # ------------------------------------------------------------------ slot observations (include/ngw.h ngw_snapshot_lidar / _agent_view / _action_mask)
     def _slots_arg(self, slots):

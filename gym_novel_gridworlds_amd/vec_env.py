@@ -1073,7 +1073,7 @@ class VecNovelGridworld:
         return s
 
     def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None,
-                 view_size=5):
+                 view_size=5, table=None, table_weights=None, outside='default'):
         """P = n_playouts valid-action random playouts of up to `steps` steps from every env's CURRENT state, without taking a step and
         without a snapshot of the caller's: Snapshot.playout(from_envs=True) with the parents repeat(arange(N), P).  Returns a Playout whose
         fields are [N, P] ('actions' is None: Snapshot.playout records them).  Playout q of env i is pair (env_index_base + i) * P + q of the
@@ -1085,8 +1085,10 @@ class VecNovelGridworld:
         rewards=True / masks=True / observe='lidar': a PlayoutTraj with 'rewards' [T, N, P], 'masks' [T, N, P] and 'obs' [T + 1, N, P, row] - every
         step's reward, the mask word its choice was made under and the LidarInFront rows before and after it (Snapshot.playout; obs takes
         (T + 1) * N * P rows of device memory).  observe='agent_view' (view_size=V, default 5): 'obs' is the AgentMap dict of Snapshot.playout,
-        'agent_map' [T + 1, N, P, W, W], 'agent_facing_id' [T + 1, N, P], 'inventory_items_quantity' [T + 1, N, P, K]; no lidar needed."""
+        'agent_map' [T + 1, N, P, W, W], 'agent_facing_id' [T + 1, N, P], 'inventory_items_quantity' [T + 1, N, P, K]; no lidar needed.
+        table / table_weights / outside: a guided playout (Snapshot.playout) - a PlayoutGuided with 'where' [T, N, P] and 'depth' [N, P]."""
         import torch
+        from .playout import check_guide
         from .snapshot import check_observe, check_playout, pairs_call
         P = int(n_playouts)
         if P < 1:
@@ -1096,9 +1098,10 @@ class VecNovelGridworld:
         parents = torch.arange(N, dtype=torch.int32, device=dev).repeat_interleave(P).contiguous()
         _, _, count, steps = check_playout(parents, steps, None, N, 0, False, lambda x: None if x is None else int(x.numel()))
         check_observe(self, observe, view_size)
+        guide = check_guide(self, table, table_weights, outside, fields)
         return pairs_call(self, self._keeper(), 'playout', None, None, parents, None, count, steps, device, seed=seed, first_pair=self.env_index_base * P,
                           weights=weights, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe,
-                          view_size=view_size).shaped(N, P)
+                          view_size=view_size, table=table, table_weights=table_weights, guide=guide).shaped(N, P)
 
     def fork(self, src, keep_episode=False):
         """Every env e becomes a copy of env src[e] (src: num_envs indices - a list / numpy array, checked, or a torch int32 tensor on the

@@ -176,7 +176,7 @@ class LimitActions(NoveltyWrapper):
         return ids[int(s.action[0])], float(s.mass[0]), word
 
     def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None,
-                 view_size=5):
+                 view_size=5, table=None, table_weights=None, outside='default'):
         """The env's playouts under this wrapper's action list: at every step the action is drawn among the LIMITED actions that would
         succeed (every limited action where none would), and 'first_action' holds limited ids.  The draw needs the limited list as the
         kernel's own action table, so the playouts run on a one-env batched env whose table is the limited one (limit_actions_vec, kept
@@ -184,9 +184,15 @@ class LimitActions(NoveltyWrapper):
         state.  weights: one per limited id.  path_keys / fields: as on the env - the keys do not depend on the action id space.
         rewards / masks / observe: as on the env; bit i of a mask word is limited id i, consistent with the actions reported here.  observe needs
         the lidar configured on the adapter's batched backend (the limited env takes its configuration over).  observe='agent_view' / view_size:
-        the AgentMap dict, which does not depend on the action id space and needs no lidar."""
+        the AgentMap dict, which does not depend on the action id space and needs no lidar.
+        table / table_weights / outside: a guided playout.  The table is one of the LIMITED env (lim.key_table(capacity): keys do not depend on
+        the action id space, tables belong to an env).  The columns of table_weights [table.buckets, n_limited] are in this wrapper's id space;
+        where the kernel's order differs they are scattered to the env's columns on the device once per call - one gather over buckets * n_limited
+        floats and a second tensor of that size, whatever the number of playouts - so keep the ids in sorted-name order (the default) in a loop."""
         limited, ids = self._limited_env()
-        if weights is not None and not hasattr(weights, 'device'):
+        if table_weights is not None and ids != list(range(len(ids))):
+            table_weights = limit_weight_columns(table_weights, ids, limited)
+        if weights is not None and not hasattr(weights, 'data_ptr'):        # (a host array; numpy 2 arrays have a `device` too)
             w = np.asarray(weights)
             if w.shape != (len(ids),):
                 raise ValueError("weights: one weight per limited action expected, shape [%d], got %s" % (len(ids), list(w.shape)))
@@ -194,7 +200,7 @@ class LimitActions(NoveltyWrapper):
         elif weights is not None and ids != list(range(len(ids))):
             import torch
             weights = weights[torch.tensor(ids, device=weights.device)].contiguous()
-        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size)
+        path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size, table, table_weights, outside)
         if observe is not None and not (isinstance(observe, str) and observe == 'agent_view'):   # (the views need no lidar) the rows are the backend's: its lidar as it is configured NOW, not as it was when the limited env was made
             vec = self.unwrapped._backend()
             mine, theirs = [(e.lidar, e.lidar_packed, e.lidar_dtype) for e in (limited, vec)]
@@ -212,6 +218,11 @@ class LimitActions(NoveltyWrapper):
             lut = torch.tensor(ids, dtype=play.first_action.dtype, device=play.first_action.device)
             return play._replace(first_action=lut[play.first_action.long()])
         return play._replace(first_action=np.asarray(ids, np.int32)[play.first_action])
+
+    def key_table(self, capacity):
+        """A key table for guided playouts() under this wrapper: VecNovelGridworld.key_table on the limited env the playouts run on.  It lives as
+        long as that env does (until close(), or until the adapter's backend is rebuilt)."""
+        return self._limited_env()[0].key_table(capacity)
 
     def close(self):
         kept = self.__dict__.pop('_playout_env', None)
@@ -260,6 +271,23 @@ def limit_mask_columns(inner, limited_actions_id, actions_id, n, dtype=bool):
         if j is not None:
             out[..., i] = inner[..., j]
     return out
+
+
+def limit_weight_columns(table_weights, ids, limited=None):
+    """Weight rows [buckets, n] whose column ids[i] belongs to a wrapper's limited id ids[i] -> the rows in the kernel's order (column i <- column
+    ids[i]).  A torch tensor is gathered where it lies; a host array goes to `limited`'s device first (one upload) and is gathered there - without
+    `limited`, on the host."""
+    if hasattr(table_weights, 'data_ptr'):
+        import torch
+        return table_weights[:, torch.tensor(ids, device=table_weights.device)].contiguous()
+    w = np.asarray(table_weights)
+    if w.ndim != 2 or w.shape[1] != len(ids):
+        raise ValueError("table_weights: one column per limited action expected, shape [buckets, %d], got %s" % (len(ids), list(w.shape)))
+    if limited is None or not hasattr(limited, 'device') or not hasattr(limited, '_h'):
+        return np.ascontiguousarray(w[:, ids])
+    import torch
+    dev = torch.device('cuda:%d' % limited.device)
+    return torch.from_numpy(np.ascontiguousarray(w, np.float32)).to(dev)[:, torch.tensor(ids, device=dev)].contiguous()
 
 
 def limit_mask_words(words, ids):

@@ -893,6 +893,46 @@ int ngw_key_table_insert(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_d
 int ngw_key_table_lookup(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_dev, int64_t count, int32_t* where_dev);
 int ngw_key_table_count(ngw_handle* h, ngw_key_table* t, int64_t* n);
 
+/* Guided playouts: ngw_snapshot_playout_traj_views whose weights depend on the STATE - at every step the pair's current state is looked up in a key
+ * table, and where the table holds it the choice is made under that bucket's row of the caller's weights.  The selection phase of MCTS (descend by
+ * the tree's statistics while the node is in the tree), tabular Q / softmax policies, Go-Explore's "return, then explore" and playouts whose bias is
+ * learned per state, in one launch in the place of a host loop of keys -> lookup -> gather -> sample -> one-step rollout.
+ * The rule.  For a pair that is alive at step t (not skipped, t below its limit, no earlier step ended its episode):
+ *   1. k = the key under `fields` of the state the pair is in before step t: what ngw_state_keys returns for that row - for t = 0 the parent's key, for
+ *      t > 0 the entry of step t - 1 of the path keys.  One `fields` governs the recorded keys and the look-up; it must be a non-empty selection even
+ *      where keys_dev is NULL.
+ *   2. b = what ngw_key_table_lookup(table, k) returns: the bucket, or -1 (key 0 gives -1).
+ *   3. outside == NGW_OUTSIDE_STOP and b < 0: the pair executes neither this step nor any later one, exactly as if limits[j] were t - it is not
+ *      `ended`, its recorded actions from t on are -1, its key / reward / mask entries 0, and a kept child receives the state it is in.
+ *   4. Otherwise the step's weights are row b of table_weights_dev (float32 [buckets][n_actions], row-major, buckets as ngw_key_table_create
+ *      defines them) where b >= 0, else weights_dev ([n_actions]), else - weights_dev == NULL - the uniform rule of ngw_snapshot_playout.
+ *   5. The choice is rules 3 - 6 of ngw_sample_actions on the playout's own mask word m and Philox word w (the stream, tag and counter of
+ *      ngw_snapshot_playout): mass 0 falls back to the uniform rule on the same w.  A bad weight (negative, NaN, above 2^64) counts as 0 and raises
+ *      NGW_F_BAD_WEIGHT if it lies in a row that a pair read for a step it executed; a bad weight in a row no executed step read raises nothing.
+ * So with an empty table and NGW_OUTSIDE_DEFAULT the call computes, bit for bit, what the same call without a table computes, and with every row
+ * equal to weights_dev what the weighted playout computes.  The draw depends on (seed, first_pair + j, t), the state, the table's contents and the
+ * weights alone: a call split with first_pair gives the rows of the whole one.
+ * Outputs beyond the trajectory playout's (device memory, each may be NULL):
+ *   where_dev  int32 [n_steps][where_stride], where_stride >= count: b of every executed step; -1 where the state was not in the table and -1 for a
+ *              step the pair did not execute (the recorded actions tell the two apart).  Exactly [t * where_stride, + count) of every row is written.
+ *   depth_dev  int32 [count]: the number of leading executed steps with where >= 0 - how far the pair stayed inside the table.  0 for a skipped pair.
+ * The table is only read: its contents, its count and every bucket stay what they were, and nothing is committed.  The call is enqueued on the
+ * handle's stream behind the table's earlier calls; an insert into the table concurrent with it is not supported.  One kernel launch
+ * (ngw_playout.inc, GUIDED: the running key of the path form is what is looked up; the rows are read in place, 2 * n_actions floats per pair and step).
+ * Map sizes: the running key needs the inventory shadows whether or not keys_dev is set, so the limit is that of the trajectory call WITH keys under
+ * the same observation kind.
+ * NGW_E_INVALID_ARG: what ngw_snapshot_playout_traj_views refuses; a NULL table or table_weights_dev; a table that is not an open table of this
+ * handle; fields == 0 or a bit outside NGW_KEY_ALL; where_stride < count with where_dev; an `outside` that is neither value. */
+#define NGW_OUTSIDE_DEFAULT 0   /* a state the table does not hold draws by weights_dev (NULL: uniformly) */
+#define NGW_OUTSIDE_STOP 1      /* a state the table does not hold ends the pair there: the leaf of a tree descent */
+int ngw_snapshot_playout_guided(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, int64_t count, int32_t n_steps, uint64_t seed, uint64_t first_pair,
+                                const float* weights_dev /* NULL: the uniform rule */, const int32_t* limits_dev, ngw_snapshot* dst,
+                                const int32_t* dst_slots_dev, int32_t* ret_dev, int32_t* length_dev, uint8_t* ended_dev, uint32_t* info_dev,
+                                int32_t* first_action_dev, int32_t* actions_dev, int64_t actions_stride, uint32_t fields, uint64_t* keys_dev,
+                                int64_t keys_stride, int32_t* rewards_dev, int64_t rewards_stride, uint64_t* masks_dev, int64_t masks_stride, void* obs_dev,
+                                int64_t obs_stride, const ngw_traj_views* views /* NULL: no views */, ngw_key_table* table, const float* table_weights_dev,
+                                int32_t* where_dev, int64_t where_stride, int32_t* depth_dev, int32_t outside);
+
 /* One-step lookahead tables: every action's outcome for every env, without taking a step.
  * For a handle with A = n_actions the table of the CURRENT state is three arrays - reward int32, done uint8, info uint32 (the NGW_INFO_* packing).
  * Entry (i, a) holds exactly what ngw_get_step_out would report for env i if ngw_step_device were called now with action a for that env, under
