@@ -53,6 +53,20 @@ __device__ __forceinline__ void expand_move_row(int8_t* gmap, int32_t* ginv, uin
     for (int p = g; p < K; p += NGW_SNAP_GROUP) { if (TO_LDS) linv[p] = ginv[p]; else ginv[p] = linv[p]; }
 }
 
+// The gathered stage-in of step 2, for every kernel that brings 64 saved rows into LDS (here, ngw_successors.inc, ngw_slot_observe.inc): row l - map at
+// lmap + l * MSdw, inventory at linv + l * KP - is the one lane l names in `sic`, an index its owner has checked and clamped.
+template <int VEC>
+__device__ __forceinline__ void expand_rows_in(const NgwSnapRows& rows, int sic, uint32_t* lmap, int32_t* linv, int MSdw, int KP, int S2, int K, uint32_t tid) {
+    const int g = (int)(tid % NGW_SNAP_GROUP), q = (int)(tid / NGW_SNAP_GROUP);
+    constexpr int ROWS = EPB / NGW_SNAP_GROUP;                                     // rows per round
+#pragma unroll 4
+    for (int it = 0; it < EPB / ROWS; it++) {
+        const int j = it * ROWS + q;
+        const int sj = __builtin_amdgcn_ds_bpermute(j << 2, sic);
+        expand_move_row<VEC, true>(rows.map + (size_t)sj * (size_t)S2, rows.inv + (size_t)sj * (size_t)K, lmap + j * MSdw, linv + j * KP, S2, K, g);
+    }
+}
+
 template <int VEC, bool EXT>
 __global__ void __launch_bounds__(NGW_EPB) ngw_expand_kernel(const NgwDevSpec* __restrict__ dspec, const NgwLaunch a, const NgwExpand x) {
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
@@ -87,12 +101,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_expand_kernel(const NgwDevSpec* _
     const int g = (int)(tid % NGW_SNAP_GROUP), q = (int)(tid / NGW_SNAP_GROUP);
     const int MSdw = a.MS >> 2, KP = a.KP;
     constexpr int ROWS = EPB / NGW_SNAP_GROUP;                                     // rows per round
-#pragma unroll 4
-    for (int it = 0; it < EPB / ROWS; it++) {
-        const int j = it * ROWS + q;
-        const int sj = __builtin_amdgcn_ds_bpermute(j << 2, sic);
-        expand_move_row<VEC, true>(x.src.map + (size_t)sj * (size_t)S2, x.src.inv + (size_t)sj * (size_t)K, lds_map + j * MSdw, lds_inv + j * KP, S2, K, g);
-    }
+    expand_rows_in<VEC>(x.src, sic, lds_map, lds_inv, MSdw, KP, S2, K, tid);
     __syncthreads();
     // ---- 3. one step of this lane's row
     int8_t* const mp = reinterpret_cast<int8_t*>(lds_map) + tid * a.MS;

@@ -3,7 +3,7 @@
 #include "ngw_common.inc"
 #include "ngw_lidar_march.inc"     // lidar_epilogue: the row builder
 #include "ngw_lean.inc"            // lane_mask, lean_gather_lane
-#include "ngw_expand.inc"          // expand_move_row: the row mover
+#include "ngw_expand.inc"          // expand_rows_in: the gathered stage-in
 
 namespace {
 //
@@ -40,18 +40,10 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_lidar_kernel(const NgwLaunch
     uint32_t* const lds_map = lds + a.off_map;
     int32_t* const lds_inv = reinterpret_cast<int32_t*>(lds + a.off_inv);
     if (tid < LIDAR_ITEM_DW) lds[a.off_litem + tid] = it;
-    const int g = (int)(tid % NGW_SNAP_GROUP), q = (int)(tid / NGW_SNAP_GROUP);
-    const int MSdw = a.MS >> 2, KP = a.KP;
-    constexpr int ROWS = EPB / NGW_SNAP_GROUP;                                     // rows per round
-#pragma unroll 4
-    for (int it_ = 0; it_ < EPB / ROWS; it_++) {
-        const int j = it_ * ROWS + q;
-        const int sj = __builtin_amdgcn_ds_bpermute(j << 2, sic);
-        expand_move_row<VEC, true>(x.src.map + (size_t)sj * (size_t)S2, x.src.inv + (size_t)sj * (size_t)K, lds_map + j * MSdw, lds_inv + j * KP, S2, K, g);
-    }
+    expand_rows_in<VEC>(x.src, sic, lds_map, lds_inv, a.MS >> 2, a.KP, S2, K, tid);
     if (inside && !ok) atomicOr(x.flags, NGW_F_BAD_INDEX);
     const int8_t* mp = reinterpret_cast<const int8_t*>(lds_map) + tid * a.MS;
-    lidar_epilogue(a, lds, tid, ok, mp + rc.x * S + rc.y, f, lds_inv + tid * KP);   // (its first barrier makes the staging visible)
+    lidar_epilogue(a, lds, tid, ok, mp + rc.x * S + rc.y, f, lds_inv + tid * a.KP);   // (its first barrier makes the staging visible)
 }
 
 // ---------------------------------------------------------------- action masks

@@ -2,7 +2,7 @@
 #pragma once
 #include "ngw_common.inc"
 #include "ngw_lean.inc"            // lean_body and its table fetches
-#include "ngw_expand.inc"          // expand_move_row: the row mover
+#include "ngw_expand.inc"          // expand_rows_in: the gathered stage-in
 #include "ngw_keys.inc"            // the terms of a key
 
 namespace {
@@ -87,15 +87,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_successors_kernel(const NgwDevSpe
     uint32_t* const work_inv = lds + EPB * MSdw;
     uint32_t* const pris_map = lds + region;
     uint32_t* const pris_inv = pris_map + EPB * MSdw;
-    const int g = (int)(tid % NGW_SNAP_GROUP), q = (int)(tid / NGW_SNAP_GROUP);
-    constexpr int ROWS = EPB / NGW_SNAP_GROUP;                                     // rows per round
-#pragma unroll 4
-    for (int it = 0; it < EPB / ROWS; it++) {
-        const int j = it * ROWS + q;
-        const int sj = __builtin_amdgcn_ds_bpermute(j << 2, sic);
-        expand_move_row<VEC, true>(x.src.map + (size_t)sj * (size_t)S2, x.src.inv + (size_t)sj * (size_t)K, pris_map + j * MSdw,
-                                   reinterpret_cast<int32_t*>(pris_inv) + j * KP, S2, K, g);
-    }
+    expand_rows_in<VEC>(x.src, sic, pris_map, reinterpret_cast<int32_t*>(pris_inv), MSdw, KP, S2, K, tid);
     __syncthreads();
     // ---- 3. this lane's row: pristine -> work, the parent's map and inventory terms
     uint32_t* const wm = work_map + tid * MSdw;
