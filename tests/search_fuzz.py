@@ -6,7 +6,16 @@ env under test and on the model, and compares after EVERY call: the seven state 
 fused lidar rows, the action-mask words, the terminal-observation rows and the error flags.  The model is the CPU oracle for the live envs,
 snapshot_oracle.NumpySnapshot for the slots, key_table_oracle.KeyTableModel for the tables and the row-level reference functions of
 tests/*_oracle.py for everything a call returns; nothing in it calls the HIP library or the package's own host restatements of the contracts
-(path keys are hashed here from the rows path_key_oracle hands back, by state_key_oracle's rule).
+(path keys are hashed here from the rows path_key_oracle hands back, by state_key_oracle's rule).  The one exception is the guided playout, whose
+reference - guided_playout_oracle.oracle_guided - is built on the public numpy contracts of the Philox word, the weighted choice and the key.
+
+The two newest features are forms and kinds of their own.  'view': a trajectory call with observe='agent_view' and a drawn view_size, on rollout,
+playout and playouts, held to trajectory_view_oracle.expect_views.  'splayout_guided' / 'splayout_guided_kids' and the 'guided' form of playouts: a
+guided playout over the case's ONE key table - whatever insert_state_keys, insert_succ_keys, slot_insert_keys and table_insert put there, under
+whatever fields, plus (three times in four) an offer of keys under the call's own fields - with limits, outside='stop', first_pair up to 2^40, every
+source, children, every fields choice, both observations.  table_weights holds f(key) in the bucket the table REPORTED for each key the model holds
+and NaN in every other row, so a lane that reads a bucket no member owns changes the actions or raises F_BAD_WEIGHT, which check_all holds to 0.
+FIELD_CHOICES includes KEY_INV alone: with an empty inventory that key is 0, the one key a table never stores and a guided step never looks up.
 
 Every draw depends on the RandomState, the settings and the model alone - never on a value the env under test returned - and every draw of a call is
 made before the model decides whether the call is refused, so the walk of a seed is the same walk on every backend.  The one state-dependent exit is
@@ -19,6 +28,7 @@ import os
 import numpy as np
 
 import expand_oracle as XO
+import guided_playout_oracle as GO
 import key_table_oracle as KT
 import lookahead_oracle as LO
 import mask_oracle as M
@@ -33,13 +43,17 @@ import snapshot_oracle as SO
 import state_key_oracle as SK
 import successor_key_oracle as SU
 import trajectory_oracle as TO
+import trajectory_view_oracle as VO
 from oracle import ngw_oracle as NO
 
 STATE_KEYS = SO.STATE_KEYS
 SUCC_MAX_MAP = 34                    # Snapshot.successor_keys: "Maps up to 34 x 34 ... beyond that the call raises" (MapsTooLarge)
 MAX_PAIRS, MAX_STEPS, MAX_PLANS = 130, 8, 3
-TABLE_CAPACITY = 2048                # 4096 buckets: a case offers at most ~2000 distinct keys, so probes collide and the table never fills
-FIELD_CHOICES = (SK.STATE, SK.ALL, SK.MAP | SK.POSE, SK.INV | SK.SELECTED, SK.STEP_COUNT | SK.EPISODE | SK.POSE, SK.MAP)
+TABLE_CAPACITY = 4096                # 8192 buckets.  A condition, asserted after every insert: the model never holds more keys (a full table is not what
+                                     # this fuzz models; a guided call's offer - up to 650 keys - is skipped on both sides where it would pass it).  The
+                                     # committed walk's largest table holds 496 keys: sparse enough to stay cheap, dense enough for probe chains
+VIEW_SIZES = (1, 2, 5, 6)
+FIELD_CHOICES = (SK.STATE, SK.ALL, SK.MAP | SK.POSE, SK.INV | SK.SELECTED, SK.STEP_COUNT | SK.EPISODE | SK.POSE, SK.MAP, SK.INV)
 
 # call kinds and how often each is drawn (tests/test_search_fuzz_cpu.py holds the coverage these give for the committed seed)
 KINDS = {
@@ -47,17 +61,21 @@ KINDS = {
     'step': 3, 'dev': 2, 'rollout': 2, 'rollact': 2, 'reset': 2, 'mask_reset': 2, 'state_steps': 2, 'state_rows': 2, 'step_sampled': 2,
     'restore': 4, 'fork': 2, 'graph_launch': 2,
     # writers of slots only
-    'save': 2, 'copy': 2, 'expand': 4, 'expand_all': 2, 'srollout_kids': 4, 'splayout_kids': 4,
-    # read-only
+    'save': 2, 'copy': 2, 'expand': 4, 'expand_all': 2, 'srollout_kids': 6, 'splayout_kids': 7, 'splayout_guided_kids': 4,
+    # read-only (a guided playout offers keys to the table first: the env and the slots stay as they are)
+    'splayout_guided': 4,
     'mask_words': 2, 'lookahead': 2, 'plans': 2, 'state_keys': 2, 'succ_keys': 2, 'insert_state_keys': 2, 'insert_succ_keys': 2, 'table_insert': 2,
-    'table_lookup': 2, 'sample': 2, 'playouts': 4, 'srollout': 4, 'splayout': 4, 'slot_lidar': 2, 'slot_view': 2, 'slot_masks': 2, 'slot_keys': 2,
+    'table_lookup': 2, 'sample': 2, 'playouts': 6, 'srollout': 6, 'splayout': 6, 'slot_lidar': 2, 'slot_view': 2, 'slot_masks': 2, 'slot_keys': 2,
     'slot_unique': 2, 'slot_insert_keys': 2, 'agent_view': 2, 'lidar': 2,
 }
 READ_ONLY = ('mask_words', 'lookahead', 'plans', 'state_keys', 'succ_keys', 'insert_state_keys', 'insert_succ_keys', 'table_insert', 'table_lookup', 'sample',
-             'playouts', 'srollout', 'splayout', 'slot_lidar', 'slot_view', 'slot_masks', 'slot_keys', 'slot_unique', 'slot_insert_keys', 'agent_view', 'lidar')
-ROLLOUT_FORMS = ('plain', 'path', 'traj')
-PLAYOUT_FORMS = ('plain', 'weighted', 'path', 'traj')
-PLAYOUTS_FORMS = ('plain', 'weights', 'path_keys', 'rewards', 'masks', 'observe')
+             'playouts', 'srollout', 'splayout', 'splayout_guided', 'slot_lidar', 'slot_view', 'slot_masks', 'slot_keys', 'slot_unique', 'slot_insert_keys',
+             'agent_view', 'lidar')
+ROLLOUT_FORMS = ('plain', 'path', 'traj', 'view')
+PLAYOUT_FORMS = ('plain', 'weighted', 'path', 'traj', 'view')
+PLAYOUTS_FORMS = ('plain', 'weights', 'path_keys', 'rewards', 'masks', 'observe', 'view', 'guided')
+GUIDED_KINDS = ('splayout_guided', 'splayout_guided_kids')
+OFFER_KEEP = (0.25, 0.6, 1.0)        # the share of the offered keys a guided call keeps (drawn per call): thin tables give the misses and re-entries
 
 
 class Refused(Exception):
@@ -126,10 +144,11 @@ def rows_at(src, idx):
 
 
 def ref_pairs(spec, rows, parents, kind, autoreset, horizon, plans=None, steps=None, seed=0, first_pair=0, weights=None, limits=None, path_keys=False,
-              fields=SK.STATE, rewards=False, masks=False, lc=None):
+              fields=SK.STATE, rewards=False, masks=False, lc=None, view_size=None):
     """What one rollout / playout call must return and leave, from the row-level references: -> dict(ends, rep, actions [T, count], keys, rewards,
     masks, obs); the last four None where the call does not ask for them.  plans [count, T] for kind 'rollout'; weights [A] or None, steps and
-    seed for kind 'playout'; lc: the LidarConfig with observe='lidar'."""
+    seed for kind 'playout'; lc: the LidarConfig with observe='lidar'; view_size: the window of observe='agent_view' (obs is then
+    trajectory_view_oracle.expect_views' dict)."""
     parents = np.asarray(parents, np.int64)
     if kind == 'playout':
         if weights is None:
@@ -140,7 +159,7 @@ def ref_pairs(spec, rows, parents, kind, autoreset, horizon, plans=None, steps=N
         plans = np.asarray(plans)
         actions, steps = np.ascontiguousarray(plans.T), plans.shape[1]
     out = dict(keys=None, rewards=None, masks=None, obs=None)
-    traj = rewards or masks or lc is not None
+    traj = rewards or masks or lc is not None or view_size is not None
     if not (traj or limits is not None or path_keys):
         if kind == 'rollout':
             ends, rep, _ = RO.oracle_slot_rollout(spec, rows, parents, plans, autoreset, horizon)
@@ -149,6 +168,8 @@ def ref_pairs(spec, rows, parents, kind, autoreset, horizon, plans=None, steps=N
             e = TO.oracle_traj(spec, rows, parents, actions, limits, autoreset, horizon, fields, lc)
             ends, rp, states = e['ends'], e['reports'], e['states']
             out.update(rewards=e['rewards'] if rewards else None, masks=e['masks'] if masks else None, obs=e['obs'])
+            if view_size is not None:
+                out['obs'] = VO.expect_views(spec, rows, parents, e, view_size)
         else:
             _, rp, ends, states, _ = KO.oracle_path(spec, rows, parents, actions, limits, autoreset, horizon, fields)
         if kind == 'playout':                            # a limited playout is the prefix of the unlimited one: the actions beyond it are -1
@@ -179,6 +200,11 @@ def check_pairs(got, exp, kind, record, where):
         g = getattr(got, k, None)
         eq(k, None if g is None else host(g).reshape(steps, -1), exp[k], where)
     g = getattr(got, 'obs', None)
+    if isinstance(exp['obs'], dict):                      # (observe='agent_view': the pair axes of every value flattened to the reference's one)
+        assert isinstance(g, dict), "%s: obs is %s, a dict of views expected" % (where, type(g).__name__)
+        g = {k: x.reshape(x.shape[0], -1, *x.shape[x.ndim - (exp['obs'][k].ndim - 2):]) if k in exp['obs'] else x for k, x in VO.OO.host(g).items()}
+        VO.assert_views(g, exp['obs'], where)
+        return
     eq('obs', None if g is None else TO.widen(g).reshape(steps + 1, -1, exp['obs'].shape[-1] if exp['obs'] is not None else 1), exp['obs'], where)
 
 
@@ -233,6 +259,7 @@ class Case:
         self.snaps = [SO.NumpySnapshot(S, self.K, c) for c in self.caps]
         self.filled = [np.zeros(c, bool) for c in self.caps]      # never-saved slots are not read: a zero map has no walls to stop an agent
         self.table, self.book = KT.KeyTableModel(), KT.WhereBook(0)
+        self.last_fields = 0                                 # the selection of the last call that inserted state keys into the table
         self.term_rows = dict(map=np.zeros((n, S * S), np.int8), loc=np.zeros((n, 2), np.int32), facing=np.zeros(n, np.int32), inv=np.zeros((n, self.K), np.int32))
         self.term_known = np.zeros(n, bool)
         self.ofail = 0
@@ -376,6 +403,8 @@ class Case:
 
     def check_insert(self, keys, found, where):
         fresh, stored = self.table.insert(keys)
+        assert len(self.table) <= TABLE_CAPACITY, "%s: the model holds %d keys, the table's capacity is %d" % (where, len(self.table), TABLE_CAPACITY)
+        self.log('(table)', 'size', len(self.table))
         eq('fresh', host(found.fresh).reshape(-1), fresh, where)
         self.book.check(keys, host(found.where).reshape(-1), stored, where)
         assert len(self.vtable) == len(self.table), "%s: the table holds %d keys, the model %d" % (where, len(self.vtable), len(self.table))
@@ -508,14 +537,21 @@ class Case:
             form = 'envs' if s is None else 'slots'
         elif kind in ('srollout', 'srollout_kids', 'splayout', 'splayout_kids'):
             form = self.pair_call(kind, where, on_dev)
+        elif kind in GUIDED_KINDS:
+            form = self.guided_call(kind, where, on_dev)
         elif kind == 'playouts':
             form = PLAYOUTS_FORMS[int(rs.randint(0, len(PLAYOUTS_FORMS)))]
             P = int(rs.randint(1, min(MAX_PLANS, MAX_PAIRS // n) + 1))
+            if form == 'guided':
+                return self.guided_call(kind, where, on_dev, P)
             steps, seed = int(rs.randint(1, MAX_STEPS + 1)), int(rs.randint(0, 2 ** 31))
             w = (rs.rand(A) * (rs.rand(A) < 0.8)).astype(np.float32)
             fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
+            V = int(rs.choice(VIEW_SIZES))
             kw, rkw = {}, {}
-            if form == 'weights':
+            if form == 'view':                              # a 'rewards' call with the AgentMap views of every visited row
+                kw.update(rewards=True, observe='agent_view', view_size=V); rkw.update(rewards=True, view_size=V)
+            elif form == 'weights':
                 kw['weights'], rkw['weights'] = (self.dev(w) if on_dev else w), w
             elif form == 'path_keys':
                 kw.update(path_keys=True, fields=fields); rkw.update(path_keys=True, fields=fields)
@@ -553,6 +589,7 @@ class Case:
                 keys, found = v.insert_state_keys(self.vtable, self.maybe_dev(envs, on_dev), fields, device=on_dev)
                 eq('keys', keys, exp, where)
                 self.check_insert(exp, found, where)
+                self.last_fields = fields
         elif kind in ('succ_keys', 'insert_succ_keys'):
             envs = self.envs_list(rs, MAX_PAIRS if kind == 'succ_keys' else 8)
             if kind == 'insert_succ_keys' and envs is None:
@@ -570,6 +607,7 @@ class Case:
                 SU.assert_successors(got, ex, fields, where)
                 assert tuple(found.fresh.shape) == tuple(ex.keys(fields).shape), where
                 self.check_insert(ex.keys(fields).reshape(-1), found, where)
+                self.last_fields = fields
         elif kind == 'table_insert':
             keys = self.draw_keys(rs, int(rs.randint(1, 65)))
             found = self.vtable.insert(self.dev(keys.view(np.int64)) if on_dev else (keys if rs.randint(0, 2) else keys.view(np.int64)), device=on_dev)
@@ -613,6 +651,7 @@ class Case:
                     keys, found = snap.insert_keys(self.vtable, arg, fields, device=on_dev)
                     eq('keys', keys, exp, where)
                     self.check_insert(exp, found, where)
+                    self.last_fields = fields
         elif kind == 'agent_view':
             V = int(rs.choice([1, 2, 5]))
             eq('agent view', v.agent_view(V, device=on_dev, copy=bool(rs.randint(0, 2))), NO.agent_view(o.st.map, o.st.loc, V), where)
@@ -657,17 +696,20 @@ class Case:
         limits = rs.randint(0, steps + 1, count).astype(np.int32) if rs.randint(0, 2) else None
         fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
         record, with_keys, with_obs, with_masks = bool(rs.randint(0, 2)), bool(rs.randint(0, 2)), bool(rs.randint(0, 2)), bool(rs.randint(0, 2))
+        V = int(rs.choice(VIEW_SIZES))
         kw, rkw = {}, {}
         if form == 'weighted' or (playout and form != 'plain' and rs.randint(0, 3) == 0):
             kw['weights'], rkw['weights'] = (self.dev(w) if on_dev else w), w
-        if form in ('path', 'traj'):
+        if form in ('path', 'traj', 'view'):
             if limits is not None:
                 kw['limits'], rkw['limits'] = self.maybe_dev(limits, on_dev), limits
             if with_keys or (form == 'path' and limits is None):
                 kw.update(path_keys=True, fields=fields); rkw.update(path_keys=True, fields=fields)
-        if form == 'traj':
+        if form in ('traj', 'view'):                        # 'view': a 'traj' call whose observation is the AgentMap dict, always asked for
             kw['rewards'] = rkw['rewards'] = True
-            if with_obs:
+            if form == 'view':
+                kw.update(observe='agent_view', view_size=V); rkw['view_size'] = V
+            elif with_obs:
                 kw['observe'], rkw['lc'] = 'lidar', self.lc
             if playout and with_masks:
                 kw['masks'] = rkw['masks'] = True
@@ -685,6 +727,118 @@ class Case:
             got = snap.rollout(p, self.dev(np.ascontiguousarray(plans.T)) if on_dev else plans, children=c, device=on_dev, **src, **kw)
         check_pairs(got, exp, 'playout' if playout else 'rollout', record, where)
         return '%s/%s' % (form, 'envs' if s is None else 'slots')
+
+    def guided_call(self, kind, where, on_dev, P=None):
+        """A guided playout - Snapshot.playout(table=, table_weights=, outside=) with or without children, or with P the 'guided' form of playouts()
+        - over the case's own table: whatever the earlier calls inserted, under whatever fields, plus (three times in four) an offer of keys under this
+        call's fields.  Every row of table_weights no member owns is NaN: a lane that reads one changes the actions or raises F_BAD_WEIGHT."""
+        rs, spec, A, n, ar, H = self.rs, self.spec, self.A, self.n, self.autoreset, self.horizon
+        batch, kids = P is not None, kind.endswith('_kids')
+        # 1. every draw
+        s, d, parents, children = self.draw_source(rs, MAX_PAIRS, need_dst=kids)
+        steps, seed, first_pair = int(rs.randint(1, MAX_STEPS + 1)), int(rs.randint(0, 2 ** 31)), int(rs.randint(0, 2 ** 40))
+        if batch:
+            s, parents, first_pair = None, np.repeat(np.arange(n), P).astype(np.int32), self.base * P
+        if not kids:
+            children = None
+        count = len(parents)
+        fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
+        limits = rs.randint(0, steps + 1, count).astype(np.int32) if rs.randint(0, 2) and not batch else None
+        w = (rs.rand(A) * (rs.rand(A) < 0.8)).astype(np.float32)
+        default = w if rs.randint(0, 3) else None
+        outside = ('default', 'stop')[int(rs.randint(0, 2))]
+        record, with_keys, rewards, masks = [bool(x) for x in rs.randint(0, 2, 4)]
+        observe = (None, None, 'lidar', 'agent_view')[int(rs.randint(0, 4))]
+        V = int(rs.choice(VIEW_SIZES))
+        fill_seed = int(rs.randint(0, 2 ** 31))
+        offer, again = bool(rs.randint(0, 4)), bool(rs.randint(0, 2))
+        if not offer and again and self.last_fields:     # a table only earlier calls filled, looked up under the selection the last of them keyed it by
+            fields = self.last_fields
+        keep = rs.rand(count * (1 + (steps + 1) // 2)) < OFFER_KEEP[int(rs.randint(0, len(OFFER_KEEP)))]
+        probe = rs.randint(0, 1 << 30, 64)
+        record = record and not batch                    # (playouts() records no actions)
+        src = self.src_rows(s)
+        rows = rows_of(src)
+        # 2. the offer: the parents' keys and the path keys of the even steps of a plain playout under the fill seed (guided_playout_oracle.inputs'
+        #    recipe), thinned, through the table's own insert
+        bound = False
+        if offer:
+            _, _, acts, _ = PO.oracle_playout(spec, rows, parents, steps, fill_seed, 0, ar, H)
+            _, _, _, states, _ = KO.oracle_path(spec, rows, parents, acts, None, ar, H, fields)
+            at = [(t, j) for t in range(0, steps, 2) for j in range(count) if (t, j) in states]
+            path = fast_keys({k: np.stack([np.asarray(states[i][k]) for i in at]) for k in STATE_KEYS}, fields) if at else np.zeros(0, np.uint64)
+            keys = np.concatenate([fast_keys(rows_at(src, parents), fields), path])
+            keys = keys[keep[:len(keys)]]
+            new = set(keys.tolist()) - set(self.table.order) - {0}
+            bound = len(self.table) + len(new) > TABLE_CAPACITY
+            if len(keys) and not bound:                  # (a full table is not what this fuzz models: both sides skip the offer)
+                self.check_insert(keys, self.vtable.insert(keys), where + ' (the offer)')
+                self.last_fields = fields
+        # 3. the weight rows: f(key) in the bucket the table reported for that key (never a fresh look-up), NaN everywhere else
+        craft = GO.craft_ids(spec)
+        members = list(self.table.order)
+        tw = np.full((self.vtable.buckets, A), np.nan, np.float32)
+        for k in members:
+            tw[self.book.of_key[k]] = GO.row_of(k, A, craft)
+        # 4. the expectation
+        e = GO.oracle_guided(spec, rows, parents, steps, seed, members, lambda k: GO.row_of(k, A, craft), default, first_pair, ar, H, fields, limits,
+                             outside == 'stop', self.lc if observe == 'lidar' else None)
+        assert not e['bad'], where + ': the model itself read a bad weight'
+        exp = dict(ends=e['ends'], rep=dict(e['reports'], first_action=e['actions'][0].copy()), actions=e['actions'], keys=None,
+                   rewards=e['rewards'] if rewards else None, masks=e['masks'] if masks else None, obs=e['obs'])
+        if observe == 'agent_view':
+            exp['obs'] = VO.expect_views(spec, rows, parents, e, V)
+        if with_keys:                                    # hashed here from the visited rows, as ref_pairs does
+            exp['keys'] = np.zeros((steps, count), np.uint64)
+            at = sorted(e['states'])
+            if at:
+                kk = fast_keys({k: np.stack([np.asarray(e['states'][i][k]) for i in at]) for k in STATE_KEYS}, fields)
+                for (t, j), x in zip(at, kk):
+                    exp['keys'][t, j] = x
+        ran = e['actions'] >= 0
+        exp_where = np.full((steps, count), -1, np.int32)
+        for t, j in np.argwhere(e['hit']):
+            exp_where[t, j] = self.book.of_key[int(e['before'][t, j])]
+        if kids:
+            self.write_children(d, children, e['ends'])
+        # the call
+        kw = dict(table=self.vtable, table_weights=self.dev(tw) if on_dev else tw, outside=outside, fields=fields, rewards=rewards, masks=masks)
+        if default is not None:
+            kw['weights'] = self.dev(default) if on_dev else default
+        if with_keys:
+            kw['path_keys'] = True
+        if observe is not None:
+            kw['observe'] = observe
+        if observe == 'agent_view':
+            kw['view_size'] = V
+        if batch:
+            got = self.v.playouts(P, steps, seed, device=on_dev, **kw)
+            assert tuple(got.ret.shape) == (n, P) and tuple(got.where.shape) == (steps, n, P) and tuple(got.depth.shape) == (n, P), where
+        else:
+            if limits is not None:
+                kw['limits'] = self.maybe_dev(limits, on_dev)
+            got = self.vsnaps[d].playout(self.maybe_dev(parents, on_dev), steps, seed, children=self.maybe_dev(children, on_dev), first_pair=first_pair,
+                                         record=record, device=on_dev, **self.src_kw(s, d), **kw)
+        assert type(got).__name__ == 'PlayoutGuided', "%s: a %s came back" % (where, type(got).__name__)
+        check_pairs(got, exp, 'playout', record, where)
+        for name, x in (('where', exp_where), ('depth', e['depth'])):
+            g = host(getattr(got, name))
+            assert g.dtype == np.int32, "%s: %s is %s" % (where, name, g.dtype)
+            eq(name, g.reshape(x.shape), x, where)
+        # the call commits nothing to the table: its count, and the buckets of up to 64 members
+        assert len(self.vtable) == len(self.table), "%s: the table holds %d keys, the model %d" % (where, len(self.vtable), len(self.table))
+        if members:
+            held = np.array([members[i % len(members)] for i in probe[:min(64, len(members))]], np.uint64)
+            self.book.check(held, host(self.vtable.lookup(held)), np.ones(len(held), bool), where + ' (members after the call)')
+        home = GO.home_buckets(np.array(members, np.uint64), self.vtable.buckets) if members else np.zeros(0, np.int64)
+        ev = e['events']
+        self.log('(guided)', kind, tuple(sorted(dict(
+            outside=outside, source='envs' if s is None else 'slots', limits=limits is not None, observe=observe, default=default is not None,
+            offered=offer, bound=bound, S=self.S, members=len(members), hits=ev['hits'], misses=ev['misses'], executed=ev['executed'],
+            reentries=ev['reentries'], zero_mass=ev['zero_mass'], differs=ev['differs'], key0=int((ran & (e['before'] == 0)).sum()),
+            displaced=int((home != np.array([self.book.of_key[k] for k in members], np.int64)).sum()),
+            shared_home=len(members) - len(set(home.tolist()))).items())))
+        return 'guided' if batch else 'guided/%s' % ('envs' if s is None else 'slots')
 
     # -------------------------------------------------------------- the walk
     def run(self):

@@ -2,9 +2,11 @@
 stand-ins composed by inheritance (trajectory_oracle.OracleVecTraj and its bases, successor_key_oracle.OracleVecSuccessors,
 lookahead_oracle.OracleVecLook, plan_oracle.OracleVecPlans, key_table_oracle.stand_in_table for the table's host checks) and the surface they lack
 written from the row-level reference functions.  Settings it has no notion of are accepted and ignored (prepared episodes, the page-locked block,
-the fused lidar's format); a "device" input is the host array in the device form's layout, wrapped in Dev.  No GPU."""
+the fused lidar's format); a "device" input is the host array in the device form's layout, wrapped in Dev.  A guided playout reads its weight rows
+from the caller's table_weights at the buckets of the stand-in's OWN table (guided_result), so the driver's rows and buckets are checked too.  No GPU."""
 import numpy as np
 
+import guided_playout_oracle as GO
 import key_table_oracle as KT
 import lookahead_oracle as LO
 import mask_oracle as M
@@ -17,8 +19,9 @@ import snapshot_oracle as SO
 import state_key_oracle as SK
 import successor_key_oracle as SU
 import trajectory_oracle as TO
+import trajectory_view_oracle as VO
 from gym_novel_gridworlds_amd.key_table import KeyInsert, check_keys
-from gym_novel_gridworlds_amd.playout import Playout, PlayoutPath, PlayoutTraj
+from gym_novel_gridworlds_amd.playout import Playout, PlayoutGuided, PlayoutPath, PlayoutTraj
 from gym_novel_gridworlds_amd.sample import Sampled
 from gym_novel_gridworlds_amd.snapshot import Expansion, MapsTooLarge, SuccessorKeys, insert_successors
 from gym_novel_gridworlds_amd.state_keys import unique_of_keys
@@ -26,6 +29,7 @@ from gym_novel_gridworlds_amd.vec_env import PLACEMENT_MESSAGE, PlanEval, Rollou
 from oracle import ngw_oracle as NO
 
 STATE_KEYS = SO.STATE_KEYS
+F_BAD_WEIGHT = 16                    # include/ngw.h NGW_F_BAD_WEIGHT: a weight row that was read holds a negative, infinite or NaN entry
 
 
 class Dev:
@@ -56,6 +60,52 @@ def pair_result(kind, e, record, path_keys, traj):
     return PlayoutPath(*head, e['keys']) if path_keys else Playout(*head)
 
 
+def run_pairs(env, kind, rows, parents, record=False, observe=None, view_size=5, table=None, table_weights=None, outside='default', **kw):
+    """One rollout / playout call of any form on the dict `rows` -> (the result as the product types it, the end rows)."""
+    lc = env.lidar if observe == 'lidar' else None
+    views = int(view_size) if observe == 'agent_view' else None
+    traj = observe is not None or kw.get('rewards') or kw.get('masks')
+    kw['limits'] = un(kw.get('limits'))
+    kw['weights'] = un(kw.get('weights'))
+    if kind == 'rollout':
+        kw.pop('weights')
+    if kw.get('fields') is None:
+        kw['fields'] = SK.STATE
+    if table is not None:
+        return guided_result(env, rows, parents, record, lc, views, table, un(table_weights), outside, **kw)
+    e = F.ref_pairs(env.spec, rows, parents, kind, env.o.autoreset, env.o.horizon, lc=lc, view_size=views, **kw)
+    if views is not None:
+        e['obs'] = env._views(e['obs'], e['rep']['length'])
+    return pair_result(kind, e, record, kw.get('path_keys'), traj), e['ends']
+
+
+def guided_result(env, rows, parents, record, lc, views, table, tw, outside, steps, seed, first_pair=0, weights=None, limits=None, path_keys=False,
+                  fields=SK.STATE, rewards=False, masks=False):
+    """A guided playout from guided_playout_oracle's forward simulation.  The members are the keys this stand-in's own table holds, and the weight row
+    of a member is read from the caller's table_weights at the bucket that table gave the key - never the driver's row function: rows written into
+    the wrong buckets, or another tensor, change the actions or (a NaN row) raise the weight flag here as on the device."""
+    assert isinstance(table, StandInTable) and table.env is env, "table: a key table of this env expected"
+    A = len(env.spec.actions_id)
+    tw = np.asarray(tw)
+    assert tw.dtype == np.float32 and tw.shape == (table.buckets, A), ("table_weights", tw.dtype, tw.shape)
+    order = table.model.order
+    e = env._guided(env.spec, rows, parents, steps, seed, list(order), lambda k: tw[order[int(k)]], weights, first_pair, env.o.autoreset, env.o.horizon,
+                    fields, limits, outside == 'stop', lc)
+    if e['bad']:
+        env._flags |= F_BAD_WEIGHT
+    where = np.full(e['hit'].shape, -1, np.int32)
+    for t, j in np.argwhere(e['hit']):
+        where[t, j] = order[int(e['before'][t, j])]
+    obs = e['obs']
+    if views is not None:
+        obs = env._views(VO.expect_views(env.spec, rows, parents, e, views), e['reports']['length'])
+    rep = e['reports']
+    got = PlayoutGuided(rep['ret'], rep['length'], rep['ended'], rep['info'], e['actions'][0].copy(), e['actions'] if record else None,
+                        e['keys'] if path_keys else None, e['rewards'] if rewards else None, e['masks'] if masks else None, obs, where,
+                        np.asarray(e['depth'], np.int32))
+    return got, e['ends']
+
+
 class StandInSnapshot(PO._BoundPlayoutSnapshot, SU._BoundSuccessorSnapshot):
     """The bound snapshots of the existing stand-ins, with every form of rollout / playout, copy, the slot observers, keys and the key-table calls."""
 
@@ -80,31 +130,23 @@ class StandInSnapshot(PO._BoundPlayoutSnapshot, SU._BoundSuccessorSnapshot):
         return super().expand_all(un(parents), first_child, from_envs=from_envs, source=source)
 
     def _pairs(self, kind, parents, children, from_envs, source, record=False, **kw):
-        env = self.env
-        lc = env.lidar if kw.pop('observe', None) is not None else None
-        traj = lc is not None or kw.get('rewards') or kw.get('masks')
-        kw['limits'] = un(kw.get('limits'))
-        kw['weights'] = un(kw.get('weights'))
-        if kind == 'rollout':
-            kw.pop('weights')
-        if kw.get('fields') is None:
-            kw['fields'] = SK.STATE
-        e = F.ref_pairs(env.spec, F.rows_of(self._parent_rows(from_envs, source)), un(parents), kind, env.o.autoreset, env.o.horizon, lc=lc, **kw)
+        got, ends = run_pairs(self.env, kind, F.rows_of(self._parent_rows(from_envs, source)), un(parents), record, **kw)
         if children is not None:
             for k in STATE_KEYS:
-                self.model.rows[k][un(children)] = e['ends'][k]
-        return pair_result(kind, e, record, kw.get('path_keys'), traj)
+                self.model.rows[k][un(children)] = ends[k]
+        return got
 
     def rollout(self, parents, plans, children=None, from_envs=False, source=None, device=False, limits=None, path_keys=False, fields=SK.STATE, rewards=False,
-                masks=False, observe=None):
+                masks=False, observe=None, view_size=5):
         plans = un(plans).T if is_dev(plans) else np.asarray(plans)
         return self._pairs('rollout', parents, children, from_envs, source, plans=plans, limits=limits, path_keys=path_keys, fields=fields, rewards=rewards,
-                           observe=observe)
+                           observe=observe, view_size=view_size)
 
     def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False, weights=None, limits=None,
-                path_keys=False, fields=SK.STATE, rewards=False, masks=False, observe=None):
+                path_keys=False, fields=SK.STATE, rewards=False, masks=False, observe=None, view_size=5, table=None, table_weights=None, outside='default'):
         return self._pairs('playout', parents, children, from_envs, source, record=record, steps=steps, seed=seed, first_pair=first_pair, weights=weights,
-                           limits=limits, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe)
+                           limits=limits, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks, observe=observe, view_size=view_size, table=table,
+                           table_weights=table_weights, outside=outside)
 
     def lidar_observation(self, slots=None, device=False):
         return OO.expect_lidar(self.env.spec, self.env.lidar, self.model.rows, un(slots))
@@ -134,7 +176,7 @@ class StandInTable:
     """KeyTable over key_table_oracle's model; the host-side argument checks are the product's (a stand_in_table runs them)."""
 
     def __init__(self, env, capacity):
-        self.checks = KT.stand_in_table(capacity, env)
+        self.env, self.checks = env, KT.stand_in_table(capacity, env)
         self.buckets, self.capacity, self.model = self.checks.buckets, capacity, KT.KeyTableModel()
 
     def _keys(self, keys):
@@ -282,8 +324,19 @@ class StandIn(TO.OracleVecTraj, SU.OracleVecSuccessors, LO.OracleVecLook, PL.Ora
         self._step(s.action)
         return s
 
-    def playouts(self, n_playouts, steps, seed, device=False, weights=None, **kw):
-        return super().playouts(n_playouts, steps, seed, weights=un(weights), **kw)
+    def playouts(self, n_playouts, steps, seed, device=False, weights=None, observe=None, view_size=5, table=None, **kw):
+        if observe != 'agent_view' and table is None:
+            return super().playouts(n_playouts, steps, seed, weights=un(weights), observe=observe, **kw)
+        P, N = int(n_playouts), self.num_envs
+        got, _ = run_pairs(self, 'playout', F.rows_of(self.o.st), np.repeat(np.arange(N), P), steps=steps, seed=seed, first_pair=self.env_index_base * P,
+                           weights=weights, observe=observe, view_size=view_size, table=table, **kw)
+        return got.shaped(N, P)
+
+    # ---- what the seeded faults of tests/test_search_fuzz_cpu.py replace
+    _guided = staticmethod(GO.oracle_guided)
+
+    def _views(self, obs, length):
+        return obs
 
 
 def make_stand_in(**kw):

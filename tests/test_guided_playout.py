@@ -112,6 +112,37 @@ def test_against_the_oracle(name):
     v.close()
 
 
+def test_limits_stop_and_a_large_first_pair_from_envs_and_from_another_snapshot():
+    """The smallest fixed shape of what tests/search_fuzz.py draws for a guided call, where a failure there can be moved to: fire12h (autoreset, a
+    horizon, the step count in the key), 130 pairs, T = 12, limits drawn in [0, T] together with outside='stop', first_pair = 2^33 + 5, children
+    kept - once from the live envs, once from another snapshot -, every field and the kept rows against the oracle."""
+    name = 'fire12h'
+    spec, v, pool, table, where_of, tw = make(name)
+    parents, default, members = GO.inputs(name)
+    _, o, _, _, _ = GO.twin(name)
+    _, _, auto, fields, _ = GO.CONFIGS[name]
+    assert auto and fields == GO.KEY_STATE | GO.KEY_STEP_COUNT
+    A, craft, first_pair = len(spec.actions_id), GO.craft_ids(spec), 2 ** 33 + 5
+    limits = np.random.RandomState(12).randint(0, STEPS + 1, COUNT).astype(np.int32)
+    e = GO.oracle_guided(spec, o.st, parents, STEPS, SEED, members, lambda k: GO.row_of(k, A, craft), default, first_pair, True, GO.HORIZON, fields, limits, True)
+    length, ended = e['reports']['length'], e['reports']['ended']
+    assert (length == limits).any() and (~ended & (length < limits)).any() and ended.any(), "pairs cut by their limit, by the table and by their episode's end"
+    assert (length == 0).any() and (length > 1).any() and (e['actions'] != GO.expected(name, stop=True)['actions']).any()
+    kw = dict(record=True, weights=default, limits=limits, first_pair=first_pair, path_keys=True, fields=fields, rewards=True, masks=True, table=table,
+              table_weights=tw, outside='stop')
+    kids = np.arange(GO.N, GO.N + COUNT)
+    got = pool.playout(parents, STEPS, SEED, children=kids, from_envs=True, **kw)
+    assert_guided(got, e, where_of, 'from the envs')
+    RO.assert_rows(pool.state(), e['ends'], 'from the envs', idx=kids)
+    other = v.snapshot(COUNT)
+    got = other.playout(parents, STEPS, SEED, children=np.arange(COUNT), source=pool, device=True, **kw)
+    assert_guided(got, e, where_of, 'from another snapshot')
+    RO.assert_rows(other.state(), e['ends'], 'from another snapshot', idx=np.arange(COUNT))
+    RO.assert_rows(pool.state(), e['ends'], 'the source keeps its rows', idx=kids)
+    assert len(table) == len(members) and v.error_flags() == 0
+    v.close()
+
+
 @pytest.mark.parametrize('observe', ['lidar', 'agent_view'])
 def test_observations_of_both_kinds(observe):
     name = 'axe11'
