@@ -21,7 +21,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_out_device_ptrs', 'ngw_sync', 'ngw_error_flags', 'ngw_timing_begin', 'ngw_timing_end',
            'ngw_graph_build', 'ngw_graph_launch', 'ngw_get_reset_prefetch', 'ngw_timing_mark', 'ngw_lidar_configure', 'ngw_lidar', 'ngw_lidar_fuse',
            'ngw_get_lidar', 'ngw_lidar_device_ptr', 'ngw_host_alloc', 'ngw_host_free', 'ngw_agent_view',
-           'ngw_get_agent_view', 'ngw_agent_view_device_ptr', 'ngw_set_reset_prefetch', 'ngw_step_host', 'ngw_lidar_set_output', 'ngw_rollout_actions',
+           'ngw_get_agent_view', 'ngw_agent_view_device_ptr', 'ngw_agent_view_fuse', 'ngw_set_reset_prefetch', 'ngw_step_host', 'ngw_lidar_set_output', 'ngw_rollout_actions',
            'ngw_pack_layout', 'ngw_pack_obs', 'ngw_unpack_obs', 'ngw_rollout_outputs', 'ngw_episode_stats', 'ngw_host_step_layout', 'ngw_step_device_many',
            'ngw_set_reset_prefetch_depth', 'ngw_get_reset_prefetch_depth', 'ngw_stream_order', 'ngw_host_mirror_invalidate', 'ngw_reset_host',
            'ngw_lidar_row_layout', 'ngw_step_kernel_info', 'ngw_set_terminal_capture', 'ngw_get_terminal_obs', 'ngw_terminal_device_ptrs',
@@ -152,6 +152,8 @@ def lib():
     L.ngw_agent_view.argtypes = [vp, C.c_int]
     L.ngw_get_agent_view.argtypes = [vp, vp]
     L.ngw_agent_view_device_ptr.argtypes = [vp, C.POINTER(vp)]
+    if hasattr(L, 'ngw_agent_view_fuse'):
+        L.ngw_agent_view_fuse.argtypes = [vp, C.c_int, C.c_int]
     if hasattr(L, 'ngw_pack_obs'):
         L.ngw_pack_layout.argtypes = [vp, C.POINTER(u64)]
         L.ngw_pack_obs.argtypes = [vp, vp]

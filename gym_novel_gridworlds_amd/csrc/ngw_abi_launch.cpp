@@ -162,6 +162,7 @@ int enter(ngw_handle* h) {
 //                      and re-seeds the delta shadows, which also ends shadow_stale - that flag only means something under mirror_valid
 //   act_mask_fresh     the mask words describe the state: ngw_action_mask runs the kernel again
 //   look_fresh         the lookahead table describes the state: ngw_lookahead runs the kernel again
+//   view_fresh         the kept AgentMap windows describe the state: ngw_agent_view runs the gather again (launch() leaves them current itself)
 //   brd_dirty          the main set's bit rows do not describe its maps: ensure_boards rebuilds them before the next reader
 // Writers differ in two ways that matter, and `how` names them:
 //   WROTE_MAPS          maps changed without their bit rows (ngw_set_state with a map, a snapshot restore, a fused rollout - it steps the
@@ -177,6 +178,7 @@ void state_written(ngw_handle* h, unsigned how) {
     h->mirror_valid = false;
     h->act_mask_fresh = false;
     h->look_fresh = false;
+    h->view_fresh = false;
     if (how & WROTE_MAPS) h->brd_dirty = true;
 }
 
@@ -238,6 +240,10 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
     // action masks of the post-step state: fused into the plain step kernels (both forms), the standalone kernel behind the others
     const bool want_mask = mode == NGW_MODE_STEP && h->act_mask_on && o.masks && h->act_mask;
     bool fused_mask = false;
+    // the kept AgentMap windows (ngw_agent_view_fuse) of the state the launch leaves: built by the in-place step kernel's VIEW form where the launch
+    // fuses nothing else and has no host write-through, by the stand-alone gather right behind the launch everywhere else
+    const bool want_view = h->view_on && (mode == NGW_MODE_STEP || mode == NGW_MODE_RESET || rollout);
+    bool fused_view = false;
     if (mode == NGW_MODE_RESET) { if (int rc = launch_reset_fast(h, NGW_MODE_RESET, mask_dev, o.seq, &taken)) return rc; }
     if (!taken && mode == NGW_MODE_STEP && step_in_place(h)) {
         NgwLaunch q = h->ns_proto;
@@ -248,8 +254,18 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
         // report a sequence number) stay on the general one in every form, also where they stage an int32 row
         const bool plain = step_plain(h) && !o.wire && !fused_mask && o.actions == LaunchOpts::ACT_I32 && q.seq == 0;
         h->last_step_plain = plain;
-        HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, NGW_FEAT_NOSTAGE | ext | (boards ? NGW_FEAT_LIDAR : 0) | (o.wire ? NGW_FEAT_WIRE : 0) | (fused_mask ? NGW_FEAT_MASK : 0) |
-                           (plain ? NGW_FEAT_PLAIN : 0), grid, h->ns_lds, h->stream));
+        fused_view = want_view && view_in_step(h) && !boards && !o.wire && !fused_mask && q.bid0 == 0;
+        const int feat = NGW_FEAT_NOSTAGE | ext | (boards ? NGW_FEAT_LIDAR : 0) | (o.wire ? NGW_FEAT_WIRE : 0) | (fused_mask ? NGW_FEAT_MASK : 0) | (plain ? NGW_FEAT_PLAIN : 0);
+        if (fused_view) {
+            NgwLaunchView qv;
+            static_cast<NgwLaunch&>(qv) = q;
+            const uint32_t W = 2u * (uint32_t)h->view_size + 1u;
+            const size_t bytes = (size_t)h->n * W * W;
+            qv.view = reinterpret_cast<uint32_t*>(h->view_out); qv.n_dwords = (uint32_t)((bytes + 3) / 4); qv.V = h->view_size;
+            qv.magicW = (uint32_t)((0x100000000ull + W - 1u) / W); qv.magicWW = (uint32_t)((0x100000000ull + W * W - 1u) / (W * W));
+            HIP_TRY(ngw_launch(h->dspec, &qv, h->map_mode, feat | NGW_FEAT_VIEW, grid, h->ns_lds, h->stream));
+        } else
+        HIP_TRY(ngw_launch(h->dspec, &q, h->map_mode, feat, grid, h->ns_lds, h->stream));
         taken = true;
     }
     if (!taken) {
@@ -267,6 +283,8 @@ int launch(ngw_handle* h, int mode, int n_steps, const int32_t* actions_dev, con
     if (boards && mode == NGW_MODE_RESET) { if (int rc = refresh_fused_obs(h)) return rc; }
     if (fused_mask) h->act_mask_fresh = true;
     else if (want_mask) { if (int rc = launch_act_mask(h)) return rc; }   // (same stream: right behind the step)
+    if (fused_view) h->view_fresh = true;
+    else if (want_view) { if (int rc = launch_view(h)) return rc; }       // (likewise)
     if (mode == NGW_MODE_RESET) return steps_since_refill(h, h->prefetch_every);
     if (mode == NGW_MODE_STEP || rollout) return steps_since_refill(h, n_steps);
     return NGW_OK;                                     // (the diagnostic modes)
@@ -299,7 +317,7 @@ int launch_step_slice(ngw_handle* h, const uint8_t* actions_u8_dev, int64_t firs
 
 // ---------------------------------------------------------------- the one-env handle's resident step loop (ngw_solo.inc)
 bool solo_ok(const ngw_handle* h) {
-    return h->solo_enabled && h->n == 1 && h->hostres && !h->autoreset && !h->lidar_fused && !h->term_on && !h->capturing && h->proto.S <= 46;
+    return h->solo_enabled && h->n == 1 && h->hostres && !h->autoreset && !h->lidar_fused && !h->term_on && !h->capturing && !h->view_on && h->proto.S <= 46;
 }
 
 namespace {
@@ -428,6 +446,7 @@ int solo_step(ngw_handle* h, int32_t action) {
 
 int step_slices_done(ngw_handle* h) {
     if (h->act_mask_on && h->act_mask) { if (int rc = launch_act_mask(h)) return rc; }
+    if (int rc = launch_view(h)) return rc;                                       // (the kept AgentMap windows: no-op unless they are on)
     return steps_since_refill(h, 1);
 }
 
@@ -525,7 +544,7 @@ int capture_graph(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride
     const bool open = h->prefetch_every > 0 && n_steps * 2 <= h->cadence;
     // Capturing runs nothing: what its launch() calls book as done is put back to `before` when the capture ends - whether the masks
     // describe the state, and, for an open graph, the steps since the last refill.
-    const struct { int since_refill; bool act_mask_fresh, look_fresh; } before = {h->since_refill, h->act_mask_fresh, h->look_fresh};
+    const struct { int since_refill; bool act_mask_fresh, look_fresh, view_fresh; } before = {h->since_refill, h->act_mask_fresh, h->look_fresh, h->view_fresh};
     h->since_refill = 0;                              // the captured refill cadence starts from a known phase
     HIP_TRY(hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal));
     h->capturing = true;                              // (the depth and cadence the handle has adapted to so far are the ones captured)
@@ -544,8 +563,10 @@ int capture_graph(ngw_handle* h, const int32_t* actions_dev, int64_t step_stride
     h->capturing = false;
     h->act_mask_fresh = before.act_mask_fresh;
     h->look_fresh = before.look_fresh;
+    h->view_fresh = before.view_fresh;
     if (open) h->since_refill = before.since_refill;
     h->graph_act_mask = h->act_mask_on;
+    h->graph_view = h->view_on;
     hipError_t e = hipStreamEndCapture(h->stream, &h->graph);
     if (rc) { drop_graph(h); return rc; }
     if (e != hipSuccess) { drop_graph(h); return fail(NGW_E_HIP, "hipStreamEndCapture failed: %s", hipGetErrorString(e)); }
@@ -856,6 +877,7 @@ int ngw_graph_launch(ngw_handle* h, int32_t reps) {
         }
         HIP_TRY(hipGraphLaunch(h->graph_exec, h->stream));
         if (h->graph_act_mask) h->act_mask_fresh = true;
+        if (h->graph_view) h->view_fresh = true;
         if (h->graph_open) h->since_refill += h->graph_steps;
     }
     return NGW_OK;

@@ -53,7 +53,40 @@ int layout_lidar(ngw_handle* h) {
     return NGW_OK;
 }
 
+// AgentMap windows: the bytes of a [n][W][W] int8 buffer, and a buffer (re)allocated for one - whole dwords, grown only
+size_t view_bytes(const ngw_handle* h, int view_size) {
+    const size_t W = 2 * (size_t)view_size + 1;
+    return (size_t)h->n * W * W;
+}
+
+int view_buffer(ngw_handle* h, int view_size, int8_t** out, int* size, size_t* cap) {
+    if (view_size == *size) return NGW_OK;
+    const size_t bytes = view_bytes(h, view_size);
+    *size = 0;
+    if (bytes > *cap) {
+        if (*out) dev_free(h, *out);
+        *out = nullptr; *cap = 0;
+        if (int rc = dev_alloc(h, out, (bytes + 3) / 4 * 4)) return rc;
+        *cap = bytes;
+    }
+    *size = view_size;
+    return NGW_OK;
+}
+
 }  // namespace
+
+// The kept windows (ngw_agent_view_fuse) of the state in HBM: the stand-alone gather, on the handle's stream - what follows every launch whose
+// kernel has no VIEW form, every explicit reset, and the switch-on itself.
+int ngwh::launch_view(ngw_handle* h) {
+    if (!h->view_on || !h->view_out) return NGW_OK;
+    HIP_TRY(ngw_agent_view_launch(h->b.map, h->b.loc, reinterpret_cast<uint32_t*>(h->view_out), (uint32_t)((view_bytes(h, h->view_size) + 3) / 4), h->proto.S,
+                                  h->view_size, h->stream));
+    h->view_fresh = true;
+    return NGW_OK;
+}
+
+// The step kernel builds them itself: asked for (not the A/B form), and a window small enough that this beats the second launch (view_fuse_max)
+bool ngwh::view_in_step(const ngw_handle* h) { return h->view_on && h->view_fused && h->view_out && h->view_size <= h->view_fuse_max; }
 
 extern "C" {
 
@@ -247,21 +280,41 @@ int ngw_lidar_device_ptr(ngw_handle* h, void** out) {
 int ngw_agent_view(ngw_handle* h, int view_size) {
     if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
     if (view_size < 1 || view_size > 127) return fail(NGW_E_INVALID_ARG, "view_size must be in 1..127");   // :99 'Increase the agent_view_size'
-    const size_t W = 2 * (size_t)view_size + 1, bytes = (size_t)h->n * W * W;
+    const size_t bytes = view_bytes(h, view_size);
     if (bytes + 4 > 0xffffffffull) return fail(NGW_E_INVALID_ARG, "agent view of %zu B exceeds the 4 GiB index range", bytes);
     if (int rc = enter(h)) return rc;
-    if (view_size != h->view_size) {
-        h->view_size = 0;
-        if (bytes > h->view_cap) {
-            if (h->view_out) dev_free(h, h->view_out);
-            h->view_out = nullptr; h->view_cap = 0;
-            if (int rc = dev_alloc(h, &h->view_out, (bytes + 3) / 4 * 4)) return rc;
-            h->view_cap = bytes;
-        }
-        h->view_size = view_size;
+    if (h->view_on && view_size != h->view_size) {
+        // another size than the one kept current: its own buffer and its own gather, the kept windows stay what they are
+        if (int rc = view_buffer(h, view_size, &h->view_side, &h->view_side_size, &h->view_side_cap)) return rc;
+        h->view_last_side = true;
+        HIP_TRY(ngw_agent_view_launch(h->b.map, h->b.loc, reinterpret_cast<uint32_t*>(h->view_side), (uint32_t)((bytes + 3) / 4), h->proto.S, view_size, h->stream));
+        return NGW_OK;
     }
+    h->view_last_side = false;
+    if (h->view_on && h->view_fresh) return NGW_OK;              // (kept current and nothing has written the state since: nothing to launch)
+    if (int rc = view_buffer(h, view_size, &h->view_out, &h->view_size, &h->view_cap)) return rc;
     HIP_TRY(ngw_agent_view_launch(h->b.map, h->b.loc, reinterpret_cast<uint32_t*>(h->view_out), (uint32_t)((bytes + 3) / 4),
                                   h->proto.S, view_size, h->stream));
+    h->view_fresh = h->view_on;
+    return NGW_OK;
+}
+
+int ngw_agent_view_fuse(ngw_handle* h, int view_size, int on) {
+    if (!h) return fail(NGW_E_INVALID_ARG, "handle is NULL");
+    if (on < 0 || on > 2) return fail(NGW_E_INVALID_ARG, "on must be 0 (off), 1 (fused into the step kernel where it has the form) or 2 (the stand-alone gather behind every launch)");
+    if (on && (view_size < 1 || view_size > 127)) return fail(NGW_E_INVALID_ARG, "view_size must be in 1..127");
+    if (on && view_bytes(h, view_size) + 4 > 0xffffffffull) return fail(NGW_E_INVALID_ARG, "agent view of %zu B exceeds the 4 GiB index range", view_bytes(h, view_size));
+    if (int rc = enter(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    drop_graph(h);                                   // captured launches bake the buffer and the form in
+    h->view_on = false; h->view_fused = false; h->view_fresh = false; h->view_last_side = false;
+    if (!on) return NGW_OK;
+    if (int rc = view_buffer(h, view_size, &h->view_out, &h->view_size, &h->view_cap)) return rc;
+    h->view_on = true;
+    h->view_fused = on == 1;
+    h->view_fuse_max = NGW_VIEW_FUSE_DEFAULT;
+    if (const char* e = getenv("NGW_VIEW_FUSE")) { const int m = atoi(e); h->view_fuse_max = m < 0 ? 0 : (m > NGW_VIEW_FUSE_MAX ? NGW_VIEW_FUSE_MAX : m); }
+    if (int rc = launch_view(h)) { h->view_on = false; return rc; }   // current from here on, whatever state the handle is in
     return NGW_OK;
 }
 
@@ -269,8 +322,8 @@ int ngw_get_agent_view(ngw_handle* h, int8_t* out_host) {
     if (!h || !out_host) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (!h->view_size) return fail(NGW_E_INVALID_ARG, "ngw_get_agent_view before ngw_agent_view");
     if (int rc = enter(h)) return rc;
-    const size_t W = 2 * (size_t)h->view_size + 1;
-    HIP_TRY(hipMemcpyAsync(out_host, h->view_out, (size_t)h->n * W * W, hipMemcpyDefault, h->stream));
+    const bool side = h->view_last_side;
+    HIP_TRY(hipMemcpyAsync(out_host, side ? h->view_side : h->view_out, view_bytes(h, side ? h->view_side_size : h->view_size), hipMemcpyDefault, h->stream));
     HIP_TRY(hipStreamSynchronize(h->stream));
     return NGW_OK;
 }
@@ -278,7 +331,7 @@ int ngw_get_agent_view(ngw_handle* h, int8_t* out_host) {
 int ngw_agent_view_device_ptr(ngw_handle* h, void** out) {
     if (!h || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (!h->view_size) return fail(NGW_E_INVALID_ARG, "ngw_agent_view_device_ptr before ngw_agent_view");
-    *out = h->view_out;
+    *out = h->view_last_side ? h->view_side : h->view_out;
     return NGW_OK;
 }
 

@@ -50,6 +50,7 @@ NGW_PART_FN(ngw_part_step_boards);
 NGW_PART_FN(ngw_part_step_wire);
 NGW_PART_FN(ngw_part_step_wire_boards);
 NGW_PART_FN(ngw_part_step_mask_ns);
+NGW_PART_FN(ngw_part_step_view);
 NGW_PART_FN(ngw_part_rollout_straight);
 NGW_PART_FN(ngw_part_rollout_dword);
 NGW_PART_FN(ngw_part_rollout_byte);

@@ -234,7 +234,20 @@ enum { NGW_FEAT_LIDAR = 1,    /* fused LidarInFront epilogue (with NGW_FEAT_NOST
        NGW_FEAT_NOSTAGE = 8,  /* NGW_MODE_STEP: the in-place step kernel (maps read where they lie, no staging through LDS) */
        NGW_FEAT_WIRE = 16,    /* ... its host write-through form (NgwWT) */
        NGW_FEAT_MASK = 32,    /* fused action masks (plain steps only: ngw_step_lean<..., MASK>) */
-       NGW_FEAT_PLAIN = 64 }; /* ... the in-place kernel's instantiation for the plain spec class (ngw_step_plain_class), int32 action rows only */
+       NGW_FEAT_PLAIN = 64,   /* ... the in-place kernel's instantiation for the plain spec class (ngw_step_plain_class), int32 action rows only */
+       NGW_FEAT_VIEW = 128 }; /* ... its form with the fused AgentMap window (ngw_step_lean<..., VIEW>): `a` points at an NgwLaunchView */
+
+/* The launch block of the in-place step kernel's VIEW form: the step's own block, then what the AgentMap epilogue needs (view_rows, ngw_lean_step.inc).
+ * The other forms keep NgwLaunch as their argument type, so their argument blocks - and their code - are what they were. */
+#define NGW_VIEW_FUSE_MAX 16     /* largest view_size the VIEW form can build (its divisions are exact up to here, as NgwTrajViews') */
+#define NGW_VIEW_FUSE_DEFAULT 2  /* ... and the largest one a handle lets it build: one wave builds its 64 windows serially, ~9 instructions per byte, and from
+                                  * view_size 5 on that costs more than the second launch saves; NGW_VIEW_FUSE=<view_size> moves it (A/B) */
+struct NgwLaunchView : NgwLaunch {
+    uint32_t* view;              /* [n][W][W] int8 as n_dwords dwords, W = 2 * V + 1 (ngw_agent_view's buffer) */
+    uint32_t n_dwords;
+    int32_t V;
+    uint32_t magicW, magicWW;    /* ceil(2^32 / W), ceil(2^32 / (W * W)): exact for the operands below 64 * W * W the epilogue divides (V <= NGW_VIEW_FUSE_MAX, as NgwTrajViews) */
+};
 
 /* The plain spec class of the in-place step kernel (ngw_step_lean<..., PLAIN>, ngw_lean_step.inc), decided once per handle: at most 12 items
  * (three 16-byte chunks hold an inventory row), no Jump action, no entities, both "near" rules look for the same item, and every byte the hot

@@ -190,6 +190,17 @@ struct ngw_handle {
     int8_t* view_out = nullptr;           // AgentMap windows
     int view_size = 0;
     size_t view_cap = 0;
+    // The AgentMap window kept current (ngw_agent_view_fuse).  view_on: every committed step and reset leaves the windows of the state it produced in
+    // view_out - built by the step kernel's VIEW form where the launch has one (view_fused, and view_size <= NGW_VIEW_FUSE_MAX), by the stand-alone
+    // gather behind the launch everywhere else.  view_fresh: view_out describes the current state (state_written clears it; ngw_agent_view of the
+    // same size then launches nothing).  A window of ANOTHER size asked for meanwhile goes to view_side and leaves view_out alone; view_last_side:
+    // ngw_get_agent_view / ngw_agent_view_device_ptr hand out that one (the result of the last ngw_agent_view).
+    bool view_on = false, view_fused = false, view_fresh = false, view_last_side = false;
+    bool graph_view = false;              // the captured graph leaves the windows of the state it ends in
+    int view_fuse_max = NGW_VIEW_FUSE_DEFAULT;   // largest view_size the step kernel builds itself (NGW_VIEW_FUSE, read by ngw_agent_view_fuse)
+    int8_t* view_side = nullptr;
+    int view_side_size = 0;
+    size_t view_side_cap = 0;
     // Action masks (ngw_abi_mask.cpp, ngw_mask.inc): [n_pad] uint64 words in HBM.  act_mask_fresh: they describe the current state
     // (state_written clears it; a step with act_mask_on leaves the post-step masks behind it on the stream and sets it)
     uint64_t* act_mask = nullptr;
@@ -307,6 +318,9 @@ void drop_graph(ngw_handle* h);
 size_t lidar_layout(const ngw_handle* h, NgwLaunch& q);   // the stand-alone lidar launch's LDS carve-up into q (S, MS, KP and the row format set) -> its bytes, whatever they come to
 // ngw_abi_mask.cpp
 int launch_act_mask(ngw_handle* h);                 // the masks of the state in HBM, on the handle's stream (allocates the buffer on first use)
+// ngw_abi_obs.cpp
+int launch_view(ngw_handle* h);                     // the kept AgentMap windows (view_on) of the state in HBM, as the stand-alone gather on the handle's stream
+bool view_in_step(const ngw_handle* h);             // ... or built by the in-place step kernel's VIEW form, where the launch is otherwise a plain one
 int alloc_act_mask(ngw_handle* h);                  // the mask buffer, published to NgwDevSpec::amask (no-op once allocated)
 bool solo_records_ready(ngw_handle* h);             // the one-env loop's speculated records belong to the host's state (waits for them like solo_step, never stops the loop)
 // ngw_abi_host.cpp

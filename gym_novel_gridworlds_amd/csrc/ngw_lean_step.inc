@@ -65,6 +65,82 @@ __device__ __forceinline__ void wire_done(const NgwWT& W, const uint32_t* dev_fl
     }
 }
 
+// VIEW: the fused AgentMap window (ngw_agent_view_kernel's observation, ngw_agent_view_fuse) - after the step's stores and, where the launch started
+// new episodes, after the cold path has put their rows in place, the wave builds the W x W windows (W = 2 * V + 1, unrotated, 0 outside the map) of
+// its 64 envs.  Wave-cooperative, the shape of traj_view_rows (ngw_traj.inc): the 64 windows are ONE aligned run of 16 * W * W dwords of the view
+// buffer and lane l builds dwords l, l + 64, ... of it - consecutive addresses across the wave whatever W is; a dword lies in at most two envs'
+// windows (W * W >= 9) and their agent cells come from the owner lanes with ds_bpermute.  The map bytes are read from HBM where the step left them:
+// four dwords' sixteen byte loads are issued together, on coordinates clamped into the map (the value of a cell outside it is dropped), so a
+// round costs one trip to the L1 / L2 the step has just filled.
+//
+// Visibility.  A lane reads cells that OTHER lanes of its wave stored in this launch (the step's cell write, an entity pick-up, a new episode's
+// row).  Writer and reader are the same wavefront, so the same CU and the same vector L1, which is write-through and coherent with its own CU's
+// stores: what is needed is that the stores have completed before the loads are issued - a workgroup-scope fence, which on this target is the
+// wait for the vector-memory counter and no cache operation (the LLVM AMDGPU memory model, gfx942 family, non-tgsplit: "no special action for
+// coherence between wavefronts in the same work-group").  The explicit s_waitcnt behind it is the wait itself, in case the fence's own is elided.
+// Nothing here is visible to another CU before the kernel ends, and nothing needs to be: the buffer's readers are later launches.
+__device__ __forceinline__ void view_sync() {
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+}
+
+// every lane of the wave calls it (ds_bpermute inside); maps: the wave's 64 map rows; gbid: the wave's block in the whole batch; r, c: this lane's agent cell
+__device__ __forceinline__ void view_rows(const NgwLaunchView& v, const char* maps, int S, int S2, uint32_t gbid, uint32_t tid, bool live, int r, int c) {
+    const int V = v.V;
+    const uint32_t W = 2u * (uint32_t)V + 1u, WW = W * W, nd = 16u * WW;          // the wave's tile: 64 * W * W bytes
+    const uint32_t d0 = gbid * nd;                                                 // (the buffer is below 4 GiB: ngw_agent_view_fuse)
+    const uint32_t left = v.n_dwords - min(d0, v.n_dwords);                        // the buffer ends with env n - 1, inside the last wave's tile
+    const int pose = live ? (r | (c << 8) | (1 << 16)) : 0;
+    GLOBAL_AS uint32_t* const g = (GLOBAL_AS uint32_t*)v.view + d0;
+#ifdef NGW_EXP_VIEW_PERLANE
+    // (experiment build, DESIGN.md 4.20: the rejected shape - every lane builds its own env's window, byte by byte; rows start at any byte)
+    GLOBAL_AS uint8_t* const gb = (GLOBAL_AS uint8_t*)g + tid * WW;
+    if (live) {
+        for (uint32_t wr = 0; wr < W; wr++) {
+            for (uint32_t wc = 0; wc < W; wc++) {
+                const int mr = r + (int)wr - V, mc = c + (int)wc - V;
+                const bool in = (unsigned)mr < (unsigned)S && (unsigned)mc < (unsigned)S;
+                const uint32_t cell = ldgg<uint8_t>(maps, tid * (uint32_t)S2 + (uint32_t)(in ? mr * S + mc : 0));
+                gb[wr * W + wc] = (uint8_t)(in ? cell : 0u);
+            }
+        }
+    }
+    (void)left; (void)pose;
+#else
+    constexpr int U = 4;                                                           // dwords per lane and round: 16 byte loads in flight
+    for (uint32_t base = 0; base < nd; base += U * EPB) {                          // (a wave-uniform trip count: ds_bpermute reads every lane)
+        uint32_t word[U];
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t p = base + (uint32_t)(u * EPB) + tid;
+            const uint32_t idx = min(p, nd - 1u) * 4u;                             // this dword's first byte in the tile
+            const uint32_t e = __umulhi(idx, v.magicWW);                           // ... lies in env e of the wave (and its last one in e or e + 1)
+            uint32_t rem = idx - e * WW;
+            const int p0 = __builtin_amdgcn_ds_bpermute((int)(e << 2), pose);
+            const int p1 = __builtin_amdgcn_ds_bpermute((int)(min(e + 1u, (uint32_t)EPB - 1u) << 2), pose);
+            uint32_t cur = 0, w = 0;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                const uint32_t wr = __umulhi(rem, v.magicW), wc = rem - wr * W;
+                const int pz = cur ? p1 : p0;
+                const int mr = (pz & 255) + (int)wr - V, mc = ((pz >> 8) & 255) + (int)wc - V;
+                const bool in = (pz >> 16) && (unsigned)mr < (unsigned)S && (unsigned)mc < (unsigned)S;
+                const uint32_t en = min(e + cur, (uint32_t)EPB - 1u);              // (the tile's last byte ends env 63: nothing is read behind it)
+                const uint32_t cell = ldgg<uint8_t>(maps, en * (uint32_t)S2 + (uint32_t)(in ? mr * S + mc : 0));
+                w |= (in ? cell : 0u) << (8 * j);
+                if (++rem == WW) { rem = 0; cur = 1; }
+            }
+            word[u] = w;
+        }
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            const uint32_t p = base + (uint32_t)(u * EPB) + tid;
+            if (p < nd && p < left) g[p] = word[u];
+        }
+    }
+#endif
+}
+
 // MASK: the fused action masks - after the step, every lane evaluates the mask of the state it leaves (the post-step pose and cells, or the
 // new episode's first state where the launch started one) with lane_mask (ngw_mask.inc) and stores it to NgwDevSpec::amask.  Plain steps
 // only (no lidar epilogue, no host write-through): with those the library runs the standalone mask kernel behind the step.
@@ -74,10 +150,11 @@ __device__ __forceinline__ void wire_done(const NgwWT& W, const uint32_t* dev_fl
 // never has is not compiled: three inventory chunks instead of six, one action load and no select, no Jump cell / entity block / second
 // neighbourhood test in lean_body.  A `PLAIN ? x : y` below picks at compile time: the general form compiles y alone.  Every address is the ONE preloaded
 // scalar base plus a 32-bit lane offset that already holds the block's share, so no 64-bit scalar base is built per array.
-template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false, bool PLAIN = false>
+template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false, bool PLAIN = false, bool VIEW = false>
 __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int32_t* actions, uint32_t n32, uint32_t o_brd, const NgwDevSpec* __restrict__ dspec,
                                                          uint32_t o_inv, uint32_t o_loc, uint32_t o_fac, uint32_t o_sel, uint32_t o_stp, uint32_t s2k,
-                                                         const NgwLaunch a) {
+                                                         const std::conditional_t<VIEW, NgwLaunchView, NgwLaunch> a) {
+    static_assert(!VIEW || (!STAGE && !LIDAR && !HW && !MASK), "the fused AgentMap window is the in-place step's, with nothing else fused");
     static_assert(!LIDAR || STAGE || NR > 0, "the fused LidarInFront epilogue marches over the map in LDS, or reads NR bit rows");
     static_assert(!HW || !STAGE, "the host write-through form is the in-place kernel's");
     static_assert(!MASK || (!LIDAR && !HW), "the fused masks are the plain step's");
@@ -326,6 +403,10 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
             uint64_t* const am = dspec->amask;
             if (am) stg<uint64_t>(reinterpret_cast<char*>(am) + (uint64_t)bid * (EPB * 8), tid * 8u, live ? m : 0ull);
         }
+        if constexpr (VIEW) {                                                      // the post-step state: this wave's cell writes are in HBM behind view_sync
+            view_sync();
+            view_rows(a, PLAIN ? bmap + (uint64_t)bid * (uint32_t)(EPB * S2) : bmap, PLAIN ? Sb : a.S, S2, bid, tid, live, o.r, o.c);
+        }
         if (HW) {
             step_signals(dspec, flags, 0u);
             wire_done(W, a.b.flags, a.seq, gridDim.x, tid);
@@ -410,6 +491,12 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
             uint64_t* const am = dspec->amask;
             if (am) stgg<uint64_t>(reinterpret_cast<char*>(am) + (uint64_t)gbid * (EPB * 8), tid * 8u, live ? m : 0ull);
         }
+        if constexpr (VIEW) {
+            // the wave has rewritten the map rows of its resetting envs in HBM (prepared-episode copies or the inline placement): the windows are
+            // built from there for every lane - the new episode's first state where the launch started one, the same state the pose stores above name
+            view_sync();
+            view_rows(a, reinterpret_cast<const char*>(c.b.map) + (uint64_t)gbid * (uint32_t)(EPB * c.S2), c.S, c.S2, gbid, tid, live, ro, co);
+        }
         if (HW) {
             step_signals(dspec, flags, 0u);
             wire_done(Wc, c.b.flags, seq, gridDim.x, tid);
@@ -424,7 +511,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_step_lean(char* sbase, const int3
 }
 
 
-template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false, bool PLAIN = false>
+template <int MAPMODE, bool STAGE, bool EXT, bool LIDAR, int NR = 0, bool HW = false, bool MASK = false, bool PLAIN = false, bool VIEW = false>
 hipError_t launch_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned grid, size_t lds_bytes, hipStream_t stream) {
     // the leading scalar arguments (see the kernel): the state slab's base and the offsets of its arrays in 16-byte units
     char* const base = reinterpret_cast<char*>(a->b.map);
@@ -452,8 +539,14 @@ hipError_t launch_lean(const NgwDevSpec* dspec, const NgwLaunch* a, unsigned gri
         uint64_t span = 0;
         for (uint64_t e : ends) span = e > span ? e : span;
         if (!ngw_step_plain_class(a->K, 0, 0, 0, 0, span, np * 4u) || a->use_action0 != 0)
-            return launch_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK, false>(dspec, a, grid, lds_bytes, stream);
+            return launch_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK, false, VIEW>(dspec, a, grid, lds_bytes, stream);
     }
+    if constexpr (VIEW) {                                                          // (`a` is the NgwLaunchView the caller built: NGW_FEAT_VIEW says so)
+        const NgwLaunchView& v = *static_cast<const NgwLaunchView*>(a);
+        if (!v.view || v.V < 1 || v.V > NGW_VIEW_FUSE_MAX || a->bid0 != 0 || a->S2 != a->S * a->S) return hipErrorInvalidValue;
+        return launch_kernel<ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK, PLAIN, true>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, base, a->actions, (uint32_t)a->n, o_brd,
+                                                                                               dspec, off[0], off[1], off[2], off[3], off[4], s2k, v);
+    } else
     return launch_kernel<ngw_step_lean<MAPMODE, STAGE, EXT, LIDAR, NR, HW, MASK, PLAIN>>(dim3(grid), dim3(NGW_EPB), lds_bytes, stream, base, a->actions, (uint32_t)a->n, o_brd, dspec,
                                                                                 off[0], off[1], off[2], off[3], off[4], s2k, *a);
 }

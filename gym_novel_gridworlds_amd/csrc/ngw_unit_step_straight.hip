@@ -11,6 +11,7 @@ extern "C" hipError_t ngw_part_step(const NgwDevSpec* dspec, const NgwLaunch* a,
         if (feat & NGW_FEAT_WIRE) return ngw_part_step_wire(dspec, a, feat, grid, lds_bytes, stream);   // ... with the host write-through
         if (feat & NGW_FEAT_LIDAR) return ngw_part_step_boards(dspec, a, feat, grid, lds_bytes, stream);
         if (feat & NGW_FEAT_MASK) return ngw_part_step_mask_ns(dspec, a, feat, grid, lds_bytes, stream);
+        if (feat & NGW_FEAT_VIEW) return ngw_part_step_view(dspec, a, feat, grid, lds_bytes, stream);   // ... with the fused AgentMap window
         if (feat & NGW_FEAT_EXT) return launch_lean<NGW_MAP_STRAIGHT, false, true, false>(dspec, a, grid, lds_bytes, stream);
         // ... the plain spec class has an instantiation of its own (launch_lean takes the launch back to the general one if it does not fit)
         return with_flag((feat & NGW_FEAT_PLAIN) != 0, [&](auto P) { return launch_lean<NGW_MAP_STRAIGHT, false, false, false, 0, false, false, decltype(P)::value>(dspec, a, grid, lds_bytes, stream); });

@@ -111,6 +111,17 @@ class ShardedVecNovelGridworld:
     def action_mask_words(self, device=False, copy=False):
         return self.local.action_mask_words(device, copy)
 
+    def set_agent_view(self, view_size=5, fused=True):
+        """Keep the AgentMap windows of this rank's shard current (VecNovelGridworld.set_agent_view): rank-local."""
+        return self.local.set_agent_view(view_size, fused=fused)
+
+    def agent_view(self, view_size=5, device=False, copy=False):
+        """The AgentMap windows of this rank's shard (VecNovelGridworld.agent_view): rank-local, no collective."""
+        return self.local.agent_view(view_size, device=device, copy=copy)
+
+    def agent_view_observation(self, view_size=5, device=False, copy=False):
+        return self.local.agent_view_observation(view_size, device=device, copy=copy)
+
     def lookahead(self, device=False, copy=False):
         """The one-step lookahead table of this rank's shard (VecNovelGridworld.lookahead): rank-local, no collective."""
         return self.local.lookahead(device=device, copy=copy)

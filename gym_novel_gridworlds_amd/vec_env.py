@@ -31,6 +31,13 @@ class _DevArray:
                                          'version': 2, 'strides': None}
 
 
+def check_view_size(view_size):
+    """The view_size of set_agent_view: an integer in 1 .. 127 (ngw_agent_view's range), as an int."""
+    if isinstance(view_size, bool) or not isinstance(view_size, (int, np.integer)) or not 1 <= view_size <= 127:
+        raise ValueError("view_size: an integer in 1..127 expected, got %r" % (view_size,))
+    return int(view_size)
+
+
 def unpack_action_masks(words, n_actions):
     """[N] packed action-mask words (bit a of word i: step(a) from env i's state would report result == True) -> bool [N, n_actions]."""
     w = np.ascontiguousarray(words, np.uint64).reshape(-1)
@@ -279,6 +286,8 @@ class VecNovelGridworld:
             self.lidar_configure(self.lidar, fused=self.lidar_fused, dtype='packed' if self.lidar_packed else self.lidar_dtype)
         if self.__dict__.get('_act_masks_on'):
             self.set_action_masks(True)
+        if self.__dict__.get('_agent_view_cfg'):
+            self.set_agent_view(*self._agent_view_cfg)
 
     def rebuild(self, spec):
         """The same batched env - same object, same shard of the global env index space (`env_index_base`), same autoreset /
@@ -1148,9 +1157,39 @@ class VecNovelGridworld:
         """Record the closing event of the timing pair without waiting for it (timing_end then only reads the pair)."""
         _cabi.check(_cabi.lib().ngw_timing_mark(self._h))
 
+    def set_agent_view(self, view_size=5, fused=True):
+        """Keep the AgentMap window current (include/ngw.h ngw_agent_view_fuse): after it, every committed step and every reset - step,
+        step_device, step_device_many, a replayed graph, step_sampled, rollout, reset with or without a mask - leaves the int8 [N, W, W] windows
+        (W = 2 * view_size + 1) of the state it produced in the handle's view buffer, on the handle's stream: what agent_view(view_size) called right
+        after it returns, byte for byte, with no second call and no host wait.  fused=True: the in-place step kernel builds the windows in the
+        launch that steps, where it fuses nothing else (no fused lidar, no action masks, no host write-through, and view_size <= 2 - larger windows measured slower than the
+        second launch); every other
+        launch is followed by the stand-alone gather.  fused=False: the gather behind every launch (the A/B form).  set_agent_view(None) switches
+        it off.  A graph is built after this call, not before."""
+        if view_size is None:
+            _cabi.check(_cabi.lib().ngw_agent_view_fuse(self._h, 0, 0))
+            self._agent_view_cfg = None
+            return
+        V = check_view_size(view_size)
+        _cabi.check(_cabi.lib().ngw_agent_view_fuse(self._h, V, 1 if fused else 2))
+        self._agent_view_cfg = (V, bool(fused))                 # (rebuild() switches it on again on the new handle)
+
+    def agent_view_observation(self, view_size=5, device=False, copy=False):
+        """The AgentMap observation of the current state, the dict Snapshot.agent_view returns: 'agent_map' (agent_view's window), 'agent_facing_id'
+        int32 [N] and 'inventory_items_quantity' int32 [N, K] - the last two are the env's own state arrays (device=True: zero-copy views of them),
+        not the output of another kernel."""
+        view = self.agent_view(view_size, device=device, copy=copy)
+        if device:
+            o = self.device_observation()
+        else:
+            o = self.get_observation(copy)
+        return {'agent_map': view, 'agent_facing_id': o['agent_facing_id'], 'inventory_items_quantity': o['inventory_items_quantity']}
+
     def agent_view(self, view_size=5, device=False, copy=False):
         """AgentMap window (reference observation_wrappers.py:104-121): int8 [N, 2*view_size+1, 2*view_size+1], the map
-        around each agent with 0 outside the map; one gather launch on the current state."""
+        around each agent with 0 outside the map; one gather launch on the current state.  With set_agent_view(view_size) on, the windows of
+        that size are kept current by the steps themselves: the call launches nothing unless the state was written some other way since
+        (set_state, a snapshot restore), and device=True is the same buffer every time.  Another size is gathered into a buffer of its own."""
         _cabi.check(_cabi.lib().ngw_agent_view(self._h, int(view_size)))
         W = 2 * int(view_size) + 1
         if device:

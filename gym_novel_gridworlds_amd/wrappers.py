@@ -93,6 +93,14 @@ class LimitActions(NoveltyWrapper):
         a limited id step() would refuse is False."""
         return limit_mask_columns(self.env.action_masks(), self.limited_actions_id, self.actions_id, len(self.limited_actions))
 
+    def set_agent_view(self, view_size=5, fused=True):
+        """The env's set_agent_view: the AgentMap window does not depend on the action id space."""
+        return self.env.set_agent_view(view_size, fused=fused)
+
+    def agent_view(self, view_size=5, device=False, copy=False):
+        """The env's agent_view, likewise passed through."""
+        return self.env.agent_view(view_size, device=device, copy=copy)
+
     def lookahead(self, device=False, copy=False):
         """The env's lookahead table in the limited id space: column i of 'reward' / 'done' / 'result' / 'info' is the env's column of the
         action limited id i steps (the same two look-ups as step); a limited id step() would refuse is a column of zeros.  device=True:

@@ -437,6 +437,27 @@ int ngw_lidar_device_ptr(ngw_handle* h, void** out);
 int ngw_agent_view(ngw_handle* h, int view_size);
 int ngw_get_agent_view(ngw_handle* h, int8_t* out_host);
 int ngw_agent_view_device_ptr(ngw_handle* h, void** out);
+/* The AgentMap window kept current.  ngw_agent_view_fuse(h, view_size, on) with on != 0 allocates the buffer of ngw_agent_view(h, view_size), fills
+ * it for the current state, and from then on every committed step and every reset - ngw_step, ngw_step_device, ngw_step_device_many, ngw_step_host,
+ * ngw_step_host_packed, a replayed graph (ngw_graph_launch: the state the last captured step leaves), the fused rollouts, ngw_reset and
+ * ngw_reset_host with or without a mask - leaves in it, on the handle's stream, the windows of the state the call produced: byte for byte what
+ * ngw_agent_view(h, view_size) issued right behind that call would gather.  For an env whose step ended its episode under autoreset that is the new
+ * episode's first state, as in every other observation.  ngw_agent_view_device_ptr returns the buffer; it stays the same allocation until the
+ * next ngw_agent_view_fuse.
+ *   on = 1  the in-place step kernel builds the windows in the launch that steps, where that launch fuses nothing else: no LidarInFront
+ *           observation, no action masks, no host write-through, and view_size <= 2 - a larger window costs the stepping wave more than the second
+ *           launch does (the environment variable NGW_VIEW_FUSE=<view_size, at most 16> moves the limit for A/B runs).  Every other launch - those forms, the staged and the general
+ *           kernel, resets, fused rollouts, larger windows - is followed by the stand-alone gather on the stream.  Same bytes either way.
+ *   on = 2  the stand-alone gather behind every launch (the A/B form of on = 1).
+ *   on = 0  off: the handle is back to gathering only when ngw_agent_view asks (view_size is ignored).
+ * While it is on, the handle tracks whether the buffer describes the current state: ngw_agent_view(h, view_size) with the kept size launches nothing
+ * when it does, and gathers again after a call that wrote the state some other way (ngw_set_state, a snapshot restore).  ngw_agent_view with ANOTHER
+ * size gathers into a buffer of its own and leaves the kept windows alone; ngw_get_agent_view / ngw_agent_view_device_ptr answer for the last
+ * ngw_agent_view call.  A one-env handle steps through per-launch kernels while it is on (the resident step loop has no view).  A captured graph is
+ * dropped (it bakes the form in): build it after this call.
+ * NGW_E_INVALID_ARG: a NULL handle; on outside 0..2; on != 0 with view_size outside 1..127 ("view_size must be in 1..127") or a buffer beyond the
+ * 4 GiB index range. */
+int ngw_agent_view_fuse(ngw_handle* h, int view_size, int on);
 
 /* Action masks (invalid-action masking, the action_masks() convention of MaskablePPO): the mask of env i is a uint64 word, bit a = 1
  * exactly when step(a) taken from env i's CURRENT state (the state the next step acts on; after an autoreset, the new episode's first
