@@ -16,6 +16,7 @@ from .spec import ENV_IDS, STEP_COSTS, EnvSpec, make_spec            # noqa: F40
 from .state_keys import (KEY_ALL, KEY_EPISODE, KEY_INV, KEY_MAP, KEY_POSE, KEY_SELECTED, KEY_STATE, KEY_STEP_COUNT,   # noqa: F401
                          keys_of_rows)
 from .vec_env import VecNovelGridworld                               # noqa: F401
+from .walk import WalkPlans, shortest_walk                           # noqa: F401
 from .wrappers import LimitActions, SaveTrajectories, limit_actions_vec             # noqa: F401
 
 __version__ = '0.1.0'

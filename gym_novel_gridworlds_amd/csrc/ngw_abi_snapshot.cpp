@@ -16,6 +16,7 @@
 // A guided playout (ngw_playout.inc, GUIDED) reads a key table and the caller's weight rows at every step: it commits nothing either, and leaves
 // the table as it was.
 // The weighted choice (ngw_sample.inc) draws one action per row by the caller's weights among the valid ones: it commits nothing either.
+// The walk (ngw_walk.inc) finds the shortest Forward / Left / Right walks from such rows to each item id: it commits nothing either.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -616,6 +617,34 @@ int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, i
     x.reward = reward_dev; x.done = done_dev; x.info = info_dev;
     x.count = count; x.rows = (int32_t)from.rows; x.fields = fields;
     HIP_TRY(ngw_successors_launch(h->dspec, &a, &x, h->ext, h->stream));
+    return NGW_OK;
+}
+
+int ngw_snapshot_walk(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, const int32_t* items_dev, int32_t n_steps, int32_t* dist_dev,
+                      int32_t* plans_dev, int32_t* length_dev) {
+    if (!h) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!items_dev && (plans_dev || length_dev)) return fail(NGW_E_INVALID_ARG, "walk plans without items: one item id per row expected");
+    if (!dist_dev && !plans_dev && !length_dev) return fail(NGW_E_INVALID_ARG, "walk without an output: nothing to do");
+    if (items_dev && n_steps < 1) return fail(NGW_E_INVALID_ARG, "walk plans of %d steps", (int)n_steps);
+    const Source from = source_of(h, s);
+    if (count < 0 || count > 0x7FFFFFFFll) return fail(NGW_E_INVALID_ARG, "walk of %lld rows", (long long)count);
+    if (!idx_dev && count > from.rows) return fail(NGW_E_INVALID_ARG, "walk of %lld rows from %lld %s", (long long)count, (long long)from.rows, from.unit);
+    // the ids a plan is written in: the lowest action id of each of the three kinds (a remapped action table keeps its kinds)
+    int32_t act[3] = {-1, -1, -1};
+    for (int a = h->spec.n_actions - 1; a >= 0; a--)
+        if (h->spec.act_kind[a] <= NGW_ACT_RIGHT) act[h->spec.act_kind[a]] = a;
+    if (plans_dev && (act[NGW_ACT_FORWARD] < 0 || act[NGW_ACT_LEFT] < 0 || act[NGW_ACT_RIGHT] < 0))
+        return fail(NGW_E_INVALID_ARG, "walk plans need a Forward, a Left and a Right action; this spec has no %s (the distances are available)",
+                    act[NGW_ACT_FORWARD] < 0 ? "Forward" : (act[NGW_ACT_LEFT] < 0 ? "Left" : "Right"));
+    if (int rc = enter(h)) return rc;                 // (s == NULL: the one-env loop has ended, HBM holds the env's state)
+    if (count == 0) return NGW_OK;
+    NgwWalk x{};
+    x.src = from.r; x.idx = idx_dev; x.items = items_dev; x.flags = h->b.flags;
+    x.dist = dist_dev; x.plans = plans_dev; x.length = length_dev;
+    x.count = count; x.rows = (int32_t)from.rows; x.S = h->proto.S; x.K = h->proto.K; x.T = items_dev ? n_steps : 0; x.SP = NGW_WALK_SP(h->proto.S);
+    x.act_forward = act[NGW_ACT_FORWARD]; x.act_left = act[NGW_ACT_LEFT]; x.act_right = act[NGW_ACT_RIGHT];
+    HIP_TRY(ngw_walk_launch(&x, h->stream));
     return NGW_OK;
 }
 

@@ -739,6 +739,34 @@ extern "C"
 #endif
 hipError_t ngw_successors_launch(const NgwDevSpec* dspec, const NgwLaunch* a, const struct NgwSuccessors* x, int ext, hipStream_t stream);
 
+/* Walk distances and go-to plans (ngw_walk.inc, ngw_abi_snapshot.cpp): for row j = row idx[j] of `src` (a snapshot or the state slab; a NULL list = j
+ * itself), dist[j * K + k] = the fewest Forward / Left / Right moves until the agent faces a cell of id k (-1: never) under the rule of include/ngw.h
+ * (ngw_snapshot_walk); with items != nullptr also length[j] = dist[j][items[j]] and plans[t * count + j] = move t of that walk for t < min(length, T), -1
+ * elsewhere (act_forward / act_left / act_right: the ids stored).  dist, and with items plans and length, may be nullptr.  An index outside [0, rows), or
+ * an item outside [0, K), is never used as an address: the row's outputs are all -1 and NGW_F_BAD_INDEX is raised in *flags.  Nothing but the three
+ * outputs and the flags word is stored.  One work-group - one wave - per row: grid = count. */
+struct NgwWalk {
+    NgwSnapRows src;
+    const int32_t* idx;
+    const int32_t* items;   /* [count], or nullptr: distances only (T, plans, length are then not read) */
+    uint32_t* flags;
+    int32_t* dist;          /* [count][K] */
+    int32_t* plans;         /* [T][count] */
+    int32_t* length;        /* [count] */
+    int64_t count;
+    int32_t rows, S, K, T;
+    int32_t SP;             /* NGW_WALK_SP(S) */
+    int32_t act_forward, act_left, act_right;
+};
+/* the row stride of the kernel's uint16 distance field: S rounded up to an even number of entries whose half is odd (lanes l and l + 1 then write
+ * the same column of their rows to different banks), and the dynamic LDS of a launch: the field [4][S][SP] and the map's S*S bytes as dwords */
+#define NGW_WALK_SP(S) (((((S) + 1) >> 1) | 1) << 1)
+#define NGW_WALK_LDS_BYTES(S) ((size_t)8 * (size_t)(S) * (size_t)NGW_WALK_SP(S) + (((size_t)(S) * (size_t)(S) + 3u) & ~(size_t)3))
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_walk_launch(const struct NgwWalk* x, hipStream_t stream);
+
 /* Key table (ngw_table.inc, ngw_abi_table.cpp): an open-addressing set of 64-bit keys in device memory.  key[] and stamp[] hold mask + 1 words
  * (a power of two); key 0 marks an empty bucket, a stamp is the smallest base + position that ever offered the bucket's key (all ones: none yet).
  * One insert is two launches: the probe places or finds keys[j], writes its bucket to where[j] (-1: key 0, or no bucket left - NGW_F_TABLE_FULL in

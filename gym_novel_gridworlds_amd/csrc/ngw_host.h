@@ -9,7 +9,7 @@
 //   ngw_abi_plans.cpp    plan evaluation: candidate action sequences scored from the current state without committing a step (ngw_plans.inc)
 //   ngw_abi_snapshot.cpp device-side snapshots: save / restore / fork env states by index (ngw_snapshot.inc), expand saved states into new slots (ngw_expand.inc),
 //                        roll action sequences out from saved states (ngw_slot_rollout.inc), observe saved states by slot (ngw_slot_observe.inc),
-//                        64-bit state keys of saved slots and live envs (ngw_keys.inc)
+//                        64-bit state keys of saved slots and live envs (ngw_keys.inc), walk distances and go-to plans of them (ngw_walk.inc)
 //   ngw_abi_table.cpp    device-side key tables: a hash set of such keys that outlives the call - insert, lookup, count, clear (ngw_table.inc)
 //
 // Three rules hold in all of them:

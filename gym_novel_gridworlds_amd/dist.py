@@ -183,6 +183,14 @@ class ShardedVecNovelGridworld:
         collective.  Keys are rank-independent, so the children's keys compare across ranks as the states' own keys do."""
         return self.local.successor_keys(envs, fields, device, reports)
 
+    def walk_distances(self, envs=None, device=False):
+        """The walk distances of this rank's shard (VecNovelGridworld.walk_distances): `envs` are the shard's own indices; rank-local, no collective."""
+        return self.local.walk_distances(envs, device)
+
+    def walk_plans(self, items, steps, envs=None, device=False):
+        """The go-to plans of this rank's shard (VecNovelGridworld.walk_plans): `envs` are the shard's own indices; rank-local, no collective."""
+        return self.local.walk_plans(items, steps, envs, device)
+
     def insert_successor_keys(self, table, envs=None, fields=KEY_STATE, device=False):
         """The successor keys of this rank's envs offered to `table` (VecNovelGridworld.insert_successor_keys)."""
         return self.local.insert_successor_keys(table, envs, fields, device)

@@ -370,6 +370,22 @@ class _NovelGridworldEnv(_EnvBase):
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
         return SuccessorKeys(*[None if x is None else x[0] for x in vec.successor_keys(fields=fields, device=device, reports=reports)])
 
+    def walk_distances(self):
+        """int32 [K]: the fewest Forward / Left / Right moves after which the agent faces a cell of each item id from the current state (0:
+        it does already, -1: no reachable pose does), computed on the device; see VecNovelGridworld.walk_distances and walk.py for the contract."""
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        return vec.walk_distances()[0]
+
+    def walk_plan(self, item, steps):
+        """(the first min(length, steps) action ids of the shortest walk that leaves the agent facing a cell of id `item`, its true length; ([], -1)
+        where no reachable pose faces one); see VecNovelGridworld.walk_plans."""
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        p = vec.walk_plans(int(item), steps)
+        length = int(p.length[0])
+        return [int(a) for a in p.plans[:max(min(length, int(steps)), 0), 0]], length
+
     def get_observation(self):
         assert not self.max_items < len(self.items), "Cannot have more than " + str(self.max_items) + " items"
         return {'map': self.map, 'agent_location': self.agent_location, 'agent_facing_id': self.agent_facing_id,

@@ -68,6 +68,12 @@ class NoveltyWrapper(object):
     def successor_keys(self, fields=KEY_STATE, device=False, reports=True):
         return self.env.successor_keys(fields=fields, device=device, reports=reports)
 
+    def walk_distances(self):
+        return self.env.walk_distances()
+
+    def walk_plan(self, item, steps):
+        return self.env.walk_plan(item, steps)
+
     def render(self, mode='human', **kwargs):
         return self.env.render(mode, **kwargs)
 

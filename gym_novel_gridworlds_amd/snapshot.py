@@ -995,6 +995,36 @@ class Snapshot:
         table._open_for(self.env)
         return insert_successors(self.successor_keys(slots, fields, device=True), table, device)
 
+    # ------------------------------------------------------------------ walk distances and go-to plans (include/ngw.h ngw_snapshot_walk; walk.py)
+    def walk_distances(self, slots=None, device=False):
+        """How far saved slots' agents are from facing each item: int32 [count, K], entry (j, k) the fewest Forward / Left / Right moves after
+        which the agent of slot slots[j] (None: every slot) faces a cell of id k - 0 where it faces one already, -1 where no reachable pose
+        does; air and wall are ordinary columns.  The public integer contract of include/ngw.h, which walk.shortest_walk() computes on the host
+        for the same state: a breadth-first search over (row, column, facing) of the saved map and pose under the BASE movement rules - the
+        map is static, no pickup and no novelty predicate enters, so under addjump, FireWall, fences and crates this is a geometric quantity,
+        not a promise about step().  An admissible heuristic for a best-first search over the pool, a shaping potential, a feature vector.
+        One kernel launch, one wavefront per row, at every map size up to 64 x 64; nothing is committed.
+        slots and device: as in lidar_observation (an index out of range in a device list: a row of -1, F_BAD_INDEX)."""
+        from .walk import walk_call
+        self._open()
+        return walk_call(self.env, self, self._s, slots, self.capacity, 'slots', None, 0, device, want_plans=False)
+
+    def walk_plans(self, slots, items, steps, device=False):
+        """The shortest walk of each saved slot's agent to the nearest cell of an item, as a plan: WalkPlans(plans int32 [steps, count], length
+        int32 [count], dist int32 [count, K]).  Column j of `plans` holds the first min(length[j], steps) moves - the env's Forward / Left /
+        Right ids - that leave the agent of slot slots[j] facing a cell of id items[j], -1 behind them: the layout and padding of
+        playout(record=True).actions, so rollout(slots, plans, limits=length.clamp(0, steps), children=c) with the tensors left on the device
+        applies the macro-action "go to the nearest X and face it" to every node in one more launch.  length[j] is the true distance, also
+        beyond `steps`, and -1 (a column of -1) where no reachable pose faces the item; dist is walk_distances() of the same rows.  Ties are
+        pinned by the contract (the goal pose with the smallest (distance, row, column, facing); walking back, the Forward predecessor before
+        the Left and the Right one).  items: an int (one id for all rows), a list / numpy array (checked: ValueError for an id outside
+        [0, K)) or a torch int32 tensor on the env's device (used in place: a bad id gives a row of -1 and F_BAD_INDEX).  A spec without a
+        Forward, a Left or a Right action raises ValueError; walk_distances() still serves it.  slots, device and the rule: as in
+        walk_distances().  One kernel launch; nothing is committed."""
+        from .walk import walk_call
+        self._open()
+        return walk_call(self.env, self, self._s, slots, self.capacity, 'slots', items, steps, device)
+
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""
         self._open()

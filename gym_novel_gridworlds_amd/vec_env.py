@@ -1048,6 +1048,20 @@ class VecNovelGridworld:
         from .snapshot import successor_keys_call
         return successor_keys_call(self, self._keeper(), None, envs, self.num_envs, 'envs', fields, device, reports)
 
+    def walk_distances(self, envs=None, device=False):
+        """How far the envs' agents are from facing each item in their CURRENT states: int32 [count, K] - Snapshot.walk_distances() without
+        the save (the contract: include/ngw.h ngw_snapshot_walk, walk.shortest_walk on the host).  envs as in state_keys() (an index out of
+        range in a device list: a row of -1, F_BAD_INDEX).  One kernel launch; nothing is committed."""
+        from .walk import walk_call
+        return walk_call(self, self._keeper(), None, envs, self.num_envs, 'envs', None, 0, device, want_plans=False)
+
+    def walk_plans(self, items, steps, envs=None, device=False):
+        """The shortest walk of each env's agent from its CURRENT state to the nearest cell of items[j], as a plan: Snapshot.walk_plans()
+        without the save - WalkPlans(plans [steps, count], length [count], dist [count, K]).  items, steps and device as there, envs as in
+        state_keys().  One kernel launch; nothing is committed."""
+        from .walk import walk_call
+        return walk_call(self, self._keeper(), None, envs, self.num_envs, 'envs', items, steps, device)
+
     def insert_successor_keys(self, table, envs=None, fields=KEY_STATE, device=False):
         """successor_keys(envs, fields) offered to `table` (a KeyTable of this env): Snapshot.insert_successor_keys() for the envs' CURRENT
         states."""

@@ -152,6 +152,13 @@ class LimitActions(NoveltyWrapper):
             return out
         return SuccessorKeys(*[cols(x) for x in t])
 
+    def walk_plan(self, item, steps):
+        """The env's walk_plan in the limited id space: every Forward / Left / Right id of the plan as this wrapper numbers it.  ValueError if
+        Forward, Left or Right is not among the limited actions.  (walk_distances() does not depend on the action id space: passed through.)"""
+        ids = limit_walk_ids(self.limited_actions_id, self.actions_id)
+        plan, length = self.env.walk_plan(item, steps)
+        return [ids[a] for a in plan], length
+
     def _limited_env(self):
         """-> (the one-env batched env whose action table is this wrapper's list - limit_actions_vec, kept from call to call - holding a copy
         of the adapter's current state, this wrapper's id of each of its actions): what playouts() and sample_action() run on."""
@@ -256,6 +263,17 @@ def limit_plan_ids(plans, limited_actions_id, actions_id, n, env_id=''):
         assert ids[i] is not None, _NOT_AN_ACTION.format(name=name, env_id=env_id)
         out[plans == i] = ids[i]
     return out
+
+
+def limit_walk_ids(limited_actions_id, actions_id):
+    """{the env's id: LimitActions' id} of Forward, Left and Right - what a walk plan written in the env's ids is translated with.  ValueError
+    where one of the three is not among the limited actions (or the env does not know it)."""
+    ids = {}
+    for name in ('Forward', 'Left', 'Right'):
+        if name not in limited_actions_id or name not in actions_id:
+            raise ValueError("walk_plan: %s is not among the limited actions %s" % (name, sorted(limited_actions_id)))
+        ids[actions_id[name]] = limited_actions_id[name]
+    return ids
 
 
 def limit_column_ids(limited_actions_id, actions_id, n, width):

@@ -45,7 +45,7 @@ extern "C" {
 /* device-side sticky error flags (ngw_error_flags) */
 #define NGW_F_INVALID_ACTION 1u
 #define NGW_F_PLACEMENT 2u
-#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout / ngw_snapshot_playout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros); ngw_state_keys: a row index outside its range (that key is 0) */
+#define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout / ngw_snapshot_playout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros); ngw_state_keys: a row index outside its range (that key is 0); ngw_snapshot_walk: a row index or an item id outside its range (that row is all -1) */
 #define NGW_F_TABLE_FULL 8u     /* ngw_key_table_insert: a key found neither itself nor a free bucket after probing every bucket (it was refused: where = -1, fresh = 0) */
 #define NGW_F_BAD_WEIGHT 16u    /* ngw_sample_actions / ngw_snapshot_playout_weighted: a weight that is negative, NaN or above 2^64 (it counted as 0) */
 
@@ -681,6 +681,51 @@ int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64
  * the call cannot hold. */
 int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev, int32_t* reward_dev,
                        uint8_t* done_dev, uint32_t* info_dev);
+
+/* Walk distances and go-to plans: "how many primitive steps until the agent can face item k, and which ones?" - the macro-action "go to the nearest
+ * X and face it" for ngw_snapshot_rollout, an admissible heuristic for a best-first search over a node pool, a shaping potential, a feature vector.
+ * The quantity is a public integer contract, defined on the saved state alone - the map bytes and the pose - under the BASE movement rules:
+ *   facing:  NORTH 0, SOUTH 1, WEST 2, EAST 3;    dr = {-1, 1, 0, 0}, dc = {0, 0, -1, 1};    left = {2, 3, 1, 0}, right = {3, 2, 0, 1}
+ *   A pose is (r, c, f).  Three moves, each of cost 1:
+ *     Forward  (r, c, f) -> (r + dr[f], c + dc[f], f)   if and only if that cell lies inside the map and holds id 0
+ *     Left     (r, c, f) -> (r, c, left[f])             Right    (r, c, f) -> (r, c, right[f])
+ *   D(p) = the breadth-first distance of pose p from the agent's pose (agent_location, agent_facing_id) over these moves; D(agent's pose) = 0
+ *   whatever the agent's own cell holds.  The map is static: no pickup, no novelty predicate enters the rule, so under a Jump action or a
+ *   FireWall / FenceRestriction / Crate predicate this is a geometric quantity, not a promise about what step() does.
+ *   front(p) = the id of the cell (r + dr[f], c + dc[f]); a pose whose front cell lies outside the map has none.
+ *   dist[k], for every item id k in [0, n_items) - air 0 and wall are ordinary columns - = min D(p) over the reachable poses with front(p) == k:
+ *     0 when the agent already faces a k cell, -1 when no reachable pose faces one.
+ *   goal(k) = the reachable pose with front(p) == k that minimises the tuple (D, r, c, f) lexicographically.
+ *   path(k): walk back from q = goal(k) to the agent's pose.  At a pose q = (r, c, f) with D(q) = d > 0 take the FIRST of these predecessors p:
+ *     1. the Forward predecessor p = (r - dr[f], c - dc[f], f), if p lies inside the map, is reachable with D(p) = d - 1, and Forward leads from p to
+ *        q (q's cell holds id 0 - every pose with d > 0 outside the agent's own cell does);
+ *     2. the pose that reaches q by Left, p = (r, c, right[f]), if D(p) = d - 1;
+ *     3. the pose that reaches q by Right, p = (r, c, left[f]) (then D(p) = d - 1: q has a predecessor in layer d - 1).
+ *     and continue from p.  The plan is the moves taken, reversed: the first move leaves the agent's pose, the last one arrives at goal(k).
+ *   The ids a plan is written in are the LOWEST action id whose act_kind is NGW_ACT_FORWARD, NGW_ACT_LEFT and NGW_ACT_RIGHT respectively, so a
+ *   remapped action table is honoured.
+ * For j < count, with K = n_items and T = n_steps:
+ *     dist_dev[j * K + k]        (int32, NULL or [count][K])  = dist[k] of row idx[j]
+ *     length_dev[j]              (int32, NULL or [count])     = dist[items_dev[j]]: the TRUE length, also beyond T
+ *     plans_dev[t * count + j]   (int32, NULL or [T][count])  = move t of path(items_dev[j]) for t < min(length, T), -1 elsewhere - the step-major layout
+ *                                and the padding of ngw_snapshot_playout's actions_dev, which ngw_snapshot_rollout reads as actions_dev with
+ *                                pair_stride = count.  A path longer than T gives its first T moves; an unreachable item a column of -1.
+ * What gives this its value: on a configuration whose Forward is the base rule, ngw_snapshot_rollout_path of these plans with limits = length clamped
+ * to [0, T] leaves child j facing a cell of id items_dev[j] after exactly length[j] steps, each with result == true.
+ * `s`, idx_dev, count and the index rules are ngw_state_keys': s == NULL means the envs' current states; idx_dev is an int32 list in DEVICE memory,
+ * NULL means 0 .. count-1 (count may then not exceed the row count); rows may repeat and count is otherwise not bound by the row count.  items_dev is
+ * an int32 list in DEVICE memory, one item id per row; NULL asks for the distances alone (plans_dev and length_dev must then be NULL, n_steps is not
+ * read) and skips the walk back.  An index outside [0, rows), or an item outside [0, n_items), is never used as an address: every output of that row
+ * is -1 (its K distances, its length, its column of plans) and the sticky NGW_F_BAD_INDEX is raised.  Exactly the ranges above are written.
+ * ONE kernel launch (ngw_walk.inc), enqueued on the handle's stream; it does not wait.  One wavefront serves one row and stages that one map, so it
+ * works at every map size up to 64 x 64 within the default 64 KiB of LDS.  count == 0 is a no-op.
+ * Nothing is committed, as for ngw_state_keys: no env, slot, mask, lookahead table, mirror or prepared episode changes, and a captured graph
+ * stays valid.
+ * NGW_E_INVALID_ARG: a NULL handle; no output pointer at all; a snapshot that is not an open snapshot of this handle; count < 0 or beyond 2^31 - 1;
+ * idx_dev == NULL with count above the row count; plans_dev or length_dev without items_dev; items_dev with n_steps < 1; plans_dev on a spec that lacks
+ * a Forward, a Left or a Right action (the distances are still served). */
+int ngw_snapshot_walk(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, const int32_t* items_dev, int32_t n_steps, int32_t* dist_dev,
+                      int32_t* plans_dev, int32_t* length_dev);
 
 /* Playouts: "from this node, play n_steps steps of a random policy and report what happened" - the default-policy simulation of MCTS, flat
  * Monte-Carlo and Go-Explore.  The policy is uniform over the actions that WOULD SUCCEED from the state the pair is in at that step, which
