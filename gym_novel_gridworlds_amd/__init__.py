@@ -8,11 +8,12 @@ reference's gym.Env surface.  Everything computes in hand-written HIP kernels re
     venv = gym_novel_gridworlds_amd.VecNovelGridworld('NovelGridworld-Pogostick-v1', num_envs=65536)
 """
 from .envs import ENTRY_POINTS, BowV0Env, BowV1Env, PogostickV0Env, PogostickV1Env, make   # noqa: F401
+from .frontier import Frontier, alloc_reference, compact_reference   # noqa: F401
 from .key_table import KeyInsert, KeyTable                           # noqa: F401
 from .novelty import NOVELTY_NAMES, apply_novelty                    # noqa: F401
 from .novelty_wrappers import inject_novelty                         # noqa: F401
 from .observation_wrappers import AgentMap, LidarInFront                    # noqa: F401
-from .spec import ENV_IDS, STEP_COSTS, EnvSpec, make_spec            # noqa: F401
+from .spec import ENV_IDS, IDX_NONE, STEP_COSTS, EnvSpec, make_spec  # noqa: F401
 from .state_keys import (KEY_ALL, KEY_EPISODE, KEY_INV, KEY_MAP, KEY_POSE, KEY_SELECTED, KEY_STATE, KEY_STEP_COUNT,   # noqa: F401
                          keys_of_rows)
 from .vec_env import VecNovelGridworld                               # noqa: F401

@@ -32,7 +32,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_snapshot_playout_weighted', 'ngw_sample_actions', 'ngw_snapshot_rollout_path', 'ngw_snapshot_playout_path',
            'ngw_snapshot_rollout_traj', 'ngw_snapshot_playout_traj', 'ngw_snapshot_rollout_traj_views', 'ngw_snapshot_playout_traj_views', 'ngw_snapshot_playout_guided',
            'ngw_key_table_create', 'ngw_key_table_destroy', 'ngw_key_table_clear', 'ngw_key_table_insert', 'ngw_key_table_lookup', 'ngw_key_table_count',
-           'ngw_snapshot_walk', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
+           'ngw_snapshot_walk', 'ngw_frontier_compact', 'ngw_frontier_alloc', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
 _lib = None
@@ -206,6 +206,9 @@ def lib():
         L.ngw_successor_keys.argtypes = [vp, vp, vp, i64, C.c_uint32, vp, vp, vp, vp]
     if hasattr(L, 'ngw_snapshot_walk'):
         L.ngw_snapshot_walk.argtypes = [vp, vp, vp, i64, vp, i32, vp, vp, vp]
+    if hasattr(L, 'ngw_frontier_compact'):
+        L.ngw_frontier_compact.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp, vp]
+        L.ngw_frontier_alloc.argtypes = [vp, vp, vp, i32, i64, vp]
     if hasattr(L, 'ngw_snapshot_copy'):
         L.ngw_snapshot_copy.argtypes = [vp, vp, vp, vp, vp, i64]
     if hasattr(L, 'ngw_key_table_create'):

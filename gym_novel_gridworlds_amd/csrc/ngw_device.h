@@ -793,4 +793,44 @@ extern "C"
 #endif
 hipError_t ngw_table_lookup_launch(const struct NgwTable* x, hipStream_t stream);
 
+/* Frontiers (ngw_frontier.inc, ngw_abi_frontier.cpp): flags -> an index list of fixed capacity, and slots for it, without the host knowing how many.
+ * Compaction: the positions p with bytes[p] != 0 in ascending order, the k-th of them to first[k] = (map ? map[p / div] : p / div) and second[k] =
+ * p % div for k < min(total, capacity), NGW_IDX_NONE behind them up to capacity, count[0] = the entries written, count[1] = total; total > capacity
+ * raises NGW_F_FRONTIER_FULL in *flags.  Two launches: the count of every tile of NGW_FRONTIER_TILE bytes to tiles[0 .. n_tiles), then the scatter,
+ * in which every work-group sums the tiles before its own (and all of them) itself.  Nothing else is stored. */
+struct NgwFrontier {
+    const uint8_t* bytes;   /* [n] */
+    const int32_t* map;     /* [ceil(n / div)], or nullptr: the identity */
+    int32_t* first;         /* [capacity] */
+    int32_t* second;        /* [capacity], or nullptr */
+    int32_t* count;         /* [2] */
+    int32_t* tiles;         /* [n_tiles]: the handle's scratch */
+    uint32_t* flags;
+    int64_t n, capacity;
+    int32_t div, n_tiles;
+};
+/* Slot allocation: c = *cursor, m = max(min(count[0], limit - c), 0); slots[k] = c + k for k < m and NGW_IDX_NONE for m <= k < capacity; *cursor = c + m,
+ * written by the work-group that takes the last ticket - after every work-group has read it -, which also puts *ticket back to 0; m < count[0]
+ * raises NGW_F_FRONTIER_FULL. */
+struct NgwFrontierAlloc {
+    const int32_t* count;
+    int32_t* cursor;
+    int32_t* slots;         /* [capacity] */
+    uint32_t* ticket;       /* one word of the handle's scratch, 0 between the calls */
+    uint32_t* flags;
+    int64_t capacity;
+    int32_t limit;
+};
+#define NGW_FRONTIER_BLOCK 256                         /* threads per workgroup: four waves, 16 flag bytes per lane */
+#define NGW_FRONTIER_TILE (16 * NGW_FRONTIER_BLOCK)    /* flag bytes per workgroup */
+#define NGW_FRONTIER_MAX_FLAGS (1ll << 24)             /* the longest flag array of one call: 4096 tiles, whose counts every work-group of the scatter sums */
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_frontier_compact_launch(const struct NgwFrontier* x, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_frontier_alloc_launch(const struct NgwFrontierAlloc* x, hipStream_t stream);
+
 #endif

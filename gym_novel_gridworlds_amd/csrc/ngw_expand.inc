@@ -82,7 +82,11 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_expand_kernel(const NgwDevSpec* _
         action = x.actions[pair];
     }
     const bool ok = inside && (uint32_t)si < (uint32_t)x.src_rows && (uint32_t)di < (uint32_t)x.dst_rows;
-    uint32_t flags = (inside && !ok) ? NGW_F_BAD_INDEX : 0u;
+    uint32_t flags = (inside && !ok && si != NGW_IDX_NONE && di != NGW_IDX_NONE) ? NGW_F_BAD_INDEX : 0u;   // (NGW_IDX_NONE: a pair that is not there)
+    if (__ballot(ok) == 0) {                                                       // no live pair in this wave - a frontier's padding: nothing to stage
+        if (flags) atomicOr(a.b.flags, flags);
+        return;
+    }
     const int sic = ok ? si : 0, dic = ok ? di : -1;
     const int2 rc = reinterpret_cast<const int2*>(x.src.loc)[sic];
     int r = rc.x, c = rc.y;

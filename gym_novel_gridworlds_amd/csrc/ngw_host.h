@@ -11,6 +11,7 @@
 //                        roll action sequences out from saved states (ngw_slot_rollout.inc), observe saved states by slot (ngw_slot_observe.inc),
 //                        64-bit state keys of saved slots and live envs (ngw_keys.inc), walk distances and go-to plans of them (ngw_walk.inc)
 //   ngw_abi_table.cpp    device-side key tables: a hash set of such keys that outlives the call - insert, lookup, count, clear (ngw_table.inc)
+//   ngw_abi_frontier.cpp device-side frontiers: flags compacted into index lists of fixed capacity, slots handed out for them (ngw_frontier.inc)
 //
 // Three rules hold in all of them:
 //   1. Guard first.  An entry point that uses the handle's stream or its device state starts with `if (int rc = enter(h)) return rc;`
@@ -226,6 +227,10 @@ struct ngw_handle {
     int plan_major = 0;                   // NGW_PLAN_ORDER=plan when the buffers were first allocated: the plan-major block order (A/B, tools/plan_cost.py)
     std::vector<ngw_snapshot*> snaps;     // open snapshots (ngw_snapshot_create); their slabs are in `allocs`, ngw_destroy deletes what is left
     std::vector<ngw_key_table*> tables;   // open key tables (ngw_key_table_create); likewise
+    // Frontiers (ngw_abi_frontier.cpp): the scratch of ngw_frontier_compact / ngw_frontier_alloc, allocated on first use and regrown when a call
+    // brings more tiles - word 0 the allocation's ticket (0 between the calls), the tile counts behind it
+    int32_t* frontier_scratch = nullptr;
+    int64_t frontier_tiles = 0;
     long long solo_starts = 0;           // launches of the one-env resident loop (ngw_debug_solo_starts)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;

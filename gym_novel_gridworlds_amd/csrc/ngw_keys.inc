@@ -115,7 +115,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_keys_kernel(const NgwKeys x) {
     }
     // ---- 4. lane l holds key l
     if (inside) x.keys[pair] = ok ? key : 0ull;
-    if (inside && !ok) atomicOr(x.flags, NGW_F_BAD_INDEX);
+    if (inside && !ok && si != NGW_IDX_NONE) atomicOr(x.flags, NGW_F_BAD_INDEX);   // (NGW_IDX_NONE: a row that is not there)
 }
 
 }  // namespace

@@ -71,7 +71,37 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_playout_kernel(const NgwDevSpec* 
         di = x.di ? x.di[pair] : (int)pair;
     }
     const bool ok = inside && (uint32_t)si < (uint32_t)x.src_rows && (!keep || (uint32_t)di < (uint32_t)x.dst_rows);
-    uint32_t flags = (inside && !ok) ? NGW_F_BAD_INDEX : 0u;
+    uint32_t flags = (inside && !ok && si != NGW_IDX_NONE && di != NGW_IDX_NONE) ? NGW_F_BAD_INDEX : 0u;   // (NGW_IDX_NONE: a pair that is not there)
+    if (__ballot(ok) == 0) {                                                       // no live pair in this wave - a frontier's padding: nothing to stage,
+        const int T = x.n_steps;                                                   // every step is one no pair executed
+        if constexpr (PATH)
+            if (x.keys && inside)
+                for (int s = 0; s < T; s++) x.keys[pair + (int64_t)s * x.keys_stride] = 0ull;
+        if constexpr (TRAJ) {
+            if (x.rewards && inside)
+                for (int s = 0; s < T; s++) x.rewards[pair + (int64_t)s * x.rewards_stride] = 0;
+            if (x.masks && inside)
+                for (int s = 0; s < T; s++) x.masks[pair + (int64_t)s * x.masks_stride] = 0ull;
+            if (x.obs) traj_zero_tiles(a, tid, x.obs, x.obs_stride, -1, T);              // (from -1: row block 0, the parents, too)
+            if (traj_views_on(x.vw)) traj_zero_views(a, x.vw, tid, -1, T);
+        }
+        if constexpr (GUIDED) {
+            if (x.where && inside)
+                for (int s = 0; s < T; s++) x.where[pair + (int64_t)s * x.where_stride] = -1;
+            if (x.depth && inside) x.depth[pair] = 0;
+        }
+        if (inside) {
+            if (x.actions)
+                for (int s = 0; s < T; s++) x.actions[pair + (int64_t)s * x.stride] = -1;
+            if (x.ret) x.ret[pair] = 0;
+            if (x.length) x.length[pair] = 0;
+            if (x.ended) x.ended[pair] = (uint8_t)0;
+            if (x.info) x.info[pair] = 0u;
+            if (x.first_action) x.first_action[pair] = -1;
+        }
+        if (flags) atomicOr(a.b.flags, flags);
+        return;
+    }
     const int sic = ok ? si : 0, dic = ok ? di : -1;
     const int2 rc = reinterpret_cast<const int2*>(x.src.loc)[sic];
     int r = rc.x, c = rc.y;

@@ -72,7 +72,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_sample_kernel(const NgwDevSpec* _
     int si = 0;
     if (inside) si = x.idx ? x.idx[pair] : (int)pair;
     const bool ok = inside && (uint32_t)si < (uint32_t)x.rows;
-    uint32_t flags = (inside && !ok) ? NGW_F_BAD_INDEX : 0u;
+    uint32_t flags = (inside && !ok && si != NGW_IDX_NONE) ? NGW_F_BAD_INDEX : 0u;   // (NGW_IDX_NONE: a pair that is not there)
     const LeanLane l = lean_gather_lane(x.src, ok ? si : 0, ok, S, K, inv_lds);
     auto cell_at = [&](int cell) -> int { return (int)ldg<int8_t>(l.bmap, l.mapoff + (uint32_t)cell); };
     const int A = min((int)dspec->u.n_actions, NGW_MAX_ACTIONS);                   // the walks' bound: a scalar

@@ -32,6 +32,14 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_lidar_kernel(const NgwLaunch
     int si = 0;
     if (inside) si = x.slots ? x.slots[pair] : (int)pair;
     const bool ok = inside && (uint32_t)si < (uint32_t)x.rows;
+    const bool bad = inside && !ok && si != NGW_IDX_NONE;                          // (NGW_IDX_NONE: a pair that is not there)
+    if (__ballot(ok) == 0) {                                                       // no live pair in this wave - a frontier's padding: a tile of zeros, nothing to stage
+        const int npc = 4 * a.l_rb;                                                // 64 rows = 4 * rb pieces of 16 B
+        GLOBAL_AS u32x4* g4 = (GLOBAL_AS u32x4*)(reinterpret_cast<char*>(a.lout) + (uint64_t)blockIdx.x * (uint32_t)(EPB * a.l_rb));
+        for (int p = (int)tid; p < npc; p += EPB) g4[p] = u32x4{0u, 0u, 0u, 0u};
+        if (bad) atomicOr(x.flags, NGW_F_BAD_INDEX);
+        return;
+    }
     const int sic = ok ? si : 0;
     uint32_t it = 0;
     if (tid < LIDAR_ITEM_DW) it = reinterpret_cast<const uint32_t*>(a.lcfg->chan_of_item)[tid];
@@ -41,7 +49,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_lidar_kernel(const NgwLaunch
     int32_t* const lds_inv = reinterpret_cast<int32_t*>(lds + a.off_inv);
     if (tid < LIDAR_ITEM_DW) lds[a.off_litem + tid] = it;
     expand_rows_in<VEC>(x.src, sic, lds_map, lds_inv, a.MS >> 2, a.KP, S2, K, tid);
-    if (inside && !ok) atomicOr(x.flags, NGW_F_BAD_INDEX);
+    if (bad) atomicOr(x.flags, NGW_F_BAD_INDEX);
     const int8_t* mp = reinterpret_cast<const int8_t*>(lds_map) + tid * a.MS;
     lidar_epilogue(a, lds, tid, ok, mp + rc.x * S + rc.y, f, lds_inv + tid * a.KP);   // (its first barrier makes the staging visible)
 }
@@ -61,7 +69,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_slot_mask_kernel(const NgwDevSpec
     auto cell_at = [&](int cell) -> int { return (int)ldg<int8_t>(l.bmap, l.mapoff + (uint32_t)cell); };
     const uint64_t mask = lane_mask<EXT>(dspec, S, K, l.r, l.c, l.f, l.sel, l.inv, cell_at);
     if (inside) out[pair] = l.live ? mask : 0ull;
-    if (inside && !ok) atomicOr(x.flags, NGW_F_BAD_INDEX);
+    if (inside && !ok && si != NGW_IDX_NONE) atomicOr(x.flags, NGW_F_BAD_INDEX);   // (NGW_IDX_NONE: a pair that is not there)
 }
 
 // ---------------------------------------------------------------- AgentMap windows, facing, inventory
@@ -77,7 +85,7 @@ __global__ __launch_bounds__(256) void ngw_slot_view_kernel(const NgwSlotObs x) 
         for (uint32_t j = t0; j < count; j += stride) {
             const int si = x.slots ? x.slots[j] : (int)j;
             const bool ok = (uint32_t)si < (uint32_t)x.rows;
-            if (!ok) atomicOr(x.flags, NGW_F_BAD_INDEX);
+            if (!ok && si != NGW_IDX_NONE) atomicOr(x.flags, NGW_F_BAD_INDEX);     // (NGW_IDX_NONE: a pair that is not there)
             const int v = x.src.facing[ok ? si : 0];
             if (x.facing) x.facing[j] = ok ? v : 0;
         }

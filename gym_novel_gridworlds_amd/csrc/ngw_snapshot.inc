@@ -35,7 +35,7 @@ __global__ void __launch_bounds__(NGW_SNAP_BLOCK) ngw_snapshot_kernel(const NgwS
     if (j >= a.count) return;
     const int si = a.si ? a.si[j] : j, di = a.di ? a.di[j] : j;
     if ((uint32_t)si >= (uint32_t)a.src_rows || (uint32_t)di >= (uint32_t)a.dst_rows) {
-        if (g == 0) atomicOr(a.flags, NGW_F_BAD_INDEX);
+        if (g == 0 && si != NGW_IDX_NONE && di != NGW_IDX_NONE) atomicOr(a.flags, NGW_F_BAD_INDEX);   // (NGW_IDX_NONE: a pair that is not there)
         return;
     }
     const int S2 = a.S2, K = a.K;

@@ -68,7 +68,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_successors_kernel(const NgwDevSpe
     int si = 0;
     if (inside) si = x.idx ? x.idx[pair] : (int)pair;
     const bool ok = inside && (uint32_t)si < (uint32_t)x.rows;
-    uint32_t flags = (inside && !ok) ? NGW_F_BAD_INDEX : 0u;
+    uint32_t flags = (inside && !ok && si != NGW_IDX_NONE) ? NGW_F_BAD_INDEX : 0u;   // (NGW_IDX_NONE: a parent that is not there)
     const int sic = ok ? si : 0;
     const int2 rc = reinterpret_cast<const int2*>(x.src.loc)[sic];
     const int r = rc.x, c = rc.y;
@@ -80,6 +80,18 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_successors_kernel(const NgwDevSpe
     NgwStepU U;
     NgwExtU X;
     lean_fetch_uniforms<EXT>(dspec, U, X);
+    if (__ballot(ok) == 0) {                                                       // no live parent in this wave - a frontier's padding: rows of zeros, nothing to stage
+        const int A0 = min(U.n_actions, NGW_MAX_ACTIONS);
+        if (inside)
+            for (int act = 0; act < A0; act++) {
+                x.keys[pair * (int64_t)A0 + act] = 0ull;
+                if (x.reward) x.reward[pair * (int64_t)A0 + act] = 0;
+                if (x.done) x.done[pair * (int64_t)A0 + act] = (uint8_t)0;
+                if (x.info) x.info[pair * (int64_t)A0 + act] = 0u;
+            }
+        if (flags) atomicOr(a.b.flags, flags);
+        return;
+    }
     // ---- 2. the 64 parent rows into the pristine region
     const int MSdw = a.MS >> 2, KP = a.KP;
     const int region = EPB * (MSdw + KP);                                          // dwords

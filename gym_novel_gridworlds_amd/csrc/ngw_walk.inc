@@ -73,7 +73,7 @@ __global__ void __launch_bounds__(NGW_EPB) ngw_walk_kernel(const NgwWalk x) {
                 for (int t = lane; t < T; t += EPB) x.plans[(int64_t)t * x.count + j] = -1;
             if (x.length && lane == 0) x.length[j] = -1;
         }
-        if (lane == 0) atomicOr(x.flags, NGW_F_BAD_INDEX);
+        if (lane == 0 && si != NGW_IDX_NONE && item != NGW_IDX_NONE) atomicOr(x.flags, NGW_F_BAD_INDEX);   // (NGW_IDX_NONE: a row that is not there)
         return;
     }
     const int2 rc = reinterpret_cast<const int2*>(x.src.loc)[si];

@@ -1025,6 +1025,15 @@ class Snapshot:
         self._open()
         return walk_call(self.env, self, self._s, slots, self.capacity, 'slots', items, steps, device)
 
+    # ------------------------------------------------------------------ device-side frontiers (include/ngw.h ngw_frontier_*; frontier.py)
+    def frontier(self, capacity):
+        """A Frontier of `capacity` entries for this snapshot: index lists padded with IDX_NONE and a slot cursor on the device, so that
+        `fresh` flags become the parents, actions and child slots of the next expand() without the host learning how many there are
+        (frontier.py).  Every call that takes a device index list skips a pair whose index is IDX_NONE and raises no F_BAD_INDEX for it."""
+        from .frontier import Frontier
+        self._open()
+        return Frontier(self, capacity)
+
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""
         self._open()

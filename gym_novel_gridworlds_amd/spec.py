@@ -38,7 +38,8 @@ ACT_FORWARD, ACT_LEFT, ACT_RIGHT, ACT_BREAK, ACT_PLACE, ACT_EXTRACT, ACT_CRAFT, 
  MSG_EXTRACT_NO_SRC, MSG_EXTRACT_NOT_NEAR, MSG_MISSING_ITEMS, MSG_NEED_TABLE, MSG_CRAFTED, MSG_NEED_AXE,
  MSG_CANNOT_CHOP, MSG_FENCE_RESTRICTION, MSG_FIRE_WALL) = range(15)
 
-F_INVALID_ACTION, F_PLACEMENT, F_BAD_INDEX, F_TABLE_FULL, F_BAD_WEIGHT = 1, 2, 4, 8, 16
+F_INVALID_ACTION, F_PLACEMENT, F_BAD_INDEX, F_TABLE_FULL, F_BAD_WEIGHT, F_FRONTIER_FULL = 1, 2, 4, 8, 16, 32
+IDX_NONE = -(1 << 31)         # include/ngw.h NGW_IDX_NONE: a pair that is not there (device index lists)
 
 DIRECTION_ID = {'NORTH': 0, 'SOUTH': 1, 'WEST': 2, 'EAST': 3}     # pogostick_v1_env.py:33
 DIRECTION_STR = ['NORTH', 'SOUTH', 'WEST', 'EAST']

@@ -48,6 +48,17 @@ extern "C" {
 #define NGW_F_BAD_INDEX 4u      /* ngw_snapshot_save / ngw_snapshot_restore / ngw_snapshot_expand / ngw_snapshot_rollout / ngw_snapshot_playout: an env or slot index outside its range (that copy / pair was skipped); ngw_snapshot_lidar / ngw_snapshot_agent_view / ngw_snapshot_action_mask: a slot index outside its range (that output row is all zeros); ngw_state_keys: a row index outside its range (that key is 0); ngw_snapshot_walk: a row index or an item id outside its range (that row is all -1) */
 #define NGW_F_TABLE_FULL 8u     /* ngw_key_table_insert: a key found neither itself nor a free bucket after probing every bucket (it was refused: where = -1, fresh = 0) */
 #define NGW_F_BAD_WEIGHT 16u    /* ngw_sample_actions / ngw_snapshot_playout_weighted: a weight that is negative, NaN or above 2^64 (it counted as 0) */
+#define NGW_F_FRONTIER_FULL 32u /* ngw_frontier_compact: more flags set than the list has room for (the first `capacity` of them were kept); ngw_frontier_alloc: fewer slots left below the limit than were asked for (the entries behind them are NGW_IDX_NONE) */
+
+/* A pair that is not there.  Every call that gathers rows through an index list in DEVICE memory - ngw_snapshot_save / _restore / _copy / _expand /
+ * _rollout* / _playout*, ngw_snapshot_lidar / _agent_view / _action_mask, ngw_state_keys, ngw_successor_keys, ngw_sample_actions, ngw_snapshot_walk - skips
+ * pair j when ANY of its indices (the source row, the destination row, the walk's item) is NGW_IDX_NONE: it stores for that pair exactly what it stores
+ * for a pair with an index out of range - nothing, zeros, action -1, key 0, distance -1, as the call says - and does NOT raise NGW_F_BAD_INDEX.  Every
+ * other value outside the range (-1, the row count, 2^31 - 1, ...) raises the flag as before.  It is how a list of fixed capacity carries fewer
+ * pairs than it has entries: ngw_frontier_compact and ngw_frontier_alloc pad their lists with it.  Key 0 is what a skipped pair's key reads, and key 0
+ * is never stored by ngw_key_table_insert (where = -1, fresh = 0, no flag): a padded list goes through keys -> insert with no special case.
+ * Lists checked on the host are not device lists: their range check stands. */
+#define NGW_IDX_NONE INT32_MIN
 
 /* action kinds (act_kind[]); act_arg[] = recipe index (CRAFT) or item id (SELECT) */
 enum { NGW_ACT_FORWARD = 0, NGW_ACT_LEFT = 1, NGW_ACT_RIGHT = 2, NGW_ACT_BREAK = 3, NGW_ACT_PLACE = 4,
@@ -958,6 +969,33 @@ int ngw_key_table_clear(ngw_handle* h, ngw_key_table* t);
 int ngw_key_table_insert(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_dev, int64_t count, int32_t* where_dev, uint8_t* fresh_dev);
 int ngw_key_table_lookup(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_dev, int64_t count, int32_t* where_dev);
 int ngw_key_table_count(ngw_handle* h, ngw_key_table* t, int64_t* n);
+
+/* Frontiers: the step `flags -> the index lists of the next call` of a search loop (expand -> keys -> insert -> next frontier), on the device.  The
+ * number of hits stays in device memory: the lists have a fixed `capacity`, the live entries come first and NGW_IDX_NONE (above) pads the rest, so
+ * the next call is launched at `capacity` and skips what is not there.  Nothing waits for the host, and a loop built on these two calls can be
+ * enqueued ahead of time.
+ * ngw_frontier_compact: let p_0 < p_1 < ... be the positions p in [0, n) with flags_dev[p] != 0 - ANY non-zero byte counts, 0x80 as well as 1 -,
+ * total their number and taken = min(total, capacity).  Then
+ *     first_dev[k]  (int32)            = map_dev ? map_dev[p_k / div] : p_k / div        for k < taken
+ *     second_dev[k] (int32, or NULL)   = p_k % div                                       for k < taken
+ *     first_dev[k] = second_dev[k]     = NGW_IDX_NONE                                    for taken <= k < capacity
+ *     count_dev[0] = taken, count_dev[1] = total   (int32 [2])
+ * and total > capacity raises the sticky NGW_F_FRONTIER_FULL.  The order is ascending and deterministic: the row-major order of a [rows, div] flag
+ * array, so `first` is the row (through map_dev: the parent slot of that row) and `second` the column (the action).  Exactly [0, capacity) of the
+ * lists and the two counts are written.  flags_dev (uint8 [n]) and map_dev (int32, at least ceil(n / div) entries, NULL: the identity) are DEVICE
+ * memory and are only read; n in [0, 2^24], div >= 1, capacity in [0, 2^31 - 1].  n == 0 fills the lists with NGW_IDX_NONE and stores two zeros.
+ * Two kernel launches (ngw_frontier.inc: the hits of every tile of 4096 flags, then the scatter), integer arithmetic only, no atomic orders the output.
+ * ngw_frontier_alloc: let c = *cursor_dev and m = max(min(count_dev[0], limit - c), 0).  Then
+ *     slots_dev[k] (int32) = c + k for k < m,  NGW_IDX_NONE for m <= k < capacity;     *cursor_dev = c + m afterwards
+ * and m < count_dev[0] raises NGW_F_FRONTIER_FULL: a pool that is full degrades into dropped children - their pairs are skipped - and a flag, never
+ * into a bad address.  count_dev is ngw_frontier_compact's (only [0] is read), cursor_dev an int32 in DEVICE memory that the caller initialises;
+ * limit >= 0 is one past the last slot that may be handed out.  One kernel launch; the cursor is written after every work-group has read it.
+ * Both are enqueued on the handle's stream and do not wait.  They write no env state: nothing is committed, a captured graph stays valid.
+ * NGW_E_INVALID_ARG: a NULL handle, count or cursor, NULL flags with n > 0, a NULL list with capacity > 0; n outside [0, 2^24]; div < 1; capacity or
+ * limit negative, capacity beyond 2^31 - 1. */
+int ngw_frontier_compact(ngw_handle* h, const uint8_t* flags_dev, int64_t n, int32_t div, const int32_t* map_dev, int64_t capacity, int32_t* first_dev,
+                         int32_t* second_dev, int32_t* count_dev);
+int ngw_frontier_alloc(ngw_handle* h, const int32_t* count_dev, int32_t* cursor_dev, int32_t limit, int64_t capacity, int32_t* slots_dev);
 
 /* Guided playouts: ngw_snapshot_playout_traj_views whose weights depend on the STATE - at every step the pair's current state is looked up in a key
  * table, and where the table holds it the choice is made under that bucket's row of the caller's weights.  The selection phase of MCTS (descend by
