@@ -1,7 +1,7 @@
 """Model-based fuzz of the whole search surface of one handle: the driver and the model (tests/test_search_fuzz.py runs it against the HIP
 path, tests/test_search_fuzz_cpu.py against an oracle-backed stand-in and against seeded faults).
 
-run_case() draws the handle's settings and 6 - 12 calls - writers of live state, writers of snapshot slots, read-only calls - performs each on the
+run_case() draws the handle's settings and 8 - 15 calls - writers of live state, writers of snapshot slots, read-only calls - performs each on the
 env under test and on the model, and compares after EVERY call: the seven state arrays, every open snapshot, the call's own return value, the
 fused lidar rows, the action-mask words, the terminal-observation rows and the error flags.  The model is the CPU oracle for the live envs,
 snapshot_oracle.NumpySnapshot for the slots, key_table_oracle.KeyTableModel for the tables and the row-level reference functions of
@@ -17,6 +17,19 @@ source, children, every fields choice, both observations.  table_weights holds f
 and NaN in every other row, so a lane that reads a bucket no member owns changes the actions or raises F_BAD_WEIGHT, which check_all holds to 0.
 FIELD_CHOICES includes KEY_INV alone: with an empty inventory that key is 0, the one key a table never stores and a guided step never looks up.
 
+Walks, frontiers and the skipped pair.  Any call drawn in its device form whose index lists live on the device may be PADDED (draw_pad, one time in
+two): a scattered third, entries 64 .. 127 of a list longer than 128, all but one or all of its entries become IDX_NONE - in the source list, the
+destination list or both.  The references run on the list as drawn (the pairs of one call do not see each other), and the pairs that are not there get
+what include/ngw.h says the call stores for them: nothing, zeros, action -1, key 0, distance -1, where -1 and fresh 0 at the table; their destination
+rows are not written in the model, so check_all holds them byte-identical, and F_BAD_INDEX stays 0.  'slot_walk' / 'walk': walk_distances and
+walk_plans of filled slots and of the live envs against walk_oracle, every item id, 1 - 12 steps.  'walk_go': walk_plans(device=True) fed to
+rollout(limits=length.clip(0, steps), children=) with nothing leaving the device.  'frontier_compact': Frontier.compact of drawn flag bytes, taken 0 -
+15 bytes into a larger tensor, against frontier_oracle.  'frontier_step': insert_successor_keys -> fresh_pairs -> alloc -> expand on a padded parents
+list, the cursor and limit drawn so that no slot handed out is a parent of the call.  F_FRONTIER_FULL is compared by the call that raises it
+(error_flags reads and clears).  'frontier_twins': a device-form guided playout recorded with record=True, then fr.fresh_steps (of
+the flags the table reports for its path keys), fr.transitions and fr.tree_steps against the same lists of the model's expected result, padded by
+frontier_oracle, each at a capacity below, at and above the hits.
+
 Every draw depends on the RandomState, the settings and the model alone - never on a value the env under test returned - and every draw of a call is
 made before the model decides whether the call is refused, so the walk of a seed is the same walk on every backend.  The one state-dependent exit is
 "Cannot place items": both sides must fail, and the case ends.
@@ -28,6 +41,7 @@ import os
 import numpy as np
 
 import expand_oracle as XO
+import frontier_oracle as FO
 import guided_playout_oracle as GO
 import key_table_oracle as KT
 import lookahead_oracle as LO
@@ -44,6 +58,7 @@ import state_key_oracle as SK
 import successor_key_oracle as SU
 import trajectory_oracle as TO
 import trajectory_view_oracle as VO
+import walk_oracle as WO
 from oracle import ngw_oracle as NO
 
 STATE_KEYS = SO.STATE_KEYS
@@ -53,6 +68,18 @@ TABLE_CAPACITY = 4096                # 8192 buckets.  A condition, asserted afte
                                      # this fuzz models; a guided call's offer - up to 650 keys - is skipped on both sides where it would pass it).  The
                                      # committed walk's largest table holds 496 keys: sparse enough to stay cheap, dense enough for probe chains
 VIEW_SIZES = (1, 2, 5, 6)
+NONE = FO.IDX_NONE                   # include/ngw.h NGW_IDX_NONE: a pair that is not there
+F_FRONTIER_FULL = FO.F_FRONTIER_FULL
+WALK_STEPS = 12                      # walk plans of 1 .. 12 steps: complete ones and ones cut short
+# The rows of one walk call: walk_oracle searches S x S x 4 poses per distinct row in Python, so beyond 16 x 16 a call walks few rows.  ngw_walk_launch
+# (csrc/ngw_unit_walk.hip) starts one work-group per row - grid = count, one wavefront each -, so any call of two rows spans several work-groups.
+WALK_ROWS_LARGE = 6
+FRONTIER_TILE = 4096                 # csrc/ngw_device.h NGW_FRONTIER_TILE
+FLAG_LENGTHS = (0, 1, 17, FRONTIER_TILE - 1, FRONTIER_TILE, FRONTIER_TILE + 1, 2 * FRONTIER_TILE + 17)
+PAD_LAYOUTS = ('third', 'wave', 'but_one', 'all')      # the entries of a device list that become IDX_NONE: a scattered third, entries 64 .. 127 of a list
+                                                       # longer than 128 (a shorter one: the third), all but one, all
+PAD_ONE_IN = 2                                         # a call with device lists is padded one time in two (one in three left kinds of weight 2 unpadded)
+PAD_SIDES = ('source', 'destination', 'both')        # where a pair is skipped (a call with one list: that list; a walk: the row, the item, both)
 FIELD_CHOICES = (SK.STATE, SK.ALL, SK.MAP | SK.POSE, SK.INV | SK.SELECTED, SK.STEP_COUNT | SK.EPISODE | SK.POSE, SK.MAP, SK.INV)
 
 # call kinds and how often each is drawn (tests/test_search_fuzz_cpu.py holds the coverage these give for the committed seed)
@@ -61,16 +88,17 @@ KINDS = {
     'step': 3, 'dev': 2, 'rollout': 2, 'rollact': 2, 'reset': 2, 'mask_reset': 2, 'state_steps': 2, 'state_rows': 2, 'step_sampled': 2,
     'restore': 4, 'fork': 2, 'graph_launch': 2,
     # writers of slots only
-    'save': 2, 'copy': 2, 'expand': 4, 'expand_all': 2, 'srollout_kids': 6, 'splayout_kids': 7, 'splayout_guided_kids': 4,
+    'save': 2, 'copy': 2, 'expand': 4, 'expand_all': 2, 'srollout_kids': 6, 'splayout_kids': 7, 'splayout_guided_kids': 4, 'walk_go': 6,
+    'frontier_step': 6,              # (and of the table)
     # read-only (a guided playout offers keys to the table first: the env and the slots stay as they are)
     'splayout_guided': 4,
     'mask_words': 2, 'lookahead': 2, 'plans': 2, 'state_keys': 2, 'succ_keys': 2, 'insert_state_keys': 2, 'insert_succ_keys': 2, 'table_insert': 2,
     'table_lookup': 2, 'sample': 2, 'playouts': 6, 'srollout': 6, 'splayout': 6, 'slot_lidar': 2, 'slot_view': 2, 'slot_masks': 2, 'slot_keys': 2,
-    'slot_unique': 2, 'slot_insert_keys': 2, 'agent_view': 2, 'lidar': 2,
+    'slot_unique': 2, 'slot_insert_keys': 2, 'agent_view': 2, 'lidar': 2, 'slot_walk': 6, 'walk': 6, 'frontier_compact': 6, 'frontier_twins': 6,
 }
 READ_ONLY = ('mask_words', 'lookahead', 'plans', 'state_keys', 'succ_keys', 'insert_state_keys', 'insert_succ_keys', 'table_insert', 'table_lookup', 'sample',
              'playouts', 'srollout', 'splayout', 'splayout_guided', 'slot_lidar', 'slot_view', 'slot_masks', 'slot_keys', 'slot_unique', 'slot_insert_keys',
-             'agent_view', 'lidar')
+             'agent_view', 'lidar', 'slot_walk', 'walk', 'frontier_compact', 'frontier_twins')
 ROLLOUT_FORMS = ('plain', 'path', 'traj', 'view')
 PLAYOUT_FORMS = ('plain', 'weighted', 'path', 'traj', 'view')
 PLAYOUTS_FORMS = ('plain', 'weights', 'path_keys', 'rewards', 'masks', 'observe', 'view', 'guided')
@@ -210,6 +238,43 @@ def check_pairs(got, exp, kind, record, where):
 
 def state_dict(st):
     return {k: getattr(st, k).copy() for k in STATE_KEYS}
+
+
+def blank_pairs(exp, skip):
+    """ref_pairs' dict with what include/ngw.h says a rollout / playout stores for a skipped pair in the places of the pairs in `skip` (bool [count]):
+    the four reports 0 (a rollout leaves them untouched: the zeros they were allocated as), first action and the column of actions -1, keys 0, rewards
+    and masks 0, every block of the observation - block 0 included - zeros, where -1 and depth 0.  The end rows are left: the caller writes the live."""
+    if skip is None:
+        return exp
+    out = dict(exp)
+    out['rep'] = {k: np.where(skip, np.full((), -1 if k == 'first_action' else 0, np.asarray(v).dtype), v) for k, v in exp['rep'].items()}
+    out['actions'] = np.where(skip[None, :], -1, exp['actions']).astype(np.int32)
+    for k in ('keys', 'rewards', 'masks'):
+        if exp.get(k) is not None:
+            out[k] = np.where(skip[None, :], np.zeros((), exp[k].dtype), exp[k])
+    obs = exp.get('obs')
+    if isinstance(obs, dict):
+        out['obs'] = {k: zero_pairs(v, skip) for k, v in obs.items()}
+    elif obs is not None:
+        out['obs'] = zero_pairs(obs, skip)
+    return out
+
+
+def zero_pairs(x, skip):
+    x = np.array(x)
+    x[:, skip] = 0
+    return x
+
+
+def walk_ids(cs):
+    """(forward, left, right): "the LOWEST action id whose act_kind is NGW_ACT_FORWARD, NGW_ACT_LEFT and NGW_ACT_RIGHT respectively" (kinds 0, 1, 2),
+    None for a kind the action table lacks."""
+    ids = [None, None, None]
+    for a in range(cs.n_actions):
+        k = int(cs.act_kind[a])
+        if k < 3 and ids[k] is None:
+            ids[k] = a
+    return tuple(ids)
 
 
 # ---------------------------------------------------------------- one case
@@ -401,8 +466,45 @@ class Case:
                 keys.append(fresh[j])
         return np.array(keys, np.uint64)
 
+    def draw_pad(self, rs, count, on_dev, kind):
+        """The padding of one call's device index lists -> the bool [count] of the entries that become IDX_NONE, or None (a host list, an empty one, or
+        two calls in three).  The side is kept in self.side for padded(); every draw is made whatever the outcome."""
+        u, one = rs.rand(count), int(rs.randint(0, max(count, 1)))
+        pad, layout, side = rs.randint(0, PAD_ONE_IN) == 0, PAD_LAYOUTS[int(rs.randint(0, len(PAD_LAYOUTS)))], PAD_SIDES[int(rs.randint(0, len(PAD_SIDES)))]
+        if not (on_dev and pad and count):
+            return None
+        at = np.arange(count)
+        if layout == 'wave' and count > 128:
+            skip = (at >= 64) & (at < 128)
+        elif layout in ('third', 'wave'):
+            layout, skip = 'third', u < 1.0 / 3
+        elif layout == 'but_one':
+            skip = at != one
+        else:
+            skip = np.ones(count, bool)
+        self.side = side
+        self.log('(pad)', kind, (layout, side))
+        return skip
+
+    def pad_envs(self, rs, envs, on_dev, kind):
+        """draw_pad for an env list -> (the list, the entries that become IDX_NONE or None); "None: every env" written out where it is padded."""
+        skip = self.draw_pad(rs, self.n if envs is None else len(envs), on_dev, kind)
+        return (np.arange(self.n, dtype=np.int32) if envs is None and skip is not None else envs), skip
+
+    def padded(self, skip, src, dst=None):
+        """The lists of a padded call: IDX_NONE in the source list, the destination list or both at the entries in `skip` (one list: that one)."""
+        if skip is None:
+            return (src, dst) if dst is not None else src
+        if dst is None:
+            return np.where(skip, NONE, src).astype(np.int32)
+        return (np.where(skip & (self.side != 'destination'), NONE, src).astype(np.int32),
+                np.where(skip & (self.side != 'source'), NONE, dst).astype(np.int32))
+
     def check_insert(self, keys, found, where):
-        fresh, stored = self.table.insert(keys)
+        self.check_found(keys, self.table.insert(keys), found, where)
+
+    def check_found(self, keys, model, found, where):
+        fresh, stored = model
         assert len(self.table) <= TABLE_CAPACITY, "%s: the model holds %d keys, the table's capacity is %d" % (where, len(self.table), TABLE_CAPACITY)
         self.log('(table)', 'size', len(self.table))
         eq('fresh', host(found.fresh).reshape(-1), fresh, where)
@@ -480,17 +582,26 @@ class Case:
                 slots = envs = None                       # the whole batch, no lists
             else:
                 slots = slots[:len(envs)]
-            self.snaps[s].restore(o.st, slots, envs, keep)
+            skip = None if slots is None else self.draw_pad(rs, len(slots), on_dev, kind)
+            if skip is None:
+                self.snaps[s].restore(o.st, slots, envs, keep)
+            else:                                          # "makes that one copy a no-op": the live copies alone
+                self.snaps[s].restore(o.st, slots[~skip], envs[~skip], keep)
+                slots, envs = self.padded(skip, slots, envs)
             self.vsnaps[s].restore(slots=self.maybe_dev(slots, on_dev), envs=self.maybe_dev(envs, on_dev), keep_episode=keep)
             self.lidar_stale = False
             form = 'keep' if keep else 'episode'
         elif kind == 'fork':
             keep = bool(rs.randint(0, 2))
             src = rs.randint(0, n, n).astype(np.int32)
+            skip = self.draw_pad(rs, n, on_dev, kind)
             tmp = SO.NumpySnapshot(self.S, self.K, n)
             tmp.save(o.st)
-            tmp.restore(o.st, src, None, keep)
-            v.fork(self.maybe_dev(src, on_dev), keep_episode=keep)
+            if skip is None:
+                tmp.restore(o.st, src, None, keep)
+            else:                                          # an env whose source is not there stays as it is
+                tmp.restore(o.st, src[~skip], np.arange(n)[~skip], keep)
+            v.fork(self.maybe_dev(self.padded(skip, src), on_dev), keep_episode=keep)
             self.lidar_stale = False
         elif kind == 'graph_launch':
             reps = int(rs.randint(1, 3))
@@ -502,22 +613,33 @@ class Case:
             d = int(rs.randint(0, 2))
             c = int(rs.randint(1, min(n, self.caps[d]) + 1))
             envs, slots = rs.randint(0, n, c).astype(np.int32), rs.permutation(self.caps[d])[:c].astype(np.int32)
-            self.snaps[d].save(o.st, envs, slots)
-            self.filled[d][slots] = True
+            skip = self.draw_pad(rs, c, on_dev, kind)
+            live = slice(None) if skip is None else ~skip
+            self.snaps[d].save(o.st, envs[live], slots[live])
+            self.filled[d][slots[live]] = True
+            envs, slots = self.padded(skip, envs, slots)
             self.vsnaps[d].save(envs=self.maybe_dev(envs, on_dev), slots=self.maybe_dev(slots, on_dev))
         elif kind == 'copy':
             s, d, src, dst = self.draw_source_slots(rs)
+            skip = self.draw_pad(rs, len(src), on_dev, kind)
+            live = slice(None) if skip is None else ~skip
             for k in STATE_KEYS:
-                self.snaps[d].rows[k][dst] = self.snaps[s].rows[k][src]
-            self.filled[d][dst] = True
+                self.snaps[d].rows[k][dst[live]] = self.snaps[s].rows[k][src[live]]
+            self.filled[d][dst[live]] = True
+            src, dst = self.padded(skip, src, dst)
             self.vsnaps[d].copy(self.maybe_dev(src, on_dev), self.maybe_dev(dst, on_dev), source=None if s == d else self.vsnaps[s])
             form = 'within' if s == d else 'between'
         elif kind == 'expand':
             s, d, parents, children = self.draw_source(rs, MAX_PAIRS)
             actions = rs.randint(0, A, len(parents)).astype(np.int32)
+            skip = self.draw_pad(rs, len(parents), on_dev, kind)
+            live = slice(None) if skip is None else ~skip
             kids, rep = XO.oracle_expand(spec, rows_of(self.src_rows(s)), parents, actions, ar, H)
-            self.write_children(d, children, kids)
-            got = self.vsnaps[d].expand(self.maybe_dev(parents, on_dev), self.maybe_dev(actions, on_dev), self.maybe_dev(children, on_dev), device=on_dev,
+            self.write_children(d, children[live], {k: kids[k][live] for k in STATE_KEYS})
+            if skip is not None:                           # "nothing is stored, its reports are left untouched": the zeros they were allocated as
+                rep = {k: np.where(skip, np.zeros((), x.dtype), x) for k, x in rep.items()}
+            p, c = self.padded(skip, parents, children)
+            got = self.vsnaps[d].expand(self.maybe_dev(p, on_dev), self.maybe_dev(actions, on_dev), self.maybe_dev(c, on_dev), device=on_dev,
                                         **self.src_kw(s, d))
             for k in ('reward', 'done', 'result', 'info'):
                 eq(k, got[k], rep[k], where)
@@ -583,6 +705,9 @@ class Case:
             envs = self.envs_list(rs, MAX_PAIRS)
             fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
             exp = fast_keys(rows_at(o.st, np.arange(n) if envs is None else envs), fields)
+            envs, skip = self.pad_envs(rs, envs, on_dev, kind)
+            if skip is not None:                           # "that key is 0"
+                exp, envs = np.where(skip, np.uint64(0), exp), self.padded(skip, envs)
             if kind == 'state_keys':
                 eq('keys', v.state_keys(self.maybe_dev(envs, on_dev), fields, device=on_dev), exp, where)
             else:
@@ -596,17 +721,22 @@ class Case:
                 envs = np.arange(min(n, 8), dtype=np.int32)
             fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
             reports = bool(rs.randint(0, 4))
+            envs, skip = self.pad_envs(rs, envs, on_dev, kind)
             if self.S > SUCC_MAX_MAP:
                 from gym_novel_gridworlds_amd.snapshot import MapsTooLarge
                 raise Refused(MapsTooLarge)
             ex = SU.Successors(spec, o.st, np.arange(n) if envs is None else envs, ar, H)
+            zero = () if skip is None else np.nonzero(skip)[0]        # a parent that is not there: its A keys are 0, its reports are 0
+            envs = envs if skip is None else self.padded(skip, envs)
             if kind == 'succ_keys':
-                SU.assert_successors(v.successor_keys(self.maybe_dev(envs, on_dev), fields, device=on_dev, reports=reports), ex, fields, where, reports)
+                SU.assert_successors(v.successor_keys(self.maybe_dev(envs, on_dev), fields, device=on_dev, reports=reports), ex, fields, where, reports, zero)
             else:
                 got, found = v.insert_successor_keys(self.vtable, self.maybe_dev(envs, on_dev), fields, device=on_dev)
-                SU.assert_successors(got, ex, fields, where)
+                SU.assert_successors(got, ex, fields, where, True, zero)
                 assert tuple(found.fresh.shape) == tuple(ex.keys(fields).shape), where
-                self.check_insert(ex.keys(fields).reshape(-1), found, where)
+                keys = ex.keys(fields).copy()
+                keys[list(zero)] = 0
+                self.check_insert(keys.reshape(-1), found, where)
                 self.last_fields = fields
         elif kind == 'table_insert':
             keys = self.draw_keys(rs, int(rs.randint(1, 65)))
@@ -622,16 +752,38 @@ class Case:
             idx = np.arange(n) if envs is None else envs
             w = SA.random_weights(rs, len(idx), A)
             seed, t = int(rs.randint(0, 2 ** 31)), int(rs.randint(0, 1000))
+            envs, skip = self.pad_envs(rs, envs, on_dev, kind)
             exp = SA.oracle_sample(spec, o.st, idx, w, seed, self.base, t)
+            if skip is not None:                           # "that pair gets action -1, mass 0 and mask 0"
+                exp = (np.where(skip, -1, exp[0]).astype(np.int32), np.where(skip, np.float32(0), exp[1]), np.where(skip, np.uint64(0), exp[2])) + exp[3:]
+                envs = self.padded(skip, envs)
             got = v.sample_actions(self.dev(np.ascontiguousarray(w.T)) if on_dev else w, seed, t, self.maybe_dev(envs, on_dev), device=on_dev)
             g = host(tuple(got))
             SA.assert_sampled((g[0], g[1], same_bits(g[2], np.zeros(0, np.uint64))), exp, where)
         elif kind in ('slot_lidar', 'slot_view', 'slot_masks', 'slot_keys', 'slot_unique', 'slot_insert_keys'):
             s, slots = self.filled_slots(rs, MAX_PAIRS)
-            snap, rows, arg = self.vsnaps[s], self.snaps[s].rows, self.maybe_dev(slots, on_dev)
+            snap, rows = self.vsnaps[s], self.snaps[s].rows
             fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
             V = int(rs.choice([1, 2, 5]))
-            if kind == 'slot_lidar':
+            skip = None if kind == 'slot_unique' else self.draw_pad(rs, len(slots), on_dev, kind)
+            arg = self.maybe_dev(self.padded(skip, slots), on_dev)
+            if skip is not None and kind in ('slot_lidar', 'slot_view', 'slot_masks'):
+                # "its output row is all zeros (mask 0, facing 0)": the references' rows with zeros in the places of the slots that are not there
+                if kind == 'slot_lidar':
+                    got = host(snap.lidar_observation(arg, device=on_dev))
+                    got, exp = {'lidar': v.lidar_widen(got) if isinstance(got, tuple) else got}, {'lidar': OO.expect_lidar(spec, self.lc, rows, slots)}
+                elif kind == 'slot_view':
+                    got, exp = OO.host(snap.agent_view(arg, V, device=on_dev)), OO.expect_view(rows, slots, V)
+                else:
+                    got, exp = {'masks': host(snap.action_masks(arg, device=on_dev))}, {'masks': OO.expect_masks(spec, rows, slots)}
+                    assert got['masks'].dtype == np.bool_, where
+                assert sorted(got) == sorted(exp), where
+                for k in exp:
+                    e = np.array(exp[k])
+                    e[skip] = 0
+                    assert kind == 'slot_lidar' or got[k].dtype == e.dtype, (where, k, got[k].dtype)
+                    eq(k, got[k], e, where)
+            elif kind == 'slot_lidar':
                 OO.assert_lidar(v, snap.lidar_observation(arg, device=on_dev), spec, self.lc, rows, slots, where)
             elif kind == 'slot_view':
                 OO.assert_view(snap.agent_view(arg, V, device=on_dev), rows, slots, V, where)
@@ -639,6 +791,8 @@ class Case:
                 OO.assert_masks(snap.action_masks(arg, device=on_dev), spec, rows, slots, where)
             else:
                 exp = fast_keys(rows_at(self.snaps[s], slots), fields)
+                if skip is not None:
+                    exp = np.where(skip, np.uint64(0), exp)
                 if kind == 'slot_keys':
                     eq('keys', snap.keys(arg, fields, device=on_dev), exp, where)
                 elif kind == 'slot_unique':
@@ -659,6 +813,16 @@ class Case:
             got = host(v.lidar_observation(device=on_dev))
             if not (self.fused and self.lidar_stale):     # (fused: the rows are the last launch's, and set_state launches nothing)
                 eq('lidar rows', v.lidar_widen(got) if isinstance(got, tuple) else got, NO.lidar(self.cc, self.S, self.K, o.st.map, o.st.loc, o.st.facing, o.st.inv), where)
+        elif kind in ('slot_walk', 'walk'):
+            form = self.walk_call(kind, where, on_dev)
+        elif kind == 'walk_go':
+            form = self.walk_go(kind, where)
+        elif kind == 'frontier_compact':
+            form = self.frontier_compact(kind, where)
+        elif kind == 'frontier_step':
+            form = self.frontier_step(kind, where)
+        elif kind == 'frontier_twins':
+            form = self.guided_call(kind, where, True, twins=True)
         else:
             raise AssertionError('unknown call kind ' + kind)
         return form
@@ -713,13 +877,20 @@ class Case:
                 kw['observe'], rkw['lc'] = 'lidar', self.lc
             if playout and with_masks:
                 kw['masks'] = rkw['masks'] = True
+        skip = self.draw_pad(rs, count, on_dev, kind)
+        live = slice(None) if skip is None else ~skip
+        # (the pairs of one call do not see each other, and a playout's draws go by the pair's position: the references run on the list as drawn,
+        # and the pairs that are not there get what the contract stores for them)
         if playout:
             exp = ref_pairs(spec, rows_of(self.src_rows(s)), parents, 'playout', self.autoreset, self.horizon, steps=steps, seed=seed, first_pair=first_pair, **rkw)
         else:
             exp = ref_pairs(spec, rows_of(self.src_rows(s)), parents, 'rollout', self.autoreset, self.horizon, plans=plans, **rkw)
         if kids:
-            self.write_children(d, children, exp['ends'])
+            self.write_children(d, children[live], {k: exp['ends'][k][live] for k in STATE_KEYS})
+        exp = blank_pairs(exp, skip)
         snap, src = self.vsnaps[d], self.src_kw(s, d)
+        if skip is not None:
+            parents, children = self.padded(skip, parents, children) if kids else (self.padded(skip, parents), None)
         p, c = self.maybe_dev(parents, on_dev), self.maybe_dev(children, on_dev)
         if playout:
             got = snap.playout(p, steps, seed, children=c, first_pair=first_pair, record=record, device=on_dev, **src, **kw)
@@ -728,7 +899,7 @@ class Case:
         check_pairs(got, exp, 'playout' if playout else 'rollout', record, where)
         return '%s/%s' % (form, 'envs' if s is None else 'slots')
 
-    def guided_call(self, kind, where, on_dev, P=None):
+    def guided_call(self, kind, where, on_dev, P=None, twins=False):
         """A guided playout - Snapshot.playout(table=, table_weights=, outside=) with or without children, or with P the 'guided' form of playouts()
         - over the case's own table: whatever the earlier calls inserted, under whatever fields, plus (three times in four) an offer of keys under this
         call's fields.  Every row of table_weights no member owns is NaN: a lane that reads one changes the actions or raises F_BAD_WEIGHT."""
@@ -748,7 +919,9 @@ class Case:
         default = w if rs.randint(0, 3) else None
         outside = ('default', 'stop')[int(rs.randint(0, 2))]
         record, with_keys, rewards, masks = [bool(x) for x in rs.randint(0, 2, 4)]
-        observe = (None, None, 'lidar', 'agent_view')[int(rs.randint(0, 4))]
+        if twins:                                        # what the three twins read: the recorded actions, the path keys, a per-step field
+            record = with_keys = rewards = True
+        observe =(None, None, 'lidar', 'agent_view')[int(rs.randint(0, 4))]
         V = int(rs.choice(VIEW_SIZES))
         fill_seed = int(rs.randint(0, 2 ** 31))
         offer, again = bool(rs.randint(0, 4)), bool(rs.randint(0, 2))
@@ -756,6 +929,7 @@ class Case:
             fields = self.last_fields
         keep = rs.rand(count * (1 + (steps + 1) // 2)) < OFFER_KEEP[int(rs.randint(0, len(OFFER_KEEP)))]
         probe = rs.randint(0, 1 << 30, 64)
+        skip = self.draw_pad(rs, count, on_dev and not batch, kind)
         record = record and not batch                    # (playouts() records no actions)
         src = self.src_rows(s)
         rows = rows_of(src)
@@ -799,8 +973,14 @@ class Case:
         exp_where = np.full((steps, count), -1, np.int32)
         for t, j in np.argwhere(e['hit']):
             exp_where[t, j] = self.book.of_key[int(e['before'][t, j])]
+        exp_depth = e['depth']
+        live = slice(None) if skip is None else ~skip
         if kids:
-            self.write_children(d, children, e['ends'])
+            self.write_children(d, children[live], {k: e['ends'][k][live] for k in STATE_KEYS})
+        if skip is not None:                             # the pairs that are not there: blank_pairs' values, where -1, "depth 0 for a skipped pair"
+            exp = blank_pairs(exp, skip)
+            exp_where, exp_depth = np.where(skip[None, :], -1, exp_where).astype(np.int32), np.where(skip, 0, exp_depth)
+            parents, children = self.padded(skip, parents, children) if kids else (self.padded(skip, parents), None)
         # the call
         kw = dict(table=self.vtable, table_weights=self.dev(tw) if on_dev else tw, outside=outside, fields=fields, rewards=rewards, masks=masks)
         if default is not None:
@@ -821,7 +1001,7 @@ class Case:
                                          record=record, device=on_dev, **self.src_kw(s, d), **kw)
         assert type(got).__name__ == 'PlayoutGuided', "%s: a %s came back" % (where, type(got).__name__)
         check_pairs(got, exp, 'playout', record, where)
-        for name, x in (('where', exp_where), ('depth', e['depth'])):
+        for name, x in (('where', exp_where), ('depth', exp_depth)):
             g = host(getattr(got, name))
             assert g.dtype == np.int32, "%s: %s is %s" % (where, name, g.dtype)
             eq(name, g.reshape(x.shape), x, where)
@@ -838,7 +1018,235 @@ class Case:
             reentries=ev['reentries'], zero_mass=ev['zero_mass'], differs=ev['differs'], key0=int((ran & (e['before'] == 0)).sum()),
             displaced=int((home != np.array([self.book.of_key[k] for k in members], np.int64)).sum()),
             shared_home=len(members) - len(set(home.tolist()))).items())))
+        if twins:
+            self.twins(got, exp, exp_where, steps, count, where)
         return 'guided' if batch else 'guided/%s' % ('envs' if s is None else 'slots')
+
+    def twins(self, got, exp, exp_where, steps, count, where):
+        """'frontier_twins': the padded twins of the dense helpers on a device-form guided playout recorded with record=True - fr.fresh_steps (of the
+        `fresh` flags the table reports for the call's path keys), fr.transitions(result), fr.tree_steps(result) - against the same lists computed from
+        the model's expected result and padded by frontier_oracle, each at a capacity below, at and above the hits."""
+        keys = exp['keys'].reshape(-1)
+        new = set(keys.tolist()) - set(self.table.order) - {0}
+        if len(self.table) + len(new) <= TABLE_CAPACITY:
+            model = self.table.insert(keys)
+            found = self.vtable.insert(got.keys.reshape(-1), device=True)
+            self.check_found(keys, model, found, where + ' (the path keys)')
+            e_fresh, fresh = model[0].reshape(steps, count), found.fresh.reshape(steps, count)
+        else:                                            # (a full table is not what this fuzz models: the flags are the executed steps' keys)
+            e_fresh, fresh = exp['keys'] != 0, got.keys.reshape(steps, count) != 0
+        fresh = fresh.contiguous() if hasattr(fresh, 'contiguous') else fresh
+        e_ran = np.arange(steps)[:, None] < exp['rep']['length'][None, :]
+        e_tree = exp_where >= 0
+        n = max(count, 1)
+        pool = self.vsnaps[0]
+        for name, flags in (('fresh_steps', e_fresh), ('transitions', e_ran), ('tree_steps', e_tree)):
+            hits = int(np.count_nonzero(flags))
+            for capacity in sorted({max(hits - 1, 0), hits, hits + 70}):
+                w = '%s, %s at capacity %d of %d hits' % (where, name, capacity, hits)
+                e_t, e_j, e_count, full = FO.compact(flags, n, None, capacity)
+                fr = pool.frontier(capacity)
+                if name == 'tree_steps':
+                    bucket, action, t, j = fr.tree_steps(got)
+                    live = e_t != NONE
+                    eq('bucket', bucket, np.where(live, exp_where[e_t * live, e_j * live], NONE).astype(np.int32), w)
+                    eq('action', action, np.where(live, exp['actions'][e_t * live, e_j * live], NONE).astype(np.int32), w)
+                else:
+                    t, j = fr.fresh_steps(fresh) if name == 'fresh_steps' else fr.transitions(got)
+                eq('t', t, e_t, w)
+                eq('j', j, e_j, w)
+                eq('count', fr.count_dev, np.array(e_count, np.int32), w)
+                self.raise_full(full, w)
+                fr.close()
+        self.log('(twins)', 'frontier_twins', (int(np.count_nonzero(e_fresh)), int(np.count_nonzero(e_ran)), int(np.count_nonzero(e_tree))))
+
+    # -------------------------------------------------------------- walk distances and go-to plans
+    def walk_rows_max(self):
+        return MAX_PAIRS if self.S <= 16 else WALK_ROWS_LARGE
+
+    def expect_walk(self, rows, idx, items, steps, skip):
+        """walk_oracle's (dist, plans, length) of rows idx; "every output of that row is -1" for a row that is not there."""
+        dist, plans, length = WO.walk_rows(rows, idx, self.K, items, steps, walk_ids(self.spec.compile()))
+        if skip is not None:
+            dist = np.where(skip[:, None], -1, dist).astype(np.int32)
+            if items is not None:
+                plans, length = np.where(skip[None, :], -1, plans).astype(np.int32), np.where(skip, -1, length).astype(np.int32)
+        return dist, plans, length
+
+    def walk_call(self, kind, where, on_dev):
+        """Snapshot.walk_distances / walk_plans on filled slots ('slot_walk'), VecNovelGridworld's on the live envs ('walk'): host and device lists, every
+        item id below K, plans complete and cut short."""
+        rs, n, K = self.rs, self.n, self.K
+        if kind == 'slot_walk':
+            s, idx = self.filled_slots(rs, self.walk_rows_max())
+            arg, rows, target = idx, self.snaps[s].rows, self.vsnaps[s]
+        else:
+            arg = self.envs_list(rs, self.walk_rows_max())
+            if arg is None and n > self.walk_rows_max():  # (every env of a large map: too many rows for the oracle)
+                arg = np.arange(self.walk_rows_max(), dtype=np.int32)
+            idx, rows, target = (np.arange(n) if arg is None else arg), rows_of(self.o.st), self.v
+        count = len(idx)
+        plans_on = bool(rs.randint(0, 3)) and None not in walk_ids(self.spec.compile())
+        steps, items = int(rs.randint(1, WALK_STEPS + 1)), rs.randint(0, K, count).astype(np.int32)
+        one_item, item_list = bool(rs.randint(0, 4) == 0), bool(rs.randint(0, 2))
+        if one_item:
+            items[:] = items[0]
+        arg, skip = self.pad_envs(rs, arg, on_dev, kind) if kind == 'walk' else (arg, self.draw_pad(rs, count, on_dev, kind))
+        dist, plans, length = self.expect_walk(rows, idx, items if plans_on else None, steps, skip)
+        it = int(items[0]) if one_item else self.maybe_dev(items, on_dev)
+        if skip is not None:                             # the row, the item or both are not there (the distances alone, one item for all: the row)
+            if plans_on and not one_item:
+                arg, it = self.padded(skip, arg, items)
+                it = self.dev(it)
+            else:
+                arg = self.padded(skip, arg)
+        arg = self.maybe_dev(arg, on_dev)
+        if not plans_on:
+            got = target.walk_distances(arg, device=on_dev)
+            eq('dist', got, dist, where)
+        else:
+            got = target.walk_plans(arg, it, steps, device=on_dev) if kind == 'slot_walk' else target.walk_plans(it, steps, envs=arg, device=on_dev)
+            for name, e in (('plans', plans), ('length', length), ('dist', dist)):
+                g = host(getattr(got, name))
+                assert g.dtype == np.int32, "%s: %s is %s" % (where, name, g.dtype)
+                eq(name, g, e, where)
+            self.log('(walk)', kind, (int((length > steps).sum()), int((length < 0).sum())))
+        return ('plans' if plans_on else 'dist') + ('/dev' if on_dev else '/host')
+
+    def walk_go(self, kind, where):
+        """The macro-action "go to the nearest X and face it", nothing leaving the device: walk_plans(device=True), then rollout(slots, plans,
+        limits=length.clamp(0, steps), children=c, device=True).  A pair whose item no reachable pose faces has limit 0 and a column of -1: it
+        executes no step, so its child is the parent's row (ngw_snapshot_rollout_path: limits "0 .. n_steps"; the row "as the last executed step
+        leaves it" of a pair that executed none) and its reports are 0."""
+        rs, spec, K = self.rs, self.spec, self.K
+        s, d, parents, children = self.draw_source(rs, self.walk_rows_max())
+        count = len(parents)
+        steps, items = int(rs.randint(1, WALK_STEPS + 1)), rs.randint(0, K, count).astype(np.int32)
+        skip = self.draw_pad(rs, count, True, kind)
+        if None in walk_ids(spec.compile()):
+            raise Refused(ValueError)
+        rows = rows_of(self.src_rows(s))
+        walk_skip = None if skip is None or self.side == 'destination' else skip
+        dist, plans, length = self.expect_walk(rows, parents, items, steps, walk_skip)
+        limits = np.clip(length, 0, steps).astype(np.int32)
+        exp = ref_pairs(spec, rows, parents, 'rollout', self.autoreset, self.horizon, plans=np.ascontiguousarray(plans.T), limits=limits)
+        live = slice(None) if skip is None else ~skip
+        self.write_children(d, children[live], {k: exp['ends'][k][live] for k in STATE_KEYS})
+        exp = blank_pairs(exp, skip)
+        p, c = self.padded(skip, parents, children)
+        p, c = self.dev(p), self.dev(c)
+        if s is None:
+            wp = self.v.walk_plans(self.dev(items), steps, envs=p, device=True)
+        else:
+            wp = self.vsnaps[s].walk_plans(p, self.dev(items), steps, device=True)
+        got = self.vsnaps[d].rollout(p, wp.plans, children=c, device=True, limits=wp.length.clip(0, steps), **self.src_kw(s, d))
+        for name, e in (('plans', plans), ('length', length), ('dist', dist)):
+            eq(name, getattr(wp, name), e, where)
+        check_pairs(got, exp, 'rollout', False, where)
+        self.log('(walk_go)', kind, (int((length[live] < 0).sum()), int((length[live] > steps).sum())))
+        return 'envs' if s is None else 'slots'
+
+    # -------------------------------------------------------------- frontiers
+    def raise_full(self, full, where):
+        """The call that raises the sticky F_FRONTIER_FULL compares the flags at once - ngw_error_flags "reads and clears" -; both sides go on."""
+        got, exp = self.v.error_flags(), self.flags | (F_FRONTIER_FULL if full else 0)
+        assert got == exp, "%s: error flags %#x, the model says %#x" % (where, got, exp)
+
+    def frontier_compact(self, kind, where):
+        """Frontier.compact of a flag tensor of drawn content, taken as a slice that starts 0 .. 15 bytes into a larger one, against frontier_oracle."""
+        rs, A = self.rs, self.A
+        s = int(rs.randint(0, 2))
+        n, off = int(FLAG_LENGTHS[rs.randint(0, len(FLAG_LENGTHS))]), int(rs.randint(0, 16))
+        content, div = ('none', 'all', 'sparse', 'stray')[int(rs.randint(0, 4))], int((1, A, 17)[rs.randint(0, 3)])
+        with_map, cap_choice = bool(rs.randint(0, 2)), int(rs.randint(0, 4))
+        sparse, stray_at = (rs.randint(0, 17, n) == 0).astype(np.uint8), rs.randint(0, max(n, 1), 6)
+        amap = (rs.permutation(-(-n // div) + 3) + 7).astype(np.int32)
+        flags = {'none': np.zeros(n, np.uint8), 'all': np.ones(n, np.uint8)}.get(content, sparse)
+        if content == 'stray' and n:
+            flags[stray_at] = np.array([2, 0x80, 0xFF, 2, 0x80, 0xFF], np.uint8)
+        big = np.ones(n + 32, np.uint8)                   # (set bytes on both sides of the slice: a load beyond it counts them)
+        big[off:off + n] = flags
+        total = int(np.count_nonzero(flags))
+        capacity = (max(total - 1, 0), 0, total, total + 70)[cap_choice]
+        e_first, e_second, e_count, full = FO.compact(flags, div, amap if with_map else None, capacity)
+        fr = self.vsnaps[s].frontier(capacity)
+        first, second = fr.compact(self.dev(big)[off:off + n], div, self.dev(amap) if with_map else None)
+        eq('first', first, e_first, where)
+        eq('second', second, e_second, where)
+        eq('count', fr.count_dev, np.array(e_count, np.int32), where)
+        assert fr.count() == e_count[0] and fr.total() == e_count[1], where
+        self.raise_full(full, where)
+        fr.close()
+        self.log('(compact)', kind, (n, off, content, div, with_map, cap_choice))
+        return content
+
+    def frontier_step(self, kind, where):
+        """One iteration of the closed loop of frontier.py on a padded parents list: insert_successor_keys -> fresh_pairs -> alloc -> expand."""
+        rs, spec, A, ar, H = self.rs, self.spec, self.A, self.autoreset, self.horizon
+        d = int(rs.randint(0, 2))
+        if not self.filled[d].any():
+            d = 0
+        cap = self.caps[d]
+        live_slots = np.nonzero(self.filled[d])[0]
+        parents = live_slots[rs.randint(0, 1 << 30, int(rs.randint(1, 9))) % len(live_slots)].astype(np.int32)
+        count = len(parents)
+        fields = int(FIELD_CHOICES[rs.randint(0, len(FIELD_CHOICES))])
+        cap_choice, mode, u = int(rs.randint(0, 3)), ('ample', 'short', 'exhausted')[int(rs.randint(0, 3))], int(rs.randint(0, 1 << 30))
+        skip = self.draw_pad(rs, count, True, kind)
+        if self.S > SUCC_MAX_MAP:
+            from gym_novel_gridworlds_amd.snapshot import MapsTooLarge
+            raise Refused(MapsTooLarge)
+        plist = self.padded(skip, parents)
+        gone = np.zeros(count, bool) if skip is None else skip
+        ex = SU.Successors(spec, self.snaps[d].rows, parents, ar, H)
+        keys = ex.keys(fields).copy()
+        keys[gone] = 0
+        model = self.table.insert(keys.reshape(-1))
+        fresh = model[0].reshape(count, A)
+        hits = int(fresh.sum())
+        capacity = min(max((max(hits - 1, 1), max(hits, 1), hits + 70)[cap_choice], 1), cap)
+        e_first, e_second, e_count, full = FO.compact(fresh, A, plist, capacity)
+        taken = e_count[0]
+        # the cursor: inside the snapshot, and the slots handed out hold no parent of the call (a condition on the draw, made from the model)
+        want = {'ample': taken, 'short': max(taken - 1 - u % 3, 0), 'exhausted': 0}[mode]
+        busy = np.zeros(cap + 1, np.int64)
+        busy[parents[~gone] + 1] = 1
+        run = np.cumsum(busy)
+        starts = [c for c in range(cap - want + 1) if run[c + want] == run[c]]
+        if not starts:
+            want, starts = 0, list(range(cap + 1))
+        cursor = starts[u % len(starts)]
+        limit = None if want == taken and cursor + want == cap and u % 2 else cursor + want
+        e_slots, e_cursor, short = FO.alloc(taken, cursor, cap if limit is None else limit, capacity)
+        pos, act = np.nonzero(fresh)
+        m = min(e_cursor - cursor, capacity)
+        kids = ex.child_rows(pos[:m], act[:m])
+        self.write_children(d, e_slots[:m], kids)
+        rep = {k: np.zeros(capacity, ex.rep[k].dtype) for k in ('reward', 'done', 'result', 'info')}
+        for k in rep:
+            rep[k][:m] = ex.rep[k][pos[:m], act[:m]]
+        # the calls
+        pool, pdev = self.vsnaps[d], self.dev(plist)
+        succ, found = pool.insert_successor_keys(self.vtable, pdev, fields, device=True)
+        fr = pool.frontier(capacity)
+        fr.reset_cursor(cursor)
+        p, a = fr.fresh_pairs(found.fresh, pdev)
+        c = fr.alloc(limit)
+        got = pool.expand(p, a, c, device=True)
+        SU.assert_successors(succ, ex, fields, where, True, np.nonzero(gone)[0])
+        self.check_found(keys.reshape(-1), model, found, where)
+        self.last_fields = fields
+        eq('parents', p, e_first, where)
+        eq('actions', a, e_second, where)
+        eq('slots', c, e_slots, where)
+        eq('count', fr.count_dev, np.array(e_count, np.int32), where)
+        eq('cursor', fr.cursor, np.array([e_cursor], np.int32), where)
+        for k in rep:
+            eq(k, got[k], rep[k], where)
+        self.raise_full(full or short, where)
+        fr.close()
+        self.log('(step)', kind, (mode, bool(short), bool(full), hits, m))
+        return mode
 
     # -------------------------------------------------------------- the walk
     def run(self):
@@ -853,7 +1261,7 @@ class Case:
         names = sorted(KINDS)
         p = np.array([KINDS[k] for k in names], np.float64)
         p /= p.sum()
-        n_calls = int(rs.randint(6, 13))
+        n_calls = int(rs.randint(8, 16))
         kinds = [names[i] for i in rs.choice(len(names), n_calls, p=p)]
         gk = int(rs.randint(1, 4))
         gacts = rs.randint(0, A, size=(gk, n)).astype(np.int32)
@@ -918,6 +1326,10 @@ class Case:
             self.v.successor_keys()
         elif kind == 'insert_succ_keys':
             self.v.insert_successor_keys(self.vtable, np.zeros(1, np.int32))
+        elif kind == 'frontier_step':
+            self.vsnaps[0].insert_successor_keys(self.vtable, np.zeros(1, np.int32))
+        elif kind == 'walk_go':                           # (a spec without a Forward, a Left or a Right action: "walk plans need ...")
+            self.vsnaps[0].walk_plans(np.zeros(1, np.int32), 0, 1)
         else:
             raise AssertionError('no refusal is documented for ' + kind)
 

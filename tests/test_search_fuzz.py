@@ -16,7 +16,14 @@ message names the configuration, the case, the settings, the call's index and ki
 side of one chunk, walked on the CPU against the stand-in (tests/test_search_fuzz_cpu.py; the stand-in computes everything a second time), was
 measured at 3.7, 2.2, 2.5, 2.7, 2.8 and 2.4 s for the committed seed, with the per-call maxima as the issue set them (130 pairs, 8 steps, 3 plans);
 on the MI355X a chunk takes 0.51 - 0.70 s (2.9 s for the first, which loads the library); before the guided kinds and the 'view' forms, measured in
-the same session, 0.30 - 0.50 s (2.3 s for the first).  Needs an MI355X."""
+the same session, 0.30 - 0.50 s (2.3 s for the first).
+
+With the walk kinds, the frontier kinds and the padded device lists (IDX_NONE in a drawn subset of a call's index lists; search_fuzz.py's docstring),
+cases of 8 - 15 calls and seed 7632, measured on one MI355X, seconds per chunk 0 .. 5:
+    before (the parent's driver, seed 7100)   2.37  0.51  0.62  0.67  0.47  0.54
+    after                                     3.39  0.76  0.74  0.77  0.96  0.70
+and the CPU walk against the stand-in 4.0, 2.7, 3.2, 3.2, 3.3 and 2.4 s.  A soak of NGW_FUZZ_SECONDS=150 with NGW_FUZZ_SEED=9001
+walked 2104 cases and passed.  Needs an MI355X."""
 import os
 import time
 
@@ -28,10 +35,10 @@ import search_fuzz as F
 pytestmark = pytest.mark.gpu
 CHUNKS = 6
 BUDGET = float(os.environ.get('NGW_FUZZ_SECONDS', '0'))
-SEED = int(os.environ.get('NGW_FUZZ_SEED', '7100'))        # (tests/test_fuzz_parity.py starts from 1000)
-# the chunks of seed 7100 in which a guided call's table holds two members with one home bucket (tests/test_search_fuzz_cpu.py asserts the list from the
+SEED = int(os.environ.get('NGW_FUZZ_SEED', '7632'))        # (tests/test_fuzz_parity.py starts from 1000)
+# the chunks of seed 7632 in which a guided call's table holds two members with one home bucket (tests/test_search_fuzz_cpu.py asserts the list from the
 # model alone): there the device's table must report a member outside its home bucket - a probe chain the guided look-up has to walk
-PROBED_CHUNKS = (0, 1, 2, 4, 5)
+PROBED_CHUNKS = (0, 2, 3, 4, 5)
 
 
 def make_env(**kw):
@@ -63,5 +70,5 @@ def test_random_search_call_sequences_match_model(chunk):
             case += 1
         if time.time() >= t_end:
             break
-    if SEED == 7100 and chunk in PROBED_CHUNKS:
+    if SEED == 7632 and chunk in PROBED_CHUNKS:
         assert sum(displaced) >= 1, "no guided call of this chunk met a member key outside its home bucket"

@@ -1,18 +1,24 @@
 """The search fuzz's own evidence, without a GPU: the walk of tests/test_search_fuzz.py - same seeds, same chunks - on an oracle-backed stand-in
 (search_fuzz_standin.StandIn) passes, which pins the driver and proves every draw executable; over all chunks it executes every call kind and
-every form of the pair calls, and few calls are refused; and nine seeded faults in the stand-in each make run_case raise.
+every form of the pair calls, and few calls are refused; and eighteen seeded faults in the stand-in each make run_case raise.
 
-Coverage of the committed seed (NGW_FUZZ_SEED = 7100, six chunks, 67 cases; executed / refused per kind, then the pair calls per form and source) is
-asserted below as conditions and printed by `pytest -s`; the whole walk takes about 16 s on the CPU, 2.2 - 3.7 s per chunk (9 s before the guided
-kinds and the 'view' forms, which replay every playout once more for the views and twice more for the offer and the guided simulation).  Every kind
-is executed 4 - 40 times, every (pair call, form, source) cell 1 - 7 times, 2 of 618 calls are refused (successor keys beyond 34 x 34 maps) and no
-case ends in "Cannot place items".  The pair kinds and playouts weigh 6 - 7 in search_fuzz.KINDS so that every cell of the wider table stays covered.
+Coverage of the committed seed (NGW_FUZZ_SEED = 7632, six chunks, 67 cases of 8 - 15 calls; executed / refused per kind, then the pair calls per
+form and source) is asserted below as conditions and printed by `pytest -s`; the whole walk takes about 19 s on the CPU, 2.4 - 4.0 s per chunk.
+Every kind is executed 5 - 41 times, 2 of 756 calls are refused (successor keys beyond 34 x 34 maps), the largest table holds 649 keys and no
+case ends in "Cannot place items".  The pair kinds, playouts and the six newest kinds weigh 6 - 7 in search_fuzz.KINDS so that every cell of the
+wider table stays covered.
 
-The 49 guided pair calls and 5 guided playouts() of the walk (test_coverage_of_the_guided_calls, from guided_playout_oracle's event counts on the
-model side): both `outside` rules from slots and from envs, limits together with 'stop', both observations, calls without default weights, calls
-that offer nothing and find the table as earlier calls left it, maps of 24 x 24 and more; hits and misses each above 20 % of the executed steps,
-re-entries, zero-mass rows, steps whose action differs from the default's, steps that look up key 0 - reachable under KEY_INV alone (an empty
-inventory), never under KEY_INV | KEY_SELECTED, whose second term is never absent -, and tables in which two members share a home bucket."""
+The 37 guided pair calls, 38 frontier_twins calls and 3 guided playouts() of the walk (test_coverage_of_the_guided_calls, from
+guided_playout_oracle's event counts on the model side): both `outside` rules from slots and from envs, limits together with 'stop', both
+observations, calls without default weights, calls that offer nothing and find the table as earlier calls left it, maps of 24 x 24 and more; hits
+and misses each above 20 % of the executed steps, re-entries, zero-mass rows, steps whose action differs from the default's, steps that look up key
+0 - reachable under KEY_INV alone (an empty inventory), never under KEY_INV | KEY_SELECTED, whose second term is never absent -, and tables in
+which two members share a home bucket.
+
+test_coverage_of_the_new_kinds_and_the_padded_lists holds the walk to: every new kind (slot_walk, walk, walk_go, frontier_compact, frontier_step,
+frontier_twins) in every chunk, every call with a device list padded at least once, a list with every pair skipped met by each kernel that returns
+before its stage-in (expand, slot rollout, playout, successors, slot lidar), a short frontier limit, a compaction across a tile border from a
+non-zero byte offset, a walk_go with an unreachable item.  Seeded faults j - r: the skipped pair, the compaction, the allocation, the walk."""
 import collections
 import time
 
@@ -29,6 +35,41 @@ from test_search_fuzz import CHUNKS, PROBED_CHUNKS, SEED
 PAIR_KINDS = {'srollout': F.ROLLOUT_FORMS, 'srollout_kids': F.ROLLOUT_FORMS, 'splayout': F.PLAYOUT_FORMS, 'splayout_kids': F.PLAYOUT_FORMS}
 EVENTS = ('hits', 'misses', 'executed', 'reentries', 'zero_mass', 'differs', 'key0', 'displaced', 'shared_home')
 _walk = {}
+NOTES = ('(pad)', '(walk)', '(walk_go)', '(compact)', '(step)', '(twins)')
+_notes, _per_chunk = [], collections.Counter()
+NEW_KINDS = ('slot_walk', 'walk', 'walk_go', 'frontier_compact', 'frontier_step', 'frontier_twins')
+# the calls that take a device index list, and the kernels that return before their stage-in when a ballot finds no live pair, by the kinds that launch them
+LIST_KINDS = ('save', 'restore', 'fork', 'copy', 'expand', 'srollout', 'srollout_kids', 'splayout', 'splayout_kids', 'splayout_guided',
+              'splayout_guided_kids', 'slot_lidar', 'slot_view', 'slot_masks', 'slot_keys', 'slot_insert_keys', 'state_keys', 'succ_keys',
+              'insert_state_keys', 'insert_succ_keys', 'sample') + NEW_KINDS[:3] + NEW_KINDS[4:]        # (frontier_compact takes no index list)
+EARLY_RETURN = {'expand': ('expand', 'frontier_step'), 'slot rollout': ('srollout', 'srollout_kids', 'walk_go'),
+                'playout': ('splayout', 'splayout_kids', 'frontier_twins') + F.GUIDED_KINDS, 'successors': ('succ_keys', 'insert_succ_keys', 'frontier_step'),
+                'slot lidar': ('slot_lidar',)}
+
+
+def coverage_gaps(notes, per_chunk):
+    """The conditions on the new kinds and the padded lists that a walk does NOT meet (the committed seed: none)."""
+    gaps = []
+    for kind in NEW_KINDS:
+        gaps += ['%s not executed in chunk %d' % (kind, c) for c in range(CHUNKS) if per_chunk[(c, kind)] < 1]
+    padded = collections.Counter(k for note, _, k, _ in notes if note == '(pad)')
+    gaps += ['%s never padded' % k for k in LIST_KINDS if padded[k] < 1]
+    for kernel, kinds in sorted(EARLY_RETURN.items()):
+        if not any(note == '(pad)' and k in kinds and form[0] == 'all' for note, _, k, form in notes):
+            gaps.append('%s never met a list with every pair skipped' % kernel)
+    if not any(note == '(step)' and form[1] for note, _, _, form in notes):
+        gaps.append('frontier_step never met a short limit')
+    if not any(note == '(compact)' and form[0] > F.FRONTIER_TILE and form[1] != 0 for note, _, _, form in notes):
+        gaps.append('frontier_compact never crossed a tile border at a non-zero byte offset')
+    if not any(note == '(walk_go)' and form[0] > 0 for note, _, _, form in notes):
+        gaps.append('walk_go never met an unreachable item')
+    return gaps
+
+
+def test_coverage_of_the_new_kinds_and_the_padded_lists():
+    walk()
+    print(collections.Counter((note, k) + (form[:2] if note == '(pad)' else ()) for note, _, k, form in _notes))
+    assert coverage_gaps(_notes, _per_chunk) == []
 
 
 def walk():
@@ -42,8 +83,12 @@ def walk():
                     guided.append(dict(form, kind=status, chunk=chunk))
                 elif kind == '(table)':
                     sizes.append(form)
+                elif kind in NOTES:                       # what the padded calls, the walks and the frontiers met: (note, chunk, kind, details)
+                    _notes.append((kind, chunk, status, form))
                 else:
                     cov.update([(kind, status, form)])
+                    if status == 'executed':
+                        _per_chunk.update([(chunk, kind)])
             t0 = time.time()
             rs = np.random.RandomState(SEED + chunk)
             for case, cfg in enumerate(F.chunk_cfgs(chunk, CHUNKS)):
@@ -255,9 +300,87 @@ class ViewsRepeatBlockZero(SI.StandIn):
         return obs
 
 
+class NoneRaisesBadIndex(SI.StandIn):
+    """(j) a pair whose index is IDX_NONE raises F_BAD_INDEX."""
+
+    def _skip(self, gone):
+        self._flags |= SI.F_BAD_INDEX
+
+
+class NoneChildGoesToSlotZero(SI.StandIn):
+    """(k) the child of a pair whose destination is IDX_NONE is written into slot 0."""
+
+    def _live(self, parents, children, gone):
+        return parents != SI.NONE, np.where(children == SI.NONE, 0, children)
+
+
+class StaleRowsWhenAllSkipped(SI.StandIn):
+    """(l) a list with every pair skipped returns the rows of the row staged last instead of the skip values: the stale stage-in."""
+
+    @staticmethod
+    def _blank(out, gone, fill=0):
+        return out if gone.all() else SI.blank_rows(out, gone, fill)
+
+
+class CompactionLosesTheSecondTile(SI.StandIn):
+    """(m) the compaction ranks the hits of the second tile of 4096 flags from 0 again."""
+
+    @staticmethod
+    def _compact(flags, div, map, capacity):
+        first, second, count, full = SI.FO.compact(flags, div, map, capacity)
+        raw = np.ascontiguousarray(flags).reshape(-1).view(np.uint8)
+        hits = F.FRONTIER_TILE + np.flatnonzero(raw[F.FRONTIER_TILE:2 * F.FRONTIER_TILE])[:len(first)]      # (their entries land on the first tile's)
+        first, second = first.copy(), second.copy()
+        first[:len(hits)] = hits // div if map is None else np.asarray(map)[hits // div]
+        second[:len(hits)] = hits % div
+        return first, second, count, full
+
+
+class AllocLeavesTheCursor(SI.StandIn):
+    """(n) alloc hands out slots and leaves the cursor where it was."""
+
+    @staticmethod
+    def _alloc(count, cursor, limit, capacity):
+        slots, _, full = SI.FO.alloc(count, cursor, limit, capacity)
+        return slots, cursor, full
+
+
+class AllocIgnoresTheLimit(SI.StandIn):
+    """(o) alloc hands out slots beyond the limit."""
+
+    @staticmethod
+    def _alloc(count, cursor, limit, capacity):
+        return SI.FO.alloc(count, cursor, 1 << 30, capacity)
+
+
+class ForwardEntersAnything(SI.StandIn):
+    """(p) the walk lets Forward enter a cell that does not hold id 0."""
+
+    def _walk_moves(self, cells, S, p):
+        r, c, f = p
+        fr, fc = r + SI.DR[f], c + SI.DC[f]
+        return ([(fr, fc, f)] if 0 <= fr < S and 0 <= fc < S else []) + [(r, c, SI.LEFT[f]), (r, c, SI.RIGHT[f])]
+
+
+class GoalTiesByColumnFirst(SI.StandIn):
+    """(q) the walk breaks goal ties by (D, c, r, f)."""
+
+    def _goal_rank(self, d, r, c, f):
+        return (d, c, r, f)
+
+
+class LengthClampedToSteps(SI.StandIn):
+    """(r) walk_plans' `length` is clamped to `steps`."""
+
+    def _walk_length(self, length, steps):
+        return min(length, steps)
+
+
 # (the fault, the chunk of the committed walk that catches it: the first with a call that meets it)
-FAULTS = [(CommitsPlayout, 0), (StaleMasks, 0), (RestoreTakesEpisode, 2), (ExpandReadsSlots, 2), (AlwaysFresh, 0), (LooksUpTheKeyItLeaves, 0),
-          (StopRunsTheStep, 0), (DepthCountsEveryHit, 0), (ViewsRepeatBlockZero, 0)]
+FAULTS = [(CommitsPlayout, 0), (StaleMasks, 0), (RestoreTakesEpisode, 3), (ExpandReadsSlots, 1), (AlwaysFresh, 0), (LooksUpTheKeyItLeaves, 0),
+          (StopRunsTheStep, 0), (DepthCountsEveryHit, 0), (ViewsRepeatBlockZero, 0), (NoneRaisesBadIndex, 0), (NoneChildGoesToSlotZero, 0),
+          (StaleRowsWhenAllSkipped, 0), (CompactionLosesTheSecondTile, 1), (AllocLeavesTheCursor, 0), (AllocIgnoresTheLimit, 0),
+          (ForwardEntersAnything, 0), (GoalTiesByColumnFirst, 0), (LengthClampedToSteps, 0)]
 
 
 @pytest.mark.parametrize('faulty, chunk', [pytest.param(f, c, id=f.__name__) for f, c in FAULTS])
