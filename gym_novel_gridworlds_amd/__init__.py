@@ -9,7 +9,7 @@ reference's gym.Env surface.  Everything computes in hand-written HIP kernels re
 """
 from .envs import ENTRY_POINTS, BowV0Env, BowV1Env, PogostickV0Env, PogostickV1Env, make   # noqa: F401
 from .frontier import Frontier, alloc_reference, compact_reference   # noqa: F401
-from .key_table import KeyInsert, KeyTable                           # noqa: F401
+from .key_table import KeyBest, KeyInsert, KeyTable, Trace                           # noqa: F401
 from .novelty import NOVELTY_NAMES, apply_novelty                    # noqa: F401
 from .novelty_wrappers import inject_novelty                         # noqa: F401
 from .observation_wrappers import AgentMap, LidarInFront                    # noqa: F401

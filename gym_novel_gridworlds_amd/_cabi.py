@@ -32,6 +32,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_snapshot_playout_weighted', 'ngw_sample_actions', 'ngw_snapshot_rollout_path', 'ngw_snapshot_playout_path',
            'ngw_snapshot_rollout_traj', 'ngw_snapshot_playout_traj', 'ngw_snapshot_rollout_traj_views', 'ngw_snapshot_playout_traj_views', 'ngw_snapshot_playout_guided',
            'ngw_key_table_create', 'ngw_key_table_destroy', 'ngw_key_table_clear', 'ngw_key_table_insert', 'ngw_key_table_lookup', 'ngw_key_table_count',
+           'ngw_key_table_create_valued', 'ngw_key_table_insert_min', 'ngw_key_table_read', 'ngw_key_table_trace',
            'ngw_snapshot_walk', 'ngw_frontier_compact', 'ngw_frontier_alloc', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
@@ -218,6 +219,11 @@ def lib():
         L.ngw_key_table_insert.argtypes = [vp, vp, vp, i64, vp, vp]
         L.ngw_key_table_lookup.argtypes = [vp, vp, vp, i64, vp]
         L.ngw_key_table_count.argtypes = [vp, vp, C.POINTER(i64)]
+    if hasattr(L, 'ngw_key_table_create_valued'):
+        L.ngw_key_table_create_valued.argtypes = [vp, i64, u64, C.POINTER(vp)]
+        L.ngw_key_table_insert_min.argtypes = [vp, vp, vp, vp, vp, i64, vp, vp, vp]
+        L.ngw_key_table_read.argtypes = [vp, vp, vp, i64, vp, vp]
+        L.ngw_key_table_trace.argtypes = [vp, vp, vp, i64, i32, i32, vp, vp, vp]
     if hasattr(L, 'ngw_snapshot_playout_guided'):            # (the _traj_views playout, then the table, its weight rows, where + stride, depth, outside)
         L.ngw_snapshot_playout_guided.argtypes = L.ngw_snapshot_playout_traj_views.argtypes + [vp, vp, vp, i64, vp, i32]
     if hasattr(L, 'ngw_lookahead'):

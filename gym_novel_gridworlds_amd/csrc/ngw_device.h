@@ -782,6 +782,16 @@ struct NgwTable {
     uint8_t* fresh;               /* [count] */
     uint64_t base, mask;
     int64_t count;
+    /* a valued table's insert_min (read by ngw_table_insert_min_launch alone; last, so that the arguments of insert and lookup lie where they lay).
+     * best[]: mask + 1 words (uint32(value) ^ 0x80000000) << 32 | low half of the base + j that offered it, all ones = never valued; tag[]: mask + 1
+     * int32.  The probe also lowers best[where[j]] to position j's word unless values[j] is NGW_VALUE_NONE; the second launch sets improved[j] =
+     * (best[where[j]] == that word) and, where it is set and tags != nullptr, tag[where[j]] = tags[j].  The host keeps the low halves growing:
+     * (uint32)base + count <= 2^32 in every launch (ngw_table_renorm_launch before the call that would pass it). */
+    uint64_t* best;
+    int32_t* tag;
+    const int32_t* values;        /* [count] */
+    const int32_t* tags;          /* [count], or nullptr */
+    uint8_t* improved;            /* [count] */
 };
 #define NGW_TABLE_BLOCK 256      /* threads per workgroup: four waves, one key per lane */
 #ifdef __cplusplus
@@ -792,6 +802,53 @@ hipError_t ngw_table_insert_launch(const struct NgwTable* x, hipStream_t stream)
 extern "C"
 #endif
 hipError_t ngw_table_lookup_launch(const struct NgwTable* x, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_table_insert_min_launch(const struct NgwTable* x, hipStream_t stream);
+/* every valued word of best[0 .. buckets) keeps its value and gets the low half 0 */
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_table_renorm_launch(uint64_t* best, uint64_t buckets, hipStream_t stream);
+
+/* value[j], tag_out[j] = the value and the tag of bucket where[j] of a valued table; (NGW_VALUE_NONE, NGW_TAG_ROOT) for a bucket outside [0, mask],
+ * which also raises NGW_F_BAD_INDEX in *flags unless it is -1 or NGW_IDX_NONE.  One lane per query, one launch. */
+struct NgwTableRead {
+    const uint64_t* best;
+    const int32_t* tag;
+    uint32_t* flags;
+    const int32_t* where;         /* [count] */
+    int32_t* value;               /* [count] */
+    int32_t* tag_out;             /* [count] */
+    uint64_t mask;
+    int64_t count;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_table_read_launch(const struct NgwTableRead* x, hipStream_t stream);
+
+/* The chain of tags = parent_bucket * A + action from bucket where[j] to a bucket whose tag is NGW_TAG_ROOT, as a plan: plans[t * count + j] = move t
+ * for t < length[j], -1 behind it, root[j] = the bucket the chain ends in.  At most T links are followed: a longer chain (a cycle), where[j] of -1 or
+ * NGW_IDX_NONE -> length = root = -1 and a column of -1; a bucket outside the table, an empty one or a tag outside [0, (mask + 1) * A) likewise, and
+ * NGW_F_BAD_INDEX in *flags.  (mask + 1) * A <= 2^31 - 1.  One lane per query, one launch. */
+struct NgwTableTrace {
+    const uint64_t* key;
+    const int32_t* tag;
+    uint32_t* flags;
+    const int32_t* where;         /* [count] */
+    int32_t* plans;               /* [T][count] */
+    int32_t* length;              /* [count] */
+    int32_t* root;                /* [count] */
+    uint64_t mask;
+    int64_t count;
+    int32_t T, A;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_table_trace_launch(const struct NgwTableTrace* x, hipStream_t stream);
 
 /* Frontiers (ngw_frontier.inc, ngw_abi_frontier.cpp): flags -> an index list of fixed capacity, and slots for it, without the host knowing how many.
  * Compaction: the positions p with bytes[p] != 0 in ascending order, the k-th of them to first[k] = (map ? map[p / div] : p / div) and second[k] =

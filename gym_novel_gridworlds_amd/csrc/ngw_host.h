@@ -10,7 +10,7 @@
 //   ngw_abi_snapshot.cpp device-side snapshots: save / restore / fork env states by index (ngw_snapshot.inc), expand saved states into new slots (ngw_expand.inc),
 //                        roll action sequences out from saved states (ngw_slot_rollout.inc), observe saved states by slot (ngw_slot_observe.inc),
 //                        64-bit state keys of saved slots and live envs (ngw_keys.inc), walk distances and go-to plans of them (ngw_walk.inc)
-//   ngw_abi_table.cpp    device-side key tables: a hash set of such keys that outlives the call - insert, lookup, count, clear (ngw_table.inc)
+//   ngw_abi_table.cpp    device-side key tables: a hash set of such keys that outlives the call - insert, lookup, count, clear -, and a value and a tag per key: insert_min, read, trace (ngw_table.inc)
 //   ngw_abi_frontier.cpp device-side frontiers: flags compacted into index lists of fixed capacity, slots handed out for them (ngw_frontier.inc)
 //
 // Three rules hold in all of them:
@@ -65,12 +65,16 @@ struct ngw_snapshot {
     NgwSnapRows r{};
 };
 
-// A device-side key table (ngw_abi_table.cpp): key[buckets] | stamp[buckets] | the counter of stored keys, in ONE allocation of its handle.
+// A device-side key table (ngw_abi_table.cpp): key[buckets] | stamp[buckets] | the counter of stored keys, in ONE allocation of its handle; a
+// valued table (ngw_key_table_create_valued) holds best[buckets] (64-bit words) | tag[buckets] (int32) behind the counter in the same allocation.
 struct ngw_key_table {
     int64_t cap = 0;
     uint64_t buckets = 0;                 // the smallest power of two >= 2 * cap
     uint64_t* slab = nullptr;
-    uint64_t base = 0;                    // keys ever offered since the last clear: the stamp of position j of an insert is base + j
+    uint64_t base = 0;                    // first + keys ever offered since the last clear (+ what insert_min skipped to keep the low half from wrapping): the stamp of position j of an insert is base + j
+    uint64_t first = 0;                   // where base starts: first_sequence of ngw_key_table_create_valued, else 0
+    uint64_t epoch = 0;                   // a valued table: the high half of the positions whose low halves the words of best[] carry (insert_min renormalises when base has left it)
+    bool valued = false;
 };
 
 struct ngw_handle {

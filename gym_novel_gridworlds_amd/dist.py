@@ -169,10 +169,15 @@ class ShardedVecNovelGridworld:
         A key depends on the state alone, not on the env index or the rank, so keys compare across ranks."""
         return self.local.state_keys(envs, fields, device)
 
-    def key_table(self, capacity):
+    def key_table(self, capacity, values=False, **kw):
         """A device-side key table of this rank's shard (VecNovelGridworld.key_table): rank-local, no collective.  Keys are rank-independent
         by contract, so every rank may offer its own states' keys to its own table; the tables are not merged."""
-        return self.local.key_table(capacity)
+        return self.local.key_table(capacity, values, **kw)
+
+    def insert_state_keys_min(self, table, values, tags=None, envs=None, fields=KEY_STATE, device=False):
+        """The keys of this rank's envs offered to `table` with values and tags (VecNovelGridworld.insert_state_keys_min); values stay
+        rank-local like the table."""
+        return self.local.insert_state_keys_min(table, values, tags, envs, fields, device)
 
     def insert_state_keys(self, table, envs=None, fields=KEY_STATE, device=False):
         """The keys of this rank's envs offered to `table` (VecNovelGridworld.insert_state_keys)."""

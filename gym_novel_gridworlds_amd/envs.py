@@ -350,9 +350,9 @@ class _NovelGridworldEnv(_EnvBase):
         path = forward_keywords(path_keys, fields, rewards, masks, observe, view_size, table, table_weights, outside)
         return vec.playouts(n_playouts, steps, seed, device=device, weights=weights, **path).row(0)
 
-    def key_table(self, capacity):
+    def key_table(self, capacity, values=False, **kw):
         """A device-side key table of this env's batched backend (VecNovelGridworld.key_table): what playouts(table=...) takes."""
-        return self._backend().key_table(capacity)
+        return self._backend().key_table(capacity, values, **kw)
 
     def state_key(self, fields=KEY_STATE):
         """The 64-bit key of the current state as a Python int, computed on the device under the field selection `fields` (KEY_* bits,

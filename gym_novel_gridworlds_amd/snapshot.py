@@ -975,6 +975,15 @@ class Snapshot:
         found = table.insert(keys, device=device)
         return (keys if device else keys.cpu().numpy().view(np.uint64)), found
 
+    def insert_keys_min(self, table, slots, values, tags=None, fields=KEY_STATE, device=False):
+        """keys(slots, fields) offered to `table` (a KeyTable of the same env made with values=True) with one value - and one tag - per slot:
+        (keys, KeyBest(where, fresh, best)) - best[j]: slot slots[j] holds its state at a smaller value than the table knew (KeyTable.insert_min).
+        values, tags: as there.  The keys stay on the device between the two calls: no host wait in between.  device: as in insert_keys()."""
+        table._open_for(self.env)
+        keys = self.keys(slots, fields, device=True)
+        found = table.insert_min(keys, values, tags, device=device)
+        return (keys if device else keys.cpu().numpy().view(np.uint64)), found
+
     # ------------------------------------------------------------------ successor keys (include/ngw.h ngw_successor_keys)
     def successor_keys(self, slots=None, fields=KEY_STATE, device=False, reports=True):
         """The key of every action's child of saved slots, with no child stored: a SuccessorKeys whose fields are [count, A] - keys[j, a] is

@@ -1018,12 +1018,14 @@ class VecNovelGridworld:
         return words if device else words.cpu().numpy().view(np.uint64)
 
     # ------------------------------------------------------------------ device-side key tables (key_table.py, include/ngw.h ngw_key_table_*)
-    def key_table(self, capacity):
+    def key_table(self, capacity, values=False, **kw):
         """A hash set of 64-bit keys on the device with room for `capacity` of them: KeyTable.insert / lookup / clear / close, len().  It
-        answers "have I seen this state before?" across calls, where Snapshot.unique() groups equal states within one call.  It belongs
-        to this env and is closed with it, and by an in-place rebuild() (inject_novelty)."""
+        answers "have I seen this state before?" across calls, where Snapshot.unique() groups equal states within one call.  values=True:
+        the table also keeps the smallest int32 value offered with each key and a tag beside it - KeyTable.insert_min / read / get /
+        trace: "is this the cheapest way I have found to this state, and which way was it?"; a table without values costs what it always
+        cost.  It belongs to this env and is closed with it, and by an in-place rebuild() (inject_novelty)."""
         from .key_table import KeyTable
-        t = KeyTable(self, capacity)
+        t = KeyTable(self, capacity, values, **kw)
         self.__dict__.setdefault('_key_tables', []).append(t)
         return t
 
@@ -1033,6 +1035,15 @@ class VecNovelGridworld:
         table._open_for(self)
         keys = self.state_keys(envs, fields, device=True)
         found = table.insert(keys, device=device)
+        return (keys if device else keys.cpu().numpy().view(np.uint64)), found
+
+    def insert_state_keys_min(self, table, values, tags=None, envs=None, fields=KEY_STATE, device=False):
+        """state_keys(envs, fields) offered to `table` (a KeyTable of this env made with values=True) with `values` and `tags`: (keys,
+        KeyBest(where, fresh, best)) - Snapshot.insert_keys_min() for the envs' CURRENT states; the keys stay on the device between the two
+        calls."""
+        table._open_for(self)
+        keys = self.state_keys(envs, fields, device=True)
+        found = table.insert_min(keys, values, tags, device=device)
         return (keys if device else keys.cpu().numpy().view(np.uint64)), found
 
     def _keeper(self):

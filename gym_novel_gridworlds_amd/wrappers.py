@@ -234,10 +234,10 @@ class LimitActions(NoveltyWrapper):
             return play._replace(first_action=lut[play.first_action.long()])
         return play._replace(first_action=np.asarray(ids, np.int32)[play.first_action])
 
-    def key_table(self, capacity):
+    def key_table(self, capacity, values=False, **kw):
         """A key table for guided playouts() under this wrapper: VecNovelGridworld.key_table on the limited env the playouts run on.  It lives as
         long as that env does (until close(), or until the adapter's backend is rebuilt)."""
-        return self._limited_env()[0].key_table(capacity)
+        return self._limited_env()[0].key_table(capacity, values, **kw)
 
     def close(self):
         kept = self.__dict__.pop('_playout_env', None)

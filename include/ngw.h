@@ -940,7 +940,7 @@ int ngw_snapshot_playout_traj_views(ngw_handle* h, ngw_snapshot* src, const int3
 
 /* Key table: an open-addressing hash set of 64-bit keys in device memory - "have I seen this state BEFORE?" across the calls of a search that
  * runs many iterations (transposition tables, duplicate removal in breadth-first solvers, Go-Explore archives, count-based bonuses).  A table
- * belongs to the handle that created it; it stores keys and nothing else: a caller keeps what it wants per state (visit counts, the best return,
+ * belongs to the handle that created it; it stores keys and nothing else (but see the valued tables below): a caller keeps what it wants per state (visit counts, the best return,
  * the archive slot) in arrays of its own of `buckets` entries, indexed by `where`.
  *   buckets  the smallest power of two >= 2 * capacity (not stored in the ABI: compute it); capacity in [1, 2^29].
  *   insert   for j < count: where[j] (int32) = the bucket that holds keys[j], and fresh[j] (uint8, 0 / 1) = 1 exactly when keys[j] was not in the
@@ -969,6 +969,53 @@ int ngw_key_table_clear(ngw_handle* h, ngw_key_table* t);
 int ngw_key_table_insert(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_dev, int64_t count, int32_t* where_dev, uint8_t* fresh_dev);
 int ngw_key_table_lookup(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_dev, int64_t count, int32_t* where_dev);
 int ngw_key_table_count(ngw_handle* h, ngw_key_table* t, int64_t* n);
+
+/* Valued key tables: the table also keeps, per key, the SMALLEST int32 value ever offered with it and an int32 tag stored by the offer that brought
+ * that value - "is this the best way I have found to this state?" for uniform-cost, A* and label-correcting searches, and Go-Explore archives that
+ * keep the better trajectory into a cell; with tags that name the parent, the way back to the root (ngw_key_table_trace).
+ *   create_valued  as ngw_key_table_create, and the table holds a value and a tag per bucket: NGW_VALUE_NONE (never valued) and NGW_TAG_ROOT until
+ *            an offer stores others.  A table of ngw_key_table_create holds neither, and insert_min / read / trace refuse it.  first_sequence (at
+ *            most 2^62) is where the table's position counter starts (and starts again after a clear); EVERY result of every call is the same for
+ *            every value of it - it exists so that a test can place the renormalising pass below where it wants it.
+ *   insert_min     an insert that also offers values.  where[j] and fresh[j] are exactly what ngw_key_table_insert stores for the same keys: the same
+ *            buckets, the same stamps, the same NGW_F_TABLE_FULL, the same treatment of key 0.  For a key k let before(k) be the value the table held
+ *            for it before the call (NGW_VALUE_NONE if k was absent or never valued), and the call's OFFER for k the position with the smallest
+ *            (values[j], j) among the positions j with keys[j] = k, where[j] >= 0 and values[j] != NGW_VALUE_NONE.  Then
+ *                best[j] (uint8, 0 / 1) = 1  exactly when j is that offer AND values[j] < before(k)
+ *            - strictly: an equal value of a later call is no improvement -, afterwards the table holds min(before(k), values[offer]) for k, and where
+ *            best[j] = 1 and tags_dev != NULL it holds tags[j] as k's tag (otherwise the tag stays).  A position whose value is NGW_VALUE_NONE makes
+ *            no offer: it behaves as under ngw_key_table_insert (best = 0).  Every other int32 is an ordinary value: negative ones, INT32_MIN.  `best`
+ *            is deterministic: it depends neither on the order in which the device runs the positions nor on which bucket a key got.  At most one
+ *            position per key and call has best = 1, so best - through ngw_frontier_compact - is the list of states to (re)open.
+ *            count in [0, 2^31 - 1].  Two kernel launches, as insert; once per 2^32 positions offered to the table one more pass over its buckets.
+ *   read     value[j], tag[j] = the value and the tag of bucket where[j] (what insert / insert_min / lookup reported).  A bucket of -1 or NGW_IDX_NONE
+ *            gives (NGW_VALUE_NONE, NGW_TAG_ROOT); so does any other bucket outside [0, buckets), which also raises NGW_F_BAD_INDEX.  A bucket that
+ *            holds no key, or a key never valued, reads as (NGW_VALUE_NONE, NGW_TAG_ROOT) too.  One kernel launch; it changes nothing.
+ *   trace    reads the tags as tag = parent_bucket * n_actions + action and NGW_TAG_ROOT as "a root": for j < count, length[j] = the number of links
+ *            from bucket where[j] to the first bucket on its chain whose tag is NGW_TAG_ROOT, root[j] = that bucket, and plans[t * count + j] (int32
+ *            [steps][count], step-major: the layout ngw_snapshot_rollout takes) = the action of link t counted FROM THE ROOT for t < length[j], -1 for
+ *            length[j] <= t < steps - the plan that leads from the root's state to the state of where[j], in execution order.  Tags are the caller's
+ *            data and may form cycles, so at most `steps` links are followed: a chain that has not reached a root after `steps` links gives length =
+ *            -1, root = -1 and a column of -1, and raises nothing.  where[j] of -1 or NGW_IDX_NONE gives the same, without a flag.  A bucket on the
+ *            chain (where[j] included) outside [0, buckets) or without a key, or a tag other than NGW_TAG_ROOT outside [0, buckets * n_actions), gives
+ *            the same and raises NGW_F_BAD_INDEX; no tag is used as an address before it is checked.  steps in [0, NGW_TRACE_MAX_STEPS], n_actions >=
+ *            1 (the caller's convention, normally the spec's), buckets * n_actions <= 2^31 - 1, count in [0, 2^31 - 1].  One kernel launch, one lane
+ *            per query; it changes nothing.
+ * ngw_key_table_clear wipes values and tags with the keys; ngw_key_table_insert on a valued table leaves values and tags alone (a key it stores is
+ * "never valued").  keys_dev / where_dev / fresh_dev as for insert; values_dev, tags_dev (int32 [count]; tags_dev may be NULL), best_dev (uint8
+ * [count]), value_dev, tag_dev, length_dev, root_dev (int32 [count]) and plans_dev are DEVICE memory; exactly the entries named are written.  count
+ * == 0 is a no-op.  All calls are enqueued on the handle's stream and do not wait; they write no env state.
+ * NGW_E_INVALID_ARG: as for insert, and: a table without values; NULL values, best or outputs; first_sequence beyond 2^62; count, steps or n_actions
+ * outside their ranges; buckets * n_actions > 2^31 - 1. */
+#define NGW_VALUE_NONE INT32_MAX
+#define NGW_TAG_ROOT (-1)
+#define NGW_TRACE_MAX_STEPS 65536
+int ngw_key_table_create_valued(ngw_handle* h, int64_t capacity, uint64_t first_sequence, ngw_key_table** out);
+int ngw_key_table_insert_min(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_dev, const int32_t* values_dev, const int32_t* tags_dev /* NULL: none */,
+                             int64_t count, int32_t* where_dev, uint8_t* fresh_dev, uint8_t* best_dev);
+int ngw_key_table_read(ngw_handle* h, ngw_key_table* t, const int32_t* where_dev, int64_t count, int32_t* value_dev, int32_t* tag_dev);
+int ngw_key_table_trace(ngw_handle* h, ngw_key_table* t, const int32_t* where_dev, int64_t count, int32_t steps, int32_t n_actions, int32_t* plans_dev,
+                        int32_t* length_dev, int32_t* root_dev);
 
 /* Frontiers: the step `flags -> the index lists of the next call` of a search loop (expand -> keys -> insert -> next frontier), on the device.  The
  * number of hits stays in device memory: the lists have a fixed `capacity`, the live entries come first and NGW_IDX_NONE (above) pads the rest, so
