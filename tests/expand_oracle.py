@@ -3,6 +3,8 @@ autoreset off - its state after the step is the expected child, no reset ever ru
 autoreset setting and horizon - its outputs are the expected reports, the info words assembled as tests/plan_oracle.py does.  A pair with
 an action id outside the list expects the parent's row and zero reports.  Nothing here comes from the HIP path (tests/test_expand*.py
 compare the device's children and reports with these)."""
+import functools
+
 import numpy as np
 
 import mask_oracle as M
@@ -41,11 +43,8 @@ def oracle_expand(spec, rows, parents, actions, autoreset=False, horizon=0):
     r = Oracle(cs, count, autoreset=autoreset, horizon=horizon)  # the reports: what the handle's own step would say
     r.st = parent.copy()
     r.step(act)
-    goal_done = (r.info >> np.uint32(1)) & np.uint32(1)
-    word = (r.result.astype(np.uint32) | (goal_done << np.uint32(1)) | (r.cost_code.astype(np.uint32) << np.uint32(2)) |
-            (r.msg_code.astype(np.uint32) << np.uint32(8)) | (r.msg_arg.astype(np.uint32) << np.uint32(16)))
     reports = dict(reward=np.where(valid, r.reward, 0).astype(np.int32), done=r.done.astype(bool) & valid,
-                   result=r.result.astype(bool) & valid, info=np.where(valid, word, 0).astype(np.uint32))
+                   result=r.result.astype(bool) & valid, info=np.where(valid, T.info_word(r), 0).astype(np.uint32))
     return children, reports
 
 
@@ -74,24 +73,28 @@ class _BoundExpandSnapshot(SO._BoundSnapshot):
     """snapshot_oracle's bound snapshot with Snapshot.expand / expand_all: the product's host checks (snapshot.check_expand,
     all_actions_pairs), the oracle's step."""
 
-    def expand(self, parents, actions, children, from_envs=False, source=None, device=False):
-        from gym_novel_gridworlds_amd.snapshot import Expansion, check_expand
+    def _source(self, call, from_envs, source):
+        """The parents of a call: -> (their rows, how many there are, are they this snapshot's own slots)."""
         self._open()
         if source is not None and from_envs:
-            raise ValueError("expand: give either source or from_envs")
+            raise ValueError("%s: give either source or from_envs" % call)
+        if from_envs:
+            return self.env.o.st, self.env.num_envs, False
         src = self if source is None else source
-        if not from_envs:
-            if not isinstance(src, _BoundExpandSnapshot):
-                raise ValueError("source: a Snapshot expected")
-            src._open()
-            if src.env is not self.env:
-                raise ValueError("source: a snapshot of another env")
+        if not isinstance(src, _BoundExpandSnapshot):
+            raise ValueError("source: a Snapshot expected")
+        src._open()
+        if src.env is not self.env:
+            raise ValueError("source: a snapshot of another env")
+        return src.model.rows, src.capacity, src is self
+
+    def expand(self, parents, actions, children, from_envs=False, source=None, device=False):
+        from gym_novel_gridworlds_amd.snapshot import Expansion, check_expand
+        rows, n_parents, own = self._source('expand', from_envs, source)
         env = self.env
-        n_parents = env.num_envs if from_envs else src.capacity
-        p, a, c, count = check_expand(parents, actions, children, n_parents, self.capacity, len(env.spec.actions_id), not from_envs and src is self)
+        p, a, c, count = check_expand(parents, actions, children, n_parents, self.capacity, len(env.spec.actions_id), own)
         p = np.arange(count) if p is None else p
         c = np.arange(count) if c is None else c
-        rows = env.o.st if from_envs else src.model.rows
         kids, rep = oracle_expand(env.spec, rows, p, a, env.o.autoreset, env.o.horizon)
         for k in STATE_KEYS:
             self.model.rows[k][c] = kids[k]
@@ -112,16 +115,7 @@ class OracleVecExpand(SO.OracleVecSnap):
         return s
 
 
-def sharded_on_oracle(**kw):
-    """The product's ShardedVecNovelGridworld with its local env replaced by OracleVecExpand (no GPU)."""
-    from gym_novel_gridworlds_amd.dist import ShardedVecNovelGridworld
-
-    class OracleSharded(ShardedVecNovelGridworld):
-        def _make_local(self, device=None, spec=None, **k):
-            k = {a: b for a, b in k.items() if a in ('num_envs', 'seed', 'autoreset', 'horizon', 'env_index_base')}
-            return OracleVecExpand(spec, **k)
-
-    return OracleSharded(**kw)
+sharded_on_oracle = functools.partial(T.sharded_on_oracle, OracleVecExpand)
 
 
 def good_seed(spec, n, lo=4):

@@ -2,9 +2,9 @@
 simulation.  Per step of the pairs still alive: the key of the row each pair is in (state_keys.keys_of_rows on the oracle's rows), membership of that
 key in the table - modelled as a SET of keys -, the weights (a function f(key) of the key where it is a member, the default vector or zeros where
 not), the mask word (trajectory_oracle.mask_words: the mask oracle with the all-actions replacement), the playout's Philox word
-(playout.playout_words), the weighted choice (sample.choose_weighted), and one step through slot_rollout_oracle's helpers.  Everything else a result
-holds - reports, keys, rewards, masks, observations, end rows - is trajectory_oracle.oracle_traj's replay of the chosen actions, cut where the
-simulation stopped.  The oracle needs no bucket numbers: the tests write f(key) into row where_of(key) after the insert, and compare the `where`
+(playout.playout_words), the weighted choice (sample.choose_weighted) - a chooser - and one step of pairs_oracle.step_pairs, whose record holds
+everything else a result does - reports, keys, rewards, end rows, the rows visited -; the observations are trajectory_oracle.observed's on those rows.
+The oracle needs no bucket numbers: the tests write f(key) into row where_of(key) after the insert, and compare the `where`
 output with what insert / lookup returned.  Nothing here uses the device's own step, mask, key, probe or choice."""
 import functools
 
@@ -12,16 +12,16 @@ import numpy as np
 
 import expand_oracle as XO
 import ngw_testlib as T
+import pairs_oracle as PA
 import path_key_oracle as KO
 import playout_oracle as PO
-import slot_rollout_oracle as RO
 import trajectory_oracle as TO
 from gym_novel_gridworlds_amd.playout import playout_words
 from gym_novel_gridworlds_amd.sample import bad_weights, choose_weighted
 from gym_novel_gridworlds_amd.state_keys import KEY_STATE, KEY_STEP_COUNT, keys_of_rows, mix64
 from oracle.ngw_oracle import Oracle
 
-STATE_KEYS = RO.STATE_KEYS
+STATE_KEYS = PA.STATE_KEYS
 COUNT, STEPS, N, HORIZON = 130, 12, 20, 9           # two full waves and two lanes, repeated parents
 SEED, FILL_SEED = 0x6D1DED0123456789, 0x7AB1E5EED0000001
 LIMITED = ('Break', 'Forward', 'Left', 'Right', 'Craft_plank', 'Craft_stick')
@@ -99,7 +99,7 @@ def inputs(name, count=COUNT, steps=STEPS):
     hz = HORIZON if auto else 0
     _, _, acts, _ = PO.oracle_playout(spec, o.st, parents, steps, FILL_SEED, 0, auto, hz)
     keys, _, _, _, _ = KO.oracle_path(spec, o.st, parents, acts, None, auto, hz, fields)
-    own = keys_of_rows(RO._rows_of(XO.rows_state(spec, o.st, parents)), fields)
+    own = keys_of_rows(PA.rows_of(XO.rows_state(spec, o.st, parents)), fields)
     offered = np.concatenate([own, keys[0::2].reshape(-1)])              # (the even steps' path keys: the states steps 0, 2, .. leave)
     members = []
     seen = set()
@@ -116,58 +116,42 @@ def oracle_guided(spec, rows, parents, steps, seed, members, row_fn, default=Non
     looked up at every executed step, 0 elsewhere), 'hit' bool [T, count], 'depth' int32 [count], 'bad' (a row that was read holds a bad weight) and
     'events' extended by the coverage counts: hits, misses, executed, reentries (pairs), zero_mass (in-table steps whose row had mass 0), differs
     (in-table steps whose action is not what the default weights give on the same word)."""
-    cs = spec.compile()
-    A = cs.n_actions
+    A = spec.compile().n_actions
     member = set(int(k) for k in np.asarray(members, np.uint64).tolist())
-    parents = np.asarray(parents, np.int64)
-    count = len(parents)
     dflt = np.zeros(A, np.float32) if default is None else np.asarray(default, np.float32)
-    lim = np.full(count, steps, np.int64) if limits is None else np.clip(np.asarray(limits, np.int64), 0, steps)
-    parent = XO.rows_state(spec, rows, parents)
-    live_rows, end_rows = RO._rows_of(parent), RO._rows_of(parent)
-    actions = np.full((steps, count), -1, np.int32)
-    before, hit, ran = np.zeros((steps, count), np.uint64), np.zeros((steps, count), bool), np.zeros((steps, count), bool)
-    ev = dict(zero_mass=0, differs=0)
-    bad = False
-    alive = np.ones(count, bool)
-    for t in range(steps):
-        alive &= lim > t
-        idx = np.nonzero(alive)[0]
-        if not idx.size:
-            break
-        keys = keys_of_rows({k: end_rows[k][idx] for k in STATE_KEYS}, fields)
+    ev = dict(zero_mass=0, differs=0, bad=False)
+
+    def choose(t, idx, now):
+        """The guided rule on the rows the pairs are in: the table look-up, `stop`, the weighted choice on the playout's own Philox word."""
+        keys = keys_of_rows(now, fields)
         inside = np.array([int(k) in member for k in keys.tolist()], bool)
-        if stop:
-            alive[idx[~inside]] = False
-            idx, keys, inside = idx[inside], keys[inside], inside[inside]
-            if not idx.size:
-                continue
-        now = {k: end_rows[k][idx] for k in STATE_KEYS}
-        m = TO.mask_words(spec, now)
-        W = np.stack([row_fn(k) if h else dflt for k, h in zip(keys.tolist(), inside)]).astype(np.float32)
-        bad = bad or bad_weights(W)
-        pairs = (first_pair + idx).astype(np.uint64)
-        words = playout_words(seed, pairs, t)
-        a, mass, _ = choose_weighted(m, W, seed, pairs, t, A, words=words)
-        a_default, _, _ = choose_weighted(m, np.broadcast_to(dflt, W.shape), seed, pairs, t, A, words=words)
-        ev['zero_mass'] += int((inside & (mass == 0)).sum())
-        ev['differs'] += int((inside & (a != a_default)).sum())
-        actions[t, idx], before[t, idx], hit[t, idx], ran[t, idx] = a, keys, inside, True
-        r = RO._step_rows(spec, cs, live_rows, idx, a, autoreset, horizon)
-        RO._step_rows(spec, cs, end_rows, idx, a, False, 0)
-        alive[idx[r.done.astype(bool)]] = False
-    length = ran.sum(0)
-    e = TO.oracle_traj(spec, rows, parents, actions, length, autoreset, horizon, fields, lc)
-    assert (e['reports']['length'] == length).all()
-    lead = np.cumprod(hit & ran, 0)
+        on = inside if stop else np.ones(len(idx), bool)
+        a, m = np.full(len(idx), -1, np.int32), np.zeros(len(idx), np.uint64)
+        if on.any():
+            m[on] = TO.mask_words(spec, {k: now[k][on] for k in STATE_KEYS})
+            W = np.stack([row_fn(k) if h else dflt for k, h in zip(keys[on].tolist(), inside[on])]).astype(np.float32)
+            ev['bad'] = ev['bad'] or bad_weights(W)
+            pairs = (first_pair + idx[on]).astype(np.uint64)
+            words = playout_words(seed, pairs, t)
+            a[on], mass, _ = choose_weighted(m[on], W, seed, pairs, t, A, words=words)
+            a_default, _, _ = choose_weighted(m[on], np.broadcast_to(dflt, W.shape), seed, pairs, t, A, words=words)
+            ev['zero_mass'] += int((inside[on] & (mass == 0)).sum())
+            ev['differs'] += int((inside[on] & (a[on] != a_default)).sum())
+        return a, dict(stop=~on, masks=m, before=keys, hit=inside)
+
+    e = TO.observed(spec, PA.step_pairs(spec, rows, parents, steps, choose, limits, autoreset, horizon, fields, record=True), lc, masks=False)
+    ran, length = e.pop('ran'), e['reports']['length']
+    hit = PA.kept(e, 'hit', bool)
     reentries = 0
-    for j in range(count):
+    for j in range(len(length)):
         h = hit[:length[j], j]
         miss = np.nonzero(~h)[0]
         reentries += int(miss.size > 0 and h[miss[0]:].any())
-    ev.update(hits=int((hit & ran).sum()), misses=int((~hit & ran).sum()), executed=int(ran.sum()), reentries=reentries)
-    e['events'] = dict(e['events'], **ev)
-    e.update(actions=actions, before=before, hit=hit, depth=lead.sum(0).astype(np.int32), bad=bool(bad))
+    e['events'].update(zero_mass=ev['zero_mass'], differs=ev['differs'], hits=int(hit.sum()), misses=int((~hit & ran).sum()), executed=int(ran.sum()),
+                       reentries=reentries)
+    e.update(masks=PA.kept(e, 'masks', np.uint64), before=PA.kept(e, 'before', np.uint64), hit=hit, depth=np.cumprod(hit, 0).sum(0).astype(np.int32),
+             bad=bool(ev['bad']))
+    del e['parent_rows']
     return e
 
 

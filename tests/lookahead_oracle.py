@@ -21,10 +21,7 @@ def oracle_lookahead(spec, st, autoreset=False, horizon=0):
         o = Oracle(cs, n, autoreset=autoreset, horizon=horizon)
         o.st = st.copy()
         o.step(np.full(n, a, np.int32))
-        goal_done = (o.info >> np.uint32(1)) & np.uint32(1)
-        reward[:, a], done[:, a], result[:, a] = o.reward, o.done.astype(bool), o.result.astype(bool)
-        info[:, a] = (o.result.astype(np.uint32) | (goal_done << np.uint32(1)) | (o.cost_code.astype(np.uint32) << np.uint32(2)) |
-                      (o.msg_code.astype(np.uint32) << np.uint32(8)) | (o.msg_arg.astype(np.uint32) << np.uint32(16)))
+        reward[:, a], done[:, a], result[:, a], info[:, a] = o.reward, o.done.astype(bool), o.result.astype(bool), T.info_word(o)
     return dict(reward=reward, done=done, result=result, info=info)
 
 

@@ -652,3 +652,22 @@ def oracle_sharded(**kw):
             return out
 
     return OracleSharded(**kw)
+
+
+def info_word(o):
+    """uint32 [n]: the packed info word of the oracle's last step - result | goal_done << 1 | cost_code << 2 | msg_code << 8 | msg_arg << 16."""
+    goal_done = (o.info >> np.uint32(1)) & np.uint32(1)
+    return (o.result.astype(np.uint32) | (goal_done << np.uint32(1)) | (o.cost_code.astype(np.uint32) << np.uint32(2)) |
+            (o.msg_code.astype(np.uint32) << np.uint32(8)) | (o.msg_arg.astype(np.uint32) << np.uint32(16)))
+
+
+def sharded_on_oracle(cls, **kw):
+    """The product's ShardedVecNovelGridworld with its local env replaced by the oracle-backed stand-in `cls` (no GPU)."""
+    from gym_novel_gridworlds_amd.dist import ShardedVecNovelGridworld
+
+    class OracleSharded(ShardedVecNovelGridworld):
+        def _make_local(self, device=None, spec=None, **k):
+            k = {a: b for a, b in k.items() if a in ('num_envs', 'seed', 'autoreset', 'horizon', 'env_index_base')}
+            return cls(spec, **k)
+
+    return OracleSharded(**kw)

@@ -25,9 +25,7 @@ def oracle_plans(spec, st, plans, autoreset=False, horizon=0):
         alive = np.ones(n, bool)
         for t in range(steps):
             o.step(np.ascontiguousarray(plans[:, p, t], np.int32))
-            goal_done = (o.info >> np.uint32(1)) & np.uint32(1)
-            word = (o.result.astype(np.uint32) | (goal_done << np.uint32(1)) | (o.cost_code.astype(np.uint32) << np.uint32(2)) |
-                    (o.msg_code.astype(np.uint32) << np.uint32(8)) | (o.msg_arg.astype(np.uint32) << np.uint32(16)))
+            word = T.info_word(o)
             done = o.done.astype(bool)
             ret[alive, p] += o.reward[alive]
             length[alive, p] += 1

@@ -1,12 +1,13 @@
 """Expected valid-action random playouts from the unmodified CPU oracle.  Per step of the pairs still alive: the mask words of their current
 rows (mask_oracle.oracle_mask_words: every action stepped on a copy), the Philox word from the oracle library's own generator
-(ngwo_philox4x32_10) under the counter and key of include/ngw.h, the k-th set bit, and one step through slot_rollout_oracle's helpers - in two
-copies, as there: one under the handle's autoreset setting and horizon for the reports, one that never resets for the end rows.  Nothing
+(ngwo_philox4x32_10) under the counter and key of include/ngw.h, the k-th set bit - a chooser - and one step of pairs_oracle.step_pairs, in two
+copies: one under the handle's autoreset setting and horizon for the reports, one that never resets for the end rows.  Nothing
 here imports gym_novel_gridworlds_amd.playout or touches the HIP path (tests/test_playout*.py compare both with these)."""
 import numpy as np
 
 import expand_oracle as XO
 import mask_oracle as M
+import pairs_oracle as PA
 import slot_rollout_oracle as RO
 from oracle.ngw_oracle import lib
 
@@ -39,41 +40,28 @@ def choose(mask_word, seed, pair, t, n_actions):
     raise AssertionError("k beyond the set bits")
 
 
+def drawn(spec, seed, first_pair, pick):
+    """A chooser for pairs_oracle.step_pairs: the mask word of every pair's current row (0 where no action would succeed) and
+    pick(word, pair number, t) -> the action."""
+    def chooser(t, idx, now):
+        words = M.oracle_mask_words(spec, XO.rows_state(spec, now, np.arange(len(idx))))
+        return np.array([pick(w, first_pair + int(j), t) for w, j in zip(words, idx)], np.int32), dict(masks=words)
+    return chooser
+
+
+def played(e):
+    """step_pairs' record as the playout oracles return it."""
+    return e['ends'], dict(e['reports'], first_action=e['actions'][0].copy()), e['actions'], PA.kept(e, 'masks', np.uint64)
+
+
 def oracle_playout(spec, rows, parents, steps, seed, first_pair=0, autoreset=False, horizon=0):
     """-> (ends, reports, actions, masks): ends = {key: [count, ...]} the seven arrays of the rows as the last executed step leaves them,
     reports = {'ret' int32, 'length' int32, 'ended' bool, 'info' uint32, 'first_action' int32}, each [count], actions int32 [steps, count]
     (-1: not executed), masks uint64 [steps, count]: the mask word before each executed step (0 elsewhere - and where no action would
     succeed).  `rows` is untouched."""
-    cs = spec.compile()
-    A = cs.n_actions
-    parents = np.asarray(parents, np.int64)
-    count = len(parents)
-    parent = XO.rows_state(spec, rows, parents)
-    live_rows, end_rows = RO._rows_of(parent), RO._rows_of(parent)
-    ret, length = np.zeros(count, np.int32), np.zeros(count, np.int32)
-    ended, info = np.zeros(count, bool), np.zeros(count, np.uint32)
-    actions, masks = np.full((steps, count), -1, np.int32), np.zeros((steps, count), np.uint64)
-    alive = np.ones(count, bool)
-    for t in range(steps):
-        idx = np.nonzero(alive)[0]
-        if not idx.size:
-            break
-        words = M.oracle_mask_words(spec, XO.rows_state(spec, end_rows, idx))
-        acts = np.array([choose(w, seed, first_pair + int(j), t, A) for w, j in zip(words, idx)], np.int32)
-        masks[t, idx], actions[t, idx] = words, acts
-        length[idx] += 1
-        r = RO._step_rows(spec, cs, live_rows, idx, acts, autoreset, horizon)
-        goal_done = (r.info >> np.uint32(1)) & np.uint32(1)
-        info[idx] = (r.result.astype(np.uint32) | (goal_done << np.uint32(1)) | (r.cost_code.astype(np.uint32) << np.uint32(2)) |
-                     (r.msg_code.astype(np.uint32) << np.uint32(8)) | (r.msg_arg.astype(np.uint32) << np.uint32(16)))
-        ret[idx] += r.reward
-        RO._step_rows(spec, cs, end_rows, idx, acts, False, 0)
-        done = r.done.astype(bool)
-        ended[idx[done]] = True
-        alive[idx[done]] = False
-    ends = {k: end_rows[k].astype(getattr(parent, k).dtype) for k in STATE_KEYS}
-    assert (ends['episode'] == parent.episode).all()
-    return ends, dict(ret=ret, length=length, ended=ended, info=info, first_action=actions[0].copy()), actions, masks
+    A = spec.compile().n_actions
+    return played(PA.step_pairs(spec, rows, parents, steps, drawn(spec, seed, first_pair, lambda w, pair, t: choose(w, seed, pair, t, A)), None,
+                                autoreset, horizon))
 
 
 def assert_playout(got, exp, exp_actions, where):
@@ -95,21 +83,10 @@ class _BoundPlayoutSnapshot(RO._BoundRolloutSnapshot):
 
     def playout(self, parents, steps, seed, children=None, from_envs=False, source=None, first_pair=0, record=False, device=False):
         from gym_novel_gridworlds_amd.snapshot import check_playout
-        self._open()
-        if source is not None and from_envs:
-            raise ValueError("playout: give either source or from_envs")
-        src = self if source is None else source
-        if not from_envs:
-            if not isinstance(src, XO._BoundExpandSnapshot):
-                raise ValueError("source: a Snapshot expected")
-            src._open()
-            if src.env is not self.env:
-                raise ValueError("source: a snapshot of another env")
+        rows, n_parents, own = self._source('playout', from_envs, source)
         env = self.env
-        n_parents = env.num_envs if from_envs else src.capacity
-        p, c, count, steps = check_playout(parents, steps, children, n_parents, self.capacity, not from_envs and src is self)
+        p, c, count, steps = check_playout(parents, steps, children, n_parents, self.capacity, own)
         p = np.arange(count) if p is None else p
-        rows = env.o.st if from_envs else src.model.rows
         ends, rep, acts, _ = oracle_playout(env.spec, rows, p, steps, seed, first_pair, env.o.autoreset, env.o.horizon)
         if c is not None:
             for k in STATE_KEYS:

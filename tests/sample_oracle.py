@@ -1,14 +1,17 @@
 """Expected weighted choices among valid actions from the unmodified CPU oracle.  The mask words are mask_oracle's (every action stepped on a
 copy), the Philox word is the oracle library's own generator (ngwo_philox4x32_10) under the counter and key of include/ngw.h, and the
 selection is written out here pair by pair in Python scalars: np.float32 adds in action order, one multiply, the first cumulative sum above
-the threshold.  A weighted playout is playout_oracle's loop with this choice in the place of the uniform one.  Nothing here imports
+the threshold.  A weighted playout is playout_oracle's chooser with this choice in the place of the uniform one.  Nothing here imports
 gym_novel_gridworlds_amd.sample or touches the HIP path (tests/test_sample*.py compare both with these)."""
+import functools
+
 import numpy as np
 
 import expand_oracle as XO
 import mask_oracle as M
+import ngw_testlib as T
+import pairs_oracle as PA
 import playout_oracle as PO
-import slot_rollout_oracle as RO
 from oracle.ngw_oracle import lib
 
 STATE_KEYS = PO.STATE_KEYS
@@ -84,36 +87,10 @@ def oracle_sample(spec, rows, idx, weights, seed, first_pair=0, t=0):
 def oracle_weighted_playout(spec, rows, parents, steps, seed, weights, first_pair=0, autoreset=False, horizon=0):
     """playout_oracle.oracle_playout with the weighted choice (weights [A]) on the playout's own mask word and Philox word (PLAYOUT_TAG):
     -> (ends, reports, actions, masks) as there."""
-    cs = spec.compile()
-    A = cs.n_actions
+    A = spec.compile().n_actions
     weights = np.asarray(weights, np.float32)
-    parents = np.asarray(parents, np.int64)
-    count = len(parents)
-    parent = XO.rows_state(spec, rows, parents)
-    live_rows, end_rows = RO._rows_of(parent), RO._rows_of(parent)
-    ret, length = np.zeros(count, np.int32), np.zeros(count, np.int32)
-    ended, info = np.zeros(count, bool), np.zeros(count, np.uint32)
-    actions, masks = np.full((steps, count), -1, np.int32), np.zeros((steps, count), np.uint64)
-    alive = np.ones(count, bool)
-    for t in range(steps):
-        idx = np.nonzero(alive)[0]
-        if not idx.size:
-            break
-        words = M.oracle_mask_words(spec, XO.rows_state(spec, end_rows, idx))
-        acts = np.array([select(w, weights, PO.philox_word(seed, first_pair + int(j), t), A)[0] for w, j in zip(words, idx)], np.int32)
-        masks[t, idx], actions[t, idx] = words, acts
-        length[idx] += 1
-        r = RO._step_rows(spec, cs, live_rows, idx, acts, autoreset, horizon)
-        goal_done = (r.info >> np.uint32(1)) & np.uint32(1)
-        info[idx] = (r.result.astype(np.uint32) | (goal_done << np.uint32(1)) | (r.cost_code.astype(np.uint32) << np.uint32(2)) |
-                     (r.msg_code.astype(np.uint32) << np.uint32(8)) | (r.msg_arg.astype(np.uint32) << np.uint32(16)))
-        ret[idx] += r.reward
-        RO._step_rows(spec, cs, end_rows, idx, acts, False, 0)
-        done = r.done.astype(bool)
-        ended[idx[done]] = True
-        alive[idx[done]] = False
-    ends = {k: end_rows[k].astype(getattr(parent, k).dtype) for k in STATE_KEYS}
-    return ends, dict(ret=ret, length=length, ended=ended, info=info, first_action=actions[0].copy()), actions, masks
+    pick = lambda w, pair, t: select(w, weights, PO.philox_word(seed, pair, t), A)[0]                    # noqa: E731
+    return PO.played(PA.step_pairs(spec, rows, parents, steps, PO.drawn(spec, seed, first_pair, pick), None, autoreset, horizon))
 
 
 def assert_sampled(got, exp, where):
@@ -160,24 +137,24 @@ class OracleVecSample(PO.OracleVecPlayout):
         return Sampled(a, mass, m)
 
     def playouts(self, n_playouts, steps, seed, device=False, weights=None):
+        return self._playouts(n_playouts, steps, seed, weights)
+
+    def _playouts(self, n_playouts, steps, seed, weights, more=None):
+        """The one body of every stand-in's playouts(): the uniform or the weighted playout of P pairs per env; more(parents, actions) -> the
+        fields a richer result holds after Playout's six, and its class."""
         from gym_novel_gridworlds_amd.playout import Playout
         P, N = int(n_playouts), self.num_envs
         parents = np.repeat(np.arange(N), P)
+        tail = (self.env_index_base * P, self.o.autoreset, self.o.horizon)
         if weights is None:
-            _, rep, _, _ = PO.oracle_playout(self.spec, self.o.st, parents, steps, seed, self.env_index_base * P, self.o.autoreset, self.o.horizon)
+            _, rep, acts, _ = PO.oracle_playout(self.spec, self.o.st, parents, steps, seed, *tail)
         else:
-            _, rep, _, _ = oracle_weighted_playout(self.spec, self.o.st, parents, steps, seed, weights, self.env_index_base * P, self.o.autoreset,
-                                                   self.o.horizon)
-        return Playout(rep['ret'], rep['length'], rep['ended'], rep['info'], rep['first_action'], None).shaped(N, P)
+            _, rep, acts, _ = oracle_weighted_playout(self.spec, self.o.st, parents, steps, seed, weights, *tail)
+        play = Playout(rep['ret'], rep['length'], rep['ended'], rep['info'], rep['first_action'], None)
+        if more is not None:
+            cls, fields = more(parents, acts)
+            play = cls(*play, *fields)
+        return play.shaped(N, P)
 
 
-def sharded_on_oracle(**kw):
-    """The product's ShardedVecNovelGridworld with its local env replaced by OracleVecSample (no GPU)."""
-    from gym_novel_gridworlds_amd.dist import ShardedVecNovelGridworld
-
-    class OracleSharded(ShardedVecNovelGridworld):
-        def _make_local(self, device=None, spec=None, **k):
-            k = {a: b for a, b in k.items() if a in ('num_envs', 'seed', 'autoreset', 'horizon', 'env_index_base')}
-            return OracleVecSample(spec, **k)
-
-    return OracleSharded(**kw)
+sharded_on_oracle = functools.partial(T.sharded_on_oracle, OracleVecSample)

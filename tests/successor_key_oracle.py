@@ -4,6 +4,8 @@ a of oracle_expand(..., actions = full(count, a)); nothing here comes from the H
 
 keys_of hashes one cell at a time, so a field's key is computed once per DISTINCT value of that field among the children (most actions leave the
 map as it is) and handed to every child that holds it: the same function on the same bytes, fewer times."""
+import functools
+
 import numpy as np
 
 import expand_oracle as XO
@@ -142,16 +144,7 @@ class OracleVecSuccessors(XO.OracleVecExpand):
         return SuccessorKeys(ex.keys(f), *([ex.rep[k] for k in REPORTS] if reports else [None] * 4))
 
 
-def sharded_on_oracle(**kw):
-    """The product's ShardedVecNovelGridworld with its local env replaced by OracleVecSuccessors (no GPU)."""
-    from gym_novel_gridworlds_amd.dist import ShardedVecNovelGridworld
-
-    class OracleSharded(ShardedVecNovelGridworld):
-        def _make_local(self, device=None, spec=None, **k):
-            k = {a: b for a, b in k.items() if a in ('num_envs', 'seed', 'autoreset', 'horizon', 'env_index_base')}
-            return OracleVecSuccessors(spec, **k)
-
-    return OracleSharded(**kw)
+sharded_on_oracle = functools.partial(SO.T.sharded_on_oracle, OracleVecSuccessors)
 
 
 __all__ = ['SO', 'Successors', 'assert_successors', 'single_field_keys', 'OracleVecSuccessors', 'ModelKeyTable', 'sharded_on_oracle']

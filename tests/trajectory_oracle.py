@@ -1,17 +1,18 @@
-"""Expected trajectories from the unmodified CPU oracle.  The recorded (or given) actions of every pair are replayed by
-path_key_oracle.oracle_path (slot_rollout_oracle's steps on a host copy of the parents' rows), which hands back the row after every executed step;
+"""Expected trajectories from the unmodified CPU oracle.  The recorded (or given) actions of every pair are replayed once by
+pairs_oracle.step_pairs (the oracle's steps on a host copy of the parents' rows), which hands back the row after every executed step;
 the per-step rewards come from the same replay, the mask words from slot_observe_oracle.expect_masks on the row BEFORE each step (every action
 where none would succeed), the lidar rows from slot_observe_oracle.expect_lidar on the parent and on every visited row.  Nothing here uses the
 device's own step, mask or lidar code (tests/test_trajectories*.py compare the HIP path with these)."""
+import functools
+
 import numpy as np
 
-import expand_oracle as XO
+import pairs_oracle as PA
 import path_key_oracle as KO
 import slot_observe_oracle as OO
-import slot_rollout_oracle as RO
 from gym_novel_gridworlds_amd.state_keys import KEY_STATE
 
-STATE_KEYS = RO.STATE_KEYS
+STATE_KEYS = PA.STATE_KEYS
 
 
 def _stack(rows_list):
@@ -27,46 +28,39 @@ def mask_words(spec, rows):
     return np.where(w == 0, np.uint64((1 << A) - 1), w)
 
 
+def observed(spec, e, lc=None, masks=True):
+    """step_pairs' record (with states) as a trajectory: the record plus masks uint64 [T, count] - the word of the row BEFORE each executed step,
+    unless a chooser kept its own - and obs int32 [T + 1, count, L] - the lidar rows of the parents and of every visited row - or None without a
+    LidarConfig `lc`; zeros for every step a pair did not execute."""
+    steps, count = e['ran'].shape
+    parent_rows, states = e['parent_rows'], e['states']
+    e['obs'] = None
+    if masks:
+        e['masks'] = np.zeros((steps, count), np.uint64)
+    if lc is not None:
+        first = OO.expect_lidar(spec, lc, parent_rows, np.arange(count))
+        e['obs'] = np.zeros((steps + 1, count, first.shape[1]), np.int32)
+        e['obs'][0] = first
+    for t in range(steps):
+        ran = np.nonzero(e['ran'][t])[0]
+        if not ran.size:
+            break
+        if masks:
+            before = _stack([{k: parent_rows[k][j] for k in STATE_KEYS} if t == 0 else states[(t - 1, int(j))] for j in ran])
+            e['masks'][t, ran] = mask_words(spec, before)
+        if lc is not None:
+            after = _stack([states[(t, int(j))] for j in ran])
+            e['obs'][t + 1, ran] = OO.expect_lidar(spec, lc, after, np.arange(len(ran)))
+    return e
+
+
 def oracle_traj(spec, rows, parents, actions, limits=None, autoreset=False, horizon=0, fields=KEY_STATE, lc=None):
     """actions int [T, count] (-1 / an id outside the list: a no-op step that counts, as in oracle_path), limits None or [count].
     -> dict(keys, reports, ends, states, events: oracle_path's five; rewards int32 [T, count]; masks uint64 [T, count]; obs int32 [T + 1, count, L]
     or None without a LidarConfig `lc`), zeros for every step a pair did not execute."""
-    cs = spec.compile()
-    parents, actions = np.asarray(parents, np.int64), np.asarray(actions, np.int64)
-    steps, count = actions.shape
-    keys, rep, ends, states, ev = KO.oracle_path(spec, rows, parents, actions, limits, autoreset, horizon, fields)
-    length = rep['length']
-    # the rewards: the same replay under the handle's autoreset setting and horizon (a pair stops at its first done, so no reset is ever used)
-    lim = np.full(count, steps, np.int64) if limits is None else np.clip(np.asarray(limits, np.int64), 0, steps)
-    valid = (actions >= 0) & (actions < cs.n_actions)
-    parent_rows = RO._rows_of(XO.rows_state(spec, rows, parents))
-    live = {k: v.copy() for k, v in parent_rows.items()}
-    rewards = np.zeros((steps, count), np.int32)
-    alive = np.ones(count, bool)
-    for t in range(steps):
-        alive &= lim > t
-        idx = np.nonzero(alive & valid[t])[0]
-        if idx.size:
-            r = RO._step_rows(spec, cs, live, idx, actions[t, idx], autoreset, horizon)
-            rewards[t, idx] = r.reward
-            alive[idx[r.done.astype(bool)]] = False
-    assert (rewards.sum(0) == rep['ret']).all() and ((np.arange(steps)[:, None] < length[None, :]) | (rewards == 0)).all()
-    masks = np.zeros((steps, count), np.uint64)
-    obs = None
-    if lc is not None:
-        first = OO.expect_lidar(spec, lc, parent_rows, np.arange(count))
-        obs = np.zeros((steps + 1, count, first.shape[1]), np.int32)
-        obs[0] = first
-    for t in range(steps):
-        ran = np.nonzero(length > t)[0]
-        if not ran.size:
-            break
-        before = _stack([{k: parent_rows[k][j] for k in STATE_KEYS} if t == 0 else states[(t - 1, int(j))] for j in ran])
-        masks[t, ran] = mask_words(spec, before)
-        if obs is not None:
-            after = _stack([states[(t, int(j))] for j in ran])
-            obs[t + 1, ran] = OO.expect_lidar(spec, lc, after, np.arange(len(ran)))
-    return dict(keys=keys, reports=rep, ends=ends, states=states, events=ev, rewards=rewards, masks=masks, obs=obs)
+    actions = np.asarray(actions, np.int64)
+    e = observed(spec, PA.step_pairs(spec, rows, parents, actions.shape[0], actions, limits, autoreset, horizon, fields, record=True), lc)
+    return {k: e[k] for k in ('keys', 'reports', 'ends', 'states', 'events', 'rewards', 'masks', 'obs')}
 
 
 def widen(obs):
@@ -106,30 +100,20 @@ class OracleVecTraj(KO.OracleVecPath):
         self.configured += 1
 
     def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None):
-        from gym_novel_gridworlds_amd.playout import PlayoutTraj
         from gym_novel_gridworlds_amd.snapshot import check_observe
         if not (check_observe(self, observe) or rewards or masks):
             return super().playouts(n_playouts, steps, seed, device=device, weights=weights, path_keys=path_keys, fields=fields)
-        P, N = int(n_playouts), self.num_envs
-        parents = np.repeat(np.arange(N), P)
-        if weights is None:
-            _, rep, acts, _ = KO.SO.PO.oracle_playout(self.spec, self.o.st, parents, steps, seed, self.env_index_base * P, self.o.autoreset, self.o.horizon)
-        else:
-            _, rep, acts, _ = KO.SO.oracle_weighted_playout(self.spec, self.o.st, parents, steps, seed, weights, self.env_index_base * P, self.o.autoreset,
-                                                            self.o.horizon)
-        e = oracle_traj(self.spec, self.o.st, parents, acts, None, self.o.autoreset, self.o.horizon, KEY_STATE if fields is None else fields,
-                        self.lidar if observe is not None else None)
-        return PlayoutTraj(rep['ret'], rep['length'], rep['ended'], rep['info'], rep['first_action'], None, e['keys'] if path_keys else None,
-                           e['rewards'] if rewards else None, e['masks'] if masks else None, e['obs']).shaped(N, P)
+        return self._playouts(n_playouts, steps, seed, weights, self._traj(path_keys, fields, rewards, masks, self.lidar if observe is not None else None))
+
+    def _traj(self, path_keys, fields, rewards, masks, lc=None, obs_of=None):
+        """The `more` of sample_oracle's _playouts for a PlayoutTraj: the fields switched on, obs_of(parents, e) in the place of the lidar rows."""
+        from gym_novel_gridworlds_amd.playout import PlayoutTraj
+
+        def more(parents, acts):
+            e = oracle_traj(self.spec, self.o.st, parents, acts, None, self.o.autoreset, self.o.horizon, KEY_STATE if fields is None else fields, lc)
+            return PlayoutTraj, (e['keys'] if path_keys else None, e['rewards'] if rewards else None, e['masks'] if masks else None,
+                                 e['obs'] if obs_of is None else obs_of(parents, e))
+        return more
 
 
-def sharded_on_oracle(**kw):
-    """The product's ShardedVecNovelGridworld with its local env replaced by OracleVecTraj (no GPU)."""
-    from gym_novel_gridworlds_amd.dist import ShardedVecNovelGridworld
-
-    class OracleSharded(ShardedVecNovelGridworld):
-        def _make_local(self, device=None, spec=None, **k):
-            k = {a: b for a, b in k.items() if a in ('num_envs', 'seed', 'autoreset', 'horizon', 'env_index_base')}
-            return OracleVecTraj(spec, **k)
-
-    return OracleSharded(**kw)
+sharded_on_oracle = functools.partial(KO.SO.T.sharded_on_oracle, OracleVecTraj)

@@ -2,6 +2,8 @@
 hands back the row after every executed step, and slot_observe_oracle.expect_view - the oracle's agent_view on a host copy of rows - gives the
 window, the facing id and the inventory of the parents (block 0) and of every visited row (block t + 1); zeros for every step a pair did not
 execute.  Nothing here uses the device's own step or view code (tests/test_trajectory_views*.py compare the HIP path with these)."""
+import functools
+
 import numpy as np
 
 import expand_oracle as XO
@@ -9,7 +11,6 @@ import path_key_oracle as KO
 import slot_observe_oracle as OO
 import slot_rollout_oracle as RO
 import trajectory_oracle as TO
-from gym_novel_gridworlds_amd.state_keys import KEY_STATE
 
 FIELDS = ('agent_map', 'agent_facing_id', 'inventory_items_quantity')
 
@@ -71,31 +72,12 @@ class OracleVecViews(TO.OracleVecTraj):
         return len(self.spec.items_id)
 
     def playouts(self, n_playouts, steps, seed, device=False, weights=None, path_keys=False, fields=None, rewards=False, masks=False, observe=None, view_size=5):
-        from gym_novel_gridworlds_amd.playout import PlayoutTraj
         from gym_novel_gridworlds_amd.snapshot import check_observe
         if check_observe(self, observe, view_size) != 'agent_view':
             return super().playouts(n_playouts, steps, seed, device=device, weights=weights, path_keys=path_keys, fields=fields, rewards=rewards, masks=masks,
                                     observe=observe)
-        P, N = int(n_playouts), self.num_envs
-        parents = np.repeat(np.arange(N), P)
-        if weights is None:
-            _, rep, acts, _ = KO.SO.PO.oracle_playout(self.spec, self.o.st, parents, steps, seed, self.env_index_base * P, self.o.autoreset, self.o.horizon)
-        else:
-            _, rep, acts, _ = KO.SO.oracle_weighted_playout(self.spec, self.o.st, parents, steps, seed, weights, self.env_index_base * P, self.o.autoreset,
-                                                            self.o.horizon)
-        e = TO.oracle_traj(self.spec, self.o.st, parents, acts, None, self.o.autoreset, self.o.horizon, KEY_STATE if fields is None else fields)
-        obs = expect_views(self.spec, self.o.st, parents, e, view_size)
-        return PlayoutTraj(rep['ret'], rep['length'], rep['ended'], rep['info'], rep['first_action'], None, e['keys'] if path_keys else None,
-                           e['rewards'] if rewards else None, e['masks'] if masks else None, obs).shaped(N, P)
+        return self._playouts(n_playouts, steps, seed, weights, self._traj(path_keys, fields, rewards, masks, None,
+                                                                          lambda parents, e: expect_views(self.spec, self.o.st, parents, e, view_size)))
 
 
-def sharded_on_oracle(**kw):
-    """The product's ShardedVecNovelGridworld with its local env replaced by OracleVecViews (no GPU)."""
-    from gym_novel_gridworlds_amd.dist import ShardedVecNovelGridworld
-
-    class OracleSharded(ShardedVecNovelGridworld):
-        def _make_local(self, device=None, spec=None, **k):
-            k = {a: b for a, b in k.items() if a in ('num_envs', 'seed', 'autoreset', 'horizon', 'env_index_base')}
-            return OracleVecViews(spec, **k)
-
-    return OracleSharded(**kw)
+sharded_on_oracle = functools.partial(KO.SO.T.sharded_on_oracle, OracleVecViews)
