@@ -8,7 +8,7 @@ reference's gym.Env surface.  Everything computes in hand-written HIP kernels re
     venv = gym_novel_gridworlds_amd.VecNovelGridworld('NovelGridworld-Pogostick-v1', num_envs=65536)
 """
 from .envs import ENTRY_POINTS, BowV0Env, BowV1Env, PogostickV0Env, PogostickV1Env, make   # noqa: F401
-from .frontier import Frontier, alloc_reference, compact_reference   # noqa: F401
+from .frontier import Frontier, Selected, alloc_reference, compact_reference, select_reference   # noqa: F401
 from .key_table import KeyBest, KeyInsert, KeyTable, Trace                           # noqa: F401
 from .novelty import NOVELTY_NAMES, apply_novelty                    # noqa: F401
 from .novelty_wrappers import inject_novelty                         # noqa: F401

@@ -33,7 +33,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_snapshot_rollout_traj', 'ngw_snapshot_playout_traj', 'ngw_snapshot_rollout_traj_views', 'ngw_snapshot_playout_traj_views', 'ngw_snapshot_playout_guided',
            'ngw_key_table_create', 'ngw_key_table_destroy', 'ngw_key_table_clear', 'ngw_key_table_insert', 'ngw_key_table_lookup', 'ngw_key_table_count',
            'ngw_key_table_create_valued', 'ngw_key_table_insert_min', 'ngw_key_table_read', 'ngw_key_table_trace',
-           'ngw_snapshot_walk', 'ngw_frontier_compact', 'ngw_frontier_alloc', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
+           'ngw_snapshot_walk', 'ngw_frontier_compact', 'ngw_frontier_alloc', 'ngw_frontier_select', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
 _lib = None
@@ -210,6 +210,8 @@ def lib():
     if hasattr(L, 'ngw_frontier_compact'):
         L.ngw_frontier_compact.argtypes = [vp, vp, i64, i32, vp, i64, vp, vp, vp]
         L.ngw_frontier_alloc.argtypes = [vp, vp, vp, i32, i64, vp]
+    if hasattr(L, 'ngw_frontier_select'):
+        L.ngw_frontier_select.argtypes = [vp, vp, vp, i64, i32, i32, vp, i32, i32, i64, vp, vp, vp, vp, vp]
     if hasattr(L, 'ngw_snapshot_copy'):
         L.ngw_snapshot_copy.argtypes = [vp, vp, vp, vp, vp, i64]
     if hasattr(L, 'ngw_key_table_create'):

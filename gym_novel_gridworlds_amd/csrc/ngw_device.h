@@ -890,4 +890,39 @@ extern "C"
 #endif
 hipError_t ngw_frontier_alloc_launch(const struct NgwFrontierAlloc* x, hipStream_t stream);
 
+/* Priority frontiers (ngw_select.inc, ngw_abi_frontier.cpp): the `keep` best candidates of each of `groups` groups of m int32 values, in the list
+ * form of the compaction.  The contract is include/ngw.h's (ngw_frontier_select); frontier.select_reference states it in numpy.  A candidate is a
+ * position p with values[p] != NGW_VALUE_NONE and (bytes == nullptr or bytes[p] != 0); the selection runs on the key uint32(value) ^ 0x80000000,
+ * complemented when `largest` is set, smallest key first and the smaller position first among equal keys.  Two forms, picked by
+ * ngw_frontier_select_launch alone: m <= NGW_SELECT_WAVE_MAX one wavefront per group and ONE launch; above it the grid form of SIX launches over
+ * tiles of NGW_FRONTIER_TILE positions (four digit histograms, the tiles' counts, the scatter), behind one hipMemsetAsync of the scratch.
+ * scratch (uint32 words, NGW_SELECT_SCRATCH_WORDS(groups, tiles_per_group) of them for the grid form, 2 for the wave form; 8-byte aligned):
+ *   [0 .. 2)  the wave form's ticket word (64 bits: waves arrived << 32 | candidates so far), 0 between the calls - the last wave puts it back
+ *   [2]       the grid form's candidates over all groups             [3] unused
+ *   [4 + 8 g .. )                       group g: (key prefix, rank still looked for under it) after the first, second and third digit, then (T, r):
+ *                                       the threshold key and how many of the keys equal to it are chosen; r == 0: nothing is chosen in the group
+ *   [4 + 8 groups + 1024 g + 256 d ..)  group g, digit d (0 = the top byte): 256 counters
+ *   [4 + 1032 groups + 2 (g tpg + t) ..)  tile t of group g: the keys below the threshold, the keys equal to it */
+struct NgwSelect {
+    const int32_t* values;  /* [groups * m] */
+    const uint8_t* bytes;   /* [groups * m], or nullptr: every position */
+    const int32_t* map;     /* [ceil(groups * m / div)], or nullptr: the identity */
+    int32_t* first;         /* [capacity] */
+    int32_t* second;        /* [capacity], or nullptr */
+    int32_t* taken;         /* [groups] */
+    int32_t* bound;         /* [groups] */
+    int32_t* count;         /* [2] */
+    uint32_t* scratch;      /* the handle's */
+    int64_t capacity;       /* >= groups * keep */
+    int32_t groups, m, div, keep, largest;
+    int32_t tiles_per_group;    /* ceil(m / NGW_FRONTIER_TILE) */
+};
+#define NGW_SELECT_WAVE_MAX 1024                       /* the largest group one wavefront selects from: 16 values per lane */
+#define NGW_SELECT_MAX_VALUES (1ll << 24)              /* the most values (and the most groups) of one call */
+#define NGW_SELECT_SCRATCH_WORDS(groups, tpg) (4ll + 1032ll * (groups) + 2ll * (groups) * (tpg))
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_frontier_select_launch(const struct NgwSelect* x, hipStream_t stream);
+
 #endif

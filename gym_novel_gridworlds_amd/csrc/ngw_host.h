@@ -11,7 +11,8 @@
 //                        roll action sequences out from saved states (ngw_slot_rollout.inc), observe saved states by slot (ngw_slot_observe.inc),
 //                        64-bit state keys of saved slots and live envs (ngw_keys.inc), walk distances and go-to plans of them (ngw_walk.inc)
 //   ngw_abi_table.cpp    device-side key tables: a hash set of such keys that outlives the call - insert, lookup, count, clear -, and a value and a tag per key: insert_min, read, trace (ngw_table.inc)
-//   ngw_abi_frontier.cpp device-side frontiers: flags compacted into index lists of fixed capacity, slots handed out for them (ngw_frontier.inc)
+//   ngw_abi_frontier.cpp device-side frontiers: flags compacted into index lists of fixed capacity, slots handed out for them (ngw_frontier.inc),
+//                        the k best candidates per group in the same list form (ngw_select.inc)
 //
 // Three rules hold in all of them:
 //   1. Guard first.  An entry point that uses the handle's stream or its device state starts with `if (int rc = enter(h)) return rc;`
@@ -235,6 +236,9 @@ struct ngw_handle {
     // brings more tiles - word 0 the allocation's ticket (0 between the calls), the tile counts behind it
     int32_t* frontier_scratch = nullptr;
     int64_t frontier_tiles = 0;
+    // ... and of ngw_frontier_select (ngw_device.h NgwSelect says what lies where), likewise
+    uint32_t* select_scratch = nullptr;
+    int64_t select_words = 0;
     long long solo_starts = 0;           // launches of the one-env resident loop (ngw_debug_solo_starts)
     hipGraph_t graph = nullptr;
     hipGraphExec_t graph_exec = nullptr;

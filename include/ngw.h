@@ -1044,6 +1044,37 @@ int ngw_frontier_compact(ngw_handle* h, const uint8_t* flags_dev, int64_t n, int
                          int32_t* second_dev, int32_t* count_dev);
 int ngw_frontier_alloc(ngw_handle* h, const int32_t* count_dev, int32_t* cursor_dev, int32_t limit, int64_t capacity, int32_t* slots_dev);
 
+/* Priority frontiers: the step "of these candidates, go on with the best k" - beam search, A*, best-first search over an archive, Go-Explore's
+ * choice of cells - in the list form of ngw_frontier_compact, with no host wait.
+ * ngw_frontier_select: values_dev (int32 [n]) is read as `groups` groups of m = n / groups values, group g the positions [g m, (g + 1) m).  A
+ * CANDIDATE is a position p with values_dev[p] != NGW_VALUE_NONE - in both modes - and (flags_dev == NULL or flags_dev[p] != 0; any non-zero byte
+ * counts, as in ngw_frontier_compact).  The candidates of a group are ordered by (value ascending, position ascending) when largest == 0 and by
+ * (value descending, position ascending) when largest == 1, and the first taken_g = min(candidates_g, keep) of them are CHOSEN: at equal values the
+ * smaller position wins, so the choice is a function of the inputs alone, whatever order the device runs in.  Let p_0 < p_1 < ... be the chosen
+ * positions of group g in ASCENDING POSITION order (the row-major order of the compaction, not the order of the values).  Then
+ *     first_dev[g keep + i]  (int32)          = map_dev ? map_dev[p_i / div] : p_i / div     for i < taken_g
+ *     second_dev[g keep + i] (int32, or NULL) = p_i % div                                    for i < taken_g
+ *     every other entry of [0, capacity) of both lists = NGW_IDX_NONE  (the rest of each group's span of `keep` entries, and [groups keep, capacity))
+ *     taken_dev[g] (int32 [groups]) = taken_g
+ *     bound_dev[g] (int32 [groups]) = the value of the last chosen candidate in selection order - the largest chosen value when largest == 0, the
+ *                                     smallest when largest == 1 -, NGW_VALUE_NONE where taken_g == 0
+ *     count_dev[1] = the candidates of all groups;  count_dev[0] = taken_0 when groups == 1 - the live entries are then a prefix and
+ *                    ngw_frontier_alloc serves exactly them -, groups * keep when groups > 1: the live entries are no prefix there, the allocation hands
+ *                    a slot to every entry of the spans and the call that takes the lists skips the padded pairs
+ * No flag is raised: dropping what lies beyond `keep` is what the call is for.  values_dev, flags_dev (uint8 [n]) and map_dev (int32, at least
+ * ceil(n / div) entries, NULL: the identity) are DEVICE memory and are only read; exactly [0, capacity) of the lists, the `groups` entries of
+ * taken_dev and bound_dev and the two counts are written.  n in [0, 2^24], groups in [1, 2^24] with n a multiple of it, div >= 1, keep in
+ * [0, 2^31 - 1] with groups * keep <= capacity, capacity in [0, 2^31 - 1], largest 0 or 1.  n == 0 (so m == 0) fills the lists with NGW_IDX_NONE,
+ * taken with 0 and bound with NGW_VALUE_NONE; keep == 0 does the same, and count_dev[1] is still the number of candidates.
+ * m <= 1024: one kernel launch, a wavefront per group; above: six launches behind a memset of the handle's scratch (ngw_select.inc).  Integer
+ * arithmetic only; the entry of a chosen position comes from counts, no atomic orders the output.  Enqueued on the handle's stream, no wait, no
+ * env state written.
+ * NGW_E_INVALID_ARG: a NULL handle, taken, bound or count, NULL values with n > 0, a NULL first with capacity > 0; n outside [0, 2^24]; groups outside
+ * [1, 2^24] or no divisor of n; div < 1; keep negative; groups * keep > capacity; capacity outside [0, 2^31 - 1]; largest neither 0 nor 1. */
+int ngw_frontier_select(ngw_handle* h, const int32_t* values_dev, const uint8_t* flags_dev /* NULL: every position */, int64_t n, int32_t groups, int32_t div,
+                        const int32_t* map_dev /* NULL: the identity */, int32_t keep, int32_t largest, int64_t capacity, int32_t* first_dev,
+                        int32_t* second_dev /* NULL: not wanted */, int32_t* taken_dev, int32_t* bound_dev, int32_t* count_dev);
+
 /* Guided playouts: ngw_snapshot_playout_traj_views whose weights depend on the STATE - at every step the pair's current state is looked up in a key
  * table, and where the table holds it the choice is made under that bucket's row of the caller's weights.  The selection phase of MCTS (descend by
  * the tree's statistics while the node is in the tree), tabular Q / softmax policies, Go-Explore's "return, then explore" and playouts whose bias is
