@@ -13,6 +13,7 @@ from .key_table import KeyBest, KeyInsert, KeyTable, Trace                      
 from .novelty import NOVELTY_NAMES, apply_novelty                    # noqa: F401
 from .novelty_wrappers import inject_novelty                         # noqa: F401
 from .observation_wrappers import AgentMap, LidarInFront                    # noqa: F401
+from .search import Search, SearchGoal, SearchStats, relax_reference  # noqa: F401
 from .spec import ENV_IDS, IDX_NONE, STEP_COSTS, EnvSpec, make_spec  # noqa: F401
 from .state_keys import (KEY_ALL, KEY_EPISODE, KEY_INV, KEY_MAP, KEY_POSE, KEY_SELECTED, KEY_STATE, KEY_STEP_COUNT,   # noqa: F401
                          keys_of_rows)

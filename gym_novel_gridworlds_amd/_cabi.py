@@ -33,6 +33,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_snapshot_rollout_traj', 'ngw_snapshot_playout_traj', 'ngw_snapshot_rollout_traj_views', 'ngw_snapshot_playout_traj_views', 'ngw_snapshot_playout_guided',
            'ngw_key_table_create', 'ngw_key_table_destroy', 'ngw_key_table_clear', 'ngw_key_table_insert', 'ngw_key_table_lookup', 'ngw_key_table_count',
            'ngw_key_table_create_valued', 'ngw_key_table_insert_min', 'ngw_key_table_read', 'ngw_key_table_trace',
+           'ngw_search_create', 'ngw_search_destroy', 'ngw_search_start', 'ngw_search_run', 'ngw_search_read',
            'ngw_snapshot_walk', 'ngw_frontier_compact', 'ngw_frontier_alloc', 'ngw_frontier_select', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
@@ -43,6 +44,20 @@ class TrajViews(C.Structure):
     """include/ngw.h ngw_traj_views: the AgentMap outputs of a trajectory call - device pointers (any may be NULL, not all), the stride of a row
     block in rows."""
     _fields_ = [('view_size', C.c_int32), ('view_dev', C.c_void_p), ('facing_dev', C.c_void_p), ('inv_dev', C.c_void_p), ('stride', C.c_int64)]
+
+
+class SearchArrays(C.Structure):
+    """include/ngw.h ngw_search_arrays: the device arrays of a search run that its caller reads and writes."""
+    _fields_ = [('parents', C.c_void_p * 2), ('g', C.c_void_p), ('bucket', C.c_void_p), ('cursor', C.c_void_p)]
+
+
+SEARCH_ROWS = 64      # include/ngw.h NGW_SEARCH_ROWS
+
+
+class SearchReport(C.Structure):
+    """include/ngw.h ngw_search_report."""
+    _fields_ = [('iterations', C.c_int64), ('overflowed', C.c_uint64), ('goal_value', C.c_int32), ('goal_bucket', C.c_int32), ('cursor', C.c_int32),
+                ('flags', C.c_uint32), ('rows', C.c_int32), ('current', C.c_int32), ('stats', (C.c_uint32 * 4) * SEARCH_ROWS)]
 
 
 class NgwError(RuntimeError):
@@ -212,6 +227,12 @@ def lib():
         L.ngw_frontier_alloc.argtypes = [vp, vp, vp, i32, i64, vp]
     if hasattr(L, 'ngw_frontier_select'):
         L.ngw_frontier_select.argtypes = [vp, vp, vp, i64, i32, i32, vp, i32, i32, i64, vp, vp, vp, vp, vp]
+    if hasattr(L, 'ngw_search_create'):
+        L.ngw_search_create.argtypes = [vp, vp, vp, i64, vp, i32, i32, i32, C.POINTER(SearchArrays), C.POINTER(vp)]
+        L.ngw_search_destroy.argtypes = [vp, vp]
+        L.ngw_search_start.argtypes = [vp, vp, vp, i64, C.POINTER(i32)]
+        L.ngw_search_run.argtypes = [vp, vp, i32, C.POINTER(i32)]
+        L.ngw_search_read.argtypes = [vp, vp, C.POINTER(SearchReport)]
     if hasattr(L, 'ngw_snapshot_copy'):
         L.ngw_snapshot_copy.argtypes = [vp, vp, vp, vp, vp, i64]
     if hasattr(L, 'ngw_key_table_create'):

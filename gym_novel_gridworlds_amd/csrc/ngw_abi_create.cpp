@@ -601,6 +601,7 @@ int ngw_destroy(ngw_handle* h) {
     for (void* p : h->allocs) (void)hipFree(p);
     for (ngw_snapshot* s : h->snaps) delete s;                       // (their slabs were in `allocs`)
     for (ngw_key_table* t : h->tables) delete t;                     // (likewise)
+    for (ngw_search* s : h->searches) delete s;                      // (likewise)
     for (void* p : h->host_allocs) (void)hipHostFree(p);
     drop_graph(h);
     if (h->info_host) (void)hipHostFree(h->info_host);

@@ -1,0 +1,203 @@
+// ngw_abi_search.cpp - search runs (see ngw_host.h): whole best-first iterations over one snapshot pool and one valued key table, enqueued from one
+// call.  The driver owns no stage of its own: successor keys, insert_min, compaction / selection, slot allocation and expand run through their own
+// entry points (ngw_abi_snapshot.cpp, ngw_abi_table.cpp, ngw_abi_frontier.cpp), called as any caller calls them, with the three kernels of
+// ngw_search.inc between them.  The calls write no env state: they neither call state_written() nor touch anything the handle derives from its
+// state.  All run on the handle's stream, behind enter(); only ngw_search_read waits.
+#include "ngw_host.h"
+
+using namespace ngwh;
+
+namespace {
+
+// The stats ring holds one row more than ngw_search_read reports: the settle kernel of iteration i zero-fills the row of iteration i + 1, which in a
+// ring of NGW_SEARCH_ROWS rows would be the row of iteration i + 1 - NGW_SEARCH_ROWS - the oldest of the rows still to be reported.
+constexpr int64_t SEARCH_RING = NGW_SEARCH_ROWS + 1;
+
+bool owns_search(const ngw_handle* h, const ngw_search* s) {
+    for (const ngw_search* q : h->searches)
+        if (q == s) return true;
+    return false;
+}
+
+// the pool and the table of `s` are still open on `h` (by address: a closed one is simply not found)
+bool parts_open(const ngw_handle* h, const ngw_search* s) {
+    bool pool = false, table = false;
+    for (const ngw_snapshot* q : h->snaps) pool = pool || q == s->pool;
+    for (const ngw_key_table* q : h->tables) table = table || q == s->table;
+    return pool && table;
+}
+
+int search_call_args(const ngw_handle* h, const ngw_search* s) {
+    if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns_search(h, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
+    if (!parts_open(h, s)) return fail(NGW_E_INVALID_ARG, "the search's snapshot or key table is closed");
+    return NGW_OK;
+}
+
+// the arguments the three kernels share, for iteration s->iterations
+NgwSearch search_args(const ngw_search* s) {
+    NgwSearch x{};
+    x.parents = s->parents[s->cur]; x.next = s->parents[s->cur ^ 1]; x.g = s->g; x.bucket = s->bucket;
+    x.info = reinterpret_cast<const uint32_t*>(s->info); x.lut = s->lut; x.values = s->values; x.tags = s->tags; x.where = s->where; x.best = s->best;
+    x.first = s->first; x.second = s->second; x.slots = s->slots; x.plist = s->plist;
+    x.goal = s->goal; x.overflowed = s->goal + 1;
+    x.row = s->stats + 4 * (s->iterations % SEARCH_RING); x.next_row = s->stats + 4 * ((s->iterations + 1) % SEARCH_RING);
+    x.capacity = s->cap; x.pool = s->pool_cap; x.A = s->A; x.by_action = s->by_action; x.stop = s->stop;
+    return x;
+}
+
+// one iteration: ngw.h's seven steps in their order
+int iterate(ngw_handle* h, ngw_search* s) {
+    const NgwSearch x = search_args(s);
+    if (int rc = ngw_successor_keys(h, s->pool, x.parents, s->cap, NGW_KEY_STATE, s->keys, nullptr, nullptr, reinterpret_cast<uint32_t*>(s->info))) return rc;
+    HIP_TRY(ngw_search_offer_launch(&x, h->stream));
+    if (int rc = ngw_key_table_insert_min(h, s->table, s->keys, s->values, s->tags, s->n, s->where, s->fresh, s->best)) return rc;
+    HIP_TRY(ngw_search_judge_launch(&x, h->stream));
+    if (s->keep < 0) {
+        if (int rc = ngw_frontier_compact(h, s->best, s->n, s->A, nullptr, s->cap, s->first, s->second, s->count)) return rc;
+    } else {
+        if (int rc = ngw_frontier_select(h, s->values, s->best, s->n, 1, s->A, nullptr, s->keep, 0, s->cap, s->first, s->second, s->taken, s->bound, s->count))
+            return rc;
+    }
+    if (int rc = ngw_frontier_alloc(h, s->count, s->cursor, (int32_t)s->pool_cap, s->cap, s->slots)) return rc;
+    HIP_TRY(ngw_search_settle_launch(&x, h->stream));
+    if (int rc = ngw_snapshot_expand(h, s->pool, s->plist, s->second, s->pool, s->slots, s->cap, nullptr, nullptr, nullptr)) return rc;
+    s->cur ^= 1;
+    s->iterations++;
+    return NGW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ngw_search_create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, int64_t capacity, const int32_t* costs_host, int32_t by_action, int32_t keep,
+                      int32_t stop_at_goals, ngw_search_arrays* arrays, ngw_search** out) {
+    if (!h || !pool || !table || !costs_host || !arrays || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    *out = nullptr;
+    ngw_search probe;
+    probe.pool = pool; probe.table = table;
+    if (!parts_open(h, &probe)) return fail(NGW_E_INVALID_ARG, "not an open snapshot and an open key table of this handle");
+    if (!table->valued) return fail(NGW_E_INVALID_ARG, "a key table without values (ngw_key_table_create_valued makes one with)");
+    const int64_t A = h->spec.n_actions;
+    if (capacity < 1 || capacity > pool->cap) return fail(NGW_E_INVALID_ARG, "search capacity %lld outside [1, the pool's %lld]", (long long)capacity, (long long)pool->cap);
+    if (capacity * A > NGW_FRONTIER_MAX_FLAGS)
+        return fail(NGW_E_INVALID_ARG, "search capacity %lld: %lld positions in one iteration (at most 2^24)", (long long)capacity, (long long)(capacity * A));
+    if (pool->cap > 0x7FFFFFFFll) return fail(NGW_E_INVALID_ARG, "a pool of %lld slots", (long long)pool->cap);
+    if ((int64_t)keep > capacity) return fail(NGW_E_INVALID_ARG, "keep: %d entries do not fit the capacity %lld", (int)keep, (long long)capacity);
+    if (table->buckets * (uint64_t)A > 0x7FFFFFFFull)
+        return fail(NGW_E_INVALID_ARG, "search: buckets * n_actions = %llu does not fit a tag (at most 2^31 - 1)", (unsigned long long)(table->buckets * (uint64_t)A));
+    const size_t lds = NGW_SUCC_LDS_BYTES(h->proto.MS, h->proto.KP);
+    if (lds > NGW_SUCC_LDS_MAX)
+        return fail(NGW_E_INVALID_ARG, "map_size %d: a search keeps two sets of a wavefront's 64 maps in LDS (ngw_successor_keys) and they need %zu B, more "
+                                       "than 160 KiB", h->proto.S, lds);
+    if (int rc = enter(h)) return rc;
+    const size_t cap = (size_t)capacity, n = cap * (size_t)A, pc = (size_t)pool->cap;
+    // 64-bit words: goal, overflowed | keys [n] | the int32 arrays, an even number of them | fresh [n], best [n]
+    const size_t head = 4 * SEARCH_RING + 64 + 8;                              // stats, cost table, cursor + count[2] + taken + bound + 3 spare
+    size_t words32 = head + 6 * cap + 2 * pc + 4 * n;
+    words32 += words32 & 1;
+    const size_t words64 = 2 + n + words32 / 2 + (2 * n + 7) / 8;
+    uint64_t* slab = nullptr;
+    if (int rc = dev_alloc(h, &slab, words64)) return rc;                          // (zero-filled on the handle's stream)
+    ngw_search* s = new ngw_search;
+    s->pool = pool; s->table = table; s->cap = capacity; s->pool_cap = pool->cap; s->n = (int64_t)n;
+    s->A = (int32_t)A; s->by_action = by_action != 0; s->keep = keep < 0 ? -1 : keep; s->stop = stop_at_goals != 0;
+    s->slab = slab; s->goal = reinterpret_cast<unsigned long long*>(slab); s->keys = slab + 2;
+    int32_t* w = reinterpret_cast<int32_t*>(slab + 2 + n);
+    s->stats = reinterpret_cast<uint32_t*>(w); w += 4 * SEARCH_RING;
+    s->lut = w; w += 64;
+    s->cursor = w; s->count = w + 1; s->taken = w + 3; s->bound = w + 4; w += 8;
+    s->parents[0] = w; s->parents[1] = w + cap; s->first = w + 2 * cap; s->second = w + 3 * cap; s->slots = w + 4 * cap; s->plist = w + 5 * cap; w += 6 * cap;
+    s->g = w; s->bucket = w + pc; w += 2 * pc;
+    s->info = w; s->values = w + n; s->tags = w + 2 * n; s->where = w + 3 * n;
+    s->fresh = reinterpret_cast<uint8_t*>(slab + 2 + n + words32 / 2); s->best = s->fresh + n;
+    hipError_t e = hipMemsetAsync(s->goal, 0xFF, 8, h->stream);                                                   // no goal yet
+    if (e == hipSuccess) e = hipMemcpyAsync(s->lut, costs_host, 64 * sizeof(int32_t), hipMemcpyDefault, h->stream);
+    if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->parents[0]), (int)NGW_IDX_NONE, 2 * cap, h->stream);
+    if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->g), NGW_VALUE_NONE, pc, h->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(s->bucket, 0xFF, pc * sizeof(int32_t), h->stream);                    // -1: no bucket
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);                                                     // (costs_host is the caller's: read by now)
+    if (e != hipSuccess) {
+        dev_free(h, slab);
+        delete s;
+        return fail(NGW_E_HIP, "search setup failed: %s", hipGetErrorString(e));
+    }
+    h->searches.push_back(s);
+    arrays->parents[0] = s->parents[0]; arrays->parents[1] = s->parents[1]; arrays->g = s->g; arrays->bucket = s->bucket; arrays->cursor = s->cursor;
+    *out = s;
+    return NGW_OK;
+}
+
+int ngw_search_destroy(ngw_handle* h, ngw_search* s) {
+    if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns_search(h, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
+    if (int rc = enter(h)) return rc;
+    HIP_TRY(hipStreamSynchronize(h->stream));                         // (queued iterations may still use the arrays)
+    for (size_t i = 0; i < h->searches.size(); i++)
+        if (h->searches[i] == s) { h->searches.erase(h->searches.begin() + (long)i); break; }
+    dev_free(h, s->slab);
+    delete s;
+    return NGW_OK;
+}
+
+int ngw_search_start(ngw_handle* h, ngw_search* s, const int32_t* roots_dev, int64_t count, int32_t* current) {
+    if (int rc = search_call_args(h, s)) return rc;
+    if (count < 0 || count > s->cap) return fail(NGW_E_INVALID_ARG, "%lld roots in a search of capacity %lld", (long long)count, (long long)s->cap);
+    if (count && !roots_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (int rc = enter(h)) return rc;
+    if (count) {
+        // the scratch of an iteration serves: values 0, tags NGW_TAG_ROOT; the values the table holds afterwards go to `info`, their tags to `plist`
+        HIP_TRY(hipMemsetAsync(s->values, 0, (size_t)count * sizeof(int32_t), h->stream));
+        HIP_TRY(hipMemsetAsync(s->tags, 0xFF, (size_t)count * sizeof(int32_t), h->stream));
+        if (int rc = ngw_state_keys(h, s->pool, roots_dev, count, NGW_KEY_STATE, s->keys)) return rc;
+        if (int rc = ngw_key_table_insert_min(h, s->table, s->keys, s->values, s->tags, count, s->where, s->fresh, s->best)) return rc;
+        if (int rc = ngw_key_table_read(h, s->table, s->where, count, s->info, s->plist)) return rc;
+    }
+    NgwSearchRoots x{};
+    x.roots = roots_dev; x.where = s->where; x.value = s->info; x.best = s->best; x.parents = s->parents[s->cur]; x.g = s->g; x.bucket = s->bucket;
+    x.count = count; x.capacity = s->cap; x.pool = s->pool_cap;
+    HIP_TRY(ngw_search_roots_launch(&x, h->stream));
+    if (current) *current = s->cur;
+    return NGW_OK;
+}
+
+int ngw_search_run(ngw_handle* h, ngw_search* s, int32_t iterations, int32_t* current) {
+    if (int rc = search_call_args(h, s)) return rc;
+    if (iterations < 0) return fail(NGW_E_INVALID_ARG, "%d iterations", (int)iterations);
+    if (int rc = enter(h)) return rc;
+    int rc = NGW_OK;
+    for (int32_t i = 0; i < iterations && rc == NGW_OK; i++) rc = iterate(h, s);
+    if (current) *current = s->cur;
+    return rc;
+}
+
+int ngw_search_read(ngw_handle* h, ngw_search* s, ngw_search_report* out) {
+    if (!h || !s || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns_search(h, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
+    if (int rc = enter(h)) return rc;
+    uint64_t head[2] = {0, 0};
+    uint32_t ring[SEARCH_RING][4];
+    int32_t cursor = 0;
+    uint32_t flags = 0;
+    HIP_TRY(hipMemcpyAsync(head, s->slab, sizeof(head), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipMemcpyAsync(ring, s->stats, sizeof(ring), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipMemcpyAsync(&cursor, s->cursor, sizeof(cursor), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipMemcpyAsync(&flags, h->b.flags, sizeof(flags), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (h->b.flags_host) flags |= *h->b.flags_host;
+    memset(out, 0, sizeof(*out));
+    out->iterations = s->iterations;
+    out->overflowed = head[1];
+    out->goal_value = (int32_t)((uint32_t)(head[0] >> 32) ^ 0x80000000u);
+    out->goal_bucket = (int32_t)(uint32_t)head[0];
+    out->cursor = cursor;
+    out->flags = flags;
+    out->rows = (int32_t)(s->iterations < NGW_SEARCH_ROWS ? s->iterations : NGW_SEARCH_ROWS);
+    out->current = s->cur;
+    for (int32_t i = 0; i < out->rows; i++)
+        memcpy(out->stats[i], ring[(s->iterations - out->rows + i) % SEARCH_RING], sizeof(ring[0]));
+    return NGW_OK;
+}
+
+}  // extern "C"

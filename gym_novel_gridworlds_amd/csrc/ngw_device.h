@@ -925,4 +925,73 @@ extern "C"
 #endif
 hipError_t ngw_frontier_select_launch(const struct NgwSelect* x, hipStream_t stream);
 
+/* Search runs (ngw_search.inc, ngw_abi_search.cpp): the glue of one best-first iteration between the five existing stages, as three kernels of one
+ * thread per position.  The contract is include/ngw.h's (ngw_search_run); search.relax_reference states the three in numpy.  n = capacity * A
+ * positions, position q = j * A + a: parent entry j, action a.
+ *   offer   values[q] = g[parents[j]] + cost, tags[q] = bucket[parents[j]] * A + a.  cost = lut[a] (by_action) or lut[NGW_INFO_COST(info[q])].  No
+ *           offer - values[q] = NGW_VALUE_NONE, tags[q] = NGW_TAG_ROOT - for a parent that is NGW_IDX_NONE or outside [0, pool), a g of
+ *           NGW_VALUE_NONE, and a sum outside [INT32_MIN, NGW_VALUE_NONE): the last is counted in row[NGW_SEARCH_OVERFLOW] and *overflowed.
+ *   judge   row[NGW_SEARCH_IMPROVED] += the positions with best[q] != 0; such a position whose info word has NGW_INFO_DONE and a message code other
+ *           than 14 lowers *goal to (uint32(values[q]) ^ 0x80000000) << 32 | uint32(where[q]) - the minimum taken inside the wave, one atomic per
+ *           wave that has one.  stop: best[q] = 0 wherever NGW_INFO_DONE(info[q]) is set.
+ *   settle  entry k < capacity of the chosen (first[k] = j, second[k] = a) and slots[k] = c: plist[k] = parents[j] (NGW_IDX_NONE for a padded
+ *           entry); where the entry and its slot are live, g[c] = values[j * A + a], bucket[c] = where[j * A + a] and next[k] = c, else next[k] =
+ *           NGW_IDX_NONE.  row[NGW_SEARCH_EXPANDED] += the live ones; thread 0 zero-fills next_row, the stats row of the following iteration.
+ * No index is used as an address unchecked: j against capacity, parents[j] and c against pool. */
+struct NgwSearch {
+    const int32_t* parents;     /* [capacity] */
+    int32_t* next;              /* [capacity]: the other parent list */
+    int32_t* g;                 /* [pool] */
+    int32_t* bucket;            /* [pool] */
+    const uint32_t* info;       /* [n] */
+    const int32_t* lut;         /* [64] */
+    int32_t* values;            /* [n] */
+    int32_t* tags;              /* [n] */
+    const int32_t* where;       /* [n] */
+    uint8_t* best;              /* [n] */
+    const int32_t* first;       /* [capacity] */
+    const int32_t* second;      /* [capacity] */
+    const int32_t* slots;       /* [capacity] */
+    int32_t* plist;             /* [capacity] */
+    unsigned long long* goal;   /* one word, all ones: no goal yet */
+    unsigned long long* overflowed;
+    uint32_t* row;              /* [4]: this iteration's stats */
+    uint32_t* next_row;         /* [4]: the next one's */
+    int64_t capacity, pool;
+    int32_t A, by_action, stop;
+};
+#define NGW_SEARCH_BLOCK 256     /* threads per workgroup: four waves, one position per lane */
+#define NGW_SEARCH_OFFERED 0     /* the columns of a stats row */
+#define NGW_SEARCH_IMPROVED 1
+#define NGW_SEARCH_EXPANDED 2
+#define NGW_SEARCH_OVERFLOW 3
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_search_offer_launch(const struct NgwSearch* x, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_search_judge_launch(const struct NgwSearch* x, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_search_settle_launch(const struct NgwSearch* x, hipStream_t stream);
+/* the roots of a search (ngw_search_start): for j < count, a root slot r = roots[j] in [0, pool) with where[j] >= 0 gets g[r] = value[j] and bucket[r] =
+ * where[j]; parents[j] = r where best[j] != 0, NGW_IDX_NONE otherwise and for count <= j < capacity. */
+struct NgwSearchRoots {
+    const int32_t* roots;       /* [count] */
+    const int32_t* where;       /* [count] */
+    const int32_t* value;       /* [count] */
+    const uint8_t* best;        /* [count] */
+    int32_t* parents;           /* [capacity] */
+    int32_t* g;                 /* [pool] */
+    int32_t* bucket;            /* [pool] */
+    int64_t count, capacity, pool;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_search_roots_launch(const struct NgwSearchRoots* x, hipStream_t stream);
+
 #endif

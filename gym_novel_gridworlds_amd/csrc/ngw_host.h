@@ -13,6 +13,8 @@
 //   ngw_abi_table.cpp    device-side key tables: a hash set of such keys that outlives the call - insert, lookup, count, clear -, and a value and a tag per key: insert_min, read, trace (ngw_table.inc)
 //   ngw_abi_frontier.cpp device-side frontiers: flags compacted into index lists of fixed capacity, slots handed out for them (ngw_frontier.inc),
 //                        the k best candidates per group in the same list form (ngw_select.inc)
+//   ngw_abi_search.cpp   search runs: the driver that enqueues whole best-first iterations - the five stages above through their own entry points, the three
+//                        kernels of ngw_search.inc between them
 //
 // Three rules hold in all of them:
 //   1. Guard first.  An entry point that uses the handle's stream or its device state starts with `if (int rc = enter(h)) return rc;`
@@ -76,6 +78,27 @@ struct ngw_key_table {
     uint64_t first = 0;                   // where base starts: first_sequence of ngw_key_table_create_valued, else 0
     uint64_t epoch = 0;                   // a valued table: the high half of the positions whose low halves the words of best[] carry (insert_min renormalises when base has left it)
     bool valued = false;
+};
+
+// A search run (ngw_abi_search.cpp): the pool and the table it works on - looked up by address in the handle's lists before every use, never
+// dereferenced first -, and ONE allocation of its handle that holds every array: the goal word and the overflow count, the keys, the int32 arrays
+// (stats rows, cost table, cursor and counts, the lists, g and bucket, the per-position scratch) and the two flag arrays.
+struct ngw_search {
+    ngw_snapshot* pool = nullptr;
+    ngw_key_table* table = nullptr;
+    int64_t cap = 0, pool_cap = 0, n = 0;   // n = cap * A positions
+    int32_t A = 0, by_action = 0, keep = -1, stop = 0;
+    int cur = 0;                          // which parent list is the current one
+    int64_t iterations = 0;
+    uint64_t* slab = nullptr;
+    unsigned long long* goal = nullptr;   // slab[0]; slab[1]: the offers dropped at the int32 range
+    uint64_t* keys = nullptr;             // [n]
+    uint32_t* stats = nullptr;            // [NGW_SEARCH_ROWS + 1][4], row i % (NGW_SEARCH_ROWS + 1): iteration i (the spare row: the next iteration's, zero-filled ahead)
+    int32_t *lut = nullptr, *cursor = nullptr, *count = nullptr, *taken = nullptr, *bound = nullptr;
+    int32_t* parents[2] = {nullptr, nullptr};
+    int32_t *first = nullptr, *second = nullptr, *slots = nullptr, *plist = nullptr, *g = nullptr, *bucket = nullptr;
+    int32_t *info = nullptr, *values = nullptr, *tags = nullptr, *where = nullptr;
+    uint8_t *fresh = nullptr, *best = nullptr;
 };
 
 struct ngw_handle {
@@ -232,6 +255,7 @@ struct ngw_handle {
     int plan_major = 0;                   // NGW_PLAN_ORDER=plan when the buffers were first allocated: the plan-major block order (A/B, tools/plan_cost.py)
     std::vector<ngw_snapshot*> snaps;     // open snapshots (ngw_snapshot_create); their slabs are in `allocs`, ngw_destroy deletes what is left
     std::vector<ngw_key_table*> tables;   // open key tables (ngw_key_table_create); likewise
+    std::vector<ngw_search*> searches;    // open search runs (ngw_search_create); likewise
     // Frontiers (ngw_abi_frontier.cpp): the scratch of ngw_frontier_compact / ngw_frontier_alloc, allocated on first use and regrown when a call
     // brings more tiles - word 0 the allocation's ticket (0 between the calls), the tile counts behind it
     int32_t* frontier_scratch = nullptr;

@@ -161,7 +161,8 @@ class ShardedVecNovelGridworld:
 
     def snapshot(self, capacity=None):
         """A device-side snapshot of this rank's shard (VecNovelGridworld.snapshot): rank-local, env indices are the shard's own - in
-        save / restore and in expand / expand_all (from_envs=True: parents are the shard's envs 0 .. num_envs-1)."""
+        save / restore and in expand / expand_all (from_envs=True: parents are the shard's envs 0 .. num_envs-1).  Its frontier() and its
+        search() are rank-local with it: a search runs over this rank's pool and this rank's key_table(), nothing is exchanged."""
         return self.local.snapshot(capacity)
 
     def state_keys(self, envs=None, fields=KEY_STATE, device=False):

@@ -31,6 +31,10 @@ which improved states to expand) with nothing in the loop that waits for the hos
     t = table.trace(table.lookup(goal_keys, device=True), steps, device=True)                     # the cheapest plan found to each goal, from its root
     pool.rollout(root_slot_of[t.root], t.plans, limits=t.length.clamp(0, steps), children=c, device=True)
 
+The same loop as one object: s = pool.search(table, capacity); s.start(roots); s.run(depth) enqueues `depth` of these iterations from one
+call, keeps g and bucket itself and records the cheapest goal reached (search.py; include/ngw.h ngw_search_*).  The loop above stays what an
+iteration IS, and the form to write when a step of it has to differ.
+
 All calls run on the env's stream, in the order they are made; concurrent inserts into one table from two streams are not supported."""
 import collections
 import ctypes as C

@@ -1,0 +1,312 @@
+"""Device-side search runs of a Snapshot: whole best-first iterations over one node pool and one valued key table, enqueued from ONE call
+with no host wait in between (include/ngw.h ngw_search_*; the kernels are csrc/ngw_search.inc, the driver csrc/ngw_abi_search.cpp).
+
+    table = env.key_table(1 << 20, values=True)
+    s = pool.search(table, capacity)                      # costs=None: the step costs, round(STEP_COSTS[code] * scale); or an int32 [A] array
+    s.reset_cursor(n_roots)                               # the next free slot of the pool
+    s.start(roots)                                        # value 0, tag TAG_ROOT; s.g / s.bucket of the roots; s.parents = the roots
+    while True:
+        s.run(8)                                          # eight iterations, enqueued; returns at once
+        goal = s.goal()                                   # the host's poll: the cheapest goal reached so far, (VALUE_NONE, -1) while none is
+        if goal.bucket >= 0: break
+    t = s.goal_plan(64)                                   # table.trace of the goal's bucket: Trace(plans, length, root)
+
+One iteration is exactly the loop of key_table.py's docstring - successor_keys, insert_min, compact (or select with keep=k), alloc, expand,
+called as that loop calls them - with the torch operations between them as three kernels: the OFFER (g[parent] + cost and the tag of every
+(parent, action)), the JUDGE (the cheapest goal among the improved positions; with stop_at_goals, ended states are not expanded) and the
+SETTLE (the expand lists, g and bucket of the children, the next parents).  relax_reference() states the three in numpy.
+
+A search is rank-local, as a frontier is: under ShardedVecNovelGridworld it belongs to the local env's pool and table."""
+import collections
+import ctypes as C
+
+import numpy as np
+
+from . import _cabi
+from .frontier import MAX_CAPACITY, MAX_FLAGS, alloc_reference, check_capacity, compact_reference, select_reference
+from .key_table import TAG_ROOT, VALUE_NONE, insert_min_reference
+from .spec import IDX_NONE, STEP_COSTS
+
+INT32_MIN = -(1 << 31)
+MSG_DIED = 14                 # the message code of a FireWall death (Expansion.died)
+STATS_ROWS = _cabi.SEARCH_ROWS    # include/ngw.h NGW_SEARCH_ROWS: the iterations stats() keeps
+
+SearchGoal = collections.namedtuple('SearchGoal', 'value bucket')
+SearchStats = collections.namedtuple('SearchStats', 'iterations offered improved expanded overflow overflowed cursor flags')
+Relaxed = collections.namedtuple('Relaxed', 'values tags best goal parents actions children next_parents cursor offered improved expanded overflow full')
+
+
+def cost_table(costs, scale, n_actions):
+    """The 64 int32 the offer kernel reads and how it indexes them -> (table, by_action).  costs None: round(STEP_COSTS[code] * scale) by the
+    cost code of the step's info word - the table of key_table.step_cost_values, refused as there; else `costs`, one int32 per action."""
+    lut = np.zeros(64, np.int32)
+    if costs is None:
+        values = [int(round(c * scale)) for c in STEP_COSTS]
+        if not all(0 <= v < VALUE_NONE for v in values):
+            raise ValueError("scale: %r takes a step cost outside [0, 2^31 - 1)" % (scale,))
+        lut[:len(values)] = values
+        return lut, False
+    if hasattr(costs, 'data_ptr'):
+        costs = costs.cpu().numpy()
+    c = np.asarray(costs)
+    if c.dtype.kind not in 'iu' or c.shape != (n_actions,):
+        raise ValueError("costs: one integer per action expected, shape [%d], got dtype %s, shape %s" % (n_actions, c.dtype, list(c.shape)))
+    if c.size and (int(c.min()) < INT32_MIN or int(c.max()) >= VALUE_NONE):
+        raise ValueError("costs: an entry outside [-2^31, 2^31 - 1)")
+    lut[:n_actions] = c
+    return lut, True
+
+
+def offer_reference(parents, g, bucket, info, n_actions, lut, by_action):
+    """Step 2 in numpy -> (values int32 [P * A], tags int32 [P * A], overflow bool [P * A]).  parents int32 [P]; g, bucket int32 [pool]; info
+    uint32 [P * A].  Position q = j * A + a offers g[parents[j]] + cost, tagged bucket[parents[j]] * A + a; no offer - (VALUE_NONE, TAG_ROOT) -
+    for a parent outside [0, pool) (IDX_NONE is), a g of VALUE_NONE, and a sum outside [-2^31, VALUE_NONE): the last is `overflow`."""
+    parents, g, bucket = np.asarray(parents, np.int64), np.asarray(g, np.int64), np.asarray(bucket, np.int64)
+    A, P = int(n_actions), len(parents)
+    info = np.asarray(info).reshape(-1).astype(np.int64)
+    a = np.tile(np.arange(A), P)
+    p = np.repeat(parents, A)
+    live = (p >= 0) & (p < len(g))
+    at = np.where(live, p, 0)
+    live &= g[at] != VALUE_NONE
+    cost = np.asarray(lut, np.int64)[a if by_action else (info >> 2) & 63]
+    total = g[at] + cost
+    overflow = live & ((total >= VALUE_NONE) | (total < INT32_MIN))
+    live &= ~overflow
+    values = np.where(live, total, VALUE_NONE).astype(np.int32)
+    tags = np.where(live, bucket[at] * A + a, TAG_ROOT).astype(np.int32)
+    return values, tags, overflow
+
+
+def judge_reference(best, info, values, where, goal=SearchGoal(VALUE_NONE, -1), stop_at_goals=False):
+    """Step 4 in numpy -> (best afterwards bool [n], the goal afterwards, improved: the positions with best set).  A position with best set
+    whose info word has the done bit (bit 1) and a message code other than 14 is a goal: the smallest (value, bucket) pair of them and of
+    `goal` stays.  stop_at_goals: best is cleared wherever the done bit is set."""
+    best = np.asarray(best).reshape(-1).astype(bool)
+    info = np.asarray(info).reshape(-1).astype(np.int64)
+    ended = ((info >> 1) & 1) != 0
+    is_goal = best & ended & (((info >> 8) & 255) != MSG_DIED)
+    pair = (int(goal[0]), int(goal[1]) & 0xFFFFFFFF)                           # (the bucket ordered as the device orders it: unsigned)
+    for q in np.flatnonzero(is_goal).tolist():
+        pair = min(pair, (int(values[q]), int(where[q]) & 0xFFFFFFFF))
+    bucket = pair[1] - (1 << 32) if pair[1] >= 1 << 31 else pair[1]
+    return (best & ~ended if stop_at_goals else best), SearchGoal(pair[0], bucket), int(best.sum())
+
+
+def settle_reference(first, second, slots, parents, values, where, g, bucket, n_actions):
+    """Step 6 in numpy -> (expand's parents int32 [capacity], the next parent list int32 [capacity], expanded).  Entry k of the chosen (first[k]
+    = j, second[k] = a) with slot c = slots[k]: the expand pair is (parents[j], a, c); where c is a slot of the pool, g[c] = values[j * A + a],
+    bucket[c] = where[j * A + a] (both updated in place) and the next list holds c.  A padded entry gives IDX_NONE in both lists."""
+    A, cap = int(n_actions), len(first)
+    plist, nxt, expanded = np.full(cap, IDX_NONE, np.int32), np.full(cap, IDX_NONE, np.int32), 0
+    for k in range(cap):
+        j, a, c = int(first[k]), int(second[k]), int(slots[k])
+        if not (0 <= j < cap and 0 <= a < A):
+            continue
+        plist[k] = parents[j]
+        if 0 <= c < len(g):
+            g[c], bucket[c], nxt[k] = values[j * A + a], where[j * A + a], c
+            expanded += 1
+    return plist, nxt, expanded
+
+
+def relax_reference(parents, g, bucket, info, keys, where, held, cursor, n_actions, lut, by_action, keep=None, stop_at_goals=False,
+                    goal=SearchGoal(VALUE_NONE, -1), limit=None):
+    """One iteration of Search.run between its successor keys and its expand, in numpy: steps 2 to 6 of include/ngw.h's ngw_search_run ->
+    Relaxed.  parents int32 [capacity]; g, bucket int32 [pool], updated in place; info, keys [capacity * A]: what successor_keys reports for
+    the parents; where int32 [capacity * A]: the bucket the table gives each key (-1: key 0 or refused - which bucket a key gets is the
+    table's choice, so it is an input here); held: the table before the call as insert_min_reference takes it, updated in place; cursor: the
+    slot cursor; limit: one past the last slot (None: the pool's size).
+    Relaxed.parents / .actions / .children are expand's three lists, .next_parents the frontier of the next iteration, .full whether
+    F_FRONTIER_FULL is due (more chosen than `capacity`, or fewer slots left than chosen)."""
+    parents = np.asarray(parents, np.int32)
+    cap, A = len(parents), int(n_actions)
+    where = np.asarray(where, np.int32).reshape(-1)
+    ks = np.asarray(keys).reshape(-1)
+    ks = ks.astype(np.int64 if ks.dtype.kind == 'i' else np.uint64).view(np.uint64)
+    values, tags, overflow = offer_reference(parents, g, bucket, info, A, lut, by_action)
+    _, _, best = insert_min_reference(held, ks, values, tags, refused=(where < 0) & (ks != 0))
+    best, goal, improved = judge_reference(best, info, values, where, goal, stop_at_goals)
+    if keep is None:
+        first, second, count, full = compact_reference(best, A, None, cap)
+    else:
+        first, second, _, _, count = select_reference(values, int(keep), A, None, best, 1, False, cap)
+        full = False
+    slots, cursor, short = alloc_reference(int(count[0]), cursor, len(g) if limit is None else limit, cap)
+    plist, nxt, expanded = settle_reference(first, second, slots, parents, values, where, g, bucket, A)
+    return Relaxed(values, tags, best, goal, plist, second, slots, nxt, cursor, int((values != VALUE_NONE).sum()), improved, expanded,
+                   int(overflow.sum()), bool(full or short))
+
+
+def check_roots(roots, limit, capacity, device_len=None):
+    """The host-side check of start()'s roots: a list / numpy array of one dimension and integer dtype whose entries are slots in [0, limit) or
+    IDX_NONE -> a contiguous int32 array; device_len(x): the length of x when it is a device tensor to be used in place (its values are then
+    not checked), else None.  At most `capacity` roots.  Returns (roots, count)."""
+    n = None if device_len is None else device_len(roots)
+    if n is None:
+        if roots is None:
+            raise ValueError("roots: a list of slots expected")
+        a = np.asarray(roots)
+        if a.size == 0 and a.ndim == 1:
+            a = np.zeros(0, np.int32)
+        if a.dtype.kind not in 'iu':
+            raise ValueError("roots: integer slots expected, got dtype %s" % a.dtype)
+        if a.ndim != 1:
+            raise ValueError("roots: a one-dimensional list expected, got shape %s" % (a.shape,))
+        bad = a[(a != IDX_NONE) & ((a < 0) | (a >= limit))]
+        if bad.size:
+            raise ValueError("roots: %d outside [0, %d)" % (int(bad[0]), limit))
+        roots, n = np.ascontiguousarray(a, np.int32), int(a.size)
+    if n > capacity:
+        raise ValueError("roots: %d roots in a search of capacity %d" % (n, capacity))
+    return roots, int(n)
+
+
+class Search:
+    """Whole best-first iterations over one Snapshot (the node pool) and one KeyTable made with values=True (Snapshot.search).  It owns, in the
+    env's device memory, two parent lists that take turns (`parents`: the current one, int32 [capacity], IDX_NONE-padded), `g` and `bucket`
+    (int32 [pool.capacity]: the cost and the bucket each slot was reached with, VALUE_NONE / -1 before), `cursor` (int32 [1]: the next slot
+    the allocation hands out) and the scratch of capacity * A entries per array; run() allocates nothing.  start() and run() are enqueued on
+    the env's stream and return at once; goal() and stats() wait.  The tensors are views of the library's memory: they are gone with close(),
+    with the snapshot, the table or the env.
+    costs: None - the step costs, round(STEP_COSTS[code] * scale) by each step's cost code (key_table.step_cost_values' table) -, or one
+    int32 per action.  keep: None - every state reached more cheaply goes on (Frontier.compact) -, or k: the k cheapest of them
+    (Frontier.select, one group, by g alone; ties: the smaller position).  stop_at_goals: a state whose step reported done - goal or
+    FireWall death - is stored and valued but never expanded.
+    An offer never wraps: where g + cost would reach VALUE_NONE no offer is made, and stats() counts it (step_cost_values on the host wraps
+    silently, as it says).  F_FRONTIER_FULL, F_TABLE_FULL and F_BAD_INDEX are raised where the hand-written loop raises them."""
+
+    def __init__(self, snap, table, capacity, costs=None, scale=1, keep=None, stop_at_goals=False):
+        import torch
+        from .snapshot import MapsTooLarge
+        from .vec_env import _DevArray
+        self.snap, self.env, self.table = snap, snap.env, table
+        snap._open()
+        if not hasattr(table, '_open_for'):
+            raise ValueError("table: a KeyTable expected")
+        table._open_for(self.env)
+        table._valued()
+        self.capacity = check_capacity(capacity)
+        A = self.env.n_actions
+        if not 1 <= self.capacity <= snap.capacity:
+            raise ValueError("capacity: %d outside [1, the pool's %d]" % (self.capacity, snap.capacity))
+        if self.capacity * A > MAX_FLAGS:
+            raise ValueError("capacity: %d parents by %d actions in one iteration (at most 2^24 positions)" % (self.capacity, A))
+        if keep is not None:
+            if isinstance(keep, bool) or not isinstance(keep, (int, np.integer)) or not 0 <= keep <= MAX_CAPACITY:
+                raise ValueError("keep: None or an integer in [0, 2^31 - 1] expected, got %r" % (keep,))
+            if keep > self.capacity:
+                raise ValueError("keep: %d entries do not fit the capacity %d" % (keep, self.capacity))
+        self.keep, self.stop_at_goals = (None if keep is None else int(keep)), bool(stop_at_goals)
+        self.costs, self.by_action = cost_table(costs, scale, A)
+        self._s, self._keep, self._cur = C.c_void_p(), None, 0
+        arrays = _cabi.SearchArrays()
+        try:
+            _cabi.check(_cabi.lib().ngw_search_create(self.env._h, snap._s, table._t, self.capacity, _cabi._ptr(self.costs, np.int32), int(self.by_action),
+                                                      -1 if self.keep is None else self.keep, int(self.stop_at_goals), C.byref(arrays), C.byref(self._s)))
+        except ValueError as e:
+            if str(e).startswith('map_size'):
+                raise MapsTooLarge(str(e)) from None
+            raise
+        dev = 'cuda:%d' % self.env.device
+        view = lambda ptr, n: torch.as_tensor(_DevArray(ptr, (n,), '<i4'), device=dev)   # noqa: E731
+        self._lists = [view(arrays.parents[0], self.capacity), view(arrays.parents[1], self.capacity)]
+        self.g, self.bucket, self.cursor = view(arrays.g, snap.capacity), view(arrays.bucket, snap.capacity), view(arrays.cursor, 1)
+        self._dev = torch.device(dev)
+
+    def _open(self):
+        if not self._s:
+            raise ValueError("search is closed")
+        self.snap._open()
+        self.table._open_for(self.env)
+        return self._s
+
+    @property
+    def parents(self):
+        """The current frontier: int32 [capacity], IDX_NONE-padded (the list the next iteration expands)."""
+        self._open()
+        return self._lists[self._cur]
+
+    def _enqueue(self, call, uploaded=()):
+        from .snapshot import enqueue_ordered
+        cur = C.c_int32(self._cur)
+        try:
+            enqueue_ordered(self.env, self, lambda: call(C.byref(cur)), 1, list(uploaded), True)
+        finally:
+            self._cur = int(cur.value)
+        # An uploaded list need not be held for the next call to synchronise on: it was allocated on torch's current stream, which
+        # enqueue_ordered has just made wait for the env's stream, and torch's allocator hands a freed block only to later work of the
+        # stream it was allocated on - work that is ordered behind the launch that reads the list.  So start(list); run(k) has no host wait.
+        self._keep = None
+
+    def reset_cursor(self, start=0):
+        """The next slot the allocation hands out (on torch's current stream; no host wait) - as on Frontier."""
+        self._open()
+        if isinstance(start, bool) or not isinstance(start, (int, np.integer)) or not 0 <= start <= MAX_CAPACITY:
+            raise ValueError("start: an integer in [0, 2^31 - 1] expected, got %r" % (start,))
+        self.cursor.fill_(int(start))
+
+    def start(self, roots):
+        """The roots of the search - slots of the pool: a list / numpy array (checked; IDX_NONE is allowed and skipped) or a contiguous torch
+        int32 tensor on the env's device, used in place; at most `capacity`.  Their keys are offered to the table with value 0 and tag
+        TAG_ROOT (insert_keys_min); g[root] = the value the table then holds, bucket[root] = its bucket, and `parents` becomes the roots -
+        IDX_NONE where a root's state was already held at a value of 0 or below, as the second position of a repeated state is.  Enqueued;
+        no host wait."""
+        from .snapshot import tensor_len, upload
+        s = self._open()
+        r, count = check_roots(roots, self.snap.capacity, self.capacity, lambda x: tensor_len(self._dev, 'roots', x))
+        (ptr,), uploaded = upload(self._dev, count, r)
+        h, L = self.env._h, _cabi.lib()
+        self._enqueue(lambda cur: L.ngw_search_start(h, s, ptr, count, cur), uploaded)
+
+    def run(self, iterations=1):
+        """`iterations` whole iterations, enqueued on the env's stream; returns at once.  An iteration whose frontier is empty runs the same
+        launches, which leave early."""
+        s = self._open()
+        if isinstance(iterations, bool) or not isinstance(iterations, (int, np.integer)) or not 0 <= iterations <= MAX_CAPACITY:
+            raise ValueError("iterations: an integer in [0, 2^31 - 1] expected, got %r" % (iterations,))
+        h, L = self.env._h, _cabi.lib()
+        self._enqueue(lambda cur: L.ngw_search_run(h, s, int(iterations), cur))
+
+    def _read(self):
+        rep = _cabi.SearchReport()
+        _cabi.check(_cabi.lib().ngw_search_read(self.env._h, self._open(), C.byref(rep)))
+        return rep
+
+    def goal(self):
+        """SearchGoal(value, bucket): the cheapest goal the search has reached - the smallest (value, bucket) among the positions that
+        brought a goal state a smaller value -, (VALUE_NONE, -1) while none was.  Waits for the env's stream."""
+        rep = self._read()
+        return SearchGoal(int(rep.goal_value), int(rep.goal_bucket))
+
+    def goal_plan(self, steps, device=False):
+        """table.trace of the goal's bucket: Trace(plans [steps, 1], length [1], root [1]) - the cheapest plan found to the goal, from its
+        root; length -1 while no goal was reached.  Waits (goal())."""
+        return self.table.trace(np.array([self.goal().bucket], np.int32), steps, device=device)
+
+    def stats(self):
+        """SearchStats: iterations run; offered / improved / expanded / overflow, uint32 arrays with one entry per iteration of the last 64,
+        oldest first - the positions that made an offer, those that brought their key a smaller value, the children written, the offers
+        dropped because g + cost left the int32 range -; overflowed: the last over the whole search; cursor: the next free slot; flags: the
+        env's sticky flags (error_flags()), left standing.  Waits for the env's stream."""
+        rep = self._read()
+        rows = np.ctypeslib.as_array(rep.stats).reshape(STATS_ROWS, 4)[:rep.rows].copy()
+        return SearchStats(int(rep.iterations), rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], int(rep.overflowed), int(rep.cursor), int(rep.flags))
+
+    @property
+    def closed(self):
+        return not self._s
+
+    def close(self):
+        if self._s and self.env._h:
+            _cabi.check(_cabi.lib().ngw_search_destroy(self.env._h, self._s))
+        self._invalidate()
+        searches = self.snap.__dict__.get('_searches')
+        if searches and self in searches:
+            searches.remove(self)
+
+    def _invalidate(self):
+        """The handle is gone (or going), and the arrays with it."""
+        self._s = C.c_void_p()
+        self._lists = self.g = self.bucket = self.cursor = None
+        self._keep = None

@@ -1043,6 +1043,20 @@ class Snapshot:
         self._open()
         return Frontier(self, capacity)
 
+    # ------------------------------------------------------------------ device-side search runs (include/ngw.h ngw_search_*; search.py)
+    def search(self, table, capacity, costs=None, scale=1, keep=None, stop_at_goals=False):
+        """A Search over this snapshot - the node pool - and `table` (a KeyTable of the same env made with values=True): whole iterations of
+        the label-correcting loop of key_table.py's docstring, `capacity` parents each, enqueued from one call with no host wait in between;
+        it keeps the cost and the bucket every slot was reached with and the cheapest goal reached (search.py says what an iteration is).
+        costs: None - the step costs times `scale`, rounded - or one int32 per action; keep: None or the k cheapest improved states that go
+        on; stop_at_goals: ended states are not expanded.  ValueError for a table without values and for keep > capacity; maps beyond
+        successor_keys' 34 x 34 raise what successor_keys raises.  Closed by its close() and with this snapshot."""
+        from .search import Search
+        self._open()
+        s = Search(self, table, capacity, costs, scale, keep, stop_at_goals)
+        self.__dict__.setdefault('_searches', []).append(s)
+        return s
+
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""
         self._open()
@@ -1064,6 +1078,8 @@ class Snapshot:
 
     def close(self):
         if self._s and self.env._h:
+            for s in list(self.__dict__.get('_searches', ())):
+                s.close()
             _cabi.check(_cabi.lib().ngw_snapshot_destroy(self.env._h, self._s))
         self._invalidate()
         snaps = self.env.__dict__.get('_snapshots')
@@ -1074,3 +1090,5 @@ class Snapshot:
         """The handle is gone (or going), and the buffer with it."""
         self._s = C.c_void_p()
         self._keep = None
+        for s in self.__dict__.pop('_searches', ()):
+            s._invalidate()

@@ -1075,6 +1075,69 @@ int ngw_frontier_select(ngw_handle* h, const int32_t* values_dev, const uint8_t*
                         const int32_t* map_dev /* NULL: the identity */, int32_t keep, int32_t largest, int64_t capacity, int32_t* first_dev,
                         int32_t* second_dev /* NULL: not wanted */, int32_t* taken_dev, int32_t* bound_dev, int32_t* count_dev);
 
+/* Search runs: whole best-first iterations over one snapshot pool and one valued key table, enqueued from ONE call with no host wait in between - the
+ * label-correcting loop built from ngw_successor_keys, ngw_key_table_insert_min, ngw_frontier_compact / _select, ngw_frontier_alloc and
+ * ngw_snapshot_expand as a library object, which also keeps the cost and the bucket every slot was reached with and the cheapest goal reached.
+ * With A = the spec's n_actions, a search of `capacity` over `pool` and `table` owns, in DEVICE memory (ngw_search_arrays): two parent lists int32
+ * [capacity] that take turns - the current frontier, NGW_IDX_NONE-padded -, g and bucket int32 [pool's capacity] - NGW_VALUE_NONE / -1 until a slot is
+ * reached -, the cursor of its slot allocation int32 [1] (0 at creation; the caller sets it to the first free slot of the pool), and scratch of
+ * capacity * A entries per array.  ngw_search_run allocates nothing.
+ * cost(a, w), the cost of action a whose step reports the info word w: costs[a] when the search was created with by_action != 0, else
+ * costs[NGW_INFO_COST(w)]; the table of 64 int32 is the caller's (the step costs scaled and rounded, or any other).
+ *   start    the roots roots[0 .. count) (slots of the pool, DEVICE memory, count <= capacity, NGW_IDX_NONE allowed: skipped): their keys under
+ *            NGW_KEY_STATE offered to the table by ngw_key_table_insert_min with value 0 and tag NGW_TAG_ROOT; then g[roots[j]] = the value the table
+ *            holds for that key, bucket[roots[j]] = its bucket, and the current parent list becomes: roots[j] where best[j] was set - the first
+ *            position of a state the table did not hold at 0 or below -, NGW_IDX_NONE elsewhere and behind `count`.
+ *   run      `iterations` times, in this order, with P the current parent list and N the other one:
+ *            1. ngw_successor_keys of P under NGW_KEY_STATE: keys and info words [capacity][A]; position q = j * A + a.
+ *            2. offer: values[q] = g[P[j]] + cost(a, info[q]), tags[q] = bucket[P[j]] * A + a.  A padded parent (NGW_IDX_NONE, or any slot outside
+ *               the pool), a parent whose g is NGW_VALUE_NONE, and a sum that would reach or pass NGW_VALUE_NONE (or fall below INT32_MIN) offer
+ *               NGW_VALUE_NONE - no offer - and never wrap; the last case is counted (ngw_search_report: overflow, overflowed).
+ *            3. ngw_key_table_insert_min(keys, values, tags): where, fresh, best.
+ *            4. judge: a position with best[q] set whose info word has NGW_INFO_DONE set and a message code other than 14 (a FireWall death) is a
+ *               goal reached more cheaply: the search's goal word is lowered to the smallest (values[q], where[q]) pair - ordered by value, then by
+ *               bucket; a bucket holds one key, so the result does not depend on the order the device runs in.  With stop_at_goals, best[q] is
+ *               then cleared wherever NGW_INFO_DONE is set, goal or death: an ended state is stored and valued but never expanded.
+ *            5. keep < 0: ngw_frontier_compact(best, div = A); keep >= 0: ngw_frontier_select(values, flags = best, one group, keep, smallest first,
+ *               div = A); both without a map: entries (j, a).  Then ngw_frontier_alloc on the search's cursor with limit = the pool's capacity.
+ *            6. settle: for every entry k with a slot c = slots[k]: the expand lists (P[j], a, c); g[c] = values[j * A + a], bucket[c] = where[j * A +
+ *               a], N[k] = c.  An entry without a slot (a full pool) keeps its pair with child NGW_IDX_NONE - skipped by the expand - and N[k] =
+ *               NGW_IDX_NONE; padded entries stay NGW_IDX_NONE and write nothing.
+ *            7. ngw_snapshot_expand(pool, the lists, pool), launched at `capacity`.  N becomes the current list.
+ *            An iteration whose frontier is empty runs the same launches; they leave early.  NGW_F_FRONTIER_FULL, NGW_F_TABLE_FULL and
+ *            NGW_F_BAD_INDEX are raised exactly where the five calls raise them; the three kernels raise none.  Every launch is enqueued on the
+ *            handle's stream; nothing waits.  Nothing is committed: no env state, mask, lookahead table or mirror changes, a captured graph stays valid.
+ *   read     waits for the stream: the iterations run, the goal (NGW_VALUE_NONE, -1 while none was reached), the cursor, the handle's sticky flags
+ *            and, for the last `rows` = min(iterations, 64) iterations, oldest first, offered (positions that made an offer) / improved (best set by
+ *            insert_min) / expanded (children written) / overflow.
+ * `current` (may be NULL) receives which of the two parent lists is the current one.
+ * NGW_E_INVALID_ARG: a NULL argument; a pool or table that is not open on this handle (also when it was closed since the creation); a table without
+ * values; capacity outside [1, the pool's capacity] or capacity * A beyond 2^24; keep > capacity; buckets * A > 2^31 - 1 (a tag would not fit); maps
+ * beyond ngw_successor_keys' limit; count outside [0, capacity]; iterations < 0. */
+typedef struct ngw_search ngw_search;
+typedef struct ngw_search_arrays {
+    void* parents[2];
+    void* g;
+    void* bucket;
+    void* cursor;
+} ngw_search_arrays;
+#define NGW_SEARCH_ROWS 64
+typedef struct ngw_search_report {
+    int64_t iterations;
+    uint64_t overflowed;        /* offers dropped because the sum left the int32 range, over the whole search */
+    int32_t goal_value, goal_bucket;
+    int32_t cursor;
+    uint32_t flags;             /* ngw_error_flags, read without clearing */
+    int32_t rows, current;
+    uint32_t stats[NGW_SEARCH_ROWS][4];   /* offered, improved, expanded, overflow */
+} ngw_search_report;
+int ngw_search_create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, int64_t capacity, const int32_t* costs_host /* [64] */, int32_t by_action,
+                      int32_t keep /* < 0: every improved state */, int32_t stop_at_goals, ngw_search_arrays* arrays, ngw_search** out);
+int ngw_search_destroy(ngw_handle* h, ngw_search* s);
+int ngw_search_start(ngw_handle* h, ngw_search* s, const int32_t* roots_dev, int64_t count, int32_t* current);
+int ngw_search_run(ngw_handle* h, ngw_search* s, int32_t iterations, int32_t* current);
+int ngw_search_read(ngw_handle* h, ngw_search* s, ngw_search_report* out);
+
 /* Guided playouts: ngw_snapshot_playout_traj_views whose weights depend on the STATE - at every step the pair's current state is looked up in a key
  * table, and where the table holds it the choice is made under that bucket's row of the caller's weights.  The selection phase of MCTS (descend by
  * the tree's statistics while the node is in the tree), tabular Q / softmax policies, Go-Explore's "return, then explore" and playouts whose bias is
