@@ -33,7 +33,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_snapshot_rollout_traj', 'ngw_snapshot_playout_traj', 'ngw_snapshot_rollout_traj_views', 'ngw_snapshot_playout_traj_views', 'ngw_snapshot_playout_guided',
            'ngw_key_table_create', 'ngw_key_table_destroy', 'ngw_key_table_clear', 'ngw_key_table_insert', 'ngw_key_table_lookup', 'ngw_key_table_count',
            'ngw_key_table_create_valued', 'ngw_key_table_insert_min', 'ngw_key_table_read', 'ngw_key_table_trace',
-           'ngw_search_create', 'ngw_search_destroy', 'ngw_search_start', 'ngw_search_run', 'ngw_search_read',
+           'ngw_search_create', 'ngw_search_destroy', 'ngw_search_start', 'ngw_search_run', 'ngw_search_read', 'ngw_search_create_open', 'ngw_search_read_open',
            'ngw_snapshot_walk', 'ngw_frontier_compact', 'ngw_frontier_alloc', 'ngw_frontier_select', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
@@ -58,6 +58,25 @@ class SearchReport(C.Structure):
     """include/ngw.h ngw_search_report."""
     _fields_ = [('iterations', C.c_int64), ('overflowed', C.c_uint64), ('goal_value', C.c_int32), ('goal_bucket', C.c_int32), ('cursor', C.c_int32),
                 ('flags', C.c_uint32), ('rows', C.c_int32), ('current', C.c_int32), ('stats', (C.c_uint32 * 4) * SEARCH_ROWS)]
+
+
+SEARCH_H_NONE, SEARCH_H_MIN, SEARCH_H_MAX = 0, 1, 2      # include/ngw.h NGW_SEARCH_H_*
+
+
+class SearchOptions(C.Structure):
+    """include/ngw.h ngw_search_options: what ngw_search_create_open takes."""
+    _fields_ = [('capacity', C.c_int64), ('costs_host', C.c_void_p), ('by_action', C.c_int32), ('keep', C.c_int32), ('stop_at_goals', C.c_int32),
+                ('prune', C.c_int32), ('heuristic', C.c_int32), ('n_weights', C.c_int32), ('weights_host', C.c_void_p)]
+
+
+class SearchArraysOpen(C.Structure):
+    """include/ngw.h ngw_search_arrays_open: ngw_search_arrays and the two arrays of an open-list search."""
+    _fields_ = [('base', SearchArrays), ('h', C.c_void_p), ('f', C.c_void_p)]
+
+
+class SearchOpenReport(C.Structure):
+    """include/ngw.h ngw_search_open_report."""
+    _fields_ = [('iterations', C.c_int64), ('rows', C.c_int32), ('reserved', C.c_int32), ('stats', (C.c_int32 * 6) * SEARCH_ROWS)]
 
 
 class NgwError(RuntimeError):
@@ -233,6 +252,9 @@ def lib():
         L.ngw_search_start.argtypes = [vp, vp, vp, i64, C.POINTER(i32)]
         L.ngw_search_run.argtypes = [vp, vp, i32, C.POINTER(i32)]
         L.ngw_search_read.argtypes = [vp, vp, C.POINTER(SearchReport)]
+    if hasattr(L, 'ngw_search_create_open'):
+        L.ngw_search_create_open.argtypes = [vp, vp, vp, C.POINTER(SearchOptions), C.POINTER(SearchArraysOpen), C.POINTER(vp)]
+        L.ngw_search_read_open.argtypes = [vp, vp, C.POINTER(SearchOpenReport)]
     if hasattr(L, 'ngw_snapshot_copy'):
         L.ngw_snapshot_copy.argtypes = [vp, vp, vp, vp, vp, i64]
     if hasattr(L, 'ngw_key_table_create'):

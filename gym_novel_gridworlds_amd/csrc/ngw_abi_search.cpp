@@ -2,7 +2,8 @@
 // call.  The driver owns no stage of its own: successor keys, insert_min, compaction / selection, slot allocation and expand run through their own
 // entry points (ngw_abi_snapshot.cpp, ngw_abi_table.cpp, ngw_abi_frontier.cpp), called as any caller calls them, with the three kernels of
 // ngw_search.inc between them.  The calls write no env state: they neither call state_written() nor touch anything the handle derives from its
-// state.  All run on the handle's stream, behind enter(); only ngw_search_read waits.
+// state.  All run on the handle's stream, behind enter(); only ngw_search_read / _read_open wait.  An open-list search (ngw_search_create_open) adds
+// the selection over f in front, the walk of the children behind, and the take and open kernels; the same driver serves it.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -43,17 +44,27 @@ NgwSearch search_args(const ngw_search* s) {
     x.goal = s->goal; x.overflowed = s->goal + 1;
     x.row = s->stats + 4 * (s->iterations % SEARCH_RING); x.next_row = s->stats + 4 * ((s->iterations + 1) % SEARCH_RING);
     x.capacity = s->cap; x.pool = s->pool_cap; x.A = s->A; x.by_action = s->by_action; x.stop = s->stop;
+    if (s->open) {
+        x.f = s->f; x.h = s->h; x.slot_of_bucket = s->slot_of_bucket; x.dist = s->dist; x.weights = s->weights; x.sel_count = s->count;
+        x.orow = s->ostats + NGW_SEARCH_OPEN_COLS * (s->iterations % SEARCH_RING); x.next_orow = s->ostats + NGW_SEARCH_OPEN_COLS * ((s->iterations + 1) % SEARCH_RING);
+        x.buckets = s->buckets; x.K = s->K; x.mode = s->hmode; x.prune = s->prune;
+    }
     return x;
 }
 
-// one iteration: ngw.h's seven steps in their order
+// one iteration: ngw.h's seven steps in their order; an open-list search: its steps 0 to 8
 int iterate(ngw_handle* h, ngw_search* s) {
     const NgwSearch x = search_args(s);
+    if (s->open) {                                    // step 0: the `keep` smallest f of the whole pool are the parents, closed by the take
+        if (int rc = ngw_frontier_select(h, s->f, nullptr, s->pool_cap, 1, 1, nullptr, s->keep, 0, s->cap, s->parents[s->cur], nullptr, s->taken, s->bound, s->count))
+            return rc;
+        HIP_TRY(ngw_search_take_launch(&x, h->stream));
+    }
     if (int rc = ngw_successor_keys(h, s->pool, x.parents, s->cap, NGW_KEY_STATE, s->keys, nullptr, nullptr, reinterpret_cast<uint32_t*>(s->info))) return rc;
     HIP_TRY(ngw_search_offer_launch(&x, h->stream));
     if (int rc = ngw_key_table_insert_min(h, s->table, s->keys, s->values, s->tags, s->n, s->where, s->fresh, s->best)) return rc;
     HIP_TRY(ngw_search_judge_launch(&x, h->stream));
-    if (s->keep < 0) {
+    if (s->keep < 0 || s->open) {                     // (an open-list search chose in step 0: every improved child is kept)
         if (int rc = ngw_frontier_compact(h, s->best, s->n, s->A, nullptr, s->cap, s->first, s->second, s->count)) return rc;
     } else {
         if (int rc = ngw_frontier_select(h, s->values, s->best, s->n, 1, s->A, nullptr, s->keep, 0, s->cap, s->first, s->second, s->taken, s->bound, s->count))
@@ -62,18 +73,21 @@ int iterate(ngw_handle* h, ngw_search* s) {
     if (int rc = ngw_frontier_alloc(h, s->count, s->cursor, (int32_t)s->pool_cap, s->cap, s->slots)) return rc;
     HIP_TRY(ngw_search_settle_launch(&x, h->stream));
     if (int rc = ngw_snapshot_expand(h, s->pool, s->plist, s->second, s->pool, s->slots, s->cap, nullptr, nullptr, nullptr)) return rc;
+    if (s->open) {                                    // step 8: the children join the open list
+        if (s->dist)
+            if (int rc = ngw_snapshot_walk(h, s->pool, x.next, s->cap, nullptr, 0, s->dist, nullptr, nullptr)) return rc;
+        HIP_TRY(ngw_search_open_launch(&x, h->stream));
+    }
     s->cur ^= 1;
     s->iterations++;
     return NGW_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int ngw_search_create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, int64_t capacity, const int32_t* costs_host, int32_t by_action, int32_t keep,
-                      int32_t stop_at_goals, ngw_search_arrays* arrays, ngw_search** out) {
-    if (!h || !pool || !table || !costs_host || !arrays || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
+// ngw_search_create and ngw_search_create_open: the checks, the ONE allocation and its initial contents
+int create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, const ngw_search_options& o, bool open, ngw_search_arrays* arrays, ngw_search_arrays_open* more,
+           ngw_search** out) {
+    const int64_t capacity = o.capacity;
+    const int32_t keep = o.keep;
     *out = nullptr;
     ngw_search probe;
     probe.pool = pool; probe.table = table;
@@ -85,6 +99,21 @@ int ngw_search_create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, i
         return fail(NGW_E_INVALID_ARG, "search capacity %lld: %lld positions in one iteration (at most 2^24)", (long long)capacity, (long long)(capacity * A));
     if (pool->cap > 0x7FFFFFFFll) return fail(NGW_E_INVALID_ARG, "a pool of %lld slots", (long long)pool->cap);
     if ((int64_t)keep > capacity) return fail(NGW_E_INVALID_ARG, "keep: %d entries do not fit the capacity %lld", (int)keep, (long long)capacity);
+    const int32_t K = h->proto.K;
+    if (open) {
+        if (keep < 1) return fail(NGW_E_INVALID_ARG, "keep: an open-list search expands keep >= 1 states per iteration, got %d", (int)keep);
+        if (pool->cap > NGW_SELECT_MAX_VALUES)
+            return fail(NGW_E_INVALID_ARG, "an open-list search chooses among every slot: a pool of %lld slots (at most 2^24)", (long long)pool->cap);
+        if (o.heuristic != NGW_SEARCH_H_NONE && o.heuristic != NGW_SEARCH_H_MIN && o.heuristic != NGW_SEARCH_H_MAX)
+            return fail(NGW_E_INVALID_ARG, "heuristic mode %d (NGW_SEARCH_H_NONE, _MIN or _MAX)", (int)o.heuristic);
+        if (o.heuristic != NGW_SEARCH_H_NONE) {
+            if (!o.weights_host) return fail(NGW_E_INVALID_ARG, "NULL argument");
+            if (o.n_weights != K) return fail(NGW_E_INVALID_ARG, "heuristic weights: %d given, one per item id (%d) expected", (int)o.n_weights, (int)K);
+            for (int32_t k = 0; k < K; k++)
+                if (o.weights_host[k] < 0) return fail(NGW_E_INVALID_ARG, "heuristic weights: weight %d is negative (%d)", (int)k, (int)o.weights_host[k]);
+        }
+    }
+    const bool walk = open && o.heuristic != NGW_SEARCH_H_NONE;
     if (table->buckets * (uint64_t)A > 0x7FFFFFFFull)
         return fail(NGW_E_INVALID_ARG, "search: buckets * n_actions = %llu does not fit a tag (at most 2^31 - 1)", (unsigned long long)(table->buckets * (uint64_t)A));
     const size_t lds = NGW_SUCC_LDS_BYTES(h->proto.MS, h->proto.KP);
@@ -96,13 +125,22 @@ int ngw_search_create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, i
     // 64-bit words: goal, overflowed | keys [n] | the int32 arrays, an even number of them | fresh [n], best [n]
     const size_t head = 4 * SEARCH_RING + 64 + 8;                              // stats, cost table, cursor + count[2] + taken + bound + 3 spare
     size_t words32 = head + 6 * cap + 2 * pc + 4 * n;
+    // an open-list search: the weights and the distances first, from a multiple of 16 bytes (the int32 arrays start 2 + n 64-bit words into the slab)
+    const size_t nb = (size_t)table->buckets, Kp = ((size_t)K + 3) & ~(size_t)3;
+    size_t extra = 0;
+    if (open) {
+        extra = words32 + ((4 - (2 * (2 + n) + words32) % 4) % 4);
+        words32 = extra + (walk ? Kp + cap * (size_t)K : 0);
+        words32 += (size_t)NGW_SEARCH_OPEN_COLS * SEARCH_RING + 2 * pc + nb;
+    }
     words32 += words32 & 1;
     const size_t words64 = 2 + n + words32 / 2 + (2 * n + 7) / 8;
     uint64_t* slab = nullptr;
     if (int rc = dev_alloc(h, &slab, words64)) return rc;                          // (zero-filled on the handle's stream)
     ngw_search* s = new ngw_search;
     s->pool = pool; s->table = table; s->cap = capacity; s->pool_cap = pool->cap; s->n = (int64_t)n;
-    s->A = (int32_t)A; s->by_action = by_action != 0; s->keep = keep < 0 ? -1 : keep; s->stop = stop_at_goals != 0;
+    s->A = (int32_t)A; s->by_action = o.by_action != 0; s->keep = keep < 0 ? -1 : keep; s->stop = o.stop_at_goals != 0;
+    s->open = open; s->prune = o.prune != 0; s->hmode = walk ? o.heuristic : NGW_SEARCH_H_NONE; s->K = K; s->buckets = (int64_t)nb;
     s->slab = slab; s->goal = reinterpret_cast<unsigned long long*>(slab); s->keys = slab + 2;
     int32_t* w = reinterpret_cast<int32_t*>(slab + 2 + n);
     s->stats = reinterpret_cast<uint32_t*>(w); w += 4 * SEARCH_RING;
@@ -112,12 +150,26 @@ int ngw_search_create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, i
     s->g = w; s->bucket = w + pc; w += 2 * pc;
     s->info = w; s->values = w + n; s->tags = w + 2 * n; s->where = w + 3 * n;
     s->fresh = reinterpret_cast<uint8_t*>(slab + 2 + n + words32 / 2); s->best = s->fresh + n;
+    if (open) {
+        w = reinterpret_cast<int32_t*>(s->stats) + extra;
+        if (walk) { s->weights = w; s->dist = w + Kp; w += Kp + cap * (size_t)K; }
+        s->ostats = reinterpret_cast<uint32_t*>(w); w += (size_t)NGW_SEARCH_OPEN_COLS * SEARCH_RING;
+        s->h = w; s->f = w + pc; s->slot_of_bucket = w + 2 * pc;
+    }
     hipError_t e = hipMemsetAsync(s->goal, 0xFF, 8, h->stream);                                                   // no goal yet
-    if (e == hipSuccess) e = hipMemcpyAsync(s->lut, costs_host, 64 * sizeof(int32_t), hipMemcpyDefault, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(s->lut, o.costs_host, 64 * sizeof(int32_t), hipMemcpyDefault, h->stream);
     if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->parents[0]), (int)NGW_IDX_NONE, 2 * cap, h->stream);
     if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->g), NGW_VALUE_NONE, pc, h->stream);
     if (e == hipSuccess) e = hipMemsetAsync(s->bucket, 0xFF, pc * sizeof(int32_t), h->stream);                    // -1: no bucket
-    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);                                                     // (costs_host is the caller's: read by now)
+    int32_t first_row[NGW_SEARCH_OPEN_COLS] = {0};                                                                // no slot chosen yet: the take's min / max words
+    first_row[NGW_SEARCH_FMIN] = NGW_VALUE_NONE; first_row[NGW_SEARCH_FBOUND] = INT32_MIN;
+    if (open) {
+        if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->f), NGW_VALUE_NONE, pc, h->stream);                        // nothing is open
+        if (e == hipSuccess) e = hipMemsetAsync(s->slot_of_bucket, 0xFF, nb * sizeof(int32_t), h->stream);                                         // -1: no slot
+        if (e == hipSuccess) e = hipMemcpyAsync(s->ostats, first_row, sizeof(first_row), hipMemcpyDefault, h->stream);
+        if (e == hipSuccess && walk) e = hipMemcpyAsync(s->weights, o.weights_host, (size_t)K * sizeof(int32_t), hipMemcpyDefault, h->stream);
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);                                                     // (the host arrays are the caller's: read by now)
     if (e != hipSuccess) {
         dev_free(h, slab);
         delete s;
@@ -125,8 +177,27 @@ int ngw_search_create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, i
     }
     h->searches.push_back(s);
     arrays->parents[0] = s->parents[0]; arrays->parents[1] = s->parents[1]; arrays->g = s->g; arrays->bucket = s->bucket; arrays->cursor = s->cursor;
+    if (more) { more->h = s->h; more->f = s->f; }
     *out = s;
     return NGW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ngw_search_create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, int64_t capacity, const int32_t* costs_host, int32_t by_action, int32_t keep,
+                      int32_t stop_at_goals, ngw_search_arrays* arrays, ngw_search** out) {
+    if (!h || !pool || !table || !costs_host || !arrays || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    ngw_search_options o{};
+    o.capacity = capacity; o.costs_host = costs_host; o.by_action = by_action; o.keep = keep; o.stop_at_goals = stop_at_goals;
+    return create(h, pool, table, o, false, arrays, nullptr, out);
+}
+
+int ngw_search_create_open(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, const ngw_search_options* options, ngw_search_arrays_open* arrays,
+                           ngw_search** out) {
+    if (!h || !pool || !table || !options || !options->costs_host || !arrays || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    return create(h, pool, table, *options, true, &arrays->base, arrays, out);
 }
 
 int ngw_search_destroy(ngw_handle* h, ngw_search* s) {
@@ -157,6 +228,11 @@ int ngw_search_start(ngw_handle* h, ngw_search* s, const int32_t* roots_dev, int
     NgwSearchRoots x{};
     x.roots = roots_dev; x.where = s->where; x.value = s->info; x.best = s->best; x.parents = s->parents[s->cur]; x.g = s->g; x.bucket = s->bucket;
     x.count = count; x.capacity = s->cap; x.pool = s->pool_cap;
+    if (s->open) {                                    // the roots are opened, not made parents: the first iteration chooses them
+        if (count && s->dist)
+            if (int rc = ngw_snapshot_walk(h, s->pool, roots_dev, count, nullptr, 0, s->dist, nullptr, nullptr)) return rc;
+        x.f = s->f; x.h = s->h; x.slot_of_bucket = s->slot_of_bucket; x.dist = s->dist; x.weights = s->weights; x.buckets = s->buckets; x.K = s->K; x.mode = s->hmode;
+    }
     HIP_TRY(ngw_search_roots_launch(&x, h->stream));
     if (current) *current = s->cur;
     return NGW_OK;
@@ -197,6 +273,28 @@ int ngw_search_read(ngw_handle* h, ngw_search* s, ngw_search_report* out) {
     out->current = s->cur;
     for (int32_t i = 0; i < out->rows; i++)
         memcpy(out->stats[i], ring[(s->iterations - out->rows + i) % SEARCH_RING], sizeof(ring[0]));
+    return NGW_OK;
+}
+
+int ngw_search_read_open(ngw_handle* h, ngw_search* s, ngw_search_open_report* out) {
+    if (!h || !s || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!owns_search(h, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
+    if (!s->open) return fail(NGW_E_INVALID_ARG, "a search without an open list (ngw_search_create_open makes one with)");
+    if (int rc = enter(h)) return rc;
+    uint32_t ring[SEARCH_RING][NGW_SEARCH_OPEN_COLS];
+    HIP_TRY(hipMemcpyAsync(ring, s->ostats, sizeof(ring), hipMemcpyDefault, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    memset(out, 0, sizeof(*out));
+    out->iterations = s->iterations;
+    out->rows = (int32_t)(s->iterations < NGW_SEARCH_ROWS ? s->iterations : NGW_SEARCH_ROWS);
+    for (int32_t i = 0; i < out->rows; i++) {
+        const uint32_t* r = ring[(s->iterations - out->rows + i) % SEARCH_RING];
+        const bool any = r[NGW_SEARCH_CHOSEN] != 0;
+        out->stats[i][0] = (int32_t)r[NGW_SEARCH_CHOSEN]; out->stats[i][1] = (int32_t)r[NGW_SEARCH_PRUNED]; out->stats[i][2] = (int32_t)r[NGW_SEARCH_SUPERSEDED];
+        out->stats[i][3] = (int32_t)r[NGW_SEARCH_OPEN];
+        out->stats[i][4] = any ? (int32_t)r[NGW_SEARCH_FMIN] : NGW_VALUE_NONE;
+        out->stats[i][5] = any ? (int32_t)r[NGW_SEARCH_FBOUND] : NGW_VALUE_NONE;
+    }
     return NGW_OK;
 }
 

@@ -959,12 +959,52 @@ struct NgwSearch {
     uint32_t* next_row;         /* [4]: the next one's */
     int64_t capacity, pool;
     int32_t A, by_action, stop;
+    /* an open-list search (below); all NULL / 0 in a closed one, whose kernels read none of them */
+    int32_t* f;                 /* [pool]: the priority of every open slot, NGW_VALUE_NONE elsewhere */
+    int32_t* h;                 /* [pool]: the heuristic of the state in every slot */
+    int32_t* slot_of_bucket;    /* [buckets]: the slot that holds the cheapest copy of the bucket's state, -1: none */
+    const int32_t* dist;        /* [capacity][K]: ngw_snapshot_walk of the child list; NULL: no heuristic */
+    const int32_t* weights;     /* [K] */
+    const int32_t* sel_count;   /* ngw_frontier_select's count words of this iteration's choice */
+    uint32_t* orow;             /* [8]: this iteration's row of the open-list stats */
+    uint32_t* next_orow;        /* [8]: the next one's */
+    int64_t buckets;
+    int32_t K, mode, prune;
 };
 #define NGW_SEARCH_BLOCK 256     /* threads per workgroup: four waves, one position per lane */
 #define NGW_SEARCH_OFFERED 0     /* the columns of a stats row */
 #define NGW_SEARCH_IMPROVED 1
 #define NGW_SEARCH_EXPANDED 2
 #define NGW_SEARCH_OVERFLOW 3
+/* Open-list searches (ngw_search_create_open; the contract is include/ngw.h's "an open-list iteration"; search.take_reference, .open_reference and
+ * .best_first_reference state the kernels in numpy).  Two kernels more, and the settle and roots kernels instantiated with the open-list work:
+ *   take    entry k < capacity of the chosen list P = parents (ngw_frontier_select's `first` over f): a slot in [0, pool) is CLOSED - f[slot] =
+ *           NGW_VALUE_NONE -; with prune, an old f >= the goal word's value makes P[k] = NGW_IDX_NONE.  orow: CHOSEN += the slots, PRUNED += the pruned
+ *           ones, FMIN / FBOUND = the smallest / largest old f (signed; one atomicMin / atomicMax per wave that has a slot); thread 0 stores
+ *           orow[OPEN] = sel_count[1].
+ *   settle  as above, and for a live child c with bucket b = where[q] in [0, buckets): an earlier slot named by slot_of_bucket[b] gets f =
+ *           NGW_VALUE_NONE and is counted in orow[SUPERSEDED]; slot_of_bucket[b] = c.  Thread 0 resets next_orow as well.
+ *   open    entry k < capacity of the child list `next`: a slot c in [0, pool) gets h[c] = the walk heuristic of dist[k][0 .. K) (0 without one)
+ *           and f[c] = min(int64(g[c]) + h[c], NGW_VALUE_NONE - 1).
+ *   roots   as below with parents[j] = NGW_IDX_NONE for every j; a root taken (best[j] set) gets slot_of_bucket[where[j]] = r, h[r] from dist[j]
+ *           and f[r] as in open.
+ * The walk heuristic of K distances d under K weights w >= 0: min (mode NGW_SEARCH_H_MIN) or max (NGW_SEARCH_H_MAX) of int64(w[k]) * d[k] over the k
+ * with w[k] > 0 and d[k] >= 0, clamped to NGW_VALUE_NONE - 1; 0 where there is no such k. */
+#define NGW_SEARCH_CHOSEN 0      /* the columns of an open-list stats row (8 words) */
+#define NGW_SEARCH_PRUNED 1
+#define NGW_SEARCH_SUPERSEDED 2
+#define NGW_SEARCH_OPEN 3
+#define NGW_SEARCH_FMIN 4        /* int32; NGW_VALUE_NONE until a slot is chosen */
+#define NGW_SEARCH_FBOUND 5      /* int32; INT32_MIN until a slot is chosen */
+#define NGW_SEARCH_OPEN_COLS 8
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_search_take_launch(const struct NgwSearch* x, hipStream_t stream);
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_search_open_launch(const struct NgwSearch* x, hipStream_t stream);
 #ifdef __cplusplus
 extern "C"
 #endif
@@ -978,7 +1018,7 @@ extern "C"
 #endif
 hipError_t ngw_search_settle_launch(const struct NgwSearch* x, hipStream_t stream);
 /* the roots of a search (ngw_search_start): for j < count, a root slot r = roots[j] in [0, pool) with where[j] >= 0 gets g[r] = value[j] and bucket[r] =
- * where[j]; parents[j] = r where best[j] != 0, NGW_IDX_NONE otherwise and for count <= j < capacity. */
+ * where[j]; parents[j] = r where best[j] != 0, NGW_IDX_NONE otherwise and for count <= j < capacity.  (An open-list search: "roots" above.) */
 struct NgwSearchRoots {
     const int32_t* roots;       /* [count] */
     const int32_t* where;       /* [count] */
@@ -988,6 +1028,14 @@ struct NgwSearchRoots {
     int32_t* g;                 /* [pool] */
     int32_t* bucket;            /* [pool] */
     int64_t count, capacity, pool;
+    /* an open-list search: f != NULL (all NULL / 0 in a closed one) */
+    int32_t* f;                 /* [pool] */
+    int32_t* h;                 /* [pool] */
+    int32_t* slot_of_bucket;    /* [buckets] */
+    const int32_t* dist;        /* [count][K]: ngw_snapshot_walk of the roots; NULL: no heuristic */
+    const int32_t* weights;     /* [K] */
+    int64_t buckets;
+    int32_t K, mode;
 };
 #ifdef __cplusplus
 extern "C"

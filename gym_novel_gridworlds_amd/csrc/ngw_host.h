@@ -82,7 +82,7 @@ struct ngw_key_table {
 
 // A search run (ngw_abi_search.cpp): the pool and the table it works on - looked up by address in the handle's lists before every use, never
 // dereferenced first -, and ONE allocation of its handle that holds every array: the goal word and the overflow count, the keys, the int32 arrays
-// (stats rows, cost table, cursor and counts, the lists, g and bucket, the per-position scratch) and the two flag arrays.
+// (stats rows, cost table, cursor and counts, the lists, g and bucket, the per-position scratch, an open-list search's own) and the two flag arrays.
 struct ngw_search {
     ngw_snapshot* pool = nullptr;
     ngw_key_table* table = nullptr;
@@ -99,6 +99,13 @@ struct ngw_search {
     int32_t *first = nullptr, *second = nullptr, *slots = nullptr, *plist = nullptr, *g = nullptr, *bucket = nullptr;
     int32_t *info = nullptr, *values = nullptr, *tags = nullptr, *where = nullptr;
     uint8_t *fresh = nullptr, *best = nullptr;
+    // an open-list search (ngw_search_create_open), in the same allocation: f, h [pool_cap], slot_of_bucket [buckets], the K weights and the walk's
+    // distances [cap][K] (both start on 16 bytes; a search without a heuristic has neither), and the second stats ring
+    bool open = false;
+    int32_t prune = 0, hmode = 0, K = 0;
+    int64_t buckets = 0;
+    int32_t *f = nullptr, *h = nullptr, *slot_of_bucket = nullptr, *weights = nullptr, *dist = nullptr;
+    uint32_t* ostats = nullptr;           // [NGW_SEARCH_ROWS + 1][NGW_SEARCH_OPEN_COLS], rows as in `stats`
 };
 
 struct ngw_handle {

@@ -81,9 +81,48 @@ __global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_judge_kernel(cons
     }
 }
 
+// The walk heuristic of one row of K distances (ngw_device.h): K consecutive int32 beside the K weights, read as 16-byte, 8-byte or 4-byte words -
+// whichever K lets every row start on (both arrays start on 16 bytes).  Integer arithmetic: the product in 64 bits, clamped.
+__device__ __forceinline__ void search_h_term(int32_t w, int32_t d, int32_t mode, int64_t& acc, bool& any) {
+    if (w > 0 && d >= 0) {
+        const int64_t t = (int64_t)w * (int64_t)d;
+        acc = !any ? t : (mode == NGW_SEARCH_H_MAX ? (t > acc ? t : acc) : (t < acc ? t : acc));
+        any = true;
+    }
+}
+
+__device__ __forceinline__ int32_t search_walk_h(const int32_t* __restrict__ d, const int32_t* __restrict__ w, int32_t K, int32_t mode) {
+    int64_t acc = 0;
+    bool any = false;
+    if ((K & 3) == 0) {
+        for (int32_t k = 0; k < K; k += 4) {
+            const int4 dd = *reinterpret_cast<const int4*>(d + k), ww = *reinterpret_cast<const int4*>(w + k);
+            search_h_term(ww.x, dd.x, mode, acc, any); search_h_term(ww.y, dd.y, mode, acc, any);
+            search_h_term(ww.z, dd.z, mode, acc, any); search_h_term(ww.w, dd.w, mode, acc, any);
+        }
+    } else if ((K & 1) == 0) {
+        for (int32_t k = 0; k < K; k += 2) {
+            const int2 dd = *reinterpret_cast<const int2*>(d + k), ww = *reinterpret_cast<const int2*>(w + k);
+            search_h_term(ww.x, dd.x, mode, acc, any); search_h_term(ww.y, dd.y, mode, acc, any);
+        }
+    } else {
+        for (int32_t k = 0; k < K; k++) search_h_term(w[k], d[k], mode, acc, any);
+    }
+    const int64_t top = (int64_t)NGW_VALUE_NONE - 1;
+    return (int32_t)(acc > top ? top : acc);
+}
+
+// f of a slot reached with g under the heuristic h: the sum in 64 bits, below NGW_VALUE_NONE so that it stays a candidate of the selection
+__device__ __forceinline__ int32_t search_priority(int32_t g, int32_t h) {
+    const int64_t sum = (int64_t)g + (int64_t)h, top = (int64_t)NGW_VALUE_NONE - 1;
+    return (int32_t)(sum > top ? top : sum);
+}
+
+// OPEN: the superseding of step 6 and the reset of the open-list stats row.  The closed instantiation is the kernel as it was.
+template <bool OPEN>
 __global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_settle_kernel(const NgwSearch x) {
     const int64_t k = (int64_t)blockIdx.x * NGW_SEARCH_BLOCK + threadIdx.x;
-    bool live = false;
+    bool live = false, superseded = false;
     if (k < x.capacity) {
         const int32_t j = x.first[k], a = x.second[k], c = x.slots[k];
         const bool entry = j >= 0 && (int64_t)j < x.capacity && a >= 0 && a < x.A;
@@ -93,15 +132,84 @@ __global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_settle_kernel(con
             const int64_t q = (int64_t)j * x.A + a;
             x.g[c] = x.values[q];
             x.bucket[c] = x.where[q];
+            if constexpr (OPEN) {
+                const int32_t b = x.where[q];
+                if (b >= 0 && (int64_t)b < x.buckets) {
+                    // insert_min sets best at most once per key and call, and a bucket holds one key: this lane is the only one of the iteration
+                    // that reads or writes slot_of_bucket[b], and - a slot has one bucket - the only one that closes `old`.  No atomic is needed.
+                    const int32_t old = x.slot_of_bucket[b];
+                    superseded = old >= 0 && (int64_t)old < x.pool && old != c;
+                    if (superseded) x.f[old] = NGW_VALUE_NONE;                     // reached more cheaply: never expanded from the dearer copy
+                    x.slot_of_bucket[b] = c;
+                }
+            }
         }
         x.next[k] = live ? c : NGW_IDX_NONE;
     }
     const uint32_t count = search_wave_count(live);
     if (search_wave_leader() && count) atomicAdd(x.row + NGW_SEARCH_EXPANDED, count);
-    if (k == 0)
+    if constexpr (OPEN) {
+        const uint32_t closed = search_wave_count(superseded);
+        if (search_wave_leader() && closed) atomicAdd(x.orow + NGW_SEARCH_SUPERSEDED, closed);
+    }
+    if (k == 0) {
         for (int i = 0; i < 4; i++) x.next_row[i] = 0;
+        if constexpr (OPEN) {
+            for (int i = 0; i < NGW_SEARCH_OPEN_COLS; i++) x.next_orow[i] = 0;
+            x.next_orow[NGW_SEARCH_FMIN] = (uint32_t)NGW_VALUE_NONE;
+            x.next_orow[NGW_SEARCH_FBOUND] = (uint32_t)INT32_MIN;
+        }
+    }
 }
 
+// TAKE (step 0): the chosen slots are closed; with prune, those that cannot beat the goal are taken off the parent list
+__global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_take_kernel(const NgwSearch x) {
+    const int64_t k = (int64_t)blockIdx.x * NGW_SEARCH_BLOCK + threadIdx.x;
+    bool chosen = false, pruned = false;
+    int32_t lo = NGW_VALUE_NONE, hi = INT32_MIN;
+    if (k < x.capacity) {
+        int32_t* const P = const_cast<int32_t*>(x.parents);
+        const int32_t slot = P[k];
+        chosen = slot >= 0 && (int64_t)slot < x.pool;
+        if (chosen) {
+            const int32_t old = x.f[slot];
+            x.f[slot] = NGW_VALUE_NONE;
+            lo = hi = old;
+            if (x.prune) {
+                const int32_t goal = (int32_t)((uint32_t)(*x.goal >> 32) ^ 0x80000000u);   // (no goal yet: all ones, NGW_VALUE_NONE - above every f)
+                pruned = old >= goal;
+                if (pruned) P[k] = NGW_IDX_NONE;
+            }
+        }
+    }
+#pragma unroll
+    for (int off = 32; off; off >>= 1) {
+        const int32_t a = __shfl_xor(lo, off), b = __shfl_xor(hi, off);
+        lo = a < lo ? a : lo;
+        hi = b > hi ? b : hi;
+    }
+    const uint32_t n_chosen = search_wave_count(chosen), n_pruned = search_wave_count(pruned);
+    if (search_wave_leader() && n_chosen) {
+        atomicAdd(x.orow + NGW_SEARCH_CHOSEN, n_chosen);
+        if (n_pruned) atomicAdd(x.orow + NGW_SEARCH_PRUNED, n_pruned);
+        atomicMin(reinterpret_cast<int32_t*>(x.orow) + NGW_SEARCH_FMIN, lo);
+        atomicMax(reinterpret_cast<int32_t*>(x.orow) + NGW_SEARCH_FBOUND, hi);
+    }
+    if (k == 0) x.orow[NGW_SEARCH_OPEN] = (uint32_t)x.sel_count[1];
+}
+
+// OPEN (step 8): h and f of every child written this iteration
+__global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_open_kernel(const NgwSearch x) {
+    const int64_t k = (int64_t)blockIdx.x * NGW_SEARCH_BLOCK + threadIdx.x;
+    if (k >= x.capacity) return;
+    const int32_t c = x.next[k];
+    if (c < 0 || (int64_t)c >= x.pool) return;
+    const int32_t hv = x.dist ? search_walk_h(x.dist + k * x.K, x.weights, x.K, x.mode) : 0;
+    x.h[c] = hv;
+    x.f[c] = search_priority(x.g[c], hv);
+}
+
+template <bool OPEN>
 __global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_roots_kernel(const NgwSearchRoots x) {
     const int64_t j = (int64_t)blockIdx.x * NGW_SEARCH_BLOCK + threadIdx.x;
     if (j >= x.capacity) return;
@@ -109,9 +217,19 @@ __global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_roots_kernel(cons
     if (j < x.count) {
         const int32_t r = x.roots[j], w = x.where[j];
         if (r >= 0 && (int64_t)r < x.pool && w >= 0) {
-            x.g[r] = x.value[j];
+            const int32_t g = x.value[j];
+            x.g[r] = g;
             x.bucket[r] = w;
-            if (x.best[j]) parent = r;
+            if (x.best[j]) {
+                if constexpr (OPEN) {                                              // opened: the first iteration chooses it from the list
+                    if ((int64_t)w < x.buckets) x.slot_of_bucket[w] = r;           // (best is set once per key: one writer per bucket)
+                    const int32_t hv = x.dist ? search_walk_h(x.dist + j * x.K, x.weights, x.K, x.mode) : 0;
+                    x.h[r] = hv;
+                    x.f[r] = search_priority(g, hv);
+                } else {
+                    parent = r;
+                }
+            }
         }
     }
     x.parents[j] = parent;

@@ -16,6 +16,21 @@ called as that loop calls them - with the torch operations between them as three
 (parent, action)), the JUDGE (the cheapest goal among the improved positions; with stop_at_goals, ended states are not expanded) and the
 SETTLE (the expand lists, g and bucket of the children, the next parents).  relax_reference() states the three in numpy.
 
+That is a LAYERED search (keep=None: every improved child is a parent of the next iteration) or a BEAM (keep=k: the k cheapest children of
+this iteration go on, the rest is dropped for good).  open_list=True is the third discipline, a BEST-FIRST search over an open list: a state
+that was reached but not yet expanded stays a candidate of every later iteration, ordered by f = g + h - uniform-cost search with h = 0,
+A* with a WalkHeuristic over walk_distances, Go-Explore's "the most promising cell of the whole archive" with an f of the caller's own:
+
+    s = pool.search(table, cap, keep=k, open_list=True, heuristic=WalkHeuristic(w, 'min'), prune=True)
+    s.reset_cursor(n); s.start(roots)
+    while not s.proven(): s.run(8)
+    plan = s.goal_plan(64)
+
+An open-list iteration puts a SELECT over s.f (Frontier.select over the whole pool, the `keep` smallest) and a TAKE (the chosen slots are
+closed; with prune, those that cannot beat the goal are dropped) in front of the loop above, always compacts, lets the settle SUPERSEDE the
+dearer copy of a state reached again, and OPENs the children behind the expand (h from a walk, f = g + h).  take_reference(),
+supersede_reference(), open_reference() and best_first_reference() state it in numpy; include/ngw.h is the contract.
+
 A search is rank-local, as a frontier is: under ShardedVecNovelGridworld it belongs to the local env's pool and table."""
 import collections
 import ctypes as C
@@ -33,6 +48,8 @@ STATS_ROWS = _cabi.SEARCH_ROWS    # include/ngw.h NGW_SEARCH_ROWS: the iteration
 
 SearchGoal = collections.namedtuple('SearchGoal', 'value bucket')
 SearchStats = collections.namedtuple('SearchStats', 'iterations offered improved expanded overflow overflowed cursor flags')
+OpenStats = collections.namedtuple('OpenStats', 'iterations chosen pruned superseded open f_min f_bound')
+BestFirst = collections.namedtuple('BestFirst', 'chosen parents pruned open f_min f_bound superseded relaxed')
 Relaxed = collections.namedtuple('Relaxed', 'values tags best goal parents actions children next_parents cursor offered improved expanded overflow full')
 
 
@@ -138,6 +155,121 @@ def relax_reference(parents, g, bucket, info, keys, where, held, cursor, n_actio
                    int(overflow.sum()), bool(full or short))
 
 
+class WalkHeuristic(collections.namedtuple('WalkHeuristic', 'weights mode')):
+    """The heuristic of an open-list search from walk_distances(): `weights` one int32 >= 0 per item id ([K], K as walk_distances returns),
+    `mode` 'min' or 'max'.  With d = walk_distances(slot), h(slot) is the minimum ('min': "walk to the nearest of these") or the maximum
+    ('max': "I need all of these") of weights[k] * d[k] over the k with weights[k] > 0 and d[k] >= 0, 0 where there is none; the product is
+    taken in 64 bits and clamped to VALUE_NONE - 1 (walk_heuristic_reference).  Whether h is admissible - never above the true cost to a
+    goal - is the caller's business.  Rule of thumb: a walk of d moves costs at least d times the cheapest of the spec's three movement costs
+    (Forward, Left, Right) under the search's `scale`, so that cost is the weight of an item the goal cannot be reached without facing."""
+    __slots__ = ()
+
+
+H_MODES = {'min': _cabi.SEARCH_H_MIN, 'max': _cabi.SEARCH_H_MAX}
+
+
+def check_heuristic(heuristic, n_items):
+    """-> (mode code, weights int32 [K] or None); ValueError for a bad mode, a wrong shape or dtype, a negative weight."""
+    if heuristic is None:
+        return _cabi.SEARCH_H_NONE, None
+    if not isinstance(heuristic, tuple) or len(heuristic) != 2:
+        raise ValueError("heuristic: None or a WalkHeuristic(weights, mode) expected, got %r" % (heuristic,))
+    weights, mode = heuristic
+    if mode not in H_MODES:
+        raise ValueError("heuristic mode: 'min' or 'max' expected, got %r" % (mode,))
+    if hasattr(weights, 'data_ptr'):
+        weights = weights.cpu().numpy()
+    w = np.asarray(weights)
+    if w.dtype.kind not in 'iu' or w.shape != (n_items,):
+        raise ValueError("heuristic weights: one integer per item id expected, shape [%d], got dtype %s, shape %s" % (n_items, w.dtype, list(w.shape)))
+    if w.size and (int(w.min()) < 0 or int(w.max()) > VALUE_NONE):
+        raise ValueError("heuristic weights: an entry outside [0, 2^31 - 1]")
+    return H_MODES[mode], np.ascontiguousarray(w, np.int32)
+
+
+def walk_heuristic_reference(dist, weights, mode):
+    """h of every row of `dist` (int32 [n, K] or [K], walk_distances' layout) -> int32 [n] (or a scalar array): the minimum ('min') or
+    maximum ('max') of int64(weights[k]) * dist[.., k] over the k with weights[k] > 0 and dist[.., k] >= 0, clamped to VALUE_NONE - 1; 0
+    where no such k exists."""
+    if mode not in H_MODES:
+        raise ValueError("heuristic mode: 'min' or 'max' expected, got %r" % (mode,))
+    d, w = np.asarray(dist, np.int64), np.asarray(weights, np.int64)
+    live = (w > 0) & (d >= 0)
+    prod = w * d
+    if mode == 'min':
+        out = np.where(live, prod, np.iinfo(np.int64).max).min(axis=-1, initial=np.iinfo(np.int64).max)
+    else:
+        out = np.where(live, prod, -1).max(axis=-1, initial=-1)
+    out = np.where(live.any(axis=-1), out, 0)
+    return np.minimum(out, VALUE_NONE - 1).astype(np.int32)
+
+
+def priority_reference(g, h):
+    """f = min(int64(g) + h, VALUE_NONE - 1)."""
+    return np.minimum(np.asarray(g, np.int64) + np.asarray(h, np.int64), VALUE_NONE - 1).astype(np.int32)
+
+
+def take_reference(f, keep, capacity, goal_value=VALUE_NONE, prune=False):
+    """Step 0 in numpy -> (chosen, parents, pruned, open, f_min, f_bound).  f int32 [pool], updated in place.  The candidates are the slots
+    with f != VALUE_NONE (`open`: how many); the `keep` smallest (f, slot) of them are `chosen` (int32 [capacity], ascending slot order,
+    IDX_NONE-padded) and closed: f = VALUE_NONE.  `parents` is `chosen` with IDX_NONE where prune is set and the old f is >= goal_value
+    (`pruned`: how many); f_min / f_bound: the smallest / largest old f chosen, VALUE_NONE for an empty choice."""
+    first, _, taken, _, count = select_reference(f, int(keep), 1, None, None, 1, False, capacity)
+    chosen = np.asarray(first, np.int32).copy()
+    parents = chosen.copy()
+    live = chosen[:int(taken[0])]
+    old = np.asarray(f)[live].astype(np.int64)
+    f[live] = VALUE_NONE
+    cut = old >= int(goal_value) if prune else np.zeros(len(old), bool)
+    parents[:len(live)][cut] = IDX_NONE
+    return chosen, parents, int(cut.sum()), int(count[1]), int(old.min()) if len(old) else VALUE_NONE, int(old.max()) if len(old) else VALUE_NONE
+
+
+def supersede_reference(children, bucket, slot_of_bucket, f):
+    """The superseding of step 6 in numpy -> how many slots were superseded.  For every child c of `children` (IDX_NONE skipped) with bucket b
+    = bucket[c] >= 0: an earlier slot named by slot_of_bucket[b] gets f = VALUE_NONE and is counted; then slot_of_bucket[b] = c.  f and
+    slot_of_bucket are updated in place.  (A bucket has at most one child per iteration, so the order of the loop does not matter.)"""
+    count = 0
+    for c in np.asarray(children).tolist():
+        if c == IDX_NONE:
+            continue
+        b = int(bucket[c])
+        if not 0 <= b < len(slot_of_bucket):
+            continue
+        old = int(slot_of_bucket[b])
+        if old >= 0 and old != c:
+            f[old] = VALUE_NONE
+            count += 1
+        slot_of_bucket[b] = c
+    return count
+
+
+def open_reference(children, g, f, h, dist=None, heuristic=None):
+    """Step 8 in numpy: for every child c of `children` (IDX_NONE skipped; entry k) h[c] = walk_heuristic_reference(dist[k], ...) - 0 without a
+    heuristic - and f[c] = min(int64(g[c]) + h[c], VALUE_NONE - 1); f and h are updated in place.  dist int32 [len(children), K]: the walk
+    distances of the children (a padded entry's row is not read)."""
+    children = np.asarray(children, np.int64)
+    at = np.flatnonzero(children != IDX_NONE)
+    c = children[at]
+    h[c] = 0 if heuristic is None else walk_heuristic_reference(np.asarray(dist)[at], heuristic[0], heuristic[1])
+    f[c] = priority_reference(np.asarray(g)[c], np.asarray(h)[c])
+
+
+def best_first_reference(f, h, g, bucket, slot_of_bucket, successors, held, cursor, n_actions, lut, by_action, keep, capacity, stop_at_goals=False,
+                         goal=SearchGoal(VALUE_NONE, -1), prune=False, heuristic=None, distances=None, limit=None):
+    """One OPEN-LIST iteration of Search.run in numpy: steps 0 to 8 of include/ngw.h's "an open-list iteration" -> BestFirst(chosen, parents,
+    pruned, open, f_min, f_bound, superseded, relaxed: the Relaxed of steps 2 to 6).  f, h, g, bucket int32 [pool] and slot_of_bucket int32
+    [buckets] are updated in place, `held` as in relax_reference.  successors(parents) -> (info, keys, where): what successor_keys reports for
+    the parent list and the bucket the table gives each key; distances(children) -> walk_distances of the child list, int32 [capacity, K]
+    (only called with a heuristic).  Step 5 always compacts: the choice was made in step 0."""
+    chosen, parents, pruned, n_open, f_min, f_bound = take_reference(f, keep, capacity, goal[0], prune)
+    info, keys, where = successors(parents)
+    r = relax_reference(parents, g, bucket, info, keys, where, held, cursor, n_actions, lut, by_action, None, stop_at_goals, goal, limit)
+    superseded = supersede_reference(r.next_parents, bucket, slot_of_bucket, f)
+    open_reference(r.next_parents, g, f, h, None if heuristic is None else distances(r.next_parents), heuristic)
+    return BestFirst(chosen, parents, pruned, n_open, f_min, f_bound, superseded, r)
+
+
 def check_roots(roots, limit, capacity, device_len=None):
     """The host-side check of start()'s roots: a list / numpy array of one dimension and integer dtype whose entries are slots in [0, limit) or
     IDX_NONE -> a contiguous int32 array; device_len(x): the length of x when it is a device tensor to be used in place (its values are then
@@ -174,9 +306,22 @@ class Search:
     (Frontier.select, one group, by g alone; ties: the smaller position).  stop_at_goals: a state whose step reported done - goal or
     FireWall death - is stored and valued but never expanded.
     An offer never wraps: where g + cost would reach VALUE_NONE no offer is made, and stats() counts it (step_cost_values on the host wraps
-    silently, as it says).  F_FRONTIER_FULL, F_TABLE_FULL and F_BAD_INDEX are raised where the hand-written loop raises them."""
+    silently, as it says).  F_FRONTIER_FULL, F_TABLE_FULL and F_BAD_INDEX are raised where the hand-written loop raises them.
+    open_list=True (requires 1 <= keep <= capacity): a best-first search over an OPEN LIST.  `keep` is then how many open states an iteration
+    expands, chosen from the WHOLE open list by the smallest f (ties: the smaller slot); `capacity` stays the width of the lists, so it bounds
+    the children written per iteration - keep * A <= capacity guarantees that no improved child is dropped by the compaction (it is not
+    enforced: F_FRONTIER_FULL reports a drop).  Two more tensors, views as g and bucket are: `h` (int32 [pool.capacity]: the heuristic of the
+    state in each slot, 0 until written) and `f` (int32 [pool.capacity]: the priority of each OPEN slot; VALUE_NONE for a slot that is
+    unreached, closed - expanded, pruned or superseded - or never opened).  The library reads f only in the selection and writes it only
+    where an iteration says (closing the chosen and the superseded, opening the children and the roots): a caller who runs run(1) and
+    rewrites f of the open slots with a torch expression of their own - a learned value, say - gets that order.  A slot written by anything
+    but the search keeps f = VALUE_NONE and is never chosen.  After start() `parents` is empty - the first iteration chooses the roots from
+    the list -; after run() it holds the children the last iteration wrote and `chosen` the slots it expanded.
+    heuristic: None (h = 0: uniform-cost search) or a WalkHeuristic.  prune=True: a chosen slot whose f is >= the goal's value is closed
+    without being expanded - valid for an admissible h and non-negative costs -, so once a goal is known iterations stop expanding what
+    cannot beat it, and when nothing can they expand nothing (the launches leave early on empty lists): the early stop on the device."""
 
-    def __init__(self, snap, table, capacity, costs=None, scale=1, keep=None, stop_at_goals=False):
+    def __init__(self, snap, table, capacity, costs=None, scale=1, keep=None, stop_at_goals=False, open_list=False, heuristic=None, prune=False):
         import torch
         from .snapshot import MapsTooLarge
         from .vec_env import _DevArray
@@ -198,12 +343,27 @@ class Search:
             if keep > self.capacity:
                 raise ValueError("keep: %d entries do not fit the capacity %d" % (keep, self.capacity))
         self.keep, self.stop_at_goals = (None if keep is None else int(keep)), bool(stop_at_goals)
+        self.open_list, self.prune, self.heuristic = bool(open_list), bool(prune), heuristic
+        if not self.open_list and (heuristic is not None or prune):
+            raise ValueError("heuristic / prune: only an open-list search has them (open_list=True)")
+        if self.open_list:
+            if self.keep is None or self.keep < 1:
+                raise ValueError("keep: an open-list search expands 1 <= keep <= capacity states per iteration, got %r" % (keep,))
+            if snap.capacity > MAX_FLAGS:
+                raise ValueError("open_list: the selection runs over every slot of the pool, at most 2^24 (this pool has %d)" % snap.capacity)
+        mode, weights = check_heuristic(heuristic, self.env.n_items)
         self.costs, self.by_action = cost_table(costs, scale, A)
         self._s, self._keep, self._cur = C.c_void_p(), None, 0
-        arrays = _cabi.SearchArrays()
+        more = _cabi.SearchArraysOpen()
+        arrays = more.base
         try:
-            _cabi.check(_cabi.lib().ngw_search_create(self.env._h, snap._s, table._t, self.capacity, _cabi._ptr(self.costs, np.int32), int(self.by_action),
-                                                      -1 if self.keep is None else self.keep, int(self.stop_at_goals), C.byref(arrays), C.byref(self._s)))
+            if self.open_list:
+                opt = _cabi.SearchOptions(self.capacity, _cabi._ptr(self.costs, np.int32), int(self.by_action), self.keep, int(self.stop_at_goals), int(self.prune),
+                                          mode, 0 if weights is None else len(weights), _cabi._ptr(weights, np.int32))
+                _cabi.check(_cabi.lib().ngw_search_create_open(self.env._h, snap._s, table._t, C.byref(opt), C.byref(more), C.byref(self._s)))
+            else:
+                _cabi.check(_cabi.lib().ngw_search_create(self.env._h, snap._s, table._t, self.capacity, _cabi._ptr(self.costs, np.int32), int(self.by_action),
+                                                          -1 if self.keep is None else self.keep, int(self.stop_at_goals), C.byref(arrays), C.byref(self._s)))
         except ValueError as e:
             if str(e).startswith('map_size'):
                 raise MapsTooLarge(str(e)) from None
@@ -212,6 +372,7 @@ class Search:
         view = lambda ptr, n: torch.as_tensor(_DevArray(ptr, (n,), '<i4'), device=dev)   # noqa: E731
         self._lists = [view(arrays.parents[0], self.capacity), view(arrays.parents[1], self.capacity)]
         self.g, self.bucket, self.cursor = view(arrays.g, snap.capacity), view(arrays.bucket, snap.capacity), view(arrays.cursor, 1)
+        self.h, self.f = (view(more.h, snap.capacity), view(more.f, snap.capacity)) if self.open_list else (None, None)
         self._dev = torch.device(dev)
 
     def _open(self):
@@ -226,6 +387,15 @@ class Search:
         """The current frontier: int32 [capacity], IDX_NONE-padded (the list the next iteration expands)."""
         self._open()
         return self._lists[self._cur]
+
+    @property
+    def chosen(self):
+        """An open-list search: the slots the last iteration expanded - int32 [capacity], ascending, IDX_NONE where pruned and behind them
+        (the other of the two parent lists: step 0's choice after the take; all IDX_NONE before the first iteration)."""
+        self._open()
+        if not self.open_list:
+            raise ValueError("chosen: only an open-list search has it (open_list=True)")
+        return self._lists[self._cur ^ 1]
 
     def _enqueue(self, call, uploaded=()):
         from .snapshot import enqueue_ordered
@@ -250,8 +420,10 @@ class Search:
         """The roots of the search - slots of the pool: a list / numpy array (checked; IDX_NONE is allowed and skipped) or a contiguous torch
         int32 tensor on the env's device, used in place; at most `capacity`.  Their keys are offered to the table with value 0 and tag
         TAG_ROOT (insert_keys_min); g[root] = the value the table then holds, bucket[root] = its bucket, and `parents` becomes the roots -
-        IDX_NONE where a root's state was already held at a value of 0 or below, as the second position of a repeated state is.  Enqueued;
-        no host wait."""
+        IDX_NONE where a root's state was already held at a value of 0 or below, as the second position of a repeated state is.  An
+        open-list search opens those roots instead - h[root], f[root] = min(g + h, VALUE_NONE - 1) - and leaves `parents` empty; a second
+        start() adds its roots to the open list that is there (f, h and the superseding's slots stay), so after table.clear() make a new
+        search instead of restarting this one.  Enqueued; no host wait."""
         from .snapshot import tensor_len, upload
         s = self._open()
         r, count = check_roots(roots, self.snap.capacity, self.capacity, lambda x: tensor_len(self._dev, 'roots', x))
@@ -293,6 +465,30 @@ class Search:
         rows = np.ctypeslib.as_array(rep.stats).reshape(STATS_ROWS, 4)[:rep.rows].copy()
         return SearchStats(int(rep.iterations), rows[:, 0], rows[:, 1], rows[:, 2], rows[:, 3], int(rep.overflowed), int(rep.cursor), int(rep.flags))
 
+    def open_stats(self):
+        """An open-list search: OpenStats - iterations run; chosen / pruned / superseded / open / f_min / f_bound, int32 arrays with one entry
+        per iteration of the last 64, oldest first: the slots the selection took, those of them pruned, the earlier copies superseded, the
+        candidates in the list before the choice, and the smallest and largest f chosen (VALUE_NONE for an empty choice).  sum(chosen -
+        pruned) is the number of states expanded.  Waits for the env's stream, as stats() does."""
+        s = self._open()
+        if not self.open_list:
+            raise ValueError("open_stats: only an open-list search has them (open_list=True)")
+        rep = _cabi.SearchOpenReport()
+        _cabi.check(_cabi.lib().ngw_search_read_open(self.env._h, s, C.byref(rep)))
+        rows = np.ctypeslib.as_array(rep.stats).reshape(STATS_ROWS, 6)[:rep.rows].copy()
+        return OpenStats(int(rep.iterations), *(rows[:, i] for i in range(6)))
+
+    def proven(self):
+        """An open-list search: True when a goal is known and the last iteration run reported open == 0 or f_min >= goal().value.  For an
+        admissible h that proves the goal cheapest: f_min is the minimum of the whole open list at the start of that iteration, every
+        cheapest path has a state on the list whose f is at most the cheapest cost C*, so C* >= f_min >= goal.value >= C* - provided no
+        state was lost, which means no F_FRONTIER_FULL and no F_TABLE_FULL (stats().flags).  Waits, as goal() does."""
+        st = self.open_stats()
+        goal = self.goal()
+        if goal.value == VALUE_NONE or not len(st.open):
+            return False
+        return bool(st.open[-1] == 0 or st.f_min[-1] >= goal.value)
+
     @property
     def closed(self):
         return not self._s
@@ -308,5 +504,5 @@ class Search:
     def _invalidate(self):
         """The handle is gone (or going), and the arrays with it."""
         self._s = C.c_void_p()
-        self._lists = self.g = self.bucket = self.cursor = None
+        self._lists = self.g = self.bucket = self.cursor = self.h = self.f = None
         self._keep = None

@@ -1044,16 +1044,19 @@ class Snapshot:
         return Frontier(self, capacity)
 
     # ------------------------------------------------------------------ device-side search runs (include/ngw.h ngw_search_*; search.py)
-    def search(self, table, capacity, costs=None, scale=1, keep=None, stop_at_goals=False):
+    def search(self, table, capacity, costs=None, scale=1, keep=None, stop_at_goals=False, open_list=False, heuristic=None, prune=False):
         """A Search over this snapshot - the node pool - and `table` (a KeyTable of the same env made with values=True): whole iterations of
         the label-correcting loop of key_table.py's docstring, `capacity` parents each, enqueued from one call with no host wait in between;
         it keeps the cost and the bucket every slot was reached with and the cheapest goal reached (search.py says what an iteration is).
         costs: None - the step costs times `scale`, rounded - or one int32 per action; keep: None or the k cheapest improved states that go
         on; stop_at_goals: ended states are not expanded.  ValueError for a table without values and for keep > capacity; maps beyond
-        successor_keys' 34 x 34 raise what successor_keys raises.  Closed by its close() and with this snapshot."""
+        successor_keys' 34 x 34 raise what successor_keys raises.  open_list=True (with keep=k): a best-first search over an open list - the k
+        open states of the smallest f = g + h of the WHOLE list are expanded per iteration -, heuristic: None or a search.WalkHeuristic,
+        prune: states that cannot beat the goal are closed unexpanded (search.Search says what each does).  Closed by its close() and with
+        this snapshot."""
         from .search import Search
         self._open()
-        s = Search(self, table, capacity, costs, scale, keep, stop_at_goals)
+        s = Search(self, table, capacity, costs, scale, keep, stop_at_goals, open_list, heuristic, prune)
         self.__dict__.setdefault('_searches', []).append(s)
         return s
 

@@ -1138,6 +1138,80 @@ int ngw_search_start(ngw_handle* h, ngw_search* s, const int32_t* roots_dev, int
 int ngw_search_run(ngw_handle* h, ngw_search* s, int32_t iterations, int32_t* current);
 int ngw_search_read(ngw_handle* h, ngw_search* s, ngw_search_report* out);
 
+/* Open-list searches: the third discipline beside the layered (keep < 0) and the beam form (keep >= 0) of ngw_search_create.  A state that was reached
+ * but not yet expanded stays a candidate of every later iteration, ordered by f = g + h: uniform-cost search (h = 0), A* (h from ngw_snapshot_walk),
+ * "the most promising cell of the whole archive".  ngw_search_create_open makes the same ngw_search object - ngw_search_start / _run / _read / _destroy
+ * serve it - which owns, beside the arrays above and in the same ONE allocation (ngw_search_arrays_open):
+ *     h  int32 [pool's capacity]   the heuristic of the state in each slot; 0 until written
+ *     f  int32 [pool's capacity]   the priority of each OPEN slot; NGW_VALUE_NONE for a slot that is unreached, closed (expanded, pruned or superseded)
+ *                                  or never opened.  The library reads f only in the selection of step 0 and writes it only where stated below: a
+ *                                  caller who runs one iteration at a time and rewrites f of the open slots (a learned value, say) gets that order.
+ *     slot_of_bucket int32 [table's buckets], -1 at creation: the slot that holds the cheapest copy of the bucket's state
+ * and the walk's distances [capacity][K], the selection's words and a second stats ring.  ngw_search_run allocates nothing in that allocation; the
+ * selection of step 0 uses the handle's scratch as every ngw_frontier_select does, which grows - once, with a wait - at the first call over more
+ * values than any selection on the handle before.  `keep` (1 <= keep <= capacity) is how many open states an
+ * iteration expands, chosen from the WHOLE open list; `capacity` stays the width of the lists, so it bounds the children written per iteration: with
+ * keep * A <= capacity no improved child is dropped by the compaction (beyond that NGW_F_FRONTIER_FULL reports the drop, as above).
+ * The walk heuristic (heuristic = NGW_SEARCH_H_MIN or _MAX, weights_host: K = n_items int32 >= 0): with d = the K distances ngw_snapshot_walk gives a
+ * slot, h(slot) = the minimum (_MIN: "walk to the nearest of these") or the maximum (_MAX: "all of these are needed") of int64(weights[k]) * d[k] over
+ * the k with weights[k] > 0 and d[k] >= 0, clamped to NGW_VALUE_NONE - 1; 0 where there is no such k, and everywhere under NGW_SEARCH_H_NONE.
+ * Whether h is admissible is the caller's business (rule of thumb: the weight is the cheapest of the three movement costs in the search's cost table).
+ *   start    as above, and for each root taken (best[j] set): slot_of_bucket[its bucket] = the root, h[root] by the rule above, f[root] =
+ *            min(int64(g[root]) + h[root], NGW_VALUE_NONE - 1).  The current parent list is then EMPTY (all NGW_IDX_NONE): the first iteration
+ *            chooses the roots from the open list like any other state.  A second start adds its roots to what is there: the open list, h and
+ *            slot_of_bucket stay as the iterations before left them, so a search is not restarted by clearing its table - destroy it and create
+ *            another.
+ *   run      an iteration, with P the current parent list and N the other one:
+ *            0. SELECT: ngw_frontier_select(values = f, flags = NULL, n = the pool's capacity, one group, div = 1, no map, keep, smallest first,
+ *               capacity): P = its `first` list, the chosen slots in ascending slot order, NGW_IDX_NONE behind them; ties in f go to the smaller
+ *               slot.  TAKE, per entry: f[slot] = NGW_VALUE_NONE (closed); with prune, an old f >= the goal's value (none yet: NGW_VALUE_NONE)
+ *               makes P[k] = NGW_IDX_NONE - valid for an admissible h and non-negative costs: such a state cannot lead to a cheaper goal.  Once
+ *               a goal is known, iterations stop expanding what cannot beat it, and when nothing can they expand nothing (the launches leave
+ *               early on empty lists): the early stop on the device.
+ *            1. - 4. as above.
+ *            5. ngw_frontier_compact(best, div = A) ALWAYS - the choice was made in step 0, every improved child is kept -, then ngw_frontier_alloc.
+ *            6. settle as above, and SUPERSEDING: for a child written to slot c with bucket b, an earlier slot named by slot_of_bucket[b] gets f =
+ *               NGW_VALUE_NONE - its state has been reached more cheaply, it is never expanded from the dearer copy - and is counted (whether it
+ *               was still open or not); then slot_of_bucket[b] = c.  (best is set at most once per key and call: one writer per bucket.)
+ *            7. ngw_snapshot_expand as above.  N becomes the current list: the children written by this iteration.  P - the slots this iteration
+ *               expanded, NGW_IDX_NONE where pruned - stays in the other list (ngw_search_arrays.parents[1 - current]) until the next iteration
+ *               makes it its N.
+ *            8. OPEN: with a heuristic, ngw_snapshot_walk(pool, N, count = capacity, items = NULL, the distances) - a padded entry gives a row of -1
+ *               and no flag -; then for every child c of N: h[c] by the rule above (0 without a heuristic), f[c] = min(int64(g[c]) + h[c],
+ *               NGW_VALUE_NONE - 1).  A child that stop_at_goals barred never reached the list and is never opened.
+ *            A slot written by anything but the search keeps f = NGW_VALUE_NONE and is never chosen.
+ *   read_open  waits for the stream: for the last `rows` = min(iterations, 64) iterations, oldest first: chosen (slots the selection took), pruned,
+ *            superseded, open (the candidates in the list before the choice: the selection's count[1]), f_min and f_bound (the smallest and the
+ *            largest f chosen, pruned ones included; NGW_VALUE_NONE for an empty choice).  f_min is the minimum of the whole open list at the
+ *            start of that iteration, so with an admissible h, a goal of value v and f_min >= v (or open == 0): C* >= f_min >= v >= C* - the goal
+ *            is proven cheapest, provided no state was lost (no NGW_F_FRONTIER_FULL, no NGW_F_TABLE_FULL).
+ * NGW_E_INVALID_ARG: what ngw_search_create refuses; keep < 1; a pool beyond 2^24 slots (the selection's limit); a heuristic mode other than the three;
+ * n_weights != n_items, a NULL or a negative weight under a heuristic; ngw_search_read_open on a search made by ngw_search_create. */
+#define NGW_SEARCH_H_NONE 0
+#define NGW_SEARCH_H_MIN 1
+#define NGW_SEARCH_H_MAX 2
+typedef struct ngw_search_options {
+    int64_t capacity;
+    const int32_t* costs_host;      /* [64] */
+    int32_t by_action, keep, stop_at_goals, prune;
+    int32_t heuristic;              /* NGW_SEARCH_H_* */
+    int32_t n_weights;              /* n_items under a heuristic */
+    const int32_t* weights_host;    /* [n_weights]; not read under NGW_SEARCH_H_NONE */
+} ngw_search_options;
+typedef struct ngw_search_arrays_open {
+    ngw_search_arrays base;
+    void* h;
+    void* f;
+} ngw_search_arrays_open;
+typedef struct ngw_search_open_report {
+    int64_t iterations;
+    int32_t rows, reserved;
+    int32_t stats[NGW_SEARCH_ROWS][6];   /* chosen, pruned, superseded, open, f_min, f_bound */
+} ngw_search_open_report;
+int ngw_search_create_open(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, const ngw_search_options* options, ngw_search_arrays_open* arrays,
+                           ngw_search** out);
+int ngw_search_read_open(ngw_handle* h, ngw_search* s, ngw_search_open_report* out);
+
 /* Guided playouts: ngw_snapshot_playout_traj_views whose weights depend on the STATE - at every step the pair's current state is looked up in a key
  * table, and where the table holds it the choice is made under that bucket's row of the caller's weights.  The selection phase of MCTS (descend by
  * the tree's statistics while the node is in the tree), tabular Q / softmax policies, Go-Explore's "return, then explore" and playouts whose bias is
