@@ -34,6 +34,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_key_table_create', 'ngw_key_table_destroy', 'ngw_key_table_clear', 'ngw_key_table_insert', 'ngw_key_table_lookup', 'ngw_key_table_count',
            'ngw_key_table_create_valued', 'ngw_key_table_insert_min', 'ngw_key_table_read', 'ngw_key_table_trace',
            'ngw_search_create', 'ngw_search_destroy', 'ngw_search_start', 'ngw_search_run', 'ngw_search_read', 'ngw_search_create_open', 'ngw_search_read_open',
+           'ngw_snapshot_recipe_costs', 'ngw_search_set_recipe',
            'ngw_snapshot_walk', 'ngw_frontier_compact', 'ngw_frontier_alloc', 'ngw_frontier_select', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
@@ -77,6 +78,20 @@ class SearchArraysOpen(C.Structure):
 class SearchOpenReport(C.Structure):
     """include/ngw.h ngw_search_open_report."""
     _fields_ = [('iterations', C.c_int64), ('rows', C.c_int32), ('reserved', C.c_int32), ('stats', (C.c_int32 * 6) * SEARCH_ROWS)]
+
+
+RECIPE_MAX_RULES, RECIPE_MAX_INPUTS, RECIPE_MAX_MAP_ITEMS = 16, 4, 4      # include/ngw.h NGW_RECIPE_MAX_*
+
+
+class RecipeRule(C.Structure):
+    """include/ngw.h ngw_recipe_rule."""
+    _fields_ = [('out_item', C.c_int32), ('out_qty', C.c_int32), ('cost', C.c_int32), ('n_in', C.c_int32), ('in_item', C.c_int32 * RECIPE_MAX_INPUTS),
+                ('in_qty', C.c_int32 * RECIPE_MAX_INPUTS), ('tool_item', C.c_int32)]
+
+
+class RecipeProgram(C.Structure):
+    """include/ngw.h ngw_recipe_program."""
+    _fields_ = [('goal_item', C.c_int32), ('n_rules', C.c_int32), ('map_items', C.c_uint32), ('reserved', C.c_int32), ('rules', RecipeRule * RECIPE_MAX_RULES)]
 
 
 class NgwError(RuntimeError):
@@ -255,6 +270,9 @@ def lib():
     if hasattr(L, 'ngw_search_create_open'):
         L.ngw_search_create_open.argtypes = [vp, vp, vp, C.POINTER(SearchOptions), C.POINTER(SearchArraysOpen), C.POINTER(vp)]
         L.ngw_search_read_open.argtypes = [vp, vp, C.POINTER(SearchOpenReport)]
+    if hasattr(L, 'ngw_snapshot_recipe_costs'):
+        L.ngw_snapshot_recipe_costs.argtypes = [vp, vp, vp, i64, C.POINTER(RecipeProgram), vp]
+        L.ngw_search_set_recipe.argtypes = [vp, vp, C.POINTER(RecipeProgram)]
     if hasattr(L, 'ngw_snapshot_copy'):
         L.ngw_snapshot_copy.argtypes = [vp, vp, vp, vp, vp, i64]
     if hasattr(L, 'ngw_key_table_create'):

@@ -3,7 +3,9 @@
 // entry points (ngw_abi_snapshot.cpp, ngw_abi_table.cpp, ngw_abi_frontier.cpp), called as any caller calls them, with the three kernels of
 // ngw_search.inc between them.  The calls write no env state: they neither call state_written() nor touch anything the handle derives from its
 // state.  All run on the handle's stream, behind enter(); only ngw_search_read / _read_open wait.  An open-list search (ngw_search_create_open) adds
-// the selection over f in front, the walk of the children behind, and the take and open kernels; the same driver serves it.
+// the selection over f in front, the walk of the children behind, and the take and open kernels; the same driver serves it.  The recipe term
+// (ngw_search_set_recipe) is one launch more in front of the open and the roots kernel, made by ngw_host_recipe.cpp through the pointer the search
+// keeps: this unit names no launcher of it, and a search without the term enqueues exactly what it always did.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -48,6 +50,7 @@ NgwSearch search_args(const ngw_search* s) {
         x.f = s->f; x.h = s->h; x.slot_of_bucket = s->slot_of_bucket; x.dist = s->dist; x.weights = s->weights; x.sel_count = s->count;
         x.orow = s->ostats + NGW_SEARCH_OPEN_COLS * (s->iterations % SEARCH_RING); x.next_orow = s->ostats + NGW_SEARCH_OPEN_COLS * ((s->iterations + 1) % SEARCH_RING);
         x.buckets = s->buckets; x.K = s->K; x.mode = s->hmode; x.prune = s->prune;
+        x.recipe = s->recipe_run ? s->recipe : nullptr;
     }
     return x;
 }
@@ -76,6 +79,8 @@ int iterate(ngw_handle* h, ngw_search* s) {
     if (s->open) {                                    // step 8: the children join the open list
         if (s->dist)
             if (int rc = ngw_snapshot_walk(h, s->pool, x.next, s->cap, nullptr, 0, s->dist, nullptr, nullptr)) return rc;
+        if (s->recipe_run)                            // (the recipe term of the same list: a padded entry gives 0 and no flag)
+            if (int rc = s->recipe_run(h, h->stream, s->pool->r, s->pool->cap, x.next, s->cap, s->recipe_prog, s->recipe)) return rc;
         HIP_TRY(ngw_search_open_launch(&x, h->stream));
     }
     s->cur ^= 1;
@@ -208,7 +213,24 @@ int ngw_search_destroy(ngw_handle* h, ngw_search* s) {
     for (size_t i = 0; i < h->searches.size(); i++)
         if (h->searches[i] == s) { h->searches.erase(h->searches.begin() + (long)i); break; }
     dev_free(h, s->slab);
+    if (s->recipe) dev_free(h, s->recipe);
     delete s;
+    return NGW_OK;
+}
+
+int ngw_search_set_recipe(ngw_handle* h, ngw_search* s, const ngw_recipe_program* program) {
+    if (int rc = search_call_args(h, s)) return rc;
+    if (!program) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (!s->open) return fail(NGW_E_INVALID_ARG, "a search without an open list has no heuristic (ngw_search_create_open makes one with)");
+    if (s->started || s->iterations) return fail(NGW_E_INVALID_ARG, "ngw_search_set_recipe is legal only before ngw_search_start");
+    if (!recipe_hooks.pack || !recipe_hooks.run) return fail(NGW_E_INVALID_ARG, "the recipe heuristic is not part of this build (ngw_host_recipe.cpp)");
+    if (int rc = enter(h)) return rc;
+    NgwRecipeProg prog;
+    if (int rc = recipe_hooks.pack(h, program, &prog)) return rc;
+    if (!s->recipe)
+        if (int rc = dev_alloc(h, &s->recipe, (size_t)s->cap)) return rc;         // (zero-filled on the handle's stream; ngw_search_run allocates nothing)
+    s->recipe_prog = prog;
+    s->recipe_run = recipe_hooks.run;
     return NGW_OK;
 }
 
@@ -217,6 +239,7 @@ int ngw_search_start(ngw_handle* h, ngw_search* s, const int32_t* roots_dev, int
     if (count < 0 || count > s->cap) return fail(NGW_E_INVALID_ARG, "%lld roots in a search of capacity %lld", (long long)count, (long long)s->cap);
     if (count && !roots_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (int rc = enter(h)) return rc;
+    s->started = true;
     if (count) {
         // the scratch of an iteration serves: values 0, tags NGW_TAG_ROOT; the values the table holds afterwards go to `info`, their tags to `plist`
         HIP_TRY(hipMemsetAsync(s->values, 0, (size_t)count * sizeof(int32_t), h->stream));
@@ -232,6 +255,11 @@ int ngw_search_start(ngw_handle* h, ngw_search* s, const int32_t* roots_dev, int
         if (count && s->dist)
             if (int rc = ngw_snapshot_walk(h, s->pool, roots_dev, count, nullptr, 0, s->dist, nullptr, nullptr)) return rc;
         x.f = s->f; x.h = s->h; x.slot_of_bucket = s->slot_of_bucket; x.dist = s->dist; x.weights = s->weights; x.buckets = s->buckets; x.K = s->K; x.mode = s->hmode;
+        if (s->recipe_run) {
+            if (count)
+                if (int rc = s->recipe_run(h, h->stream, s->pool->r, s->pool->cap, roots_dev, count, s->recipe_prog, s->recipe)) return rc;
+            x.recipe = s->recipe;
+        }
     }
     HIP_TRY(ngw_search_roots_launch(&x, h->stream));
     if (current) *current = s->cur;

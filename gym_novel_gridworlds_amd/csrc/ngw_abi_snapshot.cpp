@@ -17,6 +17,7 @@
 // the table as it was.
 // The weighted choice (ngw_sample.inc) draws one action per row by the caller's weights among the valid ones: it commits nothing either.
 // The walk (ngw_walk.inc) finds the shortest Forward / Left / Right walks from such rows to each item id: it commits nothing either.
+// The recipe costs (ngw_recipe.inc, through ngw_host_recipe.cpp) bound the crafting cost such rows still have to pay: they commit nothing either.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -646,6 +647,20 @@ int ngw_snapshot_walk(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, in
     x.act_forward = act[NGW_ACT_FORWARD]; x.act_left = act[NGW_ACT_LEFT]; x.act_right = act[NGW_ACT_RIGHT];
     HIP_TRY(ngw_walk_launch(&x, h->stream));
     return NGW_OK;
+}
+
+int ngw_snapshot_recipe_costs(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, const ngw_recipe_program* program, int32_t* out_dev) {
+    if (!h || !program || !out_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!recipe_hooks.pack || !recipe_hooks.run) return fail(NGW_E_INVALID_ARG, "the recipe heuristic is not part of this build (ngw_host_recipe.cpp)");
+    const Source from = source_of(h, s);
+    if (count < 0 || count > 0x7FFFFFFFll * NGW_EPB) return fail(NGW_E_INVALID_ARG, "recipe costs of %lld rows", (long long)count);
+    if (!idx_dev && count > from.rows) return fail(NGW_E_INVALID_ARG, "recipe costs of %lld rows from %lld %s", (long long)count, (long long)from.rows, from.unit);
+    if (int rc = enter(h)) return rc;                 // (s == NULL: the one-env loop has ended, HBM holds the env's state)
+    NgwRecipeProg prog;
+    if (int rc = recipe_hooks.pack(h, program, &prog)) return rc;
+    if (count == 0) return NGW_OK;
+    return recipe_hooks.run(h, h->stream, from.r, from.rows, idx_dev, count, prog, out_dev);
 }
 
 int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t count, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv,

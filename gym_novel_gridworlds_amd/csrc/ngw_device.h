@@ -970,6 +970,7 @@ struct NgwSearch {
     uint32_t* next_orow;        /* [8]: the next one's */
     int64_t buckets;
     int32_t K, mode, prune;
+    const int32_t* recipe;      /* [capacity]: the recipe term of every entry of the child list (ngw_recipe_launch); NULL: none, h is the walk term alone */
 };
 #define NGW_SEARCH_BLOCK 256     /* threads per workgroup: four waves, one position per lane */
 #define NGW_SEARCH_OFFERED 0     /* the columns of a stats row */
@@ -1036,10 +1037,49 @@ struct NgwSearchRoots {
     const int32_t* weights;     /* [K] */
     int64_t buckets;
     int32_t K, mode;
+    const int32_t* recipe;      /* [count]: the recipe term of every root; NULL: none */
 };
 #ifdef __cplusplus
 extern "C"
 #endif
 hipError_t ngw_search_roots_launch(const struct NgwSearchRoots* x, hipStream_t stream);
+
+/* The recipe heuristic (ngw_recipe.inc, ngw_host_recipe.cpp; the contract is include/ngw.h's ngw_snapshot_recipe_costs): out[j] = the relaxed-plan cost
+ * of row idx[j] of `src` (a snapshot or the state slab; a NULL list = j itself) under `prog`, the program as the host unit packs it - items resolved
+ * to rule numbers, the flagged map items to count slots:
+ *   rule r: d = max(0, need[r] - have), have = inv[out_item] + (map_slot >= 0: the cells equal to map_item[map_slot]); n = ceil(d / out_qty);
+ *           h = min(h + n * cost, NGW_VALUE_NONE - 1); need[in_rule[i]] = min(need + n * in_qty[i], 2^31 - 1) for the inputs that have a rule (in_rule
+ *           > r, -1: none); n > 0: need[tool_rule] = max(need, 1).  need[goal_rule] starts at 1 (goal_rule -1: h = 0).
+ * An index outside [0, rows) is never used as an address: its cost is 0 and - unless it is NGW_IDX_NONE - NGW_F_BAD_INDEX is raised in *flags.  Nothing
+ * but out[0 .. count) and the flags word is stored.  The program travels by value in the kernel's argument block (400 bytes).  With n_map == 0 no map
+ * byte is read. */
+#define NGW_RECIPE_RULES 16
+struct NgwRecipeRule {
+    int32_t cost;
+    uint16_t out_qty;
+    uint8_t out_item, n_in;
+    int8_t map_slot, tool_rule;     /* -1: none */
+    int8_t in_rule[4];              /* -1: the input has no rule */
+    uint16_t in_qty[4];
+    uint16_t pad;
+};
+struct NgwRecipeProg {
+    int32_t n_rules, goal_rule, n_map;
+    uint8_t map_item[4];
+    struct NgwRecipeRule rule[NGW_RECIPE_RULES];
+};
+struct NgwRecipe {
+    NgwSnapRows src;
+    const int32_t* idx;
+    uint32_t* flags;
+    int32_t* out;
+    int64_t count;
+    int32_t rows, S2, K;
+    struct NgwRecipeProg prog;
+};
+#ifdef __cplusplus
+extern "C"
+#endif
+hipError_t ngw_recipe_launch(const struct NgwRecipe* x, hipStream_t stream);
 
 #endif

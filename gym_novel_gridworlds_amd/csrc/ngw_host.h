@@ -15,6 +15,7 @@
 //                        the k best candidates per group in the same list form (ngw_select.inc)
 //   ngw_abi_search.cpp   search runs: the driver that enqueues whole best-first iterations - the five stages above through their own entry points, the three
 //                        kernels of ngw_search.inc between them
+//   ngw_host_recipe.cpp  the recipe heuristic (ngw_recipe.inc): program checks and the launch, behind ngwh::recipe_hooks (below) - not an ngw_abi_ unit
 //
 // Three rules hold in all of them:
 //   1. Guard first.  An entry point that uses the handle's stream or its device state starts with `if (int rc = enter(h)) return rc;`
@@ -44,6 +45,16 @@
 namespace ngwh {
 int fail(int code, const char* fmt, ...);           // sets the thread-local message ngw_last_error() returns; returns `code`
 const char* last_error();
+// The recipe heuristic's host code is a unit of its own, ngw_host_recipe.cpp - the only host unit that names ngw_recipe_launch -, and the entry points
+// (ngw_snapshot_recipe_costs in ngw_abi_snapshot.cpp, ngw_search_set_recipe in ngw_abi_search.cpp) reach it through these two pointers, which that
+// unit fills when the library is loaded.  The ngw_abi_*.cpp units therefore link without it - as the host-side sanitizer harness links them, one
+// stub per launcher it knew -, and the entry points then refuse the call.
+//   pack  checks a program against the rules of include/ngw.h and the handle's K, and packs it for the kernel (ngw_device.h NgwRecipeProg)
+//   run   out_dev[j] = the cost of row idx_dev[j] of `src`: one launch on `stream` - the handle's, handed in by the caller that stands behind enter(); count > 0
+typedef int (*RecipePack)(const ngw_handle* h, const ngw_recipe_program* in, NgwRecipeProg* out);
+typedef int (*RecipeRun)(ngw_handle* h, hipStream_t stream, const NgwSnapRows& src, int64_t rows, const int32_t* idx_dev, int64_t count, const NgwRecipeProg& prog, int32_t* out_dev);
+struct RecipeHooks { RecipePack pack = nullptr; RecipeRun run = nullptr; };
+extern RecipeHooks recipe_hooks;                    // ngw_abi_create.cpp, beside fail(); called behind enter() like any other use of the handle
 }
 
 #define HIP_TRY(expr)                                                                                   \
@@ -106,6 +117,12 @@ struct ngw_search {
     int64_t buckets = 0;
     int32_t *f = nullptr, *h = nullptr, *slot_of_bucket = nullptr, *weights = nullptr, *dist = nullptr;
     uint32_t* ostats = nullptr;           // [NGW_SEARCH_ROWS + 1][NGW_SEARCH_OPEN_COLS], rows as in `stats`
+    // the recipe term (ngw_search_set_recipe): the program, the term of every list entry [cap] - an allocation of its own, made by that call - and the
+    // way to ngw_host_recipe.cpp's launch; recipe_run NULL: no term, and every kernel gets what it got before there was one
+    bool started = false;                 // ngw_search_start was called
+    ngwh::RecipeRun recipe_run = nullptr;
+    int32_t* recipe = nullptr;
+    NgwRecipeProg recipe_prog{};
 };
 
 struct ngw_handle {

@@ -198,13 +198,14 @@ __global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_take_kernel(const
     if (k == 0) x.orow[NGW_SEARCH_OPEN] = (uint32_t)x.sel_count[1];
 }
 
-// OPEN (step 8): h and f of every child written this iteration
+// OPEN (step 8): h and f of every child written this iteration; h = the walk term plus, where the search has one, the recipe term, clamped
 __global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_open_kernel(const NgwSearch x) {
     const int64_t k = (int64_t)blockIdx.x * NGW_SEARCH_BLOCK + threadIdx.x;
     if (k >= x.capacity) return;
     const int32_t c = x.next[k];
     if (c < 0 || (int64_t)c >= x.pool) return;
-    const int32_t hv = x.dist ? search_walk_h(x.dist + k * x.K, x.weights, x.K, x.mode) : 0;
+    int32_t hv = x.dist ? search_walk_h(x.dist + k * x.K, x.weights, x.K, x.mode) : 0;
+    if (x.recipe) hv = search_priority(hv, x.recipe[k]);                               // (the two terms add: movement and rule actions are disjoint)
     x.h[c] = hv;
     x.f[c] = search_priority(x.g[c], hv);
 }
@@ -223,7 +224,8 @@ __global__ void __launch_bounds__(NGW_SEARCH_BLOCK) ngw_search_roots_kernel(cons
             if (x.best[j]) {
                 if constexpr (OPEN) {                                              // opened: the first iteration chooses it from the list
                     if ((int64_t)w < x.buckets) x.slot_of_bucket[w] = r;           // (best is set once per key: one writer per bucket)
-                    const int32_t hv = x.dist ? search_walk_h(x.dist + j * x.K, x.weights, x.K, x.mode) : 0;
+                    int32_t hv = x.dist ? search_walk_h(x.dist + j * x.K, x.weights, x.K, x.mode) : 0;
+                    if (x.recipe) hv = search_priority(hv, x.recipe[j]);
                     x.h[r] = hv;
                     x.f[r] = search_priority(g, hv);
                 } else {

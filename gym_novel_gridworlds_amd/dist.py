@@ -193,6 +193,10 @@ class ShardedVecNovelGridworld:
         """The walk distances of this rank's shard (VecNovelGridworld.walk_distances): `envs` are the shard's own indices; rank-local, no collective."""
         return self.local.walk_distances(envs, device)
 
+    def recipe_costs(self, envs=None, costs=None, scale=1, device=False):
+        """The recipe costs of this rank's shard (VecNovelGridworld.recipe_costs): `envs` are the shard's own indices; rank-local, no collective."""
+        return self.local.recipe_costs(envs, costs, scale, device)
+
     def walk_plans(self, items, steps, envs=None, device=False):
         """The go-to plans of this rank's shard (VecNovelGridworld.walk_plans): `envs` are the shard's own indices; rank-local, no collective."""
         return self.local.walk_plans(items, steps, envs, device)

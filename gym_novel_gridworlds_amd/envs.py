@@ -377,6 +377,13 @@ class _NovelGridworldEnv(_EnvBase):
         self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
         return vec.walk_distances()[0]
 
+    def recipe_cost(self, costs=None, scale=1):
+        """A Python int: what the current state still has to pay in crafts, extractions and breaks before it holds the goal item, at the
+        least, computed on the device; see VecNovelGridworld.recipe_costs and search.recipe_program for the contract."""
+        vec = self._backend()
+        self._push(vec)                                      # (attributes the caller edited since the last step go to the device first)
+        return int(vec.recipe_costs(costs=costs, scale=scale)[0])
+
     def walk_plan(self, item, steps):
         """(the first min(length, steps) action ids of the shortest walk that leaves the agent facing a cell of id `item`, its true length; ([], -1)
         where no reachable pose faces one); see VecNovelGridworld.walk_plans."""

@@ -74,6 +74,9 @@ class NoveltyWrapper(object):
     def walk_plan(self, item, steps):
         return self.env.walk_plan(item, steps)
 
+    def recipe_cost(self, costs=None, scale=1):
+        return self.env.recipe_cost(costs=costs, scale=scale)
+
     def render(self, mode='human', **kwargs):
         return self.env.render(mode, **kwargs)
 

@@ -270,6 +270,181 @@ def best_first_reference(f, h, g, bucket, slot_of_bucket, successors, held, curs
     return BestFirst(chosen, parents, pruned, n_open, f_min, f_bound, superseded, r)
 
 
+# ------------------------------------------------------------------ the recipe heuristic (include/ngw.h ngw_snapshot_recipe_costs; csrc/ngw_recipe.inc)
+RecipeRule = collections.namedtuple('RecipeRule', 'out_item out_qty cost inputs tool_item')     # inputs: ((item, qty), ...) consumed; tool_item -1: none
+MAX_RULES, MAX_RULE_INPUTS, MAX_MAP_ITEMS = _cabi.RECIPE_MAX_RULES, _cabi.RECIPE_MAX_INPUTS, _cabi.RECIPE_MAX_MAP_ITEMS
+
+
+class RecipeProgram(collections.namedtuple('RecipeProgram', 'goal_item rules map_items')):
+    """What the recipe kernel evaluates: the goal item, at most 16 RecipeRule in topological order - consumers before producers - and
+    `map_items`, a bit mask of the items whose cells on the map count as held (recipe_program() builds one from a spec)."""
+    __slots__ = ()
+
+    def struct(self):
+        """include/ngw.h ngw_recipe_program."""
+        if len(self.rules) > MAX_RULES:
+            raise ValueError("recipe program: %d rules (at most %d)" % (len(self.rules), MAX_RULES))
+        p = _cabi.RecipeProgram()
+        p.goal_item, p.n_rules, p.map_items = int(self.goal_item), len(self.rules), int(self.map_items)
+        for r, u in enumerate(self.rules):
+            if len(u.inputs) > MAX_RULE_INPUTS:
+                raise ValueError("recipe rule %d: %d inputs (at most %d)" % (r, len(u.inputs), MAX_RULE_INPUTS))
+            q = p.rules[r]
+            q.out_item, q.out_qty, q.cost, q.n_in, q.tool_item = int(u.out_item), int(u.out_qty), int(u.cost), len(u.inputs), int(u.tool_item)
+            for i, (item, qty) in enumerate(u.inputs):
+                q.in_item[i], q.in_qty[i] = int(item), int(qty)
+        return p
+
+
+def recipe_program(spec, costs=None, scale=1):
+    """The relaxed-plan program of a spec (an EnvSpec or a compiled ngw_spec) under a search's cost table - `costs` / `scale` as pool.search
+    takes them, through cost_table -> RecipeProgram.  A rule is ONE successful application of one action, at that action's cost
+    (round(STEP_COSTS[its success code] * scale), or costs[its action id]):
+        craft    a recipe: its inputs are consumed, recipe_out_qty comes out (cost code cost_ok);
+        extract  the spec's extract rule: ext_qty of ext_out (cost code ext_cost_ok).  The source is a BLOCK IN FRONT of the agent, never the
+                 inventory: where the step consumes it (Bow: a wool block -> 4 string) the rule has no input - what it takes for the block to
+                 be there is left out -, where it stays (Pogostick: the tap -> 1 rubber) it is the rule's TOOL;
+        break    an item that lies on the map at reset and has no recipe and is not extracted: no input, break_qty[item] come out (cost_break;
+                 with an axe in the spec the cheaper of the two costs and the larger of the two quantities).
+    An item with more than one source - a recipe and the extract rule, a recipe and the map (the v0 ids' sticks and planks), a crate, a Chop
+    action beside Break - gets NO rule, and so does one whose action the spec lacks: demand on it costs 0, the bound is weaker there and never
+    wrong.  Only the rules the goal item's demand can reach are kept, consumers before producers (ties: the smaller item id); a recipe table
+    with a cycle among them raises ValueError, as do a negative rule cost and more than 16 rules.  map_items flags the tools - at most 4 -
+    that no kept rule consumes: a tap standing on the map serves as one in the inventory does (so being on the map is no second source of a
+    flagged item).
+    What the rules leave out - Place, "the tap must stand beside a tree", the crafting table, every move - only lowers the bound.  Whether it
+    is admissible for a spec is the caller's business, as with WalkHeuristic; tests/test_recipe_heuristic_cpu.py shows consistency, which
+    gives it, for the base Pogostick-v1 and Bow-v1 specs."""
+    from .spec import ACT_BREAK, ACT_CHOP, ACT_CRAFT, ACT_EXTRACT
+    cs = spec.compile() if hasattr(spec, 'compile') else spec
+    K, A = int(cs.n_items), int(cs.n_actions)
+    lut, by_action = cost_table(costs, scale, A)
+    kinds, args = [int(cs.act_kind[a]) for a in range(A)], [int(cs.act_arg[a]) for a in range(A)]
+
+    def cost_of(kind, arg, code):
+        """The cost of the lowest action id of `kind` (and `arg`), None when the spec has no such action."""
+        ids = [a for a in range(A) if kinds[a] == kind and (arg is None or args[a] == arg)]
+        if not ids:
+            return None
+        return int(lut[ids[0]] if by_action else lut[code])
+
+    sources = [[] for _ in range(K)]                     # per item: the rules that give it, or None for a source that is no rule
+    for r in range(int(cs.n_recipes)):
+        out = int(cs.recipe_out_item[r])
+        inputs = tuple((int(cs.recipe_in_item[r][j]), int(cs.recipe_in[r][int(cs.recipe_in_item[r][j])])) for j in range(int(cs.recipe_n_in[r])))
+        cost = cost_of(ACT_CRAFT, r, int(cs.cost_ok[r]))
+        sources[out].append(None if cost is None else RecipeRule(out, int(cs.recipe_out_qty[r]), cost, inputs, -1))
+    if ACT_EXTRACT in kinds and int(cs.ext_qty) > 0:
+        out, src = int(cs.ext_out), int(cs.ext_src)
+        cost = cost_of(ACT_EXTRACT, None, int(cs.ext_cost_ok))
+        sources[out].append(None if cost is None else RecipeRule(out, int(cs.ext_qty), cost, (), -1 if cs.ext_consume else src))
+    tools = {u.tool_item for s in sources for u in s if u is not None and u.tool_item >= 0}
+    on_map = {int(cs.start_item[j]) for j in range(int(cs.n_start))} | {int(cs.pass_item[j]) for j in range(int(cs.n_passes))}
+    if int(cs.tap_item):
+        on_map.add(int(cs.tap_item))
+    for k in sorted(on_map - tools):                     # (a tool on the map is counted as held: map_items)
+        cost, qty = cost_of(ACT_BREAK, None, int(cs.cost_break)), int(cs.break_qty[k])
+        if int(cs.axe_item) and not by_action and cost is not None:
+            cost, qty = min(cost, int(lut[int(cs.axe_cost)])), max(qty, int(cs.axe_qty))
+        ok = cost is not None and cs.breakable[k] and qty >= 1 and ACT_CHOP not in kinds
+        sources[k].append(RecipeRule(k, qty, cost, (), -1) if ok else None)
+    for k in range(K):
+        if cs.crate_add[k]:
+            sources[k].append(None)
+    rule_of = {k: s[0] for k, s in enumerate(sources) if len(s) == 1 and s[0] is not None}
+    goal = int(cs.goal_item)
+    reach, stack = set(), [goal]
+    while stack:                                         # the rules the goal's demand can reach
+        k = stack.pop()
+        if k in reach or k not in rule_of:
+            continue
+        reach.add(k)
+        stack += [item for item, _ in rule_of[k].inputs] + ([rule_of[k].tool_item] if rule_of[k].tool_item >= 0 else [])
+    feeds = {k: {item for item, _ in rule_of[k].inputs} | ({rule_of[k].tool_item} - {-1}) for k in reach}
+    waiting = {k: sum(1 for c in reach if k in feeds[c]) for k in reach}          # consumers not yet emitted
+    rules, left = [], set(reach)
+    while left:
+        ready = sorted(k for k in left if waiting[k] == 0)
+        if not ready:
+            raise ValueError("recipe table: a cycle among the rules of items %s" % sorted(left))
+        k = ready[0]
+        left.remove(k)
+        rules.append(rule_of[k])
+        for item in feeds[k] & reach:
+            waiting[item] -= 1
+    if len(rules) > MAX_RULES:
+        raise ValueError("recipe program: %d rules (at most %d)" % (len(rules), MAX_RULES))
+    for u in rules:
+        if u.cost < 0:
+            raise ValueError("recipe program: the rule of item %d has a negative cost (%d): no lower bound comes of it" % (u.out_item, u.cost))
+    consumed = {item for u in rules for item, _ in u.inputs}
+    flagged = sorted({u.tool_item for u in rules if u.tool_item >= 0} - consumed)[:MAX_MAP_ITEMS]
+    return RecipeProgram(goal, tuple(rules), sum(1 << k for k in flagged))
+
+
+def map_item_counts(maps, n_items):
+    """on_map for recipe_cost_reference: int32 [n, K], how many cells of each map ([n, S * S] or [n, S, S] item ids) hold each id."""
+    m = np.asarray(maps)
+    m = m.reshape(m.shape[0], -1)
+    return np.stack([(m == k).sum(axis=1) for k in range(int(n_items))], axis=1).astype(np.int32)
+
+
+def recipe_cost_reference(inv, on_map, program):
+    """The recipe heuristic in numpy (the contract of include/ngw.h, ngw_snapshot_recipe_costs) -> int32 [n] (a scalar array for one row).
+    inv int32 [n, K] or [K]: the inventories; on_map the same shape (map_item_counts of the maps) or None: nothing on any map.
+        have[k] = inv[k] + (on_map[k] if bit k of program.map_items is set);  need[goal] = 1, every other need 0;  h = 0
+        for each rule in order:  d = max(0, need[out] - have[out]);  n = ceil(d / out_qty);  h += n * cost;  need[in_i] += n * in_qty_i;
+                                 if n > 0 and the rule has a tool: need[tool] = max(need[tool], 1)
+    in 64 bits, need saturating at 2^31 - 1 and h at VALUE_NONE - 1."""
+    inv = np.asarray(inv, np.int64)
+    one = inv.ndim == 1
+    have = inv.reshape(-1, inv.shape[-1]).copy()
+    K = have.shape[1]
+    if on_map is not None:
+        flagged = np.array([(int(program.map_items) >> k) & 1 for k in range(K)], np.int64)
+        have += np.asarray(on_map, np.int64).reshape(have.shape) * flagged
+    need = np.zeros_like(have)
+    need[:, int(program.goal_item)] = 1
+    h = np.zeros(len(have), np.int64)
+    for u in program.rules:
+        d = np.maximum(need[:, u.out_item] - have[:, u.out_item], 0)
+        n = (d + (int(u.out_qty) - 1)) // int(u.out_qty)
+        h = np.minimum(h + n * int(u.cost), VALUE_NONE - 1)
+        for item, qty in u.inputs:
+            need[:, item] = np.minimum(need[:, item] + n * int(qty), (1 << 31) - 1)
+        if u.tool_item >= 0:
+            need[:, u.tool_item] = np.where(n > 0, np.maximum(need[:, u.tool_item], 1), need[:, u.tool_item])
+    h = h.astype(np.int32)
+    return h[0] if one else h
+
+
+class RecipeHeuristic(collections.namedtuple('RecipeHeuristic', 'walk')):
+    """The heuristic of an open-list search from the recipe table: h(slot) = min(recipe + walk, VALUE_NONE - 1), `recipe` the relaxed-plan
+    cost of the slot's state under recipe_program(the env's spec, the search's own costs / scale) - what the crafts, extractions and breaks
+    still cost at the least - and `walk` the term of a WalkHeuristic (None: 0).  Movement actions and rule actions are disjoint, so the sum of
+    two lower bounds is one.  Whether it is admissible is the caller's business, as WalkHeuristic says."""
+    __slots__ = ()
+
+    def __new__(cls, walk=None):
+        return super().__new__(cls, walk)
+
+
+def recipe_call(env, holder, s, idx, limit, name, costs, scale, device):
+    """The one launch behind Snapshot.recipe_costs (s: the C handle of the snapshot the rows are read from) and VecNovelGridworld.recipe_costs
+    (s None: the envs' current states): idx indexes rows [0, limit); `holder` keeps an uploaded list alive.  -> int32 [count]."""
+    import torch
+
+    from .snapshot import check_slots, enqueue_ordered, tensor_len, upload
+    program = recipe_program(env.cspec, costs, scale).struct()
+    dev = torch.device('cuda:%d' % env.device)
+    rows, count = check_slots(idx, limit, lambda x: tensor_len(dev, name, x), False, name)
+    (ptr,), uploaded = upload(dev, count, rows)
+    out = torch.empty(count, dtype=torch.int32, device=dev)
+    enqueue_ordered(env, holder, lambda: _cabi.lib().ngw_snapshot_recipe_costs(env._h, s, ptr, count, C.byref(program), C.c_void_p(out.data_ptr())), count,
+                    uploaded, device)
+    return out if device else out.cpu().numpy()
+
+
 def check_roots(roots, limit, capacity, device_len=None):
     """The host-side check of start()'s roots: a list / numpy array of one dimension and integer dtype whose entries are slots in [0, limit) or
     IDX_NONE -> a contiguous int32 array; device_len(x): the length of x when it is a device tensor to be used in place (its values are then
@@ -317,7 +492,8 @@ class Search:
     rewrites f of the open slots with a torch expression of their own - a learned value, say - gets that order.  A slot written by anything
     but the search keeps f = VALUE_NONE and is never chosen.  After start() `parents` is empty - the first iteration chooses the roots from
     the list -; after run() it holds the children the last iteration wrote and `chosen` the slots it expanded.
-    heuristic: None (h = 0: uniform-cost search) or a WalkHeuristic.  prune=True: a chosen slot whose f is >= the goal's value is closed
+    heuristic: None (h = 0: uniform-cost search), a WalkHeuristic, or a RecipeHeuristic(walk=None | WalkHeuristic) - the crafting-cost lower
+    bound of recipe_program(spec, costs, scale) plus the walk term; `recipe` is then that program.  prune=True: a chosen slot whose f is >= the goal's value is closed
     without being expanded - valid for an admissible h and non-negative costs -, so once a goal is known iterations stop expanding what
     cannot beat it, and when nothing can they expand nothing (the launches leave early on empty lists): the early stop on the device."""
 
@@ -351,8 +527,10 @@ class Search:
                 raise ValueError("keep: an open-list search expands 1 <= keep <= capacity states per iteration, got %r" % (keep,))
             if snap.capacity > MAX_FLAGS:
                 raise ValueError("open_list: the selection runs over every slot of the pool, at most 2^24 (this pool has %d)" % snap.capacity)
-        mode, weights = check_heuristic(heuristic, self.env.n_items)
+        walk = heuristic.walk if isinstance(heuristic, RecipeHeuristic) else heuristic
+        mode, weights = check_heuristic(walk, self.env.n_items)
         self.costs, self.by_action = cost_table(costs, scale, A)
+        self.recipe = recipe_program(self.env.cspec, costs, scale) if isinstance(heuristic, RecipeHeuristic) else None
         self._s, self._keep, self._cur = C.c_void_p(), None, 0
         more = _cabi.SearchArraysOpen()
         arrays = more.base
@@ -368,6 +546,13 @@ class Search:
             if str(e).startswith('map_size'):
                 raise MapsTooLarge(str(e)) from None
             raise
+        if self.recipe is not None:                     # (before any start: the term's scratch is allocated here, run() allocates nothing)
+            try:
+                _cabi.check(_cabi.lib().ngw_search_set_recipe(self.env._h, self._s, C.byref(self.recipe.struct())))
+            except Exception:
+                _cabi.lib().ngw_search_destroy(self.env._h, self._s)
+                self._s = C.c_void_p()
+                raise
         dev = 'cuda:%d' % self.env.device
         view = lambda ptr, n: torch.as_tensor(_DevArray(ptr, (n,), '<i4'), device=dev)   # noqa: E731
         self._lists = [view(arrays.parents[0], self.capacity), view(arrays.parents[1], self.capacity)]

@@ -1034,6 +1034,20 @@ class Snapshot:
         self._open()
         return walk_call(self.env, self, self._s, slots, self.capacity, 'slots', items, steps, device)
 
+    # ------------------------------------------------------------------ the recipe heuristic (include/ngw.h ngw_snapshot_recipe_costs; search.py)
+    def recipe_costs(self, slots=None, costs=None, scale=1, source=None, from_envs=False, device=False):
+        """What saved slots' states still have to pay in crafts, extractions and breaks before they hold the goal item, at the least: int32
+        [count], entry j the relaxed-plan cost of slot slots[j] (None: every slot) under search.recipe_program(spec, costs, scale) - costs /
+        scale as search() takes them - read off the slot's inventory and, for the tools the program flags (the Pogostick tap), their number
+        on its map.  The public integer contract of include/ngw.h, which search.recipe_cost_reference() computes on the host for the same
+        state.  The heuristic term of an A* over the pool (search.RecipeHeuristic runs it inside run()), a shaping potential, a progress
+        feature; moves are not in it - walk_distances() bounds those.  source / from_envs: the rows of another Snapshot of the same env /
+        the env's current states, as in expand().  One kernel launch, no LDS staging: every map size; nothing is committed.
+        slots and device: as in keys() (they may repeat; IDX_NONE in a device list: 0; an index out of range there: 0, F_BAD_INDEX)."""
+        from .search import recipe_call
+        src, n_rows, _ = self._source(source, from_envs, 'recipe_costs')
+        return recipe_call(self.env, self, src, slots, n_rows, 'envs' if from_envs else 'slots', costs, scale, device)
+
     # ------------------------------------------------------------------ device-side frontiers (include/ngw.h ngw_frontier_*; frontier.py)
     def frontier(self, capacity):
         """A Frontier of `capacity` entries for this snapshot: index lists padded with IDX_NONE and a slot cursor on the device, so that
@@ -1051,8 +1065,8 @@ class Snapshot:
         costs: None - the step costs times `scale`, rounded - or one int32 per action; keep: None or the k cheapest improved states that go
         on; stop_at_goals: ended states are not expanded.  ValueError for a table without values and for keep > capacity; maps beyond
         successor_keys' 34 x 34 raise what successor_keys raises.  open_list=True (with keep=k): a best-first search over an open list - the k
-        open states of the smallest f = g + h of the WHOLE list are expanded per iteration -, heuristic: None or a search.WalkHeuristic,
-        prune: states that cannot beat the goal are closed unexpanded (search.Search says what each does).  Closed by its close() and with
+        open states of the smallest f = g + h of the WHOLE list are expanded per iteration -, heuristic: None, a search.WalkHeuristic or a
+        search.RecipeHeuristic, prune: states that cannot beat the goal are closed unexpanded (search.Search says what each does).  Closed by its close() and with
         this snapshot."""
         from .search import Search
         self._open()

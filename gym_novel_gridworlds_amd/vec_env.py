@@ -1066,6 +1066,14 @@ class VecNovelGridworld:
         from .walk import walk_call
         return walk_call(self, self._keeper(), None, envs, self.num_envs, 'envs', None, 0, device, want_plans=False)
 
+    def recipe_costs(self, envs=None, costs=None, scale=1, device=False):
+        """What the envs' CURRENT states still have to pay in crafts, extractions and breaks before they hold the goal item, at the least:
+        int32 [count] - Snapshot.recipe_costs() without the save (the contract: include/ngw.h ngw_snapshot_recipe_costs,
+        search.recipe_cost_reference on the host).  costs / scale as Snapshot.search takes them; envs as in state_keys() (an index out of range
+        in a device list: 0, F_BAD_INDEX).  One kernel launch; nothing is committed."""
+        from .search import recipe_call
+        return recipe_call(self, self._keeper(), None, envs, self.num_envs, 'envs', costs, scale, device)
+
     def walk_plans(self, items, steps, envs=None, device=False):
         """The shortest walk of each env's agent from its CURRENT state to the nearest cell of items[j], as a plan: Snapshot.walk_plans()
         without the save - WalkPlans(plans [steps, count], length [count], dist [count, K]).  items, steps and device as there, envs as in

@@ -159,6 +159,25 @@ class LimitActions(NoveltyWrapper):
         plan, length = self.env.walk_plan(item, steps)
         return [ids[a] for a in plan], length
 
+    def recipe_cost(self, costs=None, scale=1):
+        """The env's recipe_cost with a per-action `costs` written in the limited id space: entry i is the cost of the action limited id i steps
+        (the two look-ups of step()).  An action of the env that no limited id steps costs 0 there, and so does the rule it stands for: with
+        Extract_rubber outside the limited set the extraction's 50 000 drops out of the bound, with every craft and Break outside it the bound
+        is 0.  That is still a lower bound - such an action cannot be taken at all - but it can collapse silently: keep the actions the recipe
+        table needs in the limited set, or pass costs=None.  (Without `costs` nothing depends on the action id space: passed through.)"""
+        if costs is None:
+            return self.env.recipe_cost(scale=scale)
+        c = np.asarray(costs)
+        n = len(self.limited_actions)
+        if c.dtype.kind not in 'iu' or c.shape != (n,):
+            raise ValueError("costs: one integer per limited action expected, shape [%d], got dtype %s, shape %s" % (n, c.dtype, list(c.shape)))
+        env_actions = self.actions_id
+        full = np.zeros(self.unwrapped._backend().n_actions, np.int64)      # (the width of the batched env's action table)
+        for i, j in enumerate(limit_column_ids(self.limited_actions_id, env_actions, n, len(full))):
+            if j is not None:
+                full[j] = c[i]
+        return self.env.recipe_cost(costs=full, scale=scale)
+
     def _limited_env(self):
         """-> (the one-env batched env whose action table is this wrapper's list - limit_actions_vec, kept from call to call - holding a copy
         of the adapter's current state, this wrapper's id of each of its actions): what playouts() and sample_action() run on."""

@@ -1212,6 +1212,46 @@ int ngw_search_create_open(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* tab
                            ngw_search** out);
 int ngw_search_read_open(ngw_handle* h, ngw_search* s, ngw_search_open_report* out);
 
+/* The recipe heuristic: a lower bound on the craft / extract / break cost that a state still has to pay before it holds the goal item, read off its
+ * inventory and - for tools that work from the map, the Pogostick tap - off the count of an item on its map.  The term beside the walk heuristic:
+ * movement actions and rule actions are disjoint, so lower bounds on their costs add.  A relaxed plan over a PROGRAM the caller compiles from the
+ * spec's recipe table and the search's cost table (search.recipe_program does; search.recipe_cost_reference states the evaluation in numpy).
+ * A program holds the goal item, a bit mask `map_items` (bit k: cells of id k on the map count as held; at most NGW_RECIPE_MAX_MAP_ITEMS bits, none of
+ * an item that a rule consumes) and n_rules <= NGW_RECIPE_MAX_RULES rules, each ONE successful application of one action:
+ *     out_item, out_qty in [1, 65535], cost in [0, NGW_VALUE_NONE), n_in <= 4 inputs (in_item, in_qty in [1, 65535]) that it consumes, and tool_item
+ *     (-1: none): an item that must be held, and is kept.
+ * No two rules give the same item, and the order is topological, consumers first: a rule's inputs and its tool are given by LATER rules, if by any.
+ * An item without a rule costs nothing to demand: the bound is weaker there, never wrong.
+ * Evaluation, in integers:
+ *     have[k] = inv[k] + (the cells of id k on the map, if bit k of map_items is set);   need[goal_item] = 1, every other need 0;   h = 0
+ *     for each rule in order:   d = max(0, need[out_item] - have[out_item]);   n = ceil(d / out_qty);   h += n * cost;
+ *                               need[in_item[i]] += n * in_qty[i];   if n > 0 and tool_item >= 0: need[tool_item] = max(need[tool_item], 1)
+ * with every product and sum taken in 64 bits, need saturating at 2^31 - 1 and h at NGW_VALUE_NONE - 1.
+ * ngw_snapshot_recipe_costs: out_dev[j] = h of row idx_dev[j] of `s` (NULL: the handle's current states; a NULL list: row j), count rows; one launch, no
+ * LDS staging of maps - every map size -, and a program without map_items reads no map at all.  NGW_IDX_NONE gives 0 silently, an index out of range
+ * 0 and NGW_F_BAD_INDEX.  Nothing is committed.
+ * ngw_search_set_recipe: an open-list search adds the term - h = min(recipe + walk, NGW_VALUE_NONE - 1) for every root and every child opened; the
+ * kernel runs once per ngw_search_start and once per iteration over the list the open step reads.  Legal only before the first ngw_search_start; the
+ * scratch (one int32 per list entry) is allocated here, ngw_search_run still allocates nothing.  Without the call a search computes what it always did.
+ * NGW_E_INVALID_ARG: a program that breaks a rule above; a search that is not an open-list one, or was started. */
+#define NGW_RECIPE_MAX_RULES 16
+#define NGW_RECIPE_MAX_INPUTS 4
+#define NGW_RECIPE_MAX_MAP_ITEMS 4
+typedef struct ngw_recipe_rule {
+    int32_t out_item, out_qty, cost, n_in;
+    int32_t in_item[NGW_RECIPE_MAX_INPUTS], in_qty[NGW_RECIPE_MAX_INPUTS];
+    int32_t tool_item;              /* -1: none */
+} ngw_recipe_rule;
+typedef struct ngw_recipe_program {
+    int32_t goal_item, n_rules;
+    uint32_t map_items;
+    int32_t reserved;
+    ngw_recipe_rule rules[NGW_RECIPE_MAX_RULES];
+} ngw_recipe_program;
+int ngw_snapshot_recipe_costs(ngw_handle* h, ngw_snapshot* s /* NULL: the current states */, const int32_t* idx_dev, int64_t count,
+                              const ngw_recipe_program* program, int32_t* out_dev);
+int ngw_search_set_recipe(ngw_handle* h, ngw_search* s, const ngw_recipe_program* program);
+
 /* Guided playouts: ngw_snapshot_playout_traj_views whose weights depend on the STATE - at every step the pair's current state is looked up in a key
  * table, and where the table holds it the choice is made under that bucket's row of the caller's weights.  The selection phase of MCTS (descend by
  * the tree's statistics while the node is in the tree), tabular Q / softmax policies, Go-Explore's "return, then explore" and playouts whose bias is
