@@ -35,6 +35,8 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_key_table_create_valued', 'ngw_key_table_insert_min', 'ngw_key_table_read', 'ngw_key_table_trace',
            'ngw_search_create', 'ngw_search_destroy', 'ngw_search_start', 'ngw_search_run', 'ngw_search_read', 'ngw_search_create_open', 'ngw_search_read_open',
            'ngw_snapshot_recipe_costs', 'ngw_search_set_recipe',
+           'ngw_tree_create', 'ngw_tree_destroy', 'ngw_tree_arrays', 'ngw_tree_start', 'ngw_tree_run', 'ngw_tree_grow', 'ngw_tree_backup', 'ngw_tree_reweight',
+           'ngw_tree_report', 'ngw_tree_clear',
            'ngw_snapshot_walk', 'ngw_frontier_compact', 'ngw_frontier_alloc', 'ngw_frontier_select', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
@@ -92,6 +94,29 @@ class RecipeRule(C.Structure):
 class RecipeProgram(C.Structure):
     """include/ngw.h ngw_recipe_program."""
     _fields_ = [('goal_item', C.c_int32), ('n_rules', C.c_int32), ('map_items', C.c_uint32), ('reserved', C.c_int32), ('rules', RecipeRule * RECIPE_MAX_RULES)]
+
+
+TREE_ROWS = 64        # include/ngw.h NGW_TREE_ROWS
+
+
+class TreeOptions(C.Structure):
+    """include/ngw.h ngw_tree_options."""
+    _fields_ = [('playouts', C.c_int64), ('steps', C.c_int32), ('fields', C.c_uint32), ('c', C.c_float), ('q_init', C.c_float), ('priors', C.c_int32),
+                ('plain_backup', C.c_int32), ('weights_host', C.c_void_p)]
+
+
+TREE_ARRAYS = ('visits', 'returns', 'mask_words', 'rows', 'priors', 'roots', 'actions', 'keys', 'rewards', 'masks', 'where', 'depth', 'length', 'ret', 'ended',
+               'info', 'leaf_keys', 'leaf_masks', 'where_leaf', 'fresh', 'touched')
+
+
+class TreeArrays(C.Structure):
+    """include/ngw.h ngw_tree_device_arrays."""
+    _fields_ = [(name, C.c_void_p) for name in TREE_ARRAYS] + [('buckets', C.c_int64), ('n_actions', C.c_int32), ('reserved', C.c_int32)]
+
+
+class TreeReport(C.Structure):
+    """include/ngw.h ngw_tree_report_rows."""
+    _fields_ = [('iterations', C.c_uint64), ('flags', C.c_uint32), ('rows', C.c_int32), ('stats', (C.c_uint32 * 5) * TREE_ROWS)]
 
 
 class NgwError(RuntimeError):
@@ -273,6 +298,17 @@ def lib():
     if hasattr(L, 'ngw_snapshot_recipe_costs'):
         L.ngw_snapshot_recipe_costs.argtypes = [vp, vp, vp, i64, C.POINTER(RecipeProgram), vp]
         L.ngw_search_set_recipe.argtypes = [vp, vp, C.POINTER(RecipeProgram)]
+    if hasattr(L, 'ngw_tree_create'):
+        L.ngw_tree_create.argtypes = [vp, vp, C.POINTER(TreeOptions), C.POINTER(vp)]
+        L.ngw_tree_destroy.argtypes = [vp, vp]
+        L.ngw_tree_arrays.argtypes = [vp, vp, C.POINTER(TreeArrays)]
+        L.ngw_tree_start.argtypes = [vp, vp, vp, vp, i64]
+        L.ngw_tree_run.argtypes = [vp, vp, i32, u64]
+        L.ngw_tree_grow.argtypes = [vp, vp, vp, vp, vp, vp, i64, i64, i32]
+        L.ngw_tree_backup.argtypes = [vp, vp, vp, vp, vp, vp, vp, i64, i64, i32, i32, vp]
+        L.ngw_tree_reweight.argtypes = [vp, vp, vp, i64]
+        L.ngw_tree_report.argtypes = [vp, vp, C.POINTER(TreeReport)]
+        L.ngw_tree_clear.argtypes = [vp, vp]
     if hasattr(L, 'ngw_snapshot_copy'):
         L.ngw_snapshot_copy.argtypes = [vp, vp, vp, vp, vp, i64]
     if hasattr(L, 'ngw_key_table_create'):

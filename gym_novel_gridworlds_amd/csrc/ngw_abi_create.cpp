@@ -604,6 +604,7 @@ int ngw_destroy(ngw_handle* h) {
     for (ngw_snapshot* s : h->snaps) delete s;                       // (their slabs were in `allocs`)
     for (ngw_key_table* t : h->tables) delete t;                     // (likewise)
     for (ngw_search* s : h->searches) delete s;                      // (likewise)
+    for (ngw_tree* t : h->trees) delete t;                           // (likewise)
     for (void* p : h->host_allocs) (void)hipHostFree(p);
     drop_graph(h);
     if (h->info_host) (void)hipHostFree(h->info_host);

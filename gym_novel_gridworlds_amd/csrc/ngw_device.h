@@ -1082,4 +1082,55 @@ extern "C"
 #endif
 hipError_t ngw_recipe_launch(const struct NgwRecipe* x, hipStream_t stream);
 
+/* Tree-search runs (ngw_tree.inc, ngw_abi_tree.cpp; the contract is include/ngw.h's ngw_tree_run): what the four kernels between a guided playout
+ * and the table's insert read and write.  The statistics are [buckets][A] (visits int32, returns int64, rows and priors float32) and [buckets] (the
+ * mask words); the recorded arrays of the playout are step-major, row t at t * stride; `touched` is the tree's own, step-major [T][cap].
+ *   leaf      one lane per pair j < count: d = depth[j]; 1 <= d < length[j] (and d < n): leaf_keys[j] = keys[d - 1][j], leaf_masks[j] = masks[d][j];
+ *             otherwise both 0.  Counts the pairs with length >= 1 and the largest depth into `row`, zero-fills `next_row`.
+ *   grow      one lane per pair: w = where_leaf[j] in [0, buckets): mask_words[w] = leaf_masks[j] where that word is not 0 (equal states store equal words).  Counts
+ *             fresh[j] != 0 and the refusals (leaf_keys[j] != 0 with w < 0) into `row`.
+ *   backup    one lane per pair, j < cap: t from T - 1 down to 0, G += rewards[t][j] for t < n (bootstrap[j] first); for t <= min(d, length - 1), d >=
+ *             1: the bucket e = where[t][j] (t < d) or where_leaf[j] (t == d; none without where_leaf) and a = actions[t][j]; e in [0, buckets) and a
+ *             in [0, A): visits[e][a] += 1, returns[e][a] += G - integer atomics, combined inside the wave where `combine` is set - and touched[t][j]
+ *             = e; -1 everywhere else, also for the lanes count <= j < cap.  Counts the adds into `row`.
+ *   reweight  one lane per entry q < n_list of `list`: the bucket e = list[q] in [0, buckets) - unless the lane before it in the wave names the same -
+ *             gets its row by the PUCT rule of include/ngw.h.  A bad prior raises NGW_F_BAD_WEIGHT in *flags.
+ * No index becomes an address before it is checked against buckets, A, count and cap.  `row` / `next_row` NULL: nothing is counted. */
+struct NgwTree {
+    int32_t* visits;
+    unsigned long long* returns;
+    uint64_t* mask_words;
+    float* rows;
+    const float* priors;            /* NULL: every prior is 1 */
+    const int32_t *actions, *rewards, *where, *depth, *length;
+    const int32_t* bootstrap;       /* NULL: none */
+    const uint64_t *keys, *masks;
+    uint64_t *leaf_keys, *leaf_masks;
+    int32_t* where_leaf;            /* backup: NULL = no pair has a leaf */
+    const uint8_t* fresh;
+    int32_t* touched;
+    const int32_t* list;
+    uint32_t *row, *next_row, *flags;
+    int64_t count, cap, stride, buckets, n_list;
+    int32_t T, n, A, combine;       /* T: the tree's steps (rows of `touched`); n <= T: the steps of the recorded arrays */
+    float c, q_init;
+};
+#define NGW_TREE_BLOCK 256       /* threads per workgroup: four waves, one entry per lane */
+#define NGW_TREE_COLS 8          /* uint32 per stats row */
+#define NGW_TREE_ALIVE 0
+#define NGW_TREE_GROWN 1
+#define NGW_TREE_REFUSED 2
+#define NGW_TREE_BACKED 3
+#define NGW_TREE_DEPTH 4
+#ifdef __cplusplus
+extern "C" {
+#endif
+hipError_t ngw_tree_leaf_launch(const struct NgwTree* x, hipStream_t stream);
+hipError_t ngw_tree_grow_launch(const struct NgwTree* x, hipStream_t stream);
+hipError_t ngw_tree_backup_launch(const struct NgwTree* x, hipStream_t stream);
+hipError_t ngw_tree_reweight_launch(const struct NgwTree* x, hipStream_t stream);
+#ifdef __cplusplus
+}
+#endif
+
 #endif

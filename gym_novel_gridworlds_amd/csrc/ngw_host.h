@@ -16,6 +16,9 @@
 //   ngw_abi_search.cpp   search runs: the driver that enqueues whole best-first iterations - the five stages above through their own entry points, the three
 //                        kernels of ngw_search.inc between them
 //   ngw_host_recipe.cpp  the recipe heuristic (ngw_recipe.inc): program checks and the launch, behind ngwh::recipe_hooks (below) - not an ngw_abi_ unit
+//   ngw_abi_tree.cpp     tree-search runs: the ngw_tree_* entry points and the driver that enqueues whole MCTS iterations - the guided playout and the
+//                        table's insert through their own entry points, the four kernels of ngw_tree.inc between them, reached through ngwh::tree_hooks
+//   ngw_host_tree.cpp    the launches of those four kernels, behind ngwh::tree_hooks (below) - not an ngw_abi_ unit either
 //
 // Three rules hold in all of them:
 //   1. Guard first.  An entry point that uses the handle's stream or its device state starts with `if (int rc = enter(h)) return rc;`
@@ -55,6 +58,11 @@ typedef int (*RecipePack)(const ngw_handle* h, const ngw_recipe_program* in, Ngw
 typedef int (*RecipeRun)(ngw_handle* h, hipStream_t stream, const NgwSnapRows& src, int64_t rows, const int32_t* idx_dev, int64_t count, const NgwRecipeProg& prog, int32_t* out_dev);
 struct RecipeHooks { RecipePack pack = nullptr; RecipeRun run = nullptr; };
 extern RecipeHooks recipe_hooks;                    // ngw_abi_create.cpp, beside fail(); called behind enter() like any other use of the handle
+// The same for the tree-search kernels (ngw_tree.inc): ngw_host_tree.cpp alone names their launchers and fills these pointers when the library is
+// loaded; ngw_abi_tree.cpp launches through them, behind enter(), and refuses every ngw_tree_* call while they are empty.
+typedef hipError_t (*TreeLaunch)(const NgwTree* x, hipStream_t stream);
+struct TreeHooks { TreeLaunch leaf = nullptr, grow = nullptr, backup = nullptr, reweight = nullptr; };
+extern TreeHooks tree_hooks;                        // ngw_abi_tree.cpp
 }
 
 #define HIP_TRY(expr)                                                                                   \
@@ -123,6 +131,27 @@ struct ngw_search {
     ngwh::RecipeRun recipe_run = nullptr;
     int32_t* recipe = nullptr;
     NgwRecipeProg recipe_prog{};
+};
+
+// A tree-search run (ngw_abi_tree.cpp): the table it keeps statistics for and the source of its roots - looked up by address in the handle's lists
+// before every use, never dereferenced first -, and ONE allocation of its handle that holds every array: the statistics per bucket, the recorded
+// arrays of an iteration's playout, the leaves and the stats ring.
+struct ngw_tree {
+    ngw_key_table* table = nullptr;
+    ngw_snapshot* src = nullptr;          // where the roots live (ngw_tree_start); NULL: the envs' current states
+    int64_t cap = 0, buckets = 0, n_roots = 0;   // cap: playouts per iteration
+    int32_t T = 0, A = 0, combine = 1;
+    uint32_t fields = 0;
+    float c = 0, q_init = 0;
+    uint64_t iterations = 0;              // since creation or the last clear
+    uint64_t* slab = nullptr;
+    unsigned long long* returns = nullptr;                      // [buckets][A]
+    uint64_t *mask_words = nullptr, *keys = nullptr, *masks = nullptr, *leaf_keys = nullptr, *leaf_masks = nullptr;
+    int32_t *visits = nullptr, *actions = nullptr, *rewards = nullptr, *where = nullptr, *touched = nullptr;
+    int32_t *depth = nullptr, *length = nullptr, *ret = nullptr, *first_action = nullptr, *where_leaf = nullptr, *roots = nullptr, *start_actions = nullptr;
+    uint32_t *info = nullptr, *stats = nullptr;   // stats: [NGW_TREE_ROWS + 1][NGW_TREE_COLS], rows as in ngw_search
+    float *rows = nullptr, *priors = nullptr, *zero_weights = nullptr, *weights = nullptr;   // zero_weights [A][cap]: never written; weights [A]: the default policy's, or NULL
+    uint8_t *ended = nullptr, *fresh = nullptr;
 };
 
 struct ngw_handle {
@@ -280,6 +309,7 @@ struct ngw_handle {
     std::vector<ngw_snapshot*> snaps;     // open snapshots (ngw_snapshot_create); their slabs are in `allocs`, ngw_destroy deletes what is left
     std::vector<ngw_key_table*> tables;   // open key tables (ngw_key_table_create); likewise
     std::vector<ngw_search*> searches;    // open search runs (ngw_search_create); likewise
+    std::vector<ngw_tree*> trees;         // open tree-search runs (ngw_tree_create); likewise
     // Frontiers (ngw_abi_frontier.cpp): the scratch of ngw_frontier_compact / ngw_frontier_alloc, allocated on first use and regrown when a call
     // brings more tiles - word 0 the allocation's ticket (0 between the calls), the tile counts behind it
     int32_t* frontier_scratch = nullptr;

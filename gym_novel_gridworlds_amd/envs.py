@@ -354,6 +354,23 @@ class _NovelGridworldEnv(_EnvBase):
         """A device-side key table of this env's batched backend (VecNovelGridworld.key_table): what playouts(table=...) takes."""
         return self._backend().key_table(capacity, values, **kw)
 
+    def tree_search(self, table, playouts, steps, **kw):
+        """A TreeSearch (tree.py) over `table` (key_table()) rooted in this env's CURRENT state: `playouts` pairs per iteration, all from it -
+        Snapshot.tree_search on a snapshot of this env's batched backend, started with from_envs=True.  Attributes the caller edited since the
+        last step go to the device first.  After a step(), t.start(np.zeros(playouts, np.int32), from_envs=True) re-roots it and keeps the
+        statistics.  It lives as long as the backend does (until close(), or until the adapter's backend is rebuilt)."""
+        vec = self._backend()
+        self._push(vec)
+        snap = vec.snapshot(1)
+        try:
+            t = snap.tree_search(table, playouts, steps, **kw)
+        except Exception:
+            snap.close()
+            raise
+        t.owns_snapshot = True                               # (t.close() closes the snapshot made for it)
+        t.start(np.zeros(int(playouts), np.int32), from_envs=True)
+        return t
+
     def state_key(self, fields=KEY_STATE):
         """The 64-bit key of the current state as a Python int, computed on the device under the field selection `fields` (KEY_* bits,
         default KEY_STATE); see VecNovelGridworld.state_keys and state_keys.py for the contract."""

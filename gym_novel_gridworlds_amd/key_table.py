@@ -396,7 +396,9 @@ class KeyTable:
         return int(n.value)
 
     def clear(self):
-        """Empties the table, values and tags included (on the env's stream; no host wait).  Buckets reported earlier mean nothing afterwards."""
+        """Empties the table, values and tags included (on the env's stream; no host wait).  Buckets reported earlier mean nothing afterwards.
+        It does NOT clear the statistics a TreeSearch keeps per bucket of this table (visits, returns, mask words, rows): TreeSearch.clear()
+        clears both."""
         _cabi.check(_cabi.lib().ngw_key_table_clear(self.env._h, self._open()))
 
     @property

@@ -1074,6 +1074,22 @@ class Snapshot:
         self.__dict__.setdefault('_searches', []).append(s)
         return s
 
+    # ------------------------------------------------------------------ device-side tree-search runs (include/ngw.h ngw_tree_*; tree.py)
+    def tree_search(self, table, playouts, steps, c=1.0, q_init=0.0, priors=False, weights=None, fields=KEY_STATE, plain_backup=False):
+        """A TreeSearch over `table` (a KeyTable of the same env) rooted in this snapshot's slots - or, with start(from_envs=True), in the envs'
+        current states -: whole MCTS iterations of `playouts` pairs and `steps` steps each - a guided playout, the new leaves inserted, an
+        integer every-visit backup, the PUCT rows recomputed under each node's valid-action mask -, enqueued from one call with no host wait in
+        between; it keeps visit counts, return sums and mask words per bucket of the table (tree.py says what an iteration is).  c, q_init: the
+        PUCT rule's; priors=True: a [buckets, A] tensor of priors for the caller to fill; weights: the default policy's, None: uniform; fields:
+        the KEY_* selection of a node.  ValueError for a table of another env, playouts * steps or buckets * A beyond 2^31 - 1, fields == 0, a c
+        or q_init that is not finite; maps beyond the keyed guided playout's limit raise what playout(table=) raises.  Closed by its close()
+        and with this snapshot."""
+        from .tree import TreeSearch
+        self._open()
+        t = TreeSearch(self, table, playouts, steps, c, q_init, priors, weights, fields, plain_backup)
+        self.__dict__.setdefault('_searches', []).append(t)
+        return t
+
     def state(self, first=0, count=None):
         """The saved states of `count` slots from `first`, as get_state() returns them (a never-saved slot: zeros, agent at (1, 1))."""
         self._open()

@@ -1292,6 +1292,100 @@ int ngw_snapshot_playout_guided(ngw_handle* h, ngw_snapshot* src, const int32_t*
                                 int64_t obs_stride, const ngw_traj_views* views /* NULL: no views */, ngw_key_table* table, const float* table_weights_dev,
                                 int32_t* where_dev, int64_t where_stride, int32_t* depth_dev, int32_t outside);
 
+/* Tree-search runs: whole MCTS iterations - descend, simulate, expand one node, back up, reweight - over one key table, enqueued from ONE call with
+ * no host wait and no work of the caller in between: the Monte-Carlo twin of ngw_search_run.  A tree keeps, per bucket b of its table and action a,
+ *   visits[b][a]   int32     returns[b][a]  int64     rows[b][a]  float32 (the table_weights of its guided playouts)     priors[b][a]  float32 (optional)
+ * and mask_words[b] (uint64; 0: never learned), all in ONE device allocation with the recorded arrays of an iteration's playout (`playouts` pairs of
+ * `steps` = T steps).  The statistics are INTEGERS so that every sum is an integer addition: the result of a backup does not depend on the order the
+ * device runs the adds in, nor on how they are combined on the way - which float sums (index_add_) do.  Every byte below is a public contract;
+ * tree.py states it in numpy.
+ *   iteration `it` (a 64-bit count since ngw_tree_create or ngw_tree_clear), with the current root list R (count pairs, count <= playouts):
+ *     1. ngw_snapshot_playout_guided(src, R, count, n_steps = T, seed, first_pair = it * playouts, weights_dev = the tree's default-policy weights or
+ *        NULL, table, table_weights_dev = rows, outside = NGW_OUTSIDE_DEFAULT), recording actions, path keys under `fields`, rewards, mask words,
+ *        where and depth (stride `playouts`), through that entry point, unchanged.  The draws depend on (seed, it, j, t) and the state alone, so
+ *        ngw_tree_run(4, seed) and four calls of ngw_tree_run(1, seed) leave identical statistics for every key, and identical bytes everywhere the
+ *        table gives the keys the same buckets (two tables need not: ngw_key_table_insert leaves the bucket of colliding keys open).
+ *     2. leaf: d = depth[j].  1 <= d < length[j]: leaf_keys[j] = keys[d - 1][j] - the first state of the pair the table does not hold - and
+ *        leaf_masks[j] = masks[d][j], the word the default policy's draw at that state was made under.  Otherwise no leaf: key 0, mask 0.  d = 0: the
+ *        root is not in the table (never started, or refused by a full table): the pair neither grows nor backs up.
+ *     3. expand: ngw_key_table_insert(leaf_keys) -> where_leaf, fresh, through that entry point.  where_leaf[j] >= 0: mask_words[where_leaf[j]] =
+ *        leaf_masks[j] (a leaf mask is never 0; a word of 0 - a root that was skipped - is not stored); equal states write equal words, so the race is benign and the result deterministic.  The statistics of a fresh bucket are 0
+ *        (ngw_tree_create and ngw_tree_clear zero them).  A full table raises NGW_F_TABLE_FULL from the insert, as always; that pair does not grow.
+ *     4. back up, every-visit, undiscounted: the bucket of step t of pair j is e = where[t][j] for t < d, where_leaf[j] for t == d, none for t > d
+ *        (steps beyond the leaf are the default policy's, even where the walk re-enters the table).  For every executed step t <= d with e >= 0
+ *        and a = actions[t][j]: visits[e][a] += 1 and returns[e][a] += G_t, G_t = the sum of rewards[u][j] over u >= t (+ bootstrap[j] where
+ *        ngw_tree_backup was given one), as an int32 and an int64 two's-complement addition.
+ *     5. reweight every bucket b touched in 3 or 4 (every other row keeps its bytes; the rule applied to an untouched row gives the bytes it has):
+ *        m = mask_words[b]; n_b = the sum of visits[b][.] in 64 bits; in IEEE binary32, every operation rounded to nearest even on its own, none
+ *        fused, integers converted to binary32 round-to-nearest-even:
+ *            q[a] = float(returns[b][a]) / float(visits[b][a]) where visits[b][a] > 0, else q_init
+ *            u[a] = ((c * p[a]) * sqrt(float(n_b + 1))) / float(1 + visits[b][a])        score[a] = q[a] + u[a]
+ *        p[a] = 1 without priors, else priors[b][a] cleaned by rule 3 of ngw_sample_actions (outside [2^-64, 2^64]: +0; negative, NaN or above 2^64
+ *        raises NGW_F_BAD_WEIGHT, valid action or not).  The row is 1.0f at the action chosen by: pick = none; for a = 0 .. A-1 in order: bit a of m
+ *        set and (pick is none or score[a] > score[pick]) -> pick = a - the valid action of the largest score, the lowest id on ties -, 0.0f
+ *        elsewhere; m == 0: an all-zero row, which the playout treats as the uniform rule.  A one-hot row on a valid action makes rules 3 - 6 of
+ *        ngw_sample_actions pick that action with certainty, for every Philox word: v is 0 before it, so the first a with v[a] > 0 and c[a] = 1 >
+ *        thr is it, and thr = u * 1 < 1 always - also in the corner w = 0, where thr = 0 and the comparison c[a] > thr is strict.
+ *   create   the checks, the allocation (zero-filled) and the default-policy weights (weights_host: NULL or n_actions float32, copied).
+ *   arrays   the device pointers: the statistics (the caller reads them and fills priors) and the recorded arrays of the last iteration.  Waits for the
+ *            stream once, so that what the caller then writes (priors) cannot be overtaken by the allocation's zero-fill.
+ *   start    the roots: slots of `src` (NULL: the envs' current states), DEVICE memory, count <= playouts, NGW_IDX_NONE allowed (skipped).  Their keys
+ *            under `fields` (ngw_state_keys) are inserted, their mask words learned - the word ngw_sample_actions reports for the row: rule 1's m -,
+ *            and their rows written by rule 5.  visits and returns of a state the table already held are kept: re-rooting after a committed step
+ *            keeps the statistics.  R becomes these roots.
+ *   run      `iterations` iterations.  It allocates nothing, waits for nothing, and looks the table and the source up in the handle's lists before
+ *            every iteration.
+ *   grow / backup / reweight   the stages on their own, over the caller's arrays of a guided playout (step-major, stride `stride`, n_steps <= T, count
+ *            <= playouts): grow = 2 and 3 (the leaves stay in the tree's where_leaf); backup = 4 with e of step d taken from where_leaf when
+ *            use_leaves != 0 (else no pair has a leaf) and an optional int32 bootstrap [count]; reweight = 5 for a list of buckets (NULL: the buckets
+ *            the last backup touched; -1 and NGW_IDX_NONE entries are skipped, any other entry outside [0, buckets) too).  They count nothing into
+ *            the report and do not advance `it`.
+ *   report   waits for the stream: the iterations run, the handle's sticky flags (not cleared) and, for the last `rows` = min(iterations, 64)
+ *            iterations, oldest first: pairs alive (length >= 1), nodes grown (fresh), insertions refused (a leaf key without a bucket), steps backed
+ *            up, the largest depth.
+ *   clear    ngw_key_table_clear, the statistics, mask words, rows and the report zeroed, `it` = 0, no roots.  ngw_key_table_clear alone does NOT
+ *            clear the statistics: the buckets' rows then describe keys the table no longer holds.  priors are the caller's and stay.
+ * Nothing is committed, as for the guided playout.  Every launch is enqueued on the handle's stream.  A tree is rank-local.
+ * NGW_E_INVALID_ARG: a NULL argument; a table (or a source) that is not open on this handle, also when it was closed since; playouts < 1, steps < 1,
+ * playouts * steps > 2^31 - 1; buckets * n_actions > 2^31 - 1; fields == 0 or a bit outside NGW_KEY_ALL; c or q_init not finite; maps beyond the keyed
+ * guided playout's limit (its message, "map_size ..."); count outside [0, playouts]; n_steps outside [1, steps]; stride < count; iterations < 0. */
+typedef struct ngw_tree ngw_tree;
+typedef struct ngw_tree_options {
+    int64_t playouts;
+    int32_t steps;
+    uint32_t fields;
+    float c, q_init;
+    int32_t priors;                 /* != 0: the tree holds priors[buckets][A] (zero-filled: fill them before they are read) */
+    int32_t plain_backup;           /* != 0: the backup adds lane by lane, without combining inside the wave (the same bytes; for A/B timing) */
+    const float* weights_host;      /* NULL: states outside the table draw uniformly */
+} ngw_tree_options;
+typedef struct ngw_tree_device_arrays {
+    void *visits, *returns, *mask_words, *rows, *priors;      /* priors NULL without them */
+    void *roots, *actions, *keys, *rewards, *masks, *where, *depth, *length, *ret, *ended, *info;
+    void *leaf_keys, *leaf_masks, *where_leaf, *fresh, *touched;
+    int64_t buckets;
+    int32_t n_actions, reserved;
+} ngw_tree_device_arrays;
+#define NGW_TREE_ROWS 64
+typedef struct ngw_tree_report_rows {
+    uint64_t iterations;
+    uint32_t flags;
+    int32_t rows;
+    uint32_t stats[NGW_TREE_ROWS][5];   /* alive, grown, refused, backed up, largest depth */
+} ngw_tree_report_rows;
+int ngw_tree_create(ngw_handle* h, ngw_key_table* table, const ngw_tree_options* options, ngw_tree** out);
+int ngw_tree_destroy(ngw_handle* h, ngw_tree* t);
+int ngw_tree_arrays(ngw_handle* h, ngw_tree* t, ngw_tree_device_arrays* out);
+int ngw_tree_start(ngw_handle* h, ngw_tree* t, ngw_snapshot* src /* NULL: the current states */, const int32_t* roots_dev, int64_t count);
+int ngw_tree_run(ngw_handle* h, ngw_tree* t, int32_t iterations, uint64_t seed);
+int ngw_tree_grow(ngw_handle* h, ngw_tree* t, const int32_t* depth_dev, const int32_t* length_dev, const uint64_t* keys_dev, const uint64_t* masks_dev,
+                  int64_t stride, int64_t count, int32_t n_steps);
+int ngw_tree_backup(ngw_handle* h, ngw_tree* t, const int32_t* actions_dev, const int32_t* rewards_dev, const int32_t* where_dev, const int32_t* depth_dev,
+                    const int32_t* length_dev, int64_t stride, int64_t count, int32_t n_steps, int32_t use_leaves, const int32_t* bootstrap_dev);
+int ngw_tree_reweight(ngw_handle* h, ngw_tree* t, const int32_t* buckets_dev /* NULL: what the last backup touched */, int64_t count);
+int ngw_tree_report(ngw_handle* h, ngw_tree* t, ngw_tree_report_rows* out);
+int ngw_tree_clear(ngw_handle* h, ngw_tree* t);
+
 /* One-step lookahead tables: every action's outcome for every env, without taking a step.
  * For a handle with A = n_actions the table of the CURRENT state is three arrays - reward int32, done uint8, info uint32 (the NGW_INFO_* packing).
  * Entry (i, a) holds exactly what ngw_get_step_out would report for env i if ngw_step_device were called now with action a for that env, under
