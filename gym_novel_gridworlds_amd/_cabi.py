@@ -36,7 +36,7 @@ SYMBOLS = ['ngw_abi_version', 'ngw_spec_size', 'ngw_last_error', 'ngw_device_cou
            'ngw_search_create', 'ngw_search_destroy', 'ngw_search_start', 'ngw_search_run', 'ngw_search_read', 'ngw_search_create_open', 'ngw_search_read_open',
            'ngw_snapshot_recipe_costs', 'ngw_search_set_recipe',
            'ngw_tree_create', 'ngw_tree_destroy', 'ngw_tree_arrays', 'ngw_tree_start', 'ngw_tree_run', 'ngw_tree_grow', 'ngw_tree_backup', 'ngw_tree_reweight',
-           'ngw_tree_report', 'ngw_tree_clear',
+           'ngw_tree_report', 'ngw_tree_clear', 'ngw_tree_set_rule',
            'ngw_snapshot_walk', 'ngw_frontier_compact', 'ngw_frontier_alloc', 'ngw_frontier_select', 'ngw_lookahead', 'ngw_get_lookahead', 'ngw_lookahead_device_ptrs',
            'ngw_plan_eval', 'ngw_get_plan_eval', 'ngw_plan_eval_device_ptrs']
 
@@ -112,6 +112,11 @@ TREE_ARRAYS = ('visits', 'returns', 'mask_words', 'rows', 'priors', 'roots', 'ac
 class TreeArrays(C.Structure):
     """include/ngw.h ngw_tree_device_arrays."""
     _fields_ = [(name, C.c_void_p) for name in TREE_ARRAYS] + [('buckets', C.c_int64), ('n_actions', C.c_int32), ('reserved', C.c_int32)]
+
+
+class TreeRule(C.Structure):
+    """include/ngw.h ngw_tree_rule."""
+    _fields_ = [('spread', C.c_int32), ('discount_q16', C.c_int32), ('rows16', C.c_int32), ('reserved', C.c_int32)]
 
 
 class TreeReport(C.Structure):
@@ -309,6 +314,8 @@ def lib():
         L.ngw_tree_reweight.argtypes = [vp, vp, vp, i64]
         L.ngw_tree_report.argtypes = [vp, vp, C.POINTER(TreeReport)]
         L.ngw_tree_clear.argtypes = [vp, vp]
+    if hasattr(L, 'ngw_tree_set_rule'):
+        L.ngw_tree_set_rule.argtypes = [vp, vp, C.POINTER(TreeRule)]
     if hasattr(L, 'ngw_snapshot_copy'):
         L.ngw_snapshot_copy.argtypes = [vp, vp, vp, vp, vp, i64]
     if hasattr(L, 'ngw_key_table_create'):

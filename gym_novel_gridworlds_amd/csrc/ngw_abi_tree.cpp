@@ -1,8 +1,8 @@
 // ngw_abi_tree.cpp - tree-search runs (see ngw_host.h): whole MCTS iterations over one key table, enqueued from one call.  This unit names no
-// launcher of ngw_tree.inc: the four kernels are reached through ngwh::tree_hooks, which ngw_host_tree.cpp - the only host unit that names them -
+// launcher of ngw_tree.inc: the six kernels are reached through ngwh::tree_hooks, which ngw_host_tree.cpp - the only host unit that names them -
 // fills when the library is loaded, so the ngw_abi_ units link with or without it (without: every ngw_tree_* call is refused).  The
 // driver owns no stage of the playout or the table: the guided playout, the insert, the state keys and the mask words run through their own entry
-// points (ngw_abi_snapshot.cpp, ngw_abi_table.cpp), called as any caller calls them, with the four kernels of ngw_tree.inc between them.  The
+// points (ngw_abi_snapshot.cpp, ngw_abi_table.cpp), called as any caller calls them, with the kernels of ngw_tree.inc between them.  The
 // calls write no env state: they neither call state_written() nor touch anything the handle derives from its state.  All run on the handle's
 // stream, behind enter(); only ngw_tree_report waits.
 #include "ngw_host.h"
@@ -51,9 +51,9 @@ int run_parts(const ngw_handle* h, const ngw_tree* t) {
     return NGW_OK;
 }
 
-bool hooked() { return tree_hooks.leaf && tree_hooks.grow && tree_hooks.backup && tree_hooks.reweight; }
+bool hooked() { return tree_hooks.leaf && tree_hooks.grow && tree_hooks.backup && tree_hooks.reweight && tree_hooks.backup_discount && tree_hooks.reweight16; }
 
-// what the four kernels share: the statistics and the sizes
+// what the kernels share: the statistics and the sizes
 NgwTree tree_args(const ngw_handle* h, const ngw_tree* t) {
     NgwTree x{};
     x.visits = t->visits; x.returns = t->returns; x.mask_words = t->mask_words; x.rows = t->rows; x.priors = t->priors;
@@ -86,9 +86,20 @@ int grow(ngw_handle* h, ngw_tree* t, const NgwTree& x) {
     return NGW_OK;
 }
 
-int reweight(ngw_handle* h, NgwTree x, const int32_t* list, int64_t n) {
+// rule 4: the undiscounted kernel, or under a discount its twin
+int backup(ngw_handle* h, const ngw_tree* t, const NgwTree& x) {
+    const NgwTreeRule rule{t->spread, t->discount_q16};
+    if (t->discount_q16 != 65536) HIP_TRY(tree_hooks.backup_discount(&x, &rule, h->stream));
+    else HIP_TRY(tree_hooks.backup(&x, h->stream));
+    return NGW_OK;
+}
+
+// rule 5: the one-lane kernel, or the 16-lane form - for every spread above 1, and at spread 1 where the rule asks for it (rows16 = 1)
+int reweight(ngw_handle* h, const ngw_tree* t, NgwTree x, const int32_t* list, int64_t n) {
     x.list = list; x.n_list = n;
-    HIP_TRY(tree_hooks.reweight(&x, h->stream));
+    const NgwTreeRule rule{t->spread, t->discount_q16};
+    if (t->spread > 1 || t->rows16 == 1) HIP_TRY(tree_hooks.reweight16(&x, &rule, h->stream));
+    else HIP_TRY(tree_hooks.reweight(&x, h->stream));
     return NGW_OK;
 }
 
@@ -97,8 +108,8 @@ int iterate(ngw_handle* h, ngw_tree* t, uint64_t seed) {
     const NgwTree x = run_args(h, t);
     if (int rc = playout(h, t, t->n_roots, seed, t->iterations * (uint64_t)t->cap)) return rc;
     if (int rc = grow(h, t, x)) return rc;
-    HIP_TRY(tree_hooks.backup(&x, h->stream));
-    if (int rc = reweight(h, x, t->touched, (int64_t)t->T * t->cap)) return rc;
+    if (int rc = backup(h, t, x)) return rc;
+    if (int rc = reweight(h, t, x, t->touched, (int64_t)t->T * t->cap)) return rc;
     t->iterations++;
     return NGW_OK;
 }
@@ -227,7 +238,7 @@ int ngw_tree_start(ngw_handle* h, ngw_tree* t, ngw_snapshot* src, const int32_t*
     NgwTree x = tree_args(h, t);
     x.count = count; x.stride = t->cap;
     HIP_TRY(tree_hooks.grow(&x, h->stream));
-    return reweight(h, x, t->where_leaf, count);
+    return reweight(h, t, x, t->where_leaf, count);
 }
 
 int ngw_tree_run(ngw_handle* h, ngw_tree* t, int32_t iterations, uint64_t seed) {
@@ -272,8 +283,7 @@ int ngw_tree_backup(ngw_handle* h, ngw_tree* t, const int32_t* actions_dev, cons
     x.actions = actions_dev; x.rewards = rewards_dev; x.where = where_dev; x.depth = depth_dev; x.length = length_dev; x.bootstrap = bootstrap_dev;
     x.count = count; x.stride = stride; x.n = n_steps;
     if (!use_leaves) x.where_leaf = nullptr;
-    HIP_TRY(tree_hooks.backup(&x, h->stream));
-    return NGW_OK;
+    return backup(h, t, x);
 }
 
 int ngw_tree_reweight(ngw_handle* h, ngw_tree* t, const int32_t* buckets_dev, int64_t count) {
@@ -281,8 +291,23 @@ int ngw_tree_reweight(ngw_handle* h, ngw_tree* t, const int32_t* buckets_dev, in
     if (count < 0 || count > 0x7FFFFFFFll) return fail(NGW_E_INVALID_ARG, "a list of %lld buckets", (long long)count);
     if (int rc = enter(h)) return rc;
     const NgwTree x = tree_args(h, t);
-    if (!buckets_dev) return reweight(h, x, t->touched, (int64_t)t->T * t->cap);
-    return reweight(h, x, buckets_dev, count);
+    if (!buckets_dev) return reweight(h, t, x, t->touched, (int64_t)t->T * t->cap);
+    return reweight(h, t, x, buckets_dev, count);
+}
+
+int ngw_tree_set_rule(ngw_handle* h, ngw_tree* t, const ngw_tree_rule* rule) {
+    if (!h || !t || !rule) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (int rc = tree_call_args(h, t)) return rc;
+    if (rule->spread < 1 || rule->spread > 64) return fail(NGW_E_INVALID_ARG, "tree rule: spread = %d outside [1, 64]", (int)rule->spread);
+    if (rule->discount_q16 < 0 || rule->discount_q16 > 65536) return fail(NGW_E_INVALID_ARG, "tree rule: discount_q16 = %d outside [0, 65536]", (int)rule->discount_q16);
+    if (rule->rows16 < 0 || rule->rows16 > 2) return fail(NGW_E_INVALID_ARG, "tree rule: rows16 = %d outside [0, 2]", (int)rule->rows16);
+    if (rule->rows16 == 2 && rule->spread > 1) return fail(NGW_E_INVALID_ARG, "tree rule: rows16 = 2 (the one-lane reweight) serves spread = 1 only, not %d", (int)rule->spread);
+    if (rule->reserved != 0) return fail(NGW_E_INVALID_ARG, "tree rule: reserved = %d, 0 expected", (int)rule->reserved);
+    if (int rc = enter(h)) return rc;
+    // the list of the last backup is forgotten, in stream order: ngw_tree_reweight(NULL) never rewrites rows under a rule their backup did not run under
+    HIP_TRY(hipMemsetAsync(t->touched, 0xFF, (size_t)t->T * (size_t)t->cap * 4, h->stream));
+    t->spread = rule->spread; t->discount_q16 = rule->discount_q16; t->rows16 = rule->rows16;   // (host state, read by the calls enqueued from here on)
+    return NGW_OK;
 }
 
 int ngw_tree_report(ngw_handle* h, ngw_tree* t, ngw_tree_report_rows* out) {

@@ -1095,6 +1095,9 @@ hipError_t ngw_recipe_launch(const struct NgwRecipe* x, hipStream_t stream);
  *             = e; -1 everywhere else, also for the lanes count <= j < cap.  Counts the adds into `row`.
  *   reweight  one lane per entry q < n_list of `list`: the bucket e = list[q] in [0, buckets) - unless the lane before it in the wave names the same -
  *             gets its row by the PUCT rule of include/ngw.h.  A bad prior raises NGW_F_BAD_WEIGHT in *flags.
+ *   reweight16  the same list, one entry per 16 lanes (lane l holds the actions l, l + 16, l + 32): the row by the spread rule with S = `spread` in
+ *             [1, 64] - at S = 1 the bytes of `reweight`; an entry equal to the entry before it in the list is skipped.
+ *   backup with g != 65536: G_t = rewards[t][j] + ((g * G_{t+1}) >> 16) for the executed steps t < length, in int64; the steps behind them add as before.
  * No index becomes an address before it is checked against buckets, A, count and cap.  `row` / `next_row` NULL: nothing is counted. */
 struct NgwTree {
     int32_t* visits;
@@ -1115,7 +1118,10 @@ struct NgwTree {
     int32_t T, n, A, combine;       /* T: the tree's steps (rows of `touched`); n <= T: the steps of the recorded arrays */
     float c, q_init;
 };
-#define NGW_TREE_BLOCK 256       /* threads per workgroup: four waves, one entry per lane */
+/* The rule of ngw_tree_set_rule, a second argument of the two kernels that read it - NgwTree keeps its layout, so the four kernels above compile to the
+ * code they were: spread = S of the spread rule (reweight16), g = discount_q16 of the backup (65536: none, the undiscounted kernel runs). */
+struct NgwTreeRule { int32_t spread, g; };
+#define NGW_TREE_BLOCK 256       /* threads per workgroup: four waves, one entry per lane (reweight16: one entry per 16 lanes) */
 #define NGW_TREE_COLS 8          /* uint32 per stats row */
 #define NGW_TREE_ALIVE 0
 #define NGW_TREE_GROWN 1
@@ -1128,7 +1134,9 @@ extern "C" {
 hipError_t ngw_tree_leaf_launch(const struct NgwTree* x, hipStream_t stream);
 hipError_t ngw_tree_grow_launch(const struct NgwTree* x, hipStream_t stream);
 hipError_t ngw_tree_backup_launch(const struct NgwTree* x, hipStream_t stream);
+hipError_t ngw_tree_backup_discount_launch(const struct NgwTree* x, const struct NgwTreeRule* r, hipStream_t stream);
 hipError_t ngw_tree_reweight_launch(const struct NgwTree* x, hipStream_t stream);
+hipError_t ngw_tree_reweight16_launch(const struct NgwTree* x, const struct NgwTreeRule* r, hipStream_t stream);
 #ifdef __cplusplus
 }
 #endif

@@ -61,7 +61,11 @@ extern RecipeHooks recipe_hooks;                    // ngw_abi_create.cpp, besid
 // The same for the tree-search kernels (ngw_tree.inc): ngw_host_tree.cpp alone names their launchers and fills these pointers when the library is
 // loaded; ngw_abi_tree.cpp launches through them, behind enter(), and refuses every ngw_tree_* call while they are empty.
 typedef hipError_t (*TreeLaunch)(const NgwTree* x, hipStream_t stream);
-struct TreeHooks { TreeLaunch leaf = nullptr, grow = nullptr, backup = nullptr, reweight = nullptr; };
+typedef hipError_t (*TreeRuleLaunch)(const NgwTree* x, const NgwTreeRule* r, hipStream_t stream);
+struct TreeHooks {
+    TreeLaunch leaf = nullptr, grow = nullptr, backup = nullptr, reweight = nullptr;
+    TreeRuleLaunch backup_discount = nullptr, reweight16 = nullptr;      // the two kernels of ngw_tree_set_rule
+};
 extern TreeHooks tree_hooks;                        // ngw_abi_tree.cpp
 }
 
@@ -141,6 +145,7 @@ struct ngw_tree {
     ngw_snapshot* src = nullptr;          // where the roots live (ngw_tree_start); NULL: the envs' current states
     int64_t cap = 0, buckets = 0, n_roots = 0;   // cap: playouts per iteration
     int32_t T = 0, A = 0, combine = 1;
+    int32_t spread = 1, discount_q16 = 65536, rows16 = 0;   // ngw_tree_set_rule; kept by clear
     uint32_t fields = 0;
     float c = 0, q_init = 0;
     uint64_t iterations = 0;              // since creation or the last clear

@@ -1075,18 +1075,20 @@ class Snapshot:
         return s
 
     # ------------------------------------------------------------------ device-side tree-search runs (include/ngw.h ngw_tree_*; tree.py)
-    def tree_search(self, table, playouts, steps, c=1.0, q_init=0.0, priors=False, weights=None, fields=KEY_STATE, plain_backup=False):
+    def tree_search(self, table, playouts, steps, c=1.0, q_init=0.0, priors=False, weights=None, fields=KEY_STATE, plain_backup=False, spread=1, discount=1.0,
+                    rows16=0):
         """A TreeSearch over `table` (a KeyTable of the same env) rooted in this snapshot's slots - or, with start(from_envs=True), in the envs'
         current states -: whole MCTS iterations of `playouts` pairs and `steps` steps each - a guided playout, the new leaves inserted, an
         integer every-visit backup, the PUCT rows recomputed under each node's valid-action mask -, enqueued from one call with no host wait in
         between; it keeps visit counts, return sums and mask words per bucket of the table (tree.py says what an iteration is).  c, q_init: the
         PUCT rule's; priors=True: a [buckets, A] tensor of priors for the caller to fill; weights: the default policy's, None: uniform; fields:
-        the KEY_* selection of a node.  ValueError for a table of another env, playouts * steps or buckets * A beyond 2^31 - 1, fields == 0, a c
+        the KEY_* selection of a node.  spread: 1 to 64, the PUCT choices with virtual visits a row allots (above 1 the pairs of one root diverge
+        inside the tree); discount: a float in [0, 1] per executed step, applied in integers (tree.py).  ValueError for a table of another env, playouts * steps or buckets * A beyond 2^31 - 1, fields == 0, a c
         or q_init that is not finite; maps beyond the keyed guided playout's limit raise what playout(table=) raises.  Closed by its close()
         and with this snapshot."""
         from .tree import TreeSearch
         self._open()
-        t = TreeSearch(self, table, playouts, steps, c, q_init, priors, weights, fields, plain_backup)
+        t = TreeSearch(self, table, playouts, steps, c, q_init, priors, weights, fields, plain_backup, spread, discount, rows16)
         self.__dict__.setdefault('_searches', []).append(t)
         return t
 

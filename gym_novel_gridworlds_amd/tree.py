@@ -32,9 +32,13 @@ The stages are callable on their own, for a loop that asks a value network betwe
     t.backup(r, bootstrap=v)                              # G_t = the rewards from t on + v
     t.reweight()                                          # the rows of every bucket that backup touched
 
-leaf_reference, backup_reference, puct_rows_reference and iteration_reference state the contract in numpy.  NOT built: virtual loss, several
-playouts per root that diverge inside the tree (the pairs of one root follow the same one-hot rows until they leave the tree), discounting,
-max-backups, a tree across ranks, hipGraph capture, and the leaf's observation for a network - the caller gets it from
+With spread=S (1 to 64) a row is not one-hot: it is the allotment k[a] that S successive PUCT choices with virtual visits make - the divisor of
+u grows with every choice an action received, sqrt(n_b + 1 + i) with the round i, q does not change - and every pair draws its own action from
+it by (seed, pair, t), so the pairs of one root spread inside the tree and one iteration grows several nodes per root state.  With discount=d
+the backup is G_t = r_t + D(G_{t+1}), D(x) = (round(d * 65536) * x) >> 16 in int64: integers still, so the bytes stay independent of order.
+
+leaf_reference, backup_reference, puct_rows_reference, spread_rows_reference and iteration_reference state the contract in numpy.  NOT built:
+virtual loss through atomics, max-backups, a tree across ranks, hipGraph capture, and the leaf's observation for a network - the caller gets it from
 snap.lidar_observation after replaying the recorded actions with limits=depth.
 
 A tree search is rank-local, as a search is: under ShardedVecNovelGridworld it belongs to the local env's pool and table."""
@@ -65,12 +69,26 @@ def leaf_reference(depth, length, keys, masks):
     return lk, lm
 
 
-def backup_reference(visits, returns, actions, rewards, where, depth, length, where_leaf=None, bootstrap=None):
+def discount_reference(x, g):
+    """D of rule 4 on a Python int in int64 range -> a Python int: x itself for g == 65536, else (g * x) >> 16 - the product wrapped to int64, the
+    shift arithmetic (floor)."""
+    if g == 65536:
+        return x
+    y = (g * x) & 0xFFFFFFFFFFFFFFFF
+    return (y - (1 << 64) if y >> 63 else y) >> 16
+
+
+def backup_reference(visits, returns, actions, rewards, where, depth, length, where_leaf=None, bootstrap=None, discount_q16=65536):
     """Step 4 in numpy: visits int32 [buckets, A] and returns int64 [buckets, A] updated in place -> touched int32 [T, count], the bucket of
     every step that was backed up, -1 elsewhere.  actions, rewards, where int32 [T, count]; depth, length int32 [count]; where_leaf int32
     [count] or None (no pair has a leaf); bootstrap int32 [count] or None.  Pair j with d = depth[j] >= 1, for t from min(d, length[j] - 1)
     down to 0: e = where[t, j] for t < d, where_leaf[j] for t == d; where e is a bucket and actions[t, j] an action: visits[e, a] += 1,
-    returns[e, a] += G_t = rewards[t:, j].sum() + bootstrap[j], wrapping as int32 / int64 do."""
+    returns[e, a] += G_t = rewards[t:, j].sum() + bootstrap[j], wrapping as int32 / int64 do.  discount_q16 = g below 65536 (ngw_tree_set_rule):
+    with n = length[j] clamped to [0, T], G_n = bootstrap[j] + rewards[n:, j].sum() (a playout records 0 there) and G_t = rewards[t, j] +
+    ((g * G_{t+1}) >> 16) for t < n - discount_reference; the bootstrap is discounted n times, not T."""
+    g = int(discount_q16)
+    if not 0 <= g <= 65536:
+        raise ValueError("discount_q16: %r outside [0, 65536]" % (discount_q16,))
     actions, rewards, where = np.asarray(actions), np.asarray(rewards, np.int64), np.asarray(where)
     T, count = actions.shape
     buckets, A = visits.shape
@@ -81,8 +99,12 @@ def backup_reference(visits, returns, actions, rewards, where, depth, length, wh
         if d < 1:
             continue
         boot = int(0 if bootstrap is None else bootstrap[j])
+        Gs = [0] * n + [boot + int(rewards[n:, j].sum())]                       # G_t of the executed steps, G_n behind them
+        for t in range(n - 1, -1, -1):
+            y = (int(rewards[t, j]) + discount_reference(Gs[t + 1], g)) & 0xFFFFFFFFFFFFFFFF
+            Gs[t] = y - (1 << 64) if y >> 63 else y
         for t in range(min(d, n - 1), -1, -1):
-            G = boot + int(rewards[t:, j].sum())
+            G = Gs[t]
             e = int(where[t, j]) if t < d else (-1 if where_leaf is None else int(where_leaf[j]))
             a = int(actions[t, j])
             if 0 <= e < buckets and 0 <= a < A:
@@ -125,21 +147,63 @@ def puct_rows_reference(visits, returns, mask_words, c, q_init, priors=None):
     return rows, bad
 
 
+def spread_rows_reference(visits, returns, mask_words, c, q_init, spread, priors=None):
+    """Step 5 under ngw_tree_set_rule's spread = S in [1, 64], for n rows -> (rows float32 [n, A], bad).  The arguments and the cleaning of the
+    priors are puct_rows_reference's.  Per row with a mask word that is not 0: k = 0; for i in 0 .. S-1: the scores of puct_rows_reference with
+    sqrt(float32(n_b + 1 + i)) and the divisor float32(1 + visits + k) - the integers summed in 64 bits, then rounded once -, its ordered walk's
+    pick, k[pick] += 1; the row is float32(k).  S = 1: puct_rows_reference's bytes."""
+    S = int(spread)
+    if not 1 <= S <= 64:
+        raise ValueError("spread: %r outside [1, 64]" % (spread,))
+    visits, returns = np.asarray(visits, np.int64), np.asarray(returns, np.int64)
+    m = np.asarray(mask_words).view(np.uint64).reshape(-1)
+    n, A = visits.shape
+    f32 = np.float32
+    bad = False
+    rows = np.zeros((n, A), f32)
+    with np.errstate(all='ignore'):
+        if priors is None:
+            p = np.ones((n, A), f32)
+        else:
+            x = np.asarray(priors, f32)
+            bad = bool((~((x >= 0) & (x <= WEIGHT_MAX))).any())
+            p = np.where((x >= WEIGHT_MIN) & (x <= WEIGHT_MAX), x, f32(0)).astype(f32)
+        total = visits.sum(1)
+        q = np.where(visits > 0, returns.astype(f32) / np.where(visits > 0, visits, 1).astype(f32), f32(q_init)).astype(f32)
+        cp = (f32(c) * p).astype(f32)
+        for i in range(n):
+            valid = [a for a in range(A) if (int(m[i]) >> a) & 1]
+            if not valid:
+                continue
+            k = np.zeros(A, np.int64)
+            for r in range(S):
+                root = np.sqrt(f32(int(total[i]) + 1 + r)).astype(f32)
+                score = (q[i] + ((cp[i] * root).astype(f32) / (1 + visits[i] + k).astype(f32)).astype(f32)).astype(f32)
+                pick = -1
+                for a in valid:
+                    if pick < 0 or score[a] > score[pick]:
+                        pick = a
+                k[pick] += 1
+            rows[i] = k.astype(f32)
+    return rows, bad
+
+
 def iteration_reference(visits, returns, mask_words, rows, actions, rewards, where, depth, length, keys, masks, where_leaf, c, q_init, priors=None,
-                        bootstrap=None):
+                        bootstrap=None, spread=1, discount_q16=65536):
     """One iteration of TreeSearch.run behind its playout, in numpy: steps 2 to 5 of include/ngw.h's ngw_tree_run.  visits, returns, mask_words
     and rows ([buckets, A], [buckets]) are updated in place; the recorded arrays are the playout's; where_leaf int32 [count]: the bucket the
     table gives each leaf key (-1: key 0 or refused - which bucket a key gets is the table's choice, so it is an input here, as `where` is
-    in search.relax_reference).  -> (leaf_keys, leaf_masks, touched, bad)."""
+    in search.relax_reference); spread, discount_q16: the rule of ngw_tree_set_rule (the defaults: today's iteration).
+    -> (leaf_keys, leaf_masks, touched, bad)."""
     lk, lm = leaf_reference(depth, length, keys, masks)
     where_leaf = np.asarray(where_leaf, np.int64)
     for j in np.flatnonzero((where_leaf >= 0) & (lm != 0)).tolist():
         mask_words[where_leaf[j]] = lm[j]
-    touched = backup_reference(visits, returns, actions, rewards, where, depth, length, where_leaf, bootstrap)
+    touched = backup_reference(visits, returns, actions, rewards, where, depth, length, where_leaf, bootstrap, discount_q16)
     b = np.unique(touched[touched >= 0])
     bad = False
     if len(b):
-        rows[b], bad = puct_rows_reference(visits[b], returns[b], mask_words[b], c, q_init, None if priors is None else priors[b])
+        rows[b], bad = spread_rows_reference(visits[b], returns[b], mask_words[b], c, q_init, spread, None if priors is None else priors[b])
     return lk, lm, touched, bad
 
 
@@ -166,9 +230,13 @@ class TreeSearch:
     playouts: the capacity in pairs per iteration; steps: T, fixed here.  c, q_init: the PUCT rule's (module docstring).  weights: None or float32
     [A], the default policy of a state outside the table (the heavy playout's weights).  fields: the KEY_* selection of a node.
     plain_backup=True: the backup adds lane by lane instead of combining inside the wave - the same bytes, for A/B timing.
+    spread: S in [1, 64] - a row is the allotment of S successive PUCT choices with virtual visits (spread_rows_reference), so the pairs of one
+    root spread over up to S actions at every node and an iteration grows more than one node per root state; `spread` holds it.  discount: a
+    float in [0, 1], applied in integers as discount_q16 = round(discount * 65536) per executed step (backup_reference); 1.0: none.
     clear() empties the table AND the statistics; table.clear() alone does not touch the statistics - the rows then describe keys that are gone."""
 
-    def __init__(self, snap, table, playouts, steps, c=1.0, q_init=0.0, priors=False, weights=None, fields=None, plain_backup=False):
+    def __init__(self, snap, table, playouts, steps, c=1.0, q_init=0.0, priors=False, weights=None, fields=None, plain_backup=False, spread=1, discount=1.0,
+                 rows16=0):
         import torch
         from .snapshot import MapsTooLarge
         from .state_keys import KEY_STATE, check_fields
@@ -200,6 +268,13 @@ class TreeSearch:
             if weights.shape != (A,):
                 raise ValueError("weights: float32 [%d] expected, got shape %s" % (A, list(weights.shape)))
         self.weights = weights
+        if isinstance(spread, bool) or not isinstance(spread, (int, np.integer)) or not 1 <= spread <= 64:
+            raise ValueError("spread: an integer in [1, 64] expected, got %r" % (spread,))
+        if isinstance(discount, bool) or not isinstance(discount, (int, float, np.integer, np.floating)) or not 0.0 <= float(discount) <= 1.0:
+            raise ValueError("discount: a number in [0, 1] expected, got %r" % (discount,))
+        if isinstance(rows16, bool) or rows16 not in (0, 1, 2) or (rows16 == 2 and spread > 1):
+            raise ValueError("rows16: 0, 1 or 2 expected (2, the one-lane reweight, with spread = 1 only), got %r with spread = %d" % (rows16, spread))
+        self.spread, self.discount_q16, self._rows16 = int(spread), int(round(float(discount) * 65536)), int(rows16)
         self._t, self._keep, self._grown = C.c_void_p(), None, None
         opt = _cabi.TreeOptions(self.playouts, self.steps, self.fields, self.c, self.q_init, int(bool(priors)), int(bool(plain_backup)), _cabi._ptr(weights, np.float32))
         try:
@@ -208,6 +283,13 @@ class TreeSearch:
             if str(e).startswith('map_size'):
                 raise MapsTooLarge(str(e)) from None
             raise
+        if (self.spread, self.discount_q16, self._rows16) != (1, 65536, 0):       # (a default tree makes the calls it always made)
+            rule = _cabi.TreeRule(self.spread, self.discount_q16, self._rows16, 0)
+            try:
+                _cabi.check(_cabi.lib().ngw_tree_set_rule(self.env._h, self._t, C.byref(rule)))
+            except Exception:
+                _cabi.lib().ngw_tree_destroy(self.env._h, self._t)
+                raise
         arr = _cabi.TreeArrays()
         _cabi.check(_cabi.lib().ngw_tree_arrays(self.env._h, self._t, C.byref(arr)))
         dev = 'cuda:%d' % self.env.device

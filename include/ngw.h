@@ -1385,6 +1385,35 @@ int ngw_tree_backup(ngw_handle* h, ngw_tree* t, const int32_t* actions_dev, cons
 int ngw_tree_reweight(ngw_handle* h, ngw_tree* t, const int32_t* buckets_dev /* NULL: what the last backup touched */, int64_t count);
 int ngw_tree_report(ngw_handle* h, ngw_tree* t, ngw_tree_report_rows* out);
 int ngw_tree_clear(ngw_handle* h, ngw_tree* t);
+/* The rule of a tree (additive: a tree whose rule was never set enqueues what it always did and leaves the same bytes).
+ *   spread = S in [1, 64], default 1 - rule 5 generalised.  The row of a touched bucket b with m = mask_words[b] != 0 is the allotment that S
+ *     successive PUCT choices with virtual visits make:
+ *         k[a] = 0 for all a;  n_b = the sum of visits[b][.] in 64 bits
+ *         for i = 0 .. S-1:  root_i = sqrt(float(n_b + 1 + i))
+ *                            q[a] as in rule 5 (virtual visits do not change q)      u[a] = ((c * p[a]) * root_i) / float(1 + visits[b][a] + k[a])
+ *                            pick = rule 5's ordered walk over a = 0 .. A-1 on score[a] = q[a] + u[a];  k[pick] += 1
+ *         rows[b][a] = float(k[a])
+ *     in binary32, every operation rounded on its own, none fused, the integer sums formed in 64 bits and converted round-to-nearest-even; p cleaned
+ *     and NGW_F_BAD_WEIGHT raised as in rule 5; m == 0: an all-zero row.  S = 1 gives rule 5's bytes.  The entries are small integers, so the running
+ *     binary32 sum of ngw_sample_actions' rule over them is exact and its mass is S: pair j draws action a at a state with probability k[a] / S by
+ *     its own (seed, pair, t) - the pairs of one root spread over the S choices inside the tree, and the playout is unchanged.  A score that is NaN
+ *     (visits written negative by the caller) behaves as in the walk: it is never larger than the pick's, and is the pick only at the first valid action.
+ *   discount_q16 = g in [0, 65536], default 65536 - rule 4 generalised.  len = length[j] clamped to [0, n_steps]; G_len = bootstrap[j] (0 without
+ *     one) plus the rewards recorded at t >= len (a playout records 0 there); for t = len-1 .. 0: G_t = rewards[t][j] + D(G_{t+1}), D(x) = x for g ==
+ *     65536 (no multiply) and otherwise (g * x) >> 16: the int64 two's-complement product, wrapping as int64 does, then an arithmetic right shift
+ *     (floor, not truncation).  What is added where, and `touched`, are rule 4's.  Integers still: any combining gives the same bytes.  It holds for
+ *     ngw_tree_backup too.
+ *   rows16: which kernel writes the rows.  0: automatic - the one-lane kernel at spread 1, the 16-lane kernel (one list entry per 16 lanes, lane l
+ *     holding the actions l, l + 16, l + 32; the visit sum and each round's pick reduced inside the row) above; 1: the 16-lane kernel also at spread
+ *     1; 2: the one-lane kernel (spread 1 only).  The bytes are the same: the field exists to time the two forms against each other.
+ * The rule is host state, read when a call is enqueued: it holds for everything enqueued after it until it is set again or the tree is destroyed;
+ * ngw_tree_clear keeps it.  No kernel is launched, but the call DOES enqueue work on the handle's stream: one fill of `touched` with -1 (steps *
+ * playouts * 4 bytes), which forgets the list of the last backup - ngw_tree_reweight(NULL) right after it rewrites no row, so rows are never
+ * recomputed under a rule other than the one their backup ran under unless the caller names the buckets.  Set the rule once, not per iteration.
+ * NGW_E_INVALID_ARG: a NULL argument, a tree or table not open on this handle, spread outside [1, 64], discount_q16 outside [0, 65536], rows16 outside
+ * [0, 2], rows16 == 2 with spread > 1, reserved != 0. */
+typedef struct ngw_tree_rule { int32_t spread; int32_t discount_q16; int32_t rows16; int32_t reserved; } ngw_tree_rule;
+int ngw_tree_set_rule(ngw_handle* h, ngw_tree* t, const ngw_tree_rule* rule);
 
 /* One-step lookahead tables: every action's outcome for every env, without taking a step.
  * For a handle with A = n_actions the table of the CURRENT state is three arrays - reward int32, done uint8, info uint32 (the NGW_INFO_* packing).
