@@ -11,8 +11,6 @@ thread_local char g_err[512] = "";
 
 namespace ngwh {
 
-RecipeHooks recipe_hooks;                             // filled by ngw_host_recipe.cpp when the library is loaded (ngw_host.h)
-
 int fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);

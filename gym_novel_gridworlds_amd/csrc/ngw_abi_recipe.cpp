@@ -1,13 +1,11 @@
-// ngw_host_recipe.cpp - the recipe heuristic's host side (see ngw_host.h, RecipeHooks): the checks of a caller's program, its packed form and the one
-// launch of ngw_recipe.inc.  Deliberately NOT an ngw_abi_*.cpp unit: it is the only host unit that names ngw_recipe_launch, and the entry points
-// (ngw_snapshot_recipe_costs, ngw_search_set_recipe) and the search driver reach it through ngwh::recipe_hooks, filled below when the library is
-// loaded - so the ngw_abi_ units link with or without it.  Nothing here commits anything: no state_written(), no derived-state flag; both functions
-// run behind the caller's enter().
+// ngw_abi_recipe.cpp - the recipe heuristic's host side (see ngw_host.h): the checks of a caller's program, its packed form, the one launch of
+// ngw_recipe.inc, and ngw_snapshot_recipe_costs; the search's term (ngw_search_set_recipe, ngw_abi_search.cpp) goes through the first two.  Nothing
+// here commits anything: no state_written(), no derived-state flag.
 #include "ngw_host.h"
 
 using namespace ngwh;
 
-namespace {
+namespace ngwh {
 
 // The rules of include/ngw.h, one message each; -> the program as the kernel takes it: items resolved to rule numbers, flagged items to count slots.
 int recipe_pack(const ngw_handle* h, const ngw_recipe_program* in, NgwRecipeProg* out) {
@@ -63,16 +61,29 @@ int recipe_pack(const ngw_handle* h, const ngw_recipe_program* in, NgwRecipeProg
     return NGW_OK;
 }
 
-int recipe_run(ngw_handle* h, hipStream_t stream, const NgwSnapRows& src, int64_t rows, const int32_t* idx_dev, int64_t count, const NgwRecipeProg& prog, int32_t* out_dev) {
+int recipe_run(ngw_handle* h, const NgwSnapRows& src, int64_t rows, const int32_t* idx_dev, int64_t count, const NgwRecipeProg& prog, int32_t* out_dev) {
     NgwRecipe x{};
     x.src = src; x.idx = idx_dev; x.flags = h->b.flags; x.out = out_dev;
     x.count = count; x.rows = (int32_t)rows; x.S2 = h->proto.S2; x.K = h->proto.K; x.prog = prog;
-    HIP_TRY(ngw_recipe_launch(&x, stream));
+    HIP_TRY(ngw_recipe_launch(&x, h->stream));
     return NGW_OK;
 }
 
-struct Register {
-    Register() { recipe_hooks.pack = recipe_pack; recipe_hooks.run = recipe_run; }
-} register_hooks;
+}  // namespace ngwh
 
-}  // namespace
+extern "C" {
+
+int ngw_snapshot_recipe_costs(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, const ngw_recipe_program* program, int32_t* out_dev) {
+    if (!h || !program || !out_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
+    if (s && !is_open(h->snaps, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    const Source from = source_of(h, s);
+    if (count < 0 || count > 0x7FFFFFFFll * NGW_EPB) return fail(NGW_E_INVALID_ARG, "recipe costs of %lld rows", (long long)count);
+    if (!idx_dev && count > from.rows) return fail(NGW_E_INVALID_ARG, "recipe costs of %lld rows from %lld %s", (long long)count, (long long)from.rows, from.unit);
+    if (int rc = enter(h)) return rc;                 // (s == NULL: the one-env loop has ended, HBM holds the env's state)
+    NgwRecipeProg prog;
+    if (int rc = recipe_pack(h, program, &prog)) return rc;
+    if (count == 0) return NGW_OK;
+    return recipe_run(h, from.r, from.rows, idx_dev, count, prog, out_dev);
+}
+
+}  // extern "C"

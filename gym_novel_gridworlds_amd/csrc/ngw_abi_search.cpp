@@ -4,8 +4,8 @@
 // ngw_search.inc between them.  The calls write no env state: they neither call state_written() nor touch anything the handle derives from its
 // state.  All run on the handle's stream, behind enter(); only ngw_search_read / _read_open wait.  An open-list search (ngw_search_create_open) adds
 // the selection over f in front, the walk of the children behind, and the take and open kernels; the same driver serves it.  The recipe term
-// (ngw_search_set_recipe) is one launch more in front of the open and the roots kernel, made by ngw_host_recipe.cpp through the pointer the search
-// keeps: this unit names no launcher of it, and a search without the term enqueues exactly what it always did.
+// (ngw_search_set_recipe) is one launch more in front of the open and the roots kernel, recipe_run of ngw_abi_recipe.cpp; a search without the term
+// enqueues exactly what it always did.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -16,24 +16,13 @@ namespace {
 // ring of NGW_SEARCH_ROWS rows would be the row of iteration i + 1 - NGW_SEARCH_ROWS - the oldest of the rows still to be reported.
 constexpr int64_t SEARCH_RING = NGW_SEARCH_ROWS + 1;
 
-bool owns_search(const ngw_handle* h, const ngw_search* s) {
-    for (const ngw_search* q : h->searches)
-        if (q == s) return true;
-    return false;
-}
-
-// the pool and the table of `s` are still open on `h` (by address: a closed one is simply not found)
-bool parts_open(const ngw_handle* h, const ngw_search* s) {
-    bool pool = false, table = false;
-    for (const ngw_snapshot* q : h->snaps) pool = pool || q == s->pool;
-    for (const ngw_key_table* q : h->tables) table = table || q == s->table;
-    return pool && table;
-}
+// the pool and the table of a search are still open on `h` (by address: a closed one is simply not found)
+bool parts_open(const ngw_handle* h, const ngw_snapshot* pool, const ngw_key_table* table) { return is_open(h->snaps, pool) && is_open(h->tables, table); }
 
 int search_call_args(const ngw_handle* h, const ngw_search* s) {
     if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_search(h, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
-    if (!parts_open(h, s)) return fail(NGW_E_INVALID_ARG, "the search's snapshot or key table is closed");
+    if (!is_open(h->searches, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
+    if (!parts_open(h, s->pool, s->table)) return fail(NGW_E_INVALID_ARG, "the search's snapshot or key table is closed");
     return NGW_OK;
 }
 
@@ -50,7 +39,7 @@ NgwSearch search_args(const ngw_search* s) {
         x.f = s->f; x.h = s->h; x.slot_of_bucket = s->slot_of_bucket; x.dist = s->dist; x.weights = s->weights; x.sel_count = s->count;
         x.orow = s->ostats + NGW_SEARCH_OPEN_COLS * (s->iterations % SEARCH_RING); x.next_orow = s->ostats + NGW_SEARCH_OPEN_COLS * ((s->iterations + 1) % SEARCH_RING);
         x.buckets = s->buckets; x.K = s->K; x.mode = s->hmode; x.prune = s->prune;
-        x.recipe = s->recipe_run ? s->recipe : nullptr;
+        x.recipe = s->recipe;
     }
     return x;
 }
@@ -79,8 +68,8 @@ int iterate(ngw_handle* h, ngw_search* s) {
     if (s->open) {                                    // step 8: the children join the open list
         if (s->dist)
             if (int rc = ngw_snapshot_walk(h, s->pool, x.next, s->cap, nullptr, 0, s->dist, nullptr, nullptr)) return rc;
-        if (s->recipe_run)                            // (the recipe term of the same list: a padded entry gives 0 and no flag)
-            if (int rc = s->recipe_run(h, h->stream, s->pool->r, s->pool->cap, x.next, s->cap, s->recipe_prog, s->recipe)) return rc;
+        if (s->recipe)                                // (the recipe term of the same list: a padded entry gives 0 and no flag)
+            if (int rc = recipe_run(h, s->pool->r, s->pool->cap, x.next, s->cap, s->recipe_prog, s->recipe)) return rc;
         HIP_TRY(ngw_search_open_launch(&x, h->stream));
     }
     s->cur ^= 1;
@@ -94,9 +83,7 @@ int create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, const ngw_se
     const int64_t capacity = o.capacity;
     const int32_t keep = o.keep;
     *out = nullptr;
-    ngw_search probe;
-    probe.pool = pool; probe.table = table;
-    if (!parts_open(h, &probe)) return fail(NGW_E_INVALID_ARG, "not an open snapshot and an open key table of this handle");
+    if (!parts_open(h, pool, table)) return fail(NGW_E_INVALID_ARG, "not an open snapshot and an open key table of this handle");
     if (!table->valued) return fail(NGW_E_INVALID_ARG, "a key table without values (ngw_key_table_create_valued makes one with)");
     const int64_t A = h->spec.n_actions;
     if (capacity < 1 || capacity > pool->cap) return fail(NGW_E_INVALID_ARG, "search capacity %lld outside [1, the pool's %lld]", (long long)capacity, (long long)pool->cap);
@@ -126,41 +113,32 @@ int create(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* table, const ngw_se
         return fail(NGW_E_INVALID_ARG, "map_size %d: a search keeps two sets of a wavefront's 64 maps in LDS (ngw_successor_keys) and they need %zu B, more "
                                        "than 160 KiB", h->proto.S, lds);
     if (int rc = enter(h)) return rc;
-    const size_t cap = (size_t)capacity, n = cap * (size_t)A, pc = (size_t)pool->cap;
-    // 64-bit words: goal, overflowed | keys [n] | the int32 arrays, an even number of them | fresh [n], best [n]
-    const size_t head = 4 * SEARCH_RING + 64 + 8;                              // stats, cost table, cursor + count[2] + taken + bound + 3 spare
-    size_t words32 = head + 6 * cap + 2 * pc + 4 * n;
-    // an open-list search: the weights and the distances first, from a multiple of 16 bytes (the int32 arrays start 2 + n 64-bit words into the slab)
-    const size_t nb = (size_t)table->buckets, Kp = ((size_t)K + 3) & ~(size_t)3;
-    size_t extra = 0;
-    if (open) {
-        extra = words32 + ((4 - (2 * (2 + n) + words32) % 4) % 4);
-        words32 = extra + (walk ? Kp + cap * (size_t)K : 0);
-        words32 += (size_t)NGW_SEARCH_OPEN_COLS * SEARCH_RING + 2 * pc + nb;
-    }
-    words32 += words32 & 1;
-    const size_t words64 = 2 + n + words32 / 2 + (2 * n + 7) / 8;
-    uint64_t* slab = nullptr;
-    if (int rc = dev_alloc(h, &slab, words64)) return rc;                          // (zero-filled on the handle's stream)
+    const size_t cap = (size_t)capacity, n = cap * (size_t)A, pc = (size_t)pool->cap, nb = (size_t)table->buckets;
     ngw_search* s = new ngw_search;
     s->pool = pool; s->table = table; s->cap = capacity; s->pool_cap = pool->cap; s->n = (int64_t)n;
     s->A = (int32_t)A; s->by_action = o.by_action != 0; s->keep = keep < 0 ? -1 : keep; s->stop = o.stop_at_goals != 0;
     s->open = open; s->prune = o.prune != 0; s->hmode = walk ? o.heuristic : NGW_SEARCH_H_NONE; s->K = K; s->buckets = (int64_t)nb;
-    s->slab = slab; s->goal = reinterpret_cast<unsigned long long*>(slab); s->keys = slab + 2;
-    int32_t* w = reinterpret_cast<int32_t*>(slab + 2 + n);
-    s->stats = reinterpret_cast<uint32_t*>(w); w += 4 * SEARCH_RING;
-    s->lut = w; w += 64;
-    s->cursor = w; s->count = w + 1; s->taken = w + 3; s->bound = w + 4; w += 8;
-    s->parents[0] = w; s->parents[1] = w + cap; s->first = w + 2 * cap; s->second = w + 3 * cap; s->slots = w + 4 * cap; s->plist = w + 5 * cap; w += 6 * cap;
-    s->g = w; s->bucket = w + pc; w += 2 * pc;
-    s->info = w; s->values = w + n; s->tags = w + 2 * n; s->where = w + 3 * n;
-    s->fresh = reinterpret_cast<uint8_t*>(slab + 2 + n + words32 / 2); s->best = s->fresh + n;
-    if (open) {
-        w = reinterpret_cast<int32_t*>(s->stats) + extra;
-        if (walk) { s->weights = w; s->dist = w + Kp; w += Kp + cap * (size_t)K; }
-        s->ostats = reinterpret_cast<uint32_t*>(w); w += (size_t)NGW_SEARCH_OPEN_COLS * SEARCH_RING;
-        s->h = w; s->f = w + pc; s->slot_of_bucket = w + 2 * pc;
-    }
+    auto layout = [&](Carver c) {                      // the slab, described once: 64-bit words, the int32 arrays, an open-list search's own, the two flag arrays
+        s->goal = c.take<unsigned long long>(2); s->keys = c.take<uint64_t>(n);                                      // goal, overflowed | keys
+        s->stats = c.take<uint32_t>(4 * SEARCH_RING); s->lut = c.take<int32_t>(64);
+        s->cursor = c.take<int32_t>(1); s->count = c.take<int32_t>(2); s->taken = c.take<int32_t>(1); s->bound = c.take<int32_t>(1); c.take<int32_t>(3);   // (3 spare)
+        s->parents[0] = c.take<int32_t>(cap); s->parents[1] = c.take<int32_t>(cap); s->first = c.take<int32_t>(cap); s->second = c.take<int32_t>(cap);
+        s->slots = c.take<int32_t>(cap); s->plist = c.take<int32_t>(cap); s->g = c.take<int32_t>(pc); s->bucket = c.take<int32_t>(pc);
+        s->info = c.take<int32_t>(n); s->values = c.take<int32_t>(n); s->tags = c.take<int32_t>(n); s->where = c.take<int32_t>(n);
+        if (open) {
+            c.align(16);                                                           // the weights and the distances start on 16 bytes
+            if (walk) { s->weights = c.take<int32_t>(((size_t)K + 3) & ~(size_t)3); s->dist = c.take<int32_t>(cap * (size_t)K); }
+            s->ostats = c.take<uint32_t>((size_t)NGW_SEARCH_OPEN_COLS * SEARCH_RING);
+            s->h = c.take<int32_t>(pc); s->f = c.take<int32_t>(pc); s->slot_of_bucket = c.take<int32_t>(nb);
+        }
+        c.align(8);
+        s->fresh = c.take<uint8_t>(n); s->best = c.take<uint8_t>(n); c.align(8);
+        return c.bytes;
+    };
+    uint64_t* slab = nullptr;
+    if (int rc = dev_alloc(h, &slab, layout(Carver()) / 8)) { delete s; return rc; }   // (zero-filled on the handle's stream)
+    layout(Carver(slab));
+    s->slab = slab;
     hipError_t e = hipMemsetAsync(s->goal, 0xFF, 8, h->stream);                                                   // no goal yet
     if (e == hipSuccess) e = hipMemcpyAsync(s->lut, o.costs_host, 64 * sizeof(int32_t), hipMemcpyDefault, h->stream);
     if (e == hipSuccess) e = hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(s->parents[0]), (int)NGW_IDX_NONE, 2 * cap, h->stream);
@@ -207,7 +185,7 @@ int ngw_search_create_open(ngw_handle* h, ngw_snapshot* pool, ngw_key_table* tab
 
 int ngw_search_destroy(ngw_handle* h, ngw_search* s) {
     if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_search(h, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
+    if (!is_open(h->searches, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
     if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));                         // (queued iterations may still use the arrays)
     for (size_t i = 0; i < h->searches.size(); i++)
@@ -223,14 +201,12 @@ int ngw_search_set_recipe(ngw_handle* h, ngw_search* s, const ngw_recipe_program
     if (!program) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (!s->open) return fail(NGW_E_INVALID_ARG, "a search without an open list has no heuristic (ngw_search_create_open makes one with)");
     if (s->started || s->iterations) return fail(NGW_E_INVALID_ARG, "ngw_search_set_recipe is legal only before ngw_search_start");
-    if (!recipe_hooks.pack || !recipe_hooks.run) return fail(NGW_E_INVALID_ARG, "the recipe heuristic is not part of this build (ngw_host_recipe.cpp)");
     if (int rc = enter(h)) return rc;
     NgwRecipeProg prog;
-    if (int rc = recipe_hooks.pack(h, program, &prog)) return rc;
+    if (int rc = recipe_pack(h, program, &prog)) return rc;
     if (!s->recipe)
         if (int rc = dev_alloc(h, &s->recipe, (size_t)s->cap)) return rc;         // (zero-filled on the handle's stream; ngw_search_run allocates nothing)
     s->recipe_prog = prog;
-    s->recipe_run = recipe_hooks.run;
     return NGW_OK;
 }
 
@@ -255,9 +231,9 @@ int ngw_search_start(ngw_handle* h, ngw_search* s, const int32_t* roots_dev, int
         if (count && s->dist)
             if (int rc = ngw_snapshot_walk(h, s->pool, roots_dev, count, nullptr, 0, s->dist, nullptr, nullptr)) return rc;
         x.f = s->f; x.h = s->h; x.slot_of_bucket = s->slot_of_bucket; x.dist = s->dist; x.weights = s->weights; x.buckets = s->buckets; x.K = s->K; x.mode = s->hmode;
-        if (s->recipe_run) {
+        if (s->recipe) {
             if (count)
-                if (int rc = s->recipe_run(h, h->stream, s->pool->r, s->pool->cap, roots_dev, count, s->recipe_prog, s->recipe)) return rc;
+                if (int rc = recipe_run(h, s->pool->r, s->pool->cap, roots_dev, count, s->recipe_prog, s->recipe)) return rc;
             x.recipe = s->recipe;
         }
     }
@@ -278,7 +254,7 @@ int ngw_search_run(ngw_handle* h, ngw_search* s, int32_t iterations, int32_t* cu
 
 int ngw_search_read(ngw_handle* h, ngw_search* s, ngw_search_report* out) {
     if (!h || !s || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_search(h, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
+    if (!is_open(h->searches, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
     if (int rc = enter(h)) return rc;
     uint64_t head[2] = {0, 0};
     uint32_t ring[SEARCH_RING][4];
@@ -306,7 +282,7 @@ int ngw_search_read(ngw_handle* h, ngw_search* s, ngw_search_report* out) {
 
 int ngw_search_read_open(ngw_handle* h, ngw_search* s, ngw_search_open_report* out) {
     if (!h || !s || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_search(h, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
+    if (!is_open(h->searches, s)) return fail(NGW_E_INVALID_ARG, "not an open search of this handle");
     if (!s->open) return fail(NGW_E_INVALID_ARG, "a search without an open list (ngw_search_create_open makes one with)");
     if (int rc = enter(h)) return rc;
     uint32_t ring[SEARCH_RING][NGW_SEARCH_OPEN_COLS];

@@ -17,7 +17,6 @@
 // the table as it was.
 // The weighted choice (ngw_sample.inc) draws one action per row by the caller's weights among the valid ones: it commits nothing either.
 // The walk (ngw_walk.inc) finds the shortest Forward / Left / Right walks from such rows to each item id: it commits nothing either.
-// The recipe costs (ngw_recipe.inc, through ngw_host_recipe.cpp) bound the crafting cost such rows still have to pay: they commit nothing either.
 #include "ngw_host.h"
 
 using namespace ngwh;
@@ -31,19 +30,11 @@ NgwSnapRows state_rows(const ngw_handle* h) {
     return r;
 }
 
-// is `s` an open snapshot of `h`?  (looked up by address, never dereferenced first: a closed one, or another handle's, is simply not found)
-bool owns(const ngw_handle* h, const ngw_snapshot* s) {
-    for (const ngw_snapshot* q : h->snaps)
-        if (q == s) return true;
-    return false;
-}
+}  // namespace
 
-// is `t` an open key table of `h`?  (by address, as owns())
-bool owns_table(const ngw_handle* h, const ngw_key_table* t) {
-    for (const ngw_key_table* q : h->tables)
-        if (q == t) return true;
-    return false;
-}
+ngwh::Source ngwh::source_of(const ngw_handle* h, const ngw_snapshot* s) { return s ? Source{s->r, s->cap, "slots"} : Source{state_rows(h), h->n, "envs"}; }
+
+namespace {
 
 // `count` rows src -> dst on the handle's stream.  Without index lists the rows are contiguous: still the same kernel (one launch), or
 // seven device-to-device copies when the snapshot was created under NGW_SNAP_MEMCPY=1 (the comparison: DESIGN.md 4.4).
@@ -69,10 +60,6 @@ int move_rows(ngw_handle* h, bool copies, const NgwSnapRows& src, int64_t src_ro
     return NGW_OK;
 }
 
-// where the rows a call reads live: a snapshot's slots, or (s == NULL) the state slab's envs.  Only behind owns(): a closed snapshot is not dereferenced
-struct Source { NgwSnapRows r; int64_t rows; const char* unit; };   // (unit: the word of the "from %lld %s" messages)
-Source source_of(const ngw_handle* h, const ngw_snapshot* s) { return s ? Source{s->r, s->cap, "slots"} : Source{state_rows(h), h->n, "envs"}; }
-
 // a key selection; with `what`, also the stride of the [step][pair] keys a path or trajectory call writes
 int key_args(uint32_t fields, const char* what = nullptr, int64_t count = 0, int64_t stride = 0) {
     if (!fields || (fields & ~NGW_KEY_ALL)) return fail(NGW_E_INVALID_ARG, "key fields 0x%x: a non-empty selection of NGW_KEY_* bits expected", (unsigned)fields);
@@ -83,7 +70,7 @@ int key_args(uint32_t fields, const char* what = nullptr, int64_t count = 0, int
 // what the three slot observations check alike (before anything touches the stream)
 int slot_obs_args(const ngw_handle* h, const ngw_snapshot* s, const void* out, const int32_t* slots_dev, int64_t count, const char* what) {
     if (!h || !s || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!is_open(h->snaps, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (count < 0 || count > 0x7FFFFFFFll) return fail(NGW_E_INVALID_ARG, "%s of %lld slots", what, (long long)count);
     if (!slots_dev && count > s->cap) return fail(NGW_E_INVALID_ARG, "%s of %lld slots from a snapshot of %lld slots", what, (long long)count, (long long)s->cap);
     return NGW_OK;
@@ -102,7 +89,7 @@ NgwSlotObs slot_obs(const ngw_handle* h, const ngw_snapshot* s, const int32_t* s
 int step_pairs_args(const ngw_handle* h, const ngw_snapshot* src, const int32_t* src_idx_dev, const ngw_snapshot* dst, const int32_t* dst_slots_dev, int64_t count,
                     const char* what, const char* call, Source* from) {
     if (!dst && dst_slots_dev) return fail(NGW_E_INVALID_ARG, "destination slots without a destination snapshot");
-    if ((dst && !owns(h, dst)) || (src && !owns(h, src))) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if ((dst && !is_open(h->snaps, dst)) || (src && !is_open(h->snaps, src))) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     *from = source_of(h, src);
     if (count < 0 || count > 0x7FFFFFFFll || (dst && count > dst->cap))
         return fail(NGW_E_INVALID_ARG, "%s of %lld states into a snapshot of %lld slots", what, (long long)count, (long long)(dst ? dst->cap : 0x7FFFFFFFll));
@@ -253,7 +240,7 @@ int step_pairs(ngw_handle* h, const Pairs& p) {
     if (p.guided) {                                  // (the table and the rows: before anything touches the stream)
         const GuideArgs& g = p.ga;
         if (!g.table || !g.rows) return fail(NGW_E_INVALID_ARG, "NULL argument");
-        if (!owns_table(h, g.table)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
+        if (!is_open(h->tables, g.table)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
         if (g.outside != NGW_OUTSIDE_DEFAULT && g.outside != NGW_OUTSIDE_STOP)
             return fail(NGW_E_INVALID_ARG, "outside %d: NGW_OUTSIDE_DEFAULT or NGW_OUTSIDE_STOP expected", (int)g.outside);
         if (g.table->buckets < 2 || g.table->buckets > (1ull << 30) || (g.table->buckets & (g.table->buckets - 1)))   // (what ngw_key_table_create makes; the kernel's bucket is an int32)
@@ -333,7 +320,7 @@ int ngw_snapshot_create(ngw_handle* h, int64_t capacity, ngw_snapshot** out) {
 
 int ngw_snapshot_destroy(ngw_handle* h, ngw_snapshot* s) {
     if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!is_open(h->snaps, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));                         // (queued saves / restores may still use the buffer)
     for (size_t i = 0; i < h->snaps.size(); i++)
@@ -345,7 +332,7 @@ int ngw_snapshot_destroy(ngw_handle* h, ngw_snapshot* s) {
 
 int ngw_snapshot_save(ngw_handle* h, ngw_snapshot* s, const int32_t* envs_dev, const int32_t* slots_dev, int64_t count) {
     if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!is_open(h->snaps, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (count < 0 || count > s->cap) return fail(NGW_E_INVALID_ARG, "save of %lld states into a snapshot of %lld slots", (long long)count, (long long)s->cap);
     if (!envs_dev && count > h->n) return fail(NGW_E_INVALID_ARG, "save of %lld states from %lld envs", (long long)count, (long long)h->n);
     if (int rc = enter(h)) return rc;
@@ -354,7 +341,7 @@ int ngw_snapshot_save(ngw_handle* h, ngw_snapshot* s, const int32_t* envs_dev, c
 
 int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_dev, const int32_t* envs_dev, int64_t count, int flags) {
     if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!is_open(h->snaps, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (count < 0 || count > h->n) return fail(NGW_E_INVALID_ARG, "restore of %lld states into %lld envs", (long long)count, (long long)h->n);
     if (!slots_dev && count > s->cap) return fail(NGW_E_INVALID_ARG, "restore of %lld states from a snapshot of %lld slots", (long long)count, (long long)s->cap);
     if (flags & ~NGW_SNAP_KEEP_EPISODE) return fail(NGW_E_INVALID_ARG, "unknown restore flags 0x%x", (unsigned)flags);
@@ -374,7 +361,7 @@ int ngw_snapshot_restore(ngw_handle* h, ngw_snapshot* s, const int32_t* slots_de
 
 int ngw_snapshot_copy(ngw_handle* h, ngw_snapshot* src, const int32_t* src_idx_dev, ngw_snapshot* dst, const int32_t* dst_idx_dev, int64_t count) {
     if (!h || !src || !dst) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns(h, src) || !owns(h, dst)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!is_open(h->snaps, src) || !is_open(h->snaps, dst)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (count < 0 || count > dst->cap) return fail(NGW_E_INVALID_ARG, "copy of %lld states into a snapshot of %lld slots", (long long)count, (long long)dst->cap);
     if (!src_idx_dev && count > src->cap) return fail(NGW_E_INVALID_ARG, "copy of %lld states from a snapshot of %lld slots", (long long)count, (long long)src->cap);
     if (src == dst && !src_idx_dev && !dst_idx_dev && count) return fail(NGW_E_INVALID_ARG, "copy of slots 0 .. %lld of a snapshot onto themselves", (long long)count - 1);
@@ -563,7 +550,7 @@ int ngw_snapshot_action_mask(ngw_handle* h, ngw_snapshot* s, const int32_t* slot
 int ngw_sample_actions(ngw_handle* h, ngw_snapshot* src, const int32_t* idx_dev, int64_t count, const float* weights_dev, int64_t weight_stride,
                        uint64_t seed, uint64_t first_pair, uint32_t t, int32_t* actions_dev, float* mass_dev, uint64_t* masks_dev) {
     if (!h || !weights_dev || !actions_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (src && !owns(h, src)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (src && !is_open(h->snaps, src)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     const Source from = source_of(h, src);
     if (count < 0 || count > 0x7FFFFFFFll || weight_stride < count)
         return fail(NGW_E_INVALID_ARG, "sampled actions of %lld states with a weight stride of %lld", (long long)count, (long long)weight_stride);
@@ -581,7 +568,7 @@ int ngw_sample_actions(ngw_handle* h, ngw_snapshot* src, const int32_t* idx_dev,
 
 int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev) {
     if (!h || !keys_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (s && !is_open(h->snaps, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (int rc = key_args(fields)) return rc;
     const Source from = source_of(h, s);
     if (count < 0 || count > 0x7FFFFFFFll * NGW_EPB) return fail(NGW_E_INVALID_ARG, "state keys of %lld rows", (long long)count);
@@ -598,7 +585,7 @@ int ngw_state_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64
 int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, uint32_t fields, uint64_t* keys_dev, int32_t* reward_dev,
                        uint8_t* done_dev, uint32_t* info_dev) {
     if (!h || !keys_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (s && !is_open(h->snaps, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (int rc = key_args(fields)) return rc;
     const Source from = source_of(h, s);
     const int64_t A = h->spec.n_actions;
@@ -624,7 +611,7 @@ int ngw_successor_keys(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, i
 int ngw_snapshot_walk(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, const int32_t* items_dev, int32_t n_steps, int32_t* dist_dev,
                       int32_t* plans_dev, int32_t* length_dev) {
     if (!h) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (s && !is_open(h->snaps, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (!items_dev && (plans_dev || length_dev)) return fail(NGW_E_INVALID_ARG, "walk plans without items: one item id per row expected");
     if (!dist_dev && !plans_dev && !length_dev) return fail(NGW_E_INVALID_ARG, "walk without an output: nothing to do");
     if (items_dev && n_steps < 1) return fail(NGW_E_INVALID_ARG, "walk plans of %d steps", (int)n_steps);
@@ -649,24 +636,10 @@ int ngw_snapshot_walk(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, in
     return NGW_OK;
 }
 
-int ngw_snapshot_recipe_costs(ngw_handle* h, ngw_snapshot* s, const int32_t* idx_dev, int64_t count, const ngw_recipe_program* program, int32_t* out_dev) {
-    if (!h || !program || !out_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (s && !owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
-    if (!recipe_hooks.pack || !recipe_hooks.run) return fail(NGW_E_INVALID_ARG, "the recipe heuristic is not part of this build (ngw_host_recipe.cpp)");
-    const Source from = source_of(h, s);
-    if (count < 0 || count > 0x7FFFFFFFll * NGW_EPB) return fail(NGW_E_INVALID_ARG, "recipe costs of %lld rows", (long long)count);
-    if (!idx_dev && count > from.rows) return fail(NGW_E_INVALID_ARG, "recipe costs of %lld rows from %lld %s", (long long)count, (long long)from.rows, from.unit);
-    if (int rc = enter(h)) return rc;                 // (s == NULL: the one-env loop has ended, HBM holds the env's state)
-    NgwRecipeProg prog;
-    if (int rc = recipe_hooks.pack(h, program, &prog)) return rc;
-    if (count == 0) return NGW_OK;
-    return recipe_hooks.run(h, h->stream, from.r, from.rows, idx_dev, count, prog, out_dev);
-}
-
 int ngw_snapshot_get(ngw_handle* h, ngw_snapshot* s, int64_t first, int64_t count, int8_t* map, int32_t* loc, int32_t* facing, int32_t* inv,
                      int32_t* selected, int32_t* step_count, uint32_t* episode) {
     if (!h || !s) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns(h, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (!is_open(h->snaps, s)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (first < 0 || count < 0 || first + count > s->cap) return fail(NGW_E_INVALID_ARG, "slot range [%lld, +%lld) out of bounds", (long long)first, (long long)count);
     if (int rc = enter(h)) return rc;
     const size_t n = (size_t)count, f = (size_t)first, S2 = (size_t)h->proto.S2, K = (size_t)h->proto.K;

@@ -9,13 +9,6 @@ using namespace ngwh;
 
 namespace {
 
-// is `t` an open key table of `h`?  (looked up by address, never dereferenced first: a closed one, or another handle's, is simply not found)
-bool owns_table(const ngw_handle* h, const ngw_key_table* t) {
-    for (const ngw_key_table* q : h->tables)
-        if (q == t) return true;
-    return false;
-}
-
 // the two arrays of a valued table, behind the counter
 uint64_t* best_of(const ngw_key_table* t) { return t->slab + 2 * t->buckets + 1; }
 int32_t* tag_of(const ngw_key_table* t) { return reinterpret_cast<int32_t*>(t->slab + 3 * t->buckets + 1); }
@@ -48,7 +41,7 @@ NgwTable table_args(const ngw_handle* h, const ngw_key_table* t, const uint64_t*
 // what insert and lookup check alike (before anything touches the stream)
 int table_call_args(const ngw_handle* h, const ngw_key_table* t, const void* keys_dev, const void* out_a, const void* out_b, int64_t count) {
     if (!h || !t || !keys_dev || !out_a || !out_b) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_table(h, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
+    if (!is_open(h->tables, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
     if (count < 0 || count > 0x7FFFFFFFll * NGW_TABLE_BLOCK) return fail(NGW_E_INVALID_ARG, "key table call with %lld keys", (long long)count);
     return NGW_OK;
 }
@@ -81,7 +74,7 @@ int create_table(ngw_handle* h, int64_t capacity, bool valued, uint64_t first_se
 // what read and trace check alike: an open valued table of the handle, a bucket list and its outputs
 int valued_call_args(const ngw_handle* h, const ngw_key_table* t, const void* where_dev, const void* out_a, const void* out_b, int64_t count, int64_t most) {
     if (!h || !t || !where_dev || !out_a || !out_b) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_table(h, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
+    if (!is_open(h->tables, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
     if (!t->valued) return fail(NGW_E_INVALID_ARG, "a key table without values (ngw_key_table_create_valued makes one with)");
     if (count < 0 || count > most) return fail(NGW_E_INVALID_ARG, "key table call with %lld buckets", (long long)count);
     return NGW_OK;
@@ -99,7 +92,7 @@ int ngw_key_table_create_valued(ngw_handle* h, int64_t capacity, uint64_t first_
 
 int ngw_key_table_destroy(ngw_handle* h, ngw_key_table* t) {
     if (!h || !t) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_table(h, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
+    if (!is_open(h->tables, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
     if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));                         // (queued inserts / lookups may still use the table)
     for (size_t i = 0; i < h->tables.size(); i++)
@@ -111,7 +104,7 @@ int ngw_key_table_destroy(ngw_handle* h, ngw_key_table* t) {
 
 int ngw_key_table_clear(ngw_handle* h, ngw_key_table* t) {
     if (!h || !t) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_table(h, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
+    if (!is_open(h->tables, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
     if (int rc = enter(h)) return rc;
     return wipe(h, t);
 }
@@ -188,7 +181,7 @@ int ngw_key_table_lookup(ngw_handle* h, ngw_key_table* t, const uint64_t* keys_d
 
 int ngw_key_table_count(ngw_handle* h, ngw_key_table* t, int64_t* n) {
     if (!h || !t || !n) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_table(h, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
+    if (!is_open(h->tables, t)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
     if (int rc = enter(h)) return rc;
     unsigned long long stored = 0;
     HIP_TRY(hipMemcpyAsync(&stored, t->slab + 2 * t->buckets, sizeof(stored), hipMemcpyDefault, h->stream));

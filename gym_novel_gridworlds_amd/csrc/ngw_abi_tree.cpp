@@ -1,6 +1,4 @@
-// ngw_abi_tree.cpp - tree-search runs (see ngw_host.h): whole MCTS iterations over one key table, enqueued from one call.  This unit names no
-// launcher of ngw_tree.inc: the six kernels are reached through ngwh::tree_hooks, which ngw_host_tree.cpp - the only host unit that names them -
-// fills when the library is loaded, so the ngw_abi_ units link with or without it (without: every ngw_tree_* call is refused).  The
+// ngw_abi_tree.cpp - tree-search runs (see ngw_host.h): whole MCTS iterations over one key table, enqueued from one call.  The
 // driver owns no stage of the playout or the table: the guided playout, the insert, the state keys and the mask words run through their own entry
 // points (ngw_abi_snapshot.cpp, ngw_abi_table.cpp), called as any caller calls them, with the kernels of ngw_tree.inc between them.  The
 // calls write no env state: they neither call state_written() nor touch anything the handle derives from its state.  All run on the handle's
@@ -9,49 +7,25 @@
 
 using namespace ngwh;
 
-namespace ngwh {
-TreeHooks tree_hooks;                               // filled by ngw_host_tree.cpp when the library is loaded (ngw_host.h)
-}
-
 namespace {
 
 // The stats ring holds one row more than ngw_tree_report reports: the leaf kernel of iteration i zero-fills the row of iteration i + 1, which in a
 // ring of NGW_TREE_ROWS rows would be the oldest of the rows still to be reported (as in ngw_abi_search.cpp).
 constexpr uint64_t TREE_RING = NGW_TREE_ROWS + 1;
 
-bool owns_tree(const ngw_handle* h, const ngw_tree* t) {
-    for (const ngw_tree* q : h->trees)
-        if (q == t) return true;
-    return false;
-}
-
-bool table_open(const ngw_handle* h, const ngw_key_table* table) {
-    for (const ngw_key_table* q : h->tables)
-        if (q == table) return true;
-    return false;
-}
-
-bool snap_open(const ngw_handle* h, const ngw_snapshot* s) {
-    for (const ngw_snapshot* q : h->snaps)
-        if (q == s) return true;
-    return false;
-}
-
 int tree_call_args(const ngw_handle* h, const ngw_tree* t) {
     if (!h || !t) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_tree(h, t)) return fail(NGW_E_INVALID_ARG, "not an open tree search of this handle");
-    if (!table_open(h, t->table)) return fail(NGW_E_INVALID_ARG, "the tree search's key table is closed");
+    if (!is_open(h->trees, t)) return fail(NGW_E_INVALID_ARG, "not an open tree search of this handle");
+    if (!is_open(h->tables, t->table)) return fail(NGW_E_INVALID_ARG, "the tree search's key table is closed");
     return NGW_OK;
 }
 
 // the table and the source of the roots are still open on `h` (by address: a closed one is simply not found)
 int run_parts(const ngw_handle* h, const ngw_tree* t) {
     if (int rc = tree_call_args(h, t)) return rc;
-    if (t->src && !snap_open(h, t->src)) return fail(NGW_E_INVALID_ARG, "the snapshot of the tree search's roots is closed");
+    if (t->src && !is_open(h->snaps, t->src)) return fail(NGW_E_INVALID_ARG, "the snapshot of the tree search's roots is closed");
     return NGW_OK;
 }
-
-bool hooked() { return tree_hooks.leaf && tree_hooks.grow && tree_hooks.backup && tree_hooks.reweight && tree_hooks.backup_discount && tree_hooks.reweight16; }
 
 // what the kernels share: the statistics and the sizes
 NgwTree tree_args(const ngw_handle* h, const ngw_tree* t) {
@@ -80,17 +54,17 @@ int playout(ngw_handle* h, ngw_tree* t, int64_t count, uint64_t seed, uint64_t f
 
 // steps 2 and 3 of include/ngw.h over x's recorded arrays
 int grow(ngw_handle* h, ngw_tree* t, const NgwTree& x) {
-    HIP_TRY(tree_hooks.leaf(&x, h->stream));
+    HIP_TRY(ngw_tree_leaf_launch(&x, h->stream));
     if (int rc = ngw_key_table_insert(h, t->table, t->leaf_keys, x.count, t->where_leaf, t->fresh)) return rc;
-    HIP_TRY(tree_hooks.grow(&x, h->stream));
+    HIP_TRY(ngw_tree_grow_launch(&x, h->stream));
     return NGW_OK;
 }
 
 // rule 4: the undiscounted kernel, or under a discount its twin
 int backup(ngw_handle* h, const ngw_tree* t, const NgwTree& x) {
     const NgwTreeRule rule{t->spread, t->discount_q16};
-    if (t->discount_q16 != 65536) HIP_TRY(tree_hooks.backup_discount(&x, &rule, h->stream));
-    else HIP_TRY(tree_hooks.backup(&x, h->stream));
+    if (t->discount_q16 != 65536) HIP_TRY(ngw_tree_backup_discount_launch(&x, &rule, h->stream));
+    else HIP_TRY(ngw_tree_backup_launch(&x, h->stream));
     return NGW_OK;
 }
 
@@ -98,8 +72,8 @@ int backup(ngw_handle* h, const ngw_tree* t, const NgwTree& x) {
 int reweight(ngw_handle* h, const ngw_tree* t, NgwTree x, const int32_t* list, int64_t n) {
     x.list = list; x.n_list = n;
     const NgwTreeRule rule{t->spread, t->discount_q16};
-    if (t->spread > 1 || t->rows16 == 1) HIP_TRY(tree_hooks.reweight16(&x, &rule, h->stream));
-    else HIP_TRY(tree_hooks.reweight(&x, h->stream));
+    if (t->spread > 1 || t->rows16 == 1) HIP_TRY(ngw_tree_reweight16_launch(&x, &rule, h->stream));
+    else HIP_TRY(ngw_tree_reweight_launch(&x, h->stream));
     return NGW_OK;
 }
 
@@ -136,8 +110,7 @@ extern "C" {
 int ngw_tree_create(ngw_handle* h, ngw_key_table* table, const ngw_tree_options* o, ngw_tree** out) {
     if (!h || !table || !o || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
     *out = nullptr;
-    if (!hooked()) return fail(NGW_E_INVALID_ARG, "tree-search runs are not part of this build (ngw_host_tree.cpp)");
-    if (!table_open(h, table)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
+    if (!is_open(h->tables, table)) return fail(NGW_E_INVALID_ARG, "not an open key table of this handle");
     const int64_t A = h->spec.n_actions, P = o->playouts, T = o->steps;
     if (P < 1) return fail(NGW_E_INVALID_ARG, "tree search: %lld playouts per iteration", (long long)P);
     if (T < 1) return fail(NGW_E_INVALID_ARG, "tree search: playouts of %lld steps", (long long)T);
@@ -149,32 +122,27 @@ int ngw_tree_create(ngw_handle* h, ngw_key_table* table, const ngw_tree_options*
     if (!std::isfinite(o->c) || !std::isfinite(o->q_init)) return fail(NGW_E_INVALID_ARG, "tree search: c = %g, q_init = %g: finite values expected", (double)o->c, (double)o->q_init);
     if (int rc = enter(h)) return rc;
     const size_t p = (size_t)P, tp = (size_t)(P * T), nb = (size_t)table->buckets, na = nb * (size_t)A, a = (size_t)A;
-    // 64-bit words: returns [na] | mask_words [nb] | keys, masks [tp] | leaf_keys, leaf_masks [p] | the 32-bit arrays, an even number of words | the bytes
-    const size_t words64 = na + nb + 2 * tp + 2 * p;
-    size_t words32 = (2 + (o->priors ? 1 : 0)) * na + 4 * tp + 8 * p + a * p + ((a + 1) & ~(size_t)1) + TREE_RING * NGW_TREE_COLS;
-    words32 += words32 & 1;
-    uint64_t* slab = nullptr;
-    if (int rc = dev_alloc(h, &slab, words64 + words32 / 2 + (2 * p + 7) / 8)) return rc;      // (zero-filled on the handle's stream)
     ngw_tree* t = new ngw_tree;
     t->table = table; t->cap = P; t->buckets = (int64_t)nb; t->T = (int32_t)T; t->A = (int32_t)A; t->fields = o->fields; t->c = o->c; t->q_init = o->q_init;
     t->combine = o->plain_backup == 0;
+    float* weights = nullptr;
+    auto layout = [&](Carver c) {                       // the slab, described once: the 64-bit words, the 32-bit arrays, the bytes
+        t->returns = c.take<unsigned long long>(na); t->mask_words = c.take<uint64_t>(nb);
+        t->keys = c.take<uint64_t>(tp); t->masks = c.take<uint64_t>(tp); t->leaf_keys = c.take<uint64_t>(p); t->leaf_masks = c.take<uint64_t>(p);
+        t->visits = c.take<int32_t>(na); t->rows = c.take<float>(na);
+        if (o->priors) t->priors = c.take<float>(na);
+        t->actions = c.take<int32_t>(tp); t->rewards = c.take<int32_t>(tp); t->where = c.take<int32_t>(tp); t->touched = c.take<int32_t>(tp);
+        t->depth = c.take<int32_t>(p); t->length = c.take<int32_t>(p); t->ret = c.take<int32_t>(p); t->first_action = c.take<int32_t>(p);
+        t->where_leaf = c.take<int32_t>(p); t->roots = c.take<int32_t>(p); t->start_actions = c.take<int32_t>(p); t->info = c.take<uint32_t>(p);
+        t->zero_weights = c.take<float>(a * p); weights = c.take<float>((a + 1) & ~(size_t)1);      // weights: [A], an even number of words
+        t->stats = c.take<uint32_t>(TREE_RING * NGW_TREE_COLS); c.align(8);
+        t->ended = c.take<uint8_t>(p); t->fresh = c.take<uint8_t>(p); c.align(8);
+        return c.bytes;
+    };
+    uint64_t* slab = nullptr;
+    if (int rc = dev_alloc(h, &slab, layout(Carver()) / 8)) { delete t; return rc; }      // (zero-filled on the handle's stream)
+    layout(Carver(slab));
     t->slab = slab;
-    uint64_t* q = slab;
-    t->returns = reinterpret_cast<unsigned long long*>(q); q += na;
-    t->mask_words = q; q += nb;
-    t->keys = q; t->masks = q + tp; q += 2 * tp;
-    t->leaf_keys = q; t->leaf_masks = q + p; q += 2 * p;
-    int32_t* w = reinterpret_cast<int32_t*>(q);
-    t->visits = w; w += na;
-    t->rows = reinterpret_cast<float*>(w); w += na;
-    if (o->priors) { t->priors = reinterpret_cast<float*>(w); w += na; }
-    t->actions = w; t->rewards = w + tp; t->where = w + 2 * tp; t->touched = w + 3 * tp; w += 4 * tp;
-    t->depth = w; t->length = w + p; t->ret = w + 2 * p; t->first_action = w + 3 * p; t->where_leaf = w + 4 * p; t->roots = w + 5 * p; t->start_actions = w + 6 * p;
-    t->info = reinterpret_cast<uint32_t*>(w + 7 * p); w += 8 * p;
-    t->zero_weights = reinterpret_cast<float*>(w); w += a * p;
-    float* const weights = reinterpret_cast<float*>(w); w += (a + 1) & ~(size_t)1;
-    t->stats = reinterpret_cast<uint32_t*>(w);
-    t->ended = reinterpret_cast<uint8_t*>(q + words32 / 2); t->fresh = t->ended + p;
     h->trees.push_back(t);                                            // (listed before the first call that looks it up)
     int rc = zero_statistics(h, t);
     if (rc == NGW_OK && o->weights_host) {
@@ -197,7 +165,7 @@ int ngw_tree_create(ngw_handle* h, ngw_key_table* table, const ngw_tree_options*
 
 int ngw_tree_destroy(ngw_handle* h, ngw_tree* t) {
     if (!h || !t) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_tree(h, t)) return fail(NGW_E_INVALID_ARG, "not an open tree search of this handle");
+    if (!is_open(h->trees, t)) return fail(NGW_E_INVALID_ARG, "not an open tree search of this handle");
     if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));                         // (queued iterations may still use the arrays)
     for (size_t i = 0; i < h->trees.size(); i++)
@@ -209,7 +177,7 @@ int ngw_tree_destroy(ngw_handle* h, ngw_tree* t) {
 
 int ngw_tree_arrays(ngw_handle* h, ngw_tree* t, ngw_tree_device_arrays* out) {
     if (!h || !t || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_tree(h, t)) return fail(NGW_E_INVALID_ARG, "not an open tree search of this handle");
+    if (!is_open(h->trees, t)) return fail(NGW_E_INVALID_ARG, "not an open tree search of this handle");
     if (int rc = enter(h)) return rc;
     HIP_TRY(hipStreamSynchronize(h->stream));                         // (the arrays are the caller's to read and write from here on: their zero-fill has run)
     memset(out, 0, sizeof(*out));
@@ -223,7 +191,7 @@ int ngw_tree_arrays(ngw_handle* h, ngw_tree* t, ngw_tree_device_arrays* out) {
 
 int ngw_tree_start(ngw_handle* h, ngw_tree* t, ngw_snapshot* src, const int32_t* roots_dev, int64_t count) {
     if (int rc = tree_call_args(h, t)) return rc;
-    if (src && !snap_open(h, src)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
+    if (src && !is_open(h->snaps, src)) return fail(NGW_E_INVALID_ARG, "not an open snapshot of this handle");
     if (count < 0 || count > t->cap) return fail(NGW_E_INVALID_ARG, "%lld roots in a tree search of %lld playouts", (long long)count, (long long)t->cap);
     if (count && !roots_dev) return fail(NGW_E_INVALID_ARG, "NULL argument");
     if (int rc = enter(h)) return rc;
@@ -237,7 +205,7 @@ int ngw_tree_start(ngw_handle* h, ngw_tree* t, ngw_snapshot* src, const int32_t*
     if (int rc = ngw_key_table_insert(h, t->table, t->leaf_keys, count, t->where_leaf, t->fresh)) return rc;
     NgwTree x = tree_args(h, t);
     x.count = count; x.stride = t->cap;
-    HIP_TRY(tree_hooks.grow(&x, h->stream));
+    HIP_TRY(ngw_tree_grow_launch(&x, h->stream));
     return reweight(h, t, x, t->where_leaf, count);
 }
 
@@ -312,7 +280,7 @@ int ngw_tree_set_rule(ngw_handle* h, ngw_tree* t, const ngw_tree_rule* rule) {
 
 int ngw_tree_report(ngw_handle* h, ngw_tree* t, ngw_tree_report_rows* out) {
     if (!h || !t || !out) return fail(NGW_E_INVALID_ARG, "NULL argument");
-    if (!owns_tree(h, t)) return fail(NGW_E_INVALID_ARG, "not an open tree search of this handle");
+    if (!is_open(h->trees, t)) return fail(NGW_E_INVALID_ARG, "not an open tree search of this handle");
     if (int rc = enter(h)) return rc;
     uint32_t ring[TREE_RING][NGW_TREE_COLS];
     uint32_t flags = 0;

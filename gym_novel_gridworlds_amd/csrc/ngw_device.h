@@ -1044,7 +1044,7 @@ extern "C"
 #endif
 hipError_t ngw_search_roots_launch(const struct NgwSearchRoots* x, hipStream_t stream);
 
-/* The recipe heuristic (ngw_recipe.inc, ngw_host_recipe.cpp; the contract is include/ngw.h's ngw_snapshot_recipe_costs): out[j] = the relaxed-plan cost
+/* The recipe heuristic (ngw_recipe.inc, ngw_abi_recipe.cpp; the contract is include/ngw.h's ngw_snapshot_recipe_costs): out[j] = the relaxed-plan cost
  * of row idx[j] of `src` (a snapshot or the state slab; a NULL list = j itself) under `prog`, the program as the host unit packs it - items resolved
  * to rule numbers, the flagged map items to count slots:
  *   rule r: d = max(0, need[r] - have), have = inv[out_item] + (map_slot >= 0: the cells equal to map_item[map_slot]); n = ceil(d / out_qty);

@@ -15,10 +15,9 @@
 //                        the k best candidates per group in the same list form (ngw_select.inc)
 //   ngw_abi_search.cpp   search runs: the driver that enqueues whole best-first iterations - the five stages above through their own entry points, the three
 //                        kernels of ngw_search.inc between them
-//   ngw_host_recipe.cpp  the recipe heuristic (ngw_recipe.inc): program checks and the launch, behind ngwh::recipe_hooks (below) - not an ngw_abi_ unit
+//   ngw_abi_recipe.cpp   the recipe heuristic (ngw_recipe.inc): program checks, the launch, ngw_snapshot_recipe_costs
 //   ngw_abi_tree.cpp     tree-search runs: the ngw_tree_* entry points and the driver that enqueues whole MCTS iterations - the guided playout and the
-//                        table's insert through their own entry points, the four kernels of ngw_tree.inc between them, reached through ngwh::tree_hooks
-//   ngw_host_tree.cpp    the launches of those four kernels, behind ngwh::tree_hooks (below) - not an ngw_abi_ unit either
+//                        table's insert through their own entry points, the six kernels of ngw_tree.inc between them
 //
 // Three rules hold in all of them:
 //   1. Guard first.  An entry point that uses the handle's stream or its device state starts with `if (int rc = enter(h)) return rc;`
@@ -48,25 +47,6 @@
 namespace ngwh {
 int fail(int code, const char* fmt, ...);           // sets the thread-local message ngw_last_error() returns; returns `code`
 const char* last_error();
-// The recipe heuristic's host code is a unit of its own, ngw_host_recipe.cpp - the only host unit that names ngw_recipe_launch -, and the entry points
-// (ngw_snapshot_recipe_costs in ngw_abi_snapshot.cpp, ngw_search_set_recipe in ngw_abi_search.cpp) reach it through these two pointers, which that
-// unit fills when the library is loaded.  The ngw_abi_*.cpp units therefore link without it - as the host-side sanitizer harness links them, one
-// stub per launcher it knew -, and the entry points then refuse the call.
-//   pack  checks a program against the rules of include/ngw.h and the handle's K, and packs it for the kernel (ngw_device.h NgwRecipeProg)
-//   run   out_dev[j] = the cost of row idx_dev[j] of `src`: one launch on `stream` - the handle's, handed in by the caller that stands behind enter(); count > 0
-typedef int (*RecipePack)(const ngw_handle* h, const ngw_recipe_program* in, NgwRecipeProg* out);
-typedef int (*RecipeRun)(ngw_handle* h, hipStream_t stream, const NgwSnapRows& src, int64_t rows, const int32_t* idx_dev, int64_t count, const NgwRecipeProg& prog, int32_t* out_dev);
-struct RecipeHooks { RecipePack pack = nullptr; RecipeRun run = nullptr; };
-extern RecipeHooks recipe_hooks;                    // ngw_abi_create.cpp, beside fail(); called behind enter() like any other use of the handle
-// The same for the tree-search kernels (ngw_tree.inc): ngw_host_tree.cpp alone names their launchers and fills these pointers when the library is
-// loaded; ngw_abi_tree.cpp launches through them, behind enter(), and refuses every ngw_tree_* call while they are empty.
-typedef hipError_t (*TreeLaunch)(const NgwTree* x, hipStream_t stream);
-typedef hipError_t (*TreeRuleLaunch)(const NgwTree* x, const NgwTreeRule* r, hipStream_t stream);
-struct TreeHooks {
-    TreeLaunch leaf = nullptr, grow = nullptr, backup = nullptr, reweight = nullptr;
-    TreeRuleLaunch backup_discount = nullptr, reweight16 = nullptr;      // the two kernels of ngw_tree_set_rule
-};
-extern TreeHooks tree_hooks;                        // ngw_abi_tree.cpp
 }
 
 #define HIP_TRY(expr)                                                                                   \
@@ -129,10 +109,9 @@ struct ngw_search {
     int64_t buckets = 0;
     int32_t *f = nullptr, *h = nullptr, *slot_of_bucket = nullptr, *weights = nullptr, *dist = nullptr;
     uint32_t* ostats = nullptr;           // [NGW_SEARCH_ROWS + 1][NGW_SEARCH_OPEN_COLS], rows as in `stats`
-    // the recipe term (ngw_search_set_recipe): the program, the term of every list entry [cap] - an allocation of its own, made by that call - and the
-    // way to ngw_host_recipe.cpp's launch; recipe_run NULL: no term, and every kernel gets what it got before there was one
+    // the recipe term (ngw_search_set_recipe): the program and the term of every list entry [cap] - an allocation of its own, made by that call;
+    // recipe NULL: no term, and every kernel gets what it got before there was one
     bool started = false;                 // ngw_search_start was called
-    ngwh::RecipeRun recipe_run = nullptr;
     int32_t* recipe = nullptr;
     NgwRecipeProg recipe_prog{};
 };
@@ -345,6 +324,24 @@ int dev_alloc(ngw_handle* h, T** p, size_t count) {
 }
 void dev_free(ngw_handle* h, void* p);
 
+// Is `p` still open on its handle?  `list` is one of the handle's four: snaps, tables, searches, trees.  Looked up by address, never dereferenced
+// first: a closed object, or another handle's, is simply not found.
+template <class T> bool is_open(const std::vector<T*>& list, const T* p) {
+    for (const T* q : list)
+        if (q == p) return true;
+    return false;
+}
+
+// One description of a slab serves twice: run on a Carver without a base it only counts the bytes the allocation needs, run on the allocation it
+// hands the arrays out - so the size and the offsets cannot disagree.  take() neither pads nor aligns: a description calls align() where it needs to.
+struct Carver {
+    char* base;
+    size_t bytes = 0;
+    explicit Carver(void* slab = nullptr) : base(static_cast<char*>(slab)) {}
+    template <class T> T* take(size_t n) { const size_t at = bytes; bytes += n * sizeof(T); return base ? reinterpret_cast<T*>(base + at) : nullptr; }
+    void align(size_t to) { bytes = (bytes + to - 1) / to * to; }
+};
+
 // Device tables of `rows` rows, n_pad elements apart (action-major, plan-major), to the caller's env-major out[n][rows] arrays: one strided copy
 // per table brings the n live columns of every row across, ONE synchronisation waits for all of them, then the rows are transposed.  A table
 // whose `out` is NULL is left alone.
@@ -419,6 +416,15 @@ int launch_view(ngw_handle* h);                     // the kept AgentMap windows
 bool view_in_step(const ngw_handle* h);             // ... or built by the in-place step kernel's VIEW form, where the launch is otherwise a plain one
 int alloc_act_mask(ngw_handle* h);                  // the mask buffer, published to NgwDevSpec::amask (no-op once allocated)
 bool solo_records_ready(ngw_handle* h);             // the one-env loop's speculated records belong to the host's state (waits for them like solo_step, never stops the loop)
+// ngw_abi_snapshot.cpp
+// where the rows a call reads live: a snapshot's slots, or (s == NULL) the state slab's envs.  Only behind is_open(): a closed snapshot is not dereferenced
+struct Source { NgwSnapRows r; int64_t rows; const char* unit; };   // (unit: the word of the "from %lld %s" messages)
+Source source_of(const ngw_handle* h, const ngw_snapshot* s);
+// ngw_abi_recipe.cpp
+// checks a program against the rules of include/ngw.h and the handle's K, and packs it for the kernel (ngw_device.h NgwRecipeProg)
+int recipe_pack(const ngw_handle* h, const ngw_recipe_program* in, NgwRecipeProg* out);
+// out_dev[j] = the cost of row idx_dev[j] of `src`: one launch on the handle's stream, for a caller that stands behind enter(); count > 0
+int recipe_run(ngw_handle* h, const NgwSnapRows& src, int64_t rows, const int32_t* idx_dev, int64_t count, const NgwRecipeProg& prog, int32_t* out_dev);
 // ngw_abi_host.cpp
 void host_step_layout(const ngw_handle* h, uint64_t off[11]);
 int check_actions(const int32_t* actions, size_t n, int A);   // NGW_E_INVALID_ACTION naming the first id outside [0, A)

@@ -1,4 +1,4 @@
-// ngw_recipe.inc - the recipe heuristic: crafting-cost lower bounds of saved slots and live envs (a unit of its own; host side: ngw_host_recipe.cpp).
+// ngw_recipe.inc - the recipe heuristic: crafting-cost lower bounds of saved slots and live envs (a unit of its own; host side: ngw_abi_recipe.cpp).
 #pragma once
 #include "ngw_common.inc"
 

@@ -1,5 +1,5 @@
 // ngw_tree.inc - tree-search runs: the glue of one MCTS iteration between a guided playout and the key table's insert, on the device (a unit of
-// its own; host side: ngw_abi_tree.cpp, launched through ngw_host_tree.cpp).
+// its own; host side: ngw_abi_tree.cpp).
 #pragma once
 #include "ngw_common.inc"
 

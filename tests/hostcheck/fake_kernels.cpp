@@ -6,10 +6,10 @@
 //   inout(p, n)  an array the kernel reads and updates: read whole, first and last element written back unchanged (its content stays)
 // The extents are restated here from the documentation, never taken from the .cpp that computes the allocation.  Values the host acts on are
 // sane: sequence words get the sequence asked for, counters and error flags 0, index lists NGW_IDX_NONE, counts 0.
-// Full extents: search, roots, select, frontier, alloc, the table launches, snapshot, expand, keys, successors, walk, the step / reset / pack /
-// diff / wire launches.  Partial (output arrays only, inputs and the LDS layout not checked): lidar, boards, agent view, masks, lookahead, plans,
+// Full extents: search, roots, recipe, the six tree launches, select, frontier, alloc, the table launches, snapshot, expand, keys, successors, walk,
+// the step / reset / pack / diff / wire launches.  Partial (output arrays only, inputs and the LDS layout not checked): lidar, boards, agent view, masks, lookahead, plans,
 // slot observers, sample, and the seven rollout / playout launchers, of which only the [count] report arrays are written - their [step][stride]
-// outputs (actions, keys, rewards, masks, obs, views, where) are NOT touched.  ngw_solo_launch touches nothing: the one-env loop is out of scope
+// outputs (actions, keys, rewards, masks, obs, views, where) are NOT touched (the tree stubs read the ones a tree-search run records).  ngw_solo_launch touches nothing: the one-env loop is out of scope
 // and the harness runs with NGW_SOLO=0.
 #include <hip/hip_runtime.h>
 
@@ -491,6 +491,60 @@ hipError_t ngw_search_roots_launch(const struct NgwSearchRoots* x, hipStream_t) 
         inout(x->f, (size_t)x->pool); inout(x->h, (size_t)x->pool); inout(x->slot_of_bucket, (size_t)x->buckets);
         if (x->dist) { in(x->dist, n * (size_t)x->K); in(x->weights, (size_t)x->K); }
     }
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------- the recipe heuristic: map and inventory of [rows] rows, idx / out [count]
+hipError_t ngw_recipe_launch(const struct NgwRecipe* x, hipStream_t) { HIT("ngw_recipe_launch"); Scope scope_("ngw_recipe_launch");
+    const size_t rows = (size_t)x->rows, n = (size_t)x->count;
+    if (x->prog.n_map) in(x->src.map, rows * (size_t)x->S2);   // "with n_map == 0 no map byte is read"
+    in(x->src.inv, rows * (size_t)x->K);
+    in(x->idx, n);                                     // (NULL: row j itself)
+    out(x->out, n, (int32_t)0);
+    flag_word(x->flags);
+    return hipSuccess;
+}
+
+// ---------------------------------------------------------------- tree-search runs (the block comment above struct NgwTree): statistics [buckets][A]
+// and [buckets]; recorded arrays step-major, n rows at `stride` with `count` live columns; touched [T][cap]; the leaves [count]; list [n_list]
+static size_t tree_rec(const struct NgwTree* x) { return x->count ? (size_t)(x->n - 1) * (size_t)x->stride + (size_t)x->count : 0; }
+static size_t tree_na(const struct NgwTree* x) { return (size_t)x->buckets * (size_t)x->A; }
+hipError_t ngw_tree_leaf_launch(const struct NgwTree* x, hipStream_t) { HIT("ngw_tree_leaf_launch"); Scope scope_("ngw_tree_leaf_launch");
+    const size_t n = (size_t)x->count;
+    in(x->depth, n); in(x->length, n); in(x->keys, tree_rec(x)); in(x->masks, tree_rec(x));
+    out(x->leaf_keys, n, (uint64_t)0); out(x->leaf_masks, n, (uint64_t)0);              // no pair has a leaf
+    inout(x->row, NGW_TREE_COLS); out(x->next_row, NGW_TREE_COLS, 0u);
+    return hipSuccess;
+}
+hipError_t ngw_tree_grow_launch(const struct NgwTree* x, hipStream_t) { HIT("ngw_tree_grow_launch"); Scope scope_("ngw_tree_grow_launch");
+    const size_t n = (size_t)x->count;
+    in(x->where_leaf, n); in(x->leaf_keys, n); in(x->leaf_masks, n); in(x->fresh, n);
+    inout(x->mask_words, (size_t)x->buckets);
+    inout(x->row, NGW_TREE_COLS);
+    return hipSuccess;
+}
+static void tree_backup_touch(const struct NgwTree* x) {
+    const size_t n = (size_t)x->count;
+    in(x->actions, tree_rec(x)); in(x->rewards, tree_rec(x)); in(x->where, tree_rec(x));
+    in(x->depth, n); in(x->length, n); in(x->bootstrap, n); in(x->where_leaf, n);       // (bootstrap, where_leaf: NULL = none)
+    inout(x->visits, tree_na(x)); inout(x->returns, tree_na(x));
+    out(x->touched, (size_t)x->T * (size_t)x->cap, (int32_t)-1);                        // also the lanes count <= j < cap: nothing touched
+    inout(x->row, NGW_TREE_COLS);
+}
+static void tree_reweight_touch(const struct NgwTree* x) {
+    in(x->list, (size_t)x->n_list);
+    in(x->visits, tree_na(x)); in(x->returns, tree_na(x)); in(x->mask_words, (size_t)x->buckets); in(x->priors, tree_na(x));
+    inout(x->rows, tree_na(x));
+    flag_word(x->flags);
+}
+hipError_t ngw_tree_backup_launch(const struct NgwTree* x, hipStream_t) { HIT("ngw_tree_backup_launch"); Scope scope_("ngw_tree_backup_launch"); tree_backup_touch(x); return hipSuccess; }
+hipError_t ngw_tree_backup_discount_launch(const struct NgwTree* x, const struct NgwTreeRule* r, hipStream_t) { HIT("ngw_tree_backup_discount_launch"); Scope scope_("ngw_tree_backup_discount_launch");
+    in(r, 1); tree_backup_touch(x);
+    return hipSuccess;
+}
+hipError_t ngw_tree_reweight_launch(const struct NgwTree* x, hipStream_t) { HIT("ngw_tree_reweight_launch"); Scope scope_("ngw_tree_reweight_launch"); tree_reweight_touch(x); return hipSuccess; }
+hipError_t ngw_tree_reweight16_launch(const struct NgwTree* x, const struct NgwTreeRule* r, hipStream_t) { HIT("ngw_tree_reweight16_launch"); Scope scope_("ngw_tree_reweight16_launch");
+    in(r, 1); tree_reweight_touch(x);
     return hipSuccess;
 }
 

@@ -1,5 +1,5 @@
 // main.cpp - the scenarios of the host-side sanitizer harness.  Usage:
-//     hostcheck <scenario> <spec file> [<spec file> ...] [short=<allocation>]      (refusals: the second spec file is a 36 x 36 map)
+//     hostcheck <scenario> <spec file> [<spec file> ...] [short=<allocation>]      (refusals: the second spec file is a 36 x 36 map, the third 48 x 48)
 // A spec file holds the bytes of one compiled ngw_spec (its length is checked against ngw_spec_size()).  The program drives the public C-ABI
 // (include/ngw.h) only, against the fake HIP runtime and the launch stubs it is linked with; every buffer it hands in is a heap block of exactly
 // the documented size, so AddressSanitizer sees the first byte a call reads or writes past it.  After each handle's ngw_destroy the fake's
@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <vector>
 
@@ -471,6 +472,176 @@ void scenario_search() {
     }
 }
 
+// ---------------------------------------------------------------- tree
+// the staged calls over the caller's own arrays of a guided playout: step-major, `stride` > count apart, n_steps rows - each exactly that long
+void tree_stages(ngw_handle* h, ngw_tree* t, int64_t P, int32_t T) {
+    const int64_t count = P, stride = P + 3;
+    const int32_t n = T > 1 ? T - 1 : 1;
+    const size_t C = (size_t)count, rec = (size_t)(n - 1) * (size_t)stride + C;
+    Arr<int32_t> depth(C, 1), length(C, n), actions(rec, 0), rewards(rec, 1), where(rec, -1), bootstrap(C, 2), buckets(C, 0);
+    Arr<uint64_t> keys(rec, 7), masks(rec, 1);
+    OK(ngw_tree_grow(h, t, depth, length, keys, masks, stride, count, n));
+    for (int use_leaves = 0; use_leaves < 2; use_leaves++)
+        for (int boot = 0; boot < 2; boot++)
+            OK(ngw_tree_backup(h, t, actions, rewards, where, depth, length, stride, count, n, use_leaves, boot ? bootstrap.get() : nullptr));
+    OK(ngw_tree_reweight(h, t, nullptr, 0));
+    OK(ngw_tree_reweight(h, t, buckets, count));
+    OK(ngw_tree_grow(h, t, nullptr, nullptr, nullptr, nullptr, 0, 0, 1));            // no pairs: only the leaves are forgotten
+}
+
+void tree_report(ngw_handle* h, ngw_tree* t) {
+    auto* rep = static_cast<ngw_tree_report_rows*>(malloc(sizeof(ngw_tree_report_rows)));
+    OK(ngw_tree_report(h, t, rep));
+    REQUIRE(rep->rows >= 0 && rep->rows <= NGW_TREE_ROWS);
+    free(rep);
+}
+
+void scenario_tree() {
+    // (spread, discount_q16, rows16): both reweight kernels and both backup kernels, rows16 = 2 at spread 1 only
+    const ngw_tree_rule rules[8] = {{1, 65536, 1, 0}, {1, 65536, 2, 0}, {1, 32768, 0, 0}, {16, 65536, 0, 0}, {16, 32768, 1, 0}, {64, 32768, 0, 0}, {64, 65536, 1, 0},
+                                    {1, 65536, 0, 0}};
+    for (size_t si = 0; si < g_specs.size(); si++) {
+        const ngw_spec* sp = spec(si);
+        const int64_t n = 65;
+        ngw_handle* h = make(sp, n);
+        Arr<float> weights((size_t)sp->n_actions, 1.0f);
+        ngw_snapshot* snap = nullptr;
+        OK(ngw_snapshot_create(h, n, &snap));
+        OK(ngw_snapshot_save(h, snap, nullptr, nullptr, n));
+        for (int64_t tc : {(int64_t)64, (int64_t)1000}) {
+            ngw_key_table* table = nullptr;
+            OK(ngw_key_table_create(h, tc, &table));
+            for (int64_t P : {(int64_t)1, (int64_t)2, (int64_t)63, (int64_t)64, (int64_t)65})
+                for (int32_t T : {1, 2, 5})
+                    for (int priors = 0; priors < 2; priors++)
+                        for (int given = 0; given < 2; given++) {
+                            ngw_tree_options o;
+                            memset(&o, 0, sizeof(o));
+                            o.playouts = P; o.steps = T; o.fields = NGW_KEY_STATE; o.c = 1.0f; o.q_init = 0.0f; o.priors = priors;
+                            o.weights_host = given ? weights.get() : nullptr;
+                            ngw_tree* t = nullptr;
+                            if (P == 1 && T == 1 && tc == 64 && !priors && !given) arm("tree_slab");
+                            OK(ngw_tree_create(h, table, &o, &t));
+                            ngw_tree_device_arrays arr;
+                            OK(ngw_tree_arrays(h, t, &arr));
+                            REQUIRE(arr.n_actions == sp->n_actions && (arr.priors != nullptr) == (priors != 0));
+                            Arr<int32_t>* roots = iota_list((size_t)P);
+                            for (ngw_snapshot* src : {snap, (ngw_snapshot*)nullptr}) {     // count == P roots: the last byte of fresh[] is touched
+                                OK(ngw_tree_start(h, t, src, *roots, P));
+                                OK(ngw_tree_run(h, t, 1, 5));
+                                tree_report(h, t);
+                            }
+                            for (const ngw_tree_rule& r : rules) {
+                                OK(ngw_tree_set_rule(h, t, &r));
+                                OK(ngw_tree_run(h, t, 1, 5));
+                                if (P == 64 || T == 5) tree_stages(h, t, P, T);           // (the staged backup and reweight under the rule too)
+                            }
+                            tree_stages(h, t, P, T);
+                            if (P == 65 && T == 2 && !priors && given) { OK(ngw_tree_run(h, t, NGW_TREE_ROWS + 2, 5)); tree_report(h, t); }   // (the stats ring, past its wrap)
+                            OK(ngw_tree_clear(h, t));
+                            OK(ngw_tree_run(h, t, 1, 6));                                  // (no roots)
+                            OK(ngw_tree_start(h, t, nullptr, *roots, P));
+                            OK(ngw_tree_run(h, t, 1, 6));
+                            tree_report(h, t);
+                            delete roots;
+                            OK(ngw_tree_destroy(h, t));
+                        }
+            if (tc == 1000) {
+                // a tree whose table is closed first: every call that needs the table refuses it; then it stays open for ngw_destroy
+                ngw_tree_options o;
+                memset(&o, 0, sizeof(o));
+                o.playouts = 3; o.steps = 2; o.fields = NGW_KEY_STATE; o.c = 1.0f;
+                ngw_tree* t = nullptr;
+                OK(ngw_tree_create(h, table, &o, &t));
+                OK(ngw_key_table_destroy(h, table));
+                Arr<int32_t> i32(8, 0); Arr<uint64_t> u64(8, 0);
+                const ngw_tree_rule rule = {1, 65536, 0, 0};
+                REQUIRE(ngw_tree_run(h, t, 1, 0) == NGW_E_INVALID_ARG);
+                REQUIRE(ngw_tree_start(h, t, nullptr, nullptr, 0) == NGW_E_INVALID_ARG);
+                REQUIRE(ngw_tree_grow(h, t, i32, i32, u64, u64, 3, 3, 1) == NGW_E_INVALID_ARG);
+                REQUIRE(ngw_tree_backup(h, t, i32, i32, i32, i32, i32, 3, 3, 1, 0, nullptr) == NGW_E_INVALID_ARG);
+                REQUIRE(ngw_tree_reweight(h, t, nullptr, 0) == NGW_E_INVALID_ARG);
+                REQUIRE(ngw_tree_set_rule(h, t, &rule) == NGW_E_INVALID_ARG);
+                REQUIRE(ngw_tree_clear(h, t) == NGW_E_INVALID_ARG);
+                tree_report(h, t);
+            } else
+                OK(ngw_key_table_destroy(h, table));
+        }
+        DESTROY(h);                                      // (the snapshot and the last tree still open)
+    }
+}
+
+// ---------------------------------------------------------------- recipe
+// Pogostick-v1's program (tests/test_recipe_heuristic_cpu.py, by item id: plank 2, pogo_stick 3, rubber 4, stick 5, tree_log 6, tree_tap 7); the tap
+// counts on the map unless `map_items` is 0
+ngw_recipe_program pogo_program(uint32_t map_items) {
+    ngw_recipe_program p;
+    memset(&p, 0, sizeof(p));
+    p.goal_item = 3; p.n_rules = 6; p.map_items = map_items;
+    auto rule = [&](int r, int out, int qty, int cost, int tool, std::initializer_list<int> in) {
+        ngw_recipe_rule& u = p.rules[r];
+        u.out_item = out; u.out_qty = qty; u.cost = cost; u.tool_item = tool;
+        for (auto it = in.begin(); it != in.end(); it += 2) { u.in_item[u.n_in] = it[0]; u.in_qty[u.n_in++] = it[1]; }
+    };
+    rule(0, 3, 1, 8400, -1, {5, 4, 2, 2, 4, 1});
+    rule(1, 4, 1, 50000, 7, {});
+    rule(2, 7, 1, 7200, -1, {2, 5, 5, 1});
+    rule(3, 5, 4, 2400, -1, {2, 2});
+    rule(4, 2, 4, 1200, -1, {6, 1});
+    rule(5, 6, 1, 3600, -1, {});
+    return p;
+}
+
+void scenario_recipe() {
+    const ngw_spec* sp = spec();
+    const int64_t n = 130;
+    ngw_handle* h = make(sp, n);
+    const ngw_recipe_program with_map = pogo_program(1u << 7), without = pogo_program(0);
+    for (int64_t cap : {(int64_t)1, (int64_t)64, (int64_t)65, (int64_t)130}) {
+        ngw_snapshot* s = nullptr;
+        OK(ngw_snapshot_create(h, cap, &s));
+        for (const ngw_recipe_program* prog : {&with_map, &without})
+            for (int64_t c : {(int64_t)0, (int64_t)1, cap}) {
+                Arr<int32_t>* idx = iota_list((size_t)c);
+                Arr<int32_t> out((size_t)c);
+                OK(ngw_snapshot_recipe_costs(h, s, *idx, c, prog, out));
+                OK(ngw_snapshot_recipe_costs(h, s, nullptr, c, prog, out));
+                OK(ngw_snapshot_recipe_costs(h, nullptr, *idx, c, prog, out));     // the live envs (cap <= n of them)
+                OK(ngw_snapshot_recipe_costs(h, nullptr, nullptr, c, prog, out));
+                delete idx;
+            }
+        OK(ngw_snapshot_destroy(h, s));
+    }
+    // open-list searches with the term: one int32 per list entry, an allocation of its own
+    int32_t costs[64];
+    for (int i = 0; i < 64; i++) costs[i] = 1;
+    Arr<int32_t> weights((size_t)sp->n_items, 1);
+    ngw_snapshot* pool = nullptr; ngw_key_table* table = nullptr;
+    OK(ngw_snapshot_create(h, 130, &pool));
+    OK(ngw_key_table_create_valued(h, 1000, 0, &table));
+    for (int64_t cap : {(int64_t)1, (int64_t)3, (int64_t)64, (int64_t)65})
+        for (int32_t mode : {NGW_SEARCH_H_MIN, NGW_SEARCH_H_MAX}) {
+            ngw_search_options o;
+            memset(&o, 0, sizeof(o));
+            o.capacity = cap; o.costs_host = costs; o.keep = mode == NGW_SEARCH_H_MIN ? 1 : (int32_t)cap; o.prune = 1;
+            o.heuristic = mode; o.n_weights = sp->n_items; o.weights_host = weights;
+            ngw_search* s = nullptr; ngw_search_arrays_open oarr;
+            OK(ngw_search_create_open(h, pool, table, &o, &oarr, &s));
+            if (cap == 3) arm("search_recipe_term");
+            OK(ngw_search_set_recipe(h, s, mode == NGW_SEARCH_H_MIN ? &with_map : &without));
+            OK(ngw_search_set_recipe(h, s, &with_map));                              // (again before the start: the same allocation serves)
+            Arr<int32_t>* roots = iota_list((size_t)cap);
+            int32_t cur = -1;
+            OK(ngw_search_start(h, s, *roots, cap, &cur));                           // count == cap roots: the last entry of the term is written
+            delete roots;
+            OK(ngw_search_run(h, s, 2, &cur));
+            search_reads(h, s, true);
+            REQUIRE(ngw_search_set_recipe(h, s, &with_map) == NGW_E_INVALID_ARG);    // after ngw_search_start: refused
+            if (cap != 65) OK(ngw_search_destroy(h, s));                             // (the last one, and its term, are ngw_destroy's to release)
+        }
+    DESTROY(h);
+}
+
 // ---------------------------------------------------------------- refusals
 int g_refusals = 0;
 void refused(int line, int rc, long long before) {
@@ -587,6 +758,84 @@ void scenario_refusals() {
     REFUSED(ngw_search_read_open(h, q, reinterpret_cast<ngw_search_open_report*>(keys.get())));   // (a search without an open list: refused before `out` is touched)
     REFUSED(ngw_search_run(other, q, 1, nullptr));
     REFUSED(ngw_search_destroy(other, q));
+    {   // tree-search runs: ngw_tree_create, ngw_tree_start, ngw_tree_set_rule and the staged calls' stage_args, one rule each
+        ngw_tree* tr = nullptr;
+        ngw_tree_options to;
+        memset(&to, 0, sizeof(to));
+        to.playouts = 4; to.steps = 3; to.fields = NGW_KEY_STATE; to.c = 1.0f;
+        ngw_tree_options bad = to;
+        REFUSED(ngw_tree_create(h, nullptr, &to, &tr));
+        REFUSED(ngw_tree_create(h, plain, nullptr, &tr));
+        REFUSED(ngw_tree_create(h, plain, &to, nullptr));
+        REFUSED(ngw_tree_create(h, foreign, &to, &tr));
+        bad.playouts = 0; REFUSED(ngw_tree_create(h, plain, &bad, &tr)); bad = to;
+        bad.steps = 0; REFUSED(ngw_tree_create(h, plain, &bad, &tr)); bad = to;
+        bad.playouts = 1ll << 31; REFUSED(ngw_tree_create(h, plain, &bad, &tr)); bad = to;
+        bad.playouts = 1 << 20; bad.steps = 1 << 12; REFUSED(ngw_tree_create(h, plain, &bad, &tr)); bad = to;
+        bad.fields = 0; REFUSED(ngw_tree_create(h, plain, &bad, &tr)); bad = to;
+        bad.fields = NGW_KEY_ALL + 1; REFUSED(ngw_tree_create(h, plain, &bad, &tr)); bad = to;
+        bad.c = 1.0f / 0.0f; REFUSED(ngw_tree_create(h, plain, &bad, &tr)); bad = to;
+        bad.q_init = 0.0f / 0.0f; REFUSED(ngw_tree_create(h, plain, &bad, &tr));
+        OK(ngw_tree_create(h, plain, &to, &tr));
+        REFUSED(ngw_tree_start(h, tr, foreign_pool, i32, 2));
+        REFUSED(ngw_tree_start(h, tr, pool, i32, -1));
+        REFUSED(ngw_tree_start(h, tr, pool, i32, 5));
+        REFUSED(ngw_tree_start(h, tr, pool, nullptr, 2));
+        REFUSED(ngw_tree_start(other, tr, nullptr, i32, 2));
+        REFUSED(ngw_tree_run(h, tr, -1, 0));
+        ngw_tree_rule rule = {1, 65536, 0, 0};
+        REFUSED(ngw_tree_set_rule(h, tr, nullptr));
+        rule.spread = 0; REFUSED(ngw_tree_set_rule(h, tr, &rule));
+        rule.spread = 65; REFUSED(ngw_tree_set_rule(h, tr, &rule)); rule.spread = 1;
+        rule.discount_q16 = -1; REFUSED(ngw_tree_set_rule(h, tr, &rule));
+        rule.discount_q16 = 65537; REFUSED(ngw_tree_set_rule(h, tr, &rule)); rule.discount_q16 = 65536;
+        rule.rows16 = 3; REFUSED(ngw_tree_set_rule(h, tr, &rule));
+        rule.rows16 = 2; rule.spread = 2; REFUSED(ngw_tree_set_rule(h, tr, &rule)); rule.rows16 = 0; rule.spread = 1;
+        rule.reserved = 1; REFUSED(ngw_tree_set_rule(h, tr, &rule));
+        REFUSED(ngw_tree_grow(h, tr, i32, j32, keys, keys, 4, -1, 1));               // stage_args: count, n_steps, stride
+        REFUSED(ngw_tree_grow(h, tr, i32, j32, keys, keys, 8, 5, 1));
+        REFUSED(ngw_tree_grow(h, tr, i32, j32, keys, keys, 4, 4, 0));
+        REFUSED(ngw_tree_grow(h, tr, i32, j32, keys, keys, 4, 4, 4));
+        REFUSED(ngw_tree_grow(h, tr, i32, j32, keys, keys, 3, 4, 1));
+        REFUSED(ngw_tree_grow(h, tr, nullptr, j32, keys, keys, 4, 4, 1));
+        REFUSED(ngw_tree_backup(h, tr, i32, j32, k32, i32, j32, 3, 4, 1, 0, nullptr));
+        REFUSED(ngw_tree_backup(h, tr, i32, nullptr, k32, i32, j32, 4, 4, 1, 0, nullptr));
+        REFUSED(ngw_tree_reweight(h, tr, i32, -1));
+        REFUSED(ngw_tree_report(h, tr, nullptr));
+        REFUSED(ngw_tree_arrays(h, tr, nullptr));
+        REFUSED(ngw_tree_destroy(other, tr));
+        OK(ngw_tree_destroy(h, tr));
+    }
+    {   // recipe programs: the rules of recipe_pack, one each (the call of no rows makes every check)
+        const ngw_recipe_program good = pogo_program(1u << 7);
+        const int32_t K = sp->n_items;
+        auto refuse = [&](int line, const ngw_recipe_program& p) {
+            const long long before = fake_hip_live_total();
+            refused(line, ngw_snapshot_recipe_costs(h, nullptr, nullptr, 0, &p, i32), before);
+        };
+        OK(ngw_snapshot_recipe_costs(h, nullptr, nullptr, 0, &good, i32));
+        REFUSED(ngw_snapshot_recipe_costs(h, nullptr, nullptr, 0, nullptr, i32));
+        REFUSED(ngw_snapshot_recipe_costs(h, nullptr, nullptr, 0, &good, nullptr));
+        REFUSED(ngw_snapshot_recipe_costs(h, foreign_pool, nullptr, 0, &good, i32));
+        REFUSED(ngw_snapshot_recipe_costs(h, nullptr, nullptr, -1, &good, i32));
+        REFUSED(ngw_snapshot_recipe_costs(h, nullptr, nullptr, 66, &good, i32));      // more rows than envs, without a list
+        ngw_recipe_program p = good;
+        p.n_rules = NGW_RECIPE_MAX_RULES + 1; refuse(__LINE__, p); p = good;
+        p.goal_item = K; refuse(__LINE__, p); p = good;
+        p.map_items = 1u << K; refuse(__LINE__, p); p = good;
+        p.rules[1].out_item = -1; refuse(__LINE__, p); p = good;
+        p.rules[1].out_item = 3; refuse(__LINE__, p); p = good;                        // two rules give item 3
+        p.rules[1].out_qty = 0; refuse(__LINE__, p); p = good;
+        p.rules[1].cost = -1; refuse(__LINE__, p); p = good;
+        p.rules[1].n_in = NGW_RECIPE_MAX_INPUTS + 1; refuse(__LINE__, p); p = good;
+        p.rules[0].in_item[0] = K; refuse(__LINE__, p); p = good;
+        p.rules[0].in_qty[0] = 65536; refuse(__LINE__, p); p = good;
+        p.map_items = 1u << 2; refuse(__LINE__, p); p = good;                          // plank: consumed by rule 0 and counted on the map
+        p.rules[1].tool_item = -2; refuse(__LINE__, p); p = good;
+        p.map_items = (1u << 0) | (1u << 1) | (1u << 3) | (1u << 7) | (1u << 8); refuse(__LINE__, p); p = good;   // five flagged items, none consumed
+        p.rules[2].tool_item = 3; refuse(__LINE__, p); p = good;                       // a tool given by an EARLIER rule
+        p.rules[5].in_item[0] = 2; p.rules[5].in_qty[0] = 1; p.rules[5].n_in = 1; refuse(__LINE__, p);   // an input given by an earlier rule
+    }
     OK(ngw_snapshot_destroy(h, pool));                   // the search's pool closed: the refusal path
     REFUSED(ngw_search_run(h, q, 1, nullptr));
     REFUSED(ngw_search_start(h, q, nullptr, 0, nullptr));
@@ -602,7 +851,27 @@ void scenario_refusals() {
         o.keep = 1; o.heuristic = NGW_SEARCH_H_NONE;
         REFUSED(ngw_search_create_open(big, bpool, btable, &o, &oarr, &q));
         REFUSED(ngw_successor_keys(big, bpool, nullptr, 4, NGW_KEY_STATE, keys, nullptr, nullptr, nullptr));
+        // a tree's guided playout keeps ONE set of maps: 36 x 36 fits, and the tree is made
+        ngw_tree* btree = nullptr;
+        ngw_tree_options to;
+        memset(&to, 0, sizeof(to));
+        to.playouts = 4; to.steps = 3; to.fields = NGW_KEY_STATE; to.c = 1.0f;
+        OK(ngw_tree_create(big, btable, &to, &btree));
+        OK(ngw_tree_destroy(big, btree));
         OK(ngw_destroy(big));
+    }
+    {   // maps beyond the guided playout's limit: the third spec file (48 x 48).  ngw_tree_create's call of no pairs refuses it AFTER the slab exists:
+        // the error path has to release it
+        REQUIRE(g_specs.size() >= 3 && spec(2)->map_size >= 48);
+        ngw_handle* huge = make(spec(2), 65);
+        ngw_key_table* htable = nullptr; ngw_tree* htree = nullptr;
+        OK(ngw_key_table_create(huge, 8, &htable));
+        ngw_tree_options to;
+        memset(&to, 0, sizeof(to));
+        to.playouts = 4; to.steps = 3; to.fields = NGW_KEY_STATE; to.c = 1.0f;
+        REFUSED(ngw_tree_create(huge, htable, &to, &htree));
+        REQUIRE(htree == nullptr && strstr(ngw_last_error(), "map_size") != nullptr);
+        OK(ngw_destroy(huge));
     }
     REFUSED(ngw_snapshot_destroy(h, foreign_pool));
     (void)t;
@@ -646,6 +915,8 @@ int main(int argc, char** argv) {
     else if (s == "table") scenario_table();
     else if (s == "frontier") scenario_frontier();
     else if (s == "search") scenario_search();
+    else if (s == "tree") scenario_tree();
+    else if (s == "recipe") scenario_recipe();
     else if (s == "refusals") scenario_refusals();
     else if (s == "leak_selfcheck") scenario_leak_selfcheck();
     else { fprintf(stderr, "hostcheck: unknown scenario '%s'\n", g_scenario); return 2; }

@@ -13,10 +13,12 @@ realignment of an open-list search's slab depends on it:
     K = 12 (K % 4 == 0)  no entry of CFGS has 8 or 12 items (every one compiles to 9, 10 or 11), so the fixture stacks three committed
                          novelties on Bow-v1 at 12 x 12: additem/easy/arrow, axe/easy/wooden, fence/easy/oak.  This is the residue at which the
                          weights and the distances lie back to back in the slab, with no padding between them.
-Pogostick-v1 at 36 x 36 is the second spec of `refusals`: maps that ngw_successor_keys and the searches refuse (more LDS than a CU has).
+Pogostick-v1 at 36 x 36 is the second spec of `refusals`: maps that ngw_successor_keys and the searches refuse (more LDS than a CU has).  A tree
+search is still made there - its guided playout keeps one set of maps, not two -, so the third spec, 48 x 48, is the one ngw_tree_create refuses:
+by its closing call of no pairs, after the slab exists.
 
-Measured where this was written (8 cores): building both programs 4.5 s; the slowest scenario is `search` over the five specs, 0.3 s; every
-other one is under 0.1 s.
+Measured where this was written (8 cores): building both programs 4.5 s; the slowest scenarios are `tree` and `search` over the five specs, 0.5 s
+and 0.3 s; every other one is under 0.1 s.
 """
 import os
 import shutil
@@ -44,20 +46,29 @@ MUST_TRIP = [
     ('snapshot', 'snapshot_slab'),       # ngw_snapshot_create(64): episode[64] = 256 bytes, no padding behind it
     ('frontier', 'frontier_scratch_regrown'),   # regrown for 513 * 4096 + 1 flags: the ticket + 514 tile counts, exactly
     ('frontier', 'select_scratch_regrown'),     # regrown for 4 groups of 1025: NGW_SELECT_SCRATCH_WORDS(4, 1) = 4140 words, exactly
+    ('tree', 'tree_slab'),               # ngw_tree_create: ends with ended[P], fresh[P] inside (2 P + 7) / 8 words, at most 7 bytes of tail slack
+    ('recipe', 'search_recipe_term'),    # ngw_search_set_recipe on a search of capacity 3: [cap] int32, exactly
 ]
 # the size each picked allocation is asked for (9 items, 17 actions, 10 x 10; the fake prints it): the proof that the name picks what it says
 PICKED_BYTES = {'frontier_scratch': 513 * 4, 'select_scratch': 4096 * 4, 'frontier_scratch_regrown': 515 * 4, 'select_scratch_regrown': 4140 * 4,
                 'table_slab_plain': (2 * 2 + 1) * 8, 'table_slab_valued': (2 * 2 + 1 + 2 + 1) * 8, 'snapshot_slab': 64 * 100 + 64 * 9 * 4 + 512 + 4 * 256,
                 'snapshot_slab_padded': 6656 + 2560 + 768 + 512 + 256 + 512 + 512,
                 # 2 + n 64-bit words, 332 + 6 cap + 2 pool + 4 n int32 (n = cap * 17 = 17, pool 64), 2 n flag bytes rounded up to 8
-                'search_slab_closed': (2 + 17) * 8 + (332 + 6 + 128 + 68) * 4 + 40}
+                'search_slab_closed': (2 + 17) * 8 + (332 + 6 + 128 + 68) * 4 + 40,
+                # P = 1 playout of T = 1 step, a table of capacity 64 (128 buckets), 17 actions, no priors (include/ngw.h, ngw_tree_device_arrays; ngw_host.h):
+                # 64-bit words: returns 128 * 17, mask_words 128, keys and masks T * P each, leaf_keys and leaf_masks P each;
+                # 32-bit words: visits and rows 128 * 17 each, actions / rewards / where / touched T * P each, the eight [P] arrays (depth, length, ret,
+                #   first_action, where_leaf, roots, start_actions, info), the zero weight block 17 * P, the weights 17 -> 18, the stats ring 65 * 8 - 4919, made even;
+                # ended[P] and fresh[P] in one 64-bit word
+                'tree_slab': (128 * 17 + 128 + 2 + 2) * 8 + (2 * 128 * 17 + 4 + 8 + 17 + 18 + 65 * 8 + 1) * 4 + 8,
+                'search_recipe_term': 3 * 4}
 # ... and the ones the product rounds up on purpose: short by 8 bytes they still hold everything a launch may touch (scenario, allocation, the rule)
 ROUNDED_UP = [
     ('frontier', 'select_scratch', 'ngw_frontier_select: at least 4096 words; the calls before the first regrow use at most 1044'),
     ('frontier', 'frontier_scratch', 'ngw_frontier_compact: the ticket + at least 512 tile counts; the calls before the first regrow use 3 words'),
     ('snapshot', 'snapshot_slab_padded', 'ngw_snapshot_create(65): every array padded to 256 bytes, episode[65] leaves 252 behind it'),
 ]
-SCENARIOS = ['handle', 'host_step', 'snapshot', 'table', 'frontier', 'search', 'refusals']
+SCENARIOS = ['handle', 'host_step', 'snapshot', 'table', 'frontier', 'search', 'tree', 'recipe', 'refusals']
 # what a scenario must have reached (stub name -> at least one call), read from the stubs' own counters
 MUST_REACH = {
     'host_step': ['ngw_launch:wire', 'ngw_launch:lidar', 'ngw_launch:refill', 'mirror_out', 'ngw_pack_launch', 'ngw_diff_launch', 'ngw_wire_launch',
@@ -69,6 +80,9 @@ MUST_REACH = {
               'ngw_table_renorm_launch'],
     'snapshot': ['ngw_snapshot_launch', 'ngw_expand_launch', 'ngw_keys_launch', 'ngw_successors_launch', 'ngw_walk_launch', 'ngw_slot_mask_launch'],
     'frontier': ['ngw_frontier_compact_launch', 'ngw_frontier_alloc_launch', 'ngw_frontier_select_launch'],
+    'tree': ['ngw_tree_leaf_launch', 'ngw_tree_grow_launch', 'ngw_tree_backup_launch', 'ngw_tree_backup_discount_launch', 'ngw_tree_reweight_launch',
+             'ngw_tree_reweight16_launch', 'ngw_playout_guided_launch', 'ngw_table_insert_launch', 'ngw_keys_launch', 'ngw_sample_launch'],
+    'recipe': ['ngw_recipe_launch', 'ngw_search_open_launch', 'ngw_search_roots_launch'],
 }
 
 
@@ -109,7 +123,7 @@ def hostcheck(tmp_path_factory):
     for one in (('additem', 'easy', 'arrow', ''), ('axe', 'easy', 'wooden', ''), ('fence', 'easy', 'oak', '')):
         apply_novelty(k12, *one)
     named = [('pogo9', make_spec(T.POGO, 9)), ('pogo10', make_spec(T.POGO, 10)), ('axe10', T.build_spec('axe10')),
-             ('stk_add_repl12', T.build_spec('stk_add_repl12')), ('k12', k12), ('pogo36', make_spec(T.POGO, 36))]
+             ('stk_add_repl12', T.build_spec('stk_add_repl12')), ('k12', k12), ('pogo36', make_spec(T.POGO, 36)), ('pogo48', make_spec(T.POGO, 48))]
     residues = []
     for name, spec in named:
         path = os.path.join(tmp, name + '.spec')
@@ -119,12 +133,12 @@ def hostcheck(tmp_path_factory):
         specs.append(path)
         residues.append(compiled.n_items % 4)
     assert sorted(set(residues[:5])) == [0, 1, 2, 3]
-    return {'ok': os.path.join(BUILD, 'hostcheck'), 'short': os.path.join(BUILD, 'hostcheck_short'), 'specs': specs[:5], 'big': specs[5]}
+    return {'ok': os.path.join(BUILD, 'hostcheck'), 'short': os.path.join(BUILD, 'hostcheck_short'), 'specs': specs[:5], 'big': specs[5:7]}
 
 
 def _run(exe, scenario, specs, *more):
     if scenario == 'refusals':
-        specs = list(specs)[:1] + [BIG[0]]
+        specs = list(specs)[:1] + BIG[:2]
     return subprocess.run([exe, scenario] + list(specs) + list(more), capture_output=True, text=True, timeout=TIMEOUT, env=_env())
 
 
@@ -133,8 +147,8 @@ BIG = []
 
 @pytest.mark.parametrize('scenario', SCENARIOS)
 def test_scenario_is_clean(hostcheck, scenario):
-    BIG[:] = [hostcheck['big']]
-    specs = hostcheck['specs'] if scenario == 'search' else hostcheck['specs'][1:2]
+    BIG[:] = hostcheck['big']
+    specs = hostcheck['specs'] if scenario in ('search', 'tree') else hostcheck['specs'][1:2]
     r = _run(hostcheck['ok'], scenario, specs)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-6000:]
     assert "scenario '%s' passed" % scenario in r.stdout
@@ -143,10 +157,10 @@ def test_scenario_is_clean(hostcheck, scenario):
     assert not missing, 'scenario %s never reached %s' % (scenario, missing)
 
 
-@pytest.mark.parametrize('scenario', [s for s in SCENARIOS if s != 'search'])
+@pytest.mark.parametrize('scenario', [s for s in SCENARIOS if s not in ('search', 'tree')])
 def test_other_specs_are_clean(hostcheck, scenario):
-    """every scenario on the odd map (9 x 9) and on a configuration with reset passes and 11 items (`search` runs every spec above)"""
-    BIG[:] = [hostcheck['big']]
+    """every scenario on the odd map (9 x 9) and on a configuration with reset passes and 11 items (`search` and `tree` run every spec above)"""
+    BIG[:] = hostcheck['big']
     for spec in (hostcheck['specs'][0], hostcheck['specs'][3], hostcheck['specs'][4]):
         r = _run(hostcheck['ok'], scenario, [spec])
         assert r.returncode == 0, spec + '\n' + r.stdout[-2000:] + r.stderr[-6000:]

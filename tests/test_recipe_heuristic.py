@@ -1,4 +1,4 @@
-"""The recipe heuristic on the MI355X (csrc/ngw_recipe.inc, csrc/ngw_host_recipe.cpp, include/ngw.h ngw_snapshot_recipe_costs /
+"""The recipe heuristic on the MI355X (csrc/ngw_recipe.inc, csrc/ngw_abi_recipe.cpp, include/ngw.h ngw_snapshot_recipe_costs /
 ngw_search_set_recipe; search.py RecipeHeuristic, Snapshot.recipe_costs, VecNovelGridworld.recipe_costs).  Every cost is held to
 search.recipe_cost_reference of pool.state() / get_state() - never to the kernel's own output -, the search to the model of
 tests/recipe_oracle.py on the CPU oracle, iteration by iteration."""
